@@ -12,10 +12,15 @@ One "step" = one episode (T=100 env-steps, both agents acting and learning) of e
 game.  A kernel launch covers --chunk episodes (tables stay in LDS inside a launch; 32 at most);
 by default the K steps of a timed region are ONE launch when K <= 32 (what a training loop does:
 thrl_qtable_episodes cuts a training call into launches of 32 episodes), otherwise equal launches of <= 32.  The
-timed region -- exactly K steps between barrier + synchronize on both sides, max over ranks -- is
-repeated until >= 4 launches have been timed (K = 20: four regions) and the MEDIAN region is
-reported; every region's time is in the line (`region_ms`), the per-launch HIP-event average of
-the roofline block is over all of them.
+timed region is exactly K steps between barrier + synchronize on both sides, max over ranks, so --steps
+is the number of timed steps.  --regions R repeats it R times and reports the MEDIAN region; every
+region's time is in the line (`region_ms`), the per-launch HIP-event average of the roofline block
+is over all of them.
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32 /
+float64, < 64 MB): the step's mean reward / action per agent, epsilon, and the tables, visit counters
+and env states (+ network parameters on the nn workload) of a fixed, seeded sample of games
+(`game_index`).  With the same arguments the inputs are the same from run to run, so two builds can be
+compared output for output (on several GPUs: rank 0's games).
 Multi-GPU: games are seed-sharded (game_offset = rank * games), no data-path
 collective; a gloo group provides only the barrier and the max-over-ranks clock.
 
@@ -240,12 +245,12 @@ def nn_roofline(agents, env_steps, gpu_s, lib):
     return out
 
 
-def run_nn(agents, games, steps, warmup, nn_loop="fused", cpu_seconds=10.0, lib=None, noise_prob=0.0):
+def run_nn(agents, games, steps, warmup, nn_loop="fused", cpu_seconds=10.0, lib=None, noise_prob=0.0, dump=None):
     """BASELINE configs[3]: neural-policy agents (agents.py:119-220) x 65,536 games through mixed.MixedGameBatch
     (fused: thrl_mixed_episodes + the batched update kernels; unfused: one launch per reference call).
     agents: rr = 2 x Reinforce, qr = the reference's shipped pairing QTable vs Reinforce, qa / qc = QTable vs
     ActorCritic / CAC, qq = 2 x QTable on the mixed kernel.  steps = episodes; the policy trains every 10 episodes.
-    Returns the JSON line as a dict."""
+    dump: directory for the outputs of the last timed step (dump_outputs).  Returns the JSON line as a dict."""
     cpu = cpu_baseline_nn(agents, cpu_seconds) if cpu_seconds > 0 else None
     import torch
     from th_rl_amd.mixed import MixedGameBatch
@@ -264,7 +269,7 @@ def run_nn(agents, games, steps, warmup, nn_loop="fused", cpu_seconds=10.0, lib=
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()
-    mb.run(steps, fused=fused, per_game_logs=False) if fused else mb.run(steps, fused=False)
+    res = mb.run(steps, fused=fused, per_game_logs=False) if fused else mb.run(steps, fused=False)
     ev1.record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -283,6 +288,13 @@ def run_nn(agents, games, steps, warmup, nn_loop="fused", cpu_seconds=10.0, lib=
            "roofline": nn_roofline(agents, env_steps, gpu_s, lib)}
     if cpu is not None:
         out["cpu_baseline"] = cpu
+    if dump:
+        import numpy as np
+        per_game = {"tables": (mb.q, np.float32), "counters": (mb.counter, np.float64),
+                    "states": (mb.state, np.float64)}
+        per_game.update({"params_agent%d" % i: (rb.params, np.float32) for i, rb in mb.nn.items()})
+        out["outputs"] = dump_outputs(dump, per_game, {"reward": res["reward_log"][-1], "action": res["action_log"][-1],
+                                                        "epsilon": mb.eps[:mb.N]})
     del mb
     torch.cuda.empty_cache()
     return out
@@ -292,9 +304,38 @@ def bench_nn(args):
     lib = library_info()
     G = args.games if args.games != (1 << 20) else 65536
     out = run_nn(args.nn_agents, G, args.steps, args.warmup, args.nn_loop, 0.0 if args.no_cpu_baseline else args.cpu_seconds, lib,
-                 noise_prob=float(args.noise_prob or 0.0))
+                 noise_prob=float(args.noise_prob or 0.0), dump=args.dump_outputs)
     out["library"] = lib
     emit(json.dumps(out))
+
+
+DUMP_LIMIT = 48 << 20               # bytes of .npy files --dump-outputs may write (under 64 MB in either unit)
+DUMP_GAMES = 4096                   # games sampled at most
+
+
+def dump_outputs(directory, per_game, whole):
+    """Write `whole` (name -> array) and a fixed, seeded sample of the games of `per_game` (name -> (device tensor
+    [G, ...], numpy dtype)) as <directory>/<name>.npy; the sample holds as many games as fit DUMP_LIMIT, and its
+    indices go to game_index.npy.  Returns a summary for the JSON line."""
+    import numpy as np
+    import torch
+    arrays = {k: np.asarray(v, np.float64) for k, v in whole.items()}
+    G = next(iter(per_game.values()))[0].shape[0]
+    row = sum(t[0].numel() * np.dtype(dt).itemsize for t, dt in per_game.values())
+    room = DUMP_LIMIT - sum(a.nbytes for a in arrays.values()) - (1 << 16)        # (.npy headers)
+    n = max(1, min(G, DUMP_GAMES, room // (row + 8)))
+    games = np.sort(np.random.RandomState(0).choice(G, n, replace=False))
+    arrays["game_index"] = games.astype(np.float64)
+    for name, (t, dt) in per_game.items():
+        idx = torch.from_numpy(games).to(t.device)
+        arrays[name] = t.index_select(0, idx).cpu().numpy().astype(dt)
+    total = sum(a.nbytes for a in arrays.values())
+    if total + 128 * len(arrays) > DUMP_LIMIT:
+        raise RuntimeError("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {"dir": directory, "games_sampled": int(n), "bytes": int(total), "arrays": sorted(arrays)}
 
 
 _JSON_OUT = None
@@ -371,8 +412,8 @@ def main():
                     help="episodes per kernel launch (<=32); default: the whole region when steps <= 32, else equal "
                          "launches of <= 32 episodes")
     ap.add_argument("--regions", type=int, default=0,
-                    help="how many times the timed K-step region is run (median reported); default: enough for >= 4 "
-                         "timed launches")
+                    help="how many times the timed K-step region is run (median reported); default 1, so exactly "
+                         "--steps steps are timed")
     ap.add_argument("--nn-loop", default="fused", choices=["fused", "unfused"])
     ap.add_argument("--nn-agents", default="rr", choices=["rr", "qr", "qq", "qa", "qc"])
     ap.add_argument("--kernel", default="wave", choices=["wave", "generic", "auto"])
@@ -390,6 +431,9 @@ def main():
     ap.add_argument("--no-counters", action="store_true",
                     help="diagnostic only: run without QTable.counter (NOT the reported workload)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "< 64 MB; tables, counters and states of a fixed, seeded sample of games)")
     ap.add_argument("--noise-prob", type=float, default=None,
                     help="diagnostic: NoisyPriceState noise_prob (config value 0; class default 0.05)")
     ap.add_argument("--max-steps", type=int, default=None,
@@ -449,8 +493,7 @@ def main():
     else:
         n_launch = (args.steps + 31) // 32
         chunk = max(1, (args.steps + n_launch - 1) // n_launch)
-    launches_per_region = (args.steps + chunk - 1) // chunk
-    regions = args.regions if args.regions > 0 else max(1, (4 + launches_per_region - 1) // launches_per_region)
+    regions = max(1, args.regions)
     if args.noise_prob is not None:
         CFG["environment"]["noise_prob"] = float(args.noise_prob)
     T_run = T_STEPS
@@ -465,6 +508,8 @@ def main():
     if args.epsilon is not None:
         gb.eps = [float(args.epsilon)] * len(gb.eps)
 
+    last = {}                                   # what the last launch returned (--dump-outputs)
+
     def run_steps(n, events=None):
         done = 0
         while done < n:
@@ -472,7 +517,7 @@ def main():
             if events is not None:
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
-            gb.run(e, sync=False)
+            last["out"] = gb.run(e, sync=False)
             if events is not None:
                 b.record()
                 events.append((a, b, e))
@@ -594,6 +639,15 @@ def main():
                                "value": [G * T_run * args.steps / s for s in per_rank]}
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if args.dump_outputs:
+            import numpy as np
+            per_game = {"tables": (gb.q, np.float32 if args.dtype == "float32" else np.float64), "states": (gb.state, np.float64)}
+            if gb.counter is not None:
+                per_game["counters"] = (gb.counter, np.float64)
+            res = last["out"]
+            out["outputs"] = dump_outputs(args.dump_outputs, per_game,
+                                          {"reward": res["reward_log"][-1].cpu().numpy(), "action": res["action_log"][-1].cpu().numpy(),
+                                           "epsilon": gb.eps[:gb.N]})
         if world == 1 and default_cfg and not args.no_secondary and args.kernel == "wave" and G == (1 << 20):
             # BASELINE configs[3] in front of the driver: the neural pairings at 65,536 games, after the headline's
             # tensors are released (a few seconds each; their own roofline and cpu_baseline)

@@ -509,3 +509,32 @@ def test_bench_stdout_carries_only_the_json_line():
     assert r.returncode == 0, r.stderr
     assert r.stdout.splitlines() == ['{"metric": "x", "value": 1}'], r.stdout
     assert "Gloo" in r.stderr and "chatter" in r.stderr
+
+
+def test_bench_dump_outputs_is_bounded_typed_and_repeatable(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): float32 / float64 .npy files within DUMP_LIMIT (< 64 MB) in all, a fixed seeded sample of the
+    games (the same one on every call, so two builds compare output for output), whole arrays written whole."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    G, stride = 5000, 4242                                  # the headline stride: the sample is cut by the size limit
+    gen = torch.Generator().manual_seed(1)
+    q = torch.rand((G, stride), generator=gen)
+    counter = torch.randint(0, 1000, (G, stride), generator=gen, dtype=torch.int32)
+    state = torch.rand((G,), generator=gen, dtype=torch.float64)
+    per_game = {"tables": (q, np.float32), "counters": (counter, np.float64), "states": (state, np.float64)}
+    whole = {"reward": [1.5, 2.5], "epsilon": [0.25, 0.5]}
+    a = bench.dump_outputs(str(tmp_path / "a"), per_game, whole)
+    b = bench.dump_outputs(str(tmp_path / "b"), per_game, whole)
+    assert a["games_sampled"] == b["games_sampled"] and 500 < a["games_sampled"] < G
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["counters.npy", "epsilon.npy", "game_index.npy", "reward.npy", "states.npy", "tables.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    idx = np.load(tmp_path / "a" / "game_index.npy").astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[-1] < G
+    assert np.array_equal(np.load(tmp_path / "a" / "tables.npy"), q.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "counters.npy"), counter.numpy()[idx].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.npy"), [1.5, 2.5])
