@@ -354,7 +354,9 @@ typedef struct {
 } thrl_mixed;
 /* Two-agent games whose neural agents are discrete run on the tuple-chain kernel (the state is carried as the action pair of
  * the last step, or as its price after a step with a redrawn intercept; needs policy_tab; per-game sweeps are taken): same
- * results as the general kernel.  This flag keeps the general one. */
+ * results as the general kernel.  This flag keeps the general one.  Any run->n_episodes is taken in ONE launch: that
+ * kernel counts a launch's visits in 16-bit cells and folds them into `counter` every floor(65535 / max_steps) episodes
+ * (max_steps <= 256 there), so the counters are exact however many visits one cell gets. */
 #define THRL_MIXED_NO_TUPLE_KERNEL 1
 /* bytes of thrl_mixed.policy_tab this configuration can use on this many games (0: the table does not apply --
  * no discrete neural agent, a continuous agent in the game, more than 2,048 action tuples, or a price grid small

@@ -642,6 +642,8 @@ static int run_wave(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run, con
 
 static int run_tuple(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run, TuplePlan& p, hipStream_t s) {
     if (b->inj_u && !b->inj_choice) return fail(THRL_ERR_NULL, "inj_u given without inj_choice");
+    if (b->sweep_noise_prob && !(c->noise_prob > 0.0))
+        return fail(THRL_ERR_BAD_CONFIG, "sweep_noise_prob needs cfg.noise_prob > 0 (it switches the noise draws on)");
     if (b->inj_u && c->noise_prob > 0.0 && (!b->inj_noise_u || !b->inj_noise_a))
         return fail(THRL_ERR_NULL, "injected draws with noise_prob > 0 need inj_noise_u / inj_noise_a");
     const TupleWs ws = tuple_workspace(c, p);

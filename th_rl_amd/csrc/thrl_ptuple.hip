@@ -19,6 +19,9 @@
 //     over the steps: Philox draws, prices, rewards, replay-ring appends (coalesced: a game's ring slots are contiguous),
 //     the QTable agent's old-value snapshot; train_net of the QTable agent as in the tuple kernel;
 //   * logs: reward / T and scaled / T per step lane-parallel, then summed in step order (four lanes, one quantity each).
+//   * visit counters: 16-bit cells in LDS (two per dword, one LDS atomic per step), added to the int32 QTable.counter in
+//     the epilogue.  A launch may run any number of episodes (thrl_mixed_episodes does not cut it), so the cells are also
+//     folded and cleared every floor(65535 / T) episodes: no cell ever holds more than 65,535 visits.
 #include "thrl_policy.h"
 #include "thrl_tuple_kernel.h"
 
@@ -74,6 +77,7 @@ k_ptuple_episodes(const PTupleArgs a) {
     double* const logsT = reinterpret_cast<double*>(game + a.logs_off);                            // [64][4]
     const int qi = a.qi;                                     // index of the QTable agent (HASQ), policy agents a.ri[0..NR-1]
     const double Td = (double)T;
+    const int hist_flush = 65535 / T;                        // episodes whose visits fit a 16-bit histogram cell (T <= 256)
 
     // QTable agent's replay constants (lanes 0-15 own it, as agent 0 of the tuple kernel)
     const AgentParams& pq = a.ag[HASQ ? qi : 0];
@@ -119,6 +123,27 @@ k_ptuple_episodes(const PTupleArgs a) {
             }
             for (int k = lane; k < a.hist_dwords; k += 64) hist[k] = 0u;
         }
+        // QTable.counter (agents.py:76): this launch's visits, held in 16-bit LDS cells (two per dword), added to the int32
+        // counters of the window rows and the two spill rows; clear = also zero the histogram (a flush inside the launch)
+        auto fold_hist = [&](bool clear) {
+            const int W = a.win_rows, lo = a.row_lo;
+            int32_t* cg = a.counter + (int64_t)g * a.stride + pq.table_off;
+            __builtin_amdgcn_wave_barrier();
+            for (int k = lane; k < W * Aq; k += 64) {
+                const unsigned n = (hist[k >> 1] >> ((k & 1) << 4)) & 0xFFFFu;
+                if (n) cg[lo * Aq + k] += (int32_t)n;
+            }
+            if (lane < 2 * Aq) {
+                const int which = lane >= Aq, col = lane - which * Aq, k = (W + which) * Aq + col;
+                const int grow = which ? spill_t : spill_p;
+                const unsigned n = (hist[k >> 1] >> ((k & 1) << 4)) & 0xFFFFu;
+                if (grow >= 0 && n) cg[grow * Aq + col] += (int32_t)n;
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (clear)
+                for (int k = lane; k < a.hist_dwords; k += 64) hist[k] = 0u;
+            __builtin_amdgcn_wave_barrier();
+        };
         // ---- policies: CDF tables.  Entry npid = the launch's initial state (off the grid).
         PolicyRegs<APAD> net;                    // NR == 1: the network stays in registers (rows are filled on first use)
         float* const ptab = TLDS ? cdf_lds : a.policy_tab + (size_t)g * NR * (size_t)(npid + 1) * APAD;
@@ -425,6 +450,9 @@ k_ptuple_episodes(const PTupleArgs a) {
                               : __dadd_rn(pq.eps_end, __dmul_rn(__dsub_rn(eps_q, pq.eps_end), pq.eps_step));       // agents.py:78
             }
             (void)tau_in;
+            // a 16-bit cell holds at most 65,535 visits: fold and clear the histogram every hist_flush episodes (<= 65,535 steps),
+            // so no launch length can wrap a cell (never taken at <= hist_flush episodes per launch: one fold in the epilogue)
+            if (HASQ && a.counter && e + 1 < a.n_episodes && (e + 1) % hist_flush == 0) fold_hist(true);
         }
 
         // ---- epilogue: table and counters back, env state
@@ -436,19 +464,7 @@ k_ptuple_episodes(const PTupleArgs a) {
                 if (spill_p >= 0) qg[pq.table_off + spill_p * Aq + lane] = tab[W * Aq + lane];
                 if (spill_t >= 0) qg[pq.table_off + spill_t * Aq + lane] = tab[(W + 1) * Aq + lane];
             }
-            if (a.counter) {
-                int32_t* cg = a.counter + (int64_t)g * a.stride + pq.table_off;
-                for (int k = lane; k < W * Aq; k += 64) {
-                    const unsigned n = (hist[k >> 1] >> ((k & 1) << 4)) & 0xFFFFu;
-                    if (n) cg[lo * Aq + k] += (int32_t)n;
-                }
-                if (lane < 2 * Aq) {
-                    const int which = lane >= Aq, col = lane - which * Aq, k = (W + which) * Aq + col;
-                    const int grow = which ? spill_t : spill_p;
-                    const unsigned n = (hist[k >> 1] >> ((k & 1) << 4)) & 0xFFFFu;
-                    if (grow >= 0 && n) cg[grow * Aq + col] += (int32_t)n;
-                }
-            }
+            if (a.counter) fold_hist(false);
         }
         if (lane == 0 && a.n_episodes > 0) a.state[g] = (NOISE && off) ? p_off : price_lut[tau];
         if (SWEEP && HASQ && a.sw_eps && lane == 0) a.sw_eps[(size_t)qi * (size_t)a.G + (size_t)g] = eps_q;
