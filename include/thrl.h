@@ -113,6 +113,14 @@ typedef struct {
     double*  action_log;             /* device [n_episodes][N] (trainer.py:66); or NULL  */
     double*  game_reward_log;        /* device [n_episodes][N][G] per-game rows; or NULL */
     double*  game_action_log;        /* device [n_episodes][N][G]; or NULL               */
+    /* Per-game rows (either array may be given alone) are written by every kernel thrl_qtable_episodes launches:
+     * the wave kernel (all variants: plain, greedy, noise, sweeps, multi-episode training cycles; f32 / f64), the
+     * tuple kernel (1-4 agents, individual grids, noise, sweeps; f32 / f64) and the generic kernel, so asking for
+     * them does not change which kernel AUTO picks.  Row [e][i][g] = game g's rewards_log[e, i] / actions_log[e, i]
+     * (trainer.py:65-66).  The reference adds r/T (scaled/T) step by step; the wave and tuple kernels sum the
+     * episode's rewards and divide by T once, and sum the steps' scaled/T over the episode as a wave reduction,
+     * i.e. the same values up to rounding order: rtol 1e-12, the mean logs' contract.  The
+     * generic kernel keeps the sequential per-step sums. */
     /* parity mode: the reference's recorded random draws, or NULL for Philox       */
     const double* inj_u;             /* device [n_episodes][T][N][G] random.uniform(0,1) (agents.py:81) */
     const int8_t* inj_choice;        /* device [n_episodes][T][N][G] random.choice idx   (agents.py:82) */

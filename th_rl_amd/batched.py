@@ -146,10 +146,13 @@ class GameBatch:
         return self
 
     # ------------------------------------------------------------------ the hot path
-    def run(self, n_episodes, inj=None, per_game_logs=False, sync=True, logs=True):
+    def run(self, n_episodes, inj=None, per_game_logs=False, sync=True, logs=True, keep_games=None):
         """n_episodes of trainer.train_one's loop for all games.  Returns a dict with
         reward_log / action_log [E, N] (mean over games) as numpy (or device tensors
-        when sync=False)."""
+        when sync=False).  per_game_logs=True adds game_reward_log / game_action_log [E, N, G]
+        (the wave and tuple kernels write them as well as the generic one: include/thrl.h);
+        keep_games (device int64 index tensor of local games) selects those columns on the
+        device before the copy, [E, N, len(keep_games)]."""
         torch = _torch()
         if not self.initialized:
             raise ThrlError("GameBatch: call init_tables() or set_tables() first")
@@ -187,7 +190,7 @@ class GameBatch:
             # the wave kernel runs whole training cycles from empty buffers; anything else is the generic
             # kernel's, which keeps the buffers in replay_mem between calls
             cycle = int(self.L.thrl_training_cycle(ctypes.byref(self.cfg)))
-            will_generic = (self.kernel == _lib.KERNEL_GENERIC or per_game_logs or cycle == 0
+            will_generic = (self.kernel == _lib.KERNEL_GENERIC or cycle == 0
                             or E % max(cycle, 1) != 0
                             or (bool(self.sweep) and not all(self.cfg.min_memory[i] <= T <= self.cfg.capacity[i]
                                                                  for i in range(N)))
@@ -218,6 +221,8 @@ class GameBatch:
                 if logs:
                     out["reward_log"], out["action_log"] = r_log.cpu().numpy(), a_log.cpu().numpy()
                 if per_game_logs:
+                    if keep_games is not None:
+                        g_r, g_a = g_r.index_select(2, keep_games), g_a.index_select(2, keep_games)
                     out["game_reward_log"], out["game_action_log"] = g_r.cpu().numpy(), g_a.cpu().numpy()
             else:
                 out.update(reward_log=r_log, action_log=a_log, game_reward_log=g_r, game_action_log=g_a,

@@ -585,6 +585,7 @@ static int run_wave(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run, con
         }
     }
     a.tlog = (uint32_t*)((char*)b->workspace + ws.tlog_off);
+    const size_t game_rows = (size_t)2 * (size_t)c->n_games;        // per-game log elements per episode
     a.next_game = (int32_t*)((char*)b->workspace + kLutRegion - 64);       // the LUT image is < 16 KiB - 64
     a.seed = run->seed; a.game_offset = run->game_offset;
     a.sw_gamma = b->sweep_gamma; a.sw_alpha = b->sweep_alpha; a.sw_eps_end = b->sweep_eps_end;
@@ -611,6 +612,8 @@ static int run_wave(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run, con
         const int n = run->n_episodes - done < chunk_max ? run->n_episodes - done : chunk_max;
         a.n_episodes = n;
         a.first_episode = run->first_episode + (uint64_t)done;
+        a.game_reward_log = b->game_reward_log ? b->game_reward_log + (size_t)done * game_rows : nullptr;
+        a.game_action_log = b->game_action_log ? b->game_action_log + (size_t)done * game_rows : nullptr;
         if (b->inj_u) {                                  // parity mode: this chunk's slice of the draws
             const size_t per_ep = (size_t)c->max_steps * 2 * (size_t)c->n_games;
             a.inj_u = b->inj_u + (size_t)done * per_ep;
@@ -685,6 +688,8 @@ static int run_tuple(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run, Tu
         a.first_episode = run->first_episode + (uint64_t)done;
         a.sum_reward = b->reward_log ? b->reward_log + (size_t)done * a.N : nullptr;
         a.sum_action = b->action_log ? b->action_log + (size_t)done * a.N : nullptr;
+        a.game_reward_log = b->game_reward_log ? b->game_reward_log + (size_t)done * a.N * (size_t)c->n_games : nullptr;
+        a.game_action_log = b->game_action_log ? b->game_action_log + (size_t)done * a.N * (size_t)c->n_games : nullptr;
         if (b->inj_u) {
             const size_t per_ep = (size_t)c->max_steps * a.N * (size_t)c->n_games;
             a.inj_u = b->inj_u + (size_t)done * per_ep;
@@ -721,7 +726,6 @@ int thrl_qtable_episodes(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run
     run->kernel_used = 0;
     if (run->n_episodes == 0) return THRL_OK;
     const bool injected = b->inj_u != nullptr;
-    const bool per_game_logs = b->game_reward_log || b->game_action_log;
     int k = run->kernel;
     if (k != THRL_KERNEL_AUTO && k != THRL_KERNEL_GENERIC && k != THRL_KERNEL_WAVE && k != THRL_KERNEL_WAVE_PLAIN &&
         k != THRL_KERNEL_WAVE_GREEDY && k != THRL_KERNEL_TUPLE)
@@ -730,7 +734,6 @@ int thrl_qtable_episodes(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run
     if (k == THRL_KERNEL_TUPLE || k == THRL_KERNEL_AUTO) {
         // (AUTO prefers the two-agent wave kernel where it applies: decided below; the tuple kernel takes what that one cannot)
         TuplePlan tp = plan_tuple(c, run);
-        if (tp.ok && per_game_logs) { tp.ok = false; snprintf(tp.why, sizeof(tp.why), "per-game logs requested"); }
         if (tp.ok && (b->sweep_eps_end || b->sweep_eps_step) && !b->sweep_eps) {
             // a game's epsilon must survive from launch to launch: it lives in sweep_eps
             tp.ok = false; snprintf(tp.why, sizeof(tp.why), "epsilon-schedule sweep without a per-game epsilon array (sweep_eps)");
@@ -746,7 +749,6 @@ int thrl_qtable_episodes(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run
     if (force_variant) k = THRL_KERNEL_WAVE;
     if (k != THRL_KERNEL_GENERIC) {
         WavePlan p = plan_wave(c, run, injected);
-        if (p.ok && per_game_logs) { p.ok = false; snprintf(p.why, sizeof(p.why), "per-game logs requested"); }
         if (p.ok && (p.epk > 1 || p.replay_from > 0) && (b->sweep_gamma || b->sweep_alpha || b->sweep_eps_end || b->sweep_eps_step || b->sweep_eps || b->sweep_noise_prob)) {
             p.ok = false; snprintf(p.why, sizeof(p.why), "per-game sweeps with a multi-episode training cycle or a truncated deque");
         }

@@ -40,6 +40,23 @@ struct GenericArgs {
     double* sw_eps; const double* sw_noise_prob;
 };
 
+// Per-game log pointers (Args::game_reward_log, then game_action_log) of a kernel whose only argument is an Args,
+// re-read from the kernarg segment where the store is (the LOG variants of the fused kernels): uniform scalar loads, so
+// the null tests are scalar branches, and the pointers are not held in SGPRs across the whole game loop (those kernels
+// already spill SGPRs: holding them grew the spill area by up to 36 B per lane, this costs one dword)
+template <typename Args>
+__device__ __forceinline__ void game_log_ptrs(double*& rew, double*& act) {
+    static_assert(offsetof(Args, game_action_log) == offsetof(Args, game_reward_log) + sizeof(double*), "adjacent");
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned char* ka = (const unsigned char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));                    // keeps the loads at the store
+    double* const* p = reinterpret_cast<double* const*>(ka + offsetof(Args, game_reward_log));
+    rew = p[0]; act = p[1];
+#else
+    rew = act = nullptr;
+#endif
+}
+
 // ---- fused wave-per-game kernel (thrl_wave.hip) -----------------------------
 constexpr int kWaveMaxEpisodes = 32;   // 32 episodes x 4 log values = the 64 lanes of two accumulators
 
@@ -66,6 +83,8 @@ struct WaveArgs {
     long long* partial;             // device [total_waves][kWaveMaxEpisodes][4] per-wave log sums, fixed point
     double log_scale[2];            // fixed-point scales of the (reward, action) log sums: powers of two, sized by the host
                                     // so that G games cannot overflow 2^62; integer sums are order independent
+    double* game_reward_log;        // device [n_episodes][2][G] per-game rows of this launch, or null
+    double* game_action_log;        // (each may be given alone)
     uint32_t* tlog;                 // device [total_waves][32 episodes][NSEG][64] packed transitions
     int32_t* next_game;             // device: work counter of the launch (games are handed out dynamically), zeroed by the host
     const double* inj_u;            // parity mode: device [n_episodes][T][2][G] uniforms, or null (Philox)
@@ -105,6 +124,7 @@ struct TupleArgs {
     void* q; int32_t* counter; double* state;
     const unsigned char* lut;       // device: the LUT image
     double* sum_reward; double* sum_action;      // device [n_episodes][N] sums over games (zeroed by the host) or null
+    double* game_reward_log; double* game_action_log;      // device [n_episodes][N][G] per-game rows of this launch, or null
     int32_t* next_game;             // device: work counter of the launch, zeroed by the host
     const double* inj_u; const int8_t* inj_choice;   // parity mode: [n_episodes][T][N][G], or null (Philox)
     const double* inj_noise_u; const double* inj_noise_a;      // parity mode with noise: [n_episodes][T][G]

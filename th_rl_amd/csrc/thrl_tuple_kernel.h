@@ -307,7 +307,9 @@ __device__ __forceinline__ void replay_block(int nb, uint32_t xr, uint32_t xc, c
 #undef THRL_TUP_STEP
 }
 
-template <typename QT, int N, int NSEG, bool NOISE, bool SWEEP>
+// LOG: per-game log rows (TupleArgs.game_reward_log / game_action_log); a template flag so the unlogged variants are
+// compiled exactly as without the store (as k_wave_episodes).
+template <typename QT, int N, int NSEG, bool NOISE, bool SWEEP, bool LOG>
 __global__ void __launch_bounds__(1024) k_tuple_episodes(const TupleArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -707,6 +709,12 @@ __global__ void __launch_bounds__(1024) k_tuple_episodes(const TupleArgs a) {
                                                       N > 3 ? lr[N > 3 ? 3 : 0] : 0.0, lane), (double)T);
                 const double ta = wave_sum4(la[0], N > 1 ? la[N > 1 ? 1 : 0] : 0.0, N > 2 ? la[N > 2 ? 2 : 0] : 0.0,
                                             N > 3 ? la[N > 3 ? 3 : 0] : 0.0, lane);
+                if constexpr (LOG) {   // per-game rows [e][agent][g] of this launch: lane i < N holds agent i's totals
+                    double *grl, *gal;
+                    game_log_ptrs<TupleArgs>(grl, gal);
+                    if (grl && lane < N) grl[((size_t)e * N + lane) * (size_t)a.G + g] = tr;
+                    if (gal && lane < N) gal[((size_t)e * N + lane) * (size_t)a.G + g] = ta;
+                }
                 // slot e*8 + k lives in lane (e*8 + k) & 63 of accd[(e*8 + k) >> 6]: lanes with (lane >> 3) == (e & 7)
                 const int k = lane & 7;
                 const double v = k < 4 ? tr : ta;              // (lane & 3) == (k & 3): the right agent's total
@@ -805,12 +813,12 @@ __global__ void __launch_bounds__(1024) k_tuple_episodes(const TupleArgs a) {
     }
 }
 
-template <typename QT, int N, bool NOISE, bool SWEEP>
+template <typename QT, int N, bool NOISE, bool SWEEP, bool LOG>
 static int launch_tuple_n(const TupleArgs& a, int grid, int block, size_t lds, hipStream_t s) {
     const int nseg = (a.T + 63) / 64;
 #define THRL_TUP_LAUNCH(NS)                                                                                          \
     {                                                                                                                \
-        auto kern = k_tuple_episodes<QT, N, NS, NOISE, SWEEP>;                                                       \
+        auto kern = k_tuple_episodes<QT, N, NS, NOISE, SWEEP, LOG>;                                                       \
         if (lds > 64 * 1024) {                                                                                       \
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                            \
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
@@ -826,15 +834,21 @@ static int launch_tuple_n(const TupleArgs& a, int grid, int block, size_t lds, h
 }
 #undef THRL_FLD
 
-template <typename QT, bool NOISE, bool SWEEP>
-static int launch_tuple_t(const TupleArgs& a, int grid, int block, size_t lds, hipStream_t s) {
+template <typename QT, bool NOISE, bool SWEEP, bool LOG>
+static int launch_tuple_tl(const TupleArgs& a, int grid, int block, size_t lds, hipStream_t s) {
     switch (a.N) {
-        case 1: return launch_tuple_n<QT, 1, NOISE, SWEEP>(a, grid, block, lds, s);
-        case 2: return launch_tuple_n<QT, 2, NOISE, SWEEP>(a, grid, block, lds, s);
-        case 3: return launch_tuple_n<QT, 3, NOISE, SWEEP>(a, grid, block, lds, s);
-        case 4: return launch_tuple_n<QT, 4, NOISE, SWEEP>(a, grid, block, lds, s);
+        case 1: return launch_tuple_n<QT, 1, NOISE, SWEEP, LOG>(a, grid, block, lds, s);
+        case 2: return launch_tuple_n<QT, 2, NOISE, SWEEP, LOG>(a, grid, block, lds, s);
+        case 3: return launch_tuple_n<QT, 3, NOISE, SWEEP, LOG>(a, grid, block, lds, s);
+        case 4: return launch_tuple_n<QT, 4, NOISE, SWEEP, LOG>(a, grid, block, lds, s);
     }
     return -1;
+}
+
+template <typename QT, bool NOISE, bool SWEEP>
+static int launch_tuple_t(const TupleArgs& a, int grid, int block, size_t lds, hipStream_t s) {
+    if (a.game_reward_log || a.game_action_log) return launch_tuple_tl<QT, NOISE, SWEEP, true>(a, grid, block, lds, s);
+    return launch_tuple_tl<QT, NOISE, SWEEP, false>(a, grid, block, lds, s);
 }
 
 }  // namespace tup

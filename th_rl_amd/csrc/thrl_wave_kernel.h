@@ -534,7 +534,9 @@ __device__ __forceinline__ void cyclic_segment(const BlockOps<QT>& ops0, unsigne
 // its larger row window leaves room for fewer waves, so the register budget is relaxed.
 // SWEEP: per-game hyper-parameter arrays (thrl_buffers.sweep_*); compiled only together with NOISE
 // so the headline variant carries none of that state.
-template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY = false>
+// LOG: per-game log rows (thrl_buffers.game_reward_log / game_action_log).  A template flag, so the unlogged
+// variants compile exactly as without the store: with a run-time null test the headline launch lost 1.8 %.
+template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY = false, bool LOG = false>
 __global__ void __launch_bounds__(1024)
 __attribute__((amdgpu_waves_per_eu(sizeof(QT) == 8 ? 3 : (NOISE ? 4 : (NSEG <= 2 ? 5 : 4)))))
 k_wave_episodes(const WaveArgs a) {
@@ -976,9 +978,22 @@ k_wave_episodes(const WaveArgs a) {
             __builtin_amdgcn_wave_barrier();
 
             double lr0 = 0.0, lr1 = 0.0, la0 = 0.0, la1 = 0.0;
-            auto log_into = [&](int epi, double q0, double q1, double q2, double q3) {
+            // first: this call carries the first part of episode epi (a CYCLE segment holds parts of several episodes)
+            auto log_into = [&](int epi, double q0, double q1, double q2, double q3, bool first) {
                 double v = (kAblate & 64) ? q0 + q1 + q2 + q3 : wave_sum4(q0, q1, q2, q3, lane);
                 if ((lane & 3) < 2) v = __ddiv_rn(v, inv_T_den);
+                if constexpr (LOG) {   // per-game rows [epi][agent][g] of this launch: lanes 0-3 hold this game's four totals (of this part)
+                    double *grl, *gal;
+                    game_log_ptrs<WaveArgs>(grl, gal);
+                    if (grl && lane < 2) {
+                        double* p = grl + ((size_t)epi * 2 + lane) * a.G + g;
+                        *p = first ? v : *p + v;
+                    }
+                    if (gal && (lane >> 1) == 1) {
+                        double* p = gal + ((size_t)epi * 2 + (lane & 1)) * a.G + g;
+                        *p = first ? v : *p + v;
+                    }
+                }
                 const long long vq = __double2ll_rn(__dmul_rn(v, log_scale));
                 if ((lane >> 2) == (epi & 15)) { if (epi < 16) acc += vq; else acc_hi += vq; }
             };
@@ -1017,7 +1032,7 @@ k_wave_episodes(const WaveArgs a) {
                     const double s0 = lut_sct[a0], s1 = lut_sct[A + a1];
                     for (int j = j0; j <= j1; j++) {
                         const bool m = valid && ep_l == j;
-                        log_into(e + j, m ? r0d : 0.0, m ? r1d : 0.0, m ? s0 : 0.0, m ? s1 : 0.0);
+                        log_into(e + j, m ? r0d : 0.0, m ? r1d : 0.0, m ? s0 : 0.0, m ? s1 : 0.0, j * Tenv >= seg * 64);
                     }
                 }
                 // visit counters (agents.py:76): the packed transition word goes to this wave's
@@ -1129,7 +1144,7 @@ k_wave_episodes(const WaveArgs a) {
 
             // ---- (f) per-episode log sums of this game into the wave accumulator:
             //      lane L gets the wave total of quantity L&3 = (reward0, reward1, action0, action1)
-            if (epk == 1) log_into(e, lr0, lr1, la0, la1);
+            if (epk == 1) log_into(e, lr0, lr1, la0, la1, true);
             // epsilon decays after every train_net call (agents.py:78)
             if (SWEEP) {
                 epsg0 = __dadd_rn(eend0, __dmul_rn(__dsub_rn(epsg0, eend0), estep0));
@@ -1243,9 +1258,9 @@ k_wave_episodes(const WaveArgs a) {
     a.partial[(size_t)wave_gid * 128 + 64 + lane] = acc_hi;
 }
 
-template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY = false>
+template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY, bool LOG>
 static int launch_wave_t(const WaveArgs& a, int grid, int block, size_t lds, hipStream_t s) {
-    auto kern = k_wave_episodes<QT, NSEG, NRSEG, NOISE, SWEEP, CYCLE, GREEDY>;
+    auto kern = k_wave_episodes<QT, NSEG, NRSEG, NOISE, SWEEP, CYCLE, GREEDY, LOG>;
     if (lds > 64 * 1024) {                       // beyond the default dynamic-LDS limit (float64 tables: one block per CU)
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1255,26 +1270,32 @@ static int launch_wave_t(const WaveArgs& a, int grid, int block, size_t lds, hip
     return (int)hipGetLastError();
 }
 
-template <typename QT, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY = false>
-static int launch_wave_n(const WaveArgs& a, int grid, int block, size_t lds, hipStream_t s) {
+template <typename QT, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY, bool LOG>
+static int launch_wave_nl(const WaveArgs& a, int grid, int block, size_t lds, hipStream_t s) {
     const int nseg = (a.T * a.epk + 63) / 64;
     const int nrseg = (a.win_rows + 2 + 63) / 64;
     if (nrseg == 1) {
         switch (nseg) {
-            case 1: return launch_wave_t<QT, 1, 1, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
-            case 2: return launch_wave_t<QT, 2, 1, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
-            case 3: return launch_wave_t<QT, 3, 1, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
-            case 4: return launch_wave_t<QT, 4, 1, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
+            case 1: return launch_wave_t<QT, 1, 1, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
+            case 2: return launch_wave_t<QT, 2, 1, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
+            case 3: return launch_wave_t<QT, 3, 1, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
+            case 4: return launch_wave_t<QT, 4, 1, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
         }
     } else if (nrseg == 2) {
         switch (nseg) {
-            case 1: return launch_wave_t<QT, 1, 2, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
-            case 2: return launch_wave_t<QT, 2, 2, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
-            case 3: return launch_wave_t<QT, 3, 2, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
-            case 4: return launch_wave_t<QT, 4, 2, NOISE, SWEEP, CYCLE, GREEDY>(a, grid, block, lds, s);
+            case 1: return launch_wave_t<QT, 1, 2, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
+            case 2: return launch_wave_t<QT, 2, 2, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
+            case 3: return launch_wave_t<QT, 3, 2, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
+            case 4: return launch_wave_t<QT, 4, 2, NOISE, SWEEP, CYCLE, GREEDY, LOG>(a, grid, block, lds, s);
         }
     }
     return -1;
+}
+
+template <typename QT, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY = false>
+static int launch_wave_n(const WaveArgs& a, int grid, int block, size_t lds, hipStream_t s) {
+    if (a.game_reward_log || a.game_action_log) return launch_wave_nl<QT, NOISE, SWEEP, CYCLE, GREEDY, true>(a, grid, block, lds, s);
+    return launch_wave_nl<QT, NOISE, SWEEP, CYCLE, GREEDY, false>(a, grid, block, lds, s);
 }
 
 }  // namespace thrl

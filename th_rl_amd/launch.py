@@ -8,7 +8,8 @@ the contiguous block of global game ids `sharding.shard_range(n_games, r, world)
 same as in a single-GPU run of all games.  There is NO data-path collective: the only cross-rank
 step is the weighted mean of the [epochs, N] logs over a gloo (CPU) group.  Outputs: rank 0 writes
 the reference's artefacts for global game 0 and the merged log.csv into --out; every rank writes its
-shard checkpoint `--out/shard<r>/batch.pt`.
+shard checkpoint `--out/shard<r>/batch.pt`, and with training.game_logs its shard's per-game logs
+(`game_rewards.npy`, `game_actions.npy`, `game_ids.npy` with global ids; utils.game_log finds a game there).
 """
 import argparse
 import json
@@ -52,6 +53,11 @@ def shard_training(config, rank, world):
             a = numpy.asarray(v)
             return a[..., offset:offset + n_local].tolist()
         training["sweep"] = {k: cut(v) for k, v in sweep.items()}
+    game_logs = training.get("game_logs")
+    if game_logs is not None and game_logs is not True and game_logs is not False:
+        # a list of global game ids: the ones in this shard (each rank writes its own game_*.npy)
+        lo = training["game_offset"]
+        training["game_logs"] = [int(i) for i in game_logs if lo <= int(i) < lo + n_local]
     return training, offset, n_local
 
 

@@ -312,26 +312,35 @@ class MixedGameBatch:
         idx = (torch.arange(n, device=self.device) + start) % cap
         return n, {k: v.index_select(1, idx).contiguous() for k, v in b.items()}
 
-    def run(self, n_episodes, fused=None, per_game_logs=True):
+    def run(self, n_episodes, fused=None, per_game_logs=True, keep_games=None):
         """n_episodes for all games.  fused=True: thrl_mixed_episodes, one launch per run of episodes
         between network updates; fused=False: the per-call operator loop (same results); None
         (default): fused unless the library reports the configuration as unsupported by that kernel
-        (more than two Reinforce / ActorCritic agents, tables beyond 64 KiB of LDS per game, > 64 actions)."""
+        (more than two Reinforce / ActorCritic agents, tables beyond 64 KiB of LDS per game, > 64 actions).
+        keep_games (device int64 index tensor of games): the per-game logs of those games only, selected on
+        the device before the copy (fused path)."""
         if fused is None:
             first = self.episode
             try:
-                return self._run_fused(int(n_episodes), per_game_logs)
+                return self._run_fused(int(n_episodes), per_game_logs, keep_games)
             except ThrlError as e:
                 # fall back only if the episode kernel itself refused the configuration, i.e. before any
                 # launch changed tables / buffers / episode index
                 if e.code != _lib.ERR_UNSUPPORTED or self.episode != first or self._fused_launched:
                     raise
-                return self._run_unfused(int(n_episodes))
+                return self._keep(self._run_unfused(int(n_episodes)), keep_games)
         if fused:
-            return self._run_fused(int(n_episodes), per_game_logs)
-        return self._run_unfused(int(n_episodes))
+            return self._run_fused(int(n_episodes), per_game_logs, keep_games)
+        return self._keep(self._run_unfused(int(n_episodes)), keep_games)
 
-    def _run_fused(self, E, per_game_logs=True):
+    @staticmethod
+    def _keep(out, keep_games):
+        if keep_games is not None:          # (the operator loop's rows are on the host already)
+            idx = keep_games.cpu().numpy()
+            out["game_reward_log"], out["game_action_log"] = out["game_reward_log"][:, :, idx], out["game_action_log"][:, :, idx]
+        return out
+
+    def _run_fused(self, E, per_game_logs=True, keep_games=None):
         """per_game_logs=False keeps only the mean over games (reduced on the device, launch by launch):
         what train_one needs, without E x N x G arrays crossing to the host."""
         torch = _torch()
@@ -406,6 +415,8 @@ class MixedGameBatch:
             out = dict(kernel="mixed-fused", episode_kernel=self.last_episode_kernel, reward_log=rmean.cpu().numpy(),
                        action_log=amean.cpu().numpy())
             if per_game_logs:
+                if keep_games is not None:
+                    rlog, alog = rlog.index_select(2, keep_games), alog.index_select(2, keep_games)
                 out.update(game_reward_log=rlog.cpu().numpy(), game_action_log=alog.cpu().numpy())
         return out
 

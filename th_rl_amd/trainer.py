@@ -14,6 +14,9 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                  "dtype": null,       # "float64" | "float32" (default f64 for 1 game, f32 otherwise)
                  "device": "cuda:0", "game_offset": 0, "kernel": "auto",
                  "resume": null,     # path of a batch.pt written by an earlier run: continue it
+                 "game_logs": null,  # true (every game) or a list of global game ids: per-game learning curves
+                                     # game_rewards.npy / game_actions.npy, float64 [epochs, N, kept games], and
+                                     # game_ids.npy (int64 global ids); read one game with utils.game_log
                  "sweep": null}      # per-game hyper-parameters, e.g. {"gamma": [0.35, 0.95, ...]}: arrays of
                                      # length n_games (or [agent][game]) for gamma / alpha / eps / eps_end /
                                      # eps_step / noise_prob (+ entropy for neural agents) -- a config sweep
@@ -25,11 +28,14 @@ the reference draws them) and the run is float64.  n_games > 1: every game's tab
 initial state come from Philox keyed by (seed, global game id).  Output files are the
 reference's four artefacts for game 0 (`<i>.npy`, `<i>_counter.npy`, `config.json`,
 `log.csv` -- the log is the MEAN over games), plus `batch.pt` with all games when
-n_games > 1.  There is no CPU fallback: without the HIP library or a GPU this raises.
+n_games > 1, and with "game_logs" the kept games' own curves (game_rewards.npy, game_actions.npy,
+game_ids.npy).  There is no CPU fallback: without the HIP library or a GPU this raises.
 """
 import json
 import os
 import time
+
+from numpy.lib.format import open_memmap
 
 import numpy
 import pandas
@@ -78,6 +84,40 @@ def _eps_of_game0(batch):
         for i in range(min(len(eps), len(col))):
             eps[i] = float(col[i])
     return eps
+
+
+GAME_LOG_BUDGET = 256 << 20        # bytes per per-game device log buffer and chunk (as mixed.py's mean-log path)
+
+
+def game_log_chunk(n_agents, n_games, cycle=1, budget=GAME_LOG_BUDGET):
+    """Episodes per launch when per-game logs are kept: [k, N, G] float64 stays within `budget` bytes, rounded down to
+    whole training cycles of the wave kernel (thrl_training_cycle; at least one cycle)."""
+    k = max(1, budget // (8 * int(n_agents) * int(n_games)))
+    c = max(1, int(cycle))
+    return max(c, k // c * c)
+
+
+def _npy_out(path, shape):
+    """float64 .npy of `shape` filled in place (memory-mapped; an empty array is written as it is)."""
+    if all(shape):
+        return open_memmap(path, mode="w+", dtype=numpy.float64, shape=shape)
+    numpy.save(path, numpy.zeros(shape))
+    return numpy.zeros(shape)
+
+
+def game_log_ids(spec, n_games, game_offset):
+    """training.game_logs -> (global ids int64, local indices int64) of the games kept by this run: true = all,
+    a list = those global ids (each must be one of this run's games, game_offset .. game_offset + n_games - 1)."""
+    if spec is True:
+        local = numpy.arange(n_games, dtype=numpy.int64)
+    else:
+        ids = numpy.asarray(list(spec), dtype=numpy.int64).reshape(-1)
+        local = ids - int(game_offset)
+        bad = ids[(local < 0) | (local >= n_games)]
+        if bad.size:
+            raise ValueError("training.game_logs: game ids %s are not in this run (global ids %d..%d)"
+                             % (bad.tolist()[:8], game_offset, game_offset + n_games - 1))
+    return local + int(game_offset), local
 
 
 def train_one(exp_path, configpath, loadonly=False, print_eps=False):
@@ -146,14 +186,46 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     rewards_log = numpy.zeros((epochs, len(agents)))
     actions_log = numpy.zeros((epochs, len(agents)))
 
+    game_logs = training.get("game_logs", None)
+    if game_logs is not None and game_logs is not False:
+        import torch
+        gids, local = game_log_ids(game_logs, n_games, int(training.get("game_offset", 0)))
+        numpy.save(os.path.join(exp_path, "game_ids.npy"), gids)
+        g_rew = _npy_out(os.path.join(exp_path, "game_rewards.npy"), (epochs, len(agents), len(gids)))
+        g_act = _npy_out(os.path.join(exp_path, "game_actions.npy"), (epochs, len(agents), len(gids)))
+        keep = None if game_logs is True else torch.from_numpy(local).to(batch.device)
+        cycle = 1
+        if isinstance(batch, GameBatch):
+            import ctypes
+            cycle = int(batch.L.thrl_training_cycle(ctypes.byref(batch.cfg))) or 1
+        sub = game_log_chunk(len(agents), n_games, cycle)
+    else:
+        game_logs = None
+
+    def run_logged(n, at):
+        """n episodes from epoch `at`: the mean logs, and the kept games' rows into the .npy files, in launches whose
+        per-game device buffers stay within the byte budget."""
+        d = 0
+        while d < n:
+            k = min(sub, n - d)
+            out = batch.run(k, per_game_logs=True, keep_games=keep)
+            rewards_log[at + d:at + d + k] = out["reward_log"]
+            actions_log[at + d:at + d + k] = out["action_log"]
+            g_rew[at + d:at + d + k] = out["game_reward_log"]
+            g_act[at + d:at + d + k] = out["game_action_log"]
+            d += k
+
     t = time.time()
     done = 0
     chunk = max(1, int(print_freq)) if print_freq else epochs
     while done < epochs:
         n = min(chunk - (done % chunk), epochs - done)
-        out = batch.run(n) if isinstance(batch, GameBatch) else batch.run(n, per_game_logs=False)
-        rewards_log[done:done + n] = out["reward_log"]
-        actions_log[done:done + n] = out["action_log"]
+        if game_logs is not None:
+            run_logged(n, done)
+        else:
+            out = batch.run(n) if isinstance(batch, GameBatch) else batch.run(n, per_game_logs=False)
+            rewards_log[done:done + n] = out["reward_log"]
+            actions_log[done:done + n] = out["action_log"]
         done += n
         if print_freq and not done % print_freq:
             rew = numpy.mean(rewards_log[done - print_freq:done, :], axis=0)
@@ -179,6 +251,9 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     apd = pandas.DataFrame(data=actions_log, columns=numpy.arange(len(agents)))
     log = pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"])
     log.to_csv(os.path.join(exp_path, "log.csv"), index=None)
+    if game_logs is not None and g_rew.size:
+        g_rew.flush()
+        g_act.flush()
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

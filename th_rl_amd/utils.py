@@ -43,3 +43,25 @@ def play_game_batched(batch, iters=1, state0=None):
     """The same rollout for every game of a GameBatch in one kernel (thrl_play_greedy):
     per-iteration mean reward / mean scaled action, arrays [iters, N, G]."""
     return batch.play_greedy(iters=iters, state0=state0)
+
+
+def game_log(exp_path, game_id):
+    """One game's learning curve from a run trained with training.game_logs: a DataFrame with log.csv's columns
+    (rewards / actions x agent, as train_one builds it) and one row per epoch.  The game is looked up by its GLOBAL
+    id in exp_path's game_ids.npy and in those of exp_path/shard*/ (th_rl_amd.launch writes one set per rank)."""
+    import glob
+    dirs = [exp_path] + sorted(glob.glob(os.path.join(exp_path, "shard*")))
+    for d in dirs:
+        ids_path = os.path.join(d, "game_ids.npy")
+        if not os.path.isfile(ids_path):
+            continue
+        hit = numpy.flatnonzero(numpy.load(ids_path) == int(game_id))
+        if hit.size:
+            k = int(hit[0])
+            rew = numpy.load(os.path.join(d, "game_rewards.npy"), mmap_mode="r")[:, :, k]
+            act = numpy.load(os.path.join(d, "game_actions.npy"), mmap_mode="r")[:, :, k]
+            n = rew.shape[1]
+            rpd = pandas.DataFrame(data=numpy.array(rew), columns=numpy.arange(n))
+            apd = pandas.DataFrame(data=numpy.array(act), columns=numpy.arange(n))
+            return pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"])
+    raise KeyError("game %d has no per-game log under %s (training.game_logs)" % (int(game_id), exp_path))
