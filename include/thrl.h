@@ -381,6 +381,57 @@ int thrl_op_draws(const thrl_cfg* cfg, uint64_t seed, uint64_t game_offset, uint
                   double* u_out, int8_t* choice_out, double* u2_out, double* noise_u_out, double* noise_a_out,
                   void* stream);
 
+/*
+ * Per-group statistics of per-game episode rows: the distribution over replicas that the reference's analysis
+ * plots per config (utils.py plot_learning_curve_conf / plot_learning_curve_sweep: median and 25th / 75th
+ * percentile over runs of the total reward per epoch; plot_sweep_conf / plot_mean_conf: the same for greedy play).
+ * Input: the rows thrl_qtable_episodes / thrl_mixed_episodes / thrl_play_greedy write, [E][N][G] float64, and a
+ * group per game.  Q = 2N+1 quantities per game and episode, in this order: reward_i (i < N), action_i (i < N),
+ * total = sum_i reward_i (added in agent order, float64).
+ *
+ * Outputs are ACCUMULATED (+= / max) into caller-zeroed device arrays, cell [e][group][q]:
+ *   hist   uint32 [E][n_groups][Q][B+2]  bin 0 = x < lo_q, bin B+1 = x >= hi_q or x not finite, bin b in 1..B =
+ *          1 + min(B-1, (int)floor((x - lo_q) * inv_w_q)) for lo_q <= x < hi_q (two roundings: subtract, multiply).
+ *   sums   int64  [E][n_groups][Q][2]    sum of rint(xc * s1_q) and of rint((xc*xc) * s2_q), xc = x clamped to
+ *          [-M_q, M_q], M_q = 16 * max(|lo_q|, |hi_q|).  s1_q, s2_q are powers of two chosen by the caller with
+ *          s1_q * M_q * n_max <= 2^62 and s2_q * M_q^2 * n_max <= 2^62 for n_max the largest group over ALL the
+ *          calls whose outputs will be added (every shard of a run): then no partial sum can overflow an int64.
+ *          The library checks the bound for this call's n_games.  Sums are exact for |x| <= M_q; a value beyond
+ *          enters them as +-M_q (its bin and min / max stay exact).  Non-finite values count in bin B+1 only.
+ *   minmax uint64 [E][n_groups][Q][2]    [0] = ~key(min x), [1] = key(max x), key(x) = order-preserving image of
+ *          the double's bits (sign bit clear: bits | 2^63; set: ~bits), combined by atomic max; 0 = no finite value.
+ * Everything is integer, so the result is bit-identical for any launch geometry, any cut of the episodes into
+ * calls and any split of the games into shards whose outputs are combined afterwards (hist and sums added,
+ * minmax by element-wise max).
+ *
+ * Grouping: group_of (HOST, [G]) is validated here; perm / seg_off (device) are its stable sort -- local games in
+ * group order, group k at perm[seg_off[k] .. seg_off[k+1]).  Each block works inside one group at a time and keeps
+ * a private LDS histogram (B+2 words).  The kernel never reads or writes outside its arrays whatever perm /
+ * seg_off hold (out-of-range entries are skipped), but only their stable sort of group_of gives the statistics.
+ */
+#define THRL_STATS_MAX_BINS 1024
+#define THRL_STATS_MAXQ (2 * THRL_MAXA + 1)
+typedef struct {
+    int32_t n_games;                 /* G: columns of the rows                           */
+    int32_t n_agents;                /* N                                                */
+    int32_t n_episodes;              /* E: rows                                          */
+    int32_t n_groups;
+    int32_t n_bins;                  /* B in 1..THRL_STATS_MAX_BINS                      */
+    int32_t reserved;                /* 0                                                */
+    const double*  game_reward_log;  /* device [E][N][G]                                 */
+    const double*  game_action_log;  /* device [E][N][G]                                 */
+    const int32_t* group_of;         /* HOST [G], each in [0, n_groups)                  */
+    const int32_t* perm;             /* device [G]                                       */
+    const int64_t* seg_off;          /* device [n_groups + 1]                            */
+    double lo[THRL_STATS_MAXQ], hi[THRL_STATS_MAXQ];    /* histogram range per quantity, hi > lo          */
+    double inv_w[THRL_STATS_MAXQ];   /* B / (hi - lo), computed by the caller in double  */
+    double scale[THRL_STATS_MAXQ][2];/* s1, s2 per quantity                              */
+    uint32_t* hist;                  /* device outputs, see above                        */
+    int64_t*  sums;
+    uint64_t* minmax;
+} thrl_group_stats_args;
+int thrl_group_stats(const thrl_group_stats_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,23 @@ class Mixed(ctypes.Structure):
     ]
 
 
+STATS_MAX_BINS = 1024
+STATS_MAXQ = 2 * MAXA + 1
+
+
+class GroupStatsArgs(ctypes.Structure):
+    """thrl_group_stats_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_agents", ctypes.c_int32), ("n_episodes", ctypes.c_int32),
+        ("n_groups", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("game_reward_log", ctypes.c_void_p), ("game_action_log", ctypes.c_void_p),
+        ("group_of", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("seg_off", ctypes.c_void_p),
+        ("lo", ctypes.c_double * STATS_MAXQ), ("hi", ctypes.c_double * STATS_MAXQ),
+        ("inv_w", ctypes.c_double * STATS_MAXQ), ("scale", (ctypes.c_double * 2) * STATS_MAXQ),
+        ("hist", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("minmax", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -84,7 +101,7 @@ SYMBOLS = [
     "thrl_op_env_step", "thrl_op_td_update",
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
-    "thrl_cac_init", "thrl_cac_act", "thrl_cac_train",
+    "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats",
 ]
 CAC_PARAMS = 1283
 
@@ -181,6 +198,8 @@ def load():
     L.thrl_mixed_policy_table_bytes.argtypes = [cfgp, ctypes.POINTER(Mixed)]
     L.thrl_mixed_episodes.restype = ctypes.c_int
     L.thrl_mixed_episodes.argtypes = [cfgp, ctypes.POINTER(Mixed), vp, vp, vp, ctypes.POINTER(Run), vp, vp, vp]
+    L.thrl_group_stats.restype = ctypes.c_int
+    L.thrl_group_stats.argtypes = [ctypes.POINTER(GroupStatsArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -146,13 +146,16 @@ class GameBatch:
         return self
 
     # ------------------------------------------------------------------ the hot path
-    def run(self, n_episodes, inj=None, per_game_logs=False, sync=True, logs=True, keep_games=None):
+    def run(self, n_episodes, inj=None, per_game_logs=False, sync=True, logs=True, keep_games=None, group_stats=None):
         """n_episodes of trainer.train_one's loop for all games.  Returns a dict with
         reward_log / action_log [E, N] (mean over games) as numpy (or device tensors
         when sync=False).  per_game_logs=True adds game_reward_log / game_action_log [E, N, G]
         (the wave and tuple kernels write them as well as the generic one: include/thrl.h);
         keep_games (device int64 index tensor of local games) selects those columns on the
-        device before the copy, [E, N, len(keep_games)]."""
+        device before the copy, [E, N, len(keep_games)].  group_stats (a group_stats.GroupSpec of this batch's games):
+        the kernel writes the per-game rows into device scratch, thrl_group_stats reduces them on the same stream, and
+        out["group_stats"] holds the chunk's hist / sums / minmax (group_stats.to_numpy; device tensors when
+        sync=False).  The rows cross to the host only when per_game_logs asks for them."""
         torch = _torch()
         if not self.initialized:
             raise ThrlError("GameBatch: call init_tables() or set_tables() first")
@@ -169,7 +172,9 @@ class GameBatch:
             a_log = torch.zeros((E, N), dtype=torch.float64, device=self.device) if logs else None
             b.reward_log, b.action_log = self._ptr(r_log), self._ptr(a_log)
             g_r = g_a = None
-            if per_game_logs:
+            if group_stats is not None and group_stats.G != G:
+                raise ThrlError("group_stats spec is for %d games, this batch has %d" % (group_stats.G, G))
+            if per_game_logs or group_stats is not None:
                 g_r = torch.zeros((E, N, G), dtype=torch.float64, device=self.device)
                 g_a = torch.zeros((E, N, G), dtype=torch.float64, device=self.device)
                 b.game_reward_log, b.game_action_log = self._ptr(g_r), self._ptr(g_a)
@@ -216,6 +221,8 @@ class GameBatch:
             self.episode += E
             self.last_kernel = _lib.KERNEL_NAMES.get(r.kernel_used, "none")
             out = dict(kernel=self.last_kernel)
+            if group_stats is not None:
+                st = group_stats.reduce(self.L, g_r, g_a, E, group_stats.zeros(E, self.device), self._stream())
             if sync:
                 torch.cuda.synchronize(self.device)
                 if logs:
@@ -224,15 +231,24 @@ class GameBatch:
                     if keep_games is not None:
                         g_r, g_a = g_r.index_select(2, keep_games), g_a.index_select(2, keep_games)
                     out["game_reward_log"], out["game_action_log"] = g_r.cpu().numpy(), g_a.cpu().numpy()
+                if group_stats is not None:
+                    from .group_stats import to_numpy
+                    out["group_stats"] = to_numpy(st)
             else:
+                if not per_game_logs:
+                    keep += [g_r, g_a]
+                    g_r = g_a = None
                 out.update(reward_log=r_log, action_log=a_log, game_reward_log=g_r, game_action_log=g_a,
                            _keep=keep)
+                if group_stats is not None:
+                    out["group_stats"] = st
         return out
 
     # ------------------------------------------------------------------ evaluation
-    def play_greedy(self, iters=1, state0=None):
+    def play_greedy(self, iters=1, state0=None, group_stats=None):
         """utils.play_game for every game: per-iteration mean reward / scaled action
-        per agent, arrays [iters, N, G]."""
+        per agent, arrays [iters, N, G].  group_stats (a GroupSpec): the rows are also reduced on the device and
+        a third element, the raw per-group statistics [iters, n_groups, Q, ...], is returned."""
         torch = _torch()
         with torch.cuda.device(self.device):
             mr = torch.zeros((iters, self.N, self.G), dtype=torch.float64, device=self.device)
@@ -245,7 +261,13 @@ class GameBatch:
                                          self.seed, self.game_offset, self._ptr(mr), self._ptr(ma),
                                          self._stream())
             _lib.check(rc, "thrl_play_greedy")
+            if group_stats is not None:
+                from .group_stats import to_numpy
+                st = to_numpy(group_stats.reduce(self.L, mr, ma, iters, group_stats.zeros(iters, self.device),
+                                                 self._stream()))
             torch.cuda.synchronize(self.device)
+        if group_stats is not None:
+            return mr.cpu().numpy(), ma.cpu().numpy(), st
         return mr.cpu().numpy(), ma.cpu().numpy()
 
     # ------------------------------------------------------------------ checkpoint / resume

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <vector>
 
 #include "thrl_kernels.h"
 #include "thrl_wave_lut.h"
@@ -396,6 +397,14 @@ WaveWs wave_workspace(const thrl_cfg* c, const WavePlan& p) {
 }
 
 }  // namespace
+
+namespace thrl { int launch_group_stats(const thrl_group_stats_args* g, hipStream_t s); }   // thrl_stats.hip
+
+// power of two (a double with mantissa exactly 0.5 after frexp), positive and finite
+static bool pow2(double x) {
+    int ex;
+    return x > 0.0 && isfinite(x) && frexp(x, &ex) == 0.5;
+}
 
 extern "C" {
 
@@ -1242,6 +1251,55 @@ int thrl_op_draws(const thrl_cfg* c, uint64_t seed, uint64_t game_offset, uint64
                                   c->env_a, c->env_a * 0.7, nA, u_out, choice_out, u2_out, noise_u_out, noise_a_out,
                                   (hipStream_t)stream);
     return e ? hip_fail(e, "k_op_draws launch") : THRL_OK;
+}
+
+int thrl_group_stats(const thrl_group_stats_args* g, void* stream) {
+    if (!g) return fail(THRL_ERR_NULL, "args is NULL");
+    if (g->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", g->n_games);
+    if (g->n_agents < 1 || g->n_agents > THRL_MAXA)
+        return fail(THRL_ERR_BAD_CONFIG, "n_agents=%d out of [1,%d]", g->n_agents, THRL_MAXA);
+    if (g->n_episodes < 0) return fail(THRL_ERR_BAD_CONFIG, "n_episodes=%d must be >= 0", g->n_episodes);
+    if (g->n_groups < 1) return fail(THRL_ERR_BAD_CONFIG, "n_groups=%d must be >= 1", g->n_groups);
+    if (g->n_bins < 1 || g->n_bins > THRL_STATS_MAX_BINS)
+        return fail(THRL_ERR_UNSUPPORTED, "n_bins=%d out of [1,%d]", g->n_bins, THRL_STATS_MAX_BINS);
+    if (g->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved must be 0");
+    if (!g->game_reward_log || !g->game_action_log || !g->group_of || !g->perm || !g->seg_off || !g->hist || !g->sums
+        || !g->minmax)
+        return fail(THRL_ERR_NULL, "game_reward_log / game_action_log / group_of / perm / seg_off / hist / sums / minmax "
+                                   "is NULL");
+    // group ids, and the largest group of this call (the int64 bound of include/thrl.h)
+    int64_t n_max = 0;
+    {
+        std::vector<int64_t> cnt((size_t)g->n_groups, 0);
+        for (int i = 0; i < g->n_games; i++) {
+            const int32_t k = g->group_of[i];
+            if (k < 0 || k >= g->n_groups)
+                return fail(THRL_ERR_BAD_CONFIG, "group_of[%d]=%d out of [0,%d)", i, k, g->n_groups);
+            if (++cnt[(size_t)k] > n_max) n_max = cnt[(size_t)k];
+        }
+    }
+    const int Q = 2 * g->n_agents + 1;
+    for (int q = 0; q < Q; q++) {
+        const double lo = g->lo[q], hi = g->hi[q];
+        if (!isfinite(lo) || !isfinite(hi) || !(hi > lo))
+            return fail(THRL_ERR_BAD_CONFIG, "quantity %d: range [%g, %g) needs finite lo < hi", q, lo, hi);
+        if (!(g->inv_w[q] > 0.0) || !isfinite(g->inv_w[q]))
+            return fail(THRL_ERR_BAD_CONFIG, "quantity %d: inv_w=%g must be B / (hi - lo)", q, g->inv_w[q]);
+        // the int64 bound of include/thrl.h for this call's games
+        const double M = 16.0 * fmax(fabs(lo), fabs(hi));
+        const double n = (double)n_max;
+        for (int k = 0; k < 2; k++) {
+            const double sc = g->scale[q][k];
+            const double need = (k == 0 ? M : M * M) * n * sc;
+            if (!pow2(sc) || !(need <= 4611686018427387904.0))
+                return fail(THRL_ERR_BAD_CONFIG, "quantity %d: scale[%d]=%g must be a power of two with "
+                            "scale * M%s * n <= 2^62 (M = %g, n = %lld: the largest group)", q, k, sc, k ? "^2" : "", M,
+                            (long long)n_max);
+        }
+    }
+    if (g->n_episodes == 0) return THRL_OK;
+    const int e = thrl::launch_group_stats(g, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_group_stats launch") : THRL_OK;
 }
 
 }  // extern "C"

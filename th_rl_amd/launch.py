@@ -10,6 +10,9 @@ step is the weighted mean of the [epochs, N] logs over a gloo (CPU) group.  Outp
 the reference's artefacts for global game 0 and the merged log.csv into --out; every rank writes its
 shard checkpoint `--out/shard<r>/batch.pt`, and with training.game_logs its shard's per-game logs
 (`game_rewards.npy`, `game_actions.npy`, `game_ids.npy` with global ids; utils.game_log finds a game there).
+With training.group_stats, group ids come from the global sweep (or training.groups) before the cut, every shard
+writes its raw per-group statistics with histograms, and rank 0 merges them exactly into the top-level
+groups.json / group_*.npy (merge_group_stats).
 """
 import argparse
 import json
@@ -47,6 +50,16 @@ def shard_training(config, rank, world):
         training["dtype"] = "float64" if total == 1 else "float32"
     training.update(n_games=n_local, game_offset=int(training.get("game_offset", 0)) + offset,
                     philox_init=(total > 1) or bool(training.get("philox_init", False)), checkpoint=True)
+    gs = training.get("group_stats")
+    if gs is not None and gs is not False:
+        # group ids from the GLOBAL sweep / groups, so they agree across ranks; the largest group of the whole run
+        # sizes the fixed-point scales (so the shards' sums add); histograms let rank 0 merge the quantiles
+        from th_rl_amd.group_stats import assign_groups, parse_options
+        ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                         n_groups=training.get("n_groups"))
+        opt = dict(parse_options(gs))
+        opt.update(histograms=True, n_max=int(numpy.bincount(ids, minlength=n_groups).max()))
+        training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
     sweep = training.get("sweep")
     if sweep:        # slice the per-game arrays to this shard
         def cut(v):
@@ -59,6 +72,42 @@ def shard_training(config, rank, world):
         lo = training["game_offset"]
         training["game_logs"] = [int(i) for i in game_logs if lo <= int(i) < lo + n_local]
     return training, offset, n_local
+
+
+def merge_group_stats(config, out, world):
+    """Rank 0: the top-level groups.json and group_*.npy (greedy_*.npy) of a sharded run from the shards' raw
+    outputs, combined exactly (group_stats.merge)."""
+    from th_rl_amd import trainer
+    from th_rl_amd.group_stats import GroupSpec, merge, parse_options, save_json
+    training = config.get("training", {})
+    total = int(training.get("n_games", world))
+    opt = parse_options(training["group_stats"])
+    spec = GroupSpec.from_config(config, total, opt, sweep=training.get("sweep"), groups=training.get("groups"),
+                                 n_groups=training.get("n_groups"))
+    desc = spec.describe()
+    save_json(os.path.join(out, "groups.json"), desc)
+    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
+    prefixes = ["group"] + (["greedy"] if opt["greedy_iters"] > 0 else [])
+    for prefix in prefixes:
+        parts = []
+        for d in shards:
+            ld = lambda f: numpy.load(os.path.join(d, "%s_%s.npy" % (prefix, f)), mmap_mode="r")
+            # ~key(min) / key(max) of the shard's exact extremes: the same keys the kernel stored
+            parts.append({"hist": ld("hist"), "sums": ld("sums"), "minmax": _keys(ld("min"), ld("max"))})
+        raw = merge(parts)
+        files = trainer.group_stats_files(out, prefix, raw["sums"].shape[0], spec, opt["histograms"])
+        trainer.write_group_stats(files, 0, raw, desc)
+        for a in files.values():
+            if hasattr(a, "flush"):
+                a.flush()
+
+
+def _keys(vmin, vmax):
+    from th_rl_amd.group_stats import order_key
+    vmin, vmax = numpy.asarray(vmin), numpy.asarray(vmax)
+    kmin = numpy.where(numpy.isnan(vmin), numpy.uint64(0), ~order_key(numpy.nan_to_num(vmin)))
+    kmax = numpy.where(numpy.isnan(vmax), numpy.uint64(0), order_key(numpy.nan_to_num(vmax)))
+    return numpy.stack([kmin, kmax], axis=-1)
 
 
 def effective_world(config, gpus):
@@ -99,6 +148,8 @@ def _worker(rank, world, port, config, out, devices_available):
         rpd = pandas.DataFrame(data=merged[:, :n], columns=numpy.arange(n))
         apd = pandas.DataFrame(data=merged[:, n:], columns=numpy.arange(n))
         pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"]).to_csv(os.path.join(out, "log.csv"), index=None)
+        if training.get("group_stats"):
+            merge_group_stats(config, out, world)
     dist.destroy_process_group()
 
 

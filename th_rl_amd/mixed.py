@@ -191,12 +191,13 @@ class MixedGameBatch:
         return self.counter[game, o:o + r * a].cpu().numpy().astype(np.float64).reshape(r, a)
 
     # ------------------------------------------------------------------ greedy evaluation
-    def play_greedy(self, iters=1, state0=None):
+    def play_greedy(self, iters=1, state0=None, group_stats=None):
         """utils.play_game (utils.py:27-47) for every game: each agent's get_action (QTable: argmax
         on the float64-encoded state; Reinforce / ActorCritic: argmax of pi; CAC: the mean action),
         env.step, for `iters` episodes.  Returns per-iteration mean reward and mean scaled action,
         arrays [iters, N, G].  state0 [iters, G] = the states environment.reset() would draw
-        (default: uniform(0, a) from numpy RandomState(seed)).  Learning state is not touched."""
+        (default: uniform(0, a) from numpy RandomState(seed)).  Learning state is not touched.  group_stats (a
+        GroupSpec): the rows are also reduced on the device and the raw statistics are returned third."""
         torch = _torch()
         if not self.initialized:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
@@ -243,7 +244,13 @@ class MixedGameBatch:
                     mr[it] += torch.div(reward, T_t)
                     ma[it] += torch.div(scaled, T_t)
                     price = nprice.clone()
+            if group_stats is not None:
+                from .group_stats import to_numpy
+                st = to_numpy(group_stats.reduce(L, mr, ma, iters, group_stats.zeros(iters, self.device),
+                                                 self._stream()))
             torch.cuda.synchronize(self.device)
+        if group_stats is not None:
+            return mr.cpu().numpy(), ma.cpu().numpy(), st
         return mr.cpu().numpy(), ma.cpu().numpy()
 
     # ------------------------------------------------------------------ checkpoint / resume
@@ -312,26 +319,28 @@ class MixedGameBatch:
         idx = (torch.arange(n, device=self.device) + start) % cap
         return n, {k: v.index_select(1, idx).contiguous() for k, v in b.items()}
 
-    def run(self, n_episodes, fused=None, per_game_logs=True, keep_games=None):
+    def run(self, n_episodes, fused=None, per_game_logs=True, keep_games=None, group_stats=None):
         """n_episodes for all games.  fused=True: thrl_mixed_episodes, one launch per run of episodes
         between network updates; fused=False: the per-call operator loop (same results); None
         (default): fused unless the library reports the configuration as unsupported by that kernel
         (more than two Reinforce / ActorCritic agents, tables beyond 64 KiB of LDS per game, > 64 actions).
         keep_games (device int64 index tensor of games): the per-game logs of those games only, selected on
-        the device before the copy (fused path)."""
+        the device before the copy (fused path).  group_stats (a group_stats.GroupSpec of this batch's games): the
+        per-game rows are reduced on the device by thrl_group_stats after every launch (the operator loop reduces its
+        rows with the same kernel), out["group_stats"] = the raw hist / sums / minmax (group_stats.to_numpy)."""
         if fused is None:
             first = self.episode
             try:
-                return self._run_fused(int(n_episodes), per_game_logs, keep_games)
+                return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats)
             except ThrlError as e:
                 # fall back only if the episode kernel itself refused the configuration, i.e. before any
                 # launch changed tables / buffers / episode index
                 if e.code != _lib.ERR_UNSUPPORTED or self.episode != first or self._fused_launched:
                     raise
-                return self._keep(self._run_unfused(int(n_episodes)), keep_games)
+                return self._keep(self._run_unfused(int(n_episodes), group_stats), keep_games)
         if fused:
-            return self._run_fused(int(n_episodes), per_game_logs, keep_games)
-        return self._keep(self._run_unfused(int(n_episodes)), keep_games)
+            return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats)
+        return self._keep(self._run_unfused(int(n_episodes), group_stats), keep_games)
 
     @staticmethod
     def _keep(out, keep_games):
@@ -340,13 +349,15 @@ class MixedGameBatch:
             out["game_reward_log"], out["game_action_log"] = out["game_reward_log"][:, :, idx], out["game_action_log"][:, :, idx]
         return out
 
-    def _run_fused(self, E, per_game_logs=True, keep_games=None):
+    def _run_fused(self, E, per_game_logs=True, keep_games=None, group_stats=None):
         """per_game_logs=False keeps only the mean over games (reduced on the device, launch by launch):
         what train_one needs, without E x N x G arrays crossing to the host."""
         torch = _torch()
         if not self.initialized:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
         N, G, T = self.N, self.G, self.T
+        if group_stats is not None and group_stats.G != G:
+            raise ThrlError("group_stats spec is for %d games, this batch has %d" % (group_stats.G, G))
         kmax = E if per_game_logs else max(1, (1 << 25) // (N * G))      # <= 256 MiB per log buffer
         with torch.cuda.device(self.device):
             rows = E if per_game_logs else min(E, kmax)
@@ -354,6 +365,7 @@ class MixedGameBatch:
             alog = torch.zeros((rows, N, G), dtype=torch.float64, device=self.device)
             rmean = torch.zeros((E, N), dtype=torch.float64, device=self.device)
             amean = torch.zeros((E, N), dtype=torch.float64, device=self.device)
+            st = group_stats.zeros(E, self.device) if group_stats is not None else None
             if not hasattr(self, "_scratch"):
                 self._scratch = [torch.zeros_like(b["price"]) if self.kinds[i] == "QTable" else None
                                  for i, b in enumerate(self.buf)]
@@ -401,6 +413,8 @@ class MixedGameBatch:
                 self.last_episode_kernel = "tuple" if r.kernel_used == _lib.KERNEL_TUPLE else "wave"
                 rmean[done:done + k] = rlog[base:base + k].mean(dim=2)
                 amean[done:done + k] = alog[base:base + k].mean(dim=2)
+                if st is not None:
+                    group_stats.reduce(self.L, rlog[base:base + k], alog[base:base + k], k, st, self._stream(), at=done)
                 self.eps = [r.eps[i] for i in range(N)] + self.eps[N:]
                 self.count = [mx.count[i] for i in range(N)]
                 self.episode += k
@@ -418,9 +432,12 @@ class MixedGameBatch:
                 if keep_games is not None:
                     rlog, alog = rlog.index_select(2, keep_games), alog.index_select(2, keep_games)
                 out.update(game_reward_log=rlog.cpu().numpy(), game_action_log=alog.cpu().numpy())
+            if st is not None:
+                from .group_stats import to_numpy
+                out["group_stats"] = to_numpy(st)
         return out
 
-    def _run_unfused(self, n_episodes):
+    def _run_unfused(self, n_episodes, group_stats=None):
         torch = _torch()
         if not self.initialized:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
@@ -497,8 +514,15 @@ class MixedGameBatch:
                         self.eps[i] = self.cfg.eps_end[i] + (self.eps[i] - self.cfg.eps_end[i]) * self.cfg.eps_step[i]
                 self.episode += 1
             self.state.copy_(price)
+            if group_stats is not None:
+                from .group_stats import to_numpy
+                if group_stats.G != G:
+                    raise ThrlError("group_stats spec is for %d games, this batch has %d" % (group_stats.G, G))
+                st = group_stats.reduce(L, rlog, alog, E, group_stats.zeros(E, self.device), self._stream())
             torch.cuda.synchronize(self.device)
             out = dict(game_reward_log=rlog.cpu().numpy(), game_action_log=alog.cpu().numpy(), kernel="unfused")
+            if group_stats is not None:
+                out["group_stats"] = to_numpy(st)
         out["reward_log"] = out["game_reward_log"].mean(axis=2)
         out["action_log"] = out["game_action_log"].mean(axis=2)
         return out

@@ -17,6 +17,17 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                  "game_logs": null,  # true (every game) or a list of global game ids: per-game learning curves
                                      # game_rewards.npy / game_actions.npy, float64 [epochs, N, kept games], and
                                      # game_ids.npy (int64 global ids); read one game with utils.game_log
+                 "group_stats": null, # true or {"bins": 256, "quantiles": [0.25, 0.5, 0.75], "histograms": false,
+                                     # "greedy_iters": 0, "ranges": {"total": [lo, hi], ...}}: per-group learning-curve
+                                     # statistics reduced on the device (group_stats.py): groups.json and float64
+                                     # group_mean / group_std / group_min / group_max.npy [epochs, n_groups, Q],
+                                     # group_quantiles.npy [epochs, n_groups, Q, n_q], group_sums.npy int64 [.., Q, 2],
+                                     # with histograms group_hist.npy uint32 [.., Q, bins + 2]; greedy_iters k > 0 adds
+                                     # the same greedy_*.npy of play_greedy's rows ([k, ...]).  Q = 2N + 1 quantities:
+                                     # reward_i, action_i, total.  Quantiles are of the per-epoch values (the reference
+                                     # smooths each run with ewm(halflife=1000) first; that is not done here).
+                 "groups": null,     # group id of every game (default: one group per distinct sweep combination, in
+                                     # order of first appearance; one group without a sweep)
                  "sweep": null}      # per-game hyper-parameters, e.g. {"gamma": [0.35, 0.95, ...]}: arrays of
                                      # length n_games (or [agent][game]) for gamma / alpha / eps / eps_end /
                                      # eps_step / noise_prob (+ entropy for neural agents) -- a config sweep
@@ -28,8 +39,9 @@ the reference draws them) and the run is float64.  n_games > 1: every game's tab
 initial state come from Philox keyed by (seed, global game id).  Output files are the
 reference's four artefacts for game 0 (`<i>.npy`, `<i>_counter.npy`, `config.json`,
 `log.csv` -- the log is the MEAN over games), plus `batch.pt` with all games when
-n_games > 1, and with "game_logs" the kept games' own curves (game_rewards.npy, game_actions.npy,
-game_ids.npy).  There is no CPU fallback: without the HIP library or a GPU this raises.
+n_games > 1, with "game_logs" the kept games' own curves (game_rewards.npy, game_actions.npy,
+game_ids.npy), and with "group_stats" the per-group statistics (groups.json, group_*.npy; utils.group_log and
+utils.group_quantiles read them).  There is no CPU fallback: without the HIP library or a GPU this raises.
 """
 import json
 import os
@@ -97,12 +109,46 @@ def game_log_chunk(n_agents, n_games, cycle=1, budget=GAME_LOG_BUDGET):
     return max(c, k // c * c)
 
 
-def _npy_out(path, shape):
-    """float64 .npy of `shape` filled in place (memory-mapped; an empty array is written as it is)."""
+def _npy_out(path, shape, dtype=numpy.float64):
+    """.npy of `shape` filled in place (memory-mapped; an empty array is written as it is)."""
     if all(shape):
-        return open_memmap(path, mode="w+", dtype=numpy.float64, shape=shape)
-    numpy.save(path, numpy.zeros(shape))
-    return numpy.zeros(shape)
+        return open_memmap(path, mode="w+", dtype=dtype, shape=shape)
+    numpy.save(path, numpy.zeros(shape, dtype))
+    return numpy.zeros(shape, dtype)
+
+
+GROUP_FIELDS = ("mean", "std", "min", "max", "quantiles", "sums", "hist")
+
+
+def group_stats_files(exp_path, prefix, rows, spec, histograms):
+    """The memory-mapped group_*.npy (or greedy_*.npy) of a run: dict field -> array [rows, n_groups, Q, ...]."""
+    cell = (int(rows), spec.n_groups, spec.Q)
+    shapes = {"mean": cell, "std": cell, "min": cell, "max": cell, "quantiles": cell + (len(spec.quantiles),),
+              "sums": cell + (2,), "hist": cell + (spec.bins + 2,)}
+    dt = {"sums": numpy.int64, "hist": numpy.uint32}
+    return {f: _npy_out(os.path.join(exp_path, "%s_%s.npy" % (prefix, f)), shapes[f], dt.get(f, numpy.float64))
+            for f in GROUP_FIELDS if f != "hist" or histograms}
+
+
+def write_group_stats(files, at, raw, describe):
+    """Rows at .. at + len of the files from one chunk's raw outputs (group_stats.to_numpy / merge)."""
+    from th_rl_amd.group_stats import finalize
+    fin = finalize(raw, describe)
+    k = raw["sums"].shape[0]
+    for f, arr in files.items():
+        arr[at:at + k] = raw[f] if f in ("sums", "hist") else fin[f]
+
+
+def group_spec_of(config, training, n_games):
+    """training.group_stats -> (GroupSpec of this run's games, options) or (None, None)."""
+    opt = training.get("group_stats", None)
+    if opt is None or opt is False:
+        return None, None
+    from th_rl_amd.group_stats import GroupSpec, parse_options
+    opt = parse_options(opt)
+    spec = GroupSpec.from_config(config, n_games, opt, sweep=training.get("sweep", None),
+                                 groups=training.get("groups", None), n_groups=training.get("n_groups", None))
+    return spec, opt
 
 
 def game_log_ids(spec, n_games, game_offset):
@@ -194,25 +240,36 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         g_rew = _npy_out(os.path.join(exp_path, "game_rewards.npy"), (epochs, len(agents), len(gids)))
         g_act = _npy_out(os.path.join(exp_path, "game_actions.npy"), (epochs, len(agents), len(gids)))
         keep = None if game_logs is True else torch.from_numpy(local).to(batch.device)
+    else:
+        game_logs = None
+        keep = None
+
+    spec, gs_opt = group_spec_of(config, training, n_games)
+    if spec is not None:
+        from th_rl_amd.group_stats import save_json
+        save_json(os.path.join(exp_path, "groups.json"), spec.describe())
+        g_files = group_stats_files(exp_path, "group", epochs, spec, gs_opt["histograms"])
+    if spec is not None or game_logs is not None:
         cycle = 1
         if isinstance(batch, GameBatch):
             import ctypes
             cycle = int(batch.L.thrl_training_cycle(ctypes.byref(batch.cfg))) or 1
         sub = game_log_chunk(len(agents), n_games, cycle)
-    else:
-        game_logs = None
 
     def run_logged(n, at):
-        """n episodes from epoch `at`: the mean logs, and the kept games' rows into the .npy files, in launches whose
-        per-game device buffers stay within the byte budget."""
+        """n episodes from epoch `at`: the mean logs, the kept games' rows into the .npy files and the per-group
+        statistics, in launches whose per-game device buffers stay within the byte budget."""
         d = 0
         while d < n:
             k = min(sub, n - d)
-            out = batch.run(k, per_game_logs=True, keep_games=keep)
+            out = batch.run(k, per_game_logs=game_logs is not None, keep_games=keep, group_stats=spec)
             rewards_log[at + d:at + d + k] = out["reward_log"]
             actions_log[at + d:at + d + k] = out["action_log"]
-            g_rew[at + d:at + d + k] = out["game_reward_log"]
-            g_act[at + d:at + d + k] = out["game_action_log"]
+            if game_logs is not None:
+                g_rew[at + d:at + d + k] = out["game_reward_log"]
+                g_act[at + d:at + d + k] = out["game_action_log"]
+            if spec is not None:
+                write_group_stats(g_files, at + d, out["group_stats"], spec.describe())
             d += k
 
     t = time.time()
@@ -220,7 +277,7 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     chunk = max(1, int(print_freq)) if print_freq else epochs
     while done < epochs:
         n = min(chunk - (done % chunk), epochs - done)
-        if game_logs is not None:
+        if game_logs is not None or spec is not None:
             run_logged(n, done)
         else:
             out = batch.run(n) if isinstance(batch, GameBatch) else batch.run(n, per_game_logs=False)
@@ -254,6 +311,16 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if game_logs is not None and g_rew.size:
         g_rew.flush()
         g_act.flush()
+    if spec is not None:
+        if gs_opt["greedy_iters"] > 0:          # utils.play_game of every trained game, reduced the same way
+            it = gs_opt["greedy_iters"]
+            _, _, raw = batch.play_greedy(iters=it, group_stats=spec)
+            gr_files = group_stats_files(exp_path, "greedy", it, spec, gs_opt["histograms"])
+            write_group_stats(gr_files, 0, raw, spec.describe())
+            g_files.update({"greedy_" + f: a for f, a in gr_files.items()})
+        for arr in g_files.values():
+            if hasattr(arr, "flush"):
+                arr.flush()
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

@@ -65,3 +65,71 @@ def game_log(exp_path, game_id):
             apd = pandas.DataFrame(data=numpy.array(act), columns=numpy.arange(n))
             return pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"])
     raise KeyError("game %d has no per-game log under %s (training.game_logs)" % (int(game_id), exp_path))
+
+
+def load_group_stats(exp_path, prefix="group"):
+    """(describe, fields) of a run trained with training.group_stats: groups.json and the group_*.npy (prefix
+    "greedy": greedy_*.npy) of exp_path; when exp_path has none but exp_path/shard*/ do (a sharded run stopped before
+    rank 0 merged them), the shards' raw outputs merged exactly (group_stats.merge)."""
+    import glob
+    import json
+    from th_rl_amd import group_stats as gs
+    top = os.path.join(exp_path, "groups.json")
+    shards = sorted(glob.glob(os.path.join(exp_path, "shard*")))
+    if os.path.isfile(os.path.join(exp_path, "%s_mean.npy" % prefix)):
+        desc = json.load(open(top))
+        fields = {f: numpy.load(os.path.join(exp_path, "%s_%s.npy" % (prefix, f)), mmap_mode="r")
+                  for f in ("mean", "std", "min", "max", "quantiles")}
+        return desc, fields
+    have = [d for d in shards if os.path.isfile(os.path.join(d, "%s_hist.npy" % prefix))]
+    if not have:
+        raise KeyError("no per-group statistics (%s_*.npy) under %s (training.group_stats)" % (prefix, exp_path))
+    desc = json.load(open(os.path.join(have[0], "groups.json")))
+    parts = []
+    for d in have:
+        ld = lambda f: numpy.load(os.path.join(d, "%s_%s.npy" % (prefix, f)))
+        vmin, vmax = ld("min"), ld("max")
+        kmin = numpy.where(numpy.isnan(vmin), numpy.uint64(0), ~gs.order_key(numpy.nan_to_num(vmin)))
+        kmax = numpy.where(numpy.isnan(vmax), numpy.uint64(0), gs.order_key(numpy.nan_to_num(vmax)))
+        parts.append({"hist": ld("hist"), "sums": ld("sums"), "minmax": numpy.stack([kmin, kmax], axis=-1)})
+    return desc, gs.finalize(gs.merge(parts), desc)
+
+
+def group_log(exp_path, group, prefix="group"):
+    """Group `group`'s mean curve over its games, with log.csv's columns (rewards / actions x agent), one row per
+    epoch (prefix "greedy": per greedy iteration)."""
+    desc, f = load_group_stats(exp_path, prefix)
+    n = (len(desc["quantities"]) - 1) // 2
+    m = numpy.array(f["mean"][:, int(group), :])
+    rpd = pandas.DataFrame(data=m[:, :n], columns=numpy.arange(n))
+    apd = pandas.DataFrame(data=m[:, n:2 * n], columns=numpy.arange(n))
+    return pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"])
+
+
+def _quantile_column(q):
+    return {0.5: "median", 0.0: "min", 1.0: "max"}.get(float(q), "%gth" % (100.0 * float(q)))
+
+
+def group_quantiles(exp_path, group, quantity="total", prefix="group"):
+    """utils.plot_learning_curve_conf's data for one group: a DataFrame with one column per configured quantile
+    ("25th", "median", "75th" for the default [0.25, 0.5, 0.75]) of `quantity` over the group's games, one row per
+    epoch, plus "Nash" and "Cartel" from environment.get_optimal() (the reference hard-codes 22.22 and 25)."""
+    desc, f = load_group_stats(exp_path, prefix)
+    names = desc["quantities"]
+    if quantity not in names:
+        raise KeyError("quantity %r is not one of %s" % (quantity, names))
+    q = names.index(quantity)
+    vals = numpy.array(f["quantiles"][:, int(group), q, :])
+    df = pandas.DataFrame(data=vals, columns=[_quantile_column(x) for x in desc["quantiles"]])
+    cfg_dir = exp_path if os.path.isfile(os.path.join(exp_path, "config.json")) else None
+    if cfg_dir is None:
+        import glob
+        hits = sorted(glob.glob(os.path.join(exp_path, "shard*", "shard_config.json")))
+        path = hits[0] if hits else None
+    else:
+        path = os.path.join(cfg_dir, "config.json")
+    if path is not None:
+        _, _, environment = create_game(path)
+        nash, cartel = environment.get_optimal()
+        df["Nash"], df["Cartel"] = float(nash), float(cartel)
+    return df
