@@ -432,6 +432,67 @@ typedef struct {
 } thrl_group_stats_args;
 int thrl_group_stats(const thrl_group_stats_args* args, void* stream);
 
+/*
+ * Deviation analysis of the greedy policies (the test of Calvano, Calzolari, Denicolo, Pastorello, "Artificial
+ * Intelligence, Algorithmic Pricing, and Collusion", AER 2020).  No reference counterpart: it extends
+ * utils.play_game (utils.py:27-47).  QTable agents only; q, and everything else of the batch, is left untouched.
+ * Every [.][G] array here has G = args.n_games: the first n_games games of q (n_games <= cfg.n_games).
+ *
+ * Greedy map F on row tuples x = (row_0 .. row_{N-1}): agent i plays a_i = argmax_row of its row x_i (first maximum
+ * under strict >), then scale_action and env_step with NO env noise (intercept env_a) give the price p and the
+ * rewards, and F(x)_i = encode64(p) (QTable.encode on the float64 price, as utils.play_game calls it).  The reward
+ * and scaled action "at x" are those of the transition taken at x.
+ *
+ * Start state x_0 = encode64(state0[g]) per agent.  Pre-shock cycle: mu >= 0, lam >= 1 the smallest values with
+ * x_{mu+lam} = x_mu.  The cycle is found iff mu + lam <= H (horizon); then s* = x_mu.  Otherwise lam = 0, mu = H and
+ * s* = x_H (so s* = x_mu in both cases).  Cycle detection keeps O(1) state per game (Brent) with a step budget that
+ * decides "found" exactly by mu + lam <= H.
+ *   cycle_reward[i][g] = (sum_{j<lam} reward_i at F^j(s*), added in that order from 0.0) / lam, cycle_action the
+ *   same for the scaled action; both 0 when lam = 0.
+ * Deviation path y_0 = s*: for tau < L agent d plays dev_action, or with dev_action = -1 its one-period best
+ * response at y_tau (the argmax over d's actions of d's env_step reward with the others greedy at y_tau, first
+ * maximum under strict >); for tau >= L every agent is greedy.  act_dev[g] = d's action at tau = 0.  Rows
+ * reward_rows / action_rows [row_count][N][G] hold, for tau in [row_begin, row_begin + row_count), the rewards and
+ * scaled actions of the transition taken at y_tau: the layout of the episode rows, so thrl_group_stats reduces them
+ * as they are (E = row_count).  The kernel walks the whole path whatever rows it stores.
+ * Baseline path z_0 = s*, every agent greedy.
+ * gain[g] = sum_{tau<K} w_tau * (r_d(y_tau) - r_d(z_tau)), w_0 = 1, w_{tau+1} = w_tau * gamma_d, each operation rounded
+ *   once (subtract, multiply, add); gamma_d = sweep_gamma[d][g] when given, else cfg.gamma[d].
+ * Return: (mu_post, lam_post) = the cycle of F from y_L under the same horizon rule; ret_step[g] = L + mu_post if that
+ *   cycle is found and s* lies on it, else -1 (always -1 when lam = 0).
+ * The profit gain (sum_i cycle_reward_i - Nash) / (Cartel - Nash) is the caller's (th_rl_amd/deviation.py).
+ *
+ * Returns THRL_ERR_BAD_CONFIG for a deviator outside [0, N), dev_len < 1, n_steps < dev_len or > THRL_DEV_MAX_STEPS,
+ * horizon outside [1, THRL_DEV_MAX_HORIZON], dev_action outside {-1} + [0, n_actions[d]), a row range outside
+ * [0, n_steps) or n_games outside [1, cfg.n_games]; THRL_ERR_NULL for a missing q, state0 or per-game output.
+ */
+#define THRL_DEV_MAX_STEPS (1 << 20)
+#define THRL_DEV_MAX_HORIZON (1 << 24)
+typedef struct {
+    int32_t n_games;                 /* G                                                */
+    int32_t deviator;                /* d in [0, N)                                      */
+    int32_t dev_len;                 /* L >= 1                                           */
+    int32_t n_steps;                 /* K >= L                                           */
+    int32_t horizon;                 /* H >= 1 (th_rl_amd: min(prod_i n_actions_i + 1, 65536)) */
+    int32_t dev_action;              /* fixed action index of d, or -1 = best response   */
+    int32_t row_begin;               /* rows stored: tau in [row_begin, row_begin + row_count) */
+    int32_t row_count;
+    const double* state0;            /* device [G] start prices (required)               */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    int32_t* mu;                     /* device outputs [G]                               */
+    int32_t* lam;
+    int32_t* mu_post;
+    int32_t* lam_post;
+    int32_t* ret_step;
+    int32_t* act_dev;
+    double*  cycle_reward;           /* device [N][G]                                    */
+    double*  cycle_action;           /* device [N][G]                                    */
+    double*  gain;                   /* device [G]                                       */
+    double*  reward_rows;            /* device [row_count][N][G] or NULL                 */
+    double*  action_rows;            /* device [row_count][N][G] or NULL                 */
+} thrl_deviation_args;
+int thrl_deviation(const thrl_cfg* cfg, const void* q, const thrl_deviation_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,24 @@ class GroupStatsArgs(ctypes.Structure):
     ]
 
 
+DEV_MAX_STEPS = 1 << 20
+DEV_MAX_HORIZON = 1 << 24
+
+
+class DeviationArgs(ctypes.Structure):
+    """thrl_deviation_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("deviator", ctypes.c_int32), ("dev_len", ctypes.c_int32),
+        ("n_steps", ctypes.c_int32), ("horizon", ctypes.c_int32), ("dev_action", ctypes.c_int32),
+        ("row_begin", ctypes.c_int32), ("row_count", ctypes.c_int32),
+        ("state0", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p),
+        ("mu", ctypes.c_void_p), ("lam", ctypes.c_void_p), ("mu_post", ctypes.c_void_p), ("lam_post", ctypes.c_void_p),
+        ("ret_step", ctypes.c_void_p), ("act_dev", ctypes.c_void_p),
+        ("cycle_reward", ctypes.c_void_p), ("cycle_action", ctypes.c_void_p), ("gain", ctypes.c_void_p),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -101,7 +119,7 @@ SYMBOLS = [
     "thrl_op_env_step", "thrl_op_td_update",
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
-    "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats",
+    "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
 ]
 CAC_PARAMS = 1283
 
@@ -200,6 +218,8 @@ def load():
     L.thrl_mixed_episodes.argtypes = [cfgp, ctypes.POINTER(Mixed), vp, vp, vp, ctypes.POINTER(Run), vp, vp, vp]
     L.thrl_group_stats.restype = ctypes.c_int
     L.thrl_group_stats.argtypes = [ctypes.POINTER(GroupStatsArgs), vp]
+    L.thrl_deviation.restype = ctypes.c_int
+    L.thrl_deviation.argtypes = [cfgp, vp, ctypes.POINTER(DeviationArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -270,6 +270,22 @@ class GameBatch:
             return mr.cpu().numpy(), ma.cpu().numpy(), st
         return mr.cpu().numpy(), ma.cpu().numpy()
 
+    def deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, state0=None,
+                  rows=False, group_stats=None, budget=None):
+        """Deviation analysis of every game's greedy policies (thrl_deviation; definitions in include/thrl.h):
+        the pre-shock cycle (mu, lam, cycle_reward / cycle_action [N, G]), deviator `deviator` playing `action`
+        ("best_response" or an action index) for dev_len of `steps` periods, and the response (mu_post, lam_post,
+        ret_step, act_dev, gain [G]).  horizon: None = min(prod n_actions + 1, 65536); state0 [G]: the start prices
+        (default: the batch's state); the per-game sweep gamma discounts the gain.  Returns a dict of numpy arrays;
+        rows=True adds reward_rows / action_rows [steps, N, G]; group_stats (a GroupSpec): the rows are reduced on
+        the device in tau-chunks and the raw statistics [steps, n_groups, Q, ...] are returned under "group_stats".
+        Tables, counters, state, epsilon and the episode index are not touched."""
+        from . import deviation as dv
+        if not self.initialized:
+            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
+        return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
+                      state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
+
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self):
         """Everything needed to continue the run bit-identically (the reference only saves

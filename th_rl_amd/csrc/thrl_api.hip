@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "thrl_deviation.h"
 #include "thrl_kernels.h"
 #include "thrl_wave_lut.h"
 
@@ -1300,6 +1301,82 @@ int thrl_group_stats(const thrl_group_stats_args* g, void* stream) {
     if (g->n_episodes == 0) return THRL_OK;
     const int e = thrl::launch_group_stats(g, (hipStream_t)stream);
     return e ? hip_fail(e, "k_group_stats launch") : THRL_OK;
+}
+
+int thrl_deviation(const thrl_cfg* c, const void* q, const thrl_deviation_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->deviator < 0 || x->deviator >= N)
+        return fail(THRL_ERR_BAD_CONFIG, "deviator=%d out of [0,%d)", x->deviator, N);
+    if (x->dev_len < 1) return fail(THRL_ERR_BAD_CONFIG, "dev_len=%d must be >= 1", x->dev_len);
+    if (x->n_steps < x->dev_len || x->n_steps > THRL_DEV_MAX_STEPS)
+        return fail(THRL_ERR_BAD_CONFIG, "n_steps=%d out of [dev_len=%d, %d]", x->n_steps, x->dev_len, THRL_DEV_MAX_STEPS);
+    if (x->horizon < 1 || x->horizon > THRL_DEV_MAX_HORIZON)
+        return fail(THRL_ERR_BAD_CONFIG, "horizon=%d out of [1,%d]", x->horizon, THRL_DEV_MAX_HORIZON);
+    if (x->dev_action < -1 || x->dev_action >= c->n_actions[x->deviator])
+        return fail(THRL_ERR_BAD_CONFIG, "dev_action=%d: -1 (best response) or an action of agent %d in [0,%d)",
+                    x->dev_action, x->deviator, c->n_actions[x->deviator]);
+    if (x->row_begin < 0 || x->row_count < 0 || (int64_t)x->row_begin + x->row_count > x->n_steps)
+        return fail(THRL_ERR_BAD_CONFIG, "rows [%d, %d + %d) outside [0, n_steps=%d)", x->row_begin, x->row_begin,
+                    x->row_count, x->n_steps);
+    if (!q || !x->state0 || !x->mu || !x->lam || !x->mu_post || !x->lam_post || !x->ret_step || !x->act_dev
+        || !x->cycle_reward || !x->cycle_action || !x->gain)
+        return fail(THRL_ERR_NULL, "q / state0 / mu / lam / mu_post / lam_post / ret_step / act_dev / cycle_reward / "
+                                   "cycle_action / gain is NULL");
+    DevArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.d = x->deviator; a.L = x->dev_len; a.K = x->n_steps; a.H = x->horizon;
+    a.dev_action = x->dev_action; a.row_begin = x->row_begin; a.row_count = x->row_count;
+    a.stride = (int64_t)thrl_table_stride(c);
+    fill_agents(c, a.ag, &a.env);
+    // Rows reachable after a transition: the price is monotone in every agent's action index (scale, the
+    // products, the sum, b * Q and a - b * Q are monotone roundings, the clamp at 0 too), and so is encode64, so
+    // the extremes of every agent's next row lie at the 2^N corners of the action grid.
+    int lo[THRL_MAXA], hi[THRL_MAXA];
+    for (int i = 0; i < N; i++) { lo[i] = c->n_states[i]; hi[i] = 0; }
+    const double ratio = c->env_a / c->env_b;
+    for (int mask = 0; mask < (1 << N); mask++) {
+        double Q = 0.0;
+        for (int j = 0; j < N; j++) {
+            const double A = ratio * h_scale((mask >> j) & 1 ? c->n_actions[j] - 1 : 0, c, j);
+            Q = Q + A;
+        }
+        double p = c->env_a - c->env_b * Q;
+        if (!(p > 0.0)) p = 0.0;
+        for (int i = 0; i < N; i++) {
+            int r = h_encode64(p, c, i);
+            r = r < 0 ? 0 : (r > c->n_states[i] ? c->n_states[i] : r);
+            if (r < lo[i]) lo[i] = r;
+            if (r > hi[i]) hi[i] = r;
+        }
+    }
+    int entries = 0, lut_n = 0, max_a = 0;
+    for (int i = 0; i < N; i++) {
+        a.win_lo[i] = lo[i];
+        a.win_n[i] = hi[i] - lo[i] + 1;
+        a.pol_off[i] = entries;
+        entries += a.win_n[i] + 1;                   // + x_0's row
+        a.lut_off[i] = lut_n;
+        lut_n += c->n_actions[i];
+        if (c->n_actions[i] > max_a) max_a = c->n_actions[i];
+    }
+    a.pol_off[N] = entries;
+    a.pol_entries = entries;
+    a.lut_n = lut_n;
+    a.pol_bytes = max_a <= 256 ? 1 : 2;
+    const int64_t lds = (int64_t)((lut_n * 8 + 15) & ~15) + (int64_t)kDevTile * entries * a.pol_bytes;
+    a.staged = lut_n <= kDevMaxLut && lds <= kDevLdsBudget;
+    a.lds_bytes = a.staged ? (int32_t)lds : 0;
+    a.q = q; a.state0 = x->state0; a.sweep_gamma = x->sweep_gamma;
+    a.mu = x->mu; a.lam = x->lam; a.mu_post = x->mu_post; a.lam_post = x->lam_post; a.ret_step = x->ret_step;
+    a.act_dev = x->act_dev; a.cycle_reward = x->cycle_reward; a.cycle_action = x->cycle_action; a.gain = x->gain;
+    a.reward_rows = x->reward_rows; a.action_rows = x->action_rows;
+    const int e = thrl::launch_deviation(a, c->q_dtype, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_deviation launch") : THRL_OK;
 }
 
 }  // extern "C"

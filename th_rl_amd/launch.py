@@ -12,7 +12,8 @@ shard checkpoint `--out/shard<r>/batch.pt`, and with training.game_logs its shar
 (`game_rewards.npy`, `game_actions.npy`, `game_ids.npy` with global ids; utils.game_log finds a game there).
 With training.group_stats, group ids come from the global sweep (or training.groups) before the cut, every shard
 writes its raw per-group statistics with histograms, and rank 0 merges them exactly into the top-level
-groups.json / group_*.npy (merge_group_stats).
+groups.json / group_*.npy (merge_group_stats); with training.deviation every shard writes its per-game deviation
+arrays, rank 0 merges the dev<d>_* statistics the same way and writes the top-level deviation.json (merge_deviation).
 """
 import argparse
 import json
@@ -60,6 +61,13 @@ def shard_training(config, rank, world):
         opt = dict(parse_options(gs))
         opt.update(histograms=True, n_max=int(numpy.bincount(ids, minlength=n_groups).max()))
         training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
+    dv = training.get("deviation")
+    if dv is not None and dv is not False and (gs is None or gs is False):
+        # the per-group summary of each shard's deviation.json uses the global group ids too
+        from th_rl_amd.group_stats import assign_groups
+        ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                         n_groups=training.get("n_groups"))
+        training.update(groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
     sweep = training.get("sweep")
     if sweep:        # slice the per-game arrays to this shard
         def cut(v):
@@ -88,6 +96,10 @@ def merge_group_stats(config, out, world):
     save_json(os.path.join(out, "groups.json"), desc)
     shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
     prefixes = ["group"] + (["greedy"] if opt["greedy_iters"] > 0 else [])
+    dv = training.get("deviation")
+    if dv is not None and dv is not False:
+        from th_rl_amd.deviation import parse_options as deviation_options
+        prefixes += ["dev%d" % d for d in deviation_options(dv, config)["agents"]]
     for prefix in prefixes:
         parts = []
         for d in shards:
@@ -100,6 +112,27 @@ def merge_group_stats(config, out, world):
         for a in files.values():
             if hasattr(a, "flush"):
                 a.flush()
+
+
+def merge_deviation(config, out, world):
+    """Rank 0: the top-level deviation.json of a sharded run from the shards' per-game arrays (deviation.combine:
+    the concatenation in global game order, summarised as one run)."""
+    from th_rl_amd import deviation as dv
+    from th_rl_amd.group_stats import assign_groups
+    training = config.get("training", {})
+    total = int(training.get("n_games", world))
+    opt = dv.parse_options(training["deviation"], config)
+    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                     n_groups=training.get("n_groups"))
+    nash, cartel = dv.optimal(config)
+    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
+    summary = []
+    for d in opt["agents"]:
+        games = dv.combine(dv.load_games(s, d) for s in shards)
+        summary += dv.summarize(games, ids, n_groups, nash, cartel, d)
+    with open(os.path.join(shards[0], "deviation.json")) as f:
+        opt["horizon_used"] = json.load(f)["options"]["horizon_used"]
+    dv.save_json(os.path.join(out, "deviation.json"), dv.describe(opt, nash, cartel, summary))
 
 
 def _keys(vmin, vmax):
@@ -150,6 +183,8 @@ def _worker(rank, world, port, config, out, devices_available):
         pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"]).to_csv(os.path.join(out, "log.csv"), index=None)
         if training.get("group_stats"):
             merge_group_stats(config, out, world)
+        if training.get("deviation"):
+            merge_deviation(config, out, world)
     dist.destroy_process_group()
 
 

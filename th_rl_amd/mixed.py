@@ -254,6 +254,18 @@ class MixedGameBatch:
         return mr.cpu().numpy(), ma.cpu().numpy()
 
     # ------------------------------------------------------------------ checkpoint / resume
+    def deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, state0=None,
+                  rows=False, group_stats=None, budget=None):
+        """GameBatch.deviation for an all-QTable batch (the same table layout; train_one runs small float64
+        all-QTable batches here).  A batch with a neural agent raises ThrlError."""
+        from . import deviation as dv
+        if any(k != "QTable" for k in self.kinds):
+            raise ThrlError("MixedGameBatch.deviation: agents %s: %s" % (self.kinds, dv.NEURAL_FOLLOW_UP))
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
+                      state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
+
     def state_dict(self):
         """Everything a continued run needs (plain tensors / numbers: loads with weights_only=True)."""
         return dict(version=2, kind="mixed", n_games=self.G, kinds=list(self.kinds), shapes=[list(x) for x in self.shapes],

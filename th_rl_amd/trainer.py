@@ -26,6 +26,13 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                      # the same greedy_*.npy of play_greedy's rows ([k, ...]).  Q = 2N + 1 quantities:
                                      # reward_i, action_i, total.  Quantiles are of the per-epoch values (the reference
                                      # smooths each run with ewm(halflife=1000) first; that is not done here).
+                 "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
+                                     # "horizon": null}: after training (and the greedy statistics) the deviation
+                                     # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json
+                                     # (options, Nash, Cartel, per-(group, deviator) summary), dev_cycle.npy int32 [2, G]
+                                     # (mu, lam), dev_cycle_reward / dev_cycle_action.npy [N, G], per deviator d
+                                     # dev<d>_post.npy int32 [4, G] (mu_post, lam_post, ret_step, act_dev) and
+                                     # dev<d>_gain.npy [G]; with group_stats the response rows' dev<d>_*.npy [steps, ...]
                  "groups": null,     # group id of every game (default: one group per distinct sweep combination, in
                                      # order of first appearance; one group without a sweep)
                  "sweep": null}      # per-game hyper-parameters, e.g. {"gamma": [0.35, 0.95, ...]}: arrays of
@@ -177,6 +184,10 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     all_tabular = all(isinstance(a, QTable) for a in agents)
 
     training = config.get("training", {})
+    dev_opt = None
+    if training.get("deviation") is not None and training.get("deviation") is not False:
+        from th_rl_amd.deviation import parse_options as deviation_options
+        dev_opt = deviation_options(training["deviation"], config)     # refuses neural agents before training
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -321,6 +332,17 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         for arr in g_files.values():
             if hasattr(arr, "flush"):
                 arr.flush()
+
+    if dev_opt is not None:     # the greedy policies' deviation analysis (deviation.py)
+        from th_rl_amd.deviation import write_artefacts
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        write_artefacts(exp_path, batch, config, dev_opt, ids, n_groups, spec=spec,
+                        histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

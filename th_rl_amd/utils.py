@@ -133,3 +133,55 @@ def group_quantiles(exp_path, group, quantity="total", prefix="group"):
         nash, cartel = environment.get_optimal()
         df["Nash"], df["Cartel"] = float(nash), float(cartel)
     return df
+
+
+def deviation_summary(exp_path):
+    """A run's deviation analysis (training.deviation): deviation.json's summary as a DataFrame with one row per
+    (group, deviator) -- games, cycles, fixed_points, returned, unprofitable, ret_step_mean, the profit gain's mean
+    and quantiles (delta_*), gain_mean, and one lam_<bin> column per bin of the lam histogram -- plus Nash and Cartel.
+    The response curves of a run that also has training.group_stats are the per-group statistics of prefix
+    "dev<d>": group_quantiles(exp_path, group, "total", prefix="dev0") and group_log(exp_path, group, prefix="dev0"),
+    one row per period after the shock."""
+    import json
+    with open(os.path.join(exp_path, "deviation.json")) as f:
+        desc = json.load(f)
+    rows = []
+    for r in desc["summary"]:
+        r = dict(r)
+        for name, n in zip(desc["lam_bins"], r.pop("lam_hist")):
+            r["lam_" + name] = n
+        rows.append(r)
+    df = pandas.DataFrame(rows)
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def deviation_games(exp_path, deviator=0):
+    """Per-game results of the deviation analysis for `deviator`, one row per game indexed by its GLOBAL id: mu, lam,
+    mu_post, lam_post, ret_step, act_dev, gain, cycle_reward_<i> / cycle_action_<i> and the profit gain delta.  Reads
+    exp_path's dev*.npy, or those of exp_path/shard*/ (th_rl_amd.launch writes one set per rank) in game order."""
+    import glob
+    import json
+    from th_rl_amd import deviation as dv
+    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "dev_cycle.npy")) else \
+        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "dev_cycle.npy"))),
+               key=lambda d: int(os.path.basename(d)[5:]))
+    if not dirs:
+        raise KeyError("no deviation analysis (dev_cycle.npy) under %s (training.deviation)" % exp_path)
+    frames = []
+    for d in dirs:
+        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
+        with open(cfg_path) as f:
+            config = json.load(f)
+        g = dv.load_games(d, int(deviator))
+        nash, cartel = dv.optimal(config)
+        off = int(config.get("training", {}).get("game_offset", 0))
+        n = g["gain"].shape[0]
+        cols = {f: g[f] for f in dv.INT_FIELDS}
+        cols["gain"] = g["gain"]
+        for i in range(g["cycle_reward"].shape[0]):
+            cols["cycle_reward_%d" % i] = g["cycle_reward"][i]
+            cols["cycle_action_%d" % i] = g["cycle_action"][i]
+        cols["delta"] = dv.profit_gain(g["cycle_reward"], nash, cartel)
+        frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
+    return pandas.concat(frames)
