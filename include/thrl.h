@@ -493,6 +493,47 @@ typedef struct {
 } thrl_deviation_args;
 int thrl_deviation(const thrl_cfg* cfg, const void* q, const thrl_deviation_args* args, void* stream);
 
+/*
+ * Convergence tracking of the greedy policies (the stopping rule of Calvano et al., AER 2020: a session has
+ * converged when no agent's greedy strategy has changed for W periods).  No reference counterpart.  QTable agents
+ * only; q is read only.  Every [G] array here has G = args.n_games: the first n_games games of q.
+ *
+ * Policy of game g: for every agent i and every row r of its table, all n_states_i + 1 of them, the greedy action
+ * argmax_row(q[g] agent i row r): the first maximum under strict > (the rule of thrl_play_greedy, thrl_deviation and
+ * numpy.argmax).  policy[g] holds the P = sum_i (n_states_i + 1) entries, agent 0's rows first, one uint16 each.
+ *
+ * With THRL_TRACK_BASELINE: policy[g] = the policy, stable_since[g] = episode, converged_at[g] = conv_since[g] = -1,
+ * changes[g] = 0; nothing is compared and nothing converges.
+ * Otherwise, a check at episode e (= args.episode) does for every game g, in this order:
+ *   1. if any entry of the policy differs from policy[g]: policy[g] = the policy, stable_since[g] = e, changes[g] += 1;
+ *   2. if converged_at[g] < 0 and e - stable_since[g] >= W (= args.window): converged_at[g] = e,
+ *      conv_since[g] = stable_since[g], *n_converged += 1 (when given), and when q_conv is given q_conv[g] = q[g]
+ *      (the game's stride elements, in q's dtype) and state_conv[g] = state[g].
+ * Converged games go on being tracked: stable_since and changes keep updating, converged_at keeps the first
+ * convergence.  A change that reverts between two checks is not seen.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for window < 1, n_games outside [1, cfg.n_games], a flag other than
+ * THRL_TRACK_BASELINE, an agent with more than 65,536 actions, or q_conv without state or state_conv;
+ * THRL_ERR_NULL for a missing q, policy, stable_since, converged_at, conv_since or changes.
+ */
+#define THRL_TRACK_BASELINE 1
+typedef struct {
+    int32_t n_games;                 /* G in [1, cfg.n_games]                            */
+    int32_t flags;                   /* 0 or THRL_TRACK_BASELINE                         */
+    int64_t episode;                 /* e: episodes completed so far (global index)      */
+    int64_t window;                  /* W >= 1 episodes                                  */
+    uint16_t* policy;                /* device [G][P] in/out                             */
+    int64_t* stable_since;           /* device [G] in/out                                */
+    int64_t* converged_at;           /* device [G] in/out, -1 = not (yet) converged      */
+    int64_t* conv_since;             /* device [G] in/out, -1 = not (yet) converged      */
+    int32_t* changes;                /* device [G] in/out: checks at which the policy changed */
+    int32_t* n_converged;            /* device [1] += games that converge at this check, or NULL */
+    const double* state;             /* device [G]; required with q_conv                 */
+    void*    q_conv;                 /* device [G][stride] in q's dtype, or NULL         */
+    double*  state_conv;             /* device [G]; required with q_conv                 */
+} thrl_policy_track_args;
+int thrl_policy_track(const thrl_cfg* cfg, const void* q, const thrl_policy_track_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

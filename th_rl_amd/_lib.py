@@ -111,6 +111,19 @@ class DeviationArgs(ctypes.Structure):
     ]
 
 
+TRACK_BASELINE = 1
+
+
+class PolicyTrackArgs(ctypes.Structure):
+    """thrl_policy_track_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("flags", ctypes.c_int32), ("episode", ctypes.c_int64), ("window", ctypes.c_int64),
+        ("policy", ctypes.c_void_p), ("stable_since", ctypes.c_void_p), ("converged_at", ctypes.c_void_p),
+        ("conv_since", ctypes.c_void_p), ("changes", ctypes.c_void_p), ("n_converged", ctypes.c_void_p),
+        ("state", ctypes.c_void_p), ("q_conv", ctypes.c_void_p), ("state_conv", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -120,6 +133,7 @@ SYMBOLS = [
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
+    "thrl_policy_track",
 ]
 CAC_PARAMS = 1283
 
@@ -220,6 +234,8 @@ def load():
     L.thrl_group_stats.argtypes = [ctypes.POINTER(GroupStatsArgs), vp]
     L.thrl_deviation.restype = ctypes.c_int
     L.thrl_deviation.argtypes = [cfgp, vp, ctypes.POINTER(DeviationArgs), vp]
+    L.thrl_policy_track.restype = ctypes.c_int
+    L.thrl_policy_track.argtypes = [cfgp, vp, ctypes.POINTER(PolicyTrackArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -286,6 +286,14 @@ class GameBatch:
         return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
                       state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
 
+    def track_convergence(self, window, every=1, snapshot=False):
+        """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
+        its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.
+        snapshot=True keeps each game's tables and state at its convergence (one more copy of q on the device).
+        Only reads the tables."""
+        from .convergence import Tracker
+        return Tracker(self, window, every, snapshot)
+
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self):
         """Everything needed to continue the run bit-identically (the reference only saves

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "thrl_converge.h"
 #include "thrl_deviation.h"
 #include "thrl_kernels.h"
 #include "thrl_wave_lut.h"
@@ -1377,6 +1378,59 @@ int thrl_deviation(const thrl_cfg* c, const void* q, const thrl_deviation_args* 
     a.reward_rows = x->reward_rows; a.action_rows = x->action_rows;
     const int e = thrl::launch_deviation(a, c->q_dtype, (hipStream_t)stream);
     return e ? hip_fail(e, "k_deviation launch") : THRL_OK;
+}
+
+int thrl_policy_track(const thrl_cfg* c, const void* q, const thrl_policy_track_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->window < 1) return fail(THRL_ERR_BAD_CONFIG, "window=%lld must be >= 1", (long long)x->window);
+    if (x->flags & ~THRL_TRACK_BASELINE) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    // validate() caps every agent at 32,000 actions, so each greedy action fits a 16-bit policy entry (thrl.h's
+    // "more than 65,536 actions" is refused there, with THRL_ERR_BAD_CONFIG)
+    if (x->q_conv && (!x->state || !x->state_conv))
+        return fail(THRL_ERR_BAD_CONFIG, "q_conv needs state and state_conv");
+    if (!q || !x->policy || !x->stable_since || !x->converged_at || !x->conv_since || !x->changes)
+        return fail(THRL_ERR_NULL, "q / policy / stable_since / converged_at / conv_since / changes is NULL");
+    TrackArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.baseline = (x->flags & THRL_TRACK_BASELINE) ? 1 : 0;
+    a.stride = (int64_t)thrl_table_stride(c);
+    a.episode = x->episode; a.window = x->window;
+    AgentParams ag[THRL_MAXA];
+    fill_agents(c, ag, nullptr);
+    int P = 0;
+    for (int i = 0; i < N; i++) {
+        a.row_off[i] = P;
+        a.table_off[i] = ag[i].table_off;
+        a.n_actions[i] = ag[i].n_actions;
+        P += ag[i].rows;
+    }
+    a.row_off[N] = P;
+    a.P = P;
+    // the staged window: the game's block widened to 16-byte chunks at both ends
+    const int64_t esz = c->q_dtype == 1 ? 8 : 4, vec = 16 / esz;
+    const int64_t lds = ((a.stride + 2 * vec) * esz + 15) & ~(int64_t)15;
+    a.staged = lds <= kTrackLdsBudget && ((uintptr_t)q & 15) == 0;
+    a.lds_bytes = a.staged ? (int32_t)lds : 0;
+    a.q = q; a.policy = x->policy; a.stable_since = x->stable_since; a.converged_at = x->converged_at;
+    a.conv_since = x->conv_since; a.changes = x->changes; a.n_converged = x->n_converged;
+    a.state = x->state; a.q_conv = x->q_conv; a.state_conv = x->state_conv;
+    // enough one-wave blocks to fill every CU as far as LDS allows, each looping over games
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    int per_cu = kTrackMaxBlocksPerCu;
+    if (a.staged && lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes > 0 ? lds_cu / a.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_policy_track(a, c->q_dtype, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_policy_track launch") : THRL_OK;
 }
 
 }  // extern "C"

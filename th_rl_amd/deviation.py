@@ -80,7 +80,7 @@ def parse_options(opt, config):
         opt = {}
     if not isinstance(opt, dict):
         raise ValueError("training.deviation must be true or a dict, got %r" % (opt,))
-    known = {"agents", "steps", "dev_len", "action", "horizon"}
+    known = {"agents", "steps", "dev_len", "action", "horizon", "tables"}
     bad = set(opt) - known
     if bad:
         raise ValueError("training.deviation: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(known))))
@@ -102,14 +102,18 @@ def parse_options(opt, config):
         out["horizon"] = int(out["horizon"])
         if not 1 <= out["horizon"] <= _lib.DEV_MAX_HORIZON:
             raise ValueError("training.deviation.horizon=%d out of [1, %d]" % (out["horizon"], _lib.DEV_MAX_HORIZON))
+    if "tables" in out and out["tables"] not in ("final", "converged"):
+        raise ValueError("training.deviation.tables must be 'final' or 'converged', got %r" % (out["tables"],))
     return out
 
 
 # ---------------------------------------------------------------------------------------------- the device call
 def run(batch, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, state0=None, rows=False,
-        group_stats=None, budget=ROW_BUDGET):
+        group_stats=None, budget=ROW_BUDGET, q=None):
     """thrl_deviation for every game of `batch` (a GameBatch or an all-QTable MixedGameBatch; see
-    GameBatch.deviation).  The rows are produced in tau-chunks of at most `budget` bytes per device buffer."""
+    GameBatch.deviation).  The rows are produced in tau-chunks of at most `budget` bytes per device buffer.
+    q: a device tensor shaped and typed like batch.q analysed in place of the batch's tables (e.g. the tables at
+    convergence, convergence.Tracker.tables_at_convergence)."""
     import torch
     G, N = batch.G, batch.N
     K, L = int(steps), int(dev_len)
@@ -120,12 +124,19 @@ def run(batch, deviator=0, steps=32, dev_len=1, action="best_response", horizon=
     if group_stats is not None and group_stats.G != G:
         raise ThrlError("group_stats spec is for %d games, this batch has %d" % (group_stats.G, G))
     dev = batch.device
+    if q is None:
+        q = batch.q
+    elif tuple(q.shape) != tuple(batch.q.shape) or q.dtype != batch.q.dtype or q.device != batch.q.device \
+            or not q.is_contiguous():
+        raise ThrlError("deviation: q must be a contiguous %s tensor %s on %s" % (batch.q.dtype, tuple(batch.q.shape), dev))
     a = _lib.DeviationArgs()
     a.n_games, a.deviator, a.dev_len, a.n_steps, a.horizon = G, int(deviator), L, K, H
     a.dev_action = action_index(action)
     with torch.cuda.device(dev):
         if state0 is None:
             s0 = batch.state
+        elif isinstance(state0, torch.Tensor):
+            s0 = state0.to(device=dev, dtype=torch.float64).reshape(G).contiguous()
         else:
             s0 = torch.from_numpy(np.ascontiguousarray(np.asarray(state0, np.float64).reshape(G))).to(dev)
         out = {f: torch.zeros((G,), dtype=torch.int32, device=dev) for f in INT_FIELDS}
@@ -151,7 +162,7 @@ def run(batch, deviator=0, steps=32, dev_len=1, action="best_response", horizon=
             a.row_begin, a.row_count = b0, k
             a.reward_rows = rr.data_ptr() if rr is not None else None
             a.action_rows = ra.data_ptr() if ra is not None else None
-            _lib.check(batch.L.thrl_deviation(ctypes.byref(batch.cfg), batch.q.data_ptr(), ctypes.byref(a),
+            _lib.check(batch.L.thrl_deviation(ctypes.byref(batch.cfg), q.data_ptr(), ctypes.byref(a),
                                               batch._stream()), "thrl_deviation")
             if st is not None and k:
                 group_stats.reduce(batch.L, rr, ra, k, st, batch._stream(), at=b0)
@@ -251,15 +262,17 @@ def load_games(d, deviator):
             "cycle_action": np.load(os.path.join(d, "dev_cycle_action.npy"))}
 
 
-def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=ROW_BUDGET):
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=ROW_BUDGET,
+                    q=None, state0=None):
     """train_one's training.deviation outputs: the per-game .npy files, dev<d>_*.npy group statistics with a spec,
-    and deviation.json."""
+    and deviation.json.  q / state0 (device tensors): the tables and start prices analysed in place of the batch's
+    (opt["tables"] == "converged")."""
     from . import trainer
     nash, cartel = optimal(config)
     summary = []
     for d in opt["agents"]:
         r = run(batch, deviator=d, steps=opt["steps"], dev_len=opt["dev_len"], action=opt["action"],
-                horizon=opt["horizon"], group_stats=spec, budget=budget)
+                horizon=opt["horizon"], group_stats=spec, budget=budget, q=q, state0=state0)
         if d == opt["agents"][0]:
             np.save(os.path.join(exp_path, "dev_cycle.npy"), np.stack([r["mu"], r["lam"]]).astype(np.int32))
             np.save(os.path.join(exp_path, "dev_cycle_reward.npy"), r["cycle_reward"])

@@ -13,7 +13,10 @@ shard checkpoint `--out/shard<r>/batch.pt`, and with training.game_logs its shar
 With training.group_stats, group ids come from the global sweep (or training.groups) before the cut, every shard
 writes its raw per-group statistics with histograms, and rank 0 merges them exactly into the top-level
 groups.json / group_*.npy (merge_group_stats); with training.deviation every shard writes its per-game deviation
-arrays, rank 0 merges the dev<d>_* statistics the same way and writes the top-level deviation.json (merge_deviation).
+arrays, rank 0 merges the dev<d>_* statistics the same way and writes the top-level deviation.json (merge_deviation);
+with training.convergence every shard writes its per-game convergence arrays and rank 0 writes the top-level
+convergence.json and conv_*.npy (merge_convergence).  A convergence stop counts the games of every rank (the trainer
+all-reduces over the gloo group), so all ranks stop at the same episode.
 """
 import argparse
 import json
@@ -62,8 +65,9 @@ def shard_training(config, rank, world):
         opt.update(histograms=True, n_max=int(numpy.bincount(ids, minlength=n_groups).max()))
         training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
     dv = training.get("deviation")
-    if dv is not None and dv is not False and (gs is None or gs is False):
-        # the per-group summary of each shard's deviation.json uses the global group ids too
+    cv = training.get("convergence")
+    if ((dv is not None and dv is not False) or (cv is not None and cv is not False)) and (gs is None or gs is False):
+        # the per-group summaries of each shard's deviation.json / convergence.json use the global group ids too
         from th_rl_amd.group_stats import assign_groups
         ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
                                          n_groups=training.get("n_groups"))
@@ -131,8 +135,32 @@ def merge_deviation(config, out, world):
         games = dv.combine(dv.load_games(s, d) for s in shards)
         summary += dv.summarize(games, ids, n_groups, nash, cartel, d)
     with open(os.path.join(shards[0], "deviation.json")) as f:
-        opt["horizon_used"] = json.load(f)["options"]["horizon_used"]
+        first = json.load(f)["options"]
+    opt["horizon_used"] = first["horizon_used"]
+    if "tables" in first:       # recorded when the run tracks convergence
+        opt["tables"] = first["tables"]
     dv.save_json(os.path.join(out, "deviation.json"), dv.describe(opt, nash, cartel, summary))
+
+
+def merge_convergence(config, out, world):
+    """Rank 0: the top-level convergence.json and conv_*.npy of a sharded run from the shards' per-game arrays
+    (convergence.combine: the concatenation in global game order, summarised as one run)."""
+    from th_rl_amd import convergence as cv
+    from th_rl_amd.group_stats import assign_groups
+    training = config.get("training", {})
+    total = int(training.get("n_games", world))
+    opt = cv.parse_options(training["convergence"], config)
+    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                     n_groups=training.get("n_groups"))
+    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
+    games = cv.combine(cv.load_games(s) for s in shards)
+    cv.save_games(out, games)
+    with open(os.path.join(shards[0], "convergence.json")) as f:
+        first = json.load(f)
+    summary = cv.summarize(games, ids, n_groups, opt["window"], first["episode_end"])
+    cv.save_json(os.path.join(out, "convergence.json"),
+                 cv.describe(opt, first["every_used"], first["episodes_run"], first["episode_end"],
+                             first["stopped_early"], summary))
 
 
 def _keys(vmin, vmax):
@@ -185,6 +213,8 @@ def _worker(rank, world, port, config, out, devices_available):
             merge_group_stats(config, out, world)
         if training.get("deviation"):
             merge_deviation(config, out, world)
+        if training.get("convergence"):
+            merge_convergence(config, out, world)
     dist.destroy_process_group()
 
 

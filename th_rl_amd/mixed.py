@@ -266,6 +266,14 @@ class MixedGameBatch:
         return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
                       state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
 
+    def track_convergence(self, window, every=1, snapshot=False):
+        """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
+        all-QTable batches here).  A batch with a neural agent raises ThrlError."""
+        from . import convergence as cv
+        if any(k != "QTable" for k in self.kinds):
+            raise ThrlError("MixedGameBatch.track_convergence: agents %s: %s" % (self.kinds, cv.NEURAL_FOLLOW_UP))
+        return cv.Tracker(self, window, every, snapshot)
+
     def state_dict(self):
         """Everything a continued run needs (plain tensors / numbers: loads with weights_only=True)."""
         return dict(version=2, kind="mixed", n_games=self.G, kinds=list(self.kinds), shapes=[list(x) for x in self.shapes],

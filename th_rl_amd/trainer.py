@@ -32,7 +32,22 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                      # (options, Nash, Cartel, per-(group, deviator) summary), dev_cycle.npy int32 [2, G]
                                      # (mu, lam), dev_cycle_reward / dev_cycle_action.npy [N, G], per deviator d
                                      # dev<d>_post.npy int32 [4, G] (mu_post, lam_post, ret_step, act_dev) and
-                                     # dev<d>_gain.npy [G]; with group_stats the response rows' dev<d>_*.npy [steps, ...]
+                                     # dev<d>_gain.npy [G]; with group_stats the response rows' dev<d>_*.npy [steps, ...];
+                                     # "tables": "final" (default) | "converged" (needs convergence.snapshot): analyse
+                                     # each game's tables and state at its convergence (never converged: final tables)
+                 "convergence": null, # true or {"window": ceil(100000 / max_steps), "every": 20, "stop": null,
+                                     # "snapshot": false}: track every game's greedy policy (convergence.py, QTable
+                                     # agents only) at the global episodes that are multiples of `every` (on GameBatch
+                                     # rounded up to a multiple of thrl_training_cycle; launches are cut there); a game
+                                     # has converged at the first check where its policy has not changed for `window`
+                                     # episodes.  stop: a fraction in (0, 1] ends training at the first check where that
+                                     # fraction of the run's games (all shards) has converged, epochs the cap; log.csv
+                                     # and the per-epoch .npy then have episodes_run rows.  snapshot: keep each game's
+                                     # tables and state at convergence on the device (stride * 4 B per game in float32,
+                                     # * 8 B in float64, + 8 B).  Writes convergence.json (options, every_used,
+                                     # episodes_run, stopped_early, per-group summary), conv_episode.npy /
+                                     # conv_since.npy / conv_stable_since.npy int64 [G] (-1 = never), conv_changes.npy
+                                     # int32 [G] and convergence.pt (the tracker; resume picks it up beside batch.pt)
                  "groups": null,     # group id of every game (default: one group per distinct sweep combination, in
                                      # order of first appearance; one group without a sweep)
                  "sweep": null}      # per-game hyper-parameters, e.g. {"gamma": [0.35, 0.95, ...]}: arrays of
@@ -173,6 +188,22 @@ def game_log_ids(spec, n_games, game_offset):
     return local + int(game_offset), local
 
 
+def _run_totals(converged, n_games):
+    """(converged games, games) of the whole run: summed over the ranks of th_rl_amd.launch (its gloo group), so that
+    every rank stops at the same check."""
+    try:
+        import torch.distributed as dist
+        active = dist.is_available() and dist.is_initialized()
+    except ImportError:
+        active = False
+    if not active:
+        return int(converged), int(n_games)
+    import torch
+    t = torch.tensor([int(converged), int(n_games)], dtype=torch.int64)
+    dist.all_reduce(t)
+    return int(t[0]), int(t[1])
+
+
 def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if not os.path.exists(exp_path):
         os.mkdir(os.path.join(exp_path))
@@ -188,6 +219,12 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if training.get("deviation") is not None and training.get("deviation") is not False:
         from th_rl_amd.deviation import parse_options as deviation_options
         dev_opt = deviation_options(training["deviation"], config)     # refuses neural agents before training
+    conv_opt = None
+    if training.get("convergence") is not None and training.get("convergence") is not False:
+        from th_rl_amd.convergence import parse_options as convergence_options
+        conv_opt = convergence_options(training["convergence"], config)   # refuses neural agents before training
+    if dev_opt is not None and dev_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
+        raise ValueError('training.deviation.tables = "converged" needs training.convergence with "snapshot": true')
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -240,6 +277,18 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     else:
         batch.init_tables()
 
+    tracker = None
+    if conv_opt is not None:
+        import ctypes
+        from th_rl_amd.convergence import every_used
+        cycle = int(batch.L.thrl_training_cycle(ctypes.byref(batch.cfg))) if isinstance(batch, GameBatch) else 1
+        conv_every = every_used(conv_opt["every"], cycle)
+        tracker = batch.track_convergence(conv_opt["window"], conv_every, conv_opt["snapshot"])
+        if resume and os.path.isfile(os.path.join(os.path.dirname(os.path.abspath(resume)), "convergence.pt")):
+            tracker.load(os.path.join(os.path.dirname(os.path.abspath(resume)), "convergence.pt"))
+        n_conv = tracker.converged()
+    stopped_early = False
+
     rewards_log = numpy.zeros((epochs, len(agents)))
     actions_log = numpy.zeros((epochs, len(agents)))
 
@@ -288,6 +337,8 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     chunk = max(1, int(print_freq)) if print_freq else epochs
     while done < epochs:
         n = min(chunk - (done % chunk), epochs - done)
+        if tracker is not None:     # cut the launch at the next check episode
+            n = min(n, conv_every - batch.episode % conv_every)
         if game_logs is not None or spec is not None:
             run_logged(n, done)
         else:
@@ -295,11 +346,24 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             rewards_log[done:done + n] = out["reward_log"]
             actions_log[done:done + n] = out["action_log"]
         done += n
+        if tracker is not None and tracker.due():
+            # the count crosses to the host (and waits for the device) only when a stop or a progress line needs it
+            counted = tracker.check(count=conv_opt["stop"] is not None or bool(print_freq and not done % print_freq))
+            n_conv = n_conv if counted is None else counted
+            if conv_opt["stop"] is not None:
+                total_conv, total_games = _run_totals(n_conv, n_games)
+                stopped_early = done < epochs and total_conv >= conv_opt["stop"] * total_games
         if print_freq and not done % print_freq:
             rew = numpy.mean(rewards_log[done - print_freq:done, :], axis=0)
             act = numpy.mean(actions_log[done - print_freq:done, :], axis=0)
-            print(_progress_line(print_eps, _eps_of_game0(batch), time.time() - t, done - 1, rew, act, names))
+            line = _progress_line(print_eps, _eps_of_game0(batch), time.time() - t, done - 1, rew, act, names)
+            if tracker is not None:
+                line += " | converged:{:.3f}".format(n_conv / n_games)
+            print(line)
             t = time.time()
+        if stopped_early:
+            break
+    episodes_run = done
 
     # Store result: the reference's artefacts, from game 0
     for i, a in enumerate(agents):
@@ -315,13 +379,27 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     with open(os.path.join(exp_path, "config.json"), "w") as f:
         json.dump(config, f, indent=3)
 
-    rpd = pandas.DataFrame(data=rewards_log, columns=numpy.arange(len(agents)))
-    apd = pandas.DataFrame(data=actions_log, columns=numpy.arange(len(agents)))
+    rpd = pandas.DataFrame(data=rewards_log[:episodes_run], columns=numpy.arange(len(agents)))
+    apd = pandas.DataFrame(data=actions_log[:episodes_run], columns=numpy.arange(len(agents)))
     log = pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"])
     log.to_csv(os.path.join(exp_path, "log.csv"), index=None)
     if game_logs is not None and g_rew.size:
         g_rew.flush()
         g_act.flush()
+    if stopped_early:       # every per-epoch artefact has episodes_run rows
+        from th_rl_amd.convergence import truncate_rows
+        per_epoch = []
+        if game_logs is not None:
+            g_rew = g_act = None
+            per_epoch += ["game_rewards.npy", "game_actions.npy"]
+        if spec is not None:
+            for f in list(g_files):
+                if hasattr(g_files[f], "flush"):
+                    g_files[f].flush()
+                g_files[f] = None
+                per_epoch.append("group_%s.npy" % f)
+        for name in per_epoch:
+            truncate_rows(os.path.join(exp_path, name), episodes_run)
     if spec is not None:
         if gs_opt["greedy_iters"] > 0:          # utils.play_game of every trained game, reduced the same way
             it = gs_opt["greedy_iters"]
@@ -333,6 +411,16 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             if hasattr(arr, "flush"):
                 arr.flush()
 
+    if tracker is not None:     # the convergence arrays and their per-group summary (convergence.py)
+        from th_rl_amd.convergence import write_artefacts as write_convergence
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        write_convergence(exp_path, tracker, conv_opt, conv_every, ids, n_groups, episodes_run, stopped_early)
+
     if dev_opt is not None:     # the greedy policies' deviation analysis (deviation.py)
         from th_rl_amd.deviation import write_artefacts
         if spec is not None:
@@ -341,8 +429,13 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             from th_rl_amd.group_stats import assign_groups
             ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
                                              n_groups=training.get("n_groups", None))
+        q_dev = s_dev = None
+        if tracker is not None:
+            dev_opt = dict(dev_opt, tables=dev_opt.get("tables", "final"))
+            if dev_opt["tables"] == "converged":
+                q_dev, s_dev = tracker.tables_at_convergence()
         write_artefacts(exp_path, batch, config, dev_opt, ids, n_groups, spec=spec,
-                        histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET)
+                        histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET, q=q_dev, state0=s_dev)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

@@ -185,3 +185,43 @@ def deviation_games(exp_path, deviator=0):
         cols["delta"] = dv.profit_gain(g["cycle_reward"], nash, cartel)
         frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
     return pandas.concat(frames)
+
+
+def convergence_summary(exp_path):
+    """A run's convergence (training.convergence): convergence.json's summary as a DataFrame with one row per group --
+    games, converged, fraction, converged_at_mean / q25 / q50 / q75, conv_since_mean / q25 / q50 / q75 (over the
+    converged games), still_stable, changes_mean -- plus the run's window, every_used, episodes_run and
+    stopped_early."""
+    import json
+    with open(os.path.join(exp_path, "convergence.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["window"] = int(desc["options"]["window"])
+    df["every_used"] = int(desc["every_used"])
+    df["episodes_run"] = int(desc["episodes_run"])
+    df["stopped_early"] = bool(desc["stopped_early"])
+    return df
+
+
+def convergence_games(exp_path):
+    """Per-game convergence, one row per game indexed by its GLOBAL id: converged_at (-1 = never), conv_since,
+    stable_since, changes.  Reads exp_path's conv_*.npy, or those of exp_path/shard*/ in game order."""
+    import glob
+    import json
+    from th_rl_amd import convergence as cv
+    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "conv_episode.npy")) else \
+        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "conv_episode.npy"))),
+               key=lambda d: int(os.path.basename(d)[5:]))
+    if not dirs:
+        raise KeyError("no convergence arrays (conv_episode.npy) under %s (training.convergence)" % exp_path)
+    frames = []
+    for d in dirs:
+        off = 0
+        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
+        if os.path.isfile(cfg_path):
+            with open(cfg_path) as f:
+                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        g = cv.load_games(d)
+        n = g["converged_at"].shape[0]
+        frames.append(pandas.DataFrame({f: g[f] for f in cv.FILES}, index=pandas.RangeIndex(off, off + n, name="game")))
+    return pandas.concat(frames)
