@@ -534,6 +534,82 @@ typedef struct {
 } thrl_policy_track_args;
 int thrl_policy_track(const thrl_cfg* cfg, const void* q, const thrl_policy_track_args* args, void* stream);
 
+/*
+ * Equilibrium check of the greedy strategies (Calvano et al., AER 2020, equilibrium play and "Q-loss"): hold the
+ * rivals' greedy strategies fixed, solve agent i's dynamic problem exactly, and report whether its own greedy
+ * strategy is a best response on the path greedy play follows (Nash) and in every state (subgame perfect), and how
+ * much value it gives up if not.  No reference counterpart.  QTable agents only, no env noise (intercept env_a);
+ * q, and everything else of the batch, is read only.  Every [.][G] array has G = args.n_games: the first n_games
+ * games of q.  All arithmetic is float64, every operation rounded once, in the order written here.
+ *
+ * States.  Action tuples t = (a_0 .. a_{N-1}) are numbered with agent 0 slowest, T = prod_i n_actions_i of them.
+ * Tuple t gives the price p(t) (scale_action, env_step) with rewards r_i(t), and the row tuple
+ * x(t) = (encode64_i(p(t)))_i.  The state set is the set of DISTINCT ROW TUPLES, numbered 0 .. S-1 in order of first
+ * occurrence in tuple order; state(t) is the number of x(t), row_i(s) agent i's row in state s.  The library derives
+ * these tables from cfg on the host and keeps them on the device (a few configs are cached per process).
+ * Limits: T <= THRL_EQ_MAX_TUPLES and S <= THRL_EQ_MAX_STATES, otherwise THRL_ERR_UNSUPPORTED.
+ *
+ * Agent i's problem in game g.  pi_j(s) = argmax_row of agent j's row row_j(s) (first maximum under strict >).
+ * t(s, a) = the tuple with a in place i and pi_j(s) elsewhere, R(s, a) = r_i(t(s, a)), nxt(s, a) = state(t(s, a)).
+ * gamma = sweep_gamma[i][g] when given, else cfg.gamma[i].  The discounted sums below need gamma in [0, 1): without
+ * sweep_gamma, cfg.gamma[i] outside it for a selected agent is THRL_ERR_BAD_CONFIG (no other analysis call
+ * restricts gamma: thrl_deviation's gain is a finite sum and takes any).  The values of sweep_gamma live on the
+ * device and are the caller's to check; a game whose gamma is not in [0, 1) is not solved and gets iters = -1,
+ * n_diff_all = n_diff_on = 0 and NaN in every float64 output of that agent.
+ *
+ * Evaluation of a strategy sigma by doubling: V = R(., sigma), n = nxt(., sigma), w = gamma; D times, for all states
+ * at once from the old V and n:  V = V + w * V[n];  n = n[n];  w = w * w.   D = the number of squarings w = w * w
+ * (from w = gamma) until w < 2^-64: 0 for gamma = 0, 10 for 0.95, 13 for 0.99, at most 59 for any double below 1
+ * (the kernel stops at 64).  The result is the discounted sum of the first 2^D rewards.
+ *
+ * Policy iteration from the agent's own strategy: sigma_0 = pi_i.  Round k = 0, 1, ..: V_k = evaluation of sigma_k;
+ * if k == THRL_EQ_MAX_ITERS stop with iters = -1; Q(s, a) = R(s, a) + gamma * V_k[nxt(s, a)];
+ * sigma_{k+1}(s) = sigma_k(s) unless max_a Q(s, a) > Q(s, sigma_k(s)), then the first maximum (strict >, a ascending);
+ * if no state changed stop with iters = k.  V_pi = V_0, V* = the last V_k, sigma* = the last strategy.  The incumbent
+ * is kept on ties, so a strategy that is a best response gives iters = 0 and V* == V_pi bit for bit.
+ *   loss(s) = 0.0 where V*(s) == V_pi(s) or V*(s) == 0, else (V*(s) - V_pi(s)) / V*(s).
+ *
+ * Path.  x_0 = (encode64_i(state0[g]))_i, which need not be a member of the state set; x_{k+1} = x(tuple of the greedy
+ * actions at x_k), a member.  mu >= 0, lam >= 1 the smallest values with x_{mu+lam} = x_mu: thrl_deviation's mu and lam
+ * for a horizon of at least T + 1 (th_rl_amd's default).  "On path" = the lam states x_mu .. x_{mu+lam-1}, in that
+ * ("cycle") order.
+ *
+ * Outputs, per selected agent i (bit i of agents) and game; entries of agents not selected are not written:
+ *   iters, n_diff_all, n_diff_on   states / cycle states with sigma*(s) != pi_i(s)
+ *   loss_all, loss_on              the largest loss(s) over all states / cycle states
+ *   loss_all_mean, loss_on_mean    (sum of loss(s) from 0.0 in state order / cycle order) / S, / lam
+ *   v_on                           (sum of V_pi(s) from 0.0 in cycle order) / lam
+ *   br_policy, v_opt, v_pi         optional [N][G][S]: sigma*, V*, V_pi per state
+ * *n_states (HOST, optional) receives S as soon as cfg is accepted, whatever the call returns afterwards.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games outside [1, cfg.n_games], agents == 0 or with a bit >= N, or gamma as
+ * above; THRL_ERR_UNSUPPORTED for the limits; THRL_ERR_NULL for a missing q, state0 or required output.
+ */
+#define THRL_EQ_MAX_ITERS 64
+#define THRL_EQ_MAX_TUPLES 4096
+#define THRL_EQ_MAX_STATES 1024
+typedef struct {
+    int32_t n_games;                 /* G in [1, cfg.n_games]                            */
+    int32_t agents;                  /* bit i set: solve agent i                         */
+    const double* state0;            /* device [G] start prices                          */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    int32_t* n_states;               /* HOST [1] <- S, or NULL                           */
+    int32_t* mu;                     /* device [G]                                       */
+    int32_t* lam;                    /* device [G]                                       */
+    int32_t* iters;                  /* device [N][G]                                    */
+    int32_t* n_diff_all;             /* device [N][G]                                    */
+    int32_t* n_diff_on;              /* device [N][G]                                    */
+    double*  loss_all;               /* device [N][G]                                    */
+    double*  loss_on;                /* device [N][G]                                    */
+    double*  loss_all_mean;          /* device [N][G]                                    */
+    double*  loss_on_mean;           /* device [N][G]                                    */
+    double*  v_on;                   /* device [N][G]                                    */
+    uint16_t* br_policy;             /* device [N][G][S] or NULL                         */
+    double*  v_opt;                  /* device [N][G][S] or NULL                         */
+    double*  v_pi;                   /* device [N][G][S] or NULL                         */
+} thrl_equilibrium_args;
+int thrl_equilibrium(const thrl_cfg* cfg, const void* q, const thrl_equilibrium_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

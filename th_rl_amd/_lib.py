@@ -124,6 +124,24 @@ class PolicyTrackArgs(ctypes.Structure):
     ]
 
 
+EQ_MAX_ITERS = 64
+EQ_MAX_TUPLES = 4096
+EQ_MAX_STATES = 1024
+
+
+class EquilibriumArgs(ctypes.Structure):
+    """thrl_equilibrium_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("agents", ctypes.c_int32),
+        ("state0", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p), ("n_states", ctypes.POINTER(ctypes.c_int32)),
+        ("mu", ctypes.c_void_p), ("lam", ctypes.c_void_p), ("iters", ctypes.c_void_p),
+        ("n_diff_all", ctypes.c_void_p), ("n_diff_on", ctypes.c_void_p),
+        ("loss_all", ctypes.c_void_p), ("loss_on", ctypes.c_void_p), ("loss_all_mean", ctypes.c_void_p),
+        ("loss_on_mean", ctypes.c_void_p), ("v_on", ctypes.c_void_p),
+        ("br_policy", ctypes.c_void_p), ("v_opt", ctypes.c_void_p), ("v_pi", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -133,7 +151,7 @@ SYMBOLS = [
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
-    "thrl_policy_track",
+    "thrl_policy_track", "thrl_equilibrium",
 ]
 CAC_PARAMS = 1283
 
@@ -236,6 +254,8 @@ def load():
     L.thrl_deviation.argtypes = [cfgp, vp, ctypes.POINTER(DeviationArgs), vp]
     L.thrl_policy_track.restype = ctypes.c_int
     L.thrl_policy_track.argtypes = [cfgp, vp, ctypes.POINTER(PolicyTrackArgs), vp]
+    L.thrl_equilibrium.restype = ctypes.c_int
+    L.thrl_equilibrium.argtypes = [cfgp, vp, ctypes.POINTER(EquilibriumArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -286,6 +286,20 @@ class GameBatch:
         return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
                       state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
 
+    def equilibrium(self, agents=None, state0=None, policies=False, tol=0.0):
+        """Equilibrium check of every game's greedy strategies (thrl_equilibrium; definitions in include/thrl.h): for
+        each agent in `agents` (default all) the exact best response to the others' greedy strategies, and whether
+        its own is one.  Returns a dict of numpy arrays: mu, lam [G] (GameBatch.deviation's, default horizon); iters,
+        n_diff_all, n_diff_on, loss_all, loss_on, loss_all_mean, loss_on_mean, v_on [N, G]; the host-side flags
+        br_on, br_all [N, G], nash, perfect [G] for the tolerance `tol` (loss <= tol; 0.0 = exact); n_states, agents.
+        policies=True adds br_policy (uint16), v_opt, v_pi [N, G, S].  state0 [G]: the start prices (default: the
+        batch's state); the per-game sweep gamma is each game's discount factor.  Tables, counters, state, epsilon
+        and the episode index are not touched."""
+        from . import equilibrium as eq
+        if not self.initialized:
+            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
+        return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
         its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.

@@ -6,11 +6,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <map>
 #include <mutex>
 #include <vector>
 
 #include "thrl_converge.h"
 #include "thrl_deviation.h"
+#include "thrl_equilibrium.h"
 #include "thrl_kernels.h"
 #include "thrl_wave_lut.h"
 
@@ -1431,6 +1433,221 @@ int thrl_policy_track(const thrl_cfg* c, const void* q, const thrl_policy_track_
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_policy_track(a, c->q_dtype, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_policy_track launch") : THRL_OK;
+}
+
+}  // extern "C"
+
+// ---- thrl_equilibrium: the per-config plan (tuple LUTs and state rows), built on the host and cached on the device
+namespace {
+
+struct EqKey {                      // everything of thrl_cfg the plan depends on, and the device it lives on
+    int32_t dev, N;
+    double env_a, env_b;
+    int32_t n_states[THRL_MAXA], n_actions[THRL_MAXA];
+    double max_state[THRL_MAXA], act_lo[THRL_MAXA], act_hi[THRL_MAXA];
+};
+
+struct EqHostPlan {
+    int S = 0, T = 0;
+    std::vector<double> rew;        // [N][T]
+    std::vector<int32_t> srow;      // [N][S]
+    std::vector<uint16_t> sid;      // [T]
+};
+
+struct EqSlot {
+    bool used = false;
+    EqKey key;
+    int S = 0, T = 0;
+    void* mem = nullptr;            // rew | srow | sid
+    size_t off_srow = 0, off_sid = 0;
+};
+
+constexpr int kEqSlots = 4;
+std::mutex g_eq_mu;
+EqSlot g_eq_slot[kEqSlots];
+int g_eq_next = 0;
+
+EqKey eq_key(const thrl_cfg* c, int dev) {
+    EqKey k;
+    memset(&k, 0, sizeof(k));
+    k.dev = dev; k.N = c->n_agents; k.env_a = c->env_a; k.env_b = c->env_b;
+    for (int i = 0; i < c->n_agents; i++) {
+        k.n_states[i] = c->n_states[i]; k.n_actions[i] = c->n_actions[i];
+        k.max_state[i] = c->max_state[i]; k.act_lo[i] = c->act_lo[i]; k.act_hi[i] = c->act_hi[i];
+    }
+    return k;
+}
+
+// THRL_OK, or THRL_ERR_UNSUPPORTED past the limits of include/thrl.h.  The arithmetic is the device's scale_action,
+// env_step (no noise) and encode64, operation for operation.
+int eq_host_plan(const thrl_cfg* c, EqHostPlan& h) {
+    const int N = c->n_agents;
+    int64_t T = 1;
+    for (int i = 0; i < N; i++) {
+        T *= c->n_actions[i];
+        if (T > THRL_EQ_MAX_TUPLES)
+            return fail(THRL_ERR_UNSUPPORTED, "thrl_equilibrium: more than %d action tuples (prod n_actions)",
+                        THRL_EQ_MAX_TUPLES);
+    }
+    h.T = (int)T;
+    h.rew.assign((size_t)N * T, 0.0);
+    h.sid.assign((size_t)T, 0);
+    const double ratio = c->env_a / c->env_b;
+    std::map<std::vector<int32_t>, int> ids;
+    std::vector<std::vector<int32_t>> rows;
+    std::vector<int32_t> x((size_t)N);
+    for (int t = 0; t < (int)T; t++) {
+        double A[THRL_MAXA];
+        double Q = 0.0;
+        int rest = t;
+        int act[THRL_MAXA];
+        for (int i = N - 1; i >= 0; i--) { act[i] = rest % c->n_actions[i]; rest /= c->n_actions[i]; }
+        for (int i = 0; i < N; i++) {
+            A[i] = ratio * h_scale(act[i], c, i);
+            Q = Q + A[i];
+        }
+        double p = c->env_a - c->env_b * Q;
+        if (!(p > 0.0)) p = 0.0;
+        for (int i = 0; i < N; i++) {
+            h.rew[(size_t)i * T + t] = p * A[i];
+            const int r = h_encode64(p, c, i);
+            x[(size_t)i] = r < 0 ? 0 : (r > c->n_states[i] ? c->n_states[i] : r);
+        }
+        auto it = ids.find(x);
+        if (it == ids.end()) {
+            if ((int)rows.size() == THRL_EQ_MAX_STATES)
+                return fail(THRL_ERR_UNSUPPORTED, "thrl_equilibrium: more than %d distinct row tuples (states)",
+                            THRL_EQ_MAX_STATES);
+            it = ids.emplace(x, (int)rows.size()).first;
+            rows.push_back(x);
+        }
+        h.sid[(size_t)t] = (uint16_t)it->second;
+    }
+    h.S = (int)rows.size();
+    h.srow.assign((size_t)N * h.S, 0);
+    for (int s = 0; s < h.S; s++)
+        for (int i = 0; i < N; i++) h.srow[(size_t)i * h.S + s] = rows[(size_t)s][(size_t)i];
+    return THRL_OK;
+}
+
+// The device copy of the plan for (cfg, current device): cached, at most kEqSlots configs, the oldest evicted after
+// the device has drained (a kernel of an earlier call may still read it).
+int eq_device_plan(const thrl_cfg* c, const EqHostPlan& h, EqSlot& out) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail((int)e, "hipGetDevice");
+    const EqKey key = eq_key(c, dev);
+    std::lock_guard<std::mutex> lock(g_eq_mu);
+    for (int k = 0; k < kEqSlots; k++)
+        if (g_eq_slot[k].used && !memcmp(&g_eq_slot[k].key, &key, sizeof(key))) { out = g_eq_slot[k]; return THRL_OK; }
+    EqSlot& sl = g_eq_slot[g_eq_next];
+    if (sl.used) {
+        int cur = dev;
+        if ((e = hipSetDevice(sl.key.dev)) != hipSuccess) return hip_fail((int)e, "hipSetDevice");
+        e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipFree(sl.mem);
+        hipError_t e2 = hipSetDevice(cur);
+        sl.used = false;
+        sl.mem = nullptr;
+        if (e != hipSuccess) return hip_fail((int)e, "releasing a cached equilibrium plan");
+        if (e2 != hipSuccess) return hip_fail((int)e2, "hipSetDevice");
+    }
+    const size_t b_rew = h.rew.size() * sizeof(double), b_srow = h.srow.size() * sizeof(int32_t),
+                 b_sid = h.sid.size() * sizeof(uint16_t);
+    sl.off_srow = b_rew;
+    sl.off_sid = b_rew + b_srow;
+    if ((e = hipMalloc(&sl.mem, b_rew + b_srow + b_sid)) != hipSuccess) return hip_fail((int)e, "hipMalloc (equilibrium plan)");
+    unsigned char* m = (unsigned char*)sl.mem;
+    e = hipMemcpy(m, h.rew.data(), b_rew, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m + sl.off_srow, h.srow.data(), b_srow, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m + sl.off_sid, h.sid.data(), b_sid, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(sl.mem);
+        sl.mem = nullptr;
+        return hip_fail((int)e, "hipMemcpy (equilibrium plan)");
+    }
+    sl.used = true; sl.key = key; sl.S = h.S; sl.T = h.T;
+    g_eq_next = (g_eq_next + 1) % kEqSlots;
+    out = sl;
+    return THRL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int thrl_equilibrium(const thrl_cfg* c, const void* q, const thrl_equilibrium_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    EqHostPlan h;
+    if ((rc = eq_host_plan(c, h)) != THRL_OK) return rc;
+    if (x->n_states) *x->n_states = h.S;
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->agents == 0 || (x->agents & ~((1 << N) - 1)))
+        return fail(THRL_ERR_BAD_CONFIG, "agents=0x%x: a non-empty mask of agents in [0,%d)", x->agents, N);
+    if (!x->sweep_gamma)
+        for (int i = 0; i < N; i++)
+            if (((x->agents >> i) & 1) && !(c->gamma[i] >= 0.0 && c->gamma[i] < 1.0))
+                return fail(THRL_ERR_BAD_CONFIG, "agent %d: gamma=%g: the equilibrium check needs gamma in [0, 1)", i,
+                            c->gamma[i]);
+    if (!q || !x->state0 || !x->mu || !x->lam || !x->iters || !x->n_diff_all || !x->n_diff_on || !x->loss_all
+        || !x->loss_on || !x->loss_all_mean || !x->loss_on_mean || !x->v_on)
+        return fail(THRL_ERR_NULL, "q / state0 / mu / lam / iters / n_diff_all / n_diff_on / loss_all / loss_on / "
+                                   "loss_all_mean / loss_on_mean / v_on is NULL");
+    EqSlot sl;
+    if ((rc = eq_device_plan(c, h, sl)) != THRL_OK) return rc;
+    EqArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.S = h.S; a.T = h.T; a.agents = x->agents;
+    a.small = h.S <= 64;
+    a.stride = (int64_t)thrl_table_stride(c);
+    fill_agents(c, a.ag, nullptr);
+    int ts = 1;
+    for (int i = N - 1; i >= 0; i--) { a.tstride[i] = ts; ts *= c->n_actions[i]; }
+    // LDS of a block: 8-byte arrays first, then 4-byte, then 2-byte
+    const int S = h.S, T = h.T;
+    const int64_t fixed = 3 * 8 * (int64_t)S + 4 * (int64_t)S + 4 * THRL_MAXA
+                          + 2 * ((int64_t)T + (int64_t)N * S + THRL_MAXA + 5 * (int64_t)S) + 64;
+    a.lut_lds = fixed + 8 * (int64_t)N * T <= kEqLdsBudget;
+    int off = 0;
+    a.o_va = off; off += 8 * S;
+    a.o_vb = off; off += 8 * S;
+    a.o_vpi = off; off += 8 * S;
+    a.o_rew = off; off += a.lut_lds ? 8 * N * T : 0;
+    a.o_base = off; off += 4 * S;
+    a.o_x0row = off; off += 4 * THRL_MAXA;
+    a.o_sid = off; off += 2 * T;
+    a.o_first = off; off += 2 * S;
+    a.o_pol = off; off += 2 * (N * S + THRL_MAXA);
+    a.o_sigma = off; off += 2 * S;
+    a.o_jn = off; off += 2 * S;
+    a.o_na = off; off += 2 * S;
+    a.o_nb = off; off += 2 * S;
+    a.lds_bytes = (off + 15) & ~15;
+    if (a.lds_bytes > kEqLdsBudget)         // cannot happen within the limits (62 KB at S = 1024, T = 4096, N = 8)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_equilibrium: %d bytes of LDS per game", a.lds_bytes);
+    a.q = q; a.state0 = x->state0; a.sweep_gamma = x->sweep_gamma;
+    a.rew = (const double*)sl.mem;
+    a.srow = (const int32_t*)((const unsigned char*)sl.mem + sl.off_srow);
+    a.sid = (const uint16_t*)((const unsigned char*)sl.mem + sl.off_sid);
+    a.mu = x->mu; a.lam = x->lam; a.iters = x->iters; a.n_diff_all = x->n_diff_all; a.n_diff_on = x->n_diff_on;
+    a.loss_all = x->loss_all; a.loss_on = x->loss_on; a.loss_all_mean = x->loss_all_mean;
+    a.loss_on_mean = x->loss_on_mean; a.v_on = x->v_on;
+    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    int per_cu = kEqMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes > 0 ? lds_cu / a.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_equilibrium(a, c->q_dtype, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_equilibrium launch") : THRL_OK;
 }
 
 }  // extern "C"

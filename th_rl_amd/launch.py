@@ -14,6 +14,7 @@ With training.group_stats, group ids come from the global sweep (or training.gro
 writes its raw per-group statistics with histograms, and rank 0 merges them exactly into the top-level
 groups.json / group_*.npy (merge_group_stats); with training.deviation every shard writes its per-game deviation
 arrays, rank 0 merges the dev<d>_* statistics the same way and writes the top-level deviation.json (merge_deviation);
+with training.equilibrium rank 0 concatenates the shards' eq_*.npy and writes equilibrium.json (merge_equilibrium);
 with training.convergence every shard writes its per-game convergence arrays and rank 0 writes the top-level
 convergence.json and conv_*.npy (merge_convergence).  A convergence stop counts the games of every rank (the trainer
 all-reduces over the gloo group), so all ranks stop at the same episode.
@@ -65,7 +66,7 @@ def shard_training(config, rank, world):
         opt.update(histograms=True, n_max=int(numpy.bincount(ids, minlength=n_groups).max()))
         training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
     dv = training.get("deviation")
-    cv = training.get("convergence")
+    cv = training.get("convergence") or training.get("equilibrium")
     if ((dv is not None and dv is not False) or (cv is not None and cv is not False)) and (gs is None or gs is False):
         # the per-group summaries of each shard's deviation.json / convergence.json use the global group ids too
         from th_rl_amd.group_stats import assign_groups
@@ -142,6 +143,31 @@ def merge_deviation(config, out, world):
     dv.save_json(os.path.join(out, "deviation.json"), dv.describe(opt, nash, cartel, summary))
 
 
+def merge_equilibrium(config, out, world):
+    """Rank 0: the top-level equilibrium.json and eq_*.npy of a sharded run from the shards' per-game arrays
+    (equilibrium.combine: the concatenation in global game order, summarised as one run)."""
+    from th_rl_amd import equilibrium as eq
+    from th_rl_amd.group_stats import assign_groups
+    training = config.get("training", {})
+    total = int(training.get("n_games", world))
+    opt = eq.parse_options(training["equilibrium"], config)
+    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                     n_groups=training.get("n_groups"))
+    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
+    games = eq.combine(eq.load_games(s) for s in shards)
+    eq.save_games(out, games)
+    with open(os.path.join(shards[0], "equilibrium.json")) as f:
+        first = json.load(f)
+    if "tables" in first["options"]:       # recorded when the run tracks convergence
+        opt["tables"] = first["options"]["tables"]
+    delta = None
+    if first["summary"] and first["summary"][-1]["collusive"] is not None:
+        deltas = [eq.load_delta(s, config) for s in shards]
+        delta = numpy.concatenate(deltas)
+    summary = eq.summarize(games, ids, n_groups, opt["agents"], opt["tol"], delta)
+    eq.save_json(os.path.join(out, "equilibrium.json"), eq.describe(opt, first["n_states"], summary))
+
+
 def merge_convergence(config, out, world):
     """Rank 0: the top-level convergence.json and conv_*.npy of a sharded run from the shards' per-game arrays
     (convergence.combine: the concatenation in global game order, summarised as one run)."""
@@ -215,6 +241,8 @@ def _worker(rank, world, port, config, out, devices_available):
             merge_deviation(config, out, world)
         if training.get("convergence"):
             merge_convergence(config, out, world)
+        if training.get("equilibrium"):
+            merge_equilibrium(config, out, world)
     dist.destroy_process_group()
 
 

@@ -266,6 +266,16 @@ class MixedGameBatch:
         return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
                       state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
 
+    def equilibrium(self, agents=None, state0=None, policies=False, tol=0.0):
+        """GameBatch.equilibrium for an all-QTable batch (the same table layout).  A batch with a neural agent
+        raises ThrlError."""
+        from . import equilibrium as eq
+        if any(k != "QTable" for k in self.kinds):
+            raise ThrlError("MixedGameBatch.equilibrium: agents %s: %s" % (self.kinds, eq.NEURAL_FOLLOW_UP))
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

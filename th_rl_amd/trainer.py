@@ -26,6 +26,9 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                      # the same greedy_*.npy of play_greedy's rows ([k, ...]).  Q = 2N + 1 quantities:
                                      # reward_i, action_i, total.  Quantiles are of the per-epoch values (the reference
                                      # smooths each run with ewm(halflife=1000) first; that is not done here).
+                 "equilibrium": null,  # true or {"agents": [all], "tol": 0.0, "policies": false, "tables": "final"}: after
+                                       # training (and the deviation analysis) the equilibrium check of the greedy
+                                       # strategies (equilibrium.py, QTable agents only): equilibrium.json, eq_*.npy
                  "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
                                      # "horizon": null}: after training (and the greedy statistics) the deviation
                                      # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json
@@ -225,6 +228,12 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         conv_opt = convergence_options(training["convergence"], config)   # refuses neural agents before training
     if dev_opt is not None and dev_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
         raise ValueError('training.deviation.tables = "converged" needs training.convergence with "snapshot": true')
+    eq_opt = None
+    if training.get("equilibrium") is not None and training.get("equilibrium") is not False:
+        from th_rl_amd.equilibrium import parse_options as equilibrium_options
+        eq_opt = equilibrium_options(training["equilibrium"], config)     # refuses neural agents and gamma >= 1
+    if eq_opt is not None and eq_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
+        raise ValueError('training.equilibrium.tables = "converged" needs training.convergence with "snapshot": true')
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -436,6 +445,21 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
                 q_dev, s_dev = tracker.tables_at_convergence()
         write_artefacts(exp_path, batch, config, dev_opt, ids, n_groups, spec=spec,
                         histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET, q=q_dev, state0=s_dev)
+
+    if eq_opt is not None:      # are the greedy strategies an equilibrium (equilibrium.py)
+        from th_rl_amd.equilibrium import write_artefacts as write_equilibrium
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        q_eq = s_eq = None
+        if tracker is not None:
+            eq_opt = dict(eq_opt, tables=eq_opt.get("tables", "final"))
+            if eq_opt["tables"] == "converged":
+                q_eq, s_eq = tracker.tables_at_convergence()
+        write_equilibrium(exp_path, batch, config, eq_opt, ids, n_groups, q=q_eq, state0=s_eq)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

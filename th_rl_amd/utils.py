@@ -141,7 +141,8 @@ def deviation_summary(exp_path):
     and quantiles (delta_*), gain_mean, and one lam_<bin> column per bin of the lam histogram -- plus Nash and Cartel.
     The response curves of a run that also has training.group_stats are the per-group statistics of prefix
     "dev<d>": group_quantiles(exp_path, group, "total", prefix="dev0") and group_log(exp_path, group, prefix="dev0"),
-    one row per period after the shock."""
+    one row per period after the shock.  mu and lam of deviation_games are those of equilibrium_games for the same run
+    (same tables, same start prices, default horizon)."""
     import json
     with open(os.path.join(exp_path, "deviation.json")) as f:
         desc = json.load(f)
@@ -183,6 +184,55 @@ def deviation_games(exp_path, deviator=0):
             cols["cycle_reward_%d" % i] = g["cycle_reward"][i]
             cols["cycle_action_%d" % i] = g["cycle_action"][i]
         cols["delta"] = dv.profit_gain(g["cycle_reward"], nash, cartel)
+        frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
+    return pandas.concat(frames)
+
+
+def equilibrium_summary(exp_path):
+    """A run's equilibrium check (training.equilibrium): equilibrium.json's summary as a DataFrame.  Rows with an
+    agent: games, br_on, br_all (fractions of games in which the agent's greedy strategy is a best response on the
+    path / in every state), loss_on_q* / loss_all_q* (over the games with a positive loss), capped.  Rows with agent
+    NaN: the group's nash and perfect fractions and, when the run has training.deviation, collusive (games with
+    profit gain above collusive_gain), nash_collusive and perfect_collusive.  mu and lam of equilibrium_games are those
+    of deviation_games for the same run (same tables, same start prices, default horizon)."""
+    import json
+    with open(os.path.join(exp_path, "equilibrium.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["n_states"] = int(desc["n_states"])
+    df["tol"] = float(desc["options"]["tol"])
+    return df
+
+
+def equilibrium_games(exp_path, agent=0):
+    """Per-game results of the equilibrium check for `agent`, one row per game indexed by its GLOBAL id: mu, lam,
+    iters, n_diff_all, n_diff_on, loss_all, loss_on, loss_all_mean, loss_on_mean, v_on, and the flags br_on, br_all
+    (this agent) and nash, perfect (all solved agents) at the run's tol.  Reads exp_path's eq_*.npy, or those of
+    exp_path/shard*/ in game order.  mu and lam equal deviation_games' for the same run."""
+    import glob
+    import json
+    from th_rl_amd import equilibrium as eq
+    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "eq_cycle.npy")) else \
+        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "eq_cycle.npy"))),
+               key=lambda d: int(os.path.basename(d)[5:]))
+    if not dirs:
+        raise KeyError("no equilibrium check (eq_cycle.npy) under %s (training.equilibrium)" % exp_path)
+    frames = []
+    for d in dirs:
+        with open(os.path.join(d, "equilibrium.json")) as f:
+            opt = json.load(f)["options"]
+        off = 0
+        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
+        if os.path.isfile(cfg_path):
+            with open(cfg_path) as f:
+                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        g = eq.load_games(d)
+        fl = eq.flags(g, opt["agents"], opt["tol"])
+        cols = {"mu": g["mu"], "lam": g["lam"]}
+        for f in eq.INT_FIELDS + eq.FLOAT_FIELDS:
+            cols[f] = g[f][int(agent)]
+        cols.update(br_on=fl["br_on"][int(agent)], br_all=fl["br_all"][int(agent)], nash=fl["nash"], perfect=fl["perfect"])
+        n = g["mu"].shape[0]
         frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
     return pandas.concat(frames)
 
