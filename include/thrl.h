@@ -610,6 +610,70 @@ typedef struct {
 } thrl_equilibrium_args;
 int thrl_equilibrium(const thrl_cfg* cfg, const void* q, const thrl_equilibrium_args* args, void* stream);
 
+/*
+ * Cross-play: greedy play between agents of DIFFERENT games (Eschenbaum, Mellgren, Zahn, "Robust algorithmic
+ * collusion", 2022): seat agent 0 of one game against agent 1 of another, which never met in training, and find
+ * the limit cycle of their greedy play.  No reference counterpart.  QTable agents only, no env noise (intercept
+ * env_a); q, and everything else of the batch, is read only.
+ *
+ * G = args.n_games: the first n_games games of q (1 <= G <= cfg.n_games).  M = args.n_matches >= 1 matches; every
+ * [.][M] array here is indexed by match.  seat (device int32 [N][M]): in match m, seat i is taken by AGENT i OF GAME
+ * seat[i][m].  Roles are kept -- agents may have different grids, so seat i always plays from an agent-i table.
+ * Identity seats (M = G, seat[i][m] = m) give thrl_deviation's pre-shock cycle of every game.
+ *
+ * Greedy map F of match m on row tuples x = (row_0 .. row_{N-1}): a_i = argmax_row of row x_i of agent i's table in
+ * q[seat[i][m]] (first maximum under strict >), then exactly thrl_deviation's F: scale_action and env_step with NO
+ * env noise give the price p and the rewards, F(x)_i = encode64_i(p).  The reward and scaled action "at x" are those
+ * of the transition taken at x.
+ *
+ * Start state x_0 = (encode64_i(state0[m]))_i.  (mu, lam), s*, cycle_reward and cycle_action are thrl_deviation's,
+ * word for word: mu >= 0, lam >= 1 the smallest values with x_{mu+lam} = x_mu; the cycle is found iff
+ * mu + lam <= H (horizon), then s* = x_mu; otherwise lam = 0 and mu = H.  Cycle detection keeps O(1) state per match
+ * (Brent) with a step budget that decides "found" exactly by mu + lam <= H.
+ *   cycle_reward[i][m] = (sum_{j<lam} reward_i at F^j(s*), added in that order from 0.0) / lam, cycle_action the same
+ *   for the scaled action; both 0 when lam = 0.
+ * Rows reward_rows / action_rows [row_count][N][M] (each optional) hold, for tau in [row_begin, row_begin + row_count)
+ * inside [0, n_steps), the rewards and scaled actions of the transition taken at x_tau -- the path from x_0, before
+ * and on the cycle: the layout of the episode rows, so thrl_group_stats reduces them as they are (E = row_count,
+ * G = M).  All arithmetic is float64, every operation rounded once, in thrl_deviation's order.
+ *
+ * policy (device uint16 [G][P], P = sum_i (n_states_i + 1), the layout of thrl_policy_track): the matches are played
+ * from the greedy policies, not from q.  Without THRL_XPLAY_POLICY_GIVEN the call first fills policy[g] for every
+ * g < G from q (one streaming pass; the array thrl_policy_track writes with THRL_TRACK_BASELINE) and then plays;
+ * with the flag it plays from what policy holds and q may be NULL.  So a caller extracts once and plays any number
+ * of re-pairings, and the policy array of a convergence tracker can be played as it is.  Entries that are no action
+ * of their agent are the caller's to avoid (they are clamped to the last action, nothing is read out of bounds).
+ *
+ * A seat outside [0, G) is device data the host cannot see: that match reads nothing and gets mu = -1, lam = 0 and
+ * zeros in cycle_reward, cycle_action and its rows.  No other match is affected.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_matches < 1, n_games outside [1, cfg.n_games], horizon outside
+ * [1, THRL_DEV_MAX_HORIZON], n_steps outside [0, THRL_DEV_MAX_STEPS], a row range outside [0, n_steps), a flag other
+ * than THRL_XPLAY_POLICY_GIVEN or an agent with more than 65,536 actions; THRL_ERR_NULL for a missing seat, state0,
+ * policy, mu, lam, cycle_reward or cycle_action, or a missing q without THRL_XPLAY_POLICY_GIVEN.
+ */
+#define THRL_XPLAY_POLICY_GIVEN 1
+typedef struct {
+    int32_t n_games;                 /* G in [1, cfg.n_games]: games of q / policy       */
+    int32_t n_matches;               /* M >= 1                                           */
+    int32_t n_steps;                 /* K in [0, THRL_DEV_MAX_STEPS]: length of the path the rows are cut from */
+    int32_t horizon;                 /* H >= 1 (th_rl_amd: min(prod_i n_actions_i + 1, 65536)) */
+    int32_t row_begin;               /* rows stored: tau in [row_begin, row_begin + row_count) */
+    int32_t row_count;
+    int32_t flags;                   /* 0 or THRL_XPLAY_POLICY_GIVEN                     */
+    int32_t reserved;                /* 0                                                */
+    const int32_t* seat;             /* device [N][M]: game whose agent i sits in match m */
+    const double* state0;            /* device [M] start prices                          */
+    uint16_t* policy;                /* device [G][P]: out without the flag, in with it  */
+    int32_t* mu;                     /* device outputs [M]                               */
+    int32_t* lam;
+    double*  cycle_reward;           /* device [N][M]                                    */
+    double*  cycle_action;           /* device [N][M]                                    */
+    double*  reward_rows;            /* device [row_count][N][M] or NULL                 */
+    double*  action_rows;            /* device [row_count][N][M] or NULL                 */
+} thrl_crossplay_args;
+int thrl_crossplay(const thrl_cfg* cfg, const void* q, const thrl_crossplay_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

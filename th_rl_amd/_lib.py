@@ -142,6 +142,22 @@ class EquilibriumArgs(ctypes.Structure):
     ]
 
 
+XPLAY_POLICY_GIVEN = 1
+
+
+class CrossplayArgs(ctypes.Structure):
+    """thrl_crossplay_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_matches", ctypes.c_int32), ("n_steps", ctypes.c_int32),
+        ("horizon", ctypes.c_int32), ("row_begin", ctypes.c_int32), ("row_count", ctypes.c_int32),
+        ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("seat", ctypes.c_void_p), ("state0", ctypes.c_void_p), ("policy", ctypes.c_void_p),
+        ("mu", ctypes.c_void_p), ("lam", ctypes.c_void_p),
+        ("cycle_reward", ctypes.c_void_p), ("cycle_action", ctypes.c_void_p),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -151,7 +167,7 @@ SYMBOLS = [
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
-    "thrl_policy_track", "thrl_equilibrium",
+    "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay",
 ]
 CAC_PARAMS = 1283
 
@@ -256,6 +272,8 @@ def load():
     L.thrl_policy_track.argtypes = [cfgp, vp, ctypes.POINTER(PolicyTrackArgs), vp]
     L.thrl_equilibrium.restype = ctypes.c_int
     L.thrl_equilibrium.argtypes = [cfgp, vp, ctypes.POINTER(EquilibriumArgs), vp]
+    L.thrl_crossplay.restype = ctypes.c_int
+    L.thrl_crossplay.argtypes = [cfgp, vp, ctypes.POINTER(CrossplayArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -300,6 +300,23 @@ class GameBatch:
             raise ThrlError("GameBatch: call init_tables() or set_tables() first")
         return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
 
+    def crossplay(self, seats, steps=0, horizon=None, state0=None, rows=False, group_stats=None, q=None, policy=None,
+                  budget=None):
+        """Cross-play of the greedy policies (thrl_crossplay; definitions in include/thrl.h): in match m of a round
+        `seats` (int [N, M], or a list of rounds, e.g. crossplay.pairings) seat i is taken by agent i of game
+        seats[i][m]; returns mu, lam [M] and cycle_reward / cycle_action [N, M] of the cycle their greedy play ends in
+        (a leading round axis for a list), from the start prices state0 [M] (default: the state of seat 0's game).
+        Every game's greedy policy is extracted once and all rounds are played from it; policy (a device [G, P]
+        16-bit tensor such as a convergence tracker's) is played as it is.  steps K > 0 with rows=True adds the path's
+        reward_rows / action_rows [K, N, M]; group_stats (a GroupSpec with G = M) pools the rows of all rounds on the
+        device.  Identity seats give GameBatch.deviation's mu, lam, cycle_reward, cycle_action.  Tables, counters,
+        state, epsilon and the episode index are not touched."""
+        from . import crossplay as xp
+        if not self.initialized:
+            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
+        return xp.run(self, seats, steps=steps, horizon=horizon, state0=state0, rows=rows, group_stats=group_stats,
+                      q=q, policy=policy, budget=budget or xp.ROW_BUDGET)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
         its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.

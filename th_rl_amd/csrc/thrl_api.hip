@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "thrl_converge.h"
+#include "thrl_crossplay.h"
 #include "thrl_deviation.h"
 #include "thrl_equilibrium.h"
 #include "thrl_kernels.h"
@@ -101,6 +102,30 @@ void fill_agents(const thrl_cfg* c, AgentParams* ag, EnvParams* env) {
     if (env) {
         env->a = c->env_a; env->b = c->env_b; env->ratio = c->env_a / c->env_b;
         env->noise_prob = c->noise_prob; env->noise_lo = c->env_a * 0.7;
+    }
+}
+
+// Rows reachable after a transition, per agent [lo, hi]: the price is monotone in every agent's action index (scale,
+// the products, the sum, b * Q and a - b * Q are monotone roundings, the clamp at 0 too), and so is encode64, so the
+// extremes of every agent's next row lie at the 2^N corners of the action grid.
+void reach_window(const thrl_cfg* c, int* lo, int* hi) {
+    const int N = c->n_agents;
+    for (int i = 0; i < N; i++) { lo[i] = c->n_states[i]; hi[i] = 0; }
+    const double ratio = c->env_a / c->env_b;
+    for (int mask = 0; mask < (1 << N); mask++) {
+        double Q = 0.0;
+        for (int j = 0; j < N; j++) {
+            const double A = ratio * h_scale((mask >> j) & 1 ? c->n_actions[j] - 1 : 0, c, j);
+            Q = Q + A;
+        }
+        double p = c->env_a - c->env_b * Q;
+        if (!(p > 0.0)) p = 0.0;
+        for (int i = 0; i < N; i++) {
+            int r = h_encode64(p, c, i);
+            r = r < 0 ? 0 : (r > c->n_states[i] ? c->n_states[i] : r);
+            if (r < lo[i]) lo[i] = r;
+            if (r > hi[i]) hi[i] = r;
+        }
     }
 }
 
@@ -1336,27 +1361,8 @@ int thrl_deviation(const thrl_cfg* c, const void* q, const thrl_deviation_args* 
     a.dev_action = x->dev_action; a.row_begin = x->row_begin; a.row_count = x->row_count;
     a.stride = (int64_t)thrl_table_stride(c);
     fill_agents(c, a.ag, &a.env);
-    // Rows reachable after a transition: the price is monotone in every agent's action index (scale, the
-    // products, the sum, b * Q and a - b * Q are monotone roundings, the clamp at 0 too), and so is encode64, so
-    // the extremes of every agent's next row lie at the 2^N corners of the action grid.
     int lo[THRL_MAXA], hi[THRL_MAXA];
-    for (int i = 0; i < N; i++) { lo[i] = c->n_states[i]; hi[i] = 0; }
-    const double ratio = c->env_a / c->env_b;
-    for (int mask = 0; mask < (1 << N); mask++) {
-        double Q = 0.0;
-        for (int j = 0; j < N; j++) {
-            const double A = ratio * h_scale((mask >> j) & 1 ? c->n_actions[j] - 1 : 0, c, j);
-            Q = Q + A;
-        }
-        double p = c->env_a - c->env_b * Q;
-        if (!(p > 0.0)) p = 0.0;
-        for (int i = 0; i < N; i++) {
-            int r = h_encode64(p, c, i);
-            r = r < 0 ? 0 : (r > c->n_states[i] ? c->n_states[i] : r);
-            if (r < lo[i]) lo[i] = r;
-            if (r > hi[i]) hi[i] = r;
-        }
-    }
+    reach_window(c, lo, hi);
     int entries = 0, lut_n = 0, max_a = 0;
     for (int i = 0; i < N; i++) {
         a.win_lo[i] = lo[i];
@@ -1433,6 +1439,99 @@ int thrl_policy_track(const thrl_cfg* c, const void* q, const thrl_policy_track_
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_policy_track(a, c->q_dtype, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_policy_track launch") : THRL_OK;
+}
+
+int thrl_crossplay(const thrl_cfg* c, const void* q, const thrl_crossplay_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_matches < 1) return fail(THRL_ERR_BAD_CONFIG, "n_matches=%d must be >= 1", x->n_matches);
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->horizon < 1 || x->horizon > THRL_DEV_MAX_HORIZON)
+        return fail(THRL_ERR_BAD_CONFIG, "horizon=%d out of [1,%d]", x->horizon, THRL_DEV_MAX_HORIZON);
+    if (x->n_steps < 0 || x->n_steps > THRL_DEV_MAX_STEPS)
+        return fail(THRL_ERR_BAD_CONFIG, "n_steps=%d out of [0,%d]", x->n_steps, THRL_DEV_MAX_STEPS);
+    if (x->row_begin < 0 || x->row_count < 0 || (int64_t)x->row_begin + x->row_count > x->n_steps)
+        return fail(THRL_ERR_BAD_CONFIG, "rows [%d, %d + %d) outside [0, n_steps=%d)", x->row_begin, x->row_begin,
+                    x->row_count, x->n_steps);
+    if (x->flags & ~THRL_XPLAY_POLICY_GIVEN) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    // validate() caps every agent at 32,000 actions, so each greedy action fits a 16-bit policy entry (thrl.h's
+    // "more than 65,536 actions" is refused there, with THRL_ERR_BAD_CONFIG)
+    const bool given = (x->flags & THRL_XPLAY_POLICY_GIVEN) != 0;
+    if (!x->seat || !x->state0 || !x->policy || !x->mu || !x->lam || !x->cycle_reward || !x->cycle_action)
+        return fail(THRL_ERR_NULL, "seat / state0 / policy / mu / lam / cycle_reward / cycle_action is NULL");
+    if (!given && !q) return fail(THRL_ERR_NULL, "q is NULL without THRL_XPLAY_POLICY_GIVEN");
+    AgentParams ag[THRL_MAXA];
+    EnvParams env;
+    fill_agents(c, ag, &env);
+    int P = 0, row_off[THRL_MAXA + 1];
+    for (int i = 0; i < N; i++) { row_off[i] = P; P += ag[i].rows; }
+    row_off[N] = P;
+
+    if (!given) {       // one streaming pass over q: policy[g] for every g < G
+        XpExtractArgs e;
+        memset(&e, 0, sizeof(e));
+        e.G = x->n_games; e.N = N; e.P = P;
+        e.stride = (int64_t)thrl_table_stride(c);
+        for (int i = 0; i < N; i++) {
+            e.row_off[i] = row_off[i];
+            e.table_off[i] = ag[i].table_off;
+            e.n_actions[i] = ag[i].n_actions;
+        }
+        e.row_off[N] = P;
+        // the staged window: the game's block widened to 16-byte chunks at both ends
+        const int64_t esz = c->q_dtype == 1 ? 8 : 4, vec = 16 / esz;
+        const int64_t lds = ((e.stride + 2 * vec) * esz + 15) & ~(int64_t)15;
+        e.staged = lds <= kXpExtractLdsBudget && ((uintptr_t)q & 15) == 0;
+        e.lds_bytes = e.staged ? (int32_t)lds : 0;
+        e.q = q; e.policy = x->policy;
+        // enough one-wave blocks to fill every CU as far as LDS allows, each looping over games
+        int dev = 0, cus = 0, lds_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess
+            || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+            || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+            return hip_fail((int)hipGetLastError(), "device attributes");
+        int per_cu = kXpExtractMaxBlocksPerCu;
+        if (e.staged && lds_cu > 0 && lds_cu / e.lds_bytes < per_cu) per_cu = lds_cu / e.lds_bytes > 0 ? lds_cu / e.lds_bytes : 1;
+        const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+        const int grid = (int)(want < e.G ? want : e.G);
+        const int err = thrl::launch_xplay_extract(e, c->q_dtype, grid, (hipStream_t)stream);
+        if (err) return hip_fail(err, "k_xplay_extract launch");
+    }
+
+    XpWalkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.M = x->n_matches; a.N = N; a.P = P; a.H = x->horizon; a.K = x->n_steps;
+    a.row_begin = x->row_begin; a.row_count = x->row_count;
+    a.env = env;
+    int lo[THRL_MAXA], hi[THRL_MAXA];
+    reach_window(c, lo, hi);
+    int entries = 0, lut_n = 0;
+    for (int i = 0; i < N; i++) {
+        a.ag[i] = ag[i];
+        a.row_off[i] = row_off[i];
+        a.win_lo[i] = lo[i];
+        a.win_n[i] = hi[i] - lo[i] + 1;
+        a.pol_off[i] = entries;
+        entries += a.win_n[i] + 1;                   // + x_0's row
+        a.lut_off[i] = lut_n;
+        lut_n += c->n_actions[i];
+    }
+    a.pol_off[N] = entries;
+    a.pol_entries = entries;
+    a.lut_n = lut_n;
+    a.use_lut = lut_n <= kDevMaxLut;
+    const int64_t lut_bytes = a.use_lut ? (int64_t)((lut_n * 8 + 15) & ~15) : 0;
+    const int64_t lds = lut_bytes + (int64_t)kXpTile * entries * 2;
+    a.staged = lds <= kXpLdsBudget;
+    a.lds_bytes = (int32_t)(a.staged ? lds : lut_bytes);
+    a.policy = x->policy; a.seat = x->seat; a.state0 = x->state0;
+    a.mu = x->mu; a.lam = x->lam; a.cycle_reward = x->cycle_reward; a.cycle_action = x->cycle_action;
+    a.reward_rows = x->reward_rows; a.action_rows = x->action_rows;
+    const int e = thrl::launch_xplay_walk(a, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_xplay_walk launch") : THRL_OK;
 }
 
 }  // extern "C"

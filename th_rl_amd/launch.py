@@ -16,7 +16,10 @@ groups.json / group_*.npy (merge_group_stats); with training.deviation every sha
 arrays, rank 0 merges the dev<d>_* statistics the same way and writes the top-level deviation.json (merge_deviation);
 with training.equilibrium rank 0 concatenates the shards' eq_*.npy and writes equilibrium.json (merge_equilibrium);
 with training.convergence every shard writes its per-game convergence arrays and rank 0 writes the top-level
-convergence.json and conv_*.npy (merge_convergence).  A convergence stop counts the games of every rank (the trainer
+convergence.json and conv_*.npy (merge_convergence); with training.crossplay every shard draws its partners INSIDE the
+shard (the tables of other ranks are not fetched, so a sharded run's pairings are not the unsharded run's) and saves
+the seats as global game ids; rank 0 concatenates the shards' xplay_*.npy along the game axis and writes the top-level
+crossplay.json (merge_crossplay).  A convergence stop counts the games of every rank (the trainer
 all-reduces over the gloo group), so all ranks stop at the same episode.
 """
 import argparse
@@ -66,7 +69,7 @@ def shard_training(config, rank, world):
         opt.update(histograms=True, n_max=int(numpy.bincount(ids, minlength=n_groups).max()))
         training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
     dv = training.get("deviation")
-    cv = training.get("convergence") or training.get("equilibrium")
+    cv = training.get("convergence") or training.get("equilibrium") or training.get("crossplay")
     if ((dv is not None and dv is not False) or (cv is not None and cv is not False)) and (gs is None or gs is False):
         # the per-group summaries of each shard's deviation.json / convergence.json use the global group ids too
         from th_rl_amd.group_stats import assign_groups
@@ -105,6 +108,11 @@ def merge_group_stats(config, out, world):
     if dv is not None and dv is not False:
         from th_rl_amd.deviation import parse_options as deviation_options
         prefixes += ["dev%d" % d for d in deviation_options(dv, config)["agents"]]
+    xp = training.get("crossplay")
+    if xp is not None and xp is not False:
+        from th_rl_amd.crossplay import parse_options as crossplay_options
+        if crossplay_options(xp, config)["steps"] > 0:
+            prefixes.append("xplay")
     for prefix in prefixes:
         parts = []
         for d in shards:
@@ -166,6 +174,33 @@ def merge_equilibrium(config, out, world):
         delta = numpy.concatenate(deltas)
     summary = eq.summarize(games, ids, n_groups, opt["agents"], opt["tol"], delta)
     eq.save_json(os.path.join(out, "equilibrium.json"), eq.describe(opt, first["n_states"], summary))
+
+
+def merge_crossplay(config, out, world):
+    """Rank 0: the top-level crossplay.json and xplay_*.npy of a sharded run: the shards' arrays concatenated along
+    the game axis (crossplay.combine) and summarised as one run.  Every shard drew its partners INSIDE the shard -- the
+    tables of other ranks are not fetched -- so these are not the pairings of the unsharded run; the saved seats are
+    global game ids, so the merged files say who met whom."""
+    from th_rl_amd import crossplay as xp
+    from th_rl_amd.group_stats import assign_groups
+    training = config.get("training", {})
+    total = int(training.get("n_games", world))
+    opt = xp.parse_options(training["crossplay"], config)
+    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                     n_groups=training.get("n_groups"))
+    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
+    loaded = [xp.load_games(s) for s in shards]
+    games, self_play = xp.combine(g for g, _ in loaded), xp.combine(s for _, s in loaded)
+    xp.save_games(out, games, self_play)
+    with open(os.path.join(shards[0], "crossplay.json")) as f:
+        first = json.load(f)
+    for k in ("horizon_used", "rounds_played", "tables"):
+        if k in first["options"]:
+            opt[k] = first["options"][k]
+    nash, cartel = xp.optimal(config)
+    summary = xp.summarize(xp.local_seats(games, int(training.get("game_offset", 0))), self_play, ids, n_groups,
+                           nash, cartel)
+    xp.save_json(os.path.join(out, "crossplay.json"), xp.describe(opt, nash, cartel, summary))
 
 
 def merge_convergence(config, out, world):
@@ -243,6 +278,8 @@ def _worker(rank, world, port, config, out, devices_available):
             merge_convergence(config, out, world)
         if training.get("equilibrium"):
             merge_equilibrium(config, out, world)
+        if training.get("crossplay"):
+            merge_crossplay(config, out, world)
     dist.destroy_process_group()
 
 

@@ -276,6 +276,18 @@ class MixedGameBatch:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
         return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
 
+    def crossplay(self, seats, steps=0, horizon=None, state0=None, rows=False, group_stats=None, q=None, policy=None,
+                  budget=None):
+        """GameBatch.crossplay for an all-QTable batch (the same table layout).  A batch with a neural agent raises
+        ThrlError."""
+        from . import crossplay as xp
+        if any(k != "QTable" for k in self.kinds):
+            raise ThrlError("MixedGameBatch.crossplay: agents %s: %s" % (self.kinds, xp.NEURAL_FOLLOW_UP))
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return xp.run(self, seats, steps=steps, horizon=horizon, state0=state0, rows=rows, group_stats=group_stats,
+                      q=q, policy=policy, budget=budget or xp.ROW_BUDGET)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

@@ -29,6 +29,15 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                  "equilibrium": null,  # true or {"agents": [all], "tol": 0.0, "policies": false, "tables": "final"}: after
                                        # training (and the deviation analysis) the equilibrium check of the greedy
                                        # strategies (equilibrium.py, QTable agents only): equilibrium.json, eq_*.npy
+                 "crossplay": null,  # true or {"rounds": 8, "scheme": "rotate" | "random", "against": "own" | "all",
+                                     # "steps": 0, "horizon": null, "seed": 0, "tables": "final" | "converged"}: after
+                                     # training (and the equilibrium check) greedy play between agents of DIFFERENT
+                                     # games (crossplay.py, QTable agents only): crossplay.json (options, Nash, Cartel,
+                                     # per-(group, partner group) summary), xplay_seats.npy int32 [rounds, N, G] (global
+                                     # game ids), xplay_cycle.npy int32 [rounds, 2, G] (mu, lam), xplay_cycle_reward /
+                                     # xplay_cycle_action.npy [rounds, N, G], xplay_self_cycle.npy [2, G] and
+                                     # xplay_self_reward.npy [N, G] (each game's own cycle); with group_stats and
+                                     # steps > 0 the path rows pooled over the rounds, xplay_*.npy [steps, ...]
                  "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
                                      # "horizon": null}: after training (and the greedy statistics) the deviation
                                      # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json
@@ -234,6 +243,12 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         eq_opt = equilibrium_options(training["equilibrium"], config)     # refuses neural agents and gamma >= 1
     if eq_opt is not None and eq_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
         raise ValueError('training.equilibrium.tables = "converged" needs training.convergence with "snapshot": true')
+    xp_opt = None
+    if training.get("crossplay") is not None and training.get("crossplay") is not False:
+        from th_rl_amd.crossplay import parse_options as crossplay_options
+        xp_opt = crossplay_options(training["crossplay"], config)         # refuses neural agents before training
+    if xp_opt is not None and xp_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
+        raise ValueError('training.crossplay.tables = "converged" needs training.convergence with "snapshot": true')
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -314,6 +329,12 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         keep = None
 
     spec, gs_opt = group_spec_of(config, training, n_games)
+    if spec is not None and xp_opt is not None and xp_opt["steps"] > 0:
+        from th_rl_amd.crossplay import MAX_POOLED_ROUNDS
+        n_rounds = xp_opt["rounds"] * (spec.n_groups if xp_opt["against"] == "all" else 1)
+        if n_rounds > MAX_POOLED_ROUNDS:
+            raise ValueError("training.crossplay: group_stats pools the rows of at most %d rounds, this run has %d"
+                             % (MAX_POOLED_ROUNDS, n_rounds))
     if spec is not None:
         from th_rl_amd.group_stats import save_json
         save_json(os.path.join(exp_path, "groups.json"), spec.describe())
@@ -460,6 +481,22 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             if eq_opt["tables"] == "converged":
                 q_eq, s_eq = tracker.tables_at_convergence()
         write_equilibrium(exp_path, batch, config, eq_opt, ids, n_groups, q=q_eq, state0=s_eq)
+
+    if xp_opt is not None:      # do the greedy policies survive a change of partner (crossplay.py)
+        from th_rl_amd.crossplay import write_artefacts as write_crossplay
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        q_xp = s_xp = None
+        if tracker is not None:
+            xp_opt = dict(xp_opt, tables=xp_opt.get("tables", "final"))
+            if xp_opt["tables"] == "converged":
+                q_xp, s_xp = tracker.tables_at_convergence()
+        write_crossplay(exp_path, batch, config, xp_opt, ids, n_groups, spec=spec,
+                        histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET, q=q_xp, state0=s_xp)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

@@ -237,6 +237,61 @@ def equilibrium_games(exp_path, agent=0):
     return pandas.concat(frames)
 
 
+def crossplay_summary(exp_path):
+    """A run's cross-play (training.crossplay): crossplay.json's summary as a DataFrame with one row per (group of
+    seat 0, partner_group) -- matches, cycles, fixed_points, the cross-play profit gain's mean and quantiles (delta_*),
+    delta_self_mean (the same games in self-play), retained, seat_gain_<i> and one lam_<bin> column per bin of the lam
+    histogram -- plus Nash and Cartel.  In a sharded run the partners were drawn inside each shard."""
+    import json
+    with open(os.path.join(exp_path, "crossplay.json")) as f:
+        desc = json.load(f)
+    rows = []
+    for r in desc["summary"]:
+        r = dict(r)
+        for name, n in zip(desc["lam_bins"], r.pop("lam_hist")):
+            r["lam_" + name] = n
+        for i, v in enumerate(r.pop("seat_gain")):
+            r["seat_gain_%d" % i] = v
+        rows.append(r)
+    df = pandas.DataFrame(rows)
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def crossplay_games(exp_path, round=0):
+    """Per-match results of cross-play round `round`, one row per match indexed by the GLOBAL id of seat 0's game: seat_<i>
+    (global game ids), self_seat, mu, lam, cycle_reward_<i> / cycle_action_<i>, the profit gain delta, and the same
+    game's self-play lam_self and delta_self.  Reads exp_path's xplay_*.npy, or those of exp_path/shard*/
+    (th_rl_amd.launch writes one set per rank) in game order."""
+    import glob
+    import json
+    from th_rl_amd import crossplay as xp
+    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "xplay_cycle.npy")) else \
+        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "xplay_cycle.npy"))),
+               key=lambda d: int(os.path.basename(d)[5:]))
+    if not dirs:
+        raise KeyError("no cross-play (xplay_cycle.npy) under %s (training.crossplay)" % exp_path)
+    frames = []
+    for d in dirs:
+        with open(os.path.join(d, "crossplay.json")) as f:
+            desc = json.load(f)
+        g, sp = xp.load_games(d)
+        r = int(round)
+        if not 0 <= r < g["seats"].shape[0]:
+            raise KeyError("round %d out of [0, %d)" % (r, g["seats"].shape[0]))
+        seats = g["seats"][r]
+        cols = {"seat_%d" % i: seats[i] for i in range(seats.shape[0])}
+        cols.update(self_seat=xp.self_seat(seats), mu=g["mu"][r], lam=g["lam"][r])
+        for i in range(seats.shape[0]):
+            cols["cycle_reward_%d" % i] = g["cycle_reward"][r, i]
+            cols["cycle_action_%d" % i] = g["cycle_action"][r, i]
+        cols["delta"] = xp.profit_gain(g["cycle_reward"][r], desc["nash"], desc["cartel"])
+        cols["lam_self"] = sp["lam"]
+        cols["delta_self"] = xp.profit_gain(sp["cycle_reward"], desc["nash"], desc["cartel"])
+        frames.append(pandas.DataFrame(cols, index=pandas.Index(seats[0], name="game")))
+    return pandas.concat(frames)
+
+
 def convergence_summary(exp_path):
     """A run's convergence (training.convergence): convergence.json's summary as a DataFrame with one row per group --
     games, converged, fraction, converged_at_mean / q25 / q50 / q75, conv_since_mean / q25 / q50 / q75 (over the
