@@ -359,6 +359,26 @@ typedef struct {
     float*   policy_tab;
     size_t   policy_tab_bytes;
     int32_t  flags;                      /* THRL_MIXED_* */
+    /* Parity mode (optional; all five NULL = Philox draws and sampled neural play): the reference's recorded draws
+     * and sampled actions, for the run->n_episodes episodes of this call.  inj_u / inj_choice / inj_noise_u /
+     * inj_noise_a have the meaning and layout of the fields of thrl_buffers; inj_action is the action index a
+     * Reinforce / ActorCritic agent's sample_action returned at that step (agents.py:160-163, 270-273), so the
+     * float32 rounding of the policy cannot fork the trajectory: prices, rewards, replay rings and the QTable
+     * agents' tables and counters are then the reference's exactly, both fused kernels skip the policy (the update
+     * kernels recompute it from the replayed buffer).  Entries of inj_u / inj_choice that belong to a neural agent
+     * and entries of inj_action that belong to a QTable agent are not read.
+     * All or nothing: every stream the game consumes must be given -- inj_u and inj_choice with a QTable agent in
+     * the game, inj_action with a Reinforce / ActorCritic agent, inj_noise_u and inj_noise_a with
+     * cfg.noise_prob > 0 -- otherwise THRL_ERR_BAD_CONFIG.  An injected choice or action outside [0, n_actions) is
+     * device data the host cannot see: it is clamped to the last action (thrl_crossplay's rule for policy entries),
+     * nothing is read or written out of bounds.  A game with a CAC agent is THRL_ERR_UNSUPPORTED under injection:
+     * its action is a float, and the reference's play path for it cannot run (see thrl_cac_act).  Per-game sweeps
+     * combine with injection as in thrl_qtable_episodes. */
+    const double* inj_u;                 /* device [n_episodes][T][N][G] random.uniform(0,1) (agents.py:81)   */
+    const int8_t* inj_choice;            /* device [n_episodes][T][N][G] random.choice idx   (agents.py:82)   */
+    const double* inj_noise_u;           /* device [n_episodes][T][G]    (environments.py:28)                 */
+    const double* inj_noise_a;           /* device [n_episodes][T][G]    (environments.py:29)                 */
+    const int8_t* inj_action;            /* device [n_episodes][T][N][G] Categorical.sample().item()          */
 } thrl_mixed;
 /* Two-agent games whose neural agents are discrete run on the tuple-chain kernel (the state is carried as the action pair of
  * the last step, or as its price after a step with a redrawn intercept; needs policy_tab; per-game sweeps are taken): same

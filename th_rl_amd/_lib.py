@@ -16,6 +16,7 @@ ABI_VERSION = 3
 class ThrlError(RuntimeError):
     code = None             # the negative thrl_err when the error came from the library
 
+ERR_BAD_CONFIG = -1
 ERR_UNSUPPORTED = -3
 
 
@@ -73,6 +74,9 @@ class Mixed(ctypes.Structure):
         ("sweep_eps_end", ctypes.c_void_p), ("sweep_eps_step", ctypes.c_void_p),
         ("sweep_eps", ctypes.c_void_p), ("sweep_noise_prob", ctypes.c_void_p),
         ("policy_tab", ctypes.c_void_p), ("policy_tab_bytes", ctypes.c_size_t), ("flags", ctypes.c_int32),
+        # parity mode: recorded draws and sampled actions (device pointers, all None = Philox)
+        ("inj_u", ctypes.c_void_p), ("inj_choice", ctypes.c_void_p), ("inj_noise_u", ctypes.c_void_p),
+        ("inj_noise_a", ctypes.c_void_p), ("inj_action", ctypes.c_void_p),
     ]
 
 

@@ -1148,6 +1148,25 @@ int thrl_mixed_episodes(const thrl_cfg* c, thrl_mixed* mx, void* q, int32_t* cou
         return fail(THRL_ERR_BAD_CONFIG, "sweep_noise_prob needs cfg.noise_prob > 0 (it switches the noise draws on)");
     a.sw_gamma = mx->sweep_gamma; a.sw_alpha = mx->sweep_alpha; a.sw_eps_end = mx->sweep_eps_end;
     a.sw_eps_step = mx->sweep_eps_step; a.sw_eps = mx->sweep_eps; a.sw_noise_prob = mx->sweep_noise_prob;
+    // ---- parity mode: all or nothing -- every stream this game consumes must be given
+    const bool injected = mx->inj_u || mx->inj_choice || mx->inj_noise_u || mx->inj_noise_a || mx->inj_action;
+    if (injected) {
+        bool has_q = false, has_policy = false;
+        for (int i = 0; i < c->n_agents; i++) {
+            if (mx->kind[i] == 3)
+                return fail(THRL_ERR_UNSUPPORTED, "agent %d: a CAC agent cannot play from injected draws (its action is a float)", i);
+            if (mx->kind[i] == 0) has_q = true; else has_policy = true;
+        }
+        if (has_q && (!mx->inj_u || !mx->inj_choice))
+            return fail(THRL_ERR_BAD_CONFIG, "injection: a QTable agent needs inj_u and inj_choice");
+        if (has_policy && !mx->inj_action)
+            return fail(THRL_ERR_BAD_CONFIG, "injection: a Reinforce / ActorCritic agent needs inj_action");
+        if (c->noise_prob > 0.0 && (!mx->inj_noise_u || !mx->inj_noise_a))
+            return fail(THRL_ERR_BAD_CONFIG, "injection: noise_prob > 0 needs inj_noise_u and inj_noise_a");
+        a.inj = 1;
+        a.inj_u = mx->inj_u; a.inj_choice = mx->inj_choice; a.inj_action = mx->inj_action;
+        a.inj_noise_u = mx->inj_noise_u; a.inj_noise_a = mx->inj_noise_a;
+    }
     // ---- two-agent games with discrete policies, noise-free: the tuple-chain kernel (thrl_ptuple.hip), same results
     {
         PTuplePlan tp = plan_ptuple(c, mx);
@@ -1165,6 +1184,8 @@ int thrl_mixed_episodes(const thrl_cfg* c, thrl_mixed* mx, void* q, int32_t* cou
             t.q = q; t.counter = counter; t.state = state;
             t.sw_gamma = mx->sweep_gamma; t.sw_alpha = mx->sweep_alpha; t.sw_eps_end = mx->sweep_eps_end;
             t.sw_eps_step = mx->sweep_eps_step; t.sw_eps = mx->sweep_eps; t.sw_noise_prob = mx->sweep_noise_prob;
+            t.inj = a.inj; t.inj_u = a.inj_u; t.inj_choice = a.inj_choice; t.inj_action = a.inj_action;
+            t.inj_noise_u = a.inj_noise_u; t.inj_noise_a = a.inj_noise_a;
             unsigned char* base = (unsigned char*)mx->policy_tab;
             t.lut = base;
             t.next_game = (int32_t*)(base + kPTupleLutRegion - 64);

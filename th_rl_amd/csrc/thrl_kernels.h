@@ -172,6 +172,11 @@ struct PTupleArgs {
     double* game_reward_log; double* game_action_log;    // [n_episodes][2][G]
     int32_t* next_game;
     uint64_t seed, game_offset, first_episode;
+    // parity mode (thrl_mixed.inj_*; the INJ variants of the kernel): this launch's recorded draws [n_episodes][T][2][G]
+    // (noise [n_episodes][T][G]) and the policy agents' sampled actions [n_episodes][T][2][G]; `inj` = launch those variants
+    const double* inj_u; const int8_t* inj_choice; const double* inj_noise_u; const double* inj_noise_a;
+    const int8_t* inj_action;
+    int32_t inj;
 };
 int launch_ptuple_lut(const PTupleArgs& a, unsigned char* out, hipStream_t s);
 int launch_ptuple(const PTupleArgs& a, int q_dtype, int grid, int block, size_t lds_bytes, hipStream_t s);
@@ -266,6 +271,11 @@ struct MixedArgs {
     // per-game sweeps of the QTable agents / the env (null = the scalars above), [N][G] except noise_prob [G]
     const double* sw_gamma; const double* sw_alpha; const double* sw_eps_end; const double* sw_eps_step;
     double* sw_eps; const double* sw_noise_prob;
+    // parity mode (thrl_mixed.inj_*; the INJ variants of the kernel): this launch's recorded draws [n_episodes][T][N][G]
+    // (noise [n_episodes][T][G]) and the discrete neural agents' sampled actions [n_episodes][T][N][G]
+    const double* inj_u; const int8_t* inj_choice; const double* inj_noise_u; const double* inj_noise_a;
+    const int8_t* inj_action;
+    int32_t inj;
 };
 // fills n_r / ragent / lds_off / lds_bytes; returns 0 or -1 with a reason when the config does not fit
 int plan_mixed(MixedArgs& a, int q_dtype, const char** why);

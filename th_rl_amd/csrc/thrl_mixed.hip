@@ -38,7 +38,13 @@ template <> __device__ __forceinline__ double neg_inf<double>() { return -(doubl
 // Draw layout: one Philox batch covers 16 steps x 4 agent pairs, lane = pair * 16 + (step & 15).
 // MEMO: 0 = every step evaluates the policy; 1 = CDFs memoised in LDS by a tag search (small price grids);
 //       2 = CDFs in a per-game HBM table indexed by the ACTION TUPLE of the previous step (see below).
-template <typename T, int NR, int APAD, int NA, bool CAC, int MEMO>
+// INJ: parity mode (thrl_mixed.inj_*).  The QTable agents' uniform and random choice, the env's two noise draws and the
+//       neural agents' sampled action come from the recorded arrays; the policy is not needed for play (the update kernels
+//       recompute it from the replay ring), so the networks are not loaded and nothing is memoised (MEMO = 0).  The arrays
+//       are read 16 steps at a time in the Philox batch's lane layout (lane = pair * 16 + step), one chunk AHEAD of the
+//       chunk being played: the loads of steps t+16 .. t+31 (or of the next episode's first chunk) are issued when step t
+//       starts, so no HBM round trip sits on the step chain.  A separate instantiation: the others keep their code.
+template <typename T, int NR, int APAD, int NA, bool CAC, int MEMO, bool INJ = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NR == 1 ? 3 : (NR == 0 ? 4 : 2))))
 k_mixed_wave(const MixedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_mx[];
@@ -106,11 +112,11 @@ k_mixed_wave(const MixedArgs a) {
         for (int i = 0; i < N; i++)
             if (lane == i) { my_bp = a.buf_price[i]; my_ba = a.buf_action[i]; my_br = a.buf_reward[i]; my_bn = a.buf_nprice[i]; }
     int widx_l = cap_l > 0 ? cnt_l % cap_l : 0;
-    if (NR >= 1) {
+    if (!INJ && NR >= 1) {
         const int A = a.ag[a.ragent[0]].n_actions;
         policy_load(net0, a.nn_params[a.ragent[0]] + (int64_t)g * a.nn_stride[a.ragent[0]], A, lane);
     }
-    if (NR >= 2) {
+    if (!INJ && NR >= 2) {
         const int A = a.ag[a.ragent[1]].n_actions;
         policy_load(net1, a.nn_params[a.ragent[1]] + (int64_t)g * a.nn_stride[a.ragent[1]], A, lane);
     }
@@ -126,6 +132,33 @@ k_mixed_wave(const MixedArgs a) {
     asm volatile("" : "+s"(env_a), "+s"(env_b), "+s"(env_ratio));
     const int my_agent = lane & 31;
 
+    // INJ: this lane's (step, agent pair) of the chunk being played (ju / jn / jp) and of the chunk after it (ku / kn / kp).
+    // ju0 / ju1 = inj_u of the pair's even / odd agent, jn0 / jn1 = the env's two draws of the step (every pair holds them),
+    // jp = choice even | choice odd << 8 | action even << 16 | action odd << 24.  jq: bit h = the pair's agent 2*pair+h is a
+    // QTable (reads inj_u / inj_choice), bit 2+h = it is a discrete neural agent (reads inj_action).
+    double ju0 = 0.0, ju1 = 0.0, jn0 = 0.0, jn1 = 0.0, ku0 = 0.0, ku1 = 0.0, kn0 = 0.0, kn1 = 0.0;
+    uint32_t jp = 0u, kp = 0u;
+    int jq = 0;
+    auto inj_load = [&](int ep, int t0) {
+        ku0 = ku1 = kn0 = kn1 = 0.0; kp = 0u;
+        const int st = t0 + (lane & 15);
+        if (ep < a.n_episodes && st < Tn) {
+            const size_t f = (size_t)ep * (size_t)Tn + (size_t)st;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const size_t k = (f * (size_t)N + (size_t)((lane >> 4) * 2 + h)) * (size_t)G + (size_t)g;
+                if (jq & (1 << h)) { (h ? ku1 : ku0) = a.inj_u[k]; kp |= (uint32_t)(uint8_t)a.inj_choice[k] << (8 * h); }
+                if (jq & (4 << h)) kp |= (uint32_t)(uint8_t)a.inj_action[k] << (16 + 8 * h);
+            }
+            if (noisy) { kn0 = a.inj_noise_u[f * (size_t)G + g]; kn1 = a.inj_noise_a[f * (size_t)G + g]; }
+        }
+    };
+    if (INJ) {
+        for (int i = 0; i < N; i++)
+            if ((lane >> 4) == (i >> 1) && a.kind[i] != 3) jq |= (a.kind[i] == 0 ? 1 : 4) << (i & 1);
+        inj_load(0, 0);
+    }
+
     for (int e = 0; e < a.n_episodes; e++) {
         const uint32_t eg = (uint32_t)(a.first_episode + (uint64_t)e);
         double acc = 0.0;                          // lane i: reward log of agent i ; lane 32+i: action log
@@ -133,6 +166,12 @@ k_mixed_wave(const MixedArgs a) {
         float z_even = 0.0f, z_odd = 0.0f;         // CAC: standard normals of this lane's (step, pair)
         for (int t = 0; t < Tn; t++) {
             const int tl = t & 15;
+            if (INJ) {
+                if (tl == 0) {                     // the chunk fetched 16 steps ago becomes current; fetch the one after it
+                    ju0 = ku0; ju1 = ku1; jn0 = kn0; jn1 = kn1; jp = kp;
+                    if (t + 16 < Tn) inj_load(e, t + 16); else inj_load(e + 1, 0);
+                }
+            } else
             if (tl == 0) {                         // draws for steps t .. t+15 of every agent pair
                 xs = draw(a.seed, gid, eg, (uint32_t)(t + (lane & 15)), (uint32_t)(lane >> 4));
                 if (noisy) xn = draw(a.seed, gid, eg, (uint32_t)(t + (lane & 15)), kStreamNoise);
@@ -151,8 +190,11 @@ k_mixed_wave(const MixedArgs a) {
                 const int dl = (i >> 1) * 16 + tl;
                 const uint32_t xu = lane_u32((i & 1) ? xs.z : xs.x, dl), xc = lane_u32((i & 1) ? xs.w : xs.y, dl);
                 int aa;
-                if (u01_32(xu) < lane_f64(eps_l, i)) {
-                    aa = (int)__umulhi(xc, (uint32_t)p.n_actions);
+                // (INJ: the recorded uniform and choice; a choice that is no action of the agent is clamped to the last one)
+                const double uq = INJ ? lane_f64((i & 1) ? ju1 : ju0, dl) : u01_32(xu);
+                if (uq < lane_f64(eps_l, i)) {
+                    aa = INJ ? (int)min((lane_u32(jp, dl) >> (8 * (i & 1))) & 0xFFu, (uint32_t)(p.n_actions - 1))
+                             : (int)__umulhi(xc, (uint32_t)p.n_actions);
                 } else {
                     const int row = encode32(price, p);
                     const T v = lane < p.n_actions ? lds[a.lds_off[i] + row * p.n_actions + lane] : neg_inf<T>();
@@ -170,6 +212,12 @@ k_mixed_wave(const MixedArgs a) {
                 const int dl = (i >> 1) * 16 + tl;
                 const uint32_t xu = lane_u32((i & 1) ? xs.z : xs.x, dl);
                 const int A = a.ag[i].n_actions;
+                if (INJ) {                         // the recorded action (clamped to the last one), no policy evaluation
+                    const int aa = rfl((int)min((lane_u32(jp, dl) >> (16 + 8 * (i & 1))) & 0xFFu, (uint32_t)(A - 1)));
+                    const double sc = sc_tab[i * 64 + aa];
+                    if (my_agent == i) { act_l = aa; scaled_l = sc; }
+                    continue;
+                }
                 const float x = (float)price;
                 const unsigned key = __float_as_uint(x);
                 unsigned& tag = r == 0 ? tag0 : tag1;
@@ -226,6 +274,9 @@ k_mixed_wave(const MixedArgs a) {
             // ---- NoisyPriceState.step (environments.py:25-39)
             double a_eff = env_a;
             bool on_grid = true;
+            if (noisy && INJ) {                    // the recorded draws: environments.py:28-29
+                if (lane_f64(jn0, tl) < noise_prob_g) { a_eff = lane_f64(jn1, tl); on_grid = false; }
+            } else
             if (noisy) {
                 const uint32_t nx = lane_u32(xn.x, tl), ny = lane_u32(xn.y, tl);
                 if (u01_32(nx) < noise_prob_g) {
@@ -361,9 +412,9 @@ k_mixed_wave(const MixedArgs a) {
     if (a.sw_eps && lane < N && a.kind[lane] == 0) a.sw_eps[(size_t)lane * G + g] = eps_l;
 }
 
-template <typename T, int NR, int APAD, int NA, bool CAC, int MEMO>
+template <typename T, int NR, int APAD, int NA, bool CAC, int MEMO, bool INJ = false>
 int launch_cac(const MixedArgs& a, hipStream_t s) {
-    auto kern = k_mixed_wave<T, NR, APAD, NA, CAC, MEMO>;
+    auto kern = k_mixed_wave<T, NR, APAD, NA, CAC, MEMO, INJ>;
     if (a.lds_bytes > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            a.lds_bytes);
@@ -386,6 +437,10 @@ template <typename T, int NA>
 int launch_na(const MixedArgs& a, hipStream_t s) {
     int amax = 0;
     for (int r = 0; r < a.n_r; r++) amax = a.ag[a.ragent[r]].n_actions > amax ? a.ag[a.ragent[r]].n_actions : amax;
+    if (a.inj) {                            // parity mode: no policy in the kernel, so one variant per number of neural agents
+        if (a.n_r == 0) return launch_cac<T, 0, 24, NA, false, 0, true>(a, s);
+        return a.n_r == 1 ? launch_cac<T, 1, 24, NA, false, 0, true>(a, s) : launch_cac<T, 2, 24, NA, false, 0, true>(a, s);
+    }
     if (a.n_r == 0) return launch_one<T, 0, 24, NA>(a, s);
     if (a.n_r == 1) return amax <= 24 ? launch_one<T, 1, 24, NA>(a, s) : launch_one<T, 1, 32, NA>(a, s);
     return amax <= 24 ? launch_one<T, 2, 24, NA>(a, s) : launch_one<T, 2, 32, NA>(a, s);

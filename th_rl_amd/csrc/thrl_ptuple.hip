@@ -45,7 +45,12 @@ __device__ __forceinline__ uint32_t wrlane(uint32_t old, uint32_t val, int lane)
 
 // T: table dtype; NR: number of policy agents (1: the other agent is a QTable; 2: none is); APAD: padded action count of the
 // CDF rows; NSEG: 64-step segments per episode; TLDS: CDF tables in LDS (else HBM scratch)
-template <typename QT, int NR, int APAD, int NSEG, bool TLDS, bool NOISE, bool SWEEP>
+// INJ: parity mode (thrl_mixed.inj_*): the QTable agent's uniform and random choice, the env's noise draws and the policy
+// agents' sampled actions of an episode are read from the recorded arrays in phase (c), lane = step, i.e. a whole episode
+// ahead of the serial chain, which then takes them with v_readlane as it takes the Philox draws.  The policies are not
+// needed for play (the update kernels recompute them from the rings): no network is loaded, no CDF row is filled.
+// Separate instantiations (compiled with the noise path, which is inert at noise_prob = 0): the others keep their code.
+template <typename QT, int NR, int APAD, int NSEG, bool TLDS, bool NOISE, bool SWEEP, bool INJ = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NR == 1 ? 3 : 4)))
 k_ptuple_episodes(const PTupleArgs a) {
     static_assert(!SWEEP || (NR == 1 && NOISE), "per-game sweeps: the QTable agent's variant, compiled with the noise path");
@@ -149,7 +154,9 @@ k_ptuple_episodes(const PTupleArgs a) {
         float* const ptab = TLDS ? cdf_lds : a.policy_tab + (size_t)g * NR * (size_t)(npid + 1) * APAD;
         unsigned pvalid = 0u;                    // NR == 1: lane l = valid bits of price ids 32l .. 32l + 31
         bool store_pending = false;
-        if (NR == 2) {
+        if (INJ) {
+            // the actions are given: no policy
+        } else if (NR == 2) {
 #pragma unroll
             for (int r = 0; r < NR; r++) {
                 const int i = a.ri[r], A = a.ag[i].n_actions;
@@ -236,9 +243,27 @@ k_ptuple_episodes(const PTupleArgs a) {
             // ---- (c) draws, lane = step (agents 0 and 1 share Philox stream 0: words x,y / z,w -- agents.py:81-82, :161)
             uint32_t Ex[NSEG], Ch[NSEG];                 // QTable agent: explores?, random choice
             float UU[NSEG][NR];                          // policy agents: the uniform of the categorical draw
+            uint32_t Ja[NSEG];                           // INJ: the policy agents' recorded actions, agent a.ri[r] in byte r
 #pragma unroll
             for (int seg = 0; seg < NSEG; seg++) {
                 const int tt = min(seg * 64 + lane, T - 1);
+                Ja[seg] = 0u;
+                if (INJ) {       // [n_episodes][T][2][G]; a choice / action that is none of the agent's is clamped to the last one
+                    const size_t f = ((size_t)e * (size_t)T + (size_t)tt) * 2;
+                    Ex[seg] = 0u; Ch[seg] = 0u;
+                    if (HASQ) {
+                        const size_t k = (f + (size_t)qi) * (size_t)a.G + (size_t)g;
+                        Ex[seg] = a.inj_u[k] < eps_q ? 1u : 0u;
+                        Ch[seg] = min((uint32_t)(uint8_t)a.inj_choice[k], (uint32_t)(Aq - 1));
+                    }
+#pragma unroll
+                    for (int r = 0; r < NR; r++) {
+                        const size_t k = (f + (size_t)a.ri[r]) * (size_t)a.G + (size_t)g;
+                        Ja[seg] |= min((uint32_t)(uint8_t)a.inj_action[k], (uint32_t)(a.ag[a.ri[r]].n_actions - 1)) << (8 * r);
+                        UU[seg][r] = 0.0f;
+                    }
+                    continue;
+                }
                 const u32x4 x = draw(a.seed, gid, eg, (uint32_t)tt, 0u);
                 Ex[seg] = 0u; Ch[seg] = 0u;
                 if (HASQ) {
@@ -256,6 +281,13 @@ k_ptuple_episodes(const PTupleArgs a) {
 #pragma unroll
             for (int seg = 0; seg < NSEG; seg++) {
                 nzm[seg] = 0ull; NA[seg] = a.env.a;
+                if (NOISE && INJ) {                      // the recorded draws [n_episodes][T][G] (environments.py:28-29)
+                    if (a.env.noise_prob > 0.0) {
+                        const size_t k = ((size_t)e * (size_t)T + (size_t)min(seg * 64 + lane, T - 1)) * (size_t)a.G + (size_t)g;
+                        nzm[seg] = __ballot(seg * 64 + lane < T && a.inj_noise_u[k] < (SWEEP ? np_g : a.env.noise_prob));
+                        NA[seg] = a.inj_noise_a[k];
+                    }
+                } else
                 if (NOISE) {
                     const int tt = min(seg * 64 + lane, T - 1);
                     const u32x4 xn = draw(a.seed, gid, eg, (uint32_t)tt, kStreamNoise);
@@ -276,6 +308,15 @@ k_ptuple_episodes(const PTupleArgs a) {
                 const int n = min(64, T - seg * 64);
                 for (int tl = 0; tl < n; tl++) {
                     uint32_t act2[2] = {0u, 0u};
+                    if (INJ) {
+                        if (HASQ) {
+                            const uint32_t gq = (uint32_t)__builtin_amdgcn_readfirstlane((int)((NOISE && off) ? am[off_qp] : gt[tau]));
+                            act2[qi] = rdlane(Ex[seg], tl) ? rdlane(Ch[seg], tl) : gq;
+                        }
+                        const uint32_t ja = rdlane(Ja[seg], tl);
+#pragma unroll
+                        for (int r = 0; r < NR; r++) act2[a.ri[r]] = (ja >> (8 * r)) & 0xFFu;
+                    } else
                     if (NOISE && off) {
                         if (HASQ) {
                             const uint32_t gq = (uint32_t)__builtin_amdgcn_readfirstlane((int)am[off_qp]);
@@ -523,12 +564,12 @@ __global__ void __launch_bounds__(1024) k_ptuple_lut(const PTupleArgs a, unsigne
     }
 }
 
-template <typename QT, int NR, int APAD, bool TLDS, bool NOISE, bool SWEEP = false>
+template <typename QT, int NR, int APAD, bool TLDS, bool NOISE, bool SWEEP = false, bool INJ = false>
 int launch_seg(const PTupleArgs& a, int grid, int block, size_t lds, hipStream_t s) {
     const int nseg = (a.T + 63) / 64;
 #define THRL_PT_LAUNCH(NS)                                                                                           \
     {                                                                                                                \
-        auto kern = k_ptuple_episodes<QT, NR, APAD, NS, TLDS, NOISE, SWEEP>;                                         \
+        auto kern = k_ptuple_episodes<QT, NR, APAD, NS, TLDS, NOISE, SWEEP, INJ>;                                        \
         if (lds > 64 * 1024) {                                                                                       \
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                            \
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
@@ -552,6 +593,9 @@ int launch_n(const PTupleArgs& a, int grid, int block, size_t lds, hipStream_t s
 }
 template <typename QT>
 int launch_t(const PTupleArgs& a, int grid, int block, size_t lds, hipStream_t s) {
+    if (a.inj)                              // parity mode: against a QTable the sweep variant (every sweep pointer is optional)
+        return a.n_r == 1 ? launch_seg<QT, 1, 24, false, true, true, true>(a, grid, block, lds, s)
+                          : launch_seg<QT, 2, 24, false, true, false, true>(a, grid, block, lds, s);
     if (a.sweep) {                          // (plan_ptuple: only with a QTable agent in the game)
         int amax = a.ag[a.ri[0]].n_actions;
         return amax <= 24 ? launch_seg<QT, 1, 24, false, true, true>(a, grid, block, lds, s) : launch_seg<QT, 1, 32, false, true, true>(a, grid, block, lds, s);

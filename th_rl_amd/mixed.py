@@ -29,6 +29,48 @@ NN_DEFAULTS = dict(states=4, actions=2, action_range=[0, 1], gamma=0.98, capacit
                    entropy=0)
 
 
+INJ_KEYS = ("u", "choice", "action", "noise_u", "noise_a")
+
+
+def check_injection(inj, E, T, N, G, kinds, noise):
+    """Validate the parity-mode arrays of MixedGameBatch.run (host only, no device needed).  inj: dict of arrays,
+    `u` (float64), `choice`, `action` (int8) of shape [E, T, N, G] and `noise_u`, `noise_a` (float64) of shape [E, T, G].
+    All or nothing: `u` and `choice` are required with a QTable agent in the game, `action` with a Reinforce /
+    ActorCritic agent, the two noise arrays with noise_prob > 0.  Returns the arrays the game consumes, C-contiguous
+    in the library's dtypes."""
+    if not isinstance(inj, dict):
+        raise ThrlError("inj must be a dict of arrays (keys: %s)" % ", ".join(INJ_KEYS))
+    unknown = sorted(set(inj) - set(INJ_KEYS))
+    if unknown:
+        raise ThrlError("unknown injection key(s) %s (known: %s)" % (unknown, ", ".join(INJ_KEYS)))
+    if "CAC" in kinds:
+        raise ThrlError("a game with a CAC agent cannot run from injected draws: its action is a float and the "
+                        "reference's play path for it cannot run")
+    need = []
+    if "QTable" in kinds:
+        need += ["u", "choice"]
+    if any(k in ("Reinforce", "ActorCritic") for k in kinds):
+        need += ["action"]
+    if noise:
+        need += ["noise_u", "noise_a"]
+    missing = [k for k in need if inj.get(k) is None]
+    if missing:
+        raise ThrlError("injection is all or nothing: this game (%s%s) also needs %s"
+                        % (", ".join(kinds), ", env noise" if noise else "", ", ".join(missing)))
+    out = {}
+    for k in need:
+        dt = np.int8 if k in ("choice", "action") else np.float64
+        a = np.asarray(inj[k])
+        shape = (E, T, G) if k.startswith("noise") else (E, T, N, G)
+        if a.shape != shape:
+            raise ThrlError("injected %r must have shape %s=%r, got %r"
+                            % (k, "[E,T,G]" if k.startswith("noise") else "[E,T,N,G]", shape, a.shape))
+        if dt is np.int8 and a.dtype != np.int8 and a.size and (a.min() < -128 or a.max() > 127):
+            raise ThrlError("injected %r does not fit int8" % k)
+        out[k] = np.ascontiguousarray(a, dtype=dt)
+    return out
+
+
 class MixedGameBatch:
     def __init__(self, config, n_games=1, device="cuda:0", dtype="float32", seed=0, game_offset=0, sweep=None):
         self.L = _lib.load()
@@ -361,7 +403,7 @@ class MixedGameBatch:
         idx = (torch.arange(n, device=self.device) + start) % cap
         return n, {k: v.index_select(1, idx).contiguous() for k, v in b.items()}
 
-    def run(self, n_episodes, fused=None, per_game_logs=True, keep_games=None, group_stats=None):
+    def run(self, n_episodes, fused=None, per_game_logs=True, keep_games=None, group_stats=None, inj=None):
         """n_episodes for all games.  fused=True: thrl_mixed_episodes, one launch per run of episodes
         between network updates; fused=False: the per-call operator loop (same results); None
         (default): fused unless the library reports the configuration as unsupported by that kernel
@@ -369,20 +411,27 @@ class MixedGameBatch:
         keep_games (device int64 index tensor of games): the per-game logs of those games only, selected on
         the device before the copy (fused path).  group_stats (a group_stats.GroupSpec of this batch's games): the
         per-game rows are reduced on the device by thrl_group_stats after every launch (the operator loop reduces its
-        rows with the same kernel), out["group_stats"] = the raw hist / sums / minmax (group_stats.to_numpy)."""
+        rows with the same kernel), out["group_stats"] = the raw hist / sums / minmax (group_stats.to_numpy).
+        inj (parity mode, see check_injection): the reference's recorded draws `u`, `choice` [E, T, N, G] of the QTable
+        agents, the sampled actions `action` [E, T, N, G] of the Reinforce / ActorCritic agents and the env's
+        `noise_u`, `noise_a` [E, T, G].  Entries of u / choice in a neural agent's slot and of action in a QTable's are
+        not read.  All three paths take it; prices, rewards, replay rings, tables and counters are then the
+        reference's exactly, the network parameters to float32 rounding of the update kernels."""
+        if inj is not None:
+            inj = check_injection(inj, int(n_episodes), self.T, self.N, self.G, self.kinds, self.cfg.noise_prob > 0)
         if fused is None:
             first = self.episode
             try:
-                return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats)
+                return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats, inj)
             except ThrlError as e:
                 # fall back only if the episode kernel itself refused the configuration, i.e. before any
                 # launch changed tables / buffers / episode index
                 if e.code != _lib.ERR_UNSUPPORTED or self.episode != first or self._fused_launched:
                     raise
-                return self._keep(self._run_unfused(int(n_episodes), group_stats), keep_games)
+                return self._keep(self._run_unfused(int(n_episodes), group_stats, inj), keep_games)
         if fused:
-            return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats)
-        return self._keep(self._run_unfused(int(n_episodes), group_stats), keep_games)
+            return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats, inj)
+        return self._keep(self._run_unfused(int(n_episodes), group_stats, inj), keep_games)
 
     @staticmethod
     def _keep(out, keep_games):
@@ -391,7 +440,11 @@ class MixedGameBatch:
             out["game_reward_log"], out["game_action_log"] = out["game_reward_log"][:, :, idx], out["game_action_log"][:, :, idx]
         return out
 
-    def _run_fused(self, E, per_game_logs=True, keep_games=None, group_stats=None):
+    def _inj_to_device(self, inj):
+        torch = _torch()
+        return {k: torch.from_numpy(v).to(self.device) for k, v in inj.items()}
+
+    def _run_fused(self, E, per_game_logs=True, keep_games=None, group_stats=None, inj=None):
         """per_game_logs=False keeps only the mean over games (reduced on the device, launch by launch):
         what train_one needs, without E x N x G arrays crossing to the host."""
         torch = _torch()
@@ -411,6 +464,7 @@ class MixedGameBatch:
             if not hasattr(self, "_scratch"):
                 self._scratch = [torch.zeros_like(b["price"]) if self.kinds[i] == "QTable" else None
                                  for i, b in enumerate(self.buf)]
+            dinj = self._inj_to_device(inj) if inj is not None else None
             done = 0
             while done < E:
                 k = min(E - done, kmax)
@@ -443,6 +497,9 @@ class MixedGameBatch:
                         mx.policy_tab, mx.policy_tab_bytes = self._ptab.data_ptr(), self._ptab.numel() * 4
                 if not self.tuple_kernel:
                     mx.flags = 1                       # THRL_MIXED_NO_TUPLE_KERNEL
+                if dinj is not None:                   # this launch's slice: the episodes already done are behind it
+                    for key, t in dinj.items():
+                        setattr(mx, "inj_" + key, t[done:].data_ptr())
                 r = _lib.Run()
                 r.seed, r.game_offset, r.first_episode, r.n_episodes = self.seed, self.game_offset, self.episode, k
                 for i in range(N):
@@ -479,7 +536,7 @@ class MixedGameBatch:
                 out["group_stats"] = to_numpy(st)
         return out
 
-    def _run_unfused(self, n_episodes, group_stats=None):
+    def _run_unfused(self, n_episodes, group_stats=None, inj=None):
         torch = _torch()
         if not self.initialized:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
@@ -508,10 +565,17 @@ class MixedGameBatch:
             # a tensor divisor: torch turns "/ python_scalar" into "* (1/scalar)", which is not the
             # reference's IEEE division
             T_t = torch.tensor(float(T), dtype=torch.float64, device=self.device)
+            dinj = self._inj_to_device(inj) if inj is not None else None
             for e in range(E):
                 for t in range(T):
-                    _lib.check(L.thrl_op_draws(cfg, self.seed, self.game_offset, self.episode, t, self._p(u), self._p(ch),
-                                               self._p(u2), self._p(nu), self._p(na), self._stream()), "thrl_op_draws")
+                    if dinj is None:
+                        _lib.check(L.thrl_op_draws(cfg, self.seed, self.game_offset, self.episode, t, self._p(u), self._p(ch),
+                                                   self._p(u2), self._p(nu), self._p(na), self._stream()), "thrl_op_draws")
+                    else:      # parity mode: this step's recorded draws ([G] rows of the arrays) in place of Philox
+                        if "u" in dinj:
+                            u, ch = dinj["u"][e, t], dinj["choice"][e, t]
+                        if noise:
+                            nu, na = dinj["noise_u"][e, t], dinj["noise_a"][e, t]
                     for i in range(N):
                         if self.kinds[i] == "QTable":
                             _lib.check(L.thrl_op_sample_action(cfg, i, self._p(self.q), self._p(price), self.eps[i],
@@ -526,7 +590,10 @@ class MixedGameBatch:
                             scaled[i].copy_(acts_f[i].to(torch.float64) * (hi - lo) + lo)
                         else:
                             rb = self.nn[i]
-                            acts[i].copy_(rb.act(price, u=u[i]))
+                            if dinj is None:
+                                acts[i].copy_(rb.act(price, u=u[i]))
+                            else:      # the recorded action; one that is no action of the agent counts as the last one
+                                acts[i].copy_(torch.clamp(dinj["action"][e, t, i].to(torch.int32) & 0xFF, max=rb.A - 1))
                             lo, hi = [float(x) for x in self.nn_cfg[i]["action_range"]]
                             # Reinforce.scale (agents.py:153-157): action / actions * (hi - lo) + lo
                             A_t = torch.tensor(float(rb.A), dtype=torch.float64, device=self.device)
