@@ -694,6 +694,95 @@ typedef struct {
 } thrl_crossplay_args;
 int thrl_crossplay(const thrl_cfg* cfg, const void* q, const thrl_crossplay_args* args, void* stream);
 
+/*
+ * Attractor analysis of the greedy strategies: ALL limit cycles of a game's greedy play and their basins, not only the
+ * one the training state falls into (thrl_deviation, thrl_equilibrium and thrl_crossplay follow one path).  No
+ * reference counterpart: utils.play_game starts every evaluation from environment.reset(), a uniform draw on [0, a),
+ * and plot_mean_conf / plot_sweep_conf average over such draws; reset_reward below is the exact value of that
+ * expectation for greedy play.  QTable agents only, no env noise (intercept env_a); q, and everything else of the
+ * batch, is read only.  Every [.][G] array has G = args.n_games: the first n_games games of q.  All arithmetic is
+ * float64, every operation rounded once, in the order written here.
+ *
+ * States.  Exactly thrl_equilibrium's: action tuples t (agent 0 slowest, T of them), rewards r_i(t), the scaled action
+ * sc_i(t) = scale_action of agent i's action in t, state(t), and the S distinct row tuples numbered by first
+ * occurrence in tuple order with rows row_i(s); the same limits (THRL_EQ_MAX_TUPLES, THRL_EQ_MAX_STATES, otherwise
+ * THRL_ERR_UNSUPPORTED) and the same cached per-config plan.  A game's working set lives in one block's LDS; a config
+ * inside the limits that needs more than 64 KB of it (six or more agents with S near the limit) is
+ * THRL_ERR_UNSUPPORTED too.
+ *
+ * Policies.  policy (device uint16 [G][P], P = sum_i (n_states_i + 1), the layout of thrl_policy_track): without
+ * THRL_ATTR_POLICY_GIVEN the call first fills policy[g] for every g < G from q (thrl_crossplay's extraction pass) and
+ * then works from it; with the flag it works from what policy holds and q may be NULL.  So one extraction, or the
+ * policy array of a convergence tracker, serves this call and cross-play alike.  Entries that are no action of their
+ * agent are clamped to the last action (nothing is read out of bounds).
+ *
+ * Map.  pi_i(r) = the policy entry of agent i's row r.  t(s) = the tuple (pi_i(row_i(s)))_i, f(s) = state(t(s)).  For
+ * every state s: mu(s) = the smallest k >= 0 for which f^k(s) lies on a cycle of f, rep(s) = the smallest state number
+ * on that cycle, lam(s) = its length.
+ *
+ * Attractors of a game = the distinct values of rep, n_attr of them.  basin(r) = the number of states s with
+ * rep(s) = r, the cycle's own states included.  Order: basin descending, ties by rep ascending.  The first
+ * THRL_ATTR_KEEP are reported, slot k of game g at [k][G] / [k][N][G]:
+ *   rep, lam, basin
+ *   cycle_reward[k][i][g] = (sum_{j<lam} r_i(t(f^j(rep))), added in that order from 0.0) / lam
+ *   cycle_action[k][i][g] = the same for sc_i
+ * Slots k >= n_attr get rep = -1, lam = 0, basin = 0 and zeros.  Per game: n_attr, mu_max = max_s mu(s),
+ * n_cycle_states = the sum of lam over all attractors, kept or not.
+ *
+ * Training state.  x_0 = (encode64_i(state0[g]))_i, which need not be a member of the state set; its successor
+ * state(tuple of the greedy actions at x_0's rows) is.  rep_x0 = rep of the cycle x_0 reaches, mu_x0 = the steps to
+ * it -- thrl_deviation's mu for a horizon of at least T + 1, and lam of rep_x0's attractor is its lam -- and
+ * slot_x0 = that attractor's slot, or -1 if it is not among the kept.
+ *
+ * Reset distribution (optional: n_starts = 0 skips it, its tables and outputs may then be NULL).  The caller cuts
+ * [0, env_a) at every agent's encode breakpoints into J = n_starts intervals: start_rows (device int32 [N][J]) holds
+ * agent i's row on interval j, start_w (device double [J]) its length / env_a (th_rl_amd.attractors.starts).  Rows
+ * are clamped to [0, n_states_i].  Start j reaches the attractor A(j) of state(tuple of pi_i(start_rows[i][j])).
+ *   reset_mass[k][g]    = sum of w_j over the j with A(j) in slot k, reset_mass_other[g] over the j whose attractor
+ *                         is not kept; both added in ascending j from 0.0
+ *   reset_reward[i][g]  = sum_j w_j * cycle_reward_i(A(j)) over ALL j, kept or not, in ascending j from 0.0, each
+ *                         multiply and each add rounded once
+ *
+ * state_rep, state_mu (optional, uint16 [G][S]): rep(s) and mu(s) of every state.
+ * *n_states (HOST, optional) receives S as soon as cfg is accepted, whatever the call returns afterwards.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games outside [1, cfg.n_games], a flag other than THRL_ATTR_POLICY_GIVEN or
+ * n_starts outside [0, THRL_ATTR_MAX_STARTS]; THRL_ERR_UNSUPPORTED for the limits; THRL_ERR_NULL for a missing
+ * state0, policy or per-game / per-slot output, a missing q without THRL_ATTR_POLICY_GIVEN, or with n_starts > 0 a
+ * missing start_rows, start_w, reset_mass, reset_mass_other or reset_reward.
+ */
+#define THRL_ATTR_KEEP 8
+#define THRL_ATTR_POLICY_GIVEN 1
+#define THRL_ATTR_MAX_STARTS (1 << 20)
+typedef struct {
+    int32_t n_games;                 /* G in [1, cfg.n_games]                            */
+    int32_t flags;                   /* 0 or THRL_ATTR_POLICY_GIVEN                      */
+    int32_t n_starts;                /* J in [0, THRL_ATTR_MAX_STARTS]                   */
+    int32_t reserved;                /* 0                                                */
+    const double* state0;            /* device [G] training states (prices)              */
+    uint16_t* policy;                /* device [G][P]: out without the flag, in with it  */
+    const int32_t* start_rows;       /* device [N][J], or NULL with J = 0                */
+    const double* start_w;           /* device [J], or NULL with J = 0                   */
+    int32_t* n_states;               /* HOST [1] <- S, or NULL                           */
+    int32_t* n_attr;                 /* device [G]                                       */
+    int32_t* mu_max;                 /* device [G]                                       */
+    int32_t* n_cycle_states;         /* device [G]                                       */
+    int32_t* rep;                    /* device [KEEP][G]                                 */
+    int32_t* lam;                    /* device [KEEP][G]                                 */
+    int32_t* basin;                  /* device [KEEP][G]                                 */
+    double*  cycle_reward;           /* device [KEEP][N][G]                              */
+    double*  cycle_action;           /* device [KEEP][N][G]                              */
+    int32_t* rep_x0;                 /* device [G]                                       */
+    int32_t* mu_x0;                  /* device [G]                                       */
+    int32_t* slot_x0;                /* device [G]                                       */
+    double*  reset_mass;             /* device [KEEP][G], or NULL with J = 0             */
+    double*  reset_mass_other;       /* device [G], or NULL with J = 0                   */
+    double*  reset_reward;           /* device [N][G], or NULL with J = 0                */
+    uint16_t* state_rep;             /* device [G][S] or NULL                            */
+    uint16_t* state_mu;              /* device [G][S] or NULL                            */
+} thrl_attractors_args;
+int thrl_attractors(const thrl_cfg* cfg, const void* q, const thrl_attractors_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,26 @@ class CrossplayArgs(ctypes.Structure):
     ]
 
 
+ATTR_KEEP = 8
+ATTR_POLICY_GIVEN = 1
+ATTR_MAX_STARTS = 1 << 20
+
+
+class AttractorsArgs(ctypes.Structure):
+    """thrl_attractors_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("flags", ctypes.c_int32), ("n_starts", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("state0", ctypes.c_void_p), ("policy", ctypes.c_void_p), ("start_rows", ctypes.c_void_p),
+        ("start_w", ctypes.c_void_p), ("n_states", ctypes.POINTER(ctypes.c_int32)),
+        ("n_attr", ctypes.c_void_p), ("mu_max", ctypes.c_void_p), ("n_cycle_states", ctypes.c_void_p),
+        ("rep", ctypes.c_void_p), ("lam", ctypes.c_void_p), ("basin", ctypes.c_void_p),
+        ("cycle_reward", ctypes.c_void_p), ("cycle_action", ctypes.c_void_p),
+        ("rep_x0", ctypes.c_void_p), ("mu_x0", ctypes.c_void_p), ("slot_x0", ctypes.c_void_p),
+        ("reset_mass", ctypes.c_void_p), ("reset_mass_other", ctypes.c_void_p), ("reset_reward", ctypes.c_void_p),
+        ("state_rep", ctypes.c_void_p), ("state_mu", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -171,7 +191,7 @@ SYMBOLS = [
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
-    "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay",
+    "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors",
 ]
 CAC_PARAMS = 1283
 
@@ -278,6 +298,8 @@ def load():
     L.thrl_equilibrium.argtypes = [cfgp, vp, ctypes.POINTER(EquilibriumArgs), vp]
     L.thrl_crossplay.restype = ctypes.c_int
     L.thrl_crossplay.argtypes = [cfgp, vp, ctypes.POINTER(CrossplayArgs), vp]
+    L.thrl_attractors.restype = ctypes.c_int
+    L.thrl_attractors.argtypes = [cfgp, vp, ctypes.POINTER(AttractorsArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -317,6 +317,24 @@ class GameBatch:
         return xp.run(self, seats, steps=steps, horizon=horizon, state0=state0, rows=rows, group_stats=group_stats,
                       q=q, policy=policy, budget=budget or xp.ROW_BUDGET)
 
+    def attractors(self, state0=None, policies=False, q=None, policy=None, reset=True, n_games=None):
+        """Attractor analysis of the greedy strategies (thrl_attractors; definitions in include/thrl.h): ALL limit
+        cycles of every game's greedy map on the state set and their basins, where GameBatch.deviation follows the one
+        path from the training state.  Returns a dict of numpy arrays: n_attr, mu_max, n_cycle_states [G]; the 8
+        attractors with the largest basins as rep, lam, basin [8, G] and cycle_reward, cycle_action [8, N, G] (slots
+        past n_attr: rep = -1 and zeros); the attractor of the training state, rep_x0, mu_x0, slot_x0 [G] (mu_x0 and
+        that slot's lam are GameBatch.deviation's mu and lam); with reset=True (the environment's reset distribution,
+        attractors.starts; False skips it, a (rows, w) pair replaces it) reset_mass [8, G], reset_mass_other [G] and
+        reset_reward [N, G], the exact expectation of greedy play from a reset; n_states.  policies=True adds state_rep,
+        state_mu (uint16) [G, S].  state0 [G]: the training states (default: the batch's state).  The greedy policies
+        are extracted once from the tables (or from q); policy (a device [G, P] 16-bit tensor such as a convergence
+        tracker's, or crossplay.extract's) is analysed as it is.  n_games: only the first n_games games.  Tables,
+        counters, state, epsilon and the episode index are not touched."""
+        from . import attractors as at
+        if not self.initialized:
+            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
+        return at.run(self, state0=state0, policies=policies, q=q, policy=policy, reset=reset, n_games=n_games)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
         its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.

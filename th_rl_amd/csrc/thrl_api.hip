@@ -10,6 +10,7 @@
 #include <mutex>
 #include <vector>
 
+#include "thrl_attractors.h"
 #include "thrl_converge.h"
 #include "thrl_crossplay.h"
 #include "thrl_deviation.h"
@@ -1462,6 +1463,44 @@ int thrl_policy_track(const thrl_cfg* c, const void* q, const thrl_policy_track_
     return e ? hip_fail(e, "k_policy_track launch") : THRL_OK;
 }
 
+// The greedy policy of the first G games of q into policy [G][P], 2 bytes per table row (k_xplay_extract): the pass
+// thrl_crossplay and thrl_attractors run without their POLICY_GIVEN flag.
+static int extract_policies(const thrl_cfg* c, const void* q, int G, uint16_t* policy, void* stream) {
+    const int N = c->n_agents;
+    AgentParams ag[THRL_MAXA];
+    fill_agents(c, ag, nullptr);
+    XpExtractArgs e;
+    memset(&e, 0, sizeof(e));
+    int P = 0;
+    for (int i = 0; i < N; i++) {
+        e.row_off[i] = P;
+        e.table_off[i] = ag[i].table_off;
+        e.n_actions[i] = ag[i].n_actions;
+        P += ag[i].rows;
+    }
+    e.row_off[N] = P;
+    e.G = G; e.N = N; e.P = P;
+    e.stride = (int64_t)thrl_table_stride(c);
+    // the staged window: the game's block widened to 16-byte chunks at both ends
+    const int64_t esz = c->q_dtype == 1 ? 8 : 4, vec = 16 / esz;
+    const int64_t lds = ((e.stride + 2 * vec) * esz + 15) & ~(int64_t)15;
+    e.staged = lds <= kXpExtractLdsBudget && ((uintptr_t)q & 15) == 0;
+    e.lds_bytes = e.staged ? (int32_t)lds : 0;
+    e.q = q; e.policy = policy;
+    // enough one-wave blocks to fill every CU as far as LDS allows, each looping over games
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    int per_cu = kXpExtractMaxBlocksPerCu;
+    if (e.staged && lds_cu > 0 && lds_cu / e.lds_bytes < per_cu) per_cu = lds_cu / e.lds_bytes > 0 ? lds_cu / e.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < e.G ? want : e.G);
+    const int err = thrl::launch_xplay_extract(e, c->q_dtype, grid, (hipStream_t)stream);
+    return err ? hip_fail(err, "k_xplay_extract launch") : THRL_OK;
+}
+
 int thrl_crossplay(const thrl_cfg* c, const void* q, const thrl_crossplay_args* x, void* stream) {
     int rc = validate(c);
     if (rc) return rc;
@@ -1492,34 +1531,7 @@ int thrl_crossplay(const thrl_cfg* c, const void* q, const thrl_crossplay_args* 
     row_off[N] = P;
 
     if (!given) {       // one streaming pass over q: policy[g] for every g < G
-        XpExtractArgs e;
-        memset(&e, 0, sizeof(e));
-        e.G = x->n_games; e.N = N; e.P = P;
-        e.stride = (int64_t)thrl_table_stride(c);
-        for (int i = 0; i < N; i++) {
-            e.row_off[i] = row_off[i];
-            e.table_off[i] = ag[i].table_off;
-            e.n_actions[i] = ag[i].n_actions;
-        }
-        e.row_off[N] = P;
-        // the staged window: the game's block widened to 16-byte chunks at both ends
-        const int64_t esz = c->q_dtype == 1 ? 8 : 4, vec = 16 / esz;
-        const int64_t lds = ((e.stride + 2 * vec) * esz + 15) & ~(int64_t)15;
-        e.staged = lds <= kXpExtractLdsBudget && ((uintptr_t)q & 15) == 0;
-        e.lds_bytes = e.staged ? (int32_t)lds : 0;
-        e.q = q; e.policy = x->policy;
-        // enough one-wave blocks to fill every CU as far as LDS allows, each looping over games
-        int dev = 0, cus = 0, lds_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess
-            || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
-            || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
-            return hip_fail((int)hipGetLastError(), "device attributes");
-        int per_cu = kXpExtractMaxBlocksPerCu;
-        if (e.staged && lds_cu > 0 && lds_cu / e.lds_bytes < per_cu) per_cu = lds_cu / e.lds_bytes > 0 ? lds_cu / e.lds_bytes : 1;
-        const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
-        const int grid = (int)(want < e.G ? want : e.G);
-        const int err = thrl::launch_xplay_extract(e, c->q_dtype, grid, (hipStream_t)stream);
-        if (err) return hip_fail(err, "k_xplay_extract launch");
+        if ((rc = extract_policies(c, q, x->n_games, x->policy, stream)) != THRL_OK) return rc;
     }
 
     XpWalkArgs a;
@@ -1692,6 +1704,23 @@ int eq_device_plan(const thrl_cfg* c, const EqHostPlan& h, EqSlot& out) {
     return THRL_OK;
 }
 
+// The plan of cfg on the current device without deriving it again when it is cached (thrl_attractors: one call per
+// analysis, the same config every time): out.S / out.T are the plan's.  A miss derives it and uploads it.
+int eq_cached_plan(const thrl_cfg* c, EqSlot& out) {
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail((int)e, "hipGetDevice");
+    const EqKey key = eq_key(c, dev);
+    {
+        std::lock_guard<std::mutex> lock(g_eq_mu);
+        for (int k = 0; k < kEqSlots; k++)
+            if (g_eq_slot[k].used && !memcmp(&g_eq_slot[k].key, &key, sizeof(key))) { out = g_eq_slot[k]; return THRL_OK; }
+    }
+    EqHostPlan h;
+    const int rc = eq_host_plan(c, h);
+    return rc != THRL_OK ? rc : eq_device_plan(c, h, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1768,6 +1797,105 @@ int thrl_equilibrium(const thrl_cfg* c, const void* q, const thrl_equilibrium_ar
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_equilibrium(a, c->q_dtype, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_equilibrium launch") : THRL_OK;
+}
+
+int thrl_attractors(const thrl_cfg* c, const void* q, const thrl_attractors_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // S without a device: the limits and *n_states are answered from the host plan when no GPU holds a cached one
+    EqSlot sl;
+    int devs = 0;
+    const bool have_dev = hipGetDeviceCount(&devs) == hipSuccess && devs > 0;
+    if (!have_dev) (void)hipGetLastError();
+    int S = 0, T = 0;
+    if (have_dev) {
+        if ((rc = eq_cached_plan(c, sl)) != THRL_OK) return rc;
+        S = sl.S; T = sl.T;
+    } else {
+        EqHostPlan h;
+        if ((rc = eq_host_plan(c, h)) != THRL_OK) return rc;
+        S = h.S; T = h.T;
+    }
+    if (x->n_states) *x->n_states = S;
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->flags & ~THRL_ATTR_POLICY_GIVEN) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (x->n_starts < 0 || x->n_starts > THRL_ATTR_MAX_STARTS)
+        return fail(THRL_ERR_BAD_CONFIG, "n_starts=%d out of [0,%d]", x->n_starts, THRL_ATTR_MAX_STARTS);
+    const bool given = (x->flags & THRL_ATTR_POLICY_GIVEN) != 0;
+    if (!x->state0 || !x->policy || !x->n_attr || !x->mu_max || !x->n_cycle_states || !x->rep || !x->lam || !x->basin
+        || !x->cycle_reward || !x->cycle_action || !x->rep_x0 || !x->mu_x0 || !x->slot_x0)
+        return fail(THRL_ERR_NULL, "state0 / policy / n_attr / mu_max / n_cycle_states / rep / lam / basin / cycle_reward / "
+                                   "cycle_action / rep_x0 / mu_x0 / slot_x0 is NULL");
+    if (x->n_starts > 0 && (!x->start_rows || !x->start_w || !x->reset_mass || !x->reset_mass_other || !x->reset_reward))
+        return fail(THRL_ERR_NULL, "n_starts=%d: start_rows / start_w / reset_mass / reset_mass_other / reset_reward is NULL",
+                    x->n_starts);
+    if (!given && !q) return fail(THRL_ERR_NULL, "q is NULL without THRL_ATTR_POLICY_GIVEN");
+    if (!have_dev) return hip_fail((int)hipErrorNoDevice, "thrl_attractors");
+
+    AttrArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.S = S; a.T = T; a.J = x->n_starts;
+    while ((1 << a.L) < S) a.L++;
+    fill_agents(c, a.ag, nullptr);
+    int ts = 1, P = 0;
+    for (int i = N - 1; i >= 0; i--) { a.tstride[i] = ts; ts *= c->n_actions[i]; }
+    for (int i = 0; i < N; i++) { a.row_off[i] = P; P += a.ag[i].rows; }
+    a.P = P;
+    // LDS of a block: 8-byte arrays first, then 4-byte, then 2-byte
+    const int64_t fixed = 8 * 64 * (int64_t)(1 + N) + 4 * (2 * (int64_t)S + THRL_MAXA + THRL_ATTR_KEEP + 64)
+                          + 2 * ((int64_t)T + (int64_t)N * S + THRL_MAXA + (int64_t)(a.L + 1) * S + 7 * (int64_t)S) + 64;
+    a.lut_lds = fixed + 8 * (int64_t)N * T <= kAttrLdsBudget;
+    if (fixed > kAttrLdsBudget)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_attractors: %lld bytes of LDS per game (N=%d, S=%d, T=%d)", (long long)fixed,
+                    N, S, T);
+    int off = 0;
+    a.o_rew = off; off += a.lut_lds ? 8 * N * T : 0;
+    a.o_cw = off; off += 8 * 64;
+    a.o_cprod = off; off += 8 * 64 * N;
+    a.o_basin = off; off += 4 * S;
+    a.o_lamc = off; off += 4 * S;
+    a.o_x0row = off; off += 4 * THRL_MAXA;
+    a.o_sel = off; off += 4 * THRL_ATTR_KEEP;
+    a.o_cslot = off; off += 4 * 64;
+    a.o_sid = off; off += 2 * T;
+    a.o_pol = off; off += 2 * (N * S + THRL_MAXA);
+    a.o_lev = off; off += 2 * (a.L + 1) * S;
+    a.o_ma = off; off += 2 * S;
+    a.o_mb = off; off += 2 * S;
+    a.o_rep = off; off += 2 * S;
+    a.o_mu = off; off += 2 * S;
+    a.o_on = off; off += 2 * S;
+    a.o_tup = off; off += 2 * S;
+    a.o_slot = off; off += 2 * S;
+    a.lds_bytes = (off + 15) & ~15;
+
+    if (!given && (rc = extract_policies(c, q, x->n_games, x->policy, stream)) != THRL_OK) return rc;
+
+    a.policy = x->policy; a.state0 = x->state0;
+    a.rew = (const double*)sl.mem;
+    a.srow = (const int32_t*)((const unsigned char*)sl.mem + sl.off_srow);
+    a.sid = (const uint16_t*)((const unsigned char*)sl.mem + sl.off_sid);
+    a.start_rows = x->start_rows; a.start_w = x->start_w;
+    a.n_attr = x->n_attr; a.mu_max = x->mu_max; a.n_cycle_states = x->n_cycle_states;
+    a.rep = x->rep; a.lam = x->lam; a.basin = x->basin;
+    a.cycle_reward = x->cycle_reward; a.cycle_action = x->cycle_action;
+    a.rep_x0 = x->rep_x0; a.mu_x0 = x->mu_x0; a.slot_x0 = x->slot_x0;
+    a.reset_mass = x->reset_mass; a.reset_mass_other = x->reset_mass_other; a.reset_reward = x->reset_reward;
+    a.state_rep = x->state_rep; a.state_mu = x->state_mu;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    int per_cu = kAttrMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes > 0 ? lds_cu / a.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_attractors(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_attractors launch") : THRL_OK;
 }
 
 }  // extern "C"

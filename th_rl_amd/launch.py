@@ -19,7 +19,8 @@ with training.convergence every shard writes its per-game convergence arrays and
 convergence.json and conv_*.npy (merge_convergence); with training.crossplay every shard draws its partners INSIDE the
 shard (the tables of other ranks are not fetched, so a sharded run's pairings are not the unsharded run's) and saves
 the seats as global game ids; rank 0 concatenates the shards' xplay_*.npy along the game axis and writes the top-level
-crossplay.json (merge_crossplay).  A convergence stop counts the games of every rank (the trainer
+crossplay.json (merge_crossplay); with training.attractors rank 0 concatenates the shards' attr_*.npy and writes
+attractors.json (merge_attractors).  A convergence stop counts the games of every rank (the trainer
 all-reduces over the gloo group), so all ranks stop at the same episode.
 """
 import argparse
@@ -69,7 +70,8 @@ def shard_training(config, rank, world):
         opt.update(histograms=True, n_max=int(numpy.bincount(ids, minlength=n_groups).max()))
         training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
     dv = training.get("deviation")
-    cv = training.get("convergence") or training.get("equilibrium") or training.get("crossplay")
+    cv = training.get("convergence") or training.get("equilibrium") or training.get("crossplay") \
+        or training.get("attractors")
     if ((dv is not None and dv is not False) or (cv is not None and cv is not False)) and (gs is None or gs is False):
         # the per-group summaries of each shard's deviation.json / convergence.json use the global group ids too
         from th_rl_amd.group_stats import assign_groups
@@ -203,6 +205,29 @@ def merge_crossplay(config, out, world):
     xp.save_json(os.path.join(out, "crossplay.json"), xp.describe(opt, nash, cartel, summary))
 
 
+def merge_attractors(config, out, world):
+    """Rank 0: the top-level attractors.json and attr_*.npy of a sharded run from the shards' per-game arrays
+    (attractors.combine: the concatenation in global game order, summarised as one run)."""
+    from th_rl_amd import attractors as at
+    from th_rl_amd.group_stats import assign_groups
+    training = config.get("training", {})
+    total = int(training.get("n_games", world))
+    opt = at.parse_options(training["attractors"], config)
+    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                     n_groups=training.get("n_groups"))
+    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
+    games = at.combine(at.load_games(s) for s in shards)
+    at.save_games(out, games)
+    with open(os.path.join(shards[0], "attractors.json")) as f:
+        first = json.load(f)
+    if "tables" in first["options"]:       # recorded when the run tracks convergence
+        opt["tables"] = first["options"]["tables"]
+    nash, cartel = at.optimal(config)
+    summary = at.summarize(games, ids, n_groups, nash, cartel)
+    at.save_json(os.path.join(out, "attractors.json"),
+                 at.describe(opt, first["n_states"], first["n_starts"], nash, cartel, summary))
+
+
 def merge_convergence(config, out, world):
     """Rank 0: the top-level convergence.json and conv_*.npy of a sharded run from the shards' per-game arrays
     (convergence.combine: the concatenation in global game order, summarised as one run)."""
@@ -280,6 +305,8 @@ def _worker(rank, world, port, config, out, devices_available):
             merge_equilibrium(config, out, world)
         if training.get("crossplay"):
             merge_crossplay(config, out, world)
+        if training.get("attractors"):
+            merge_attractors(config, out, world)
     dist.destroy_process_group()
 
 

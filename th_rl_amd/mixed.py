@@ -330,6 +330,16 @@ class MixedGameBatch:
         return xp.run(self, seats, steps=steps, horizon=horizon, state0=state0, rows=rows, group_stats=group_stats,
                       q=q, policy=policy, budget=budget or xp.ROW_BUDGET)
 
+    def attractors(self, state0=None, policies=False, q=None, policy=None, reset=True, n_games=None):
+        """GameBatch.attractors for an all-QTable batch (the same table layout).  A batch with a neural agent raises
+        ThrlError."""
+        from . import attractors as at
+        if any(k != "QTable" for k in self.kinds):
+            raise ThrlError("MixedGameBatch.attractors: agents %s: %s" % (self.kinds, at.NEURAL_FOLLOW_UP))
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return at.run(self, state0=state0, policies=policies, q=q, policy=policy, reset=reset, n_games=n_games)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

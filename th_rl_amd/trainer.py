@@ -38,6 +38,12 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                      # xplay_cycle_action.npy [rounds, N, G], xplay_self_cycle.npy [2, G] and
                                      # xplay_self_reward.npy [N, G] (each game's own cycle); with group_stats and
                                      # steps > 0 the path rows pooled over the rounds, xplay_*.npy [steps, ...]
+                 "attractors": null,  # true or {"policies": false, "tables": "final" | "converged"}: after training (and
+                                      # cross-play) ALL limit cycles of the greedy strategies and their basins
+                                      # (attractors.py, QTable agents only): attractors.json (options, Nash, Cartel,
+                                      # per-group summary), attr_games.npy int32 [6, G], attr_slots.npy int32 [3, 8, G],
+                                      # attr_cycle.npy [2, 8, N, G], attr_reset_mass.npy [9, G], attr_reset_reward.npy
+                                      # [N, G]; with policies attr_state.npy uint16 [2, G, S]
                  "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
                                      # "horizon": null}: after training (and the greedy statistics) the deviation
                                      # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json
@@ -249,6 +255,12 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         xp_opt = crossplay_options(training["crossplay"], config)         # refuses neural agents before training
     if xp_opt is not None and xp_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
         raise ValueError('training.crossplay.tables = "converged" needs training.convergence with "snapshot": true')
+    at_opt = None
+    if training.get("attractors") is not None and training.get("attractors") is not False:
+        from th_rl_amd.attractors import parse_options as attractors_options
+        at_opt = attractors_options(training["attractors"], config)       # refuses neural agents before training
+    if at_opt is not None and at_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
+        raise ValueError('training.attractors.tables = "converged" needs training.convergence with "snapshot": true')
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -497,6 +509,21 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
                 q_xp, s_xp = tracker.tables_at_convergence()
         write_crossplay(exp_path, batch, config, xp_opt, ids, n_groups, spec=spec,
                         histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET, q=q_xp, state0=s_xp)
+
+    if at_opt is not None:      # every limit cycle of the greedy strategies and its basin (attractors.py)
+        from th_rl_amd.attractors import write_artefacts as write_attractors
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        q_at = s_at = None
+        if tracker is not None:
+            at_opt = dict(at_opt, tables=at_opt.get("tables", "final"))
+            if at_opt["tables"] == "converged":
+                q_at, s_at = tracker.tables_at_convergence()
+        write_attractors(exp_path, batch, config, at_opt, ids, n_groups, q=q_at, state0=s_at)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

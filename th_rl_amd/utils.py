@@ -292,6 +292,61 @@ def crossplay_games(exp_path, round=0):
     return pandas.concat(frames)
 
 
+def attractor_summary(exp_path):
+    """A run's attractor analysis (training.attractors): attractors.json's summary as a DataFrame with one row per
+    group -- games, single, the quantiles of n_attr and mu_max, delta_train_mean / delta_largest_mean /
+    delta_reset_mean (profit gains of the training state's attractor, of the largest basin and in expectation over the
+    environment's reset distribution), train_is_largest, train_mass_q*, luck_mean -- plus n_states, n_starts, Nash
+    and Cartel."""
+    import json
+    with open(os.path.join(exp_path, "attractors.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["n_states"], df["n_starts"] = int(desc["n_states"]), int(desc["n_starts"])
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def attractor_games(exp_path):
+    """Per-game results of the attractor analysis, one row per game indexed by its GLOBAL id: n_attr, mu_max,
+    n_cycle_states, rep_x0, mu_x0, slot_x0, per kept slot k rep_<k>, lam_<k>, basin_<k>, delta_<k> (its profit gain, NaN
+    past n_attr) and mass_<k>, and delta_train, delta_reset, mass_other.  Reads exp_path's attr_*.npy, or those of
+    exp_path/shard*/ (th_rl_amd.launch writes one set per rank) in game order."""
+    import glob
+    import json
+    from th_rl_amd import attractors as at
+    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "attr_games.npy")) else \
+        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "attr_games.npy"))),
+               key=lambda d: int(os.path.basename(d)[5:]))
+    if not dirs:
+        raise KeyError("no attractor analysis (attr_games.npy) under %s (training.attractors)" % exp_path)
+    frames = []
+    for d in dirs:
+        with open(os.path.join(d, "attractors.json")) as f:
+            desc = json.load(f)
+        off = 0
+        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
+        if os.path.isfile(cfg_path):
+            with open(cfg_path) as f:
+                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        g = at.load_games(d)
+        gn = at.gains(g, desc["nash"], desc["cartel"])
+        cols = {f: g[f] for f in at.GAME_INT}
+        for k in range(g["rep"].shape[0]):
+            cols.update({"rep_%d" % k: g["rep"][k], "lam_%d" % k: g["lam"][k], "basin_%d" % k: g["basin"][k]})
+            cols["delta_%d" % k] = numpy.where(g["rep"][k] >= 0, at.profit_gain(g["cycle_reward"][k], desc["nash"], desc["cartel"]),
+                                               numpy.nan)
+            if "reset_mass" in g:
+                cols["mass_%d" % k] = g["reset_mass"][k]
+        cols["delta_train"] = gn["train"]
+        if gn["reset"] is not None:
+            cols["delta_reset"] = gn["reset"]
+            cols["mass_other"] = g["reset_mass_other"]
+        n = g["n_attr"].shape[0]
+        frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
+    return pandas.concat(frames)
+
+
 def convergence_summary(exp_path):
     """A run's convergence (training.convergence): convergence.json's summary as a DataFrame with one row per group --
     games, converged, fraction, converged_at_mean / q25 / q50 / q75, conv_since_mean / q25 / q50 / q75 (over the
