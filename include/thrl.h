@@ -783,6 +783,118 @@ typedef struct {
 } thrl_attractors_args;
 int thrl_attractors(const thrl_cfg* cfg, const void* q, const thrl_attractors_args* args, void* stream);
 
+/*
+ * Greedy play under demand noise: the exact long-run behaviour of a game's greedy strategies in the environment the
+ * reference ships, NoisyPriceState with noise_prob > 0, which redraws the demand intercept from U(0.7 a, a) with that
+ * probability at every step (utils.play_game, behind plot_mean_conf / plot_sweep_conf / plot_mean_result, steps through
+ * it).  thrl_deviation, thrl_equilibrium, thrl_crossplay and thrl_attractors describe the deterministic greedy map;
+ * that map usually has several limit cycles, and a demand shock moves a game from one to another, so the profit that
+ * greedy play sustains belongs to no single cycle: it is the stationary behaviour of a Markov chain.  With the price
+ * axis cut at the agents' encode breakpoints the chain is finite, and this call iterates it; the only other route,
+ * thrl_play_greedy with noise, samples it.  QTable agents only; q, and everything else of the batch, is read only.
+ * Every [.][G] array has G = args.n_games: the first n_games games of q.  All arithmetic is float64, every operation
+ * rounded once, in the order written here.
+ *
+ * Cells.  The caller cuts [0, env_a) at every agent's encode breakpoints into J = n_cells cells [c_k, c_{k+1})
+ * (th_rl_amd.attractors.starts): cell_rows (device int32 [N][J]) holds agent i's row on cell k (clamped to
+ * [0, n_states_i]), cell_w (device double [J]) the cell's length / env_a.  A noise-free price that sits exactly on a
+ * breakpoint where the agents' half-even ties disagree has a row tuple that no interval has; the caller appends every
+ * such row tuple as a POINT CELL (its rows, cell_w = 0, no band entry: a redrawn intercept lands on a single price with
+ * probability 0), so the cells are any J distinct row tuples with weights.  J <= THRL_STAT_MAX_CELLS, above it
+ * THRL_ERR_UNSUPPORTED; the same when a game's working set (two iterates and the tuple per cell, 18 J bytes, plus
+ * 512 (2 N + 2) bytes of staging) does not fit one block's 64 KB of LDS.
+ *
+ * Tuples.  thrl_equilibrium's: action tuples t (agent 0 slowest, T of them), the noise-free price p(t) and rewards
+ * r_i(t) (scale_action, env_step with intercept env_a), the scaled action sc_i(t); the limit THRL_EQ_MAX_TUPLES and
+ * the same cached per-config plan.  *n_tuples (HOST, optional) receives T as soon as cfg is accepted.
+ *
+ * Per-config tables, computed by the caller (th_rl_amd.stationary.tables) and only read here, so that the device and
+ * a host restatement share their bits.  With u(t) = the amount env_step subtracts from the intercept (env_b * Q),
+ * noise_lo = 0.7 env_a, lo = noise_lo - u, hi = env_a - u, width = env_a - noise_lo:
+ *   det_cell (device int32 [T])      the cell whose row tuple equals (encode64_i(p(t)))_i: the noise-free part of the
+ *                                    chain is thrl_deviation's F.  An entry outside [0, J) is no cell: that mass is lost
+ *   band_lo (device int32 [T]), band (device double [T][W], W = band_w)
+ *                                    n(t, k) = band[t][k - band_lo[t]] where 0 <= k - band_lo[t] < W, else 0: the
+ *                                    probability that a redrawn intercept puts the price of t into cell k,
+ *                                    (len_k + [k = 0] z) / width with len_k = max(0, min(c_{k+1}, hi) - max(c_k, lo))
+ *                                    and z = max(0, -lo) - max(0, -hi), the mass of prices clipped to 0
+ *   noise_price (device double [T])  the expected price of t under a redrawn intercept: (lo + hi) / 2 if lo >= 0,
+ *                                    0 if hi <= 0, else hi^2 / (2 width)
+ *   noise_reward (device double [N][T])  that price times agent i's quantity in t (env_step's ratio * sc_i)
+ *
+ * Noise probability.  p_g = args.noise_prob, or noise_prob_g[g] where that array (device double [G]) is given, then
+ * args.noise_prob is not read; q_g = 1 - p_g.  It need not be the one the games were trained with.  A host-visible
+ * value outside (0, 1] is THRL_ERR_BAD_CONFIG; an entry of noise_prob_g outside it (NaN included) is device data: that
+ * game gets iters = -1 and zeros in every output, and no other game is affected.
+ *
+ * Policies.  policy (device uint16 [G][P], P = sum_i (n_states_i + 1), the layout of thrl_policy_track): without
+ * THRL_STAT_POLICY_GIVEN the call first fills policy[g] for every g < G from q (thrl_crossplay's extraction pass) and
+ * then works from it; with the flag it works from what policy holds and q may be NULL.  Entries that are no action of
+ * their agent are clamped to the last action (nothing is read out of bounds).  t_g(k) = the tuple of the policy
+ * entries at cell_rows[.][k].
+ *
+ * Chain.  P_g(j, k) = q_g [det_cell(t_g(j)) = k] + p_g n(t_g(j), k): the product p_g * n is computed, and q_g is added
+ * to it only where the bracket is 1.
+ *
+ * Iteration, in the lazy form (I + P) / 2, which converges for every finite chain to the Cesaro limit from the start
+ * distribution whatever the periods (a chain with p = 1 whose band alternates between two cells has no other limit).
+ *   mu_0 = cell_w (the environment's reset distribution), or with THRL_STAT_START_STATE the unit mass on the cell
+ *          whose row tuple equals (encode64_i(state0[g]))_i; a game whose state0 has the rows of no cell (a price on a
+ *          breakpoint where the ties disagree, which is no noise-free price) gets iters = -1 and zeros
+ *   s(k) = sum_j mu_m(j) * P_g(j, k), in ascending j from 0.0 (terms that are zero may be skipped: adding +0.0 is
+ *          exact)
+ *   mu_{m+1}(k) = 0.5 * mu_m(k) + 0.5 * s(k)
+ *   chg_m = max_k |mu_{m+1}(k) - mu_m(k)|
+ * Stop after the first step with chg <= args.tol, or after args.max_iters steps.
+ *
+ * Outputs, per game, from the last iterate mu; every sum over ascending k from 0.0, each multiply and add rounded once:
+ *   iters                the steps taken (= max_iters: the tolerance was not reached), change = the last chg
+ *   mass                 sum_k mu(k)
+ *   stat_reward[i][g]    sum_k mu(k) * (q_g * r_i(t(k)) + p_g * noise_reward_i(t(k)))
+ *   stat_action[i][g]    sum_k mu(k) * sc_i(t(k))
+ *   stat_price[g]        sum_k mu(k) * (q_g * p(t(k)) + p_g * noise_price(t(k)))
+ *   pi (optional, double [G][J])   mu itself
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games outside [1, cfg.n_games], an unknown flag, n_cells < 1, band_w < 1,
+ * max_iters outside [1, THRL_STAT_MAX_ITERS], tol < 0 or NaN, or noise_prob as above; THRL_ERR_UNSUPPORTED for the
+ * limits; THRL_ERR_NULL for a missing table (cell_rows, cell_w, det_cell, band_lo, band, noise_reward, noise_price),
+ * policy or per-game output, a missing state0 with THRL_STAT_START_STATE, or a missing q without
+ * THRL_STAT_POLICY_GIVEN.
+ */
+#define THRL_STAT_POLICY_GIVEN 1
+#define THRL_STAT_START_STATE 2
+#define THRL_STAT_MAX_CELLS 4096
+#define THRL_STAT_MAX_ITERS 65536
+typedef struct {
+    int32_t n_games;                 /* G in [1, cfg.n_games]                            */
+    int32_t flags;                   /* THRL_STAT_POLICY_GIVEN | THRL_STAT_START_STATE   */
+    int32_t n_cells;                 /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t band_w;                  /* W >= 1                                           */
+    int32_t max_iters;               /* in [1, THRL_STAT_MAX_ITERS]                      */
+    int32_t reserved;                /* 0                                                */
+    double  noise_prob;              /* p in (0, 1], read when noise_prob_g is NULL      */
+    double  tol;                     /* >= 0                                             */
+    const double* noise_prob_g;      /* device [G] or NULL                               */
+    const double* state0;            /* device [G] prices, with THRL_STAT_START_STATE    */
+    uint16_t* policy;                /* device [G][P]: out without the flag, in with it  */
+    const int32_t* cell_rows;        /* device [N][J]                                    */
+    const double* cell_w;            /* device [J]                                       */
+    const int32_t* det_cell;         /* device [T]                                       */
+    const int32_t* band_lo;          /* device [T]                                       */
+    const double* band;              /* device [T][W]                                    */
+    const double* noise_reward;      /* device [N][T]                                    */
+    const double* noise_price;       /* device [T]                                       */
+    int32_t* n_tuples;               /* HOST [1] <- T, or NULL                           */
+    int32_t* iters;                  /* device [G]                                       */
+    double*  change;                 /* device [G]                                       */
+    double*  mass;                   /* device [G]                                       */
+    double*  stat_reward;            /* device [N][G]                                    */
+    double*  stat_action;            /* device [N][G]                                    */
+    double*  stat_price;             /* device [G]                                       */
+    double*  pi;                     /* device [G][J] or NULL                            */
+} thrl_stationary_args;
+int thrl_stationary(const thrl_cfg* cfg, const void* q, const thrl_stationary_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,28 @@ class AttractorsArgs(ctypes.Structure):
     ]
 
 
+STAT_POLICY_GIVEN = 1
+STAT_START_STATE = 2
+STAT_MAX_CELLS = 4096
+STAT_MAX_ITERS = 65536
+
+
+class StationaryArgs(ctypes.Structure):
+    """thrl_stationary_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("flags", ctypes.c_int32), ("n_cells", ctypes.c_int32), ("band_w", ctypes.c_int32),
+        ("max_iters", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("noise_prob", ctypes.c_double), ("tol", ctypes.c_double),
+        ("noise_prob_g", ctypes.c_void_p), ("state0", ctypes.c_void_p), ("policy", ctypes.c_void_p),
+        ("cell_rows", ctypes.c_void_p), ("cell_w", ctypes.c_void_p), ("det_cell", ctypes.c_void_p),
+        ("band_lo", ctypes.c_void_p), ("band", ctypes.c_void_p), ("noise_reward", ctypes.c_void_p),
+        ("noise_price", ctypes.c_void_p), ("n_tuples", ctypes.POINTER(ctypes.c_int32)),
+        ("iters", ctypes.c_void_p), ("change", ctypes.c_void_p), ("mass", ctypes.c_void_p),
+        ("stat_reward", ctypes.c_void_p), ("stat_action", ctypes.c_void_p), ("stat_price", ctypes.c_void_p),
+        ("pi", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -191,7 +213,7 @@ SYMBOLS = [
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
-    "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors",
+    "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
 ]
 CAC_PARAMS = 1283
 
@@ -300,6 +322,8 @@ def load():
     L.thrl_crossplay.argtypes = [cfgp, vp, ctypes.POINTER(CrossplayArgs), vp]
     L.thrl_attractors.restype = ctypes.c_int
     L.thrl_attractors.argtypes = [cfgp, vp, ctypes.POINTER(AttractorsArgs), vp]
+    L.thrl_stationary.restype = ctypes.c_int
+    L.thrl_stationary.argtypes = [cfgp, vp, ctypes.POINTER(StationaryArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

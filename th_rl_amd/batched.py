@@ -335,6 +335,26 @@ class GameBatch:
             raise ThrlError("GameBatch: call init_tables() or set_tables() first")
         return at.run(self, state0=state0, policies=policies, q=q, policy=policy, reset=reset, n_games=n_games)
 
+    def stationary(self, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters=8192, pi=False, q=None,
+                   policy=None, n_games=None):
+        """Greedy play under demand noise (thrl_stationary; definitions in include/thrl.h): the long-run distribution
+        of every game's noisy greedy play over the price cells (attractors.starts), by lazy power iteration of its
+        Markov chain, and what that distribution earns.  Returns a dict of numpy arrays: iters (steps taken; max_iters
+        = the tolerance was not reached, -1 = not solved), change, mass [G], stat_reward, stat_action [N, G], stat_price
+        [G], noise_prob [G] (the values analysed), n_cells, max_iters; pi=True adds pi [G, J].  noise_prob: the
+        probability of a redrawn intercept per step, a number in (0, 1] or [G] values; None = the batch's per-game sweep
+        array if it has one, else the config's value (ThrlError if that is 0); it need not be the one the games were
+        trained with.  start: "reset" (the environment's reset distribution) or "state" (the unit mass on the cell of
+        state0 [G], default the batch's state).  tol, max_iters: the stopping rule.  The greedy policies are extracted
+        once from the tables (or from q); policy (a device [G, P] 16-bit tensor such as a convergence tracker's, or
+        crossplay.extract's) is analysed as it is.  n_games: only the first n_games games.  Tables, counters, state,
+        epsilon and the episode index are not touched."""
+        from . import stationary as sn
+        if not self.initialized:
+            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
+        return sn.run(self, noise_prob=noise_prob, start=start, state0=state0, tol=tol, max_iters=max_iters, pi=pi, q=q,
+                      policy=policy, n_games=n_games)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
         its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "thrl_attractors.h"
+#include "thrl_stationary.h"
 #include "thrl_converge.h"
 #include "thrl_crossplay.h"
 #include "thrl_deviation.h"
@@ -1896,6 +1897,100 @@ int thrl_attractors(const thrl_cfg* c, const void* q, const thrl_attractors_args
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_attractors(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_attractors launch") : THRL_OK;
+}
+
+int thrl_stationary(const thrl_cfg* c, const void* q, const thrl_stationary_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // T is the product of the action counts: the tuple limit and *n_tuples need no plan, and every host-visible
+    // argument is checked before the device is touched (the plan is fetched, and cached, only by a call that launches)
+    int64_t T64 = 1;
+    for (int i = 0; i < N; i++) {
+        T64 *= c->n_actions[i];
+        if (T64 > THRL_EQ_MAX_TUPLES)
+            return fail(THRL_ERR_UNSUPPORTED, "thrl_stationary: more than %d action tuples (prod n_actions)",
+                        THRL_EQ_MAX_TUPLES);
+    }
+    const int T = (int)T64;
+    if (x->n_tuples) *x->n_tuples = T;
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->flags & ~(THRL_STAT_POLICY_GIVEN | THRL_STAT_START_STATE))
+        return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (x->n_cells < 1 || x->band_w < 1)
+        return fail(THRL_ERR_BAD_CONFIG, "n_cells=%d and band_w=%d must be >= 1", x->n_cells, x->band_w);
+    if (x->max_iters < 1 || x->max_iters > THRL_STAT_MAX_ITERS)
+        return fail(THRL_ERR_BAD_CONFIG, "max_iters=%d out of [1,%d]", x->max_iters, THRL_STAT_MAX_ITERS);
+    if (!(x->tol >= 0.0)) return fail(THRL_ERR_BAD_CONFIG, "tol=%g must be >= 0", x->tol);
+    if (!x->noise_prob_g && !(x->noise_prob > 0.0 && x->noise_prob <= 1.0))
+        return fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of (0, 1]", x->noise_prob);
+    if (x->n_cells > THRL_STAT_MAX_CELLS)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_stationary: n_cells=%d, at most %d", x->n_cells, THRL_STAT_MAX_CELLS);
+    // LDS of a block: the two iterates, the staging of the ordered sums and the tuple per cell must fit
+    const int64_t J = x->n_cells;
+    const int64_t need = 8 * 2 * J + 8 * 64 * (int64_t)(2 * N + 2) + 2 * J + 16;
+    if (need > kStatLdsBudget)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_stationary: %lld bytes of LDS per game (N=%d, n_cells=%d)", (long long)need,
+                    N, x->n_cells);
+    const bool given = (x->flags & THRL_STAT_POLICY_GIVEN) != 0;
+    const bool start_state = (x->flags & THRL_STAT_START_STATE) != 0;
+    if (!x->cell_rows || !x->cell_w || !x->det_cell || !x->band_lo || !x->band || !x->noise_reward || !x->noise_price)
+        return fail(THRL_ERR_NULL, "cell_rows / cell_w / det_cell / band_lo / band / noise_reward / noise_price is NULL");
+    if (!x->policy || !x->iters || !x->change || !x->mass || !x->stat_reward || !x->stat_action || !x->stat_price)
+        return fail(THRL_ERR_NULL, "policy / iters / change / mass / stat_reward / stat_action / stat_price is NULL");
+    if (start_state && !x->state0) return fail(THRL_ERR_NULL, "state0 is NULL with THRL_STAT_START_STATE");
+    if (!given && !q) return fail(THRL_ERR_NULL, "q is NULL without THRL_STAT_POLICY_GIVEN");
+
+    StatArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = T; a.J = x->n_cells; a.W = x->band_w;
+    a.max_iters = x->max_iters; a.start_state = start_state;
+    a.noise_prob = x->noise_prob; a.tol = x->tol;
+    fill_agents(c, a.ag, &a.env);
+    int ts = 1, P = 0;
+    for (int i = N - 1; i >= 0; i--) { a.tstride[i] = ts; ts *= c->n_actions[i]; }
+    for (int i = 0; i < N; i++) { a.row_off[i] = P; P += a.ag[i].rows; }
+    a.P = P;
+    // LDS layout: 8-byte arrays first, then 4-byte, then 2-byte
+    a.cell_lds = need + 10 * J <= kStatLdsBudget;
+    int off = 0;
+    a.o_mua = off; off += 8 * a.J;
+    a.o_mub = off; off += 8 * a.J;
+    a.o_prod = off; off += 8 * 64 * (2 * N + 2);
+    a.o_boff = off; off += a.cell_lds ? 4 * a.J : 0;
+    a.o_blo = off; off += a.cell_lds ? 4 * a.J : 0;
+    a.o_det = off; off += a.cell_lds ? 2 * a.J : 0;
+    a.o_tup = off; off += 2 * a.J;
+    a.lds_bytes = (off + 15) & ~15;
+    int devs = 0;
+    if (hipGetDeviceCount(&devs) != hipSuccess || devs <= 0) {
+        (void)hipGetLastError();
+        return hip_fail((int)hipErrorNoDevice, "thrl_stationary");
+    }
+    EqSlot sl;
+    if ((rc = eq_cached_plan(c, sl)) != THRL_OK) return rc;
+
+    if (!given && (rc = extract_policies(c, q, x->n_games, x->policy, stream)) != THRL_OK) return rc;
+
+    a.policy = x->policy; a.noise_prob_g = x->noise_prob_g; a.state0 = x->state0;
+    a.rew = (const double*)sl.mem;
+    a.cell_rows = x->cell_rows; a.cell_w = x->cell_w; a.det_cell = x->det_cell; a.band_lo = x->band_lo; a.band = x->band;
+    a.noise_reward = x->noise_reward; a.noise_price = x->noise_price;
+    a.iters = x->iters; a.change = x->change; a.mass = x->mass; a.stat_reward = x->stat_reward;
+    a.stat_action = x->stat_action; a.stat_price = x->stat_price; a.pi = x->pi;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    int per_cu = kStatMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes > 0 ? lds_cu / a.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_stationary(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_stationary launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -20,7 +20,8 @@ convergence.json and conv_*.npy (merge_convergence); with training.crossplay eve
 shard (the tables of other ranks are not fetched, so a sharded run's pairings are not the unsharded run's) and saves
 the seats as global game ids; rank 0 concatenates the shards' xplay_*.npy along the game axis and writes the top-level
 crossplay.json (merge_crossplay); with training.attractors rank 0 concatenates the shards' attr_*.npy and writes
-attractors.json (merge_attractors).  A convergence stop counts the games of every rank (the trainer
+attractors.json (merge_attractors), and with training.stationary the shards' stat_*.npy and stationary.json
+(merge_stationary).  A convergence stop counts the games of every rank (the trainer
 all-reduces over the gloo group), so all ranks stop at the same episode.
 """
 import argparse
@@ -71,7 +72,7 @@ def shard_training(config, rank, world):
         training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
     dv = training.get("deviation")
     cv = training.get("convergence") or training.get("equilibrium") or training.get("crossplay") \
-        or training.get("attractors")
+        or training.get("attractors") or training.get("stationary")
     if ((dv is not None and dv is not False) or (cv is not None and cv is not False)) and (gs is None or gs is False):
         # the per-group summaries of each shard's deviation.json / convergence.json use the global group ids too
         from th_rl_amd.group_stats import assign_groups
@@ -228,6 +229,29 @@ def merge_attractors(config, out, world):
                  at.describe(opt, first["n_states"], first["n_starts"], nash, cartel, summary))
 
 
+def merge_stationary(config, out, world):
+    """Rank 0: the top-level stationary.json and stat_*.npy of a sharded run from the shards' per-game arrays
+    (stationary.combine: the concatenation in global game order, summarised as one run)."""
+    from th_rl_amd import stationary as sn
+    from th_rl_amd.group_stats import assign_groups
+    training = config.get("training", {})
+    total = int(training.get("n_games", world))
+    opt = sn.parse_options(training["stationary"], config)
+    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
+                                     n_groups=training.get("n_groups"))
+    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
+    games = sn.combine(sn.load_games(s) for s in shards)
+    sn.save_games(out, games)
+    with open(os.path.join(shards[0], "stationary.json")) as f:
+        first = json.load(f)
+    if "tables" in first["options"]:       # recorded when the run tracks convergence
+        opt["tables"] = first["options"]["tables"]
+    nash, cartel = sn.optimal(config)
+    rr = sn.reset_reward_of(out, total) if training.get("attractors") else None       # merge_attractors ran before
+    summary = sn.summarize(games, ids, n_groups, nash, cartel, opt["max_iters"], reset_reward=rr)
+    sn.save_json(os.path.join(out, "stationary.json"), sn.describe(opt, first["n_cells"], nash, cartel, summary))
+
+
 def merge_convergence(config, out, world):
     """Rank 0: the top-level convergence.json and conv_*.npy of a sharded run from the shards' per-game arrays
     (convergence.combine: the concatenation in global game order, summarised as one run)."""
@@ -307,6 +331,8 @@ def _worker(rank, world, port, config, out, devices_available):
             merge_crossplay(config, out, world)
         if training.get("attractors"):
             merge_attractors(config, out, world)
+        if training.get("stationary"):
+            merge_stationary(config, out, world)
     dist.destroy_process_group()
 
 

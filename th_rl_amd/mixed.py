@@ -340,6 +340,18 @@ class MixedGameBatch:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
         return at.run(self, state0=state0, policies=policies, q=q, policy=policy, reset=reset, n_games=n_games)
 
+    def stationary(self, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters=8192, pi=False, q=None,
+                   policy=None, n_games=None):
+        """GameBatch.stationary for an all-QTable batch (the same table layout).  A batch with a neural agent raises
+        ThrlError."""
+        from . import stationary as sn
+        if any(k != "QTable" for k in self.kinds):
+            raise ThrlError("MixedGameBatch.stationary: agents %s: %s" % (self.kinds, sn.NEURAL_FOLLOW_UP))
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return sn.run(self, noise_prob=noise_prob, start=start, state0=state0, tol=tol, max_iters=max_iters, pi=pi, q=q,
+                      policy=policy, n_games=n_games)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

@@ -44,6 +44,13 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                       # per-group summary), attr_games.npy int32 [6, G], attr_slots.npy int32 [3, 8, G],
                                       # attr_cycle.npy [2, 8, N, G], attr_reset_mass.npy [9, G], attr_reset_reward.npy
                                       # [N, G]; with policies attr_state.npy uint16 [2, G, S]
+                 "stationary": null,  # true or {"noise_prob": null, "start": "reset", "tol": 1e-12, "max_iters": 8192,
+                                      # "pi": false, "tables": "final" | "converged"}: after training (and the attractor
+                                      # analysis) the long-run distribution of greedy play UNDER DEMAND NOISE and what
+                                      # it earns (stationary.py, QTable agents only; noise_prob null = the run's own):
+                                      # stationary.json (options, Nash, Cartel, per-group summary), stat_iters.npy int32
+                                      # [G], stat_games.npy [4, G], stat_reward.npy / stat_action.npy [N, G]; with pi
+                                      # stat_pi.npy [G, J]
                  "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
                                      # "horizon": null}: after training (and the greedy statistics) the deviation
                                      # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json
@@ -261,6 +268,12 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         at_opt = attractors_options(training["attractors"], config)       # refuses neural agents before training
     if at_opt is not None and at_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
         raise ValueError('training.attractors.tables = "converged" needs training.convergence with "snapshot": true')
+    st_opt = None
+    if training.get("stationary") is not None and training.get("stationary") is not False:
+        from th_rl_amd.stationary import parse_options as stationary_options
+        st_opt = stationary_options(training["stationary"], config)       # refuses neural agents before training
+    if st_opt is not None and st_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
+        raise ValueError('training.stationary.tables = "converged" needs training.convergence with "snapshot": true')
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -524,6 +537,22 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             if at_opt["tables"] == "converged":
                 q_at, s_at = tracker.tables_at_convergence()
         write_attractors(exp_path, batch, config, at_opt, ids, n_groups, q=q_at, state0=s_at)
+
+    if st_opt is not None:      # the long-run distribution of greedy play under demand noise (stationary.py)
+        from th_rl_amd.stationary import write_artefacts as write_stationary
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        q_st = s_st = None
+        if tracker is not None:
+            st_opt = dict(st_opt, tables=st_opt.get("tables", "final"))
+            if st_opt["tables"] == "converged":
+                q_st, s_st = tracker.tables_at_convergence()
+        write_stationary(exp_path, batch, config, st_opt, ids, n_groups, q=q_st, state0=s_st,
+                         with_attractors=at_opt is not None)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

@@ -347,6 +347,59 @@ def attractor_games(exp_path):
     return pandas.concat(frames)
 
 
+def stationary_summary(exp_path):
+    """A run's stationary analysis (training.stationary: greedy play under demand noise): stationary.json's summary as
+    a DataFrame with one row per group -- games, converged (share with iters < max_iters), iters_q25 / q50 / q75 / max,
+    delta_noise_mean / q25 / q50 / q75 (deviation.profit_gain of the long-run reward stat_reward; Nash and Cartel are
+    deviation.optimal(config), the NOISE-FREE benchmark of every other analysis, so a delta below the noise-free one
+    also carries the demand the noise removes), price_mean and, when attr_reset_reward.npy (training.attractors) is in
+    the same directory, delta_reset_mean and noise_cost_mean = delta_reset - delta_noise -- plus n_cells, Nash and
+    Cartel."""
+    import json
+    with open(os.path.join(exp_path, "stationary.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["n_cells"] = int(desc["n_cells"])
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def stationary_games(exp_path):
+    """Per-game results of the stationary analysis, one row per game indexed by its GLOBAL id: iters, change, mass,
+    noise_prob, price, reward_<i>, action_<i>, delta_noise (against the noise-free Nash / Cartel) and, with
+    attr_reset_reward.npy beside them, delta_reset.  Reads exp_path's stat_*.npy, or those of exp_path/shard*/
+    (th_rl_amd.launch writes one set per rank) in game order."""
+    import glob
+    import json
+    from th_rl_amd import stationary as sn
+    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "stat_iters.npy")) else \
+        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "stat_iters.npy"))),
+               key=lambda d: int(os.path.basename(d)[5:]))
+    if not dirs:
+        raise KeyError("no stationary analysis (stat_iters.npy) under %s (training.stationary)" % exp_path)
+    frames = []
+    for d in dirs:
+        with open(os.path.join(d, "stationary.json")) as f:
+            desc = json.load(f)
+        off = 0
+        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
+        if os.path.isfile(cfg_path):
+            with open(cfg_path) as f:
+                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        g = sn.load_games(d)
+        cols = {"iters": g["iters"], "change": g["change"], "mass": g["mass"], "noise_prob": g["noise_prob"],
+                "price": g["stat_price"]}
+        for i in range(g["stat_reward"].shape[0]):
+            cols["reward_%d" % i], cols["action_%d" % i] = g["stat_reward"][i], g["stat_action"][i]
+        cols["delta_noise"] = sn.profit_gain(g["stat_reward"], desc["nash"], desc["cartel"])
+        rr = sn.reset_reward_of(d, g["iters"].shape[0])
+        if rr is not None:
+            cols["delta_reset"] = sn.profit_gain(rr, desc["nash"], desc["cartel"])
+        n = g["iters"].shape[0]
+        frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
+    return pandas.concat(frames)
+
+
 def convergence_summary(exp_path):
     """A run's convergence (training.convergence): convergence.json's summary as a DataFrame with one row per group --
     games, converged, fraction, converged_at_mean / q25 / q50 / q75, conv_since_mean / q25 / q50 / q75 (over the
