@@ -895,6 +895,100 @@ typedef struct {
 } thrl_stationary_args;
 int thrl_stationary(const thrl_cfg* cfg, const void* q, const thrl_stationary_args* args, void* stream);
 
+/*
+ * Strategies as tables over the game's action tuples, for ANY discrete agent: QTable, Reinforce, ActorCritic.  No
+ * reference counterpart.  The analyses above index a policy by the agent's table row, which a network does not have.
+ * The game has a finite state set of its own: with discrete agents and no env noise the price after a step is a
+ * function of that step's action tuple, so what an agent does next is a function of the tuple index.  Tuples are
+ * numbered with agent 0 slowest: t = sum_i k_i * prod_{j > i} n_actions_j, T = prod_i n_actions_i <=
+ * THRL_TP_MAX_TUPLES.  price (device float64 [T]) holds the noise-free price after every tuple; the CALLER computes
+ * it (th_rl_amd.tuple_play.tables: scale, env_step with intercept env_a, every operation rounded once, QTable agents
+ * scaled by k / (A - 1), Reinforce / ActorCritic agents by k / A), the device does no scaling arithmetic.
+ *
+ * thrl_tuple_policy fills tuple_policy (device uint16 [G][N][T], G = args.n_games, 1 <= G <= cfg.n_games):
+ * entry [g][i][t] is what get_action of agent i of game g returns at the state price[t].
+ *   kind[i] = 0, QTable: the first maximum (strict >) of row encode64_i(price[t]) of agent i's table in q[g]: the
+ *     entry thrl_crossplay's extraction writes for that row.
+ *   kind[i] = 1 / 2, Reinforce / ActorCritic: argmax pi at x = (float)price[t], evaluated by the function
+ *     thrl_nn_act / thrl_ac_act evaluate: bit for bit the action they return with u = NULL at that price.
+ *     nn_params[i] (device [G][thrl_nn_param_count / thrl_ac_param_count]) as in thrl_mixed; cfg.n_actions[i] in
+ *     [2, 32], cfg.n_states[i] is not read.
+ * kind and nn_params have thrl_mixed's meanings; q may be NULL when no agent is a QTable.  Everything but
+ * tuple_policy is read only.
+ *
+ * Returns THRL_ERR_UNSUPPORTED for a CAC agent (kind 3: its action is continuous) or n_tuples > THRL_TP_MAX_TUPLES;
+ * THRL_ERR_BAD_CONFIG for n_games outside [1, cfg.n_games], a kind outside [0, 3], a neural agent with actions
+ * outside [2, 32], n_tuples < 1 or n_tuples != prod_i n_actions_i; THRL_ERR_NULL for a missing cfg, args, price,
+ * tuple_policy, nn_params[i] of a neural agent, or q with a QTable agent in the game.
+ */
+#define THRL_TP_MAX_TUPLES 4096
+typedef struct {
+    int32_t n_games;                     /* G in [1, cfg.n_games]                            */
+    int32_t n_tuples;                    /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t kind[THRL_MAXA];             /* 0 = QTable, 1 = Reinforce, 2 = ActorCritic (3 = CAC is refused) */
+    const float* nn_params[THRL_MAXA];   /* device [G][P] for the neural agents              */
+    const double* price;                 /* device [T]                                       */
+    uint16_t* tuple_policy;              /* device [G][N][T], out                            */
+} thrl_tuple_policy_args;
+int thrl_tuple_policy(const thrl_cfg* cfg, const void* q, const thrl_tuple_policy_args* args, void* stream);
+
+/*
+ * Greedy play on tuple indices between any agents of any games, from a tuple_policy array: thrl_crossplay for
+ * strategies in tuple form, with no encode and no network in it.  Of a valid cfg only n_agents and n_actions are used.
+ *
+ * G = args.n_games >= 1: the games of tuple_policy (it need not be cfg.n_games: the array may hold the games of
+ * several batches of one config).  M = args.n_matches >= 1; seat (device int32 [N][M]), thrl_crossplay's layout: in
+ * match m, seat i is taken by AGENT i OF GAME seat[i][m].  start (device int32 [M]): the tuple index t_0 of match m
+ * (the tuple whose price is the state play starts from).
+ *
+ * Step: t_{k+1} is the index of the tuple (tuple_policy[seat[i][m]][i][t_k])_i.  Entries at or above n_actions_i are
+ * clamped to n_actions_i - 1 (the caller's to avoid; nothing is read out of bounds).
+ * (mu, lam) are thrl_crossplay's, word for word: mu >= 0, lam >= 1 the smallest values with t_{mu+lam} = t_mu; the
+ * cycle is found iff mu + lam <= H (horizon); otherwise lam = 0 and mu = H.  Cycle detection keeps O(1) state per
+ * match (Brent) with a step budget that decides "found" exactly by mu + lam <= H.
+ * The transition taken at t_k plays the tuple t_{k+1}: its rewards are reward[i][t_{k+1}] and its scaled actions
+ * scaled[i][t_{k+1}] (device float64 [N][T] each, the caller's per-config tables).
+ *   cycle_reward[i][m] = (sum_{j<lam} reward[i][t_{mu+j+1}], added in that order from 0.0) / lam, cycle_action the
+ *   same with scaled; both 0 when lam = 0.  With the tables of tuple_play.tables these are thrl_crossplay's numbers
+ *   for the same strategies whenever the two walks visit the same transitions.
+ * cycle_start (optional, device int32 [M]): t_mu, or -1 when lam = 0.
+ * Rows reward_rows / action_rows [row_count][N][M] (each optional) hold, for tau in [row_begin, row_begin + row_count)
+ * inside [0, n_steps), reward[i][t_{tau+1}] and scaled[i][t_{tau+1}]: the layout of the episode rows, so
+ * thrl_group_stats reduces them as they are (E = row_count, G = M).
+ *
+ * A seat outside [0, G) or a start outside [0, T) is device data the host cannot see: that match reads nothing and
+ * gets mu = -1, lam = 0, cycle_start = -1 and zeros in cycle_reward, cycle_action and its rows.  No other match is
+ * affected.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_matches < 1, n_games < 1, horizon outside [1, THRL_DEV_MAX_HORIZON], n_steps
+ * outside [0, THRL_DEV_MAX_STEPS], a row range outside [0, n_steps), reserved != 0, n_tuples < 1 or
+ * n_tuples != prod_i n_actions_i; THRL_ERR_UNSUPPORTED for n_tuples > THRL_TP_MAX_TUPLES; THRL_ERR_NULL for a missing
+ * cfg, args, seat, start, tuple_policy, reward, scaled, mu, lam, cycle_reward or cycle_action.
+ */
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of tuple_policy                    */
+    int32_t n_matches;               /* M >= 1                                           */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t n_steps;                 /* K in [0, THRL_DEV_MAX_STEPS]: length of the path the rows are cut from */
+    int32_t horizon;                 /* H >= 1 (th_rl_amd: min(T + 1, 65536))            */
+    int32_t row_begin;               /* rows stored: tau in [row_begin, row_begin + row_count) */
+    int32_t row_count;
+    int32_t reserved;                /* 0                                                */
+    const int32_t* seat;             /* device [N][M]: game whose agent i sits in match m */
+    const int32_t* start;            /* device [M]: start tuple t_0                      */
+    const uint16_t* tuple_policy;    /* device [G][N][T]                                 */
+    const double* reward;            /* device [N][T]                                    */
+    const double* scaled;            /* device [N][T]                                    */
+    int32_t* mu;                     /* device outputs [M]                               */
+    int32_t* lam;
+    int32_t* cycle_start;            /* device [M] or NULL                               */
+    double*  cycle_reward;           /* device [N][M]                                    */
+    double*  cycle_action;           /* device [N][M]                                    */
+    double*  reward_rows;            /* device [row_count][N][M] or NULL                 */
+    double*  action_rows;            /* device [row_count][N][M] or NULL                 */
+} thrl_tuple_walk_args;
+int thrl_tuple_walk(const thrl_cfg* cfg, const thrl_tuple_walk_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

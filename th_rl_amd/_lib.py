@@ -204,6 +204,32 @@ class StationaryArgs(ctypes.Structure):
     ]
 
 
+TP_MAX_TUPLES = 4096
+
+
+class TuplePolicyArgs(ctypes.Structure):
+    """thrl_tuple_policy_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32),
+        ("kind", ctypes.c_int32 * MAXA), ("nn_params", ctypes.c_void_p * MAXA),
+        ("price", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p),
+    ]
+
+
+class TupleWalkArgs(ctypes.Structure):
+    """thrl_tuple_walk_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_matches", ctypes.c_int32), ("n_tuples", ctypes.c_int32),
+        ("n_steps", ctypes.c_int32), ("horizon", ctypes.c_int32), ("row_begin", ctypes.c_int32),
+        ("row_count", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("seat", ctypes.c_void_p), ("start", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p),
+        ("reward", ctypes.c_void_p), ("scaled", ctypes.c_void_p),
+        ("mu", ctypes.c_void_p), ("lam", ctypes.c_void_p), ("cycle_start", ctypes.c_void_p),
+        ("cycle_reward", ctypes.c_void_p), ("cycle_action", ctypes.c_void_p),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -214,6 +240,7 @@ SYMBOLS = [
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
+    "thrl_tuple_policy", "thrl_tuple_walk",
 ]
 CAC_PARAMS = 1283
 
@@ -324,6 +351,10 @@ def load():
     L.thrl_attractors.argtypes = [cfgp, vp, ctypes.POINTER(AttractorsArgs), vp]
     L.thrl_stationary.restype = ctypes.c_int
     L.thrl_stationary.argtypes = [cfgp, vp, ctypes.POINTER(StationaryArgs), vp]
+    L.thrl_tuple_policy.restype = ctypes.c_int
+    L.thrl_tuple_policy.argtypes = [cfgp, vp, ctypes.POINTER(TuplePolicyArgs), vp]
+    L.thrl_tuple_walk.restype = ctypes.c_int
+    L.thrl_tuple_walk.argtypes = [cfgp, ctypes.POINTER(TupleWalkArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

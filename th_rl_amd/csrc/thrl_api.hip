@@ -17,6 +17,7 @@
 #include "thrl_deviation.h"
 #include "thrl_equilibrium.h"
 #include "thrl_kernels.h"
+#include "thrl_tuple_play.h"
 #include "thrl_wave_lut.h"
 
 using namespace thrl;
@@ -1566,6 +1567,101 @@ int thrl_crossplay(const thrl_cfg* c, const void* q, const thrl_crossplay_args* 
     a.reward_rows = x->reward_rows; a.action_rows = x->action_rows;
     const int e = thrl::launch_xplay_walk(a, (hipStream_t)stream);
     return e ? hip_fail(e, "k_xplay_walk launch") : THRL_OK;
+}
+
+// n_tuples must be the game's own: prod_i n_actions_i, at most THRL_TP_MAX_TUPLES
+static int tuple_count_check(const thrl_cfg* c, int n_tuples) {
+    if (n_tuples < 1) return fail(THRL_ERR_BAD_CONFIG, "n_tuples=%d must be >= 1", n_tuples);
+    if (n_tuples > THRL_TP_MAX_TUPLES)
+        return fail(THRL_ERR_UNSUPPORTED, "n_tuples=%d, at most %d", n_tuples, THRL_TP_MAX_TUPLES);
+    int64_t prod = 1;
+    for (int i = 0; i < c->n_agents; i++) {
+        prod *= c->n_actions[i];
+        if (prod > THRL_TP_MAX_TUPLES) break;
+    }
+    if (prod != n_tuples)
+        return fail(THRL_ERR_BAD_CONFIG, "n_tuples=%d is not the product of the agents' action counts", n_tuples);
+    return THRL_OK;
+}
+
+int thrl_tuple_policy(const thrl_cfg* c, const void* q, const thrl_tuple_policy_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    for (int i = 0; i < N; i++) {
+        if (x->kind[i] == 3)
+            return fail(THRL_ERR_UNSUPPORTED, "agent %d is a CAC agent: its action is continuous, the game has no tuples", i);
+        if (x->kind[i] < 0 || x->kind[i] > 3) return fail(THRL_ERR_BAD_CONFIG, "agent %d: kind=%d", i, x->kind[i]);
+        if (x->kind[i] != 0 && (c->n_actions[i] < 2 || c->n_actions[i] > 32))
+            return fail(THRL_ERR_BAD_CONFIG, "neural agent %d: actions=%d out of [2,32]", i, c->n_actions[i]);
+    }
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (!x->price || !x->tuple_policy) return fail(THRL_ERR_NULL, "price / tuple_policy is NULL");
+    TpPolicyArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_agents(c, a.ag, nullptr);
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples;
+    a.stride = (int64_t)thrl_table_stride(c);
+    for (int i = 0; i < N; i++) {
+        if (x->kind[i] == 0) {
+            a.q_agent[a.n_q++] = i;
+        } else {
+            if (!x->nn_params[i]) return fail(THRL_ERR_NULL, "nn_params[%d] is NULL", i);
+            const int j = a.n_nn++;
+            a.nn_agent[j] = i;
+            a.nn_actions[j] = c->n_actions[i];
+            a.nn_stride[j] = x->kind[i] == 2 ? (int32_t)thrl_ac_param_count(c->n_actions[i])
+                                             : (int32_t)thrl_nn_param_count(c->n_actions[i]);
+            a.nn_params[j] = x->nn_params[i];
+        }
+    }
+    if (a.n_q > 0 && !q) return fail(THRL_ERR_NULL, "q is NULL with a QTable agent in the game");
+    a.q = q; a.price = x->price; a.policy = x->tuple_policy;
+    const int e = thrl::launch_tp_policy(a, c->q_dtype, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_tp_qtable / k_tp_neural launch") : THRL_OK;
+}
+
+int thrl_tuple_walk(const thrl_cfg* c, const thrl_tuple_walk_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_matches < 1) return fail(THRL_ERR_BAD_CONFIG, "n_matches=%d must be >= 1", x->n_matches);
+    if (x->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", x->n_games);
+    if (x->horizon < 1 || x->horizon > THRL_DEV_MAX_HORIZON)
+        return fail(THRL_ERR_BAD_CONFIG, "horizon=%d out of [1,%d]", x->horizon, THRL_DEV_MAX_HORIZON);
+    if (x->n_steps < 0 || x->n_steps > THRL_DEV_MAX_STEPS)
+        return fail(THRL_ERR_BAD_CONFIG, "n_steps=%d out of [0,%d]", x->n_steps, THRL_DEV_MAX_STEPS);
+    if (x->row_begin < 0 || x->row_count < 0 || (int64_t)x->row_begin + x->row_count > x->n_steps)
+        return fail(THRL_ERR_BAD_CONFIG, "rows [%d, %d + %d) outside [0, n_steps=%d)", x->row_begin, x->row_begin,
+                    x->row_count, x->n_steps);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (!x->seat || !x->start || !x->tuple_policy || !x->reward || !x->scaled || !x->mu || !x->lam || !x->cycle_reward
+        || !x->cycle_action)
+        return fail(THRL_ERR_NULL, "seat / start / tuple_policy / reward / scaled / mu / lam / cycle_reward / cycle_action is NULL");
+    TpWalkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.M = x->n_matches; a.N = N; a.T = x->n_tuples; a.H = x->horizon; a.K = x->n_steps;
+    a.row_begin = x->row_begin; a.row_count = x->row_count;
+    int stride = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        a.n_actions[i] = c->n_actions[i];
+        a.tstride[i] = stride;
+        stride *= c->n_actions[i];
+    }
+    const int64_t lds = (int64_t)2 * N * a.T * 8;
+    a.in_lds = lds <= kTpLdsBudget;
+    a.lds_bytes = a.in_lds ? (int32_t)lds : 0;
+    a.policy = x->tuple_policy; a.seat = x->seat; a.start = x->start; a.reward = x->reward; a.scaled = x->scaled;
+    a.mu = x->mu; a.lam = x->lam; a.cycle_start = x->cycle_start;
+    a.cycle_reward = x->cycle_reward; a.cycle_action = x->cycle_action;
+    a.reward_rows = x->reward_rows; a.action_rows = x->action_rows;
+    const int e = thrl::launch_tp_walk(a, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_tp_walk launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,245 @@
+// thrl_tuple_play.hip -- strategies as tables over the game's action tuples, and greedy play on tuple indices
+// (thrl_tuple_policy, thrl_tuple_walk, include/thrl.h).  With discrete agents and no noise the price after a step is a
+// function of that step's action tuple, so what any agent does next is a function of the tuple index: a uint16 per
+// (game, agent, tuple), whatever the agent is.  Three kernels.
+//
+// k_tp_neural: one wavefront per game for ONE Reinforce / ActorCritic agent (a launch per neural agent, so the
+//   register-resident network is sized for that agent's action count, as k_nn_act's is).  policy_load puts the
+//   weights in registers once; the T prices come in runs of 64, one per lane, and are handed to the whole wave by
+//   v_readlane, so the evaluation loop touches no memory.  Lane j keeps the action of the run's j-th price and the
+//   wave stores the run as one contiguous 128-byte piece.  The evaluation is thrl_policy.h's policy_act, the function
+//   k_nn_act calls, with the same padding: the same bits.
+// k_tp_qtable: one thread per (game, tuple), every QTable agent in turn: the first maximum of row encode64(price[t]).
+//   Consecutive tuples have neighbouring prices, so a wave reads a few neighbouring rows and its stores are contiguous.
+// k_tp_walk: one lane per match, the walk of k_xplay_walk on a single integer.  The 2-byte policy entries it visits
+//   are gathered from global memory (mu + lam is a handful of steps); the per-config reward and scaled-action tables
+//   sit in LDS when they fit kTpLdsBudget.
+#include "thrl_tuple_play.h"
+
+#include "thrl_policy.h"
+
+namespace thrl {
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ extraction
+template <int APAD>
+__global__ void __launch_bounds__(256) k_tp_neural(int G, int A, int T, const float* __restrict__ params, int P,
+                                                    const double* __restrict__ price, uint16_t* __restrict__ out,
+                                                    int64_t out_stride) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= G) return;
+    PolicyRegs<APAD> r;
+    policy_load(r, params + (int64_t)g * P, A, lane);
+    uint16_t* o = out + (int64_t)g * out_stride;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int n = T - t0 < 64 ? T - t0 : 64;
+        const float xv = (float)price[t0 + (lane < n ? lane : n - 1)];
+        int keep = 0;
+        for (int j = 0; j < n; j++) {
+            const float x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xv), j));
+            const int act = policy_act(r, A, x, false, 0.0f, lane, nullptr);
+            if (lane == j) keep = act;
+        }
+        if (lane < n) o[t0 + lane] = (uint16_t)keep;
+    }
+}
+
+template <typename Tq>
+__global__ void __launch_bounds__(256) k_tp_qtable(const TpPolicyArgs a) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)a.G * a.T) return;
+    const int64_t g = idx / a.T;
+    const int t = (int)(idx - g * a.T);
+    const double p = a.price[t];
+    const Tq* __restrict__ q = reinterpret_cast<const Tq*>(a.q) + g * a.stride;
+    for (int j = 0; j < a.n_q; j++) {
+        const int i = a.q_agent[j];
+        const AgentParams& ag = a.ag[i];
+        const int row = encode64(p, ag);
+        a.policy[(g * a.N + i) * a.T + t] = (uint16_t)argmax_row(q + ag.table_off + (int64_t)row * ag.n_actions, ag.n_actions);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ walk
+template <int MAXN>
+struct TpSeats {
+    const uint16_t* gp[MAXN];       // agent i's T entries of the seated game
+};
+
+// t <- the index of the tuple the seated agents play at t
+template <int MAXN>
+__device__ __forceinline__ int tp_next(const TpWalkArgs& a, const TpSeats<MAXN>& v, int t) {
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < MAXN; i++)
+        if (i < a.N) n += min((int)v.gp[i][t], a.n_actions[i] - 1) * a.tstride[i];
+    return n;
+}
+
+template <bool kLds, int MAXN>
+__global__ void __launch_bounds__(kTpTile) k_tp_walk(const TpWalkArgs a) {
+    extern __shared__ __align__(16) unsigned char s_mem[];
+    const int tid = threadIdx.x;
+    const int M = a.M, N = a.N, T = a.T, H = a.H;
+    const double* rew = a.reward;
+    const double* sca = a.scaled;
+    if constexpr (kLds) {
+        double* tab = reinterpret_cast<double*>(s_mem);
+        for (int j = tid; j < N * T; j += kTpTile) {
+            tab[j] = a.reward[j];
+            tab[N * T + j] = a.scaled[j];
+        }
+        __syncthreads();
+        rew = tab;
+        sca = tab + N * T;
+    }
+    const int64_t m = (int64_t)blockIdx.x * kTpTile + tid;
+    if (m >= M) return;
+
+    TpSeats<MAXN> v;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < MAXN; i++) {
+        if (i >= N) break;
+        const int64_t g = a.seat[(int64_t)i * M + m];
+        const bool in = g >= 0 && g < a.G;
+        ok = ok && in;
+        v.gp[i] = a.policy + ((in ? g : 0) * N + i) * T;
+    }
+    const int t0 = a.start[m];
+    ok = ok && t0 >= 0 && t0 < T;
+    const int64_t plane = (int64_t)N * M;
+    const int n_rows = a.row_count;
+
+    if (!ok) {                                          // the stated sentinel: mu = -1, lam = 0 and zeros
+        a.mu[m] = -1;
+        a.lam[m] = 0;
+        if (a.cycle_start) a.cycle_start[m] = -1;
+        for (int i = 0; i < N; i++) {
+            a.cycle_reward[(int64_t)i * M + m] = 0.0;
+            a.cycle_action[(int64_t)i * M + m] = 0.0;
+            for (int rr = 0; rr < n_rows; rr++) {
+                const int64_t o = (int64_t)rr * plane + (int64_t)i * M + m;
+                if (a.reward_rows) a.reward_rows[o] = 0.0;
+                if (a.action_rows) a.action_rows[o] = 0.0;
+            }
+        }
+        return;
+    }
+
+    // Brent, the search of k_xplay_walk: found iff mu + lam <= H; phase 1 stops at hare position 3H
+    int tort = t0, hare = tp_next<MAXN>(a, v, t0);
+    int power = 1, l = 1, pos = 1;
+    bool det = false;
+    for (;;) {
+        if (tort == hare) { det = true; break; }
+        if (pos >= 3 * H) break;
+        if (power == l) { tort = hare; power <<= 1; l = 0; }
+        hare = tp_next<MAXN>(a, v, hare);
+        l++;
+        pos++;
+    }
+    bool found = det && l <= H;
+    int mu = 0;
+    if (found) {
+        tort = t0;
+        hare = t0;
+        for (int j = 0; j < l; j++) hare = tp_next<MAXN>(a, v, hare);
+        while (tort != hare) {
+            if (mu + l >= H) { found = false; break; }
+            tort = tp_next<MAXN>(a, v, tort);
+            hare = tp_next<MAXN>(a, v, hare);
+            mu++;
+        }
+    }
+    const int lam = found ? l : 0;
+    if (!found) mu = H;
+
+    double cr[MAXN], ca[MAXN];
+#pragma unroll
+    for (int i = 0; i < MAXN; i++) { cr[i] = 0.0; ca[i] = 0.0; }
+    if (lam > 0) {
+        int x = tort;
+        for (int j = 0; j < lam; j++) {
+            x = tp_next<MAXN>(a, v, x);
+#pragma unroll
+            for (int i = 0; i < MAXN; i++)
+                if (i < N) { cr[i] = __dadd_rn(cr[i], rew[i * T + x]); ca[i] = __dadd_rn(ca[i], sca[i * T + x]); }
+        }
+#pragma unroll
+        for (int i = 0; i < MAXN; i++)
+            if (i < N) { cr[i] = __ddiv_rn(cr[i], (double)lam); ca[i] = __ddiv_rn(ca[i], (double)lam); }
+    }
+    a.mu[m] = mu;
+    a.lam[m] = lam;
+    if (a.cycle_start) a.cycle_start[m] = lam > 0 ? tort : -1;
+#pragma unroll
+    for (int i = 0; i < MAXN; i++) {
+        if (i >= N) break;
+        a.cycle_reward[(int64_t)i * M + m] = cr[i];
+        a.cycle_action[(int64_t)i * M + m] = ca[i];
+    }
+
+    // the path from t_0: the rows of tau in [row_begin, row_begin + row_count)
+    if (n_rows > 0 && (a.reward_rows || a.action_rows)) {
+        int x = t0;
+        const int end = a.row_begin + n_rows;
+        for (int tau = 0; tau < end; tau++) {
+            x = tp_next<MAXN>(a, v, x);
+            const int rr = tau - a.row_begin;
+            if (rr >= 0) {
+#pragma unroll
+                for (int i = 0; i < MAXN; i++) {
+                    if (i >= N) break;
+                    const int64_t o = (int64_t)rr * plane + (int64_t)i * M + m;
+                    if (a.reward_rows) a.reward_rows[o] = rew[i * T + x];
+                    if (a.action_rows) a.action_rows[o] = sca[i * T + x];
+                }
+            }
+        }
+    }
+}
+
+template <bool kLds>
+void launch_walk_n(const TpWalkArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)(((int64_t)a.M + kTpTile - 1) / kTpTile)), block(kTpTile);
+    const size_t lds = (size_t)a.lds_bytes;
+    if (a.N <= 2) hipLaunchKernelGGL((k_tp_walk<kLds, 2>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((k_tp_walk<kLds, THRL_MAXA>), grid, block, lds, s, a);
+}
+
+}  // namespace
+
+int launch_tp_policy(const TpPolicyArgs& a, int q_dtype, hipStream_t s) {
+    if (a.n_q > 0) {
+        const int64_t n = (int64_t)a.G * a.T;
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        if (q_dtype == 1) hipLaunchKernelGGL(k_tp_qtable<double>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(k_tp_qtable<float>, grid, block, 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    for (int j = 0; j < a.n_nn; j++) {
+        const dim3 grid((unsigned)((a.G + 3) / 4)), block(256);
+        const int A = a.nn_actions[j];
+        uint16_t* out = a.policy + (int64_t)a.nn_agent[j] * a.T;
+        const int64_t os = (int64_t)a.N * a.T;
+        // the padding k_nn_act takes for this action count
+        if (A <= 8) hipLaunchKernelGGL(k_tp_neural<8>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, out, os);
+        else if (A <= 24) hipLaunchKernelGGL(k_tp_neural<24>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, out, os);
+        else hipLaunchKernelGGL(k_tp_neural<32>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, out, os);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return (int)hipSuccess;
+}
+
+int launch_tp_walk(const TpWalkArgs& a, hipStream_t s) {
+    if (a.in_lds) launch_walk_n<true>(a, s);
+    else launch_walk_n<false>(a, s);
+    return (int)hipGetLastError();
+}
+
+}  // namespace thrl

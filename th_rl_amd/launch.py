@@ -336,11 +336,21 @@ def _worker(rank, world, port, config, out, devices_available):
     dist.destroy_process_group()
 
 
+def check_launch_config(config):
+    """ValueError for a training key that has no sharded form: training.greedy_cycles re-seats agents across games and
+    its merge over shards is not built."""
+    gc = config.get("training", {}).get("greedy_cycles")
+    if gc is not None and gc is not False:
+        raise ValueError("training.greedy_cycles is not available under th_rl_amd.launch (sharded runs are not merged); "
+                         "run it through th_rl_amd.main / trainer.train_one on one device")
+
+
 def launch(configpath, out, gpus=None):
     """Train `configpath` with its games sharded over `gpus` processes (default: all visible GPUs)."""
     import torch
     import torch.multiprocessing as mp
     config = json.load(open(configpath))
+    check_launch_config(config)                # before any shard starts
     avail = torch.cuda.device_count()          # device_count() does not initialise the GPU
     if avail < 1:
         from th_rl_amd._lib import ThrlError

@@ -352,6 +352,19 @@ class MixedGameBatch:
         return sn.run(self, noise_prob=noise_prob, start=start, state0=state0, tol=tol, max_iters=max_iters, pi=pi, q=q,
                       policy=policy, n_games=n_games)
 
+    def greedy_cycles(self, seats=None, start=None, steps=0, rows=False, horizon=None, tuple_policy=None,
+                      group_stats=None, budget=None):
+        """The limit cycle of greedy play for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_play.run):
+        every agent's strategy as a table over the game's action tuples (thrl_tuple_policy), then a walk on tuple
+        indices (thrl_tuple_walk).  seats (default: every game's own agents) re-seat agents across games as
+        crossplay does; start (default: the tuple whose price is the state of seat 0's game, -1 when the state is
+        no tuple's price: that match gets mu = -1).  A batch with a CAC agent raises ValueError."""
+        from . import tuple_play as tp
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return tp.run(self, seats=seats, start=start, steps=steps, rows=rows, horizon=horizon,
+                      tuple_policy=tuple_policy, group_stats=group_stats, budget=budget or tp.ROW_BUDGET)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

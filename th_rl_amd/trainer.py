@@ -274,6 +274,10 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         st_opt = stationary_options(training["stationary"], config)       # refuses neural agents before training
     if st_opt is not None and st_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
         raise ValueError('training.stationary.tables = "converged" needs training.convergence with "snapshot": true')
+    gc_opt = None
+    if training.get("greedy_cycles") is not None and training.get("greedy_cycles") is not False:
+        from th_rl_amd.tuple_play import parse_options as greedy_cycle_options
+        gc_opt = greedy_cycle_options(training["greedy_cycles"], config)  # refuses CAC and too many tuples before training
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -360,6 +364,12 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         if n_rounds > MAX_POOLED_ROUNDS:
             raise ValueError("training.crossplay: group_stats pools the rows of at most %d rounds, this run has %d"
                              % (MAX_POOLED_ROUNDS, n_rounds))
+    if spec is not None and gc_opt is not None and gc_opt["steps"] > 0:
+        from th_rl_amd.crossplay import MAX_POOLED_ROUNDS
+        n_rounds = 1 + gc_opt["rounds"] * (spec.n_groups if gc_opt["against"] == "all" else 1)
+        if n_rounds > MAX_POOLED_ROUNDS:
+            raise ValueError("training.greedy_cycles: group_stats pools the rows of at most %d rounds (the self-play "
+                             "round included), this run has %d" % (MAX_POOLED_ROUNDS, n_rounds))
     if spec is not None:
         from th_rl_amd.group_stats import save_json
         save_json(os.path.join(exp_path, "groups.json"), spec.describe())
@@ -553,6 +563,17 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
                 q_st, s_st = tracker.tables_at_convergence()
         write_stationary(exp_path, batch, config, st_opt, ids, n_groups, q=q_st, state0=s_st,
                          with_attractors=at_opt is not None)
+
+    if gc_opt is not None:      # the limit cycle of greedy play, neural agents included (tuple_play.py)
+        from th_rl_amd.tuple_play import write_artefacts as write_greedy_cycles
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        write_greedy_cycles(exp_path, batch, config, gc_opt, ids, n_groups, spec=spec,
+                            histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

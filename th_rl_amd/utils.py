@@ -292,6 +292,57 @@ def crossplay_games(exp_path, round=0):
     return pandas.concat(frames)
 
 
+def greedy_cycle_summary(exp_path):
+    """A run's greedy cycles (training.greedy_cycles, any mix of QTable / Reinforce / ActorCritic agents):
+    greedy_cycles.json as a pair of DataFrames.  The first has one row per group for the self-play round -- matches,
+    no_start (games whose state is no tuple's price), cycles, fixed_points, the profit gain's mean and quantiles
+    (delta_*) and one lam_<bin> column per bin of the lam histogram; the second one row per (group of seat 0,
+    partner_group) over the re-seated rounds, with crossplay_summary's columns and no_start (empty without such
+    rounds).  Both carry Nash and Cartel."""
+    import json
+    with open(os.path.join(exp_path, "greedy_cycles.json")) as f:
+        desc = json.load(f)
+
+    def frame(rows):
+        out = []
+        for r in rows:
+            r = dict(r)
+            for name, n in zip(desc["lam_bins"], r.pop("lam_hist")):
+                r["lam_" + name] = n
+            for i, v in enumerate(r.pop("seat_gain", [])):
+                r["seat_gain_%d" % i] = v
+            out.append(r)
+        df = pandas.DataFrame(out)
+        df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+        return df
+
+    return frame(desc["self_play"]), frame(desc["summary"])
+
+
+def greedy_cycle_games(exp_path, round=0):
+    """Per-match results of round `round` of training.greedy_cycles (0 = every game's own agents, k >= 1 the k-th
+    re-seating), one row per match indexed by the GLOBAL id of seat 0's game: seat_<i> (global game ids), start (the
+    start tuple, -1 = none), mu, lam, cycle_start, cycle_reward_<i> / cycle_action_<i> and the profit gain delta."""
+    import json
+    from th_rl_amd import tuple_play as tp
+    if not os.path.isfile(os.path.join(exp_path, "gcyc_cycle.npy")):
+        raise KeyError("no greedy cycles (gcyc_cycle.npy) under %s (training.greedy_cycles)" % exp_path)
+    with open(os.path.join(exp_path, "greedy_cycles.json")) as f:
+        desc = json.load(f)
+    g = tp.load_games(exp_path)
+    r = int(round)
+    if not 0 <= r < g["seats"].shape[0]:
+        raise KeyError("round %d out of [0, %d)" % (r, g["seats"].shape[0]))
+    seats = g["seats"][r]
+    cols = {"seat_%d" % i: seats[i] for i in range(seats.shape[0])}
+    cols.update(start=g["start"][r], mu=g["mu"][r], lam=g["lam"][r], cycle_start=g["cycle_start"][r])
+    for i in range(seats.shape[0]):
+        cols["cycle_reward_%d" % i] = g["cycle_reward"][r, i]
+        cols["cycle_action_%d" % i] = g["cycle_action"][r, i]
+    cols["delta"] = tp.profit_gain(g["cycle_reward"][r], desc["nash"], desc["cartel"])
+    return pandas.DataFrame(cols, index=pandas.Index(seats[0], name="game"))
+
+
 def attractor_summary(exp_path):
     """A run's attractor analysis (training.attractors): attractors.json's summary as a DataFrame with one row per
     group -- games, single, the quantiles of n_attr and mu_max, delta_train_mean / delta_largest_mean /
