@@ -989,6 +989,141 @@ typedef struct {
 } thrl_tuple_walk_args;
 int thrl_tuple_walk(const thrl_cfg* cfg, const thrl_tuple_walk_args* args, void* stream);
 
+/*
+ * Deviation test and equilibrium check in tuple form, for ANY mix of QTable, Reinforce and ActorCritic agents:
+ * thrl_deviation and thrl_equilibrium on the arrays thrl_tuple_policy and th_rl_amd.tuple_play.tables produce.  No
+ * reference counterpart.  Both calls read tuple_policy (device uint16 [G][N][T], G = args.n_games >= 1), reward (device
+ * float64 [N][T]) and start (device int32 [G], the start tuple t_0 of game g, -1 = none); thrl_tuple_deviation also reads
+ * scaled (device float64 [N][T]).  Every game is played by its own agents: there is no seat array.  No table, network
+ * or price is read and nothing of a batch is written.  Of a valid cfg only n_agents, n_actions and gamma are used.  All
+ * arithmetic is float64, every operation rounded once, in the order written here.
+ *
+ * Tuples are numbered with agent 0 slowest: t = sum_i k_i * prod_{j > i} n_actions_j, T = args.n_tuples =
+ * prod_i n_actions_i, 1 <= T <= THRL_TP_MAX_TUPLES.  pi_i(t) = tuple_policy[g][i][t], entries at or above n_actions_i
+ * clamped to n_actions_i - 1 (the caller's to avoid; nothing is read out of bounds).  The greedy map is
+ * F(t) = the index of the tuple (pi_i(t))_i.
+ * THE TRANSITION TAKEN AT t (thrl_tuple_walk's meaning, used by both calls): at t the agents play a tuple u -- F(t) when
+ * all are greedy -- and the game moves to u; the reward and scaled action of that transition are reward[i][u] and
+ * scaled[i][u].
+ *
+ * thrl_tuple_deviation: thrl_deviation with "row tuple x" replaced by "tuple index t" and x_0 by start[g].
+ * Pre-shock cycle: t_{k+1} = F(t_k); mu >= 0, lam >= 1 the smallest values with t_{mu+lam} = t_mu.  The cycle is found
+ * iff mu + lam <= H (horizon); then s* = t_mu.  Otherwise lam = 0, mu = H and s* = t_H (so s* = t_mu in both cases).
+ * Cycle detection keeps O(1) state per game (Brent) with a step budget that decides "found" exactly by mu + lam <= H.
+ *   cycle_reward[i][g] = (sum_{j<lam} reward_i of the transition taken at F^j(s*), added in that order from 0.0) / lam,
+ *   cycle_action the same for the scaled action; both 0 when lam = 0.
+ * Deviation path y_0 = s*: for tau < L agent d plays dev_action, or with dev_action = -1 its one-period best response
+ * at y_tau: the argmax over k < n_actions_d of reward[d][t'], t' the tuple with k in place d and pi_j(y_tau) in the
+ * other places (first maximum under strict >); the others play pi_j(y_tau); y_{tau+1} = the tuple played.  For
+ * tau >= L every agent is greedy: y_{tau+1} = F(y_tau).  act_dev[g] = d's action at tau = 0.  Rows reward_rows /
+ * action_rows [row_count][N][G] hold, for tau in [row_begin, row_begin + row_count), the rewards and scaled actions of
+ * the transition taken at y_tau: the layout of the episode rows, so thrl_group_stats reduces them as they are
+ * (E = row_count).  The kernel walks the whole path whatever rows it stores.
+ * Baseline path z_0 = s*, every agent greedy.
+ * gain[g] = sum_{tau<K} w_tau * (r_d(y_tau) - r_d(z_tau)), r_d(.) agent d's reward of the transition taken there,
+ *   w_0 = 1, w_{tau+1} = w_tau * gamma_d, each operation rounded once (subtract, multiply, add);
+ *   gamma_d = sweep_gamma[d][g] when given, else cfg.gamma[d].
+ * Return: (mu_post, lam_post) = the cycle of F from y_L under the same horizon rule; ret_step[g] = L + mu_post if that
+ *   cycle is found and s* lies on it, else -1 (always -1 when lam = 0).
+ * A game with start[g] < 0 or start[g] >= T is refused: mu = -1, lam = 0, mu_post = lam_post = 0, ret_step = -1,
+ * act_dev = -1, zeros in cycle_reward, cycle_action, gain and its rows.  No other game is affected.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games < 1, a deviator outside [0, N), dev_len < 1, n_steps < dev_len or
+ * > THRL_DEV_MAX_STEPS, horizon outside [1, THRL_DEV_MAX_HORIZON], dev_action outside {-1} + [0, n_actions[d]), a row
+ * range outside [0, n_steps), reserved != 0, n_tuples < 1 or n_tuples != prod_i n_actions_i; THRL_ERR_UNSUPPORTED for
+ * n_tuples > THRL_TP_MAX_TUPLES; THRL_ERR_NULL for a missing cfg, args, start, tuple_policy, reward, scaled or per-game
+ * output.
+ */
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of tuple_policy                    */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t deviator;                /* d in [0, N)                                      */
+    int32_t dev_len;                 /* L >= 1                                           */
+    int32_t n_steps;                 /* K >= L                                           */
+    int32_t horizon;                 /* H >= 1 (th_rl_amd: min(T + 1, 65536))            */
+    int32_t dev_action;              /* fixed action index of d, or -1 = best response   */
+    int32_t row_begin;               /* rows stored: tau in [row_begin, row_begin + row_count) */
+    int32_t row_count;
+    int32_t reserved;                /* 0                                                */
+    const int32_t* start;            /* device [G]: start tuple t_0, outside [0, T) = refused */
+    const uint16_t* tuple_policy;    /* device [G][N][T]                                 */
+    const double* reward;            /* device [N][T]                                    */
+    const double* scaled;            /* device [N][T]                                    */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    int32_t* mu;                     /* device outputs [G]                               */
+    int32_t* lam;
+    int32_t* mu_post;
+    int32_t* lam_post;
+    int32_t* ret_step;
+    int32_t* act_dev;
+    double*  cycle_reward;           /* device [N][G]                                    */
+    double*  cycle_action;           /* device [N][G]                                    */
+    double*  gain;                   /* device [G]                                       */
+    double*  reward_rows;            /* device [row_count][N][G] or NULL                 */
+    double*  action_rows;            /* device [row_count][N][G] or NULL                 */
+} thrl_tuple_deviation_args;
+int thrl_tuple_deviation(const thrl_cfg* cfg, const thrl_tuple_deviation_args* args, void* stream);
+
+/*
+ * thrl_tuple_equilibrium: thrl_equilibrium with the state set replaced by the T tuples, so S = T and state(t) = t.
+ * Agent i's problem in game g.  pi_j(s) as above.  t(s, a) = the tuple with a in place i and pi_j(s) elsewhere,
+ * R(s, a) = reward[i][t(s, a)] (the reward of the transition taken at s), nxt(s, a) = t(s, a).
+ * gamma = sweep_gamma[i][g] when given, else cfg.gamma[i].  Without sweep_gamma, cfg.gamma[i] outside [0, 1) for a
+ * selected agent is THRL_ERR_BAD_CONFIG; a game whose sweep gamma is not in [0, 1) is not solved and gets iters = -1,
+ * n_diff_all = n_diff_on = 0 and NaN in every float64 output of that agent (br_policy, v_opt, v_pi are not written).
+ *
+ * Evaluation of a strategy sigma by doubling: V = R(., sigma), n = nxt(., sigma), w = gamma; D times, for all states
+ * at once from the old V and n:  V = V + w * V[n];  n = n[n];  w = w * w.   D = the number of squarings w = w * w
+ * (from w = gamma) until w < 2^-64, stopping at 64.
+ * Policy iteration from the agent's own strategy: sigma_0 = pi_i.  Round k = 0, 1, ..: V_k = evaluation of sigma_k;
+ * if k == THRL_EQ_MAX_ITERS stop with iters = -1; Q(s, a) = R(s, a) + gamma * V_k[nxt(s, a)];
+ * sigma_{k+1}(s) = sigma_k(s) unless max_a Q(s, a) > Q(s, sigma_k(s)), then the first maximum (strict >, a ascending);
+ * if no state changed stop with iters = k.  V_pi = V_0, V* = the last V_k, sigma* = the last strategy.  The incumbent
+ * is kept on ties, so a strategy that is a best response gives iters = 0 and V* == V_pi bit for bit.
+ *   loss(s) = 0.0 where V*(s) == V_pi(s) or V*(s) == 0, else (V*(s) - V_pi(s)) / V*(s).
+ *
+ * Path.  t_0 = start[g], t_{k+1} = F(t_k); mu >= 0, lam >= 1 the smallest values with t_{mu+lam} = t_mu:
+ * thrl_tuple_walk's mu and lam for a horizon of at least T + 1.  "On path" = the lam tuples t_mu .. t_{mu+lam-1}, in
+ * that ("cycle") order.
+ *
+ * Outputs, per selected agent i (bit i of agents) and game; entries of agents not selected are not written:
+ *   iters, n_diff_all, n_diff_on   states / cycle states with sigma*(s) != pi_i(s)
+ *   loss_all, loss_on              the largest loss(s) over all states / cycle states
+ *   loss_all_mean, loss_on_mean    (sum of loss(s) from 0.0 in state order / cycle order) / T, / lam
+ *   v_on                           (sum of V_pi(s) from 0.0 in cycle order) / lam
+ *   br_policy, v_opt, v_pi         optional [N][G][T]: sigma*, V*, V_pi per state
+ * A game with start[g] < 0 or start[g] >= T has no path: mu = -1, lam = 0, n_diff_on = 0 and NaN in loss_on,
+ * loss_on_mean and v_on; its all-states outputs are computed as for any game.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games < 1, agents == 0 or with a bit >= N, gamma as above, reserved != 0,
+ * n_tuples < 1 or n_tuples != prod_i n_actions_i; THRL_ERR_UNSUPPORTED for n_tuples > THRL_TP_MAX_TUPLES;
+ * THRL_ERR_NULL for a missing cfg, args, start, tuple_policy, reward or required output.
+ */
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of tuple_policy                    */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t agents;                  /* bit i set: solve agent i                         */
+    int32_t reserved;                /* 0                                                */
+    const int32_t* start;            /* device [G]: start tuple t_0, outside [0, T) = no path */
+    const uint16_t* tuple_policy;    /* device [G][N][T]                                 */
+    const double* reward;            /* device [N][T]                                    */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    int32_t* mu;                     /* device [G]                                       */
+    int32_t* lam;                    /* device [G]                                       */
+    int32_t* iters;                  /* device [N][G]                                    */
+    int32_t* n_diff_all;             /* device [N][G]                                    */
+    int32_t* n_diff_on;              /* device [N][G]                                    */
+    double*  loss_all;               /* device [N][G]                                    */
+    double*  loss_on;                /* device [N][G]                                    */
+    double*  loss_all_mean;          /* device [N][G]                                    */
+    double*  loss_on_mean;           /* device [N][G]                                    */
+    double*  v_on;                   /* device [N][G]                                    */
+    uint16_t* br_policy;             /* device [N][G][T] or NULL                         */
+    double*  v_opt;                  /* device [N][G][T] or NULL                         */
+    double*  v_pi;                   /* device [N][G][T] or NULL                         */
+} thrl_tuple_equilibrium_args;
+int thrl_tuple_equilibrium(const thrl_cfg* cfg, const thrl_tuple_equilibrium_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,37 @@ class TupleWalkArgs(ctypes.Structure):
     ]
 
 
+class TupleDeviationArgs(ctypes.Structure):
+    """thrl_tuple_deviation_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("deviator", ctypes.c_int32),
+        ("dev_len", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("horizon", ctypes.c_int32),
+        ("dev_action", ctypes.c_int32), ("row_begin", ctypes.c_int32), ("row_count", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("start", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+        ("scaled", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p),
+        ("mu", ctypes.c_void_p), ("lam", ctypes.c_void_p), ("mu_post", ctypes.c_void_p), ("lam_post", ctypes.c_void_p),
+        ("ret_step", ctypes.c_void_p), ("act_dev", ctypes.c_void_p),
+        ("cycle_reward", ctypes.c_void_p), ("cycle_action", ctypes.c_void_p), ("gain", ctypes.c_void_p),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p),
+    ]
+
+
+class TupleEquilibriumArgs(ctypes.Structure):
+    """thrl_tuple_equilibrium_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("agents", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("start", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+        ("sweep_gamma", ctypes.c_void_p),
+        ("mu", ctypes.c_void_p), ("lam", ctypes.c_void_p), ("iters", ctypes.c_void_p),
+        ("n_diff_all", ctypes.c_void_p), ("n_diff_on", ctypes.c_void_p),
+        ("loss_all", ctypes.c_void_p), ("loss_on", ctypes.c_void_p), ("loss_all_mean", ctypes.c_void_p),
+        ("loss_on_mean", ctypes.c_void_p), ("v_on", ctypes.c_void_p),
+        ("br_policy", ctypes.c_void_p), ("v_opt", ctypes.c_void_p), ("v_pi", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -240,7 +271,7 @@ SYMBOLS = [
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
-    "thrl_tuple_policy", "thrl_tuple_walk",
+    "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
 ]
 CAC_PARAMS = 1283
 
@@ -355,6 +386,10 @@ def load():
     L.thrl_tuple_policy.argtypes = [cfgp, vp, ctypes.POINTER(TuplePolicyArgs), vp]
     L.thrl_tuple_walk.restype = ctypes.c_int
     L.thrl_tuple_walk.argtypes = [cfgp, ctypes.POINTER(TupleWalkArgs), vp]
+    L.thrl_tuple_deviation.restype = ctypes.c_int
+    L.thrl_tuple_deviation.argtypes = [cfgp, ctypes.POINTER(TupleDeviationArgs), vp]
+    L.thrl_tuple_equilibrium.restype = ctypes.c_int
+    L.thrl_tuple_equilibrium.argtypes = [cfgp, ctypes.POINTER(TupleEquilibriumArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -17,6 +17,7 @@
 #include "thrl_deviation.h"
 #include "thrl_equilibrium.h"
 #include "thrl_kernels.h"
+#include "thrl_tuple_analysis.h"
 #include "thrl_tuple_play.h"
 #include "thrl_wave_lut.h"
 
@@ -1662,6 +1663,119 @@ int thrl_tuple_walk(const thrl_cfg* c, const thrl_tuple_walk_args* x, void* stre
     a.reward_rows = x->reward_rows; a.action_rows = x->action_rows;
     const int e = thrl::launch_tp_walk(a, (hipStream_t)stream);
     return e ? hip_fail(e, "k_tp_walk launch") : THRL_OK;
+}
+
+int thrl_tuple_deviation(const thrl_cfg* c, const thrl_tuple_deviation_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", x->n_games);
+    if (x->deviator < 0 || x->deviator >= N)
+        return fail(THRL_ERR_BAD_CONFIG, "deviator=%d out of [0,%d)", x->deviator, N);
+    if (x->dev_len < 1) return fail(THRL_ERR_BAD_CONFIG, "dev_len=%d must be >= 1", x->dev_len);
+    if (x->n_steps < x->dev_len || x->n_steps > THRL_DEV_MAX_STEPS)
+        return fail(THRL_ERR_BAD_CONFIG, "n_steps=%d out of [dev_len=%d, %d]", x->n_steps, x->dev_len, THRL_DEV_MAX_STEPS);
+    if (x->horizon < 1 || x->horizon > THRL_DEV_MAX_HORIZON)
+        return fail(THRL_ERR_BAD_CONFIG, "horizon=%d out of [1,%d]", x->horizon, THRL_DEV_MAX_HORIZON);
+    if (x->dev_action < -1 || x->dev_action >= c->n_actions[x->deviator])
+        return fail(THRL_ERR_BAD_CONFIG, "dev_action=%d: -1 (best response) or an action of agent %d in [0,%d)",
+                    x->dev_action, x->deviator, c->n_actions[x->deviator]);
+    if (x->row_begin < 0 || x->row_count < 0 || (int64_t)x->row_begin + x->row_count > x->n_steps)
+        return fail(THRL_ERR_BAD_CONFIG, "rows [%d, %d + %d) outside [0, n_steps=%d)", x->row_begin, x->row_begin,
+                    x->row_count, x->n_steps);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (!x->start || !x->tuple_policy || !x->reward || !x->scaled || !x->mu || !x->lam || !x->mu_post || !x->lam_post
+        || !x->ret_step || !x->act_dev || !x->cycle_reward || !x->cycle_action || !x->gain)
+        return fail(THRL_ERR_NULL, "start / tuple_policy / reward / scaled / mu / lam / mu_post / lam_post / ret_step / "
+                                   "act_dev / cycle_reward / cycle_action / gain is NULL");
+    TaDevArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples; a.H = x->horizon; a.d = x->deviator; a.L = x->dev_len;
+    a.K = x->n_steps; a.dev_action = x->dev_action; a.row_begin = x->row_begin; a.row_count = x->row_count;
+    int stride = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        a.n_actions[i] = c->n_actions[i];
+        a.tstride[i] = stride;
+        stride *= c->n_actions[i];
+    }
+    a.gamma_d = c->gamma[x->deviator];
+    const int64_t lds = (int64_t)2 * N * a.T * 8;
+    a.in_lds = lds <= kTaDevLdsBudget;
+    a.lds_bytes = a.in_lds ? (int32_t)lds : 0;
+    a.start = x->start; a.policy = x->tuple_policy; a.reward = x->reward; a.scaled = x->scaled;
+    a.sweep_gamma = x->sweep_gamma;
+    a.mu = x->mu; a.lam = x->lam; a.mu_post = x->mu_post; a.lam_post = x->lam_post; a.ret_step = x->ret_step;
+    a.act_dev = x->act_dev; a.cycle_reward = x->cycle_reward; a.cycle_action = x->cycle_action; a.gain = x->gain;
+    a.reward_rows = x->reward_rows; a.action_rows = x->action_rows;
+    const int e = thrl::launch_ta_deviation(a, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_ta_deviation launch") : THRL_OK;
+}
+
+int thrl_tuple_equilibrium(const thrl_cfg* c, const thrl_tuple_equilibrium_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", x->n_games);
+    if (x->agents == 0 || (x->agents & ~((1 << N) - 1)))
+        return fail(THRL_ERR_BAD_CONFIG, "agents=0x%x: a non-empty mask of agents in [0,%d)", x->agents, N);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (!x->sweep_gamma)
+        for (int i = 0; i < N; i++)
+            if (((x->agents >> i) & 1) && !(c->gamma[i] >= 0.0 && c->gamma[i] < 1.0))
+                return fail(THRL_ERR_BAD_CONFIG, "agent %d: gamma=%g: the equilibrium check needs gamma in [0, 1)", i,
+                            c->gamma[i]);
+    if (!x->start || !x->tuple_policy || !x->reward || !x->mu || !x->lam || !x->iters || !x->n_diff_all
+        || !x->n_diff_on || !x->loss_all || !x->loss_on || !x->loss_all_mean || !x->loss_on_mean || !x->v_on)
+        return fail(THRL_ERR_NULL, "start / tuple_policy / reward / mu / lam / iters / n_diff_all / n_diff_on / loss_all / "
+                                   "loss_on / loss_all_mean / loss_on_mean / v_on is NULL");
+    TaEqArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples; a.agents = x->agents;
+    int ts = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        a.n_actions[i] = c->n_actions[i];
+        a.tstride[i] = ts;
+        ts *= c->n_actions[i];
+        a.gamma[i] = c->gamma[i];
+    }
+    // LDS of a block: 8-byte arrays first, then 2-byte (each padded to 16 bytes), then the fixed words: at most
+    // kTaEqLdsPerTuple * T + kTaEqLdsFixed + 144 bytes, 144.3 KB at T = 4096, whatever N is
+    const int T = a.T;
+    const int b8 = (8 * T + 15) & ~15, b2 = (2 * T + 15) & ~15;
+    int off = 0;
+    a.o_va = off; off += b8;
+    a.o_vb = off; off += b8;
+    a.o_rew = off; off += b8;
+    a.o_na = off; off += b2;
+    a.o_nb = off; off += b2;
+    a.o_sigma = off; off += b2;
+    a.o_jn = off; off += b2;
+    a.o_mark = off; off += b2;
+    a.o_base = off; off += b2;
+    a.o_misc = off; off += kTaEqLdsFixed;
+    a.lds_bytes = off;
+    a.start = x->start; a.policy = x->tuple_policy; a.reward = x->reward; a.sweep_gamma = x->sweep_gamma;
+    a.mu = x->mu; a.lam = x->lam; a.iters = x->iters; a.n_diff_all = x->n_diff_all; a.n_diff_on = x->n_diff_on;
+    a.loss_all = x->loss_all; a.loss_on = x->loss_on; a.loss_all_mean = x->loss_all_mean;
+    a.loss_on_mean = x->loss_on_mean; a.v_on = x->v_on;
+    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    if (lds_cu > 0 && a.lds_bytes > lds_cu)          // cannot happen on a 160 KB CU within THRL_TP_MAX_TUPLES
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_tuple_equilibrium: %d bytes of LDS per game, the device has %d", a.lds_bytes, lds_cu);
+    int per_cu = kTaEqMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_ta_equilibrium(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_ta_equilibrium launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,465 @@
+// thrl_tuple_analysis.hip -- the deviation test and the equilibrium check for strategies in tuple form
+// (thrl_tuple_deviation, thrl_tuple_equilibrium, include/thrl.h): thrl_deviation and thrl_equilibrium for any mix of
+// QTable, Reinforce and ActorCritic agents, on the uint16 tables thrl_tuple_policy writes.  No encode, no network and
+// no env arithmetic: rewards and scaled actions are looked up in the caller's per-config tables.  Two kernels.
+//
+// k_ta_deviation: one lane per game, k_tp_walk's shape.  The walk (Brent, the deviation and baseline paths in
+//   lockstep, the return) runs on a single integer; the 2-byte policy entries it visits are gathered from global
+//   memory and the reward / scaled tables sit in LDS when they fit kTaDevLdsBudget.
+// k_ta_equilibrium: one 256-thread block per game, looping over games; lanes own the states s = tid, tid + 256, ..
+//   (at most 16 each).  The state set is the T tuples, up to four times thrl_equilibrium's 1024 states, and every
+//   doubling pass of an evaluation depends on the whole previous pass, so four waves share a game.  LDS holds, per
+//   tuple, the two V buffers and the two jump tables of the evaluation, sigma, the joint map, the other agents' base
+//   tuple and the solved agent's reward row: 36 bytes, 144 KB at T = 4096.  The strategies themselves are read from
+//   tuple_policy with coalesced loads (a handful of sweeps per agent), and V_pi stays in the owning lane's registers
+//   until the losses are formed; it then replaces V* in LDS for the sums along the cycle.  What has to be done in a
+//   stated order is done by one wave alone: wave 0 walks the path and adds the losses in state order, wave 1 adds
+//   along the cycle.  Nothing depends on the grid size or on which block takes which game.
+#include "thrl_tuple_analysis.h"
+
+namespace thrl {
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ deviation
+template <int MAXN>
+struct TaView {
+    const uint16_t* gp[MAXN];       // agent i's T entries of this lane's game
+};
+
+template <int MAXN>
+__device__ __forceinline__ int ta_act(const TaDevArgs& a, const TaView<MAXN>& v, int i, int t) {
+    return min((int)v.gp[i][t], a.n_actions[i] - 1);
+}
+
+// F(t): the index of the tuple the game's agents play at t
+template <int MAXN>
+__device__ __forceinline__ int ta_next(const TaDevArgs& a, const TaView<MAXN>& v, int t) {
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < MAXN; i++)
+        if (i < a.N) n += ta_act<MAXN>(a, v, i, t) * a.tstride[i];
+    return n;
+}
+
+// Cycle of F from t0 within the horizon H, find_cycle of thrl_deviation.hip on one integer.  Found iff mu + lam <= H:
+// then s = t_mu.  Otherwise mu = H, lam = 0 and s = t_H (when want_s).
+template <int MAXN>
+__device__ __forceinline__ bool ta_cycle(const TaDevArgs& a, const TaView<MAXN>& v, int t0, int& mu, int& lam, int& s,
+                                         bool want_s) {
+    const int H = a.H;
+    int tort = t0, hare = ta_next<MAXN>(a, v, t0);
+    int power = 1, l = 1, pos = 1;
+    bool det = false;
+    for (;;) {
+        if (tort == hare) { det = true; break; }
+        if (pos >= 3 * H) break;
+        if (power == l) { tort = hare; power <<= 1; l = 0; }
+        hare = ta_next<MAXN>(a, v, hare);
+        l++;
+        pos++;
+    }
+    bool found = det && l <= H;
+    int m = 0;
+    if (found) {
+        tort = t0;
+        hare = t0;
+        for (int j = 0; j < l; j++) hare = ta_next<MAXN>(a, v, hare);
+        while (tort != hare) {
+            if (m + l >= H) { found = false; break; }
+            tort = ta_next<MAXN>(a, v, tort);
+            hare = ta_next<MAXN>(a, v, hare);
+            m++;
+        }
+    }
+    if (found) {
+        mu = m;
+        lam = l;
+        s = tort;
+    } else {
+        mu = H;
+        lam = 0;
+        if (want_s) {
+            s = t0;
+            for (int j = 0; j < H; j++) s = ta_next<MAXN>(a, v, s);
+        }
+    }
+    return found;
+}
+
+template <bool kLds, int MAXN>
+__global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) {
+    extern __shared__ __align__(16) unsigned char s_mem[];
+    const int tid = threadIdx.x;
+    const int G = a.G, N = a.N, T = a.T;
+    const double* rew = a.reward;
+    const double* sca = a.scaled;
+    if constexpr (kLds) {
+        double* tab = reinterpret_cast<double*>(s_mem);
+        for (int j = tid; j < N * T; j += kTaDevTile) {
+            tab[j] = a.reward[j];
+            tab[N * T + j] = a.scaled[j];
+        }
+        __syncthreads();
+        rew = tab;
+        sca = tab + N * T;
+    }
+    const int64_t g = (int64_t)blockIdx.x * kTaDevTile + tid;
+    if (g >= G) return;
+    const int64_t plane = (int64_t)N * G;
+    const int t0 = a.start[g];
+
+    if (t0 < 0 || t0 >= T) {                            // the stated refusal: nothing of the game is read
+        a.mu[g] = -1;
+        a.lam[g] = 0;
+        a.mu_post[g] = 0;
+        a.lam_post[g] = 0;
+        a.ret_step[g] = -1;
+        a.act_dev[g] = -1;
+        a.gain[g] = 0.0;
+        for (int i = 0; i < N; i++) {
+            a.cycle_reward[(int64_t)i * G + g] = 0.0;
+            a.cycle_action[(int64_t)i * G + g] = 0.0;
+            for (int rr = 0; rr < a.row_count; rr++) {
+                const int64_t o = (int64_t)rr * plane + (int64_t)i * G + g;
+                if (a.reward_rows) a.reward_rows[o] = 0.0;
+                if (a.action_rows) a.action_rows[o] = 0.0;
+            }
+        }
+        return;
+    }
+
+    TaView<MAXN> v;
+#pragma unroll
+    for (int i = 0; i < MAXN; i++)
+        v.gp[i] = a.policy + (g * N + (i < N ? i : 0)) * T;
+
+    // pre-shock cycle
+    int mu, lam, s;
+    ta_cycle<MAXN>(a, v, t0, mu, lam, s, true);
+    double cr[MAXN], ca[MAXN];
+#pragma unroll
+    for (int i = 0; i < MAXN; i++) { cr[i] = 0.0; ca[i] = 0.0; }
+    if (lam > 0) {
+        int x = s;
+        for (int j = 0; j < lam; j++) {
+            x = ta_next<MAXN>(a, v, x);
+#pragma unroll
+            for (int i = 0; i < MAXN; i++)
+                if (i < N) { cr[i] = __dadd_rn(cr[i], rew[i * T + x]); ca[i] = __dadd_rn(ca[i], sca[i * T + x]); }
+        }
+#pragma unroll
+        for (int i = 0; i < MAXN; i++)
+            if (i < N) { cr[i] = __ddiv_rn(cr[i], (double)lam); ca[i] = __ddiv_rn(ca[i], (double)lam); }
+    }
+
+    // deviation path y and baseline path z, in lockstep
+    const int d = a.d, L = a.L, K = a.K;
+    const int nd = a.n_actions[d], tsd = a.tstride[d];
+    const double* rd = rew + d * T;
+    const double gam = a.sweep_gamma ? a.sweep_gamma[(int64_t)d * G + g] : a.gamma_d;
+    int y = s, z = s, yL = s;
+    double gain = 0.0, w = 1.0;
+    int adev = 0;
+    for (int t = 0; t < K; t++) {
+        if (t < L) {
+            int ub = 0;                                 // the others greedy at y
+#pragma unroll
+            for (int i = 0; i < MAXN; i++)
+                if (i < N && i != d) ub += ta_act<MAXN>(a, v, i, y) * a.tstride[i];
+            int ad = a.dev_action;
+            if (ad < 0) {                               // one-period best response: first maximum of d's reward
+                double bv = 0.0;
+                ad = 0;
+                for (int k = 0; k < nd; k++) {
+                    const double r = rd[ub + k * tsd];
+                    if (k == 0 || r > bv) { bv = r; ad = k; }
+                }
+            }
+            if (t == 0) adev = ad;
+            y = ub + ad * tsd;
+        } else {
+            y = ta_next<MAXN>(a, v, y);
+        }
+        const int rr = t - a.row_begin;
+        if (rr >= 0 && rr < a.row_count) {
+#pragma unroll
+            for (int i = 0; i < MAXN; i++) {
+                if (i >= N) break;
+                const int64_t o = (int64_t)rr * plane + (int64_t)i * G + g;
+                if (a.reward_rows) a.reward_rows[o] = rew[i * T + y];
+                if (a.action_rows) a.action_rows[o] = sca[i * T + y];
+            }
+        }
+        z = ta_next<MAXN>(a, v, z);
+        gain = __dadd_rn(gain, __dmul_rn(w, __dsub_rn(rd[y], rd[z])));
+        w = __dmul_rn(w, gam);
+        if (t + 1 == L) yL = y;
+    }
+
+    // return to the pre-shock cycle
+    int mp, lp, sp = 0;
+    const bool fp = ta_cycle<MAXN>(a, v, yL, mp, lp, sp, false);
+    int ret = -1;
+    if (lam > 0 && fp) {
+        for (int j = 0; j < lp; j++) {
+            if (sp == s) { ret = L + mp; break; }
+            sp = ta_next<MAXN>(a, v, sp);
+        }
+    }
+
+    a.mu[g] = mu;
+    a.lam[g] = lam;
+    a.mu_post[g] = mp;
+    a.lam_post[g] = lp;
+    a.ret_step[g] = ret;
+    a.act_dev[g] = adev;
+    a.gain[g] = gain;
+#pragma unroll
+    for (int i = 0; i < MAXN; i++) {
+        if (i >= N) break;
+        a.cycle_reward[(int64_t)i * G + g] = cr[i];
+        a.cycle_action[(int64_t)i * G + g] = ca[i];
+    }
+}
+
+template <bool kLds>
+void launch_dev_n(const TaDevArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)(((int64_t)a.G + kTaDevTile - 1) / kTaDevTile)), block(kTaDevTile);
+    const size_t lds = (size_t)a.lds_bytes;
+    if (a.N <= 2) hipLaunchKernelGGL((k_ta_deviation<kLds, 2>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((k_ta_deviation<kLds, THRL_MAXA>), grid, block, lds, s, a);
+}
+
+// ------------------------------------------------------------------------------------------------ equilibrium
+constexpr int kTaEqMaxD = 64;
+
+__global__ void __launch_bounds__(kTaEqBlock) k_ta_equilibrium(const TaEqArgs a) {
+    extern __shared__ __align__(16) unsigned char s_mem[];
+    constexpr int B = kTaEqBlock;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = a.T, N = a.N, G = a.G;
+    double* Va = reinterpret_cast<double*>(s_mem + a.o_va);
+    double* Vb = reinterpret_cast<double*>(s_mem + a.o_vb);
+    double* R = reinterpret_cast<double*>(s_mem + a.o_rew);             // the solved agent's reward per tuple
+    uint16_t* na = reinterpret_cast<uint16_t*>(s_mem + a.o_na);
+    uint16_t* nb = reinterpret_cast<uint16_t*>(s_mem + a.o_nb);
+    uint16_t* sigma = reinterpret_cast<uint16_t*>(s_mem + a.o_sigma);
+    uint16_t* jn = reinterpret_cast<uint16_t*>(s_mem + a.o_jn);         // F
+    int16_t* mark = reinterpret_cast<int16_t*>(s_mem + a.o_mark);       // walk: step of the first visit; then sigma* != pi_i
+    uint16_t* base = reinterpret_cast<uint16_t*>(s_mem + a.o_base);     // the tuple of the others' actions, 0 in place i
+    double* red_d = reinterpret_cast<double*>(s_mem + a.o_misc);        // [4] per-wave maxima
+    int32_t* red_i = reinterpret_cast<int32_t*>(s_mem + a.o_misc + 32); // [4] per-wave counts, then mu, lam, t_mu
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+    for (int64_t g = blockIdx.x; g < G; g += gridDim.x) {
+        const uint16_t* __restrict__ pg = a.policy + g * N * T;
+
+        // ---- the joint greedy map, and the path from the start tuple (wave 0 alone: its lanes walk the same words)
+        for (int s = tid; s < T; s += B) {
+            int t = 0;
+            for (int i = 0; i < N; i++) t += min((int)pg[i * T + s], a.n_actions[i] - 1) * a.tstride[i];
+            jn[s] = (uint16_t)t;
+            mark[s] = -1;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int t0 = a.start[g];
+            int mu = -1, lam = 0, cur = 0;
+            if (t0 >= 0 && t0 < T) {
+                cur = t0;
+                int tm = 0;
+                for (int guard = 0; guard <= T; guard++) {
+                    const int f = mark[cur];
+                    if (f >= 0) { mu = f; lam = tm - f; break; }
+                    mark[cur] = (int16_t)tm;
+                    cur = jn[cur];
+                    tm++;
+                }
+            }
+            if (lane == 0) {
+                red_i[4] = mu; red_i[5] = lam; red_i[6] = cur;
+                a.mu[g] = mu;
+                a.lam[g] = lam;
+            }
+        }
+        __syncthreads();
+        const int lam = red_i[5], c0 = red_i[6];
+
+        for (int i = 0; i < N; i++) {
+            if (!((a.agents >> i) & 1)) continue;
+            const int64_t o = (int64_t)i * G + g;
+            const double gam = a.sweep_gamma ? a.sweep_gamma[o] : a.gamma[i];
+            if (!(gam >= 0.0 && gam < 1.0)) {
+                if (tid == 0) {
+                    a.iters[o] = -1; a.n_diff_all[o] = 0; a.n_diff_on[o] = 0;
+                    a.loss_all[o] = nan; a.loss_on[o] = nan; a.loss_all_mean[o] = nan; a.loss_on_mean[o] = nan;
+                    a.v_on[o] = nan;
+                }
+                continue;
+            }
+            int D = 0;
+            for (double w = gam; w >= 0x1p-64 && D < kTaEqMaxD; D++) w = __dmul_rn(w, w);
+            const int nact = a.n_actions[i], ts = a.tstride[i];
+            const uint16_t* __restrict__ pi = pg + i * T;
+            const double* __restrict__ Rg = a.reward + (int64_t)i * T;
+
+            for (int s = tid; s < T; s += B) {
+                int t = 0;
+                for (int j = 0; j < N; j++)
+                    if (j != i) t += min((int)pg[j * T + s], a.n_actions[j] - 1) * a.tstride[j];
+                base[s] = (uint16_t)t;
+                sigma[s] = (uint16_t)min((int)pi[s], nact - 1);
+                R[s] = Rg[s];
+            }
+            __syncthreads();
+
+            double vpi[kTaEqMaxPerLane];                 // V_pi of this lane's states
+            double* V = Va;
+            int iters = -1;
+            for (int k = 0;; k++) {
+                // ---- V = evaluation of sigma
+                double* Vo = Va;
+                double* Vn = Vb;
+                uint16_t* no = na;
+                uint16_t* nn = nb;
+                for (int s = tid; s < T; s += B) {
+                    const int t = (int)base[s] + (int)sigma[s] * ts;
+                    Vo[s] = R[t];
+                    no[s] = (uint16_t)t;
+                }
+                __syncthreads();
+                double w = gam;
+                for (int d = 0; d < D; d++) {
+                    for (int s = tid; s < T; s += B) {
+                        const int m = no[s];
+                        Vn[s] = __dadd_rn(Vo[s], __dmul_rn(w, Vo[m]));
+                        nn[s] = no[m];
+                    }
+                    __syncthreads();
+                    double* tv = Vo; Vo = Vn; Vn = tv;
+                    uint16_t* tn = no; no = nn; nn = tn;
+                    w = __dmul_rn(w, w);
+                }
+                V = Vo;
+                if (k == 0) {
+#pragma unroll
+                    for (int kk = 0; kk < kTaEqMaxPerLane; kk++) {
+                        const int s = tid + kk * B;
+                        vpi[kk] = s < T ? V[s] : 0.0;
+                    }
+                }
+                if (k == THRL_EQ_MAX_ITERS) break;
+
+                // ---- improvement: keep the incumbent unless some action is strictly better
+                int changed = 0;
+                for (int s = tid; s < T; s += B) {
+                    const int b = base[s];
+                    const int tc = b + (int)sigma[s] * ts;
+                    const double qc = __dadd_rn(R[tc], __dmul_rn(gam, V[tc]));
+                    double bv = __dadd_rn(R[b], __dmul_rn(gam, V[b]));
+                    int ba = 0;
+                    for (int act = 1; act < nact; act++) {
+                        const int t = b + act * ts;
+                        const double qv = __dadd_rn(R[t], __dmul_rn(gam, V[t]));
+                        if (qv > bv) { bv = qv; ba = act; }
+                    }
+                    if (bv > qc) { sigma[s] = (uint16_t)ba; changed = 1; }
+                }
+                // the barrier also ends every read of V before the next evaluation overwrites it
+                if (!__syncthreads_or(changed)) { iters = k; break; }
+            }
+
+            // ---- losses: per state into the free V buffer; then V_pi takes V*'s place for the sums along the cycle
+            double* loss = (V == Va) ? Vb : Va;
+            int nd = 0;
+            double lmax = -__builtin_huge_val();
+#pragma unroll
+            for (int kk = 0; kk < kTaEqMaxPerLane; kk++) {
+                const int s = tid + kk * B;
+                if (s < T) {
+                    const double vs = V[s], vp = vpi[kk];
+                    const double l = (vs == vp || vs == 0.0) ? 0.0 : __ddiv_rn(__dsub_rn(vs, vp), vs);
+                    loss[s] = l;
+                    if (l > lmax) lmax = l;
+                    const int diff = (int)sigma[s] != min((int)pi[s], nact - 1) ? 1 : 0;
+                    mark[s] = (int16_t)diff;
+                    nd += diff;
+                    const int64_t os = o * T + s;
+                    if (a.br_policy) a.br_policy[os] = sigma[s];
+                    if (a.v_opt) a.v_opt[os] = vs;
+                    if (a.v_pi) a.v_pi[os] = vp;
+                }
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                const double ol = __shfl_xor(lmax, m);
+                if (ol > lmax) lmax = ol;
+                nd += __shfl_xor(nd, m);
+            }
+            if (lane == 0) { red_d[wave] = lmax; red_i[wave] = nd; }
+            __syncthreads();                             // every read of V* is done
+#pragma unroll
+            for (int kk = 0; kk < kTaEqMaxPerLane; kk++) {
+                const int s = tid + kk * B;
+                if (s < T) V[s] = vpi[kk];
+            }
+            __syncthreads();
+            if (wave == 0) {                             // all states, in state order
+                double sum_all = 0.0;
+                for (int s = 0; s < T; s++) sum_all = __dadd_rn(sum_all, loss[s]);
+                if (lane == 0) {
+                    double lm = red_d[0];
+                    int ndall = red_i[0];
+                    for (int wv = 1; wv < B / 64; wv++) {
+                        if (red_d[wv] > lm) lm = red_d[wv];
+                        ndall += red_i[wv];
+                    }
+                    a.iters[o] = iters;
+                    a.n_diff_all[o] = ndall;
+                    a.loss_all[o] = lm;
+                    a.loss_all_mean[o] = __ddiv_rn(sum_all, (double)T);
+                }
+            } else if (wave == 1) {                      // the cycle, in cycle order
+                double sum_on = 0.0, von = 0.0, lon = -__builtin_huge_val();
+                int nd_on = 0, c = c0;
+                for (int j = 0; j < lam; j++) {
+                    const double l = loss[c];
+                    sum_on = __dadd_rn(sum_on, l);
+                    von = __dadd_rn(von, V[c]);
+                    if (l > lon) lon = l;
+                    nd_on += mark[c];
+                    c = jn[c];
+                }
+                if (lane == 0) {
+                    a.n_diff_on[o] = nd_on;
+                    a.loss_on[o] = lam > 0 ? lon : nan;
+                    a.loss_on_mean[o] = lam > 0 ? __ddiv_rn(sum_on, (double)lam) : nan;
+                    a.v_on[o] = lam > 0 ? __ddiv_rn(von, (double)lam) : nan;
+                }
+            }
+            __syncthreads();                             // loss / V / mark reads before the next agent's writes
+        }
+        __syncthreads();                                 // this game's LDS reads before the next game's writes
+    }
+}
+
+}  // namespace
+
+int launch_ta_deviation(const TaDevArgs& a, hipStream_t s) {
+    if (a.in_lds) launch_dev_n<true>(a, s);
+    else launch_dev_n<false>(a, s);
+    return (int)hipGetLastError();
+}
+
+int launch_ta_equilibrium(const TaEqArgs& a, int grid, hipStream_t s) {
+    if (a.lds_bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ta_equilibrium),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(k_ta_equilibrium, dim3(grid), dim3(kTaEqBlock), (size_t)a.lds_bytes, s, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace thrl

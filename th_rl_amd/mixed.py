@@ -365,6 +365,32 @@ class MixedGameBatch:
         return tp.run(self, seats=seats, start=start, steps=steps, rows=rows, horizon=horizon,
                       tuple_policy=tuple_policy, group_stats=group_stats, budget=budget or tp.ROW_BUDGET)
 
+    def greedy_deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, start=None,
+                         rows=False, group_stats=None, tuple_policy=None, budget=None):
+        """The deviation test for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.deviation,
+        thrl_tuple_deviation): MixedGameBatch.deviation's outputs on the strategies in tuple form, from the start tuples
+        `start` int [G] (default: the tuple whose price is the game's state; -1 = none, the game is refused with
+        mu = -1).  tuple_policy: the strategies of tuple_play.extract() (default: extracted here).  The gain is
+        discounted by the per-game sweep gamma, else by the deviator's own gamma.  A batch with a CAC agent or more than
+        4096 action tuples raises ValueError.  Nothing of the batch is written."""
+        from . import tuple_analysis as ta
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return ta.deviation(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
+                            start=start, rows=rows, group_stats=group_stats, tuple_policy=tuple_policy,
+                            budget=budget or ta.dv.ROW_BUDGET)
+
+    def greedy_equilibrium(self, agents=None, start=None, policies=False, tol=0.0, tuple_policy=None):
+        """The equilibrium check for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.equilibrium,
+        thrl_tuple_equilibrium): MixedGameBatch.equilibrium's outputs with the game's T action tuples as the state set
+        (n_states = T; policies=True adds br_policy, v_opt, v_pi [N, G, T]).  start and tuple_policy as in
+        greedy_deviation; a game without a start tuple has mu = -1 and NaN on-path outputs.  A batch with a CAC agent
+        or more than 4096 action tuples raises ValueError.  Nothing of the batch is written."""
+        from . import tuple_analysis as ta
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return ta.equilibrium(self, agents=agents, start=start, policies=policies, tol=tol, tuple_policy=tuple_policy)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

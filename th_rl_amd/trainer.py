@@ -278,6 +278,13 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if training.get("greedy_cycles") is not None and training.get("greedy_cycles") is not False:
         from th_rl_amd.tuple_play import parse_options as greedy_cycle_options
         gc_opt = greedy_cycle_options(training["greedy_cycles"], config)  # refuses CAC and too many tuples before training
+    gdev_opt = geq_opt = None
+    if training.get("greedy_deviation") is not None and training.get("greedy_deviation") is not False:
+        from th_rl_amd.tuple_analysis import parse_deviation_options
+        gdev_opt = parse_deviation_options(training["greedy_deviation"], config)   # refuses CAC and too many tuples
+    if training.get("greedy_equilibrium") is not None and training.get("greedy_equilibrium") is not False:
+        from th_rl_amd.tuple_analysis import parse_equilibrium_options
+        geq_opt = parse_equilibrium_options(training["greedy_equilibrium"], config)   # ... and gamma >= 1
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -564,6 +571,11 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         write_stationary(exp_path, batch, config, st_opt, ids, n_groups, q=q_st, state0=s_st,
                          with_attractors=at_opt is not None)
 
+    tuple_policy = None
+    if gc_opt is not None or gdev_opt is not None or geq_opt is not None:
+        from th_rl_amd.tuple_play import extract as extract_tuple_policy
+        tuple_policy = extract_tuple_policy(batch)      # every agent's strategy in tuple form, once for all three
+
     if gc_opt is not None:      # the limit cycle of greedy play, neural agents included (tuple_play.py)
         from th_rl_amd.tuple_play import write_artefacts as write_greedy_cycles
         if spec is not None:
@@ -573,7 +585,27 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
                                              n_groups=training.get("n_groups", None))
         write_greedy_cycles(exp_path, batch, config, gc_opt, ids, n_groups, spec=spec,
-                            histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET)
+                            histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET,
+                            tuple_policy=tuple_policy)
+
+    if gdev_opt is not None or geq_opt is not None:     # is a deviation punished, is the strategy a best response
+        from th_rl_amd import tuple_analysis            # (tuple_analysis.py: neural agents included)
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        cycle_reward = None
+        if gdev_opt is not None:
+            r_dev = tuple_analysis.write_deviation(exp_path, batch, config, gdev_opt, ids, n_groups, spec=spec,
+                                                   histograms=bool(gs_opt and gs_opt["histograms"]),
+                                                   budget=GAME_LOG_BUDGET, tuple_policy=tuple_policy)
+            if gdev_opt["horizon"] is None:             # the full cycle: the one the equilibrium check's path ends in
+                cycle_reward = r_dev["cycle_reward"]
+        if geq_opt is not None:
+            tuple_analysis.write_equilibrium(exp_path, batch, config, geq_opt, ids, n_groups, tuple_policy=tuple_policy,
+                                             cycle_reward=cycle_reward)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

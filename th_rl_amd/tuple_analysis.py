@@ -1,0 +1,381 @@
+"""Deviation test and equilibrium check of trained games whose agents may be networks (thrl_tuple_deviation,
+thrl_tuple_equilibrium, include/thrl.h): deviation.py and equilibrium.py for any mix of QTable, Reinforce and
+ActorCritic agents, on the strategies in tuple form that tuple_play.extract() fills.
+
+A strategy of any discrete agent is a table over the game's T = prod_i A_i action tuples (tuple_play.py), so "is a
+deviation punished" and "is the strategy a best response" are questions about a map on tuple indices: the state set
+of the equilibrium check is the T tuples (n_states = T), and the paths of both analyses start at a tuple, by default
+the one whose price is the state training stopped at (tuple_play.start_tuples; a game whose state is no tuple's price
+has none: -1, refused by the deviation test, without on-path outputs in the equilibrium check, counted under no_start).
+
+deviation() and equilibrium() return the dict fields of deviation.run / equilibrium.run plus "start"; the summaries
+are deviation.summarize's and equilibrium.summarize's rows with no_start added.  The discount factor of agent i is the
+per-game sweep gamma when the batch has one, else the agent's own gamma (a network's is its class default or the
+config's, not the placeholder table slot's).  Sharded runs (th_rl_amd.launch) are refused.
+"""
+import ctypes
+import json
+import os
+
+import numpy as np
+
+from . import _lib
+from . import deviation as dv
+from . import equilibrium as eq
+from . import tuple_play as tp
+from ._lib import ThrlError
+
+DEV_DEFAULTS = dict(dv.DEFAULTS)
+EQ_DEFAULTS = dict(eq.DEFAULTS)
+
+
+def _agent_gammas(config):
+    from .mixed import NN_DEFAULTS
+    return [float(dict(_lib.QTABLE_DEFAULTS if a.get("name", "QTable") == "QTable" else NN_DEFAULTS, **a)["gamma"])
+            for a in config["agents"]]
+
+
+def _int(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError("%s must be an integer, got %r" % (name, v))
+    return int(v)
+
+
+def _agents(name, opt, n):
+    try:
+        ag = [_int(name + ".agents[]", d) for d in opt]
+    except TypeError:
+        raise ValueError("%s.agents must be a list of agent indices, got %r" % (name, opt))
+    if not ag or any(not 0 <= d < n for d in ag):
+        raise ValueError("%s.agents %r: agents must lie in [0, %d)" % (name, ag, n))
+    return ag
+
+
+def parse_deviation_options(opt, config):
+    """training.greedy_deviation (true or a dict) -> the dict with every key filled in: agents (the deviators, default
+    all), steps K, dev_len L, action ('best_response' or an index), horizon (None = deviation.default_horizon).
+    Refuses a CAC agent and more than tuple_play.MAX_TUPLES tuples."""
+    name = "training.greedy_deviation"
+    ps, _ = tp.check_config(config)
+    n = len(ps)
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict):
+        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
+    known = {"agents", "steps", "dev_len", "action", "horizon"}
+    bad = set(opt) - known
+    if bad:
+        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(known))))
+    out = dict(DEV_DEFAULTS, agents=list(range(n)))
+    out.update(opt)
+    out["agents"] = _agents(name, out["agents"], n)
+    out["steps"], out["dev_len"] = _int(name + ".steps", out["steps"]), _int(name + ".dev_len", out["dev_len"])
+    if not 1 <= out["dev_len"] <= out["steps"] <= _lib.DEV_MAX_STEPS:
+        raise ValueError("%s: needs 1 <= dev_len <= steps <= %d, got dev_len=%d steps=%d"
+                         % (name, _lib.DEV_MAX_STEPS, out["dev_len"], out["steps"]))
+    idx = dv.action_index(out["action"])
+    if idx >= 0:
+        acts = [ps[d][1] for d in out["agents"]]
+        if idx >= min(acts):
+            raise ValueError("%s.action=%d is not an action of every deviator (%s)" % (name, idx, acts))
+    if out["horizon"] is not None:
+        out["horizon"] = _int(name + ".horizon", out["horizon"])
+        if not 1 <= out["horizon"] <= _lib.DEV_MAX_HORIZON:
+            raise ValueError("%s.horizon=%d out of [1, %d]" % (name, out["horizon"], _lib.DEV_MAX_HORIZON))
+    return out
+
+
+def parse_equilibrium_options(opt, config):
+    """training.greedy_equilibrium (true or a dict) -> the dict with every key filled in: agents (those solved, default
+    all), tol, policies (store the per-state arrays).  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples and,
+    for the solved agents, a gamma outside [0, 1) in the config or in training.sweep.gamma."""
+    name = "training.greedy_equilibrium"
+    ps, _ = tp.check_config(config)
+    n = len(ps)
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict):
+        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
+    known = {"agents", "tol", "policies"}
+    bad = set(opt) - known
+    if bad:
+        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(known))))
+    out = dict(EQ_DEFAULTS, agents=list(range(n)))
+    out.update(opt)
+    out["agents"] = sorted(set(_agents(name, out["agents"], n)))
+    if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float, np.integer, np.floating)) \
+            or not float(out["tol"]) >= 0.0:
+        raise ValueError("%s.tol=%r must be a number >= 0" % (name, out["tol"]))
+    out["tol"] = float(out["tol"])
+    if not isinstance(out["policies"], (bool, np.bool_)):
+        raise ValueError("%s.policies must be true or false, got %r" % (name, out["policies"]))
+    out["policies"] = bool(out["policies"])
+    sweep = (config.get("training") or {}).get("sweep") or {}
+    gammas = _agent_gammas(config)
+    for d in out["agents"]:
+        try:
+            if "gamma" in sweep:
+                sg = np.asarray(sweep["gamma"], np.float64)
+                eq.check_gamma(sg[d] if sg.ndim == 2 else sg, "sweep.gamma")
+            else:
+                eq.check_gamma([gammas[d]], "agents[%d].gamma" % d)
+        except ValueError as e:
+            raise ValueError(str(e).replace("training.equilibrium", name))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the device calls
+def _gamma(batch):
+    """The discount factors as a device tensor [N, G], or None when cfg.gamma is every agent's own: the per-game sweep
+    when there is one, else (with a network in the game, whose table slot is a placeholder) the agents' own gammas."""
+    import torch
+    gam = batch.sweep.get("gamma") if getattr(batch, "sweep", None) else None
+    if gam is not None:
+        return gam
+    nn = getattr(batch, "nn", None)
+    if not nn:
+        return None
+    g = np.array([float(nn[i].gamma) if i in nn else float(batch.cfg.gamma[i]) for i in range(batch.N)], np.float64)
+    return torch.from_numpy(np.ascontiguousarray(np.repeat(g[:, None], batch.G, axis=1))).to(batch.device)
+
+
+def _inputs(batch, tuple_policy, start, tabs):
+    """(tabs, T, tuple_policy, start int32 [G], reward, scaled) on the batch's device."""
+    import torch
+    G, N = batch.G, batch.N
+    tabs = tp._batch_tables(batch, tabs)
+    T = int(tabs["T"])
+    dev = batch.device
+    if tuple_policy is None:
+        tuple_policy = tp.extract(batch, tabs)
+    elif tuple(tuple_policy.shape) != (G, N, T) or tuple_policy.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) \
+            or tuple_policy.device != batch.state.device or not tuple_policy.is_contiguous():
+        raise ThrlError("tuple_analysis: tuple_policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, T), dev))
+    with torch.cuda.device(dev):
+        if start is None:
+            t0 = tp.start_tuples(batch.state, tabs).contiguous()
+        elif isinstance(start, torch.Tensor):
+            t0 = start.to(device=dev, dtype=torch.int32).reshape(G).contiguous()
+        else:
+            t0 = torch.from_numpy(np.ascontiguousarray(np.asarray(start).reshape(G).astype(np.int32))).to(dev)
+        d_rew = torch.from_numpy(np.ascontiguousarray(tabs["reward"], np.float64)).to(dev)
+        d_sca = torch.from_numpy(np.ascontiguousarray(tabs["scaled"], np.float64)).to(dev)
+    return tabs, T, tuple_policy, t0, d_rew, d_sca
+
+
+def deviation(batch, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, start=None, rows=False,
+              group_stats=None, tuple_policy=None, budget=dv.ROW_BUDGET, tabs=None):
+    """thrl_tuple_deviation for every game of `batch` (a GameBatch, or a MixedGameBatch of QTable / Reinforce /
+    ActorCritic agents): deviation.run's dict fields, from the strategies tuple_policy (a device int16 tensor [G, N, T] of
+    tuple_play.extract(), default: extracted here) and the start tuples `start` int [G] (default: the tuple whose
+    price is the game's state, -1 when there is none: that game is refused).  "start" [G] is returned too.  The rows
+    are produced in tau-chunks of at most `budget` bytes per device buffer."""
+    import torch
+    G, N = batch.G, batch.N
+    K, L = int(steps), int(dev_len)
+    if not 0 <= int(deviator) < N:
+        raise ThrlError("deviator %d out of [0, %d)" % (int(deviator), N))
+    if group_stats is not None and group_stats.G != G:
+        raise ThrlError("group_stats spec is for %d games, this batch has %d" % (group_stats.G, G))
+    tabs, T, tuple_policy, t0, d_rew, d_sca = _inputs(batch, tuple_policy, start, tabs)
+    H = dv.default_horizon([int(x) for x in tabs["n_actions"]]) if horizon is None else int(horizon)
+    dev = batch.device
+    a = _lib.TupleDeviationArgs()
+    a.n_games, a.n_tuples, a.deviator, a.dev_len, a.n_steps, a.horizon = G, T, int(deviator), L, K, H
+    a.dev_action = dv.action_index(action)
+    with torch.cuda.device(dev):
+        out = {f: torch.zeros((G,), dtype=torch.int32, device=dev) for f in dv.INT_FIELDS}
+        out.update(cycle_reward=torch.zeros((N, G), dtype=torch.float64, device=dev),
+                   cycle_action=torch.zeros((N, G), dtype=torch.float64, device=dev),
+                   gain=torch.zeros((G,), dtype=torch.float64, device=dev))
+        a.start, a.tuple_policy, a.reward, a.scaled = t0.data_ptr(), tuple_policy.data_ptr(), d_rew.data_ptr(), d_sca.data_ptr()
+        gam = _gamma(batch)
+        a.sweep_gamma = gam.data_ptr() if gam is not None else None
+        for f, t in out.items():
+            setattr(a, f, t.data_ptr())
+        want = bool(rows) or group_stats is not None
+        chunk = max(1, min(K, int(budget) // (8 * N * G))) if want else K
+        st = group_stats.zeros(K, dev) if group_stats is not None else None
+        host_r, host_a = [], []
+        b0 = 0
+        while True:
+            k = min(chunk, K - b0) if want else 0
+            rr = ra = None
+            if k:
+                rr = torch.empty((k, N, G), dtype=torch.float64, device=dev)
+                ra = torch.empty((k, N, G), dtype=torch.float64, device=dev)
+            a.row_begin, a.row_count = (b0, k) if k else (0, 0)
+            a.reward_rows = rr.data_ptr() if rr is not None else None
+            a.action_rows = ra.data_ptr() if ra is not None else None
+            _lib.check(batch.L.thrl_tuple_deviation(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                       "thrl_tuple_deviation")
+            if st is not None and k:
+                group_stats.reduce(batch.L, rr, ra, k, st, batch._stream(), at=b0)
+            if rows and k:
+                host_r.append(rr.cpu().numpy())
+                host_a.append(ra.cpu().numpy())
+            b0 += k
+            if b0 >= K or not want:
+                break
+        torch.cuda.synchronize(dev)
+        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res["start"] = t0.cpu().numpy()
+        res["horizon"] = H
+        if rows:
+            res["reward_rows"] = np.concatenate(host_r, axis=0) if host_r else np.zeros((0, N, G))
+            res["action_rows"] = np.concatenate(host_a, axis=0) if host_a else np.zeros((0, N, G))
+        if st is not None:
+            from .group_stats import to_numpy
+            res["group_stats"] = to_numpy(st)
+    return res
+
+
+def equilibrium(batch, agents=None, start=None, policies=False, tol=0.0, tuple_policy=None, tabs=None):
+    """thrl_tuple_equilibrium for every game of `batch`: equilibrium.run's dict fields with n_states = T, plus "start"
+    [G].  tuple_policy and start as in deviation(); a game without a start tuple gets mu = -1, lam = 0 and NaN in its
+    on-path outputs (its flags br_on and nash are False).  policies=True adds br_policy (uint16), v_opt, v_pi [N, G, T]."""
+    import torch
+    G, N = batch.G, batch.N
+    ag, mask = eq.agents_mask(agents, N)
+    tabs, T, tuple_policy, t0, d_rew, _ = _inputs(batch, tuple_policy, start, tabs)
+    dev = batch.device
+    a = _lib.TupleEquilibriumArgs()
+    a.n_games, a.n_tuples, a.agents = G, T, mask
+    with torch.cuda.device(dev):
+        gam = _gamma(batch)
+        if gam is not None:
+            sel = gam[ag]
+            if not bool(((sel >= 0.0) & (sel < 1.0)).all()):
+                raise ThrlError("equilibrium: every solved agent's gamma must lie in [0, 1)")
+        out = {"mu": torch.zeros((G,), dtype=torch.int32, device=dev),
+               "lam": torch.zeros((G,), dtype=torch.int32, device=dev)}
+        out.update({f: torch.zeros((N, G), dtype=torch.int32, device=dev) for f in eq.INT_FIELDS})
+        out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in eq.FLOAT_FIELDS})
+        if policies:
+            out["br_policy"] = torch.zeros((N, G, T), dtype=torch.int16, device=dev)
+            out["v_opt"] = torch.zeros((N, G, T), dtype=torch.float64, device=dev)
+            out["v_pi"] = torch.zeros((N, G, T), dtype=torch.float64, device=dev)
+        a.start, a.tuple_policy, a.reward = t0.data_ptr(), tuple_policy.data_ptr(), d_rew.data_ptr()
+        a.sweep_gamma = gam.data_ptr() if gam is not None else None
+        for f, t in out.items():
+            setattr(a, f, t.data_ptr())
+        _lib.check(batch.L.thrl_tuple_equilibrium(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                   "thrl_tuple_equilibrium")
+        torch.cuda.synchronize(dev)
+        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res["start"] = t0.cpu().numpy()
+    if policies:
+        res["br_policy"] = res["br_policy"].view(np.uint16)
+    res["agents"] = ag
+    res["n_states"] = T
+    res["tol"] = float(tol)
+    res.update(eq.flags(res, ag, tol))
+    return res
+
+
+# ---------------------------------------------------------------------------------------------- host side
+def _no_start(rows, start, ids):
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    start = np.asarray(start).reshape(-1)
+    for r in rows:
+        r["no_start"] = int(np.sum((ids == r["group"]) & (start < 0)))
+    return rows
+
+
+def summarize_deviation(games, ids, n_groups, nash, cartel, deviator):
+    """deviation.summarize's rows for one deviator with no_start (the group's refused games; they count under games
+    with lam = 0 and gain = 0) added.  games also holds start [G]."""
+    return _no_start(dv.summarize(games, ids, n_groups, nash, cartel, deviator), games["start"], ids)
+
+
+def summarize_equilibrium(games, ids, n_groups, agents, tol=0.0, delta=None):
+    """equilibrium.summarize's rows with no_start added (those games have NaN on-path losses: not a best response on a
+    path they do not have).  games also holds start [G]."""
+    return _no_start(eq.summarize(games, ids, n_groups, agents, tol, delta), games["start"], ids)
+
+
+def load_deviation_games(d, deviator):
+    """The per-game arrays a run directory holds for `deviator` (training.greedy_deviation)."""
+    cyc = np.load(os.path.join(d, "gdev_cycle.npy"))
+    post = np.load(os.path.join(d, "gdev%d_post.npy" % deviator))
+    return {"mu": cyc[0], "lam": cyc[1], "start": cyc[2], "mu_post": post[0], "lam_post": post[1], "ret_step": post[2],
+            "act_dev": post[3], "gain": np.load(os.path.join(d, "gdev%d_gain.npy" % deviator)),
+            "cycle_reward": np.load(os.path.join(d, "gdev_cycle_reward.npy")),
+            "cycle_action": np.load(os.path.join(d, "gdev_cycle_action.npy"))}
+
+
+def load_equilibrium_games(d):
+    """The per-game arrays a run directory holds (training.greedy_equilibrium)."""
+    cyc, diff, loss = (np.load(os.path.join(d, "geq_%s.npy" % f)) for f in ("cycle", "diff", "loss"))
+    g = {"mu": cyc[0], "lam": cyc[1], "start": cyc[2], "iters": np.load(os.path.join(d, "geq_iters.npy")),
+         "n_diff_all": diff[0], "n_diff_on": diff[1], "loss_all": loss[0], "loss_on": loss[1], "loss_all_mean": loss[2],
+         "loss_on_mean": loss[3], "v_on": np.load(os.path.join(d, "geq_value.npy"))}
+    if os.path.isfile(os.path.join(d, "geq_policy.npy")):
+        g.update(br_policy=np.load(os.path.join(d, "geq_policy.npy")), v_opt=np.load(os.path.join(d, "geq_v_opt.npy")),
+                 v_pi=np.load(os.path.join(d, "geq_v_pi.npy")))
+    return g
+
+
+def write_deviation(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=dv.ROW_BUDGET,
+                    tuple_policy=None):
+    """train_one's training.greedy_deviation outputs, with the shapes of deviation.write_artefacts': gdev_cycle.npy int32
+    [3, G] (mu, lam, start), gdev_cycle_reward / gdev_cycle_action [N, G], per deviator gdev<d>_post.npy int32 [4, G]
+    (mu_post, lam_post, ret_step, act_dev) and gdev<d>_gain.npy [G], gdev<d>_*.npy group statistics with a spec, and
+    greedy_deviation.json.  Returns the last deviator's per-game arrays."""
+    from . import trainer
+    nash, cartel = dv.optimal(config)
+    tabs = tp.tables(config)
+    if tuple_policy is None:
+        tuple_policy = tp.extract(batch, tabs)
+    summary = []
+    for d in opt["agents"]:
+        r = deviation(batch, deviator=d, steps=opt["steps"], dev_len=opt["dev_len"], action=opt["action"],
+                      horizon=opt["horizon"], group_stats=spec, budget=budget, tuple_policy=tuple_policy, tabs=tabs)
+        if d == opt["agents"][0]:
+            np.save(os.path.join(exp_path, "gdev_cycle.npy"), np.stack([r["mu"], r["lam"], r["start"]]).astype(np.int32))
+            np.save(os.path.join(exp_path, "gdev_cycle_reward.npy"), r["cycle_reward"])
+            np.save(os.path.join(exp_path, "gdev_cycle_action.npy"), r["cycle_action"])
+        np.save(os.path.join(exp_path, "gdev%d_post.npy" % d),
+                np.stack([r["mu_post"], r["lam_post"], r["ret_step"], r["act_dev"]]).astype(np.int32))
+        np.save(os.path.join(exp_path, "gdev%d_gain.npy" % d), r["gain"])
+        if spec is not None:
+            files = trainer.group_stats_files(exp_path, "gdev%d" % d, opt["steps"], spec, histograms)
+            trainer.write_group_stats(files, 0, r["group_stats"], spec.describe())
+            for arr in files.values():
+                if hasattr(arr, "flush"):
+                    arr.flush()
+        summary += summarize_deviation(r, ids, n_groups, nash, cartel, d)
+    opt = dict(opt, horizon_used=int(r["horizon"]))
+    with open(os.path.join(exp_path, "greedy_deviation.json"), "w") as f:
+        json.dump(dict(dv.describe(opt, nash, cartel, summary), T=int(tabs["T"])), f, indent=2)
+    return r
+
+
+def write_equilibrium(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None, cycle_reward=None):
+    """train_one's training.greedy_equilibrium outputs, with the shapes of equilibrium.save_games': geq_cycle.npy int32
+    [3, G] (mu, lam, start), geq_iters [N, G], geq_diff [2, N, G], geq_loss [4, N, G], geq_value [N, G], with
+    policies geq_policy, geq_v_opt, geq_v_pi [N, G, T], and greedy_equilibrium.json.  cycle_reward [N, G]: the cycle
+    rewards of the same strategies and starts for the collusive fractions (default: one thrl_tuple_walk)."""
+    tabs = tp.tables(config)
+    if tuple_policy is None:
+        tuple_policy = tp.extract(batch, tabs)
+    r = equilibrium(batch, agents=opt["agents"], policies=opt["policies"], tol=opt["tol"], tuple_policy=tuple_policy,
+                    tabs=tabs)
+    np.save(os.path.join(exp_path, "geq_cycle.npy"), np.stack([r["mu"], r["lam"], r["start"]]).astype(np.int32))
+    np.save(os.path.join(exp_path, "geq_iters.npy"), np.asarray(r["iters"], np.int32))
+    np.save(os.path.join(exp_path, "geq_diff.npy"), np.stack([r["n_diff_all"], r["n_diff_on"]]).astype(np.int32))
+    np.save(os.path.join(exp_path, "geq_loss.npy"),
+            np.stack([r["loss_all"], r["loss_on"], r["loss_all_mean"], r["loss_on_mean"]]).astype(np.float64))
+    np.save(os.path.join(exp_path, "geq_value.npy"), np.asarray(r["v_on"], np.float64))
+    if "br_policy" in r:
+        np.save(os.path.join(exp_path, "geq_policy.npy"), np.asarray(r["br_policy"], np.uint16))
+        np.save(os.path.join(exp_path, "geq_v_opt.npy"), np.asarray(r["v_opt"], np.float64))
+        np.save(os.path.join(exp_path, "geq_v_pi.npy"), np.asarray(r["v_pi"], np.float64))
+    if cycle_reward is None:
+        cycle_reward = tp.run(batch, start=r["start"], tuple_policy=tuple_policy, tabs=tabs)["cycle_reward"]
+    nash, cartel = dv.optimal(config)
+    delta = np.where(r["lam"] > 0, dv.profit_gain(cycle_reward, nash, cartel), -np.inf)      # no path: not collusive
+    summary = summarize_equilibrium(r, ids, n_groups, opt["agents"], opt["tol"], delta)
+    with open(os.path.join(exp_path, "greedy_equilibrium.json"), "w") as f:
+        json.dump(eq.describe(opt, r["n_states"], summary), f, indent=2)
+    return r

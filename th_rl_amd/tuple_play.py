@@ -390,24 +390,27 @@ def load_games(d):
             "cycle_action": np.load(os.path.join(d, "gcyc_cycle_action.npy"))}
 
 
-def analyse(batch, ids, n_groups, opt, group_stats=None, budget=ROW_BUDGET):
+def analyse(batch, ids, n_groups, opt, group_stats=None, budget=ROW_BUDGET, tuple_policy=None):
     """The self-play round and the rounds of crossplay.pairings(ids, ...) for the options `opt` played on `batch` from
-    the states it holds: the result of run() for the list [identity, round 1, ...], seats local."""
+    the states it holds: the result of run() for the list [identity, round 1, ...], seats local.  tuple_policy: the
+    strategies of extract() when the caller already has them."""
     from .crossplay import pairings
     seats = [identity(batch.N, batch.G)]
     if opt["rounds"] > 0:
         seats += pairings(ids, n_groups, opt["scheme"], opt["rounds"], opt["against"], opt["seed"], batch.N)
-    return run(batch, seats, steps=opt["steps"], horizon=opt["horizon"], group_stats=group_stats, budget=budget)
+    return run(batch, seats, steps=opt["steps"], horizon=opt["horizon"], group_stats=group_stats, budget=budget,
+               tuple_policy=tuple_policy)
 
 
-def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=ROW_BUDGET):
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=ROW_BUDGET,
+                    tuple_policy=None):
     """train_one's training.greedy_cycles outputs: the gcyc_*.npy files, with a spec and steps > 0 the rows' group
     statistics pooled over the rounds under prefix "gcyc" (group = seat 0's group), and greedy_cycles.json."""
     from . import trainer
     nash, cartel = optimal(config)
     tabs = tables(config)
     pooled = spec if opt["steps"] > 0 else None
-    games = analyse(batch, ids, n_groups, opt, group_stats=pooled, budget=budget)
+    games = analyse(batch, ids, n_groups, opt, group_stats=pooled, budget=budget, tuple_policy=tuple_policy)
     off = int(batch.game_offset)
     save_games(exp_path, dict(games, seats=games["seats"].astype(np.int64) + off))
     if pooled is not None:

@@ -489,3 +489,85 @@ def convergence_games(exp_path):
         n = g["converged_at"].shape[0]
         frames.append(pandas.DataFrame({f: g[f] for f in cv.FILES}, index=pandas.RangeIndex(off, off + n, name="game")))
     return pandas.concat(frames)
+
+
+def greedy_deviation_summary(exp_path):
+    """A run's deviation test in tuple form (training.greedy_deviation, any mix of QTable / Reinforce / ActorCritic
+    agents): greedy_deviation.json's summary as a DataFrame with deviation_summary's columns, one row per (group,
+    deviator), plus no_start (the group's games whose state is no tuple's price: refused, lam = 0) and T."""
+    import json
+    with open(os.path.join(exp_path, "greedy_deviation.json")) as f:
+        desc = json.load(f)
+    rows = []
+    for r in desc["summary"]:
+        r = dict(r)
+        for name, n in zip(desc["lam_bins"], r.pop("lam_hist")):
+            r["lam_" + name] = n
+        rows.append(r)
+    df = pandas.DataFrame(rows)
+    df["Nash"], df["Cartel"], df["T"] = float(desc["nash"]), float(desc["cartel"]), int(desc["T"])
+    return df
+
+
+def greedy_deviation_games(exp_path, deviator=0):
+    """Per-game results of training.greedy_deviation for `deviator`, one row per game indexed by its GLOBAL id: start
+    (the start tuple, -1 = none), mu, lam, mu_post, lam_post, ret_step, act_dev, gain, cycle_reward_<i> /
+    cycle_action_<i> and the profit gain delta."""
+    import json
+    from th_rl_amd import deviation as dv, tuple_analysis as ta
+    if not os.path.isfile(os.path.join(exp_path, "gdev_cycle.npy")):
+        raise KeyError("no deviation test in tuple form (gdev_cycle.npy) under %s (training.greedy_deviation)" % exp_path)
+    with open(os.path.join(exp_path, "greedy_deviation.json")) as f:
+        desc = json.load(f)
+    if int(deviator) not in desc["options"]["agents"]:
+        raise KeyError("deviator %d was not analysed (agents %s)" % (int(deviator), desc["options"]["agents"]))
+    off = 0
+    if os.path.isfile(os.path.join(exp_path, "config.json")):
+        with open(os.path.join(exp_path, "config.json")) as f:
+            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    g = ta.load_deviation_games(exp_path, int(deviator))
+    cols = {"start": g["start"]}
+    cols.update({f: g[f] for f in dv.INT_FIELDS})
+    cols["gain"] = g["gain"]
+    for i in range(g["cycle_reward"].shape[0]):
+        cols["cycle_reward_%d" % i] = g["cycle_reward"][i]
+        cols["cycle_action_%d" % i] = g["cycle_action"][i]
+    cols["delta"] = dv.profit_gain(g["cycle_reward"], desc["nash"], desc["cartel"])
+    n = g["gain"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
+def greedy_equilibrium_summary(exp_path):
+    """A run's equilibrium check in tuple form (training.greedy_equilibrium): greedy_equilibrium.json's summary as a
+    DataFrame with equilibrium_summary's columns (n_states = T, the game's action tuples) plus no_start."""
+    import json
+    with open(os.path.join(exp_path, "greedy_equilibrium.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["n_states"] = int(desc["n_states"])
+    df["tol"] = float(desc["options"]["tol"])
+    return df
+
+
+def greedy_equilibrium_games(exp_path, agent=0):
+    """Per-game results of training.greedy_equilibrium for `agent`, one row per game indexed by its GLOBAL id: start,
+    mu, lam, equilibrium_games' columns for this agent and the flags br_on, br_all (this agent) and nash, perfect (all
+    solved agents) at the run's tol."""
+    import json
+    from th_rl_amd import equilibrium as eq, tuple_analysis as ta
+    if not os.path.isfile(os.path.join(exp_path, "geq_cycle.npy")):
+        raise KeyError("no equilibrium check in tuple form (geq_cycle.npy) under %s (training.greedy_equilibrium)" % exp_path)
+    with open(os.path.join(exp_path, "greedy_equilibrium.json")) as f:
+        opt = json.load(f)["options"]
+    off = 0
+    if os.path.isfile(os.path.join(exp_path, "config.json")):
+        with open(os.path.join(exp_path, "config.json")) as f:
+            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    g = ta.load_equilibrium_games(exp_path)
+    fl = eq.flags(g, opt["agents"], opt["tol"])
+    cols = {"start": g["start"], "mu": g["mu"], "lam": g["lam"]}
+    for f in eq.INT_FIELDS + eq.FLOAT_FIELDS:
+        cols[f] = g[f][int(agent)]
+    cols.update(br_on=fl["br_on"][int(agent)], br_all=fl["br_all"][int(agent)], nash=fl["nash"], perfect=fl["perfect"])
+    n = g["mu"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
