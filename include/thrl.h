@@ -1124,6 +1124,78 @@ typedef struct {
 } thrl_tuple_equilibrium_args;
 int thrl_tuple_equilibrium(const thrl_cfg* cfg, const thrl_tuple_equilibrium_args* args, void* stream);
 
+/*
+ * thrl_tuple_attractors: thrl_attractors with the state set replaced by the T tuples, so S = T and state(t) = t: ALL
+ * limit cycles of a game's greedy map F on tuple indices and their basins, for ANY mix of QTable, Reinforce and
+ * ActorCritic agents.  No reference counterpart.  It follows thrl_tuple_deviation / thrl_tuple_equilibrium: of a valid
+ * cfg only n_agents and n_actions are used, there is no seat array, nothing of a batch is read or written, pi_i(t) =
+ * tuple_policy[g][i][t] with entries at or above n_actions_i clamped to n_actions_i - 1, F(t) = the index of the tuple
+ * (pi_i(t))_i, and the transition taken at t earns reward[i][F(t)] and scaled[i][F(t)] (device float64 [N][T] each).
+ * G = args.n_games >= 1, T = args.n_tuples = prod_i n_actions_i, 1 <= T <= THRL_TP_MAX_TUPLES.  All arithmetic is
+ * float64, every operation rounded once, in the order written here.
+ *
+ * For every tuple t: mu(t) = the smallest k >= 0 for which F^k(t) lies on a cycle of F, rep(t) = the smallest tuple
+ * index on that cycle, lam = its length.
+ *
+ * Attractors of a game = the distinct values of rep, n_attr of them.  basin(r) = the number of tuples t with
+ * rep(t) = r, the cycle's own tuples included.  Order: basin descending, ties by rep ascending.  The first
+ * THRL_ATTR_KEEP are reported, slot k of game g at [k][G] / [k][N][G]:
+ *   rep, lam, basin
+ *   cycle_reward[k][i][g] = (sum_{j<lam} reward[i][F^{j+1}(rep)], added in that order from 0.0) / lam
+ *   cycle_action[k][i][g] = the same with scaled
+ * -- the numbers thrl_tuple_walk reports for a walk started at rep.  Slots k >= n_attr get rep = -1, lam = 0,
+ * basin = 0 and zeros.  Per game: n_attr, mu_max = max_t mu(t), n_cycle_states = the sum of lam over all attractors,
+ * kept or not.
+ *
+ * Training tuple.  start (device int32 [G]): rep_x0 = rep(start[g]), mu_x0 = mu(start[g]) -- thrl_tuple_walk's mu for
+ * a horizon of at least T + 1, and lam of rep_x0's attractor is its lam -- and slot_x0 = that attractor's slot, or -1
+ * if it is not among the kept.  A game with start[g] < 0 or start[g] >= T has no training tuple: all three are -1; its
+ * other outputs are computed as for any game.
+ *
+ * Start weights (optional: start_w = NULL skips them, their outputs may then be NULL).  start_w (device float64 [T])
+ * holds a weight w_t of every tuple as a starting point; it takes the place of thrl_attractors' reset distribution,
+ * which a network would have to be evaluated on a continuum of prices for.  Tuple t reaches the attractor A(t) = the
+ * one with rep(t).
+ *   start_mass[k][g]    = sum of w_t over the t with A(t) in slot k, start_mass_other[g] over the t whose attractor
+ *                         is not kept; both added in ascending t from 0.0
+ *   start_reward[i][g]  = sum_t w_t * cycle_reward_i(A(t)) over ALL t, kept or not, in ascending t from 0.0, each
+ *                         multiply and each add rounded once
+ *
+ * tuple_rep, tuple_mu (optional, uint16 [G][T]): rep(t) and mu(t) of every tuple.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games < 1, reserved != 0, n_tuples < 1 or n_tuples != prod_i n_actions_i;
+ * THRL_ERR_UNSUPPORTED for n_tuples > THRL_TP_MAX_TUPLES; THRL_ERR_NULL for a missing cfg, args, tuple_policy, reward,
+ * scaled, start or per-game / per-slot output, or with start_w a missing start_mass, start_mass_other or start_reward.
+ */
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of tuple_policy                    */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t reserved;                /* 0                                                */
+    int32_t reserved2;               /* 0                                                */
+    const int32_t* start;            /* device [G]: training tuple, outside [0, T) = none */
+    const uint16_t* tuple_policy;    /* device [G][N][T]                                 */
+    const double* reward;            /* device [N][T]                                    */
+    const double* scaled;            /* device [N][T]                                    */
+    const double* start_w;           /* device [T], or NULL: no start weights            */
+    int32_t* n_attr;                 /* device [G]                                       */
+    int32_t* mu_max;                 /* device [G]                                       */
+    int32_t* n_cycle_states;         /* device [G]                                       */
+    int32_t* rep;                    /* device [KEEP][G]                                 */
+    int32_t* lam;                    /* device [KEEP][G]                                 */
+    int32_t* basin;                  /* device [KEEP][G]                                 */
+    double*  cycle_reward;           /* device [KEEP][N][G]                              */
+    double*  cycle_action;           /* device [KEEP][N][G]                              */
+    int32_t* rep_x0;                 /* device [G]                                       */
+    int32_t* mu_x0;                  /* device [G]                                       */
+    int32_t* slot_x0;                /* device [G]                                       */
+    double*  start_mass;             /* device [KEEP][G], or NULL without start_w        */
+    double*  start_mass_other;       /* device [G], or NULL without start_w              */
+    double*  start_reward;           /* device [N][G], or NULL without start_w           */
+    uint16_t* tuple_rep;             /* device [G][T] or NULL                            */
+    uint16_t* tuple_mu;              /* device [G][T] or NULL                            */
+} thrl_tuple_attractors_args;
+int thrl_tuple_attractors(const thrl_cfg* cfg, const thrl_tuple_attractors_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

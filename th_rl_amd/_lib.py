@@ -261,6 +261,22 @@ class TupleEquilibriumArgs(ctypes.Structure):
     ]
 
 
+class TupleAttractorsArgs(ctypes.Structure):
+    """thrl_tuple_attractors_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("reserved2", ctypes.c_int32),
+        ("start", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+        ("scaled", ctypes.c_void_p), ("start_w", ctypes.c_void_p),
+        ("n_attr", ctypes.c_void_p), ("mu_max", ctypes.c_void_p), ("n_cycle_states", ctypes.c_void_p),
+        ("rep", ctypes.c_void_p), ("lam", ctypes.c_void_p), ("basin", ctypes.c_void_p),
+        ("cycle_reward", ctypes.c_void_p), ("cycle_action", ctypes.c_void_p),
+        ("rep_x0", ctypes.c_void_p), ("mu_x0", ctypes.c_void_p), ("slot_x0", ctypes.c_void_p),
+        ("start_mass", ctypes.c_void_p), ("start_mass_other", ctypes.c_void_p), ("start_reward", ctypes.c_void_p),
+        ("tuple_rep", ctypes.c_void_p), ("tuple_mu", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -272,6 +288,7 @@ SYMBOLS = [
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
+    "thrl_tuple_attractors",
 ]
 CAC_PARAMS = 1283
 
@@ -390,6 +407,8 @@ def load():
     L.thrl_tuple_deviation.argtypes = [cfgp, ctypes.POINTER(TupleDeviationArgs), vp]
     L.thrl_tuple_equilibrium.restype = ctypes.c_int
     L.thrl_tuple_equilibrium.argtypes = [cfgp, ctypes.POINTER(TupleEquilibriumArgs), vp]
+    L.thrl_tuple_attractors.restype = ctypes.c_int
+    L.thrl_tuple_attractors.argtypes = [cfgp, ctypes.POINTER(TupleAttractorsArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -18,6 +18,7 @@
 #include "thrl_equilibrium.h"
 #include "thrl_kernels.h"
 #include "thrl_tuple_analysis.h"
+#include "thrl_tuple_attractors.h"
 #include "thrl_tuple_play.h"
 #include "thrl_wave_lut.h"
 
@@ -1776,6 +1777,76 @@ int thrl_tuple_equilibrium(const thrl_cfg* c, const thrl_tuple_equilibrium_args*
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_ta_equilibrium(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_ta_equilibrium launch") : THRL_OK;
+}
+
+int thrl_tuple_attractors(const thrl_cfg* c, const thrl_tuple_attractors_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    if (x->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", x->n_games);
+    if (x->reserved != 0 || x->reserved2 != 0)
+        return fail(THRL_ERR_BAD_CONFIG, "reserved=%d, %d must be 0", x->reserved, x->reserved2);
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (!x->start || !x->tuple_policy || !x->reward || !x->scaled || !x->n_attr || !x->mu_max || !x->n_cycle_states
+        || !x->rep || !x->lam || !x->basin || !x->cycle_reward || !x->cycle_action || !x->rep_x0 || !x->mu_x0 || !x->slot_x0)
+        return fail(THRL_ERR_NULL, "start / tuple_policy / reward / scaled / n_attr / mu_max / n_cycle_states / rep / lam / "
+                                   "basin / cycle_reward / cycle_action / rep_x0 / mu_x0 / slot_x0 is NULL");
+    if (x->start_w && (!x->start_mass || !x->start_mass_other || !x->start_reward))
+        return fail(THRL_ERR_NULL, "start_mass / start_mass_other / start_reward is NULL with start_w given");
+    TatArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples;
+    while ((1 << a.L) < a.T) a.L++;
+    int ts = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        a.n_actions[i] = c->n_actions[i];
+        a.tstride[i] = ts;
+        ts *= c->n_actions[i];
+    }
+    // LDS of a block: 8-byte arrays first, then 4-byte, then 2-byte (each padded to 16 bytes): kTatLdsPerTuple * T plus
+    // the staging of a chunk of start weights, (8 * (1 + N) + 2) * kTatBlock bytes, and under 1 KB of fixed words:
+    // 102.7 KB at T = 4096 with two agents, 115.1 KB with eight
+    const int T = a.T;
+    const int b4 = (4 * T + 15) & ~15, b2 = (2 * T + 15) & ~15;
+    int off = 0;
+    a.o_cw = off; off += 8 * kTatBlock;
+    a.o_cprod = off; off += 8 * kTatBlock * N;
+    a.o_cmean = off; off += 8 * THRL_ATTR_KEEP * N;
+    a.o_basin = off; off += b4;
+    a.o_lamc = off; off += b4;
+    a.o_sel = off; off += 4 * THRL_ATTR_KEEP;
+    a.o_red = off; off += 4 * 20;
+    off = (off + 15) & ~15;
+    a.o_f = off; off += b2;
+    a.o_pa = off; off += b2;
+    a.o_pb = off; off += b2;
+    a.o_ma = off; off += b2;
+    a.o_mb = off; off += b2;
+    a.o_rep = off; off += b2;
+    a.o_on = off; off += b2;
+    a.o_slot = off; off += b2;
+    a.o_cslot = off; off += 2 * kTatBlock;
+    a.lds_bytes = off;
+    a.start = x->start; a.policy = x->tuple_policy; a.reward = x->reward; a.scaled = x->scaled; a.start_w = x->start_w;
+    a.n_attr = x->n_attr; a.mu_max = x->mu_max; a.n_cycle_states = x->n_cycle_states;
+    a.rep = x->rep; a.lam = x->lam; a.basin = x->basin; a.cycle_reward = x->cycle_reward; a.cycle_action = x->cycle_action;
+    a.rep_x0 = x->rep_x0; a.mu_x0 = x->mu_x0; a.slot_x0 = x->slot_x0;
+    a.start_mass = x->start_mass; a.start_mass_other = x->start_mass_other; a.start_reward = x->start_reward;
+    a.tuple_rep = x->tuple_rep; a.tuple_mu = x->tuple_mu;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    if (lds_cu > 0 && a.lds_bytes > lds_cu)          // cannot happen on a 160 KB CU within THRL_TP_MAX_TUPLES
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_tuple_attractors: %d bytes of LDS per game, the device has %d", a.lds_bytes, lds_cu);
+    int per_cu = kTatMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_tuple_attractors(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_ta_attractors launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -391,6 +391,19 @@ class MixedGameBatch:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
         return ta.equilibrium(self, agents=agents, start=start, policies=policies, tol=tol, tuple_policy=tuple_policy)
 
+    def greedy_attractors(self, start=None, weights="uniform", policies=False, tuple_policy=None):
+        """The attractor analysis for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.attractors,
+        thrl_tuple_attractors): MixedGameBatch.attractors' outputs with the game's T action tuples as the state set
+        (n_states = T; policies=True adds tuple_rep, tuple_mu [G, T]) and start_mass, start_mass_other, start_reward in
+        place of the reset_* fields: weights is a weight per start tuple, "uniform" = 1 / T (a start drawn uniformly over
+        action profiles, not the environment's reset distribution), None = none, or T numbers.  start and tuple_policy
+        as in greedy_deviation; a game without a start tuple has rep_x0 = mu_x0 = slot_x0 = -1.  A batch with a CAC
+        agent or more than 4096 action tuples raises ValueError.  Nothing of the batch is written."""
+        from . import tuple_analysis as ta
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return ta.attractors(self, start=start, weights=weights, policies=policies, tuple_policy=tuple_policy)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

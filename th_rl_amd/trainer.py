@@ -285,6 +285,10 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if training.get("greedy_equilibrium") is not None and training.get("greedy_equilibrium") is not False:
         from th_rl_amd.tuple_analysis import parse_equilibrium_options
         geq_opt = parse_equilibrium_options(training["greedy_equilibrium"], config)   # ... and gamma >= 1
+    gat_opt = None
+    if training.get("greedy_attractors") is not None and training.get("greedy_attractors") is not False:
+        from th_rl_amd.tuple_analysis import parse_attractor_options
+        gat_opt = parse_attractor_options(training["greedy_attractors"], config)      # refuses CAC and too many tuples
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -572,9 +576,9 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
                          with_attractors=at_opt is not None)
 
     tuple_policy = None
-    if gc_opt is not None or gdev_opt is not None or geq_opt is not None:
+    if gc_opt is not None or gdev_opt is not None or geq_opt is not None or gat_opt is not None:
         from th_rl_amd.tuple_play import extract as extract_tuple_policy
-        tuple_policy = extract_tuple_policy(batch)      # every agent's strategy in tuple form, once for all three
+        tuple_policy = extract_tuple_policy(batch)      # every agent's strategy in tuple form, once for all greedy_* keys
 
     if gc_opt is not None:      # the limit cycle of greedy play, neural agents included (tuple_play.py)
         from th_rl_amd.tuple_play import write_artefacts as write_greedy_cycles
@@ -606,6 +610,16 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         if geq_opt is not None:
             tuple_analysis.write_equilibrium(exp_path, batch, config, geq_opt, ids, n_groups, tuple_policy=tuple_policy,
                                              cycle_reward=cycle_reward)
+
+    if gat_opt is not None:     # all limit cycles of the greedy map on tuples and their basins
+        from th_rl_amd import tuple_analysis
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        tuple_analysis.write_attractors(exp_path, batch, config, gat_opt, ids, n_groups, tuple_policy=tuple_policy)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

@@ -1,6 +1,7 @@
-"""Deviation test and equilibrium check of trained games whose agents may be networks (thrl_tuple_deviation,
-thrl_tuple_equilibrium, include/thrl.h): deviation.py and equilibrium.py for any mix of QTable, Reinforce and
-ActorCritic agents, on the strategies in tuple form that tuple_play.extract() fills.
+"""Deviation test, equilibrium check and attractor analysis of trained games whose agents may be networks
+(thrl_tuple_deviation, thrl_tuple_equilibrium, thrl_tuple_attractors, include/thrl.h): deviation.py, equilibrium.py and
+attractors.py for any mix of QTable, Reinforce and ActorCritic agents, on the strategies in tuple form that
+tuple_play.extract() fills.
 
 A strategy of any discrete agent is a table over the game's T = prod_i A_i action tuples (tuple_play.py), so "is a
 deviation punished" and "is the strategy a best response" are questions about a map on tuple indices: the state set
@@ -12,6 +13,12 @@ deviation() and equilibrium() return the dict fields of deviation.run / equilibr
 are deviation.summarize's and equilibrium.summarize's rows with no_start added.  The discount factor of agent i is the
 per-game sweep gamma when the batch has one, else the agent's own gamma (a network's is its class default or the
 config's, not the placeholder table slot's).  Sharded runs (th_rl_amd.launch) are refused.
+
+attractors() returns attractors.run's dict fields with the T tuples as the state set (n_states = T) and start_mass,
+start_mass_other, start_reward in place of the reset_* fields: the environment's reset distribution, a uniform price on
+[0, a), would need a network's action at a continuum of prices, so its place is taken by a weight per start tuple,
+by default 1 / T: a start drawn uniformly over action profiles, NOT the environment's reset.  The stationary analysis
+has no tuple form: under demand noise the next price is no tuple's price.
 """
 import ctypes
 import json
@@ -20,6 +27,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import attractors as at
 from . import deviation as dv
 from . import equilibrium as eq
 from . import tuple_play as tp
@@ -27,6 +35,11 @@ from ._lib import ThrlError
 
 DEV_DEFAULTS = dict(dv.DEFAULTS)
 EQ_DEFAULTS = dict(eq.DEFAULTS)
+ATTR_DEFAULTS = dict(policies=False, weights="uniform")
+KEEP = at.KEEP
+START_FIELDS = ("start_mass", "start_mass_other", "start_reward")
+TUPLE_FIELDS = ("tuple_rep", "tuple_mu")
+UNIFORM_LABEL = "a start drawn uniformly over action profiles (1 / T per tuple), not the environment's reset distribution"
 
 
 def _agent_gammas(config):
@@ -121,6 +134,47 @@ def parse_equilibrium_options(opt, config):
                 eq.check_gamma([gammas[d]], "agents[%d].gamma" % d)
         except ValueError as e:
             raise ValueError(str(e).replace("training.equilibrium", name))
+    return out
+
+
+def start_weights(weights, T, name="weights"):
+    """float64 [T] or None: "uniform" = 1 / T per tuple, None = no start weights, else T finite numbers >= 0."""
+    if weights is None:
+        return None
+    if isinstance(weights, str):
+        if weights != "uniform":
+            raise ValueError("%s must be 'uniform', null or %d numbers, got %r" % (name, T, weights))
+        return np.full(T, 1.0 / float(T), np.float64)
+    try:
+        w = np.array(weights, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be 'uniform', null or %d numbers, got %r" % (name, T, weights))
+    if w.shape != (T,) or not np.isfinite(w).all() or (w < 0.0).any():
+        raise ValueError("%s must hold %d finite numbers >= 0 (one per action tuple), got shape %s" % (name, T, w.shape))
+    return np.ascontiguousarray(w)
+
+
+def parse_attractor_options(opt, config):
+    """training.greedy_attractors (true or a dict) -> the dict with every key filled in: policies (store the per-tuple
+    arrays), weights ("uniform" = 1 / T per start tuple, null = none, or a list of T numbers >= 0).  Refuses a CAC agent
+    and more than tuple_play.MAX_TUPLES tuples."""
+    name = "training.greedy_attractors"
+    _, T = tp.check_config(config)
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict):
+        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
+    bad = set(opt) - set(ATTR_DEFAULTS)
+    if bad:
+        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(ATTR_DEFAULTS))))
+    out = dict(ATTR_DEFAULTS)
+    out.update(opt)
+    if not isinstance(out["policies"], (bool, np.bool_)):
+        raise ValueError("%s.policies must be true or false, got %r" % (name, out["policies"]))
+    out["policies"] = bool(out["policies"])
+    w = start_weights(out["weights"], T, name + ".weights")
+    if w is not None and not isinstance(out["weights"], str):
+        out["weights"] = [float(x) for x in w]
     return out
 
 
@@ -273,6 +327,48 @@ def equilibrium(batch, agents=None, start=None, policies=False, tol=0.0, tuple_p
     return res
 
 
+def attractors(batch, start=None, weights="uniform", policies=False, tuple_policy=None, tabs=None):
+    """thrl_tuple_attractors for every game of `batch`: attractors.run's dict fields with the T tuples as the state set
+    (n_states = T), start_mass [KEEP, G], start_mass_other [G] and start_reward [N, G] in place of the reset_* fields,
+    plus "start" [G].  tuple_policy and start as in deviation(); a game without a start tuple has rep_x0 = mu_x0 =
+    slot_x0 = -1.  weights: "uniform" (1 / T per start tuple), None (no start_* fields) or T numbers >= 0.
+    policies=True adds tuple_rep, tuple_mu (uint16) [G, T]."""
+    import torch
+    G, N = batch.G, batch.N
+    tabs, T, tuple_policy, t0, d_rew, d_sca = _inputs(batch, tuple_policy, start, tabs)
+    w = start_weights(weights, T)
+    dev = batch.device
+    a = _lib.TupleAttractorsArgs()
+    a.n_games, a.n_tuples = G, T
+    with torch.cuda.device(dev):
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        out = {f: i32(G) for f in at.GAME_INT}
+        out.update({f: i32(KEEP, G) for f in at.SLOT_INT})
+        out.update({f: f64(KEEP, N, G) for f in at.SLOT_FLOAT})
+        d_w = None
+        if w is not None:
+            d_w = torch.from_numpy(w).to(dev)
+            a.start_w = d_w.data_ptr()
+            out.update(start_mass=f64(KEEP, G), start_mass_other=f64(G), start_reward=f64(N, G))
+        if policies:
+            out["tuple_rep"] = torch.zeros((G, T), dtype=torch.int16, device=dev)
+            out["tuple_mu"] = torch.zeros((G, T), dtype=torch.int16, device=dev)
+        a.start, a.tuple_policy, a.reward, a.scaled = t0.data_ptr(), tuple_policy.data_ptr(), d_rew.data_ptr(), d_sca.data_ptr()
+        for f, t in out.items():
+            setattr(a, f, t.data_ptr())
+        _lib.check(batch.L.thrl_tuple_attractors(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                   "thrl_tuple_attractors")
+        torch.cuda.synchronize(dev)
+        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res["start"] = t0.cpu().numpy()
+    for f in TUPLE_FIELDS:
+        if f in res:
+            res[f] = res[f].view(np.uint16)
+    res["n_states"] = T
+    return res
+
+
 # ---------------------------------------------------------------------------------------------- host side
 def _no_start(rows, start, ids):
     ids = np.asarray(ids, np.int64).reshape(-1)
@@ -292,6 +388,33 @@ def summarize_equilibrium(games, ids, n_groups, agents, tol=0.0, delta=None):
     """equilibrium.summarize's rows with no_start added (those games have NaN on-path losses: not a best response on a
     path they do not have).  games also holds start [G]."""
     return _no_start(eq.summarize(games, ids, n_groups, agents, tol, delta), games["start"], ids)
+
+
+def _as_reset(games):
+    """games with the start_* fields under attractors.py's reset_* names (its gains() and summarize() read those)."""
+    g = dict(games)
+    for f in START_FIELDS:
+        if f in g:
+            g["reset" + f[5:]] = g[f]
+    return g
+
+
+def attractor_gains(games, nash, cartel):
+    """attractors.gains on the tuple form's arrays: per-game profit gains train, largest and start (None without the
+    start weights)."""
+    gn = at.gains(_as_reset(games), nash, cartel)
+    return {"train": gn["train"], "largest": gn["largest"], "start": gn["reset"]}
+
+
+def summarize_attractors(games, ids, n_groups, nash, cartel):
+    """attractors.summarize's rows with delta_reset_mean named delta_start_mean (the gain in expectation over the start
+    weights), train_mass_* the training attractor's share of the start weights, luck_mean against the start-expected
+    gain, and no_start added (those games have no training attractor: they count under games only).  games also holds
+    start [G]."""
+    rows = []
+    for r in at.summarize(_as_reset(games), ids, n_groups, nash, cartel):
+        rows.append({("delta_start_mean" if k == "delta_reset_mean" else k): v for k, v in r.items()})
+    return _no_start(rows, games["start"], ids)
 
 
 def load_deviation_games(d, deviator):
@@ -314,6 +437,55 @@ def load_equilibrium_games(d):
         g.update(br_policy=np.load(os.path.join(d, "geq_policy.npy")), v_opt=np.load(os.path.join(d, "geq_v_opt.npy")),
                  v_pi=np.load(os.path.join(d, "geq_v_pi.npy")))
     return g
+
+
+def save_attractor_games(d, r):
+    """gattr_games int32 [6, G], gattr_slots int32 [3, KEEP, G], gattr_cycle float64 [2, KEEP, N, G] (attractors.
+    save_games' shapes and orders), gattr_start int32 [G]; with start weights gattr_start_mass [KEEP + 1, G] (the slots,
+    then the attractors not kept) and gattr_start_reward [N, G]; with per-tuple arrays gattr_state uint16 [2, G, T]
+    (rep, mu)."""
+    np.save(os.path.join(d, "gattr_games.npy"), np.stack([r[f] for f in at.GAME_INT]).astype(np.int32))
+    np.save(os.path.join(d, "gattr_slots.npy"), np.stack([r[f] for f in at.SLOT_INT]).astype(np.int32))
+    np.save(os.path.join(d, "gattr_cycle.npy"), np.stack([r[f] for f in at.SLOT_FLOAT]).astype(np.float64))
+    np.save(os.path.join(d, "gattr_start.npy"), np.asarray(r["start"], np.int32))
+    if "start_mass" in r:
+        np.save(os.path.join(d, "gattr_start_mass.npy"),
+                np.concatenate([r["start_mass"], np.asarray(r["start_mass_other"])[None]]).astype(np.float64))
+        np.save(os.path.join(d, "gattr_start_reward.npy"), np.asarray(r["start_reward"], np.float64))
+    if "tuple_rep" in r:
+        np.save(os.path.join(d, "gattr_state.npy"), np.stack([r["tuple_rep"], r["tuple_mu"]]).astype(np.uint16))
+
+
+def load_attractor_games(d):
+    """The per-game arrays a run directory holds (training.greedy_attractors)."""
+    gm, sl, cy = (np.load(os.path.join(d, "gattr_%s.npy" % f)) for f in ("games", "slots", "cycle"))
+    g = {f: gm[k] for k, f in enumerate(at.GAME_INT)}
+    g.update({f: sl[k] for k, f in enumerate(at.SLOT_INT)})
+    g.update({f: cy[k] for k, f in enumerate(at.SLOT_FLOAT)})
+    g["start"] = np.load(os.path.join(d, "gattr_start.npy"))
+    if os.path.isfile(os.path.join(d, "gattr_start_mass.npy")):
+        sm = np.load(os.path.join(d, "gattr_start_mass.npy"))
+        g.update(start_mass=sm[:-1], start_mass_other=sm[-1],
+                 start_reward=np.load(os.path.join(d, "gattr_start_reward.npy")))
+    if os.path.isfile(os.path.join(d, "gattr_state.npy")):
+        st = np.load(os.path.join(d, "gattr_state.npy"))
+        g.update(tuple_rep=st[0], tuple_mu=st[1])
+    return g
+
+
+def write_attractors(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None):
+    """train_one's training.greedy_attractors outputs: the gattr_*.npy files (save_attractor_games) and
+    greedy_attractors.json."""
+    tabs = tp.tables(config)
+    r = attractors(batch, weights=opt["weights"], policies=opt["policies"], tuple_policy=tuple_policy, tabs=tabs)
+    save_attractor_games(exp_path, r)
+    nash, cartel = dv.optimal(config)
+    summary = summarize_attractors(r, ids, n_groups, nash, cartel)
+    label = UNIFORM_LABEL if opt["weights"] == "uniform" else ("none" if opt["weights"] is None else "given per tuple")
+    with open(os.path.join(exp_path, "greedy_attractors.json"), "w") as f:
+        json.dump({"options": opt, "n_states": int(r["n_states"]), "keep": KEEP, "nash": nash, "cartel": cartel,
+                   "quantiles": list(at.QUANTILES), "start_weights": label, "summary": summary}, f, indent=2)
+    return r
 
 
 def write_deviation(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=dv.ROW_BUDGET,

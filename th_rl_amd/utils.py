@@ -571,3 +571,50 @@ def greedy_equilibrium_games(exp_path, agent=0):
     cols.update(br_on=fl["br_on"][int(agent)], br_all=fl["br_all"][int(agent)], nash=fl["nash"], perfect=fl["perfect"])
     n = g["mu"].shape[0]
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
+def greedy_attractor_summary(exp_path):
+    """A run's attractor analysis in tuple form (training.greedy_attractors, any mix of QTable / Reinforce / ActorCritic
+    agents): greedy_attractors.json's summary as a DataFrame with attractor_summary's columns, delta_start_mean (the
+    profit gain in expectation over the start weights, by default a start drawn uniformly over action profiles -- not
+    the environment's reset distribution) in place of delta_reset_mean, plus no_start, n_states (= T), Nash and
+    Cartel."""
+    import json
+    with open(os.path.join(exp_path, "greedy_attractors.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["n_states"] = int(desc["n_states"])
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def greedy_attractor_games(exp_path):
+    """Per-game results of training.greedy_attractors, one row per game indexed by its GLOBAL id: start (the training
+    tuple, -1 = none), n_attr, mu_max, n_cycle_states, rep_x0, mu_x0, slot_x0, per kept slot k rep_<k>, lam_<k>,
+    basin_<k>, delta_<k> (its profit gain, NaN past n_attr) and mass_<k>, and delta_train, delta_start, mass_other."""
+    import json
+    from th_rl_amd import attractors as at, tuple_analysis as ta
+    if not os.path.isfile(os.path.join(exp_path, "gattr_games.npy")):
+        raise KeyError("no attractor analysis in tuple form (gattr_games.npy) under %s (training.greedy_attractors)" % exp_path)
+    with open(os.path.join(exp_path, "greedy_attractors.json")) as f:
+        desc = json.load(f)
+    off = 0
+    if os.path.isfile(os.path.join(exp_path, "config.json")):
+        with open(os.path.join(exp_path, "config.json")) as f:
+            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    g = ta.load_attractor_games(exp_path)
+    gn = ta.attractor_gains(g, desc["nash"], desc["cartel"])
+    cols = {"start": g["start"]}
+    cols.update({f: g[f] for f in at.GAME_INT})
+    for k in range(g["rep"].shape[0]):
+        cols.update({"rep_%d" % k: g["rep"][k], "lam_%d" % k: g["lam"][k], "basin_%d" % k: g["basin"][k]})
+        cols["delta_%d" % k] = numpy.where(g["rep"][k] >= 0, at.profit_gain(g["cycle_reward"][k], desc["nash"], desc["cartel"]),
+                                           numpy.nan)
+        if "start_mass" in g:
+            cols["mass_%d" % k] = g["start_mass"][k]
+    cols["delta_train"] = gn["train"]
+    if gn["start"] is not None:
+        cols["delta_start"] = gn["start"]
+        cols["mass_other"] = g["start_mass_other"]
+    n = g["n_attr"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
