@@ -1196,6 +1196,148 @@ typedef struct {
 } thrl_tuple_attractors_args;
 int thrl_tuple_attractors(const thrl_cfg* cfg, const thrl_tuple_attractors_args* args, void* stream);
 
+/*
+ * thrl_price_policy: thrl_tuple_policy's contract with a free list of prices in place of the T tuple prices.  No
+ * reference counterpart.  price_policy (device uint16 [G][N][J], G = args.n_games in [1, cfg.n_games], J =
+ * args.n_prices in [1, THRL_STAT_MAX_CELLS]): entry [g][i][k] is what get_action of agent i of game g returns at the
+ * state x[k]:
+ *   kind[i] = 0, QTable: the first maximum (strict >) of row encode64_i(x[k]) of agent i's table in q[g];
+ *   kind[i] = 1 / 2, Reinforce / ActorCritic: bit for bit the action thrl_nn_act / thrl_ac_act return with u = NULL at
+ *     the price (float)x[k] (the evaluation thrl_tuple_policy runs: a game's network stays in a wave's registers while
+ *     the wave goes through the game's prices).
+ * price (device float64): [J], the same prices for every game, or with THRL_PP_PER_GAME [G][J], x[k] of game g =
+ * price[g][k] (J = 1 at a batch's state: the action every agent takes where training stopped).  kind, nn_params and q
+ * as in thrl_tuple_policy; everything but price_policy is read only.  Called with the T tuple prices the call writes
+ * exactly what thrl_tuple_policy writes.
+ *
+ * Returns THRL_ERR_UNSUPPORTED for a CAC agent (kind 3) or n_prices > THRL_STAT_MAX_CELLS; THRL_ERR_BAD_CONFIG for
+ * n_games outside [1, cfg.n_games], an unknown flag, reserved != 0, a kind outside [0, 3], a neural agent with actions
+ * outside [2, 32] or n_prices < 1; THRL_ERR_NULL for a missing cfg, args, price, price_policy, nn_params[i] of a neural
+ * agent, or q with a QTable agent in the game.
+ */
+#define THRL_PP_PER_GAME 1
+typedef struct {
+    int32_t n_games;                     /* G in [1, cfg.n_games]                            */
+    int32_t n_prices;                    /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t flags;                       /* THRL_PP_PER_GAME                                 */
+    int32_t reserved;                    /* 0                                                */
+    int32_t kind[THRL_MAXA];             /* 0 = QTable, 1 = Reinforce, 2 = ActorCritic (3 = CAC is refused) */
+    const float* nn_params[THRL_MAXA];   /* device [G][P] for the neural agents              */
+    const double* price;                 /* device [J], with THRL_PP_PER_GAME [G][J]         */
+    uint16_t* price_policy;              /* device [G][N][J], out                            */
+} thrl_price_policy_args;
+int thrl_price_policy(const thrl_cfg* cfg, const void* q, const thrl_price_policy_args* args, void* stream);
+
+/*
+ * thrl_tuple_stationary: greedy play under demand noise (thrl_stationary) for ANY mix of QTable, Reinforce and
+ * ActorCritic agents.  No reference counterpart.  Under noise the next price is no tuple's price, but its distribution
+ * depends only on the tuple just played: with probability 1 - p it is the tuple's noise-free price, with probability p
+ * it is uniform on [0.7 a - u(t), a - u(t)] clipped at 0.  So the distribution over the tuple played at a step is a
+ * Markov chain on the game's T action tuples, and this call iterates it.  What it needs beyond tuple_policy is every
+ * agent's greedy action as a function of the price on [0, a): a QTable's is piecewise constant with known cuts, a
+ * network's is piecewise constant with unknown cuts and is SAMPLED on a per-config grid of cells (thrl_price_policy at
+ * the cell midpoints); the share of the axis on which the sampling may be wrong is reported per game (unresolved).
+ * Of a valid cfg only n_agents and n_actions are used; nothing of a batch is read or written, every input is read
+ * only.  G = args.n_games >= 1, T = args.n_tuples = prod_i n_actions_i <= THRL_TP_MAX_TUPLES, J = args.n_cells in
+ * [1, THRL_STAT_MAX_CELLS].  All arithmetic is float64, every operation rounded once, in the order written here.
+ *
+ * Strategies.  tuple_policy (device uint16 [G][N][T], thrl_tuple_policy) and cell_policy (device uint16 [G][N][J],
+ * thrl_price_policy at the cell midpoints); entries at or above n_actions_i are clamped to n_actions_i - 1.  With
+ * tstride_i = prod_{j > i} n_actions_j:
+ *   F_g(t)   = sum_i min(tuple_policy[g][i][t], A_i - 1) * tstride_i     the tuple played after tuple t without a shock
+ *   tau_g(k) = sum_i min(cell_policy[g][i][k], A_i - 1) * tstride_i      the tuple played at a price in cell k
+ *
+ * Per-config tables, computed by the caller (th_rl_amd.tuple_stationary.tables) and only read here.  Cells: [0, a) cut
+ * at {0, a}, at the encode breakpoints of the QTable agents and at a * m / R, m = 1..R-1 (R = the caller's
+ * resolution); there are no point cells.  cell_w (device double [J]) = the cell's length / a; the strategies are
+ * sampled at the midpoints, which lie strictly inside their cells, so a QTable's entry is exact for its whole cell.
+ * reward, scaled (device double [N][T]) and the noise-free price (device double [T]) are th_rl_amd.tuple_play.tables'
+ * arrays; band_lo (device int32 [T]), band (device double [T][W], W = band_w), noise_price (device double [T]) and
+ * noise_reward (device double [N][T]) are thrl_stationary's "Per-config tables" computed over these cells, with u(t)
+ * from tuple_play's quantities: n(t, k) = band[t][k - band_lo[t]] where 0 <= k - band_lo[t] < W, else 0.
+ *
+ * Noise probability: p_g, q_g = 1 - p_g, the host-visible and the per-game rules of thrl_stationary (an entry of
+ * noise_prob_g outside (0, 1], NaN included: that game gets iters = -1 and zeros, no other game is affected).
+ *
+ * Start distribution over the tuple played first:
+ *   m_0(t') = sum over the cells k with tau_g(k) = t' of cell_w(k), in ascending k from 0.0 (the environment's reset,
+ *             a uniform price on [0, a)), or
+ *   with THRL_TS_START_TUPLE the unit mass on start[g] (device int32 [G]); a value outside [0, T) refuses that game:
+ *             iters = -1 and zeros.
+ *
+ * One step from m, in the lazy form of thrl_stationary:
+ *   nu(k)  = sum_t m(t) * n(t, k)                      ascending t from 0.0; terms that are zero may be skipped
+ *   D(t')  = sum over the t with F_g(t) = t' of m(t)   ascending t from 0.0
+ *   Nn(t') = sum over the k with tau_g(k) = t' of nu(k)   ascending k from 0.0
+ *   s(t')  = q_g * D(t') + p_g * Nn(t')
+ *   m'(t') = 0.5 * m(t') + 0.5 * s(t')
+ *   chg    = max_t |m'(t) - m(t)|
+ * Stop after the first step with chg <= args.tol, or after args.max_iters steps.
+ *
+ * Outputs, per game, from the last iterate m; every sum over ascending t from 0.0:
+ *   iters, change        the steps taken and the last chg
+ *   mass                 sum_t m(t)
+ *   stat_reward[i][g]    sum_t m(t) * (q_g * reward_i(t) + p_g * noise_reward_i(t))
+ *   stat_action[i][g]    sum_t m(t) * scaled_i(t)
+ *   stat_price[g]        sum_t m(t) * (q_g * price(t) + p_g * noise_price(t))
+ *   pi (optional, double [G][T])   m itself
+ *
+ * Diagnostics of the sampling (optional, each may be NULL), from cell_policy alone and for every game, refused or not.
+ * kind[i] (thrl_tuple_policy's codes) says which agents are networks:
+ *   n_switch[g]    the number of pairs of adjacent cells (k, k + 1) on which the clamped entry of some neural agent
+ *                  differs
+ *   unresolved[g]  sum over those pairs of 0.5 * (cell_w(k) + cell_w(k + 1)), in ascending k from 0.0: the share of the
+ *                  price axis on which a sampled network strategy may differ from the true one
+ * A strategy that switches twice between two adjacent midpoints is not seen by either; a finer grid is the remedy.
+ *
+ * Working set.  A game is solved by one block in LDS: the two iterates and nu (16 T + 8 J bytes), the stable groupings
+ * of the cells by tau_g and of the tuples by F_g (2 J + 6 T + 4 bytes) and 512 (2 N + 2) bytes of staging, the sum
+ * rounded up to 16 bytes: 22 T + 10 J + 512 (2 N + 2) + 4.  The call returns THRL_ERR_UNSUPPORTED when that exceeds a
+ * CU's LDS; on a 160 KB CU it does not within the limits on T and J (131.0 KB at T = J = 4096 with two agents,
+ * 137.0 KB with eight), so every game within them is solved.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games < 1, an unknown flag, n_tuples < 1 or n_tuples != prod_i n_actions_i,
+ * n_cells < 1, band_w < 1, max_iters outside [1, THRL_STAT_MAX_ITERS], tol < 0 or NaN, noise_prob as above, or a kind
+ * outside [0, 3]; THRL_ERR_UNSUPPORTED for a CAC agent (kind 3), n_tuples > THRL_TP_MAX_TUPLES, n_cells >
+ * THRL_STAT_MAX_CELLS or the working set; THRL_ERR_NULL for a missing cfg, args, tuple_policy, cell_policy, table
+ * (cell_w, reward, scaled, price, band_lo, band, noise_reward, noise_price), per-game output other than pi, n_switch and
+ * unresolved, or start with THRL_TS_START_TUPLE.
+ */
+#define THRL_TS_START_TUPLE 1
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of tuple_policy and cell_policy    */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t n_cells;                 /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t band_w;                  /* W >= 1                                           */
+    int32_t max_iters;               /* in [1, THRL_STAT_MAX_ITERS]                      */
+    int32_t flags;                   /* THRL_TS_START_TUPLE                              */
+    int32_t kind[THRL_MAXA];         /* 0 = QTable, 1 = Reinforce, 2 = ActorCritic: read for n_switch / unresolved */
+    double  noise_prob;              /* p in (0, 1], read when noise_prob_g is NULL      */
+    double  tol;                     /* >= 0                                             */
+    const double* noise_prob_g;      /* device [G] or NULL                               */
+    const int32_t* start;            /* device [G], with THRL_TS_START_TUPLE             */
+    const uint16_t* tuple_policy;    /* device [G][N][T]                                 */
+    const uint16_t* cell_policy;     /* device [G][N][J]                                 */
+    const double* cell_w;            /* device [J]                                       */
+    const double* reward;            /* device [N][T]                                    */
+    const double* scaled;            /* device [N][T]                                    */
+    const double* price;             /* device [T]                                       */
+    const int32_t* band_lo;          /* device [T]                                       */
+    const double* band;              /* device [T][W]                                    */
+    const double* noise_reward;      /* device [N][T]                                    */
+    const double* noise_price;       /* device [T]                                       */
+    int32_t* iters;                  /* device [G]                                       */
+    double*  change;                 /* device [G]                                       */
+    double*  mass;                   /* device [G]                                       */
+    double*  stat_reward;            /* device [N][G]                                    */
+    double*  stat_action;            /* device [N][G]                                    */
+    double*  stat_price;             /* device [G]                                       */
+    double*  pi;                     /* device [G][T] or NULL                            */
+    int32_t* n_switch;               /* device [G] or NULL                               */
+    double*  unresolved;             /* device [G] or NULL                               */
+} thrl_tuple_stationary_args;
+int thrl_tuple_stationary(const thrl_cfg* cfg, const thrl_tuple_stationary_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,35 @@ class TupleAttractorsArgs(ctypes.Structure):
     ]
 
 
+PP_PER_GAME = 1
+TS_START_TUPLE = 1
+
+
+class PricePolicyArgs(ctypes.Structure):
+    """thrl_price_policy_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_prices", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("kind", ctypes.c_int32 * MAXA), ("nn_params", ctypes.c_void_p * MAXA),
+        ("price", ctypes.c_void_p), ("price_policy", ctypes.c_void_p),
+    ]
+
+
+class TupleStationaryArgs(ctypes.Structure):
+    """thrl_tuple_stationary_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("n_cells", ctypes.c_int32), ("band_w", ctypes.c_int32),
+        ("max_iters", ctypes.c_int32), ("flags", ctypes.c_int32), ("kind", ctypes.c_int32 * MAXA),
+        ("noise_prob", ctypes.c_double), ("tol", ctypes.c_double),
+        ("noise_prob_g", ctypes.c_void_p), ("start", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p),
+        ("cell_policy", ctypes.c_void_p), ("cell_w", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+        ("scaled", ctypes.c_void_p), ("price", ctypes.c_void_p), ("band_lo", ctypes.c_void_p), ("band", ctypes.c_void_p),
+        ("noise_reward", ctypes.c_void_p), ("noise_price", ctypes.c_void_p),
+        ("iters", ctypes.c_void_p), ("change", ctypes.c_void_p), ("mass", ctypes.c_void_p),
+        ("stat_reward", ctypes.c_void_p), ("stat_action", ctypes.c_void_p), ("stat_price", ctypes.c_void_p),
+        ("pi", ctypes.c_void_p), ("n_switch", ctypes.c_void_p), ("unresolved", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -288,7 +317,7 @@ SYMBOLS = [
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
-    "thrl_tuple_attractors",
+    "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary",
 ]
 CAC_PARAMS = 1283
 
@@ -409,6 +438,10 @@ def load():
     L.thrl_tuple_equilibrium.argtypes = [cfgp, ctypes.POINTER(TupleEquilibriumArgs), vp]
     L.thrl_tuple_attractors.restype = ctypes.c_int
     L.thrl_tuple_attractors.argtypes = [cfgp, ctypes.POINTER(TupleAttractorsArgs), vp]
+    L.thrl_price_policy.restype = ctypes.c_int
+    L.thrl_price_policy.argtypes = [cfgp, vp, ctypes.POINTER(PricePolicyArgs), vp]
+    L.thrl_tuple_stationary.restype = ctypes.c_int
+    L.thrl_tuple_stationary.argtypes = [cfgp, ctypes.POINTER(TupleStationaryArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

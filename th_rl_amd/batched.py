@@ -394,6 +394,21 @@ class GameBatch:
             raise ThrlError("GameBatch: call init_tables() or set_tables() first")
         return ta.attractors(self, start=start, weights=weights, policies=policies, tuple_policy=tuple_policy)
 
+    def greedy_stationary(self, noise_prob=None, start="reset", resolution=1024, tol=1e-12, max_iters=8192, pi=False,
+                          tuple_policy=None, cell_policy=None, n_games=None, tabs=None):
+        """Greedy play under demand noise for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_stationary.run,
+        thrl_price_policy + thrl_tuple_stationary): the long-run distribution over the tuple played and what it earns --
+        GameBatch.stationary's outputs with pi [G, T] over the action tuples, plus n_switch and unresolved [G]: a network's
+        strategy is sampled at the midpoints of `resolution` uniform cells of the price axis (beside the QTable agents'
+        breakpoints), and unresolved is the share of the axis on which that sampling may be wrong.  start: "reset", "state"
+        (the tuple played at the state the batch holds) or int [G] start tuples.  A batch with a CAC agent or more than
+        4096 action tuples or cells raises ValueError.  Nothing of the batch is written."""
+        from . import tuple_stationary as ts
+        if not self.initialized:
+            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
+        return ts.run(self, noise_prob=noise_prob, start=start, resolution=resolution, tol=tol, max_iters=max_iters, pi=pi,
+                      tuple_policy=tuple_policy, cell_policy=cell_policy, n_games=n_games, tabs=tabs)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
         its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.

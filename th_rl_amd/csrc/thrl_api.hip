@@ -20,6 +20,7 @@
 #include "thrl_tuple_analysis.h"
 #include "thrl_tuple_attractors.h"
 #include "thrl_tuple_play.h"
+#include "thrl_tuple_stationary.h"
 #include "thrl_wave_lut.h"
 
 using namespace thrl;
@@ -1586,44 +1587,74 @@ static int tuple_count_check(const thrl_cfg* c, int n_tuples) {
     return THRL_OK;
 }
 
+// kinds of a game in tuple form: CAC has no tuples, a network has 2..32 actions
+static int tuple_kinds_check(const thrl_cfg* c, const int32_t* kind) {
+    for (int i = 0; i < c->n_agents; i++) {
+        if (kind[i] == 3)
+            return fail(THRL_ERR_UNSUPPORTED, "agent %d is a CAC agent: its action is continuous, the game has no tuples", i);
+        if (kind[i] < 0 || kind[i] > 3) return fail(THRL_ERR_BAD_CONFIG, "agent %d: kind=%d", i, kind[i]);
+        if (kind[i] != 0 && (c->n_actions[i] < 2 || c->n_actions[i] > 32))
+            return fail(THRL_ERR_BAD_CONFIG, "neural agent %d: actions=%d out of [2,32]", i, c->n_actions[i]);
+    }
+    return THRL_OK;
+}
+
+// the extraction of thrl_tuple_policy and thrl_price_policy: n_prices states per game, shared (price_stride = 0) or
+// per game, into out [G][N][n_prices]
+static int extract_at_prices(const thrl_cfg* c, const void* q, const int32_t* kind, const float* const* nn_params, int G,
+                             int n_prices, const double* price, int64_t price_stride, uint16_t* out, void* stream) {
+    const int N = c->n_agents;
+    TpPolicyArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_agents(c, a.ag, nullptr);
+    a.G = G; a.N = N; a.T = n_prices;
+    a.stride = (int64_t)thrl_table_stride(c);
+    for (int i = 0; i < N; i++) {
+        if (kind[i] == 0) {
+            a.q_agent[a.n_q++] = i;
+        } else {
+            if (!nn_params[i]) return fail(THRL_ERR_NULL, "nn_params[%d] is NULL", i);
+            const int j = a.n_nn++;
+            a.nn_agent[j] = i;
+            a.nn_actions[j] = c->n_actions[i];
+            a.nn_stride[j] = kind[i] == 2 ? (int32_t)thrl_ac_param_count(c->n_actions[i])
+                                          : (int32_t)thrl_nn_param_count(c->n_actions[i]);
+            a.nn_params[j] = nn_params[i];
+        }
+    }
+    if (a.n_q > 0 && !q) return fail(THRL_ERR_NULL, "q is NULL with a QTable agent in the game");
+    a.q = q; a.price = price; a.price_stride = price_stride; a.policy = out;
+    const int e = thrl::launch_tp_policy(a, c->q_dtype, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_tp_qtable / k_tp_neural launch") : THRL_OK;
+}
+
 int thrl_tuple_policy(const thrl_cfg* c, const void* q, const thrl_tuple_policy_args* x, void* stream) {
     int rc = validate(c);
     if (rc) return rc;
     if (!x) return fail(THRL_ERR_NULL, "args is NULL");
-    const int N = c->n_agents;
     if (x->n_games < 1 || x->n_games > c->n_games)
         return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
-    for (int i = 0; i < N; i++) {
-        if (x->kind[i] == 3)
-            return fail(THRL_ERR_UNSUPPORTED, "agent %d is a CAC agent: its action is continuous, the game has no tuples", i);
-        if (x->kind[i] < 0 || x->kind[i] > 3) return fail(THRL_ERR_BAD_CONFIG, "agent %d: kind=%d", i, x->kind[i]);
-        if (x->kind[i] != 0 && (c->n_actions[i] < 2 || c->n_actions[i] > 32))
-            return fail(THRL_ERR_BAD_CONFIG, "neural agent %d: actions=%d out of [2,32]", i, c->n_actions[i]);
-    }
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
     if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
     if (!x->price || !x->tuple_policy) return fail(THRL_ERR_NULL, "price / tuple_policy is NULL");
-    TpPolicyArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_agents(c, a.ag, nullptr);
-    a.G = x->n_games; a.N = N; a.T = x->n_tuples;
-    a.stride = (int64_t)thrl_table_stride(c);
-    for (int i = 0; i < N; i++) {
-        if (x->kind[i] == 0) {
-            a.q_agent[a.n_q++] = i;
-        } else {
-            if (!x->nn_params[i]) return fail(THRL_ERR_NULL, "nn_params[%d] is NULL", i);
-            const int j = a.n_nn++;
-            a.nn_agent[j] = i;
-            a.nn_actions[j] = c->n_actions[i];
-            a.nn_stride[j] = x->kind[i] == 2 ? (int32_t)thrl_ac_param_count(c->n_actions[i])
-                                             : (int32_t)thrl_nn_param_count(c->n_actions[i]);
-            a.nn_params[j] = x->nn_params[i];
-        }
-    }
-    if (a.n_q > 0 && !q) return fail(THRL_ERR_NULL, "q is NULL with a QTable agent in the game");
-    a.q = q; a.price = x->price; a.policy = x->tuple_policy;
-    const int e = thrl::launch_tp_policy(a, c->q_dtype, (hipStream_t)stream);
-    return e ? hip_fail(e, "k_tp_qtable / k_tp_neural launch") : THRL_OK;
+    return extract_at_prices(c, q, x->kind, x->nn_params, x->n_games, x->n_tuples, x->price, 0, x->tuple_policy, stream);
+}
+
+int thrl_price_policy(const thrl_cfg* c, const void* q, const thrl_price_policy_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->flags & ~THRL_PP_PER_GAME) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if (x->n_prices < 1) return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d must be >= 1", x->n_prices);
+    if (x->n_prices > THRL_STAT_MAX_CELLS)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_price_policy: n_prices=%d, at most %d", x->n_prices, THRL_STAT_MAX_CELLS);
+    if (!x->price || !x->price_policy) return fail(THRL_ERR_NULL, "price / price_policy is NULL");
+    return extract_at_prices(c, q, x->kind, x->nn_params, x->n_games, x->n_prices, x->price,
+                             (x->flags & THRL_PP_PER_GAME) ? x->n_prices : 0, x->price_policy, stream);
 }
 
 int thrl_tuple_walk(const thrl_cfg* c, const thrl_tuple_walk_args* x, void* stream) {
@@ -1847,6 +1878,81 @@ int thrl_tuple_attractors(const thrl_cfg* c, const thrl_tuple_attractors_args* x
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_tuple_attractors(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_ta_attractors launch") : THRL_OK;
+}
+
+int thrl_tuple_stationary(const thrl_cfg* c, const thrl_tuple_stationary_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // every host-visible argument is checked before the device is touched
+    if (x->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", x->n_games);
+    if (x->flags & ~THRL_TS_START_TUPLE) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (x->n_cells < 1 || x->band_w < 1)
+        return fail(THRL_ERR_BAD_CONFIG, "n_cells=%d and band_w=%d must be >= 1", x->n_cells, x->band_w);
+    if (x->max_iters < 1 || x->max_iters > THRL_STAT_MAX_ITERS)
+        return fail(THRL_ERR_BAD_CONFIG, "max_iters=%d out of [1,%d]", x->max_iters, THRL_STAT_MAX_ITERS);
+    if (!(x->tol >= 0.0)) return fail(THRL_ERR_BAD_CONFIG, "tol=%g must be >= 0", x->tol);
+    if (!x->noise_prob_g && !(x->noise_prob > 0.0 && x->noise_prob <= 1.0))
+        return fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of (0, 1]", x->noise_prob);
+    if (x->n_cells > THRL_STAT_MAX_CELLS)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_tuple_stationary: n_cells=%d, at most %d", x->n_cells, THRL_STAT_MAX_CELLS);
+    const bool start_tuple = (x->flags & THRL_TS_START_TUPLE) != 0;
+    if (!x->tuple_policy || !x->cell_policy || !x->cell_w || !x->reward || !x->scaled || !x->price || !x->band_lo || !x->band
+        || !x->noise_reward || !x->noise_price)
+        return fail(THRL_ERR_NULL, "tuple_policy / cell_policy / cell_w / reward / scaled / price / band_lo / band / "
+                                   "noise_reward / noise_price is NULL");
+    if (!x->iters || !x->change || !x->mass || !x->stat_reward || !x->stat_action || !x->stat_price)
+        return fail(THRL_ERR_NULL, "iters / change / mass / stat_reward / stat_action / stat_price is NULL");
+    if (start_tuple && !x->start) return fail(THRL_ERR_NULL, "start is NULL with THRL_TS_START_TUPLE");
+
+    TsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples; a.J = x->n_cells; a.W = x->band_w;
+    a.max_iters = x->max_iters; a.start_tuple = start_tuple;
+    a.noise_prob = x->noise_prob; a.tol = x->tol;
+    int ts = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        a.n_actions[i] = c->n_actions[i];
+        a.tstride[i] = ts;
+        ts *= c->n_actions[i];
+        if (x->kind[i] != 0) a.neural_mask |= 1 << i;
+    }
+    // LDS of a block (the working set of include/thrl.h): 8-byte arrays first, nu directly behind the second iterate,
+    // then the 2-byte arrays of the two groupings
+    const int T = a.T, J = a.J;
+    int off = 0;
+    a.o_ma = off; off += 8 * T;
+    a.o_mb = off; off += 8 * T;
+    a.o_nu = off; off += 8 * J;
+    a.o_prod = off; off += 8 * 64 * (2 * N + 2);
+    a.o_permk = off; off += 2 * J;
+    a.o_startk = off; off += 2 * (T + 1);
+    a.o_permt = off; off += 2 * T;
+    a.o_startt = off; off += 2 * (T + 1);
+    a.lds_bytes = (off + 15) & ~15;
+    a.noise_prob_g = x->noise_prob_g; a.start = x->start; a.tuple_policy = x->tuple_policy; a.cell_policy = x->cell_policy;
+    a.cell_w = x->cell_w; a.reward = x->reward; a.scaled = x->scaled; a.price = x->price; a.band_lo = x->band_lo;
+    a.band = x->band; a.noise_reward = x->noise_reward; a.noise_price = x->noise_price;
+    a.iters = x->iters; a.change = x->change; a.mass = x->mass; a.stat_reward = x->stat_reward;
+    a.stat_action = x->stat_action; a.stat_price = x->stat_price; a.pi = x->pi;
+    a.n_switch = x->n_switch; a.unresolved = x->unresolved;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    if (lds_cu > 0 && a.lds_bytes > lds_cu)          // cannot happen on a 160 KB CU within the limits on T and J
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_tuple_stationary: %d bytes of LDS per game (T=%d, n_cells=%d), the device has %d",
+                    a.lds_bytes, T, J, lds_cu);
+    int per_cu = kTsMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes > 0 ? lds_cu / a.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_tuple_stationary(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_ts_switch / k_ts_chain launch") : THRL_OK;
 }
 
 }  // extern "C"

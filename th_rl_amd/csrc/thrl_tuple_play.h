@@ -22,7 +22,8 @@ struct TpPolicyArgs {
     AgentParams ag[THRL_MAXA];
     int64_t stride;                            // elements per game of q
     const void* q;
-    const double* price;                       // [T]
+    const double* price;                       // [T], or [G][T] with price_stride = T (thrl_price_policy per game)
+    int64_t price_stride;                      // doubles between two games' prices: 0 = every game reads the same T
     uint16_t* policy;                          // [G][N][T]
 };
 

@@ -9,6 +9,8 @@
 //   v_readlane, so the evaluation loop touches no memory.  Lane j keeps the action of the run's j-th price and the
 //   wave stores the run as one contiguous 128-byte piece.  The evaluation is thrl_policy.h's policy_act, the function
 //   k_nn_act calls, with the same padding: the same bits.
+//   thrl_price_policy runs the same kernels on a free list of J prices, shared by the games or one list per game
+//   (price_stride): T stands for J there.
 // k_tp_qtable: one thread per (game, tuple), every QTable agent in turn: the first maximum of row encode64(price[t]).
 //   Consecutive tuples have neighbouring prices, so a wave reads a few neighbouring rows and its stores are contiguous.
 // k_tp_walk: one lane per match, the walk of k_xplay_walk on a single integer.  The 2-byte policy entries it visits
@@ -25,14 +27,15 @@ namespace {
 // ------------------------------------------------------------------------------------------------ extraction
 template <int APAD>
 __global__ void __launch_bounds__(256) k_tp_neural(int G, int A, int T, const float* __restrict__ params, int P,
-                                                    const double* __restrict__ price, uint16_t* __restrict__ out,
-                                                    int64_t out_stride) {
+                                                    const double* __restrict__ price, int64_t price_stride,
+                                                    uint16_t* __restrict__ out, int64_t out_stride) {
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= G) return;
     PolicyRegs<APAD> r;
     policy_load(r, params + (int64_t)g * P, A, lane);
     uint16_t* o = out + (int64_t)g * out_stride;
+    price += (int64_t)g * price_stride;
     for (int t0 = 0; t0 < T; t0 += 64) {
         const int n = T - t0 < 64 ? T - t0 : 64;
         const float xv = (float)price[t0 + (lane < n ? lane : n - 1)];
@@ -52,7 +55,7 @@ __global__ void __launch_bounds__(256) k_tp_qtable(const TpPolicyArgs a) {
     if (idx >= (int64_t)a.G * a.T) return;
     const int64_t g = idx / a.T;
     const int t = (int)(idx - g * a.T);
-    const double p = a.price[t];
+    const double p = a.price[g * a.price_stride + t];
     const Tq* __restrict__ q = reinterpret_cast<const Tq*>(a.q) + g * a.stride;
     for (int j = 0; j < a.n_q; j++) {
         const int i = a.q_agent[j];
@@ -227,9 +230,9 @@ int launch_tp_policy(const TpPolicyArgs& a, int q_dtype, hipStream_t s) {
         uint16_t* out = a.policy + (int64_t)a.nn_agent[j] * a.T;
         const int64_t os = (int64_t)a.N * a.T;
         // the padding k_nn_act takes for this action count
-        if (A <= 8) hipLaunchKernelGGL(k_tp_neural<8>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, out, os);
-        else if (A <= 24) hipLaunchKernelGGL(k_tp_neural<24>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, out, os);
-        else hipLaunchKernelGGL(k_tp_neural<32>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, out, os);
+        if (A <= 8) hipLaunchKernelGGL(k_tp_neural<8>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, a.price_stride, out, os);
+        else if (A <= 24) hipLaunchKernelGGL(k_tp_neural<24>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, a.price_stride, out, os);
+        else hipLaunchKernelGGL(k_tp_neural<32>, grid, block, 0, s, a.G, A, a.T, a.nn_params[j], a.nn_stride[j], a.price, a.price_stride, out, os);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }

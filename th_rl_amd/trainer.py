@@ -51,6 +51,13 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                       # stationary.json (options, Nash, Cartel, per-group summary), stat_iters.npy int32
                                       # [G], stat_games.npy [4, G], stat_reward.npy / stat_action.npy [N, G]; with pi
                                       # stat_pi.npy [G, J]
+                 "greedy_stationary": null,  # true or {"noise_prob": null, "start": "reset" | "state", "tol": 1e-12,
+                                      # "max_iters": 8192, "pi": false, "resolution": 1024}: "stationary" for any mix of
+                                      # QTable, Reinforce and ActorCritic agents (tuple_stationary.py): the chain of noisy
+                                      # greedy play on the game's action tuples, a network's strategy sampled on
+                                      # `resolution` uniform cells of the price axis: greedy_stationary.json,
+                                      # gstat_iters.npy int32 [2, G] (iters, n_switch), gstat_games.npy [5, G],
+                                      # gstat_reward.npy / gstat_action.npy [N, G]; with pi gstat_pi.npy [G, T]
                  "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
                                      # "horizon": null}: after training (and the greedy statistics) the deviation
                                      # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json
@@ -289,6 +296,10 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if training.get("greedy_attractors") is not None and training.get("greedy_attractors") is not False:
         from th_rl_amd.tuple_analysis import parse_attractor_options
         gat_opt = parse_attractor_options(training["greedy_attractors"], config)      # refuses CAC and too many tuples
+    gst_opt = None
+    if training.get("greedy_stationary") is not None and training.get("greedy_stationary") is not False:
+        from th_rl_amd.tuple_stationary import parse_options as greedy_stationary_options
+        gst_opt = greedy_stationary_options(training["greedy_stationary"], config)     # refuses CAC, too many tuples / cells
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -576,7 +587,7 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
                          with_attractors=at_opt is not None)
 
     tuple_policy = None
-    if gc_opt is not None or gdev_opt is not None or geq_opt is not None or gat_opt is not None:
+    if gc_opt is not None or gdev_opt is not None or geq_opt is not None or gat_opt is not None or gst_opt is not None:
         from th_rl_amd.tuple_play import extract as extract_tuple_policy
         tuple_policy = extract_tuple_policy(batch)      # every agent's strategy in tuple form, once for all greedy_* keys
 
@@ -620,6 +631,16 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
                                              n_groups=training.get("n_groups", None))
         tuple_analysis.write_attractors(exp_path, batch, config, gat_opt, ids, n_groups, tuple_policy=tuple_policy)
+
+    if gst_opt is not None:     # the long-run distribution of greedy play under demand noise over the tuples played
+        from th_rl_amd import tuple_stationary
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        tuple_stationary.write_artefacts(exp_path, batch, config, gst_opt, ids, n_groups, tuple_policy=tuple_policy)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

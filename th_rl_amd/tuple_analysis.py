@@ -18,7 +18,7 @@ attractors() returns attractors.run's dict fields with the T tuples as the state
 start_mass_other, start_reward in place of the reset_* fields: the environment's reset distribution, a uniform price on
 [0, a), would need a network's action at a continuum of prices, so its place is taken by a weight per start tuple,
 by default 1 / T: a start drawn uniformly over action profiles, NOT the environment's reset.  The stationary analysis
-has no tuple form: under demand noise the next price is no tuple's price.
+in tuple form is tuple_stationary.py.
 """
 import ctypes
 import json

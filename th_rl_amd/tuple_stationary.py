@@ -1,0 +1,379 @@
+"""Greedy play under demand noise for games whose agents may be networks (thrl_price_policy, thrl_tuple_stationary,
+include/thrl.h): stationary.py for any mix of QTable, Reinforce and ActorCritic agents: the exact long-run profit of
+greedy play in the environment the reference ships, NoisyPriceState(noise_prob=0.05).
+
+Under noise the next price is no tuple's price, but its distribution depends only on the tuple just played: with
+probability 1 - p the tuple's noise-free price, with probability p uniform on [0.7 a - u(t), a - u(t)], clipped at 0.  So
+the distribution over the tuple played at a step is a Markov chain on the game's T action tuples (tuple_play.py).  Beyond
+the strategies in tuple form it needs every agent's greedy action as a function of the price on [0, a): a QTable's is
+piecewise constant with known cuts; a network's is piecewise constant with unknown cuts and is sampled at the midpoints
+of a per-config grid of cells (`resolution` uniform cuts beside the QTable agents' breakpoints).  The share of the price
+axis on which that sampling may be wrong is reported per game: n_switch, the pairs of adjacent cells between which a
+network's action changes, and unresolved, their share of the axis.  A strategy that switches twice between two adjacent
+midpoints is not seen; a higher resolution is the remedy.
+
+tables(config, resolution) derives the per-config tables in numpy; the device only reads them.  extract_cells() samples
+the strategies at the cell midpoints, run() iterates the chain and returns per game (definitions in include/thrl.h)
+iters, change, mass, stat_price, n_switch, unresolved [G], stat_reward, stat_action [N, G], optionally pi [G, T].
+summarize() gives stationary.summarize's rows per group plus n_switch_max, unresolved_mean and unresolved_max.  Sharded
+runs (th_rl_amd.launch) are refused.
+"""
+import ctypes
+import json
+import os
+
+import numpy as np
+
+from . import _lib
+from . import stationary as sn
+from . import tuple_play as tp
+from ._lib import ThrlError
+from .deviation import optimal
+
+DEFAULTS = dict(noise_prob=None, start="reset", tol=1e-12, max_iters=8192, pi=False, resolution=1024)
+STARTS = sn.STARTS
+MAX_CELLS = _lib.STAT_MAX_CELLS
+GAME_FLOAT = sn.GAME_FLOAT + ("unresolved",)
+AGENT_FLOAT = sn.AGENT_FLOAT
+PER_GAME = ("iters", "n_switch", "noise_prob", "start") + GAME_FLOAT + AGENT_FLOAT + ("pi",)
+
+
+def _check_resolution(r, what):
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) <= MAX_CELLS:
+        raise ValueError("%s must be an integer in [0, %d], got %r" % (what, MAX_CELLS, r))
+    return int(r)
+
+
+def parse_options(opt, config):
+    """training.greedy_stationary (true or a dict) -> the dict with every key filled in: noise_prob (None = the run's
+    own), start ('reset' or 'state'), tol, max_iters, pi (store the distributions), resolution (uniform cuts of the price
+    axis).  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples and more than MAX_CELLS cells."""
+    name = "training.greedy_stationary"
+    tp.check_config(config)
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict):
+        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
+    bad = set(opt) - set(DEFAULTS)
+    if bad:
+        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(DEFAULTS))))
+    out = dict(DEFAULTS)
+    out.update(opt)
+    if out["noise_prob"] is not None:
+        out["noise_prob"] = sn._check_prob(out["noise_prob"], name + ".noise_prob")
+    else:       # the run's own noise: refuse a noise-free run before training, as the batch would after it
+        env = dict(_lib.ENV_DEFAULTS, **config["environment"])
+        sweep = config.get("training", {}).get("sweep") or {}
+        if float(env["noise_prob"]) == 0.0 and "noise_prob" not in sweep:
+            raise ValueError("%s: the environment has noise_prob = 0: give the noise_prob to analyse" % name)
+    if out["start"] not in STARTS:
+        raise ValueError("%s.start must be one of %s, got %r" % (name, STARTS, out["start"]))
+    if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float)) or not out["tol"] >= 0.0:
+        raise ValueError("%s.tol must be a number >= 0, got %r" % (name, out["tol"]))
+    out["tol"] = float(out["tol"])
+    if isinstance(out["max_iters"], bool) or not isinstance(out["max_iters"], int) \
+            or not 1 <= out["max_iters"] <= _lib.STAT_MAX_ITERS:
+        raise ValueError("%s.max_iters must be an integer in [1, %d], got %r" % (name, _lib.STAT_MAX_ITERS, out["max_iters"]))
+    if not isinstance(out["pi"], bool):
+        raise ValueError("%s.pi must be true or false, got %r" % (name, out["pi"]))
+    out["resolution"] = _check_resolution(out["resolution"], name + ".resolution")
+    try:
+        cuts(config, out["resolution"])          # more than MAX_CELLS cells: refused before training
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the per-config tables
+def cuts(config, resolution):
+    """c float64 [J + 1]: the ends of the cells, cell k = [c[k], c[k + 1]): [0, a) cut at the encode breakpoints of the
+    QTable agents (the construction of stationary.cuts) and at a * m / resolution, m = 1..resolution-1 (0 = none).  Two
+    cuts so close that the midpoint between them rounds onto one of them (the same number reached by two roundings) are
+    one cut: every midpoint lies strictly inside its cell."""
+    resolution = _check_resolution(resolution, "resolution")
+    env = dict(_lib.ENV_DEFAULTS, **config["environment"])
+    a = float(env["a"])
+    parts = [np.array([0.0, a])]
+    for ag in config["agents"]:
+        if ag.get("name", "QTable") != "QTable":
+            continue
+        p = dict(_lib.QTABLE_DEFAULTS, **ag)
+        n, ms = int(p["states"]), float(p["max_state"])
+        b = (np.arange(n, dtype=np.float64) + 0.5) * ms / float(n)
+        parts.append(b[(b > 0.0) & (b < a)])
+    if resolution > 1:
+        u = a * np.arange(1, resolution, dtype=np.float64) / float(resolution)
+        parts.append(u[(u > 0.0) & (u < a)])
+    c = np.unique(np.concatenate(parts))
+    while True:
+        x = 0.5 * (c[:-1] + c[1:])
+        bad = np.flatnonzero(~((c[:-1] < x) & (x < c[1:])))
+        if not bad.size:
+            break
+        k = int(bad[0])
+        c = np.delete(c, k + 1 if k + 2 < c.size else k)
+    if c.size - 1 > MAX_CELLS:
+        raise ValueError("tuple_stationary: resolution=%d gives %d cells, at most %d" % (resolution, c.size - 1, MAX_CELLS))
+    return c
+
+
+def tables(config, resolution=DEFAULTS["resolution"]):
+    """The per-config tables of thrl_tuple_stationary (include/thrl.h) as a dict of numpy arrays: cuts [J + 1], cell_w
+    [J] (length / a), cell_x [J] (the midpoints the strategies are sampled at); tuple_play.tables' T, n_actions, kinds,
+    price [T], reward and scaled [N, T]; band_lo int32 [T], band [T, W], noise_price [T], noise_reward [N, T] by the
+    formulas of thrl_stationary's tables over these cells; n_cells, n_tuples, band_w, resolution.  More than MAX_CELLS
+    cells is a ValueError that names the resolution."""
+    t = tp.tables(config)
+    c = cuts(config, resolution)
+    J = int(c.size - 1)
+    env = dict(_lib.ENV_DEFAULTS, **config["environment"])
+    a, b = float(env["a"]), float(env["b"])
+    # u(t): the amount env_step subtracts from the intercept, from tuple_play's quantities
+    ratio = a / b
+    quantity = ratio * t["scaled"]
+    total = np.zeros(t["T"], np.float64)
+    for qn in quantity:
+        total = total + qn
+    u = b * total
+    w = (c[1:] - c[:-1]) / a
+    x = 0.5 * (c[:-1] + c[1:])
+    noise_lo = a * 0.7
+    lo, hi, width = noise_lo - u, a - u, a - noise_lo
+    length = np.maximum(0.0, np.minimum(c[None, 1:], hi[:, None]) - np.maximum(c[None, :-1], lo[:, None]))
+    z = np.maximum(0.0, -lo) - np.maximum(0.0, -hi)
+    length[:, 0] = length[:, 0] + z
+    n = length / width
+    nz = n > 0.0
+    first = np.where(nz.any(axis=1), nz.argmax(axis=1), 0)
+    last = np.where(nz.any(axis=1), J - 1 - nz[:, ::-1].argmax(axis=1), 0)
+    W = int((last - first + 1).max())
+    pad = np.concatenate([n, np.zeros((t["T"], W))], axis=1)
+    band = pad[np.arange(t["T"])[:, None], first[:, None] + np.arange(W)[None, :]]
+    nprice = np.where(lo >= 0.0, (lo + hi) / 2.0, np.where(hi <= 0.0, 0.0, hi * hi / (2.0 * width)))
+    out = dict(t)
+    out.update(cuts=c, cell_w=np.ascontiguousarray(w), cell_x=np.ascontiguousarray(x), band_lo=first.astype(np.int32),
+               band=np.ascontiguousarray(band, np.float64), noise_price=np.ascontiguousarray(nprice),
+               noise_reward=np.ascontiguousarray(nprice[None, :] * quantity), n_cells=J, n_tuples=int(t["T"]), band_w=W,
+               resolution=int(resolution))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the device calls
+def _is_policy(x, shape, dev):
+    import torch
+    return tuple(x.shape) == shape and x.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)) \
+        and x.device == dev and x.is_contiguous()
+
+
+def price_policy(batch, price, per_game=False, n_games=None):
+    """thrl_price_policy: what every agent of the first n_games (default all) games of `batch` plays at the prices
+    `price` (J numbers shared by the games, or with per_game [G, J]: each game its own), as a device int16 tensor
+    [G, N, J] holding uint16 entries.  Nothing of the batch is written."""
+    import torch
+    kinds = tp._kinds(batch)
+    if not getattr(batch, "initialized", True):
+        raise ThrlError("tuple_stationary: call init_tables() or set_tables() first")
+    G = batch.G if n_games is None else int(n_games)
+    if not 1 <= G <= batch.G:
+        raise ThrlError("tuple_stationary: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    dev = batch.device
+    with torch.cuda.device(dev):
+        if isinstance(price, torch.Tensor):
+            x = price.to(device=dev, dtype=torch.float64).contiguous()
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(price, np.float64)).to(dev)
+        if per_game:
+            x = x.reshape(x.shape[0], -1)[:G].contiguous()
+            if x.shape[0] != G:
+                raise ThrlError("tuple_stationary: per-game prices must hold %d rows" % G)
+        else:
+            x = x.reshape(-1)
+        J = int(x.shape[-1])
+        pol = torch.empty((G, batch.N, J), dtype=torch.int16, device=dev)
+        a = _lib.PricePolicyArgs()
+        a.n_games, a.n_prices, a.flags = G, J, _lib.PP_PER_GAME if per_game else 0
+        for i, k in enumerate(kinds):
+            a.kind[i] = tp.KINDS[k]
+            if k != "QTable":
+                a.nn_params[i] = batch.nn[i].params.data_ptr()
+        a.price, a.price_policy = x.data_ptr(), pol.data_ptr()
+        q = batch.q.data_ptr() if "QTable" in kinds else None
+        _lib.check(batch.L.thrl_price_policy(ctypes.byref(batch.cfg), q, ctypes.byref(a), batch._stream()),
+                   "thrl_price_policy")
+        torch.cuda.synchronize(dev)
+    return pol
+
+
+def extract_cells(batch, tabs, n_games=None):
+    """The strategies of `batch` sampled at the cell midpoints of `tabs`: device int16 [G, N, J] (thrl_price_policy)."""
+    return price_policy(batch, tabs["cell_x"], n_games=n_games)
+
+
+def state_tuples(batch, tabs, n_games=None):
+    """int32 [G] (device): the tuple every game plays at the state it holds: the strategies evaluated at batch.state
+    through thrl_price_policy's per-game mode."""
+    import torch
+    G = batch.G if n_games is None else int(n_games)
+    pol = price_policy(batch, batch.state[:G].reshape(G, 1), per_game=True, n_games=G)
+    e = (pol.reshape(G, batch.N).to(torch.int32) & 0xffff)
+    nact = torch.from_numpy(np.asarray(tabs["n_actions"], np.int32)).to(e.device)
+    stride = np.concatenate([np.cumprod(np.asarray(tabs["n_actions"], np.int64)[::-1])[::-1][1:], [1]]).astype(np.int32)
+    t = (torch.minimum(e, nact[None, :] - 1) * torch.from_numpy(stride).to(e.device)[None, :]).sum(dim=1)
+    return t.to(torch.int32).contiguous()
+
+
+def run(batch, noise_prob=None, start="reset", resolution=DEFAULTS["resolution"], tol=1e-12, max_iters=8192, pi=False,
+        tuple_policy=None, cell_policy=None, n_games=None, tabs=None):
+    """thrl_tuple_stationary for the first n_games (default all) games of `batch` (a MixedGameBatch of QTable / Reinforce
+    / ActorCritic agents, or a GameBatch).  noise_prob: stationary.resolve_noise's rules (None = the batch's per-game
+    sweep array, else the config's value; 0 asks for an explicit one).  start: "reset" (a uniform price on [0, a)),
+    "state" (the tuple played at batch.state), or int [G] start tuples (outside [0, T): that game is refused with
+    iters = -1).  tuple_policy / cell_policy: the strategies of tuple_play.extract() / extract_cells() (default:
+    extracted here).  tabs: tables(batch.config, resolution).  Returns a dict of numpy arrays."""
+    import torch
+    N = batch.N
+    G = batch.G if n_games is None else int(n_games)
+    if not 1 <= G <= batch.G:
+        raise ThrlError("tuple_stationary: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    given_start = not isinstance(start, str)
+    if not given_start and start not in STARTS:
+        raise ThrlError("tuple_stationary: start must be one of %s or an array of tuples, got %r" % (STARTS, start))
+    if tabs is None:
+        tabs = tables(batch.config, resolution)
+    tp._batch_tables(batch, tabs)
+    dev = batch.device
+    J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
+    shapes = dict(cell_w=(J,), reward=(N, T), scaled=(N, T), price=(T,), band_lo=(T,), band=(T, W), noise_reward=(N, T),
+                  noise_price=(T,))
+    sdev = batch.state.device
+    if tuple_policy is None:
+        tuple_policy = tp.extract(batch, tabs)
+    if not _is_policy(tuple_policy, (batch.G, N, T), sdev) and not _is_policy(tuple_policy, (G, N, T), sdev):
+        raise ThrlError("tuple_stationary: tuple_policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, T), dev))
+    if cell_policy is None:
+        cell_policy = extract_cells(batch, tabs, n_games=G)
+    if not _is_policy(cell_policy, (G, N, J), sdev):
+        raise ThrlError("tuple_stationary: cell_policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, J), dev))
+    a = _lib.TupleStationaryArgs()
+    a.n_games, a.n_tuples, a.n_cells, a.band_w, a.max_iters, a.tol = G, T, J, W, int(max_iters), float(tol)
+    for i, k in enumerate(tp._kinds(batch)):
+        a.kind[i] = tp.KINDS[k]
+    with torch.cuda.device(dev):
+        p, p_g = sn.resolve_noise(batch, noise_prob, G)
+        keep = {}
+        for f, shape in shapes.items():
+            x = np.ascontiguousarray(tabs[f], np.int32 if f == "band_lo" else np.float64)
+            if x.shape != shape:
+                raise ThrlError("tuple_stationary: table %s has shape %s, expected %s" % (f, x.shape, shape))
+            keep[f] = torch.from_numpy(x).to(dev)
+            setattr(a, f, keep[f].data_ptr())
+        if p_g is not None:
+            a.noise_prob_g = p_g.data_ptr()
+        else:
+            a.noise_prob = p
+        t0 = None
+        if given_start:
+            if isinstance(start, torch.Tensor):
+                t0 = start.to(device=dev, dtype=torch.int32).reshape(-1)[:G].contiguous()
+            else:
+                t0 = torch.from_numpy(np.ascontiguousarray(np.asarray(start).reshape(-1)[:G].astype(np.int32))).to(dev)
+            if t0.numel() != G:
+                raise ThrlError("tuple_stationary: start must hold %d tuples" % G)
+        elif start == "state":
+            t0 = state_tuples(batch, tabs, n_games=G)
+        if t0 is not None:
+            a.flags = _lib.TS_START_TUPLE
+            a.start = t0.data_ptr()
+        a.tuple_policy, a.cell_policy = tuple_policy.data_ptr(), cell_policy.data_ptr()
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        out = {"iters": torch.zeros((G,), dtype=torch.int32, device=dev),
+               "n_switch": torch.zeros((G,), dtype=torch.int32, device=dev)}
+        out.update({f: f64(G) for f in GAME_FLOAT})
+        out.update({f: f64(N, G) for f in AGENT_FLOAT})
+        if pi:
+            out["pi"] = f64(G, T)
+        for f, t in out.items():
+            setattr(a, f, t.data_ptr())
+        _lib.check(batch.L.thrl_tuple_stationary(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                   "thrl_tuple_stationary")
+        torch.cuda.synchronize(dev)
+        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res["noise_prob"] = np.full(G, p, np.float64) if p_g is None else p_g.cpu().numpy()
+        if t0 is not None:
+            res["start"] = t0.cpu().numpy()
+    res["n_cells"], res["T"], res["max_iters"], res["resolution"] = J, T, int(max_iters), int(tabs.get("resolution", resolution))
+    return res
+
+
+# ---------------------------------------------------------------------------------------------- host side
+def summarize(games, ids, n_groups, nash, cartel, max_iters):
+    """stationary.summarize's rows, one per group, plus n_switch_max, unresolved_mean and unresolved_max over the
+    group's games (solved or not: they describe the sampling of the strategies, not the chain)."""
+    rows = sn.summarize(games, ids, n_groups, nash, cartel, max_iters)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    ns = np.asarray(games["n_switch"], np.int64)
+    un = np.asarray(games["unresolved"], np.float64)
+    for r in rows:
+        m = ids == r["group"]
+        r["n_switch_max"] = int(ns[m].max()) if m.any() else None
+        r["unresolved_mean"] = sn._mean(un[m])
+        r["unresolved_max"] = sn._num(un[m].max()) if m.any() else None
+    return rows
+
+
+def combine(parts):
+    """Per-game arrays of disjoint sets of games (in global game order) as one run's: concatenated along the game axis
+    (axis 0 of pi [G, T], the last axis of the others)."""
+    parts = list(parts)
+    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=0 if f == "pi" else -1)
+            for f in parts[0] if f in PER_GAME}
+
+
+def describe(options, n_cells, T, nash, cartel, summary):
+    """greedy_stationary.json's content."""
+    return {"options": options, "n_cells": int(n_cells), "T": int(T), "nash": nash, "cartel": cartel,
+            "quantiles": list(sn.QUANTILES), "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)",
+            "summary": summary}
+
+
+def save_games(d, r):
+    """gstat_iters int32 [2, G] (iters, n_switch), gstat_games float64 [5, G] (change, mass, stat_price, unresolved,
+    noise_prob), gstat_reward and gstat_action float64 [N, G]; from given start tuples gstat_start int32 [G]; with the
+    distributions gstat_pi float64 [G, T]."""
+    np.save(os.path.join(d, "gstat_iters.npy"), np.stack([r["iters"], r["n_switch"]]).astype(np.int32))
+    np.save(os.path.join(d, "gstat_games.npy"),
+            np.stack([np.asarray(r[f], np.float64) for f in GAME_FLOAT + ("noise_prob",)]))
+    np.save(os.path.join(d, "gstat_reward.npy"), np.asarray(r["stat_reward"], np.float64))
+    np.save(os.path.join(d, "gstat_action.npy"), np.asarray(r["stat_action"], np.float64))
+    for f, name in (("start", "gstat_start.npy"), ("pi", "gstat_pi.npy")):
+        path = os.path.join(d, name)
+        if f in r:
+            np.save(path, np.asarray(r[f], np.int32 if f == "start" else np.float64))
+        elif os.path.isfile(path):               # a file left by an earlier run with other options
+            os.remove(path)
+
+
+def load_games(d):
+    """The per-game arrays one run directory holds (training.greedy_stationary)."""
+    it = np.load(os.path.join(d, "gstat_iters.npy"))
+    gm = np.load(os.path.join(d, "gstat_games.npy"))
+    g = {"iters": it[0], "n_switch": it[1]}
+    g.update({f: gm[k] for k, f in enumerate(GAME_FLOAT + ("noise_prob",))})
+    g.update(stat_reward=np.load(os.path.join(d, "gstat_reward.npy")), stat_action=np.load(os.path.join(d, "gstat_action.npy")))
+    for f, name in (("start", "gstat_start.npy"), ("pi", "gstat_pi.npy")):
+        if os.path.isfile(os.path.join(d, name)):
+            g[f] = np.load(os.path.join(d, name))
+    return g
+
+
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None):
+    """train_one's training.greedy_stationary outputs: the per-game gstat_*.npy files and greedy_stationary.json."""
+    tabs = tables(config, opt["resolution"])
+    r = run(batch, noise_prob=opt["noise_prob"], start=opt["start"], tol=opt["tol"], max_iters=opt["max_iters"],
+            pi=opt["pi"], tuple_policy=tuple_policy, tabs=tabs)
+    save_games(exp_path, r)
+    nash, cartel = optimal(config)
+    summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"])
+    with open(os.path.join(exp_path, "greedy_stationary.json"), "w") as f:
+        json.dump(describe(opt, r["n_cells"], r["T"], nash, cartel, summary), f, indent=2)
+    return r

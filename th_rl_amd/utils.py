@@ -618,3 +618,43 @@ def greedy_attractor_games(exp_path):
         cols["mass_other"] = g["start_mass_other"]
     n = g["n_attr"].shape[0]
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
+def greedy_stationary_summary(exp_path):
+    """A run's stationary analysis in tuple form (training.greedy_stationary: greedy play under demand noise for any mix
+    of QTable / Reinforce / ActorCritic agents): greedy_stationary.json's summary as a DataFrame with
+    stationary_summary's columns plus n_switch_max, unresolved_mean, unresolved_max (the share of the price axis on which
+    a network's sampled strategy may differ from the true one), T, n_cells, Nash and Cartel."""
+    import json
+    with open(os.path.join(exp_path, "greedy_stationary.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["T"], df["n_cells"] = int(desc["T"]), int(desc["n_cells"])
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def greedy_stationary_games(exp_path):
+    """Per-game results of training.greedy_stationary, one row per game indexed by its GLOBAL id: iters, change, mass,
+    noise_prob, price, n_switch, unresolved, reward_<i>, action_<i>, delta_noise (against the noise-free Nash / Cartel)
+    and, from the training state, start (the tuple played there)."""
+    import json
+    from th_rl_amd import stationary as sn, tuple_stationary as ts
+    if not os.path.isfile(os.path.join(exp_path, "gstat_iters.npy")):
+        raise KeyError("no stationary analysis in tuple form (gstat_iters.npy) under %s (training.greedy_stationary)" % exp_path)
+    with open(os.path.join(exp_path, "greedy_stationary.json")) as f:
+        desc = json.load(f)
+    off = 0
+    if os.path.isfile(os.path.join(exp_path, "config.json")):
+        with open(os.path.join(exp_path, "config.json")) as f:
+            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    g = ts.load_games(exp_path)
+    cols = {"iters": g["iters"], "change": g["change"], "mass": g["mass"], "noise_prob": g["noise_prob"],
+            "price": g["stat_price"], "n_switch": g["n_switch"], "unresolved": g["unresolved"]}
+    for i in range(g["stat_reward"].shape[0]):
+        cols["reward_%d" % i], cols["action_%d" % i] = g["stat_reward"][i], g["stat_action"][i]
+    cols["delta_noise"] = sn.profit_gain(g["stat_reward"], desc["nash"], desc["cartel"])
+    if "start" in g:
+        cols["start"] = g["start"]
+    n = g["iters"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
