@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # (translation unit, regular expression over the mangled kernel name, key in the output)
-KERNELS = [("thrl_wave_f32.hip", "k_wave_episodesIfLi2ELi1ELb0ELb0ELb0ELb0EE", "k_wave_episodes<float,2,1> (headline)"),
+KERNELS = [("thrl_wave_f32.hip", r"k_wave_episodesIfLi2ELi1ELb0ELb0ELb0ELb0E(Lb0E)*E", "k_wave_episodes<float,2,1> (headline)"),
            ("thrl_mixed.hip", "k_mixed_waveIfLi1ELi24ELi2ELb0ELi2EE", "k_mixed_wave<float,NR=1,24,2,table> (QTable vs Reinforce)"),
            ("thrl_mixed.hip", "k_mixed_waveIfLi2ELi24ELi2ELb0ELi1EE", "k_mixed_wave<float,NR=2,24,2,memo> (2 x Reinforce)"),
            ("thrl_nn.hip", "k_nn_reinforce_trainILi24ELb0EE", "k_nn_reinforce_train<24,false>"),

@@ -191,6 +191,45 @@ __device__ __forceinline__ double wave_sum4(double q0, double q1, double q2, dou
     return v;
 }
 
+// DPP source operand without an old value (bound_ctrl, full masks): hipcc folds it into the instruction that consumes
+// it (v_xor_b32_dpp, v_or_b32_dpp) instead of emitting a copy and a v_mov_b32_dpp in front of it.  Only for controls
+// under which every lane has a source lane (quad_perm).
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_src(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
+}
+
+__device__ __forceinline__ float max3_f32(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// Index of the FIRST maximum of a 21-column float32 row at LDS byte address `row`: what
+//     b = v[0]; i = 0; for (j = 1; j < 21; j++) if (v[j] > b) { b = v[j]; i = j; }
+// returns, in 30 vector instructions instead of 60.  The row maximum m comes from ten v_max3_f32 over seven groups
+// of three columns; a descending scan with inline-constant group numbers finds the first group whose maximum equals m,
+// that group's first two columns are read again and two more compares place m inside it.
+// Same result as the loop for every value arithmetic can produce: v_cmp_eq_f32 and `>` agree on +-0 (neither is
+// greater, both are equal), v_max3_f32 skips a quiet NaN exactly as `>` does in columns 1-20, and a NaN in column 0
+// (nothing is greater than it: the loop answers 0) is tested for at the end.  (A SIGNALLING NaN, which no arithmetic
+// produces, would make v_max3_f32 return NaN under the kernel's IEEE mode.)
+__device__ __forceinline__ uint32_t argmax21_first(unsigned row) {
+    float g[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++)
+        g[k] = max3_f32(lds_load<float>(row + 12u * k), lds_load<float>(row + 12u * k + 4u), lds_load<float>(row + 12u * k + 8u));
+    const float m = max3_f32(max3_f32(g[0], g[1], g[2]), max3_f32(g[3], g[4], g[5]), g[6]);
+    uint32_t c3 = 18u;                                       // first column of the first group that holds m
+#pragma unroll
+    for (int k = 5; k >= 0; k--) c3 = (g[k] == m) ? (uint32_t)(3 * k) : c3;
+    const unsigned ad = row + 4u * c3;
+    const float va = lds_load<float>(ad), vb = lds_load<float>(ad + 4u);
+    uint32_t pos = (vb == m) ? 1u : 2u;
+    pos = (va == m) ? 0u : pos;
+    const float v0 = lds_load<float>(row);
+    return (v0 != v0) ? 0u : c3 + pos;
+}
+
 __device__ __forceinline__ uint32_t readlane_u(uint32_t v, int lane) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
 }
@@ -581,6 +620,11 @@ k_wave_episodes(const WaveArgs a) {
     // 256 bytes behind the wave's tables (float32, noise-free configurations: thrl_api.hip plan_wave): per-step words of a segment
     constexpr bool kLdsMK = sizeof(QT) == 4 && !NOISE && !GREEDY && NRSEG == 1 && !(kAblate & 6);
     const unsigned mk_addr = tab0_off + 2u * (unsigned)((W + 2) * A) * (unsigned)sizeof(QT);
+    // float32 tables with 21 actions: per-row greedy actions by row maximum + scan (argmax21_first)
+    constexpr bool kArgmax21 = sizeof(QT) == 4;
+    // variants without the NOISE / GREEDY additions to the fixed-point flag: replay schedule from three hazard ballots and
+    // scalar mask arithmetic (phase (d2))
+    constexpr bool kMaskSched = !NOISE && !GREEDY;
 
     const AgentParams& p0 = a.ag[0];
     const AgentParams& p1 = a.ag[1];
@@ -688,6 +732,9 @@ k_wave_episodes(const WaveArgs a) {
                 QT b0 = r0[0], b1 = r1[0];
                 uint32_t i0 = 0, i1 = 0;
                 if (kAblate & 16) {
+                } else if (kArgmax21 && A == 21) {
+                    i0 = argmax21_first(tab0_off + (unsigned)row * 84u);
+                    i1 = argmax21_first(tab1_off + (unsigned)row * 84u);
                 } else if (A == 21) {
                     // the reference's example configs: constant trip count, so the column numbers are inline
                     // constants of the selects (no index register, no loop control): 7 instructions per column pair
@@ -1045,8 +1092,37 @@ k_wave_episodes(const WaveArgs a) {
                 //      Transition j may share a pass with an earlier transition i of its group unless it
                 //      reads the row i writes (live next_max, agents.py:71) or rewrites i's cell (:75).
                 uint32_t P;
-                if (kAblate & 128) P = (act[seg] >> 24) * 0x204081u;
-                else {
+                bool any_fixed;
+                if (kAblate & 128) { P = (act[seg] >> 24) * 0x204081u; any_fixed = false; }
+                else if constexpr (kMaskSched) {
+                    // x_i = my word ^ the word of position i of my quad (DPP folded into the xor): every test below is a
+                    // byte-field zero test of x_i.  With d = my next row ^ my row, "my next row == its row" is
+                    // byte 2 of x_i == d.  H_i = lanes with a hazard against position i (read by positions > i only).
+                    const uint32_t w = act[seg];
+                    const uint32_t d = (w >> 24) ^ ((w >> 16) & 0xFFu);
+                    uint32_t x0 = w ^ dpp_src<0x00>(w), x1 = w ^ dpp_src<0x55>(w), x2 = w ^ dpp_src<0xAA>(w);
+                    asm("" : "+v"(x0), "+v"(x1), "+v"(x2));       // (the fields are taken from x_i, not recomputed from the DPP value)
+                    auto hz = [&](uint32_t x) -> unsigned long long {
+                        const uint32_t xr = (x >> 16) & 0xFFu;
+                        // same row, and a0 or a1 the same | next row == its row: one compare per ballot, ored as masks
+                        return __ballot((((x & 0xFFu) * ((x >> 8) & 0xFFu)) | xr) == 0u) | __ballot(xr == d);
+                    };
+                    const unsigned long long H0 = hz(x0), H1 = hz(x1), H2 = hz(x2);
+                    // cut bits of all 16 groups at once, as scalar arithmetic on the masks (bit 4g = group g)
+                    const unsigned long long M = 0x1111111111111111ull;
+                    const unsigned long long C1 = (H0 >> 1) & M;
+                    const unsigned long long C2 = ((H1 >> 2) | ((H0 >> 2) & ~C1)) & M;
+                    const unsigned long long C3 = ((H2 >> 3) | (((H1 >> 3) | ((H0 >> 3) & ~C1)) & ~C2)) & M;
+                    // four identical transitions that stay in their row: position 3 equals positions 0-2, position 0 stays
+                    const unsigned long long F = (__ballot((x0 | x1 | x2) == 0u) >> 3) & __ballot(d == 0u) & M;
+                    const unsigned long long sched = C1 | (C2 << 1) | (C3 << 2) | (F << 3);
+                    any_fixed = F != 0ull;
+                    // the four next rows, 7 bits each: every lane shifts its own into place, two DPP ors collect the quad's
+                    uint32_t rows = (w >> 24) << (7u * ((uint32_t)lane & 3u));
+                    rows |= dpp_src<0xB1>(rows);                                   // quad_perm [1,0,3,2]
+                    rows |= dpp_src<0x4E>(rows);                                   // quad_perm [2,3,0,1]
+                    P = ((uint32_t)(sched >> lane) << 28) | rows;                  // (read from lanes 4g only)
+                } else {
                     const uint32_t w = act[seg];
                     const uint32_t b0 = dpp_mov32<0x00>(w), b1 = dpp_mov32<0x55>(w), b2 = dpp_mov32<0xAA>(w),
                                    b3 = dpp_mov32<0xFF>(w);                       // quad broadcasts of positions 0..3
@@ -1074,6 +1150,7 @@ k_wave_episodes(const WaveArgs a) {
                                              (b1 >> 24) == ((b0 >> 16) & 0xFFu) && (b0 >> 24) != (b1 >> 24))) ? 1u : 0u;
                     P = (b0 >> 24) | ((b1 >> 24) << 7) | ((b2 >> 24) << 14) | ((b3 >> 24) << 21) |
                         ((c1 | (c2 << 1) | (c3 << 2)) << 28) | (same4 << 31);
+                    any_fixed = __ballot((P >> 31) != 0u) != 0ull;
                 }
 
                 // ---- (e) replay (agents.py:68-76): live next_max, writes in transition order
@@ -1120,7 +1197,6 @@ k_wave_episodes(const WaveArgs a) {
                         }
                     }
                 }
-                const bool any_fixed = __ballot((P >> 31) != 0u) != 0ull;
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
                     if (GREEDY && seg_done) break;
