@@ -1338,6 +1338,141 @@ typedef struct {
 } thrl_tuple_stationary_args;
 int thrl_tuple_stationary(const thrl_cfg* cfg, const thrl_tuple_stationary_args* args, void* stream);
 
+/*
+ * thrl_price_probs: the action PROBABILITIES of the neural agents at a free list of prices, where thrl_price_policy
+ * gives their greedy action.  No reference counterpart.  For every agent i with kind[i] = 1 / 2 (Reinforce /
+ * ActorCritic) the call writes prob[i] (device float32 [G][J][A_i], G = args.n_games in [1, cfg.n_games], J =
+ * args.n_prices in [1, THRL_STAT_MAX_CELLS]): row [g][k] is bit for bit the vector thrl_nn_act / thrl_ac_act return in
+ * prob_out for game g at the price (float)x[k] -- the softmax training samples from (agents.py:148-163), evaluated by
+ * the same device function with the same padding, a game's network held in a wave's registers while the wave goes
+ * through the J prices.  price (device float64 [J]) is shared by the games.  QTable agents (kind 0) are skipped: their
+ * prob[i] and nn_params[i] are not read; their greedy entry at the same prices is thrl_price_policy's.  Of a valid cfg
+ * only n_games, n_agents and n_actions are used; everything but prob[i] is read only.
+ *
+ * Returns THRL_ERR_UNSUPPORTED for a CAC agent (kind 3) or n_prices > THRL_STAT_MAX_CELLS; THRL_ERR_BAD_CONFIG for
+ * n_games outside [1, cfg.n_games], flags != 0, reserved != 0, a kind outside [0, 3], a neural agent with actions
+ * outside [2, 32] or n_prices < 1; THRL_ERR_NULL for a missing cfg, args, price, or nn_params[i] / prob[i] of a neural
+ * agent.
+ */
+typedef struct {
+    int32_t n_games;                     /* G in [1, cfg.n_games]                            */
+    int32_t n_prices;                    /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t flags;                       /* 0                                                */
+    int32_t reserved;                    /* 0                                                */
+    int32_t kind[THRL_MAXA];             /* 0 = QTable (skipped), 1 = Reinforce, 2 = ActorCritic (3 = CAC is refused) */
+    const float* nn_params[THRL_MAXA];   /* device [G][P] for the neural agents              */
+    const double* price;                 /* device [J]                                       */
+    float* prob[THRL_MAXA];              /* device [G][J][A_i] for the neural agents, out    */
+} thrl_price_probs_args;
+int thrl_price_probs(const thrl_cfg* cfg, const thrl_price_probs_args* args, void* stream);
+
+/*
+ * thrl_sampled_chain: SAMPLED play, the exact long-run profit of the stochastic policies the agents were trained
+ * with, where every other analysis call treats an agent as its greedy policy.  No reference counterpart (the closest is
+ * play_game with the commented-out sample_action, utils.py:36-39).  Without demand noise the price after a step is a
+ * function of the action tuple just played, so under sampling the tuple played at a step is a Markov chain on the
+ * game's T tuples with P(t -> t') = prod_i pi_i(a_i(t') | price(t)), and this call iterates it.  The transition row
+ * depends on t only through price(t), so everything is indexed by the D <= T DISTINCT prices of the config; the row is
+ * a product over agents, so a step costs T D N multiplications and needs D sum_i A_i probabilities, never a T x T
+ * matrix.  Of a valid cfg only n_agents and n_actions are used; nothing of a batch is read or written, every input is
+ * read only.  G = args.n_games >= 1, T = args.n_tuples = prod_i n_actions_i <= THRL_TP_MAX_TUPLES, D = args.n_prices in
+ * [1, T].  a_i(t) = (t / tstride_i) mod A_i with tstride_i = prod_{j > i} n_actions_j (agent 0 slowest).  All
+ * arithmetic is float64, every operation is rounded once (no contraction), in the order written here.
+ *
+ * Per-config tables, computed by the caller (th_rl_amd.sampled_play.tables) and only read here; no device arithmetic
+ * produces any of them.  dprice [D]: the distinct values of tuple_play's price [T], ascending (two prices are equal
+ * when their float64 bits are equal); it is what the caller hands to thrl_price_probs and thrl_price_policy and is not
+ * an argument here.  row(t) = the index of price(t) in dprice, given as its stable grouping: grp_first (device int32
+ * [D + 1]) and grp_perm (device int32 [T]): the tuples with row(t) = d are grp_perm[grp_first[d] .. grp_first[d + 1])
+ * in ascending t.  The device clamps grp_first to [0, T] and grp_perm to [0, T) when it stages them, so no entry leads
+ * out of bounds.  reward, scaled (device double [N][T]) and price (device double [T]) are tuple_play's arrays.
+ *
+ * Inputs per game.  prob[i] for the neural agents (kind[i] = 1 / 2): device float32 [G][D][A_i], thrl_price_probs at
+ * dprice.  dpolicy (device uint16 [G][N][D]), thrl_price_policy at dprice: read for the QTable agents and for `agree`;
+ * entries are clamped to A_i - 1: g_i(d) = min(dpolicy[g][i][d], A_i - 1).  eps[i] scalars, or eps_g (device double
+ * [N][G]) which then replaces them: the exploration rate of the QTable agents (the entries of neural agents are not
+ * read).  A scalar outside [0, 1] (NaN included) for a QTable agent is THRL_ERR_BAD_CONFIG; such an entry of eps_g is
+ * device data and refuses that game only: iters = -1 and zeros, no other game is affected.
+ *
+ * Probabilities.
+ *   neural agent:  P_i(k|d) = (double)prob[i][g][d][k];  S_i(d) = sum_k P_i(k|d), ascending k from 0.0
+ *   QTable agent (agents.py:80-89, random.choice over ALL actions):  lo = eps / A_i;
+ *                  P_i(k|d) = (1 - eps) + lo for k = g_i(d), else lo;  S_i(d) = 1.0 exactly
+ *   Z(d) = S_0(d) * S_1(d) * ...   multiplied left to right
+ * The float32 softmax rows do not sum to one; the division by Z keeps the chain's mass from drifting over thousands of
+ * steps.
+ *
+ * Start.  m_0 = 1 / T on every tuple, or with THRL_SP_START_TUPLE the unit mass on start[g] (device int32 [G]); a
+ * value outside [0, T) refuses that game: iters = -1 and zeros.
+ *
+ * One step from m, in thrl_stationary's lazy form (with eps = 0 tables the chain is a deterministic map and may be
+ * periodic):
+ *   M(d)   = sum over the t with row(t) = d of m(t)          ascending t from 0.0
+ *   W(d)   = M(d) / Z(d)
+ *   s(t')  = sum_d ((W(d) * P_0(a_0(t')|d)) * P_1(a_1(t')|d)) * ...      ascending d from 0.0; a d with W(d) == 0.0 is
+ *            skipped (M(d) == 0: its terms are +0.0)
+ *   m'(t') = 0.5 * m(t') + 0.5 * s(t')
+ *   chg    = max_t |m'(t) - m(t)|
+ * Stop after the first step with chg <= args.tol, or after args.max_iters steps.
+ *
+ * Outputs, per game, from the last iterate m (M and W recomputed from it); every sum in ascending index from 0.0:
+ *   iters, change        the steps taken and the last chg
+ *   mass                 sum_t m(t)
+ *   samp_reward[i][g]    sum_t m(t) * reward_i(t)
+ *   samp_action[i][g]    sum_t m(t) * scaled_i(t)
+ *   samp_price[g]        sum_t m(t) * price(t)
+ *   agree[g]             sum_d ((W(d) * P_0(g_0(d)|d)) * P_1(g_1(d)|d)) * ...   every d, none skipped: the long-run share
+ *                        of steps on which every agent plays its greedy action
+ *   pi (optional, double [G][T])   m itself
+ *
+ * Working set.  A game is solved by one 256-thread block in LDS: the two iterates (16 T bytes), W and Z (16 D), the
+ * float32 probability rows of the neural agents (4 D A_i each, row-major [d][k], so lanes with consecutive a_{N-1} read
+ * consecutive words), 2 bytes per (QTable agent, d), the grouping (2 (D + 1) + 2 T), 512 (2 N + 2) bytes of staging
+ * for the ordered output sums and 256 bytes of per-game constants, each array rounded up to 16 bytes:
+ *   sum of r16(x) over x in { 8 T, 8 T, 8 D, 8 D, 4 D A_i (neural i), 2 D (QTable i), 2 (D + 1), 2 T, 512 (2 N + 2), 256 }
+ * The call returns THRL_ERR_UNSUPPORTED, without launching, when that exceeds THRL_SP_MAX_LDS = 160 KB (a CU's LDS on
+ * gfx950) or the device's own limit.  QTable 21 x Reinforce 21 (T = D = 441) takes 57,216 bytes, 2 x Reinforce 21 on
+ * one exact grid (T = 441, D = 41) 18,976; against a 32-action network a QTable of 30 actions (T = D = 960, 162,704
+ * bytes) fits and one of 32 (T = D = 1024) does not.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games < 1, an unknown flag, reserved != 0, n_tuples < 1 or n_tuples != prod_i
+ * n_actions_i, n_prices outside [1, n_tuples], max_iters outside [1, THRL_STAT_MAX_ITERS], tol < 0 or NaN, eps as
+ * above, or a kind outside [0, 3]; THRL_ERR_UNSUPPORTED for a CAC agent (kind 3), n_tuples > THRL_TP_MAX_TUPLES or the
+ * working set; THRL_ERR_NULL for a missing cfg, args, prob[i] of a neural agent, dpolicy, table (grp_first, grp_perm,
+ * reward, scaled, price), per-game output other than pi, or start with THRL_SP_START_TUPLE.
+ */
+#define THRL_SP_START_TUPLE 1
+#define THRL_SP_MAX_LDS (160 * 1024)
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of prob and dpolicy                */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t n_prices;                /* D in [1, T]: the distinct prices                 */
+    int32_t max_iters;               /* in [1, THRL_STAT_MAX_ITERS]                      */
+    int32_t flags;                   /* THRL_SP_START_TUPLE                              */
+    int32_t reserved;                /* 0                                                */
+    int32_t kind[THRL_MAXA];         /* 0 = QTable, 1 = Reinforce, 2 = ActorCritic (3 = CAC is refused) */
+    double  eps[THRL_MAXA];          /* QTable agents' epsilon in [0, 1], read when eps_g is NULL */
+    double  tol;                     /* >= 0                                             */
+    const double* eps_g;             /* device [N][G] or NULL                            */
+    const int32_t* start;            /* device [G], with THRL_SP_START_TUPLE             */
+    const float* prob[THRL_MAXA];    /* device [G][D][A_i] for the neural agents         */
+    const uint16_t* dpolicy;         /* device [G][N][D]                                 */
+    const int32_t* grp_first;        /* device [D + 1]                                   */
+    const int32_t* grp_perm;         /* device [T]                                       */
+    const double* reward;            /* device [N][T]                                    */
+    const double* scaled;            /* device [N][T]                                    */
+    const double* price;             /* device [T]                                       */
+    int32_t* iters;                  /* device [G]                                       */
+    double*  change;                 /* device [G]                                       */
+    double*  mass;                   /* device [G]                                       */
+    double*  samp_reward;            /* device [N][G]                                    */
+    double*  samp_action;            /* device [N][G]                                    */
+    double*  samp_price;             /* device [G]                                       */
+    double*  agree;                  /* device [G]                                       */
+    double*  pi;                     /* device [G][T] or NULL                            */
+} thrl_sampled_chain_args;
+int thrl_sampled_chain(const thrl_cfg* cfg, const thrl_sampled_chain_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@
 #include "thrl_tuple_analysis.h"
 #include "thrl_tuple_attractors.h"
 #include "thrl_tuple_play.h"
+#include "thrl_sampled.h"
 #include "thrl_tuple_stationary.h"
 #include "thrl_wave_lut.h"
 
@@ -1953,6 +1954,98 @@ int thrl_tuple_stationary(const thrl_cfg* c, const thrl_tuple_stationary_args* x
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_tuple_stationary(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_ts_switch / k_ts_chain launch") : THRL_OK;
+}
+
+int thrl_price_probs(const thrl_cfg* c, const thrl_price_probs_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    if (x->n_games < 1 || x->n_games > c->n_games)
+        return fail(THRL_ERR_BAD_CONFIG, "n_games=%d out of [1,%d]", x->n_games, c->n_games);
+    if (x->flags != 0) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if (x->n_prices < 1) return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d must be >= 1", x->n_prices);
+    if (x->n_prices > THRL_STAT_MAX_CELLS)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_price_probs: n_prices=%d, at most %d", x->n_prices, THRL_STAT_MAX_CELLS);
+    if (!x->price) return fail(THRL_ERR_NULL, "price is NULL");
+    for (int i = 0; i < c->n_agents; i++)
+        if (x->kind[i] != 0 && (!x->nn_params[i] || !x->prob[i]))
+            return fail(THRL_ERR_NULL, "nn_params[%d] / prob[%d] is NULL", i, i);
+    for (int i = 0; i < c->n_agents; i++) {
+        if (x->kind[i] == 0) continue;
+        const int A = c->n_actions[i];
+        const int P = x->kind[i] == 2 ? (int)thrl_ac_param_count(A) : (int)thrl_nn_param_count(A);
+        const int e = thrl::launch_tp_probs(x->n_games, A, x->n_prices, x->nn_params[i], P, x->price, x->prob[i],
+                                            (hipStream_t)stream);
+        if (e) return hip_fail(e, "k_tp_probs launch");
+    }
+    return THRL_OK;
+}
+
+int thrl_sampled_chain(const thrl_cfg* c, const thrl_sampled_chain_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // every host-visible argument is checked before the device is touched
+    if (x->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", x->n_games);
+    if (x->flags & ~THRL_SP_START_TUPLE) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (x->n_prices < 1 || x->n_prices > x->n_tuples)
+        return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", x->n_prices, x->n_tuples);
+    if (x->max_iters < 1 || x->max_iters > THRL_STAT_MAX_ITERS)
+        return fail(THRL_ERR_BAD_CONFIG, "max_iters=%d out of [1,%d]", x->max_iters, THRL_STAT_MAX_ITERS);
+    if (!(x->tol >= 0.0)) return fail(THRL_ERR_BAD_CONFIG, "tol=%g must be >= 0", x->tol);
+    if (!x->eps_g)
+        for (int i = 0; i < N; i++)
+            if (x->kind[i] == 0 && !(x->eps[i] >= 0.0 && x->eps[i] <= 1.0))
+                return fail(THRL_ERR_BAD_CONFIG, "eps[%d]=%g out of [0, 1]", i, x->eps[i]);
+    SpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples; a.D = x->n_prices;
+    a.max_iters = x->max_iters; a.start_tuple = (x->flags & THRL_SP_START_TUPLE) != 0;
+    a.tol = x->tol;
+    int ts = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        a.kind[i] = x->kind[i];
+        a.n_actions[i] = c->n_actions[i];
+        a.tstride[i] = ts;
+        ts *= c->n_actions[i];
+        a.eps[i] = x->eps[i];
+        a.prob[i] = x->prob[i];
+    }
+    thrl::sp_layout(a);                              // the working set of include/thrl.h
+    if (a.lds_bytes > THRL_SP_MAX_LDS)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_chain: %d bytes of LDS per game (T=%d, n_prices=%d), at most %d",
+                    a.lds_bytes, a.T, a.D, THRL_SP_MAX_LDS);
+    for (int i = 0; i < N; i++)
+        if (x->kind[i] != 0 && !x->prob[i]) return fail(THRL_ERR_NULL, "prob[%d] is NULL", i);
+    if (!x->dpolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->scaled || !x->price)
+        return fail(THRL_ERR_NULL, "dpolicy / grp_first / grp_perm / reward / scaled / price is NULL");
+    if (!x->iters || !x->change || !x->mass || !x->samp_reward || !x->samp_action || !x->samp_price || !x->agree)
+        return fail(THRL_ERR_NULL, "iters / change / mass / samp_reward / samp_action / samp_price / agree is NULL");
+    if (a.start_tuple && !x->start) return fail(THRL_ERR_NULL, "start is NULL with THRL_SP_START_TUPLE");
+    a.eps_g = x->eps_g; a.start = x->start; a.dpolicy = x->dpolicy; a.grp_first = x->grp_first; a.grp_perm = x->grp_perm;
+    a.reward = x->reward; a.scaled = x->scaled; a.price = x->price;
+    a.iters = x->iters; a.change = x->change; a.mass = x->mass; a.samp_reward = x->samp_reward;
+    a.samp_action = x->samp_action; a.samp_price = x->samp_price; a.agree = x->agree; a.pi = x->pi;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    if (lds_cu > 0 && a.lds_bytes > lds_cu)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_chain: %d bytes of LDS per game (T=%d, n_prices=%d), the device has %d",
+                    a.lds_bytes, a.T, a.D, lds_cu);
+    int per_cu = kSpMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / a.lds_bytes < per_cu) per_cu = lds_cu / a.lds_bytes > 0 ? lds_cu / a.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < a.G ? want : a.G);
+    const int e = thrl::launch_sampled_chain(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_sp_chain launch") : THRL_OK;
 }
 
 }  // extern "C"

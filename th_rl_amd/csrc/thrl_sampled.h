@@ -1,0 +1,69 @@
+// thrl_sampled.h -- launch arguments of sampled play (thrl_sampled_chain, include/thrl.h).  thrl_api.hip validates and
+// lays out LDS; thrl_sampled.hip holds the kernel.
+#pragma once
+#ifndef THRL_SP_HOST_BUILD
+#include <hip/hip_runtime.h>
+#endif
+#include <stdint.h>
+
+#ifndef THRL_SP_HOST_BUILD
+#include "thrl_device.h"
+#endif
+
+namespace thrl {
+
+constexpr int kSpBlock = 256;                  // threads of a game's block
+constexpr int kSpMaxBlocksPerCu = 8;
+constexpr int kSpMaxA = 8;                     // THRL_MAXA
+
+struct SpArgs {
+    int32_t G, N, T, D;
+    int32_t max_iters;
+    int32_t start_tuple;                       // m_0 = the unit mass on start[g] (else 1 / T everywhere)
+    int32_t lds_bytes;
+    // byte offsets into the block's LDS (each array starts on a multiple of 16)
+    int32_t o_ma, o_mb, o_w, o_z, o_first, o_perm, o_prod, o_cst;
+    int32_t o_row[kSpMaxA];                    // agent i's rows: float [D][A_i] (network) or uint16 [D] (QTable)
+    int32_t kind[kSpMaxA];                     // 0 = QTable, 1 / 2 = network
+    int32_t n_actions[kSpMaxA];
+    int32_t tstride[kSpMaxA];                  // prod_{j > i} n_actions[j]: agent 0 slowest
+    double eps[kSpMaxA];
+    double tol;
+    const double* eps_g;                       // [N][G] or NULL
+    const int32_t* start;                      // [G] (start_tuple)
+    const float* prob[kSpMaxA];                // [G][D][A_i] (networks)
+    const uint16_t* dpolicy;                   // [G][N][D]
+    const int32_t* grp_first;                  // [D + 1]
+    const int32_t* grp_perm;                   // [T]
+    const double* reward;                      // [N][T]
+    const double* scaled;                      // [N][T]
+    const double* price;                       // [T]
+    int32_t* iters;
+    double *change, *mass, *samp_reward, *samp_action, *samp_price, *agree, *pi;
+};
+
+// the LDS layout of include/thrl.h's working set; returns the bytes of a block
+inline int32_t sp_layout(SpArgs& a) {
+    auto r16 = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
+    int64_t off = 0;
+    a.o_ma = (int32_t)off; off += r16(8 * (int64_t)a.T);
+    a.o_mb = (int32_t)off; off += r16(8 * (int64_t)a.T);
+    a.o_w = (int32_t)off; off += r16(8 * (int64_t)a.D);
+    a.o_z = (int32_t)off; off += r16(8 * (int64_t)a.D);
+    for (int i = 0; i < a.N; i++) {
+        a.o_row[i] = (int32_t)off;
+        off += r16(a.kind[i] == 0 ? 2 * (int64_t)a.D : 4 * (int64_t)a.D * a.n_actions[i]);
+    }
+    a.o_first = (int32_t)off; off += r16(2 * ((int64_t)a.D + 1));
+    a.o_perm = (int32_t)off; off += r16(2 * (int64_t)a.T);
+    a.o_prod = (int32_t)off; off += r16(512 * (2 * (int64_t)a.N + 2));
+    a.o_cst = (int32_t)off; off += 256;
+    a.lds_bytes = (int32_t)off;
+    return a.lds_bytes;
+}
+
+#ifndef THRL_SP_HOST_BUILD
+int launch_sampled_chain(const SpArgs& a, int grid, hipStream_t s);
+#endif
+
+}  // namespace thrl

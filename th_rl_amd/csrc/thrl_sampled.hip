@@ -1,0 +1,264 @@
+// thrl_sampled.hip -- sampled play on the game's action tuples (thrl_sampled_chain, include/thrl.h): the long-run
+// distribution over the tuple played when every agent SAMPLES its action (a network from its softmax, a QTable agent
+// epsilon-greedily), by lazy power iteration of the chain P(t -> t') = prod_i pi_i(a_i(t') | price(t)).  One kernel.
+//
+// k_sp_chain: a 256-thread block per game, looping over games.  The transition row depends on t only through its price,
+//   so the block keeps per DISTINCT price d: the mass M(d) on the tuples with that price, divided by the normaliser
+//   Z(d) into W(d); the float32 probability rows of the networks, row-major [d][k]; and for a QTable agent its greedy
+//   action at d (2 bytes) beside two per-game constants.  The grouping of the tuples by price is per config: it is staged
+//   once per block, clamped, so M(d) is a segmented sum in ascending t by one thread per d.  A thread owns output tuples
+//   t' and walks d ascending: W(d) is a broadcast (and the skip of an empty d is block-uniform), the rows of the last
+//   agent are read at consecutive words by consecutive lanes, those of the slower agents by runs of lanes at one word.
+//   The ordered sum over d forbids a split over d and any matrix instruction; the parallelism is across t'.  The largest
+//   change is a maximum, whose order is free: it goes through LDS in two levels, no shuffle.  The ordered output sums
+//   follow k_ts_chain: chunks of 64 tuples, one lane per tuple for the products, then one lane per output reading them
+//   back in ascending t; `agree` is one more lane over the D terms parked in the dead iterate.
+//   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
+#include "thrl_sampled.h"
+
+namespace thrl {
+
+namespace {
+
+struct SpCst {                                   // per game, per QTable agent: eps / A and (1 - eps) + eps / A
+    double lo[kSpMaxA], hi[kSpMaxA];
+    double red[16];                              // the second level of the maximum
+};
+
+// M(d) over the tuples of price d in ascending t, W(d) = M(d) / Z(d)
+__device__ __forceinline__ void sp_weights(const SpArgs& a, const double* m, const uint16_t* first, const uint16_t* perm,
+                                           const double* Z, double* W, int tid) {
+    for (int d = tid; d < a.D; d += kSpBlock) {
+        double M = 0.0;
+        const int e = first[d + 1];
+        for (int s = first[d]; s < e; s++) M = __dadd_rn(M, m[perm[s]]);
+        W[d] = __ddiv_rn(M, Z[d]);
+    }
+}
+
+template <int MAXN>
+__device__ __forceinline__ void sp_block(const SpArgs& a, unsigned char* s_mem, int tid, int bid, int nblk) {
+    const int N = a.N, G = a.G, T = a.T, D = a.D;
+    double* ma = reinterpret_cast<double*>(s_mem + a.o_ma);
+    double* mb = reinterpret_cast<double*>(s_mem + a.o_mb);
+    double* W = reinterpret_cast<double*>(s_mem + a.o_w);
+    double* Z = reinterpret_cast<double*>(s_mem + a.o_z);
+    uint16_t* first = reinterpret_cast<uint16_t*>(s_mem + a.o_first);
+    uint16_t* perm = reinterpret_cast<uint16_t*>(s_mem + a.o_perm);
+    double* prod = reinterpret_cast<double*>(s_mem + a.o_prod);       // [2N + 2][64] >= 256 words: also the threads' maxima
+    SpCst* cst = reinterpret_cast<SpCst*>(s_mem + a.o_cst);
+    const int n_out = 2 * N + 2;                                      // mass, N rewards, N actions, price
+
+    // ---- the grouping of the tuples by price: per config, staged once; no entry leads out of bounds
+    for (int d = tid; d <= D; d += kSpBlock) first[d] = (uint16_t)min(max(a.grp_first[d], 0), T);
+    for (int t = tid; t < T; t += kSpBlock) perm[t] = (uint16_t)min(max(a.grp_perm[t], 0), T - 1);
+
+    for (int64_t g = bid; g < G; g += nblk) {
+        bool ok = true;
+        for (int i = 0; i < N; i++)
+            if (a.kind[i] == 0) {
+                const double e = a.eps_g ? a.eps_g[(int64_t)i * G + g] : a.eps[i];
+                ok = ok && e >= 0.0 && e <= 1.0;
+            }
+        int t_start = -1;
+        if (a.start_tuple) {
+            t_start = a.start[g];
+            ok = ok && t_start >= 0 && t_start < T;
+        }
+        if (!ok) {                                       // block-uniform: this game is not solved
+            if (tid == 0) {
+                a.iters[g] = -1;
+                a.change[g] = 0.0;
+                a.mass[g] = 0.0;
+                a.samp_price[g] = 0.0;
+                a.agree[g] = 0.0;
+            }
+            if (tid < N) {
+                a.samp_reward[(int64_t)tid * G + g] = 0.0;
+                a.samp_action[(int64_t)tid * G + g] = 0.0;
+            }
+            if (a.pi)
+                for (int t = tid; t < T; t += kSpBlock) a.pi[g * T + t] = 0.0;
+            continue;
+        }
+        __syncthreads();                                 // the game before is read to its end; the grouping is staged
+
+        // ---- the game's rows and constants
+        if (tid < N) {
+            double lo = 0.0, hi = 0.0;
+            if (a.kind[tid] == 0) {
+                const double e = a.eps_g ? a.eps_g[(int64_t)tid * G + g] : a.eps[tid];
+                lo = __ddiv_rn(e, (double)a.n_actions[tid]);
+                hi = __dadd_rn(__dsub_rn(1.0, e), lo);
+            }
+            cst->lo[tid] = lo;
+            cst->hi[tid] = hi;
+        }
+        for (int i = 0; i < N; i++) {
+            const int A = a.n_actions[i];
+            if (a.kind[i] == 0) {
+                uint16_t* rq = reinterpret_cast<uint16_t*>(s_mem + a.o_row[i]);
+                const uint16_t* __restrict__ src = a.dpolicy + (g * N + i) * D;
+                for (int d = tid; d < D; d += kSpBlock) rq[d] = (uint16_t)min((int)src[d], A - 1);
+            } else {
+                float* rf = reinterpret_cast<float*>(s_mem + a.o_row[i]);
+                const int n = D * A;
+                const float* __restrict__ src = a.prob[i] + g * n;
+                for (int j = tid; j < n; j += kSpBlock) rf[j] = src[j];
+            }
+        }
+        __syncthreads();
+        for (int d = tid; d < D; d += kSpBlock) {
+            double z = 1.0;
+            for (int i = 0; i < N; i++) {
+                double S = 1.0;
+                if (a.kind[i] != 0) {
+                    const int A = a.n_actions[i];
+                    const float* rf = reinterpret_cast<const float*>(s_mem + a.o_row[i]) + d * A;
+                    S = 0.0;
+                    for (int k = 0; k < A; k++) S = __dadd_rn(S, (double)rf[k]);
+                }
+                z = i == 0 ? S : __dmul_rn(z, S);
+            }
+            Z[d] = z;
+        }
+        const double unif = __ddiv_rn(1.0, (double)T);
+        for (int t = tid; t < T; t += kSpBlock) ma[t] = a.start_tuple ? (t == t_start ? 1.0 : 0.0) : unif;
+        __syncthreads();
+
+        // ---- m' = m / 2 + s / 2 until the largest change is within tol
+        double* mo = ma;
+        double* mn = mb;
+        int it = 0;
+        double chg = 0.0;
+        for (;;) {
+            sp_weights(a, mo, first, perm, Z, W, tid);
+            __syncthreads();
+            double c = 0.0;
+            for (int t = tid; t < T; t += kSpBlock) {
+                int off[MAXN];                           // where this tuple's action sits in a row of agent i
+#pragma unroll
+                for (int i = 0; i < MAXN; i++) off[i] = i < N ? (t / a.tstride[i]) % a.n_actions[i] : 0;
+                double s = 0.0;
+                for (int d = 0; d < D; d++) {
+                    const double w = W[d];
+                    if (w == 0.0) continue;              // no mass at this price: the terms are +0.0
+                    double term = w;
+#pragma unroll
+                    for (int i = 0; i < MAXN; i++) {
+                        if (i >= N) break;
+                        double p;
+                        if (a.kind[i] == 0) {
+                            const uint16_t* rq = reinterpret_cast<const uint16_t*>(s_mem + a.o_row[i]);
+                            p = (int)rq[d] == off[i] ? cst->hi[i] : cst->lo[i];
+                        } else {
+                            const float* rf = reinterpret_cast<const float*>(s_mem + a.o_row[i]);
+                            p = (double)rf[d * a.n_actions[i] + off[i]];
+                        }
+                        term = __dmul_rn(term, p);
+                    }
+                    s = __dadd_rn(s, term);
+                }
+                const double v = __dadd_rn(__dmul_rn(0.5, mo[t]), __dmul_rn(0.5, s));
+                mn[t] = v;
+                c = fmax(c, fabs(__dsub_rn(v, mo[t])));
+            }
+            prod[tid] = c;
+            __syncthreads();
+            if (tid < 16) {
+                double cc = prod[tid * 16];
+                for (int k = 1; k < 16; k++) cc = fmax(cc, prod[tid * 16 + k]);
+                cst->red[tid] = cc;
+            }
+            __syncthreads();
+            c = cst->red[0];
+            for (int k = 1; k < 16; k++) c = fmax(c, cst->red[k]);
+            double* tm = mo; mo = mn; mn = tm;
+            it++;
+            chg = c;
+            if (c <= a.tol || it >= a.max_iters) break;
+        }
+        __syncthreads();                                 // the maxima are read before prod is staged over
+
+        // ---- the outputs, from the last iterate
+        sp_weights(a, mo, first, perm, Z, W, tid);
+        __syncthreads();
+        for (int d = tid; d < D; d += kSpBlock) {        // agree's terms, parked in the dead iterate (D <= T)
+            double term = W[d];
+            for (int i = 0; i < N; i++) {
+                const int A = a.n_actions[i];
+                double p;
+                if (a.kind[i] == 0) {
+                    p = cst->hi[i];
+                } else {
+                    const int gi = min((int)a.dpolicy[(g * N + i) * D + d], A - 1);
+                    p = (double)(reinterpret_cast<const float*>(s_mem + a.o_row[i])[d * A + gi]);
+                }
+                term = __dmul_rn(term, p);
+            }
+            mn[d] = term;
+        }
+        if (a.pi)
+            for (int t = tid; t < T; t += kSpBlock) a.pi[g * T + t] = mo[t];
+        double acc = 0.0;
+        for (int t0 = 0; t0 < T; t0 += 64) {
+            const int t = t0 + tid;
+            if (tid < 64 && t < T) {
+                const double m = mo[t];
+                prod[tid] = m;
+                for (int i = 0; i < N; i++) {
+                    prod[(1 + i) * 64 + tid] = __dmul_rn(m, a.reward[(int64_t)i * T + t]);
+                    prod[(1 + N + i) * 64 + tid] = __dmul_rn(m, a.scaled[(int64_t)i * T + t]);
+                }
+                prod[(1 + 2 * N) * 64 + tid] = __dmul_rn(m, a.price[t]);
+            }
+            __syncthreads();
+            const int n = min(64, T - t0);
+            if (tid < n_out) {
+                const double* pr = prod + tid * 64;
+                for (int kk = 0; kk < n; kk++) acc = __dadd_rn(acc, pr[kk]);
+            } else if (tid == 64 && t0 == 0) {
+                for (int d = 0; d < D; d++) acc = __dadd_rn(acc, mn[d]);
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            a.iters[g] = it;
+            a.change[g] = chg;
+            a.mass[g] = acc;
+        } else if (tid <= N) {
+            a.samp_reward[(int64_t)(tid - 1) * G + g] = acc;
+        } else if (tid <= 2 * N) {
+            a.samp_action[(int64_t)(tid - 1 - N) * G + g] = acc;
+        } else if (tid == 2 * N + 1) {
+            a.samp_price[g] = acc;
+        } else if (tid == 64) {
+            a.agree[g] = acc;
+        }
+    }
+}
+
+#ifndef THRL_SP_HOST_BUILD
+template <int MAXN>
+__global__ void __launch_bounds__(kSpBlock) k_sp_chain(const SpArgs a) {
+    extern __shared__ __align__(16) unsigned char s_mem[];
+    sp_block<MAXN>(a, s_mem, (int)threadIdx.x, (int)blockIdx.x, (int)gridDim.x);
+}
+#endif
+
+}  // namespace
+
+#ifndef THRL_SP_HOST_BUILD
+int launch_sampled_chain(const SpArgs& a, int grid, hipStream_t s) {
+    const void* fn = a.N <= 2 ? reinterpret_cast<const void*>(k_sp_chain<2>) : reinterpret_cast<const void*>(k_sp_chain<kSpMaxA>);
+    if (a.lds_bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (a.N <= 2) hipLaunchKernelGGL(k_sp_chain<2>, dim3(grid), dim3(kSpBlock), (size_t)a.lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_sp_chain<kSpMaxA>, dim3(grid), dim3(kSpBlock), (size_t)a.lds_bytes, s, a);
+    return (int)hipGetLastError();
+}
+#endif
+
+}  // namespace thrl

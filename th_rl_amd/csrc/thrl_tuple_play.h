@@ -45,5 +45,7 @@ struct TpWalkArgs {
 
 int launch_tp_policy(const TpPolicyArgs& a, int q_dtype, hipStream_t s);
 int launch_tp_walk(const TpWalkArgs& a, hipStream_t s);
+// thrl_price_probs for one neural agent: out [G][J][A], the softmax at the J shared prices
+int launch_tp_probs(int G, int A, int J, const float* params, int P, const double* price, float* out, hipStream_t s);
 
 }  // namespace thrl

@@ -1,7 +1,7 @@
 // thrl_tuple_play.hip -- strategies as tables over the game's action tuples, and greedy play on tuple indices
 // (thrl_tuple_policy, thrl_tuple_walk, include/thrl.h).  With discrete agents and no noise the price after a step is a
 // function of that step's action tuple, so what any agent does next is a function of the tuple index: a uint16 per
-// (game, agent, tuple), whatever the agent is.  Three kernels.
+// (game, agent, tuple), whatever the agent is.  Four kernels.
 //
 // k_tp_neural: one wavefront per game for ONE Reinforce / ActorCritic agent (a launch per neural agent, so the
 //   register-resident network is sized for that agent's action count, as k_nn_act's is).  policy_load puts the
@@ -11,6 +11,7 @@
 //   k_nn_act calls, with the same padding: the same bits.
 //   thrl_price_policy runs the same kernels on a free list of J prices, shared by the games or one list per game
 //   (price_stride): T stands for J there.
+// k_tp_probs: k_tp_neural's loop storing the probabilities themselves (thrl_price_probs): float32 [G][J][A].
 // k_tp_qtable: one thread per (game, tuple), every QTable agent in turn: the first maximum of row encode64(price[t]).
 //   Consecutive tuples have neighbouring prices, so a wave reads a few neighbouring rows and its stores are contiguous.
 // k_tp_walk: one lane per match, the walk of k_xplay_walk on a single integer.  The 2-byte policy entries it visits
@@ -46,6 +47,30 @@ __global__ void __launch_bounds__(256) k_tp_neural(int G, int A, int T, const fl
             if (lane == j) keep = act;
         }
         if (lane < n) o[t0 + lane] = (uint16_t)keep;
+    }
+}
+
+// the probabilities where k_tp_neural keeps the action (thrl_price_probs): policy_probs, the function policy_act calls
+// first, with the network in registers across the J shared prices; lane 2k holds action k's probability and stores it,
+// so a price's row leaves the wave as one contiguous piece of A floats
+template <int APAD>
+__global__ void __launch_bounds__(256) k_tp_probs(int G, int A, int J, const float* __restrict__ params, int P,
+                                                   const double* __restrict__ price, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= G) return;
+    PolicyRegs<APAD> r;
+    policy_load(r, params + (int64_t)g * P, A, lane);
+    float* o = out + (int64_t)g * J * A;
+    const bool mine = !(lane & 1) && (lane >> 1) < A;
+    for (int t0 = 0; t0 < J; t0 += 64) {
+        const int n = J - t0 < 64 ? J - t0 : 64;
+        const float xv = (float)price[t0 + (lane < n ? lane : n - 1)];
+        for (int j = 0; j < n; j++) {
+            const float x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xv), j));
+            const float p = policy_probs(r, A, x, lane);
+            if (mine) o[(int64_t)(t0 + j) * A + (lane >> 1)] = p;
+        }
     }
 }
 
@@ -237,6 +262,15 @@ int launch_tp_policy(const TpPolicyArgs& a, int q_dtype, hipStream_t s) {
         if (e != hipSuccess) return (int)e;
     }
     return (int)hipSuccess;
+}
+
+int launch_tp_probs(int G, int A, int J, const float* params, int P, const double* price, float* out, hipStream_t s) {
+    const dim3 grid((unsigned)((G + 3) / 4)), block(256);
+    // the padding k_nn_act takes for this action count
+    if (A <= 8) hipLaunchKernelGGL(k_tp_probs<8>, grid, block, 0, s, G, A, J, params, P, price, out);
+    else if (A <= 24) hipLaunchKernelGGL(k_tp_probs<24>, grid, block, 0, s, G, A, J, params, P, price, out);
+    else hipLaunchKernelGGL(k_tp_probs<32>, grid, block, 0, s, G, A, J, params, P, price, out);
+    return (int)hipGetLastError();
 }
 
 int launch_tp_walk(const TpWalkArgs& a, hipStream_t s) {

@@ -339,8 +339,9 @@ def _worker(rank, world, port, config, out, devices_available):
 def check_launch_config(config):
     """ValueError for a training key that has no sharded form: training.greedy_cycles re-seats agents across games and
     its merge over shards is not built, nor is that of training.greedy_deviation, training.greedy_equilibrium,
-    training.greedy_attractors and training.greedy_stationary."""
-    for key in ("greedy_cycles", "greedy_deviation", "greedy_equilibrium", "greedy_attractors", "greedy_stationary"):
+    training.greedy_attractors, training.greedy_stationary and training.sampled_play."""
+    for key in ("greedy_cycles", "greedy_deviation", "greedy_equilibrium", "greedy_attractors", "greedy_stationary",
+                "sampled_play"):
         gc = config.get("training", {}).get(key)
         if gc is not None and gc is not False:
             raise ValueError("training.%s is not available under th_rl_amd.launch (sharded runs are not merged); "

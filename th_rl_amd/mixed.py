@@ -419,6 +419,22 @@ class MixedGameBatch:
         return ts.run(self, noise_prob=noise_prob, start=start, resolution=resolution, tol=tol, max_iters=max_iters, pi=pi,
                       tuple_policy=tuple_policy, cell_policy=cell_policy, n_games=n_games, tabs=tabs)
 
+    def sampled_play(self, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None,
+                     tuple_policy=None, probs=None, dpolicy=None, tabs=None):
+        """The exact long-run profit of SAMPLED play (sampled_play.run, thrl_price_probs + thrl_sampled_chain): every
+        agent plays the way it was trained -- a Reinforce / ActorCritic agent samples its softmax, a QTable agent is
+        epsilon-greedy (epsilon: "current" = the batch's epsilon now, a number, one per agent, or an array [N, G]) --
+        with no demand noise, so the tuple played is a Markov chain on the game's T action tuples: iters, change, mass,
+        samp_price, agree [G] (the share of steps on which every agent plays its greedy action), samp_reward,
+        samp_action [N, G], with pi the distribution [G, T].  start: "uniform", "state" or int [G] start tuples.  A batch
+        with a CAC agent or more than 4096 action tuples raises ValueError; a working set above a CU's LDS is
+        THRL_ERR_UNSUPPORTED.  Nothing of the batch is written."""
+        from . import sampled_play as sp
+        if not self.initialized:
+            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
+        return sp.run(self, epsilon=epsilon, start=start, tol=tol, max_iters=max_iters, pi=pi, n_games=n_games,
+                      tuple_policy=tuple_policy, probs=probs, dpolicy=dpolicy, tabs=tabs)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
         all-QTable batches here).  A batch with a neural agent raises ThrlError."""

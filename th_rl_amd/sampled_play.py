@@ -1,0 +1,403 @@
+"""Sampled play: the exact long-run profit of the STOCHASTIC policies the agents were trained with (thrl_price_probs,
+thrl_sampled_chain, include/thrl.h), where every other analysis treats an agent as its greedy policy.
+
+A Reinforce / ActorCritic agent learns a distribution (pi -> Categorical(...).sample()); a QTable agent plays
+epsilon-greedily.  Without demand noise the price after a step is a function of the action tuple just played
+(tuple_play.py), so under sampling the tuple played at a step is a Markov chain on the game's T tuples with
+P(t -> t') = prod_i pi_i(a_i(t') | price(t)).  The row depends on t only through its price and many tuples share one, so
+everything is indexed by the D <= T distinct prices of the config, and the row is a product over agents: a step costs
+T D N multiplications and needs D sum_i A_i probabilities, never a T x T matrix.
+
+tables(config) derives the per-config tables in numpy (tuple_play.tables' arrays, the distinct prices and the grouping of
+the tuples by price); the device only reads them.  price_probs() evaluates the networks' softmax at a list of prices,
+run() iterates the chain and returns per game (definitions in include/thrl.h) iters, change, mass, samp_price, agree [G],
+samp_reward, samp_action [N, G], optionally pi [G, T].  `agree` is the long-run share of steps on which every agent plays
+its greedy action.  summarize() gives per group converged, iters_*, delta_sampled_* (the profit gain of sampled play),
+agree_mean and price_mean.  Demand noise, the reset distribution as a start, sharded runs (th_rl_amd.launch) and CAC
+agents are out of scope.
+"""
+import ctypes
+import json
+import os
+
+import numpy as np
+
+from . import _lib
+from . import stationary as sn
+from . import tuple_play as tp
+from ._lib import ThrlError
+from .deviation import optimal, profit_gain
+
+DEFAULTS = dict(epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False)
+STARTS = ("uniform", "state")
+MAX_PRICES = _lib.STAT_MAX_CELLS
+MAX_LDS = _lib.SP_MAX_LDS
+GAME_FLOAT = ("change", "mass", "samp_price", "agree")
+AGENT_FLOAT = ("samp_reward", "samp_action")
+PER_GAME = ("iters", "start", "epsilon") + GAME_FLOAT + AGENT_FLOAT + ("pi",)
+
+
+def _check_eps(e, what):
+    if isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating)) or not 0.0 <= float(e) <= 1.0:
+        raise ValueError("%s must be a number in [0, 1], got %r" % (what, e))
+    return float(e)
+
+
+def parse_options(opt, config):
+    """training.sampled_play (true or a dict) -> the dict with every key filled in: epsilon ("current": the QTable
+    agents' epsilon where training stopped; a number, or one per agent), start ("uniform" or "state"), tol, max_iters,
+    pi (store the distributions).  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples and a working set above a
+    CU's LDS."""
+    name = "training.sampled_play"
+    tp.check_config(config)
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict):
+        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
+    bad = set(opt) - set(DEFAULTS)
+    if bad:
+        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(DEFAULTS))))
+    out = dict(DEFAULTS)
+    out.update(opt)
+    e = out["epsilon"]
+    if isinstance(e, (list, tuple)):
+        if len(e) != len(config["agents"]):
+            raise ValueError("%s.epsilon holds %d numbers, the game has %d agents" % (name, len(e), len(config["agents"])))
+        out["epsilon"] = [_check_eps(x, name + ".epsilon") for x in e]
+    elif e != "current":
+        out["epsilon"] = _check_eps(e, name + ".epsilon")
+    if out["start"] not in STARTS:
+        raise ValueError("%s.start must be one of %s, got %r" % (name, STARTS, out["start"]))
+    if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float)) or not out["tol"] >= 0.0:
+        raise ValueError("%s.tol must be a number >= 0, got %r" % (name, out["tol"]))
+    out["tol"] = float(out["tol"])
+    if isinstance(out["max_iters"], bool) or not isinstance(out["max_iters"], int) \
+            or not 1 <= out["max_iters"] <= _lib.STAT_MAX_ITERS:
+        raise ValueError("%s.max_iters must be an integer in [1, %d], got %r" % (name, _lib.STAT_MAX_ITERS, out["max_iters"]))
+    if not isinstance(out["pi"], bool):
+        raise ValueError("%s.pi must be true or false, got %r" % (name, out["pi"]))
+    ws = working_set(config)
+    if not ws["fits"]:
+        raise ValueError("%s: a game's working set is %d bytes (T=%d, D=%d), a CU's LDS holds %d"
+                         % (name, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the per-config tables
+def tables(config):
+    """The per-config tables of thrl_sampled_chain (include/thrl.h) as a dict of numpy arrays: tuple_play.tables' T,
+    n_actions, kinds, price [T], reward and scaled [N, T] as they are; dprice [D], the distinct values of price ascending
+    (two prices are equal when their float64 bits are equal); row int32 [T], the index of price[t] in dprice; grp_first
+    int32 [D + 1] and grp_perm int32 [T], the stable grouping of the tuples by row (ascending t inside a group);
+    n_tuples, n_prices."""
+    t = tp.tables(config)
+    price = np.ascontiguousarray(t["price"], np.float64)
+    # prices are >= +0.0, so the order of the bit patterns is the order of the values
+    bits, row = np.unique(price.view(np.int64), return_inverse=True)
+    row = row.reshape(-1).astype(np.int32)
+    D = int(bits.size)
+    perm = np.argsort(row, kind="stable").astype(np.int32)
+    first = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=D))]).astype(np.int32)
+    out = dict(t)
+    out.update(dprice=np.ascontiguousarray(bits.view(np.float64)), row=row, grp_first=first, grp_perm=perm,
+               n_tuples=int(t["T"]), n_prices=D)
+    return out
+
+
+def _r16(x):
+    return (int(x) + 15) & ~15
+
+
+def working_set(config, tabs=None):
+    """The LDS bytes one game takes in thrl_sampled_chain, by include/thrl.h's formula: the sum of r16(x) over 8 T, 8 T
+    (the iterates), 8 D, 8 D (W, Z), 4 D A_i per network, 2 D per QTable agent, 2 (D + 1), 2 T (the grouping),
+    512 (2 N + 2) (staging) and 256 (constants).  Returns dict(bytes, T, D, fits): fits = within a CU's 160 KB."""
+    tabs = tables(config) if tabs is None else tabs
+    T, D, N = int(tabs["n_tuples"]), int(tabs["n_prices"]), len(tabs["kinds"])
+    b = 2 * _r16(8 * T) + 2 * _r16(8 * D)
+    for kind, A in zip(tabs["kinds"], tabs["n_actions"]):
+        b += _r16(2 * D) if kind == "QTable" else _r16(4 * D * int(A))
+    b += _r16(2 * (D + 1)) + _r16(2 * T) + _r16(512 * (2 * N + 2)) + 256
+    return dict(bytes=int(b), T=T, D=D, fits=b <= MAX_LDS)
+
+
+# ---------------------------------------------------------------------------------------------- the device calls
+def _games(batch, n_games):
+    G = batch.G if n_games is None else int(n_games)
+    if not 1 <= G <= batch.G:
+        raise ThrlError("sampled_play: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    if not getattr(batch, "initialized", True):
+        raise ThrlError("sampled_play: call init_tables() or set_tables() first")
+    return G
+
+
+def price_probs(batch, prices, n_games=None):
+    """thrl_price_probs: {agent index: device float32 [G, J, A_i]} for the Reinforce / ActorCritic agents of the first
+    n_games (default all) games of `batch`: the softmax each samples from at the J prices `prices` (shared by the
+    games), bit for bit what thrl_nn_act / thrl_ac_act return as prob_out.  An all-QTable batch gives {}.  Nothing of the
+    batch is written."""
+    import torch
+    kinds = tp._kinds(batch)
+    G = _games(batch, n_games)
+    dev = batch.device
+    with torch.cuda.device(dev):
+        if isinstance(prices, torch.Tensor):
+            x = prices.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(np.asarray(prices, np.float64).reshape(-1))).to(dev)
+        J = int(x.numel())
+        if not 1 <= J <= MAX_PRICES:
+            raise ThrlError("sampled_play: %d prices, the list must hold 1 to %d" % (J, MAX_PRICES))
+        a = _lib.PriceProbsArgs()
+        a.n_games, a.n_prices = G, J
+        out = {}
+        for i, k in enumerate(kinds):
+            a.kind[i] = tp.KINDS[k]
+            if k != "QTable" and k != "CAC":
+                out[i] = torch.empty((G, J, int(batch.cfg.n_actions[i])), dtype=torch.float32, device=dev)
+                a.nn_params[i] = batch.nn[i].params.data_ptr()
+                a.prob[i] = out[i].data_ptr()
+        a.price = x.data_ptr()
+        _lib.check(batch.L.thrl_price_probs(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()), "thrl_price_probs")
+        torch.cuda.synchronize(dev)
+    return out
+
+
+def resolve_epsilon(batch, epsilon, G):
+    """(eps [N] floats, eps_g device float64 [N, G] or None) for `epsilon`: "current" = the batch's epsilon now (the
+    per-game sweep array where a sweep has one, else batch.eps); a number = every QTable agent's; N numbers; or an
+    array [N, G] (device data: an entry outside [0, 1] refuses that game)."""
+    import torch
+    N = batch.N
+    if isinstance(epsilon, str):
+        if epsilon != "current":
+            raise ThrlError("sampled_play: epsilon must be 'current', a number, N numbers or an array [N, G], got %r" % epsilon)
+        sw = getattr(batch, "sweep", None) or {}
+        if "eps" in sw:
+            return [0.0] * N, sw["eps"][:, :G].to(torch.float64).contiguous()
+        return [float(x) for x in list(batch.eps)[:N]], None
+    if isinstance(epsilon, torch.Tensor) or np.ndim(epsilon) == 2:
+        e = epsilon if isinstance(epsilon, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(epsilon, np.float64))
+        e = e.to(device=batch.device, dtype=torch.float64)
+        if e.dim() != 2 or e.shape[0] != N or e.shape[1] < G:
+            raise ThrlError("sampled_play: a per-game epsilon must be [N=%d, G>=%d], got %s" % (N, G, tuple(e.shape)))
+        return [0.0] * N, e[:, :G].contiguous()
+    e = [float(epsilon)] * N if np.ndim(epsilon) == 0 else [float(x) for x in epsilon]
+    if len(e) != N:
+        raise ThrlError("sampled_play: epsilon holds %d numbers, the game has %d agents" % (len(e), N))
+    kinds = tp._kinds(batch)
+    for i, x in enumerate(e):
+        if kinds[i] == "QTable" and not 0.0 <= x <= 1.0:
+            raise ThrlError("sampled_play: epsilon[%d]=%r out of [0, 1]" % (i, x))
+    return e, None
+
+
+def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None, tuple_policy=None,
+        probs=None, dpolicy=None, tabs=None):
+    """thrl_sampled_chain for the first n_games (default all) games of `batch` (a MixedGameBatch of QTable / Reinforce /
+    ActorCritic agents, or a GameBatch).  epsilon: resolve_epsilon's rules.  start: "uniform" (1 / T on every tuple),
+    "state" (the tuple whose price is the state the batch holds, tuple_play.start_tuples; a game whose state is no
+    tuple's price is refused with iters = -1), or int [G] start tuples (outside [0, T): refused).  probs / dpolicy: the
+    strategies at tabs["dprice"] ({i: float32 [G, D, A_i]} of price_probs, int16 [G, N, D] of
+    tuple_stationary.price_policy; default: evaluated here; tuple_policy, tuple_play.extract()'s tensor, gives dpolicy
+    without a device call, the tuple prices being the distinct prices repeated).  Returns a dict of numpy arrays."""
+    import torch
+    from . import tuple_stationary as ts
+    N = batch.N
+    G = _games(batch, n_games)
+    given_start = not isinstance(start, str)
+    if not given_start and start not in STARTS:
+        raise ThrlError("sampled_play: start must be one of %s or an array of tuples, got %r" % (STARTS, start))
+    if isinstance(max_iters, bool) or not 1 <= int(max_iters) <= _lib.STAT_MAX_ITERS:
+        raise ThrlError("sampled_play: max_iters=%r out of [1, %d]" % (max_iters, _lib.STAT_MAX_ITERS))
+    if tabs is None:
+        tabs = tables(batch.config)
+    tp._batch_tables(batch, tabs)
+    ws = working_set(batch.config, tabs)
+    if not ws["fits"]:                                   # what thrl_sampled_chain answers from the shape alone
+        err = ThrlError("thrl_sampled_chain refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d), at most %d"
+                        % (_lib.ERR_UNSUPPORTED, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    kinds = tp._kinds(batch)
+    dev = batch.device
+    sdev = batch.state.device
+    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
+    a = _lib.SampledChainArgs()
+    a.n_games, a.n_tuples, a.n_prices, a.max_iters, a.tol = G, T, D, int(max_iters), float(tol)
+    for i, k in enumerate(kinds):
+        a.kind[i] = tp.KINDS[k]
+    with torch.cuda.device(dev):
+        eps, eps_g = resolve_epsilon(batch, epsilon, G)
+        for i in range(N):
+            a.eps[i] = eps[i]
+        if eps_g is not None:
+            a.eps_g = eps_g.data_ptr()
+        if probs is None:
+            probs = price_probs(batch, tabs["dprice"], n_games=G)
+        if dpolicy is None:
+            if tuple_policy is not None and ts._is_policy(tuple_policy, (batch.G, N, T), sdev):
+                rep = torch.from_numpy(np.asarray(tabs["grp_perm"])[np.asarray(tabs["grp_first"])[:-1]].astype(np.int64))
+                dpolicy = tuple_policy[:G].index_select(2, rep.to(sdev)).contiguous()
+            else:
+                dpolicy = ts.price_policy(batch, tabs["dprice"], n_games=G)
+        if not ts._is_policy(dpolicy, (G, N, D), sdev):
+            raise ThrlError("sampled_play: dpolicy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, D), dev))
+        for i, k in enumerate(kinds):
+            if k == "QTable":
+                continue
+            p = probs.get(i)
+            shape = (G, D, int(batch.cfg.n_actions[i]))
+            if p is None or tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != sdev or not p.is_contiguous():
+                raise ThrlError("sampled_play: probs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
+            a.prob[i] = p.data_ptr()
+        a.dpolicy = dpolicy.data_ptr()
+        keep = {}
+        for f, shape, dt in (("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32), ("reward", (N, T), np.float64),
+                             ("scaled", (N, T), np.float64), ("price", (T,), np.float64)):
+            x = np.ascontiguousarray(tabs[f], dt)
+            if x.shape != shape:
+                raise ThrlError("sampled_play: table %s has shape %s, expected %s" % (f, x.shape, shape))
+            keep[f] = torch.from_numpy(x).to(dev)
+            setattr(a, f, keep[f].data_ptr())
+        t0 = None
+        if given_start:
+            if isinstance(start, torch.Tensor):
+                t0 = start.to(device=dev, dtype=torch.int32).reshape(-1)[:G].contiguous()
+            else:
+                t0 = torch.from_numpy(np.ascontiguousarray(np.asarray(start).reshape(-1)[:G].astype(np.int32))).to(dev)
+            if t0.numel() != G:
+                raise ThrlError("sampled_play: start must hold %d tuples" % G)
+        elif start == "state":
+            t0 = tp.start_tuples(batch.state[:G], tabs).to(torch.int32).contiguous()
+        if t0 is not None:
+            a.flags = _lib.SP_START_TUPLE
+            a.start = t0.data_ptr()
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        out = {"iters": torch.zeros((G,), dtype=torch.int32, device=dev)}
+        out.update({f: f64(G) for f in GAME_FLOAT})
+        out.update({f: f64(N, G) for f in AGENT_FLOAT})
+        if pi:
+            out["pi"] = f64(G, T)
+        for f, t in out.items():
+            setattr(a, f, t.data_ptr())
+        _lib.check(batch.L.thrl_sampled_chain(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                   "thrl_sampled_chain")
+        torch.cuda.synchronize(dev)
+        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res["epsilon"] = np.repeat(np.asarray(eps, np.float64)[:, None], G, axis=1) if eps_g is None else eps_g.cpu().numpy()
+        if t0 is not None:
+            res["start"] = t0.cpu().numpy()
+    res["T"], res["n_prices"], res["max_iters"], res["lds_bytes"] = T, D, int(max_iters), ws["bytes"]
+    return res
+
+
+# ---------------------------------------------------------------------------------------------- host side
+def summarize(games, ids, n_groups, nash, cartel, max_iters, cycle_reward=None):
+    """The summary rows, one per group: games, converged (solved and stopped before max_iters), iters_q25 / q50 / q75 /
+    max, delta_sampled_mean / q25 / q50 / q75 (the profit gain of samp_reward, deviation.profit_gain), agree_mean,
+    price_mean over the solved games.  cycle_reward [N, G] with lam [G] (the greedy cycles of the same run, where it has
+    them): also delta_greedy_mean and randomness_cost_mean = delta_greedy - delta_sampled over the solved games that
+    have a greedy cycle."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    iters = np.asarray(games["iters"], np.int64)
+    solved = iters >= 0
+    delta = profit_gain(np.asarray(games["samp_reward"], np.float64), nash, cartel)
+    price = np.asarray(games["samp_price"], np.float64)
+    agree = np.asarray(games["agree"], np.float64)
+    dgreedy = has = None
+    if cycle_reward is not None:
+        cr, lam = cycle_reward
+        dgreedy = profit_gain(np.asarray(cr, np.float64), nash, cartel)
+        has = np.asarray(lam).reshape(-1) > 0
+    out = []
+    for k in range(int(n_groups)):
+        m = ids == k
+        ms = m & solved
+        row = {"group": k, "games": int(m.sum()),
+               "converged": sn._mean(solved[m] & (iters[m] < int(max_iters))) if m.any() else None}
+        sn._quantiles(row, "iters", iters[ms])
+        row["iters_max"] = int(iters[ms].max()) if ms.any() else None
+        row["delta_sampled_mean"] = sn._mean(delta[ms])
+        sn._quantiles(row, "delta_sampled", delta[ms])
+        row["agree_mean"] = sn._mean(agree[ms])
+        row["price_mean"] = sn._mean(price[ms])
+        if dgreedy is not None:
+            mg = ms & has
+            row["delta_greedy_mean"] = sn._mean(dgreedy[mg])
+            row["randomness_cost_mean"] = sn._mean(dgreedy[mg] - delta[mg])
+        out.append(row)
+    return out
+
+
+def combine(parts):
+    """Per-game arrays of disjoint sets of games (in global game order) as one run's: concatenated along the game axis
+    (axis 0 of pi [G, T], the last axis of the others)."""
+    parts = list(parts)
+    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=0 if f == "pi" else -1)
+            for f in parts[0] if f in PER_GAME}
+
+
+def describe(options, T, n_prices, nash, cartel, summary):
+    """sampled_play.json's content."""
+    return {"options": options, "T": int(T), "n_prices": int(n_prices), "nash": nash, "cartel": cartel,
+            "quantiles": list(sn.QUANTILES), "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)",
+            "summary": summary}
+
+
+def save_games(d, r):
+    """splay_iters int32 [G], splay_games float64 [4, G] (change, mass, samp_price, agree), splay_reward, splay_action and
+    splay_epsilon float64 [N, G]; from start tuples splay_start int32 [G]; with the distributions splay_pi float64
+    [G, T]."""
+    np.save(os.path.join(d, "splay_iters.npy"), np.asarray(r["iters"], np.int32))
+    np.save(os.path.join(d, "splay_games.npy"), np.stack([np.asarray(r[f], np.float64) for f in GAME_FLOAT]))
+    np.save(os.path.join(d, "splay_reward.npy"), np.asarray(r["samp_reward"], np.float64))
+    np.save(os.path.join(d, "splay_action.npy"), np.asarray(r["samp_action"], np.float64))
+    np.save(os.path.join(d, "splay_epsilon.npy"), np.asarray(r["epsilon"], np.float64))
+    for f, name in (("start", "splay_start.npy"), ("pi", "splay_pi.npy")):
+        path = os.path.join(d, name)
+        if f in r:
+            np.save(path, np.asarray(r[f], np.int32 if f == "start" else np.float64))
+        elif os.path.isfile(path):               # a file left by an earlier run with other options
+            os.remove(path)
+
+
+def load_games(d):
+    """The per-game arrays one run directory holds (training.sampled_play)."""
+    gm = np.load(os.path.join(d, "splay_games.npy"))
+    g = {"iters": np.load(os.path.join(d, "splay_iters.npy"))}
+    g.update({f: gm[k] for k, f in enumerate(GAME_FLOAT)})
+    g.update(samp_reward=np.load(os.path.join(d, "splay_reward.npy")), samp_action=np.load(os.path.join(d, "splay_action.npy")),
+             epsilon=np.load(os.path.join(d, "splay_epsilon.npy")))
+    for f, name in (("start", "splay_start.npy"), ("pi", "splay_pi.npy")):
+        if os.path.isfile(os.path.join(d, name)):
+            g[f] = np.load(os.path.join(d, name))
+    return g
+
+
+def greedy_cycles_of(d, n_games):
+    """(cycle_reward [N, G], lam [G]) of the self-play round of training.greedy_cycles in the same directory, or None
+    when there is none or it holds another number of games."""
+    pr, pc = os.path.join(d, "gcyc_cycle_reward.npy"), os.path.join(d, "gcyc_cycle.npy")
+    if not (os.path.isfile(pr) and os.path.isfile(pc)):
+        return None
+    cr, cyc = np.load(pr), np.load(pc)
+    if cr.ndim != 3 or cr.shape[2] != int(n_games) or cyc.shape[0] < 1:
+        return None
+    return cr[0], cyc[0, 1]
+
+
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None, with_cycles=False):
+    """train_one's training.sampled_play outputs: the per-game splay_*.npy files and sampled_play.json.  with_cycles:
+    this run wrote the gcyc_* files (training.greedy_cycles) just before; only then does the summary carry
+    delta_greedy_mean and randomness_cost_mean."""
+    tabs = tables(config)
+    r = run(batch, epsilon=opt["epsilon"], start=opt["start"], tol=opt["tol"], max_iters=opt["max_iters"], pi=opt["pi"],
+            tuple_policy=tuple_policy, tabs=tabs)
+    save_games(exp_path, r)
+    nash, cartel = optimal(config)
+    cyc = greedy_cycles_of(exp_path, np.asarray(r["iters"]).size) if with_cycles else None
+    summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"], cycle_reward=cyc)
+    with open(os.path.join(exp_path, "sampled_play.json"), "w") as f:
+        json.dump(describe(opt, r["T"], r["n_prices"], nash, cartel, summary), f, indent=2)
+    return r

@@ -58,6 +58,13 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                       # `resolution` uniform cells of the price axis: greedy_stationary.json,
                                       # gstat_iters.npy int32 [2, G] (iters, n_switch), gstat_games.npy [5, G],
                                       # gstat_reward.npy / gstat_action.npy [N, G]; with pi gstat_pi.npy [G, T]
+                 "sampled_play": null,  # true or {"epsilon": "current", "start": "uniform" | "state", "tol": 1e-12,
+                                      # "max_iters": 8192, "pi": false}: after training the exact long-run profit of
+                                      # SAMPLED play, the way the agents were trained (sampled_play.py: a network samples
+                                      # its softmax, a QTable agent is epsilon-greedy; no demand noise), for any mix of
+                                      # QTable, Reinforce and ActorCritic agents: sampled_play.json, splay_iters.npy int32
+                                      # [G], splay_games.npy [4, G] (change, mass, price, agree), splay_reward.npy /
+                                      # splay_action.npy / splay_epsilon.npy [N, G]; with pi splay_pi.npy [G, T]
                  "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
                                      # "horizon": null}: after training (and the greedy statistics) the deviation
                                      # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json
@@ -300,6 +307,10 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if training.get("greedy_stationary") is not None and training.get("greedy_stationary") is not False:
         from th_rl_amd.tuple_stationary import parse_options as greedy_stationary_options
         gst_opt = greedy_stationary_options(training["greedy_stationary"], config)     # refuses CAC, too many tuples / cells
+    sp_opt = None
+    if training.get("sampled_play") is not None and training.get("sampled_play") is not False:
+        from th_rl_amd.sampled_play import parse_options as sampled_play_options
+        sp_opt = sampled_play_options(training["sampled_play"], config)     # refuses CAC, too many tuples, the working set
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -641,6 +652,17 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
                                              n_groups=training.get("n_groups", None))
         tuple_stationary.write_artefacts(exp_path, batch, config, gst_opt, ids, n_groups, tuple_policy=tuple_policy)
+
+    if sp_opt is not None:      # what the agents earn when they play the way they were trained: sampled, not greedy
+        from th_rl_amd import sampled_play
+        if spec is not None:
+            ids, n_groups = spec.ids, spec.n_groups
+        else:
+            from th_rl_amd.group_stats import assign_groups
+            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                             n_groups=training.get("n_groups", None))
+        sampled_play.write_artefacts(exp_path, batch, config, sp_opt, ids, n_groups, tuple_policy=tuple_policy,
+                                     with_cycles=gc_opt is not None)
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

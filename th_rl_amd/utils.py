@@ -658,3 +658,46 @@ def greedy_stationary_games(exp_path):
         cols["start"] = g["start"]
     n = g["iters"].shape[0]
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
+def sampled_play_summary(exp_path):
+    """A run's sampled-play analysis (training.sampled_play: the exact long-run profit of the stochastic policies the
+    agents were trained with, for any mix of QTable / Reinforce / ActorCritic agents): sampled_play.json's summary as a
+    DataFrame, one row per group: games, converged, iters_*, delta_sampled_* (the profit gain of sampled play),
+    agree_mean (the share of steps on which every agent plays its greedy action), price_mean; where greedy_cycles ran in
+    the same experiment also delta_greedy_mean and randomness_cost_mean = delta_greedy - delta_sampled; plus T,
+    n_prices, Nash and Cartel."""
+    import json
+    with open(os.path.join(exp_path, "sampled_play.json")) as f:
+        desc = json.load(f)
+    df = pandas.DataFrame(desc["summary"])
+    df["T"], df["n_prices"] = int(desc["T"]), int(desc["n_prices"])
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def sampled_play_games(exp_path):
+    """Per-game results of training.sampled_play, one row per game indexed by its GLOBAL id: iters, change, mass, price,
+    agree, reward_<i>, action_<i>, epsilon_<i>, delta_sampled (the profit gain, as stationary_games computes
+    delta_noise) and, from the training state, start (the tuple played there)."""
+    import json
+    from th_rl_amd import sampled_play as sp
+    from th_rl_amd.deviation import profit_gain
+    if not os.path.isfile(os.path.join(exp_path, "splay_iters.npy")):
+        raise KeyError("no sampled-play analysis (splay_iters.npy) under %s (training.sampled_play)" % exp_path)
+    with open(os.path.join(exp_path, "sampled_play.json")) as f:
+        desc = json.load(f)
+    off = 0
+    if os.path.isfile(os.path.join(exp_path, "config.json")):
+        with open(os.path.join(exp_path, "config.json")) as f:
+            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    g = sp.load_games(exp_path)
+    cols = {"iters": g["iters"], "change": g["change"], "mass": g["mass"], "price": g["samp_price"], "agree": g["agree"]}
+    for i in range(g["samp_reward"].shape[0]):
+        cols["reward_%d" % i], cols["action_%d" % i] = g["samp_reward"][i], g["samp_action"][i]
+        cols["epsilon_%d" % i] = g["epsilon"][i]
+    cols["delta_sampled"] = profit_gain(g["samp_reward"], desc["nash"], desc["cartel"])
+    if "start" in g:
+        cols["start"] = g["start"]
+    n = g["iters"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
