@@ -1,7 +1,8 @@
 """GPU tests of the neural policy path (Reinforce, reference agents.py:119-220) against the numpy
 oracle and the reference-generated fixture G7.  float32 tolerances (torch's summation order is
-unspecified): probabilities rtol 2e-5, clipped gradients rtol 2e-4 + atol 2e-6, Adam moments rtol
-1e-3, parameters atol 5e-6 except Adam's sign-sensitive near-zero-gradient elements (<= 0.2 %)."""
+unspecified): probabilities rtol 2e-5 (at the initial weight scale; the derived bound of
+tests/policy_reference.py otherwise, see tests/test_gpu_policy.py), clipped gradients rtol 2e-4 + atol 2e-6, Adam
+moments rtol 1e-3, parameters atol 5e-6 except Adam's sign-sensitive near-zero-gradient elements (<= 0.2 %)."""
 import os
 
 import numpy as np
@@ -239,65 +240,165 @@ def test_mixed_episode_kernel_equals_operator_loop(dtype, noise, order):
         assert np.array_equal(a.nn[i].adam_v.cpu().numpy(), b.nn[i].adam_v.cpu().numpy())
 
 
-def test_qtable_vs_reinforce_game_against_composed_oracle():
-    """The reference's own pairing (QTable vs Reinforce): the device loop against a Python loop
-    composed from the pinned oracles (C oracle for env / encode / TD, numpy oracle for the MLP),
-    fed the same Philox draws.  Tables are bit-identical; network parameters to float32 rounding."""
-    import ctypes
+AC_AGENT = {"name": "ActorCritic", "gamma": 0.98, "actions": 21, "states": 1, "action_range": [0.2, 0.4]}
+AUDIT_GAMES = {
+    "q_vs_reinforce21": [dict(Q_AGENT, min_memory=30), dict(R_AGENT, min_memory=60, entropy=0.01)],
+    "q_vs_reinforce25": [dict(Q_AGENT, min_memory=30), dict(R_AGENT, actions=25, min_memory=60, entropy=0.01)],
+    "q_vs_actorcritic": [dict(Q_AGENT, min_memory=30), dict(AC_AGENT, min_memory=60, entropy=0.01)],
+    "q_vs_reinforce32": [dict(Q_AGENT, min_memory=30), dict(R_AGENT, actions=32, min_memory=60, entropy=0.01)],
+    "reinforce_vs_reinforce": [dict(R_AGENT, min_memory=60, entropy=0.01), dict(R_AGENT, actions=32, min_memory=30)],
+}
+
+
+def _audit_neural_game(label, path, E=5, G=3, T=30, seed=11):
+    """A whole game with sampled neural play, audited step by step against the composed oracle (C oracle for env / encode /
+    TD, the float64 mirror tests/policy_reference.py for the policy, the numpy oracle for the network update).  A CPU loop
+    beside the device forks at the first float32 summation-order difference after an update, so the oracle is teacher-forced
+    from the device's own state, one episode (one run() call) at a time: from the snapshot before the call it regenerates
+    the Philox draws, replays the QTable agent exactly, requires each neural action in the replay ring to lie in the
+    mirror's window at the ring's price and adopts it, and requires env_step to give the ring's reward and next price bit
+    for bit.  After each episode: table, counter, epsilon exact; at each network update the numpy oracle's step from the
+    snapshot on the ring's transitions within the per-update tolerances of this file (|diff| > 5e-6 in under 0.2 % of the
+    elements, max 4.1e-4).  path: "unfused" (operator loop), "wave" (k_mixed_wave), "tuple" (k_ptuple_episodes), None
+    (run()'s default).  Returns the batch."""
+    import policy_reference as PR
     from th_rl_amd.mixed import MixedGameBatch
-    T, mm = 30, 60
-    config = {"agents": [dict(Q_AGENT, min_memory=T), dict(R_AGENT, min_memory=mm, entropy=0.01)],
-              "environment": dict(ENV, max_steps=T)}
-    G, E = 3, 5
-    mb = MixedGameBatch(config, n_games=G, dtype="float64", seed=11).init_tables()
-    q0, s0 = mb.tables_numpy().copy(), mb.states_numpy().copy()
-    w0 = mb.nn[1].params.cpu().numpy().copy()
-    out = mb.run(E)
-    # ---- composed oracle
-    qcfg, eps0 = O.cfg_from_config({"agents": [config["agents"][0], dict(Q_AGENT, states=1, actions=21)],
-                                    "environment": config["environment"]}, 1, 1)
-    for g in range(G):
-        table = q0[g, :2121].reshape(101, 21).copy(); counter = np.zeros((101, 21), np.int32)
-        w = w0[g].copy(); m = np.zeros_like(w); v = np.zeros_like(w); step = 0
-        price = s0[g]; eps = 0.5
-        memq = []; memr = []
-        for e in range(E):
-            rl = np.zeros(2); al = np.zeros(2)
-            for t in range(T):
-                ctr = [t, e, g, 0]
-                xs = O.philox(ctr, [11, 0])
-                u0 = xs[0] * 2.0 ** -32; c0 = (xs[1] * 21) >> 32; u1 = xs[2] * 2.0 ** -32
-                if u0 < eps:
-                    a0 = c0
-                else:
-                    a0 = int(np.argmax(table[O.encode32(price, 10, 100)]))
-                a1 = int(NN.sample_action(w, 21, [price], [u1])[0])
-                sc0 = O.scale(a0, 21, 0.2, 0.4); sc1 = NN.scale(a1, 21, 0.2, 0.4)
-                nprice, rew = O.env_step(qcfg, [sc0, sc1])
-                memq.append((O.encode64(price, 10, 100), a0, rew[0], O.encode64(nprice, 10, 100)))
-                memr.append((price, a1, rew[1]))
-                rl += rew / T; al += np.array([sc0, sc1]) / T
-                price = nprice
-            if len(memq) >= T:
-                st, ac, rw, ns = zip(*memq)
-                O.td_update(table, counter, st, ac, rw, ns, 0.1, 0.95); memq = []
-            eps = 0.001 + (eps - 0.001) * 0.9995
-            if len(memr) >= mm:
-                pr, ac, rw = zip(*memr)
-                w, m, v, step, _ = NN.train_net(w, m, v, step, 21, pr, ac, rw, 0.995, 0.01); memr = []
-            if e == 0:
-                np.testing.assert_allclose(out["game_reward_log"][e, :, g], rl, rtol=1e-13)
-        # the float32 policy can flip an inverse-CDF draw after an update, so compare the parts that
-        # are insensitive to it only when the whole action sequence agreed
-        if np.array_equal(mb.table(g, 0), table):
-            assert np.array_equal(mb.counter_of(g, 0), counter.astype(np.float64))
-            diff = np.abs(mb.nn[1].params[g].cpu().numpy() - w)
-            assert (diff > 1e-5).mean() < 0.01 and diff.max() <= 1e-3, (float((diff > 1e-5).mean()), float(diff.max()))
-            matched = True
+    agents = [dict(a) for a in AUDIT_GAMES[label]]
+    config = {"agents": agents, "environment": dict(ENV, max_steps=T)}
+    mb = MixedGameBatch(config, n_games=G, dtype="float64", seed=seed).init_tables()
+    mb.tuple_kernel = path != "wave"
+    N = len(agents)
+    nn_i = sorted(mb.nn)
+    q_i = [i for i in range(N) if i not in mb.nn]
+    # the C oracle's env: neural agents as placeholder QTable slots (env_step reads the agent count, a and b only)
+    qcfg, _ = O.cfg_from_config({"agents": [a if i in q_i else dict(Q_AGENT, states=1, actions=int(a["actions"])) for i, a in enumerate(agents)],
+                                 "environment": config["environment"]}, 1, 1)
+    multi = steps = 0
+    for e in range(E):
+        # ---- snapshot, one episode on the device, the rings
+        q0, c0, s0, eps0, count0 = mb.tables_numpy().copy(), mb.counters_numpy().copy(), mb.states_numpy().copy(), list(mb.eps), list(mb.count)
+        nn0 = {i: dict(w=mb.nn[i].params.cpu().numpy().copy(), m=mb.nn[i].adam_m.cpu().numpy().copy(),
+                       v=mb.nn[i].adam_v.cpu().numpy().copy(), step=mb.nn[i].step) for i in nn_i}
+        assert mb.episode == e
+        out = mb.run(1, fused=None if path is None else path != "unfused")
+        if path == "unfused":
+            assert out["kernel"] == "unfused"
         else:
-            matched = False
-        assert matched or E > 2     # before the first network update (episode 2) everything is exact
+            assert out["kernel"] == "mixed-fused" and (path is None or out["episode_kernel"] == path), (out["kernel"], out.get("episode_kernel"))
+        ring = {}
+        for i in nn_i:
+            assert count0[i] + T <= mb.buf_len[i]                                       # (no wrap in these games)
+            ring[i] = {k: v[:, count0[i]:count0[i] + T].cpu().numpy() for k, v in mb.buf[i].items()}
+        q_ring = {i: mb.buf[i]["action"][:, :T].cpu().numpy() for i in q_i} if path == "unfused" else {}
+        q1, c1 = mb.tables_numpy(), mb.counters_numpy()
+        for g in range(G):
+            # the policies of this episode, from the snapshot parameters at the ring's prices
+            win = {}
+            for i in nn_i:
+                A = mb.nn[i].A
+                assert ring[i]["price"][g, 0] == s0[g]
+                p64, S = PR.probs64(nn0[i]["w"][g], A, ring[i]["price"][g], value_head=mb.nn[i].value_head)
+                win[i] = (p64, PR.prob_bound(p64, S, init_scale=nn0[i]["step"] == 0))
+            price = s0[g]
+            tables = {i: q0[g, mb.offsets[i]:mb.offsets[i] + mb.shapes[i][0] * mb.shapes[i][1]].reshape(mb.shapes[i]).copy() for i in q_i}
+            counters = {i: c0[g, mb.offsets[i]:mb.offsets[i] + mb.shapes[i][0] * mb.shapes[i][1]].reshape(mb.shapes[i]).astype(np.int32) for i in q_i}
+            memq = {i: [] for i in q_i}
+            rl = np.zeros(N)
+            for t in range(T):
+                xs = O.philox([t, e, g, 0], [seed, 0])
+                acts, scaled = [0] * N, [0.0] * N
+                for i in range(N):
+                    a_cfg = agents[i]
+                    lo, hi = a_cfg["action_range"]
+                    u = xs[2 * i] * 2.0 ** -32
+                    if i in q_i:
+                        nA, ns = int(a_cfg["actions"]), int(a_cfg["states"])
+                        if u < eps0[i]:
+                            acts[i] = (xs[2 * i + 1] * nA) >> 32
+                        else:
+                            acts[i] = int(np.argmax(tables[i][O.encode32(price, 10, ns)]))
+                        if i in q_ring:
+                            assert q_ring[i][g, t] == acts[i], (label, path, e, g, t)
+                        scaled[i] = O.scale(acts[i], nA, lo, hi)
+                    else:
+                        assert ring[i]["price"][g, t] == price, (label, path, e, g, t, i)
+                        a = int(ring[i]["action"][g, t])
+                        p64, bound = win[i]
+                        ok = PR.window(p64[t:t + 1], bound[t:t + 1], np.array([u], np.float32))[0]
+                        assert 0 <= a < mb.nn[i].A and ok[a], (label, path, "episode", e, "game", g, "step", t, "agent", i, "draw", u,
+                                                               "device", a, "admissible", np.flatnonzero(ok))
+                        multi += int(ok.sum() > 1); steps += 1
+                        acts[i] = a                                                     # the oracle adopts the ring's action
+                        scaled[i] = NN.scale(a, mb.nn[i].A, lo, hi)
+                nprice, rew = O.env_step(qcfg, scaled)
+                for i in nn_i:
+                    assert ring[i]["reward"][g, t] == rew[i] and ring[i]["nprice"][g, t] == nprice, (label, path, e, g, t, i)
+                for i in q_i:
+                    ns = int(agents[i]["states"])
+                    memq[i].append((O.encode64(price, 10, ns), acts[i], rew[i], O.encode64(nprice, 10, ns)))
+                rl += rew / T
+                price = nprice
+            assert mb.states_numpy()[g] == price
+            np.testing.assert_allclose(out["game_reward_log"][0, :, g], rl, rtol=1e-13)
+            for i in q_i:                                                               # QTable.train_net after every episode
+                st, ac, rw, ns = zip(*memq[i])
+                O.td_update(tables[i], counters[i], st, ac, rw, ns, float(agents[i]["alpha"]), float(agents[i]["gamma"]))
+                sl = slice(mb.offsets[i], mb.offsets[i] + tables[i].size)
+                assert np.array_equal(q1[g, sl], tables[i].ravel()), (label, path, e, g)
+                assert np.array_equal(c1[g, sl], counters[i].ravel()), (label, path, e, g)
+        for i in q_i:
+            a_cfg = agents[i]
+            assert mb.eps[i] == a_cfg["eps_end"] + (eps0[i] - a_cfg["eps_end"]) * a_cfg["eps_step"]
+        # ---- network updates: the numpy oracle's step from the snapshot on the ring's transitions
+        for i in nn_i:
+            rb, mm = mb.nn[i], int(agents[i]["min_memory"])
+            n = count0[i] + T
+            if n < mm:
+                assert rb.step == nn0[i]["step"] and mb.count[i] == n
+                assert np.array_equal(rb.params.cpu().numpy(), nn0[i]["w"])
+                continue
+            assert rb.step == nn0[i]["step"] + 1 and mb.count[i] == 0
+            full = {k: v[:, :n].cpu().numpy() for k, v in mb.buf[i].items()}
+            w1 = rb.params.cpu().numpy()
+            for g in range(G):
+                args = (nn0[i]["w"][g], nn0[i]["m"][g], nn0[i]["v"][g], nn0[i]["step"], rb.A, full["price"][g], full["action"][g], full["reward"][g])
+                if rb.value_head:
+                    ow = NN.ac_train_net(*args, full["nprice"][g], float(agents[i]["gamma"]), float(agents[i].get("entropy", 0.0)))[0]
+                else:
+                    ow = NN.train_net(*args, float(agents[i]["gamma"]), float(agents[i].get("entropy", 0.0)))[0]
+                diff = np.abs(w1[g] - ow)
+                assert (diff > 5e-6).mean() < 0.002 and diff.max() <= 4.1e-4, (label, path, e, g, i, float((diff > 5e-6).mean()), float(diff.max()))
+                assert not np.array_equal(w1[g], nn0[i]["w"][g])
+    for i in nn_i:
+        assert mb.nn[i].step >= 2
+    print("%s on %s: %d of %d sampled steps had a window of more than one action" % (label, path or "the default path", multi, steps))
+    # a condition, not a measurement: at these weight scales the window's half-width is about 1e-5 of the CDF range per
+    # boundary, so a draw falls inside one with probability ~ 2 A 1e-5 per step; a seed that breaks this says the sampler is wrong
+    assert multi < 0.01 * steps, (multi, steps)
+    return mb
+
+
+def test_qtable_vs_reinforce_game_against_composed_oracle():
+    """The reference's own pairing (QTable vs Reinforce) on run()'s default path: every step audited (see
+    _audit_neural_game).  Tables, counters, epsilon, rewards and prices exact; every sampled action inside the float64
+    mirror's window; network parameters within the per-update tolerance after each of the two updates."""
+    mb = _audit_neural_game("q_vs_reinforce21", None)
     assert mb.nn[1].step == 2 and mb.count[1] == 30
+
+
+@pytest.mark.parametrize("label,path", [
+    ("q_vs_reinforce21", "unfused"), ("q_vs_reinforce21", "wave"), ("q_vs_reinforce21", "tuple"),
+    ("q_vs_reinforce25", "unfused"), ("q_vs_reinforce25", "wave"), ("q_vs_reinforce25", "tuple"),
+    ("q_vs_reinforce32", "tuple"), ("q_vs_actorcritic", "unfused"), ("q_vs_actorcritic", "wave"),
+    ("reinforce_vs_reinforce", "wave")])
+def test_neural_game_step_audit(label, path):
+    """Whole games with sampled neural play on each path, audited step by step against the float64 mirror and the
+    composed oracle (see _audit_neural_game): QTable vs Reinforce with 21 and 25 actions on the operator loop, the general
+    fused kernel and the tuple-chain kernel; QTable vs ActorCritic; two Reinforce agents.  With 25 actions the only action
+    in the fourth DPP row is the last one, which is also the fallback, so the 32-action agents (tuple-chain kernel, and the
+    second agent of the two-network game on the general kernel) are what reaches that row in the fused samplers."""
+    mb = _audit_neural_game(label, path)
+    assert mb.episode == 5
 
 
 def test_train_one_reference_example_config(tmp_path):
@@ -832,6 +933,38 @@ def test_policy_tuple_kernel_equals_general_kernel_and_operator_loop(label, agen
             n = min(a.count[i], a.buf_len[i])
             for k in ("price", "action", "reward", "nprice"):
                 assert np.array_equal(a.buf[i][k][:, :n].cpu().numpy(), other.buf[i][k][:, :n].cpu().numpy()), (label, k)
+
+
+@pytest.mark.parametrize("kind", ["Reinforce", "ActorCritic"])
+@pytest.mark.parametrize("A", [2, 8, 9, 24, 25, 32])
+def test_policy_kernels_agree_at_the_edge_action_counts(A, kind):
+    """The in-kernel samplers at the action counts where the register layout changes (k_nn_act pads to 8 / 24 / 32, the
+    fused kernels to 24 / 32): the tuple-chain kernel == the general fused kernel == the operator loop, whose actions are
+    k_nn_act's -- the kernel tests/test_gpu_policy.py pins to the float64 mirror.  Two network updates, bit for bit."""
+    from th_rl_amd.mixed import MixedGameBatch
+    T, G, E = 10, 5, 5
+    nn_agent = dict(R_AGENT, name=kind, actions=A, min_memory=2 * T, entropy=0.01, gamma=0.98)
+    config = {"agents": [dict(Q_AGENT, min_memory=T), nn_agent], "environment": dict(ENV, max_steps=T)}
+    runs = []
+    for path in ("tuple", "wave", "unfused"):
+        mb = MixedGameBatch(config, n_games=G, dtype="float64", seed=50 + A).init_tables()
+        mb.tuple_kernel = path == "tuple"
+        out = mb.run(E, fused=path != "unfused")
+        assert (out["kernel"], out.get("episode_kernel")) == (("unfused", None) if path == "unfused" else ("mixed-fused", path))
+        runs.append((mb, out))
+    a, ra = runs[0]
+    assert a.nn[1].step == 2 and a.nn[1].A == A
+    acts = a.buf[1]["action"].cpu().numpy()
+    assert acts.min() >= 0 and acts.max() < A and (A == 2 or np.unique(acts).size > 2)
+    for other, ro in runs[1:]:
+        assert np.array_equal(ra["game_reward_log"], ro["game_reward_log"]) and np.array_equal(ra["game_action_log"], ro["game_action_log"])
+        assert np.array_equal(a.tables_numpy(), other.tables_numpy()) and np.array_equal(a.counters_numpy(), other.counters_numpy())
+        assert np.array_equal(a.states_numpy(), other.states_numpy()) and a.eps == other.eps and a.count == other.count
+        assert other.nn[1].step == 2
+        for name in ("params", "adam_m", "adam_v"):
+            assert np.array_equal(getattr(a.nn[1], name).cpu().numpy(), getattr(other.nn[1], name).cpu().numpy()), name
+        for k in ("price", "action", "reward", "nprice"):
+            assert np.array_equal(a.buf[1][k].cpu().numpy(), other.buf[1][k].cpu().numpy()), k
 
 
 @pytest.mark.parametrize("noise", [0.0, 0.2])

@@ -114,6 +114,48 @@ def test_neural_entries_after_training_and_one_game(trained):
     _check_neural_rows(one, MIXED, _policy(one), 0.0)
 
 
+@pytest.mark.parametrize("kind", ["Reinforce", "ActorCritic"])
+@pytest.mark.parametrize("A", [2, 8, 9, 24, 25, 32])
+def test_neural_strategy_and_price_probs_against_the_float64_mirror(A, kind):
+    """k_tp_neural and k_tp_probs against tests/policy_reference.py, not against the act kernel: every strategy entry
+    of the neural agent lies in the mirror's argmax set at that tuple's price, every probability of price_probs within
+    the derived bound.  Action counts at both dispatch edges and at 2 and 32; ActorCritic with a value head that is
+    far from zero behind the policy's parameters."""
+    import policy_reference as PR
+    from th_rl_amd import sampled_play as sp, tuple_play as tp
+    n = 5
+    config = {"agents": [dict(AG, actions=5, states=30), dict(RF, name=kind, actions=A)], "environment": dict(ENV)}
+    mb = _mixed(config, n_games=n, seed=17 + A, weights_seed=A)
+    vh = kind == "ActorCritic"
+    Pp = PR.n_policy_params(A)
+    w = mb.nn[1].params.cpu().numpy().copy()
+    if vh:
+        w[:, Pp:] = np.random.RandomState(A).uniform(-1, 1, (n, 257)) * 1e3
+        mb.nn[1].set_params(w)
+    tabs = tp.tables(config)
+    price, T = tabs["price"], int(tabs["T"])
+    assert T == 5 * A and mb.nn[1].P == Pp + (257 if vh else 0)
+    pol = _policy(mb)
+    probs = sp.price_probs(mb, price)[1].cpu().numpy()
+    assert pol.shape == (n, 2, T) and probs.shape == (n, T, A)
+    worst, decided = 0.0, []
+    for g in range(n):
+        p64, S = PR.probs64(w[g], A, price, value_head=vh)
+        bound = PR.prob_bound(p64, S)
+        am = PR.argmax_set(p64, bound)
+        decided.append(am.sum(axis=1) == 1)
+        assert pol[g, 1].max() < A
+        bad = np.flatnonzero(~am[np.arange(T), pol[g, 1].astype(np.int64)])
+        assert bad.size == 0, (g, bad[:5], pol[g, 1][bad[:5]], [np.flatnonzero(am[t]) for t in bad[:5]])
+        ratio = np.abs(probs[g].astype(np.float64) - p64) / bound
+        worst = max(worst, float(ratio.max()))
+        assert ratio.max() <= 1.0, (g, float(ratio.max()), np.unravel_index(ratio.argmax(), ratio.shape))
+        assert np.abs(probs[g].astype(np.float64).sum(axis=1) - 1.0).max() <= A * 2 * PR.U
+    decided = np.concatenate(decided)
+    print("A=%d %s: worst |dp| / bound %.4f, entries with one admissible action %.3f" % (A, kind, worst, decided.mean()))
+    assert decided.mean() >= 0.9, decided.mean()                       # (of the mirror: the check above decides the entry)
+
+
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 @pytest.mark.parametrize("episodes", [0, 40])
 def test_qtable_entries_equal_crossplay_extraction(dtype, episodes):
