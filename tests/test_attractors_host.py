@@ -311,10 +311,10 @@ def test_shards_combine_to_the_unsharded_run(tmp_path):
     assert len(df) == 2 and df["n_states"].tolist() == [41] * 2 and df["n_starts"].tolist() == [101] * 2
     with pytest.raises(KeyError):
         utils.attractor_games(str(tmp_path))
-    # launch.merge_attractors: the shards' files merged are the whole run's
+    # launch.merge_analysis: the shards' files merged are the whole run's
     from th_rl_amd import launch
     cfg = dict(CFG, training={"n_games": G, "attractors": True, "groups": ids.tolist(), "n_groups": 2})
-    launch.merge_attractors(cfg, str(two), 3)
+    launch.merge_analysis("attractors", cfg, str(two), 3)
     merged = at.load_games(str(two))
     for f in fields:
         assert np.array_equal(merged[f], np.asarray(full[f])), f

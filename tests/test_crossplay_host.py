@@ -299,6 +299,6 @@ def test_args_struct_and_limits_match_header():
 
 def test_docs_say_that_shards_pair_inside_themselves():
     from th_rl_amd import launch
-    for text in (launch.merge_crossplay.__doc__, xp.__doc__, open(os.path.join(ROOT, "README.md")).read(),
+    for text in (launch.merge_analysis.__doc__, xp.__doc__, open(os.path.join(ROOT, "README.md")).read(),
                  open(os.path.join(ROOT, "DESIGN.md")).read()):
         assert "inside" in text.lower() and "shard" in text.lower()

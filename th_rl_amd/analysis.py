@@ -1,0 +1,375 @@
+"""What the post-training analyses share: the one table of `training` keys (REGISTRY), the host-side helpers every
+analysis module used to carry a copy of, and the analysis methods of GameBatch and MixedGameBatch (AnalysisMethods).
+
+REGISTRY is read by trainer.train_one (parse the options before training, write the artefacts after it),
+launch (which keys merge over shards and how) and the tests; utils has `<reader>_summary` / `<reader>_games` per record.
+Order is execution order: a later analysis may read what an earlier one left (`after`).
+"""
+import collections
+import ctypes
+import importlib
+import json
+
+import numpy as np
+
+from . import _lib
+from ._lib import ThrlError
+
+QUANTILES = (0.25, 0.5, 0.75)
+
+# key         the `training` key; `<key>.json` is the analysis's summary file
+# module      the module of th_rl_amd that holds it, parse / write: the names of its option parser and artefact writer
+# reader      utils.<reader>_summary and utils.<reader>_games read the results
+# converged   honours "tables": "converged" (the writer takes q= and state0=)
+# tuple_policy  "extract": the run extracts every agent's strategy in tuple form once and the writer takes it;
+#             "use": the writer takes it when another key had it extracted
+# rows        the writer takes spec=, histograms= and budget= (response rows reduced per group)
+# merge       th_rl_amd.launch merges the shards through the module's merged() hook
+# copy        option keys the merge copies from shard 0's JSON (what only a run knows)
+# after       (keyword, earlier key) pairs: the writer takes what that key's writer returned (None when it did not run)
+Analysis = collections.namedtuple("Analysis", "key module parse write reader converged tuple_policy rows merge copy after")
+
+
+def _a(key, module, reader, parse="parse_options", write="write_artefacts", converged=False, tuple_policy=None,
+       rows=False, merge=False, copy=(), after=()):
+    return Analysis(key, module, parse, write, reader, converged, tuple_policy, rows, merge, tuple(copy), tuple(after))
+
+
+REGISTRY = (
+    _a("convergence", "convergence", "convergence", merge=True),
+    _a("deviation", "deviation", "deviation", converged=True, rows=True, merge=True, copy=("horizon_used", "tables")),
+    _a("equilibrium", "equilibrium", "equilibrium", converged=True, merge=True, copy=("tables",)),   # dev_cycle_reward.npy
+    _a("crossplay", "crossplay", "crossplay", converged=True, rows=True, merge=True,
+       copy=("horizon_used", "rounds_played", "tables")),
+    _a("attractors", "attractors", "attractor", converged=True, merge=True, copy=("tables",)),
+    _a("stationary", "stationary", "stationary", converged=True, merge=True, copy=("tables",),
+       after=(("with_attractors", "attractors"),)),
+    _a("greedy_cycles", "tuple_play", "greedy_cycle", tuple_policy="extract", rows=True),
+    _a("greedy_deviation", "tuple_analysis", "greedy_deviation", "parse_deviation_options", "write_deviation",
+       tuple_policy="extract", rows=True),
+    _a("greedy_equilibrium", "tuple_analysis", "greedy_equilibrium", "parse_equilibrium_options", "write_equilibrium",
+       tuple_policy="extract", after=(("deviation", "greedy_deviation"),)),
+    _a("greedy_attractors", "tuple_analysis", "greedy_attractor", "parse_attractor_options", "write_attractors",
+       tuple_policy="extract"),
+    _a("greedy_stationary", "tuple_stationary", "greedy_stationary", tuple_policy="extract"),
+    _a("sampled_play", "sampled_play", "sampled_play", tuple_policy="use", after=(("with_cycles", "greedy_cycles"),)),
+)
+
+
+def record(key):
+    for a in REGISTRY:
+        if a.key == key:
+            return a
+    raise KeyError("no analysis %r (known: %s)" % (key, ", ".join(a.key for a in REGISTRY)))
+
+
+def module_of(a):
+    return importlib.import_module("th_rl_amd." + a.module)
+
+
+def enabled(training, key):
+    """True when the `training` block asks for `key` (present, not null, not false)."""
+    v = training.get(key)
+    return v is not None and v is not False
+
+
+# ---------------------------------------------------------------------------------------------- summaries and JSON
+def num(x):
+    """A JSON-safe number: None for None, NaN and infinities."""
+    return None if x is None or not np.isfinite(x) else float(x)
+
+
+def mean(x):
+    x = np.asarray(x, np.float64)
+    return num(x.mean()) if x.size else None
+
+
+def frac(mask):
+    return num(mask.mean()) if mask.size else None
+
+
+def quantiles(row, name, x):
+    """row[<name>_q25 / q50 / q75] = the QUANTILES of x (None without values)."""
+    x = np.asarray(x, np.float64)
+    qs = np.quantile(x, QUANTILES) if x.size else [None] * len(QUANTILES)
+    for qq, v in zip(QUANTILES, qs):
+        row["%s_q%d" % (name, int(round(qq * 100)))] = num(v)
+
+
+def save_json(path, content):
+    with open(path, "w") as f:
+        json.dump(content, f, indent=2)
+
+
+def combine(parts, other=None, only=None):
+    """Per-game arrays of disjoint shards (in global game order) as one run's: concatenated along the game axis, the
+    last one, except for the fields of `other` (field -> axis); only: the fields kept (default all)."""
+    parts = list(parts)
+    other = other or {}
+    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=other.get(f, -1))
+            for f in parts[0] if only is None or f in only}
+
+
+# ---------------------------------------------------------------------------------------------- options
+def check_qtable_only(config, key, follow_up):
+    """ValueError for a config with neural agents (the QTable analyses need every agent's greedy table)."""
+    kinds = [a.get("name", "QTable") for a in config["agents"]]
+    if any(k != "QTable" for k in kinds):
+        raise ValueError("training.%s: agents %s: %s" % (key, kinds, follow_up))
+
+
+def options(key, opt, defaults, tables=False):
+    """training.<key> (true or a dict) -> dict(defaults) updated with it; ValueError for another type, for a key that
+    is neither in `defaults` nor (with tables) "tables", and for a "tables" other than "final" or "converged"."""
+    name = "training." + key
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict):
+        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
+    known = set(defaults) | ({"tables"} if tables else set())
+    bad = set(opt) - known
+    if bad:
+        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(known))))
+    out = dict(defaults)
+    out.update(opt)
+    if "tables" in out and out["tables"] not in ("final", "converged"):
+        raise ValueError("%s.tables must be 'final' or 'converged', got %r" % (name, out["tables"]))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- device arguments
+def state0_tensor(batch, state0, G, what):
+    """The start prices of the first G games (matches) as a contiguous device float64 tensor [G]: the batch's state
+    for None, else the first G of a tensor or array."""
+    import torch
+    dev = batch.device
+    if state0 is None:
+        return batch.state[:G].contiguous()
+    if isinstance(state0, torch.Tensor):
+        s0 = state0.to(device=dev, dtype=torch.float64).reshape(-1)[:G].contiguous()
+    else:
+        s0 = torch.from_numpy(np.ascontiguousarray(np.asarray(state0, np.float64).reshape(-1)[:G])).to(dev)
+    if s0.numel() != G:
+        raise ThrlError("%s: state0 must hold %d prices" % (what, G))
+    return s0
+
+
+def tables_tensor(batch, q, what):
+    """batch.q for None, else q checked to be shaped, typed and placed like it."""
+    if q is None:
+        return batch.q
+    if tuple(q.shape) != tuple(batch.q.shape) or q.dtype != batch.q.dtype or q.device != batch.q.device \
+            or not q.is_contiguous():
+        raise ThrlError("%s: q must be a contiguous %s tensor %s on %s"
+                        % (what, batch.q.dtype, tuple(batch.q.shape), batch.device))
+    return q
+
+
+def is_policy(x, shape, dev, more_games=False):
+    """True for a contiguous 16-bit integer tensor of `shape` on `dev` (more_games: the first axis may be longer)."""
+    import torch
+    got = tuple(x.shape)
+    same = len(got) == len(shape) and got[1:] == tuple(shape[1:]) and \
+        (got[0] >= shape[0] if more_games else got[0] == shape[0])
+    return same and x.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)) and x.device == dev \
+        and x.is_contiguous()
+
+
+def check_policy(batch, x, shape, what, name="policy", more_games=False):
+    if not is_policy(x, shape, batch.state.device, more_games):
+        raise ThrlError("%s: %s must be a contiguous 16-bit integer tensor %s on %s" % (what, name, shape, batch.device))
+    return x
+
+
+def n_states(batch, call, args):
+    """S of the batch's config (include/thrl.h "States") from the library's own plan: `call` with `args` (its n_games
+    set) and no tables; no device work."""
+    s = ctypes.c_int32(-1)
+    args.n_states = ctypes.pointer(s)
+    rc = getattr(batch.L, call)(ctypes.byref(batch.cfg), None, ctypes.byref(args), None)
+    if s.value < 0:
+        _lib.check(rc, call)
+    return int(s.value)
+
+
+# ---------------------------------------------------------------------------------------------- the batch methods
+class AnalysisMethods:
+    """The analysis methods of GameBatch and MixedGameBatch.  The QTable analyses (deviation, equilibrium, crossplay,
+    attractors, stationary, track_convergence) read the tables, which both classes lay out alike; a MixedGameBatch with a
+    neural agent raises ThrlError there, and its greedy_* / sampled_play methods are the ones for any mix of QTable,
+    Reinforce and ActorCritic agents.  Tables, counters, state, epsilon and the episode index are never touched."""
+
+    def _qtable_only(self, method, follow_up):
+        kinds = getattr(self, "kinds", None)            # a GameBatch has QTable agents only
+        if kinds and any(k != "QTable" for k in kinds):
+            raise ThrlError("%s.%s: agents %s: %s" % (type(self).__name__, method, kinds, follow_up))
+
+    def _ready(self):
+        if not self.initialized:
+            raise ThrlError("%s: call init_tables() or set_tables() first" % type(self).__name__)
+
+    def deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, state0=None,
+                  rows=False, group_stats=None, budget=None):
+        """Deviation analysis of every game's greedy policies (thrl_deviation; definitions in include/thrl.h):
+        the pre-shock cycle (mu, lam, cycle_reward / cycle_action [N, G]), deviator `deviator` playing `action`
+        ("best_response" or an action index) for dev_len of `steps` periods, and the response (mu_post, lam_post,
+        ret_step, act_dev, gain [G]).  horizon: None = min(prod n_actions + 1, 65536); state0 [G]: the start prices
+        (default: the batch's state); the per-game sweep gamma discounts the gain.  Returns a dict of numpy arrays;
+        rows=True adds reward_rows / action_rows [steps, N, G]; group_stats (a GroupSpec): the rows are reduced on
+        the device in tau-chunks and the raw statistics [steps, n_groups, Q, ...] are returned under "group_stats"."""
+        from . import deviation as dv
+        self._qtable_only("deviation", dv.NEURAL_FOLLOW_UP)
+        self._ready()
+        return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
+                      state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
+
+    def equilibrium(self, agents=None, state0=None, policies=False, tol=0.0):
+        """Equilibrium check of every game's greedy strategies (thrl_equilibrium; definitions in include/thrl.h): for
+        each agent in `agents` (default all) the exact best response to the others' greedy strategies, and whether
+        its own is one.  Returns a dict of numpy arrays: mu, lam [G] (deviation's, default horizon); iters,
+        n_diff_all, n_diff_on, loss_all, loss_on, loss_all_mean, loss_on_mean, v_on [N, G]; the host-side flags
+        br_on, br_all [N, G], nash, perfect [G] for the tolerance `tol` (loss <= tol; 0.0 = exact); n_states, agents.
+        policies=True adds br_policy (uint16), v_opt, v_pi [N, G, S].  state0 [G]: the start prices (default: the
+        batch's state); the per-game sweep gamma is each game's discount factor."""
+        from . import equilibrium as eq
+        self._qtable_only("equilibrium", eq.NEURAL_FOLLOW_UP)
+        self._ready()
+        return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
+
+    def crossplay(self, seats, steps=0, horizon=None, state0=None, rows=False, group_stats=None, q=None, policy=None,
+                  budget=None):
+        """Cross-play of the greedy policies (thrl_crossplay; definitions in include/thrl.h): in match m of a round
+        `seats` (int [N, M], or a list of rounds, e.g. crossplay.pairings) seat i is taken by agent i of game
+        seats[i][m]; returns mu, lam [M] and cycle_reward / cycle_action [N, M] of the cycle their greedy play ends in
+        (a leading round axis for a list), from the start prices state0 [M] (default: the state of seat 0's game).
+        Every game's greedy policy is extracted once and all rounds are played from it; policy (a device [G, P]
+        16-bit tensor such as a convergence tracker's) is played as it is.  steps K > 0 with rows=True adds the path's
+        reward_rows / action_rows [K, N, M]; group_stats (a GroupSpec with G = M) pools the rows of all rounds on the
+        device.  Identity seats give deviation's mu, lam, cycle_reward, cycle_action."""
+        from . import crossplay as xp
+        self._qtable_only("crossplay", xp.NEURAL_FOLLOW_UP)
+        self._ready()
+        return xp.run(self, seats, steps=steps, horizon=horizon, state0=state0, rows=rows, group_stats=group_stats,
+                      q=q, policy=policy, budget=budget or xp.ROW_BUDGET)
+
+    def attractors(self, state0=None, policies=False, q=None, policy=None, reset=True, n_games=None):
+        """Attractor analysis of the greedy strategies (thrl_attractors; definitions in include/thrl.h): ALL limit
+        cycles of every game's greedy map on the state set and their basins, where deviation follows the one
+        path from the training state.  Returns a dict of numpy arrays: n_attr, mu_max, n_cycle_states [G]; the 8
+        attractors with the largest basins as rep, lam, basin [8, G] and cycle_reward, cycle_action [8, N, G] (slots
+        past n_attr: rep = -1 and zeros); the attractor of the training state, rep_x0, mu_x0, slot_x0 [G] (mu_x0 and
+        that slot's lam are deviation's mu and lam); with reset=True (the environment's reset distribution,
+        attractors.starts; False skips it, a (rows, w) pair replaces it) reset_mass [8, G], reset_mass_other [G] and
+        reset_reward [N, G], the exact expectation of greedy play from a reset; n_states.  policies=True adds state_rep,
+        state_mu (uint16) [G, S].  state0 [G]: the training states (default: the batch's state).  The greedy policies
+        are extracted once from the tables (or from q); policy (a device [G, P] 16-bit tensor such as a convergence
+        tracker's, or crossplay.extract's) is analysed as it is.  n_games: only the first n_games games."""
+        from . import attractors as at
+        self._qtable_only("attractors", at.NEURAL_FOLLOW_UP)
+        self._ready()
+        return at.run(self, state0=state0, policies=policies, q=q, policy=policy, reset=reset, n_games=n_games)
+
+    def stationary(self, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters=8192, pi=False, q=None,
+                   policy=None, n_games=None):
+        """Greedy play under demand noise (thrl_stationary; definitions in include/thrl.h): the long-run distribution
+        of every game's noisy greedy play over the price cells (attractors.starts), by lazy power iteration of its
+        Markov chain, and what that distribution earns.  Returns a dict of numpy arrays: iters (steps taken; max_iters
+        = the tolerance was not reached, -1 = not solved), change, mass [G], stat_reward, stat_action [N, G], stat_price
+        [G], noise_prob [G] (the values analysed), n_cells, max_iters; pi=True adds pi [G, J].  noise_prob: the
+        probability of a redrawn intercept per step, a number in (0, 1] or [G] values; None = the batch's per-game sweep
+        array if it has one, else the config's value (ThrlError if that is 0); it need not be the one the games were
+        trained with.  start: "reset" (the environment's reset distribution) or "state" (the unit mass on the cell of
+        state0 [G], default the batch's state).  tol, max_iters: the stopping rule.  The greedy policies are extracted
+        once from the tables (or from q); policy (a device [G, P] 16-bit tensor such as a convergence tracker's, or
+        crossplay.extract's) is analysed as it is.  n_games: only the first n_games games."""
+        from . import stationary as sn
+        self._qtable_only("stationary", sn.NEURAL_FOLLOW_UP)
+        self._ready()
+        return sn.run(self, noise_prob=noise_prob, start=start, state0=state0, tol=tol, max_iters=max_iters, pi=pi, q=q,
+                      policy=policy, n_games=n_games)
+
+    def greedy_cycles(self, seats=None, start=None, steps=0, rows=False, horizon=None, tuple_policy=None,
+                      group_stats=None, budget=None):
+        """The limit cycle of greedy play for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_play.run):
+        every agent's strategy as a table over the game's action tuples (thrl_tuple_policy), then a walk on tuple
+        indices (thrl_tuple_walk).  seats (default: every game's own agents) re-seat agents across games as
+        crossplay does; start (default: the tuple whose price is the state of seat 0's game, -1 when the state is
+        no tuple's price: that match gets mu = -1).  A batch with a CAC agent raises ValueError."""
+        from . import tuple_play as tp
+        self._ready()
+        return tp.run(self, seats=seats, start=start, steps=steps, rows=rows, horizon=horizon,
+                      tuple_policy=tuple_policy, group_stats=group_stats, budget=budget or tp.ROW_BUDGET)
+
+    def greedy_deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, start=None,
+                         rows=False, group_stats=None, tuple_policy=None, budget=None):
+        """The deviation test for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.deviation,
+        thrl_tuple_deviation): deviation's outputs on the strategies in tuple form, from the start tuples
+        `start` int [G] (default: the tuple whose price is the game's state; -1 = none, the game is refused with
+        mu = -1).  tuple_policy: the strategies of tuple_play.extract() (default: extracted here).  The gain is
+        discounted by the per-game sweep gamma, else by the deviator's own gamma.  A batch with a CAC agent or more than
+        4096 action tuples raises ValueError."""
+        from . import tuple_analysis as ta
+        self._ready()
+        return ta.deviation(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
+                            start=start, rows=rows, group_stats=group_stats, tuple_policy=tuple_policy,
+                            budget=budget or ta.dv.ROW_BUDGET)
+
+    def greedy_equilibrium(self, agents=None, start=None, policies=False, tol=0.0, tuple_policy=None):
+        """The equilibrium check for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.equilibrium,
+        thrl_tuple_equilibrium): equilibrium's outputs with the game's T action tuples as the state set
+        (n_states = T; policies=True adds br_policy, v_opt, v_pi [N, G, T]).  start and tuple_policy as in
+        greedy_deviation; a game without a start tuple has mu = -1 and NaN on-path outputs.  A batch with a CAC agent
+        or more than 4096 action tuples raises ValueError."""
+        from . import tuple_analysis as ta
+        self._ready()
+        return ta.equilibrium(self, agents=agents, start=start, policies=policies, tol=tol, tuple_policy=tuple_policy)
+
+    def greedy_attractors(self, start=None, weights="uniform", policies=False, tuple_policy=None):
+        """The attractor analysis for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.attractors,
+        thrl_tuple_attractors): attractors' outputs with the game's T action tuples as the state set
+        (n_states = T; policies=True adds tuple_rep, tuple_mu [G, T]) and start_mass, start_mass_other, start_reward in
+        place of the reset_* fields: weights is a weight per start tuple, "uniform" = 1 / T (a start drawn uniformly over
+        action profiles, not the environment's reset distribution), None = none, or T numbers.  start and tuple_policy
+        as in greedy_deviation; a game without a start tuple has rep_x0 = mu_x0 = slot_x0 = -1.  A batch with a CAC
+        agent or more than 4096 action tuples raises ValueError."""
+        from . import tuple_analysis as ta
+        self._ready()
+        return ta.attractors(self, start=start, weights=weights, policies=policies, tuple_policy=tuple_policy)
+
+    def greedy_stationary(self, noise_prob=None, start="reset", resolution=1024, tol=1e-12, max_iters=8192, pi=False,
+                          tuple_policy=None, cell_policy=None, n_games=None, tabs=None):
+        """Greedy play under demand noise for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_stationary.run,
+        thrl_price_policy + thrl_tuple_stationary): the long-run distribution over the tuple played and what it earns --
+        stationary's outputs with pi [G, T] over the action tuples, plus n_switch and unresolved [G]: a network's
+        strategy is sampled at the midpoints of `resolution` uniform cells of the price axis (beside the QTable agents'
+        breakpoints), and unresolved is the share of the axis on which that sampling may be wrong.  start: "reset", "state"
+        (the tuple played at the state the batch holds) or int [G] start tuples.  A batch with a CAC agent or more than
+        4096 action tuples or cells raises ValueError."""
+        from . import tuple_stationary as ts
+        self._ready()
+        return ts.run(self, noise_prob=noise_prob, start=start, resolution=resolution, tol=tol, max_iters=max_iters, pi=pi,
+                      tuple_policy=tuple_policy, cell_policy=cell_policy, n_games=n_games, tabs=tabs)
+
+    def sampled_play(self, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None,
+                     tuple_policy=None, probs=None, dpolicy=None, tabs=None):
+        """The exact long-run profit of SAMPLED play (sampled_play.run, thrl_price_probs + thrl_sampled_chain): every
+        agent plays the way it was trained -- a Reinforce / ActorCritic agent samples its softmax, a QTable agent is
+        epsilon-greedy (epsilon: "current" = the batch's epsilon now, a number, one per agent, or an array [N, G]) --
+        with no demand noise, so the tuple played is a Markov chain on the game's T action tuples: iters, change, mass,
+        samp_price, agree [G] (the share of steps on which every agent plays its greedy action), samp_reward,
+        samp_action [N, G], with pi the distribution [G, T].  start: "uniform", "state" or int [G] start tuples.  A batch
+        with a CAC agent or more than 4096 action tuples raises ValueError; a working set above a CU's LDS is
+        THRL_ERR_UNSUPPORTED."""
+        from . import sampled_play as sp
+        self._ready()
+        return sp.run(self, epsilon=epsilon, start=start, tol=tol, max_iters=max_iters, pi=pi, n_games=n_games,
+                      tuple_policy=tuple_policy, probs=probs, dpolicy=dpolicy, tabs=tabs)
+
+    def track_convergence(self, window, every=1, snapshot=False):
+        """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
+        its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.
+        snapshot=True keeps each game's tables and state at its convergence (one more copy of q on the device).
+        Only reads the tables."""
+        from . import convergence as cv
+        self._qtable_only("track_convergence", cv.NEURAL_FOLLOW_UP)
+        return cv.Tracker(self, window, every, snapshot)

@@ -25,18 +25,18 @@ Statistics that have no games are None.  Shards combine exactly: their per-game 
 order (combine) and summarised as one run.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from ._lib import ThrlError
+from .analysis import QUANTILES, save_json  # noqa: F401  (at.save_json stays a public name)
 from .deviation import optimal, profit_gain
 
 KEEP = _lib.ATTR_KEEP
 DEFAULTS = dict(policies=False)
-QUANTILES = (0.25, 0.5, 0.75)
 GAME_INT = ("n_attr", "mu_max", "n_cycle_states", "rep_x0", "mu_x0", "slot_x0")
 SLOT_INT = ("rep", "lam", "basin")
 SLOT_FLOAT = ("cycle_reward", "cycle_action")
@@ -48,29 +48,16 @@ NEURAL_FOLLOW_UP = ("the attractor analysis runs on QTable agents only; neural a
 
 def check_config(config):
     """ValueError for a config with neural agents (the analysis needs every agent's greedy table)."""
-    kinds = [a.get("name", "QTable") for a in config["agents"]]
-    if any(k != "QTable" for k in kinds):
-        raise ValueError("training.attractors: agents %s: %s" % (kinds, NEURAL_FOLLOW_UP))
+    an.check_qtable_only(config, "attractors", NEURAL_FOLLOW_UP)
 
 
 def parse_options(opt, config):
     """training.attractors (true or a dict) -> the dict with every key filled in: policies (store the per-state
     arrays), and tables when given."""
     check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("training.attractors must be true or a dict, got %r" % (opt,))
-    known = set(DEFAULTS) | {"tables"}
-    bad = set(opt) - known
-    if bad:
-        raise ValueError("training.attractors: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(known))))
-    out = dict(DEFAULTS)
-    out.update(opt)
+    out = an.options("attractors", opt, DEFAULTS, tables=True)
     if not isinstance(out["policies"], bool):
         raise ValueError("training.attractors.policies must be true or false, got %r" % (out["policies"],))
-    if "tables" in out and out["tables"] not in ("final", "converged"):
-        raise ValueError("training.attractors.tables must be 'final' or 'converged', got %r" % (out["tables"],))
     return out
 
 
@@ -112,14 +99,9 @@ def policy_entries(batch):
 
 def n_states(batch):
     """S of the batch's config (include/thrl.h "States"), from the library's own plan."""
-    s = ctypes.c_int32(-1)
     a = _lib.AttractorsArgs()
     a.n_games = 1
-    a.n_states = ctypes.pointer(s)
-    rc = batch.L.thrl_attractors(ctypes.byref(batch.cfg), None, ctypes.byref(a), None)
-    if s.value < 0:
-        _lib.check(rc, "thrl_attractors")
-    return int(s.value)
+    return an.n_states(batch, "thrl_attractors", a)
 
 
 def run(batch, state0=None, policies=False, q=None, policy=None, reset=True, n_games=None):
@@ -137,28 +119,16 @@ def run(batch, state0=None, policies=False, q=None, policy=None, reset=True, n_g
     given = policy is not None
     P = policy_entries(batch)
     if given:
-        if policy.dim() != 2 or policy.shape[0] < G or policy.shape[1] != P or policy.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) \
-                or policy.device != batch.q.device or not policy.is_contiguous():
-            raise ThrlError("attractors: policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, P), dev))
-    elif q is None:
-        q = batch.q
-    elif tuple(q.shape) != tuple(batch.q.shape) or q.dtype != batch.q.dtype or q.device != batch.q.device \
-            or not q.is_contiguous():
-        raise ThrlError("attractors: q must be a contiguous %s tensor %s on %s" % (batch.q.dtype, tuple(batch.q.shape), dev))
+        an.check_policy(batch, policy, (G, P), "attractors", more_games=True)
+    else:
+        q = an.tables_tensor(batch, q, "attractors")
     if reset is True:
         reset = starts(batch.config)
     S = n_states(batch)
     a = _lib.AttractorsArgs()
     a.n_games, a.flags = G, _lib.ATTR_POLICY_GIVEN if given else 0
     with torch.cuda.device(dev):
-        if state0 is None:
-            s0 = batch.state[:G].contiguous()
-        elif isinstance(state0, torch.Tensor):
-            s0 = state0.to(device=dev, dtype=torch.float64).reshape(-1)[:G].contiguous()
-        else:
-            s0 = torch.from_numpy(np.ascontiguousarray(np.asarray(state0, np.float64).reshape(-1)[:G])).to(dev)
-        if s0.numel() != G:
-            raise ThrlError("attractors: state0 must hold %d prices" % G)
+        s0 = an.state0_tensor(batch, state0, G, "attractors")
         if not given:
             policy = torch.empty((G, P), dtype=torch.int16, device=dev)
         i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
@@ -194,22 +164,6 @@ def run(batch, state0=None, policies=False, q=None, policy=None, reset=True, n_g
 
 
 # ---------------------------------------------------------------------------------------------- host side
-def _num(x):
-    return None if x is None or not np.isfinite(x) else float(x)
-
-
-def _mean(x):
-    x = np.asarray(x, np.float64)
-    return _num(x.mean()) if x.size else None
-
-
-def _quantiles(row, name, x):
-    x = np.asarray(x, np.float64)
-    qs = np.quantile(x, QUANTILES) if x.size else [None] * len(QUANTILES)
-    for qq, v in zip(QUANTILES, qs):
-        row["%s_q%d" % (name, int(round(qq * 100)))] = _num(v)
-
-
 def train_slot_values(games, field):
     """field [KEEP, ..., G] at every game's training slot -> [..., G]; NaN where the training attractor is not kept."""
     x = np.asarray(games[field], np.float64)
@@ -242,16 +196,16 @@ def summarize(games, ids, n_groups, nash, cartel):
     for k in range(int(n_groups)):
         m = ids == k
         kept = m & (slot >= 0)
-        row = {"group": k, "games": int(m.sum()), "single": _mean(n_attr[m] == 1) if m.any() else None}
-        _quantiles(row, "n_attr", n_attr[m])
+        row = {"group": k, "games": int(m.sum()), "single": an.mean(n_attr[m] == 1) if m.any() else None}
+        an.quantiles(row, "n_attr", n_attr[m])
         row["n_attr_max"] = int(n_attr[m].max()) if m.any() else None
-        _quantiles(row, "mu_max", mu_max[m])
-        row["delta_train_mean"] = _mean(gn["train"][kept])
-        row["delta_largest_mean"] = _mean(gn["largest"][m])
-        row["delta_reset_mean"] = _mean(gn["reset"][m]) if gn["reset"] is not None else None
-        row["train_is_largest"] = _mean(slot[m] == 0) if m.any() else None
-        _quantiles(row, "train_mass", mass[kept] if mass is not None else [])
-        row["luck_mean"] = _mean(gn["train"][kept] - gn["reset"][kept]) if gn["reset"] is not None else None
+        an.quantiles(row, "mu_max", mu_max[m])
+        row["delta_train_mean"] = an.mean(gn["train"][kept])
+        row["delta_largest_mean"] = an.mean(gn["largest"][m])
+        row["delta_reset_mean"] = an.mean(gn["reset"][m]) if gn["reset"] is not None else None
+        row["train_is_largest"] = an.mean(slot[m] == 0) if m.any() else None
+        an.quantiles(row, "train_mass", mass[kept] if mass is not None else [])
+        row["luck_mean"] = an.mean(gn["train"][kept] - gn["reset"][kept]) if gn["reset"] is not None else None
         out.append(row)
     return out
 
@@ -259,19 +213,13 @@ def summarize(games, ids, n_groups, nash, cartel):
 def combine(parts):
     """Per-game arrays of disjoint shards (in global game order) as one run's: concatenated along the game axis (axis
     0 of the per-state [G, S] arrays, the last axis of the others)."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=0 if f in STATE_FIELDS else -1) for f in parts[0]}
+    return an.combine(parts, other=dict.fromkeys(STATE_FIELDS, 0))
 
 
 def describe(options, n_states, n_starts, nash, cartel, summary):
     """attractors.json's content."""
     return {"options": options, "n_states": int(n_states), "n_starts": int(n_starts), "keep": KEEP, "nash": nash,
             "cartel": cartel, "quantiles": list(QUANTILES), "summary": summary}
-
-
-def save_json(path, content):
-    with open(path, "w") as f:
-        json.dump(content, f, indent=2)
 
 
 # ---------------------------------------------------------------------------------------------- artefacts
@@ -304,6 +252,14 @@ def load_games(d):
         st = np.load(os.path.join(d, "attr_state.npy"))
         g.update(state_rep=st[0], state_mu=st[1])
     return g
+
+
+def merged(shards, out, config, opt, ids, n_groups, first):
+    """attractors.json and attr_*.npy of a sharded run (launch.merge_analysis)."""
+    games = combine(load_games(s) for s in shards)
+    save_games(out, games)
+    nash, cartel = optimal(config)
+    return describe(opt, first["n_states"], first["n_starts"], nash, cartel, summarize(games, ids, n_groups, nash, cartel))
 
 
 def write_artefacts(exp_path, batch, config, opt, ids, n_groups, q=None, state0=None):

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ThrlError
+from .analysis import AnalysisMethods
 
 _KERNELS = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "wave": _lib.KERNEL_WAVE,
             # the wave kernel with its code variant pinned (same results; include/thrl.h)
@@ -37,7 +38,7 @@ def _require_gpu(device):
     return torch.device(device)
 
 
-class GameBatch:
+class GameBatch(AnalysisMethods):
     def __init__(self, config, n_games=1, device="cuda:0", dtype="float32", seed=0, game_offset=0,
                  kernel="auto", counters=True, sweep=None):
         self.L = _lib.load()
@@ -270,166 +271,7 @@ class GameBatch:
             return mr.cpu().numpy(), ma.cpu().numpy(), st
         return mr.cpu().numpy(), ma.cpu().numpy()
 
-    def deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, state0=None,
-                  rows=False, group_stats=None, budget=None):
-        """Deviation analysis of every game's greedy policies (thrl_deviation; definitions in include/thrl.h):
-        the pre-shock cycle (mu, lam, cycle_reward / cycle_action [N, G]), deviator `deviator` playing `action`
-        ("best_response" or an action index) for dev_len of `steps` periods, and the response (mu_post, lam_post,
-        ret_step, act_dev, gain [G]).  horizon: None = min(prod n_actions + 1, 65536); state0 [G]: the start prices
-        (default: the batch's state); the per-game sweep gamma discounts the gain.  Returns a dict of numpy arrays;
-        rows=True adds reward_rows / action_rows [steps, N, G]; group_stats (a GroupSpec): the rows are reduced on
-        the device in tau-chunks and the raw statistics [steps, n_groups, Q, ...] are returned under "group_stats".
-        Tables, counters, state, epsilon and the episode index are not touched."""
-        from . import deviation as dv
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
-                      state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
-
-    def equilibrium(self, agents=None, state0=None, policies=False, tol=0.0):
-        """Equilibrium check of every game's greedy strategies (thrl_equilibrium; definitions in include/thrl.h): for
-        each agent in `agents` (default all) the exact best response to the others' greedy strategies, and whether
-        its own is one.  Returns a dict of numpy arrays: mu, lam [G] (GameBatch.deviation's, default horizon); iters,
-        n_diff_all, n_diff_on, loss_all, loss_on, loss_all_mean, loss_on_mean, v_on [N, G]; the host-side flags
-        br_on, br_all [N, G], nash, perfect [G] for the tolerance `tol` (loss <= tol; 0.0 = exact); n_states, agents.
-        policies=True adds br_policy (uint16), v_opt, v_pi [N, G, S].  state0 [G]: the start prices (default: the
-        batch's state); the per-game sweep gamma is each game's discount factor.  Tables, counters, state, epsilon
-        and the episode index are not touched."""
-        from . import equilibrium as eq
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
-
-    def crossplay(self, seats, steps=0, horizon=None, state0=None, rows=False, group_stats=None, q=None, policy=None,
-                  budget=None):
-        """Cross-play of the greedy policies (thrl_crossplay; definitions in include/thrl.h): in match m of a round
-        `seats` (int [N, M], or a list of rounds, e.g. crossplay.pairings) seat i is taken by agent i of game
-        seats[i][m]; returns mu, lam [M] and cycle_reward / cycle_action [N, M] of the cycle their greedy play ends in
-        (a leading round axis for a list), from the start prices state0 [M] (default: the state of seat 0's game).
-        Every game's greedy policy is extracted once and all rounds are played from it; policy (a device [G, P]
-        16-bit tensor such as a convergence tracker's) is played as it is.  steps K > 0 with rows=True adds the path's
-        reward_rows / action_rows [K, N, M]; group_stats (a GroupSpec with G = M) pools the rows of all rounds on the
-        device.  Identity seats give GameBatch.deviation's mu, lam, cycle_reward, cycle_action.  Tables, counters,
-        state, epsilon and the episode index are not touched."""
-        from . import crossplay as xp
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return xp.run(self, seats, steps=steps, horizon=horizon, state0=state0, rows=rows, group_stats=group_stats,
-                      q=q, policy=policy, budget=budget or xp.ROW_BUDGET)
-
-    def attractors(self, state0=None, policies=False, q=None, policy=None, reset=True, n_games=None):
-        """Attractor analysis of the greedy strategies (thrl_attractors; definitions in include/thrl.h): ALL limit
-        cycles of every game's greedy map on the state set and their basins, where GameBatch.deviation follows the one
-        path from the training state.  Returns a dict of numpy arrays: n_attr, mu_max, n_cycle_states [G]; the 8
-        attractors with the largest basins as rep, lam, basin [8, G] and cycle_reward, cycle_action [8, N, G] (slots
-        past n_attr: rep = -1 and zeros); the attractor of the training state, rep_x0, mu_x0, slot_x0 [G] (mu_x0 and
-        that slot's lam are GameBatch.deviation's mu and lam); with reset=True (the environment's reset distribution,
-        attractors.starts; False skips it, a (rows, w) pair replaces it) reset_mass [8, G], reset_mass_other [G] and
-        reset_reward [N, G], the exact expectation of greedy play from a reset; n_states.  policies=True adds state_rep,
-        state_mu (uint16) [G, S].  state0 [G]: the training states (default: the batch's state).  The greedy policies
-        are extracted once from the tables (or from q); policy (a device [G, P] 16-bit tensor such as a convergence
-        tracker's, or crossplay.extract's) is analysed as it is.  n_games: only the first n_games games.  Tables,
-        counters, state, epsilon and the episode index are not touched."""
-        from . import attractors as at
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return at.run(self, state0=state0, policies=policies, q=q, policy=policy, reset=reset, n_games=n_games)
-
-    def stationary(self, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters=8192, pi=False, q=None,
-                   policy=None, n_games=None):
-        """Greedy play under demand noise (thrl_stationary; definitions in include/thrl.h): the long-run distribution
-        of every game's noisy greedy play over the price cells (attractors.starts), by lazy power iteration of its
-        Markov chain, and what that distribution earns.  Returns a dict of numpy arrays: iters (steps taken; max_iters
-        = the tolerance was not reached, -1 = not solved), change, mass [G], stat_reward, stat_action [N, G], stat_price
-        [G], noise_prob [G] (the values analysed), n_cells, max_iters; pi=True adds pi [G, J].  noise_prob: the
-        probability of a redrawn intercept per step, a number in (0, 1] or [G] values; None = the batch's per-game sweep
-        array if it has one, else the config's value (ThrlError if that is 0); it need not be the one the games were
-        trained with.  start: "reset" (the environment's reset distribution) or "state" (the unit mass on the cell of
-        state0 [G], default the batch's state).  tol, max_iters: the stopping rule.  The greedy policies are extracted
-        once from the tables (or from q); policy (a device [G, P] 16-bit tensor such as a convergence tracker's, or
-        crossplay.extract's) is analysed as it is.  n_games: only the first n_games games.  Tables, counters, state,
-        epsilon and the episode index are not touched."""
-        from . import stationary as sn
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return sn.run(self, noise_prob=noise_prob, start=start, state0=state0, tol=tol, max_iters=max_iters, pi=pi, q=q,
-                      policy=policy, n_games=n_games)
-
-    def greedy_deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, start=None,
-                         rows=False, group_stats=None, tuple_policy=None, budget=None):
-        """The deviation test for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.deviation,
-        thrl_tuple_deviation): GameBatch.deviation's outputs on the strategies in tuple form, from the start tuples
-        `start` int [G] (default: the tuple whose price is the game's state; -1 = none, the game is refused with
-        mu = -1).  tuple_policy: the strategies of tuple_play.extract() (default: extracted here).  The gain is
-        discounted by the per-game sweep gamma, else by the deviator's own gamma.  A batch with a CAC agent or more than
-        4096 action tuples raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_analysis as ta
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return ta.deviation(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
-                            start=start, rows=rows, group_stats=group_stats, tuple_policy=tuple_policy,
-                            budget=budget or ta.dv.ROW_BUDGET)
-
-    def greedy_equilibrium(self, agents=None, start=None, policies=False, tol=0.0, tuple_policy=None):
-        """The equilibrium check for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.equilibrium,
-        thrl_tuple_equilibrium): GameBatch.equilibrium's outputs with the game's T action tuples as the state set
-        (n_states = T; policies=True adds br_policy, v_opt, v_pi [N, G, T]).  start and tuple_policy as in
-        greedy_deviation; a game without a start tuple has mu = -1 and NaN on-path outputs.  A batch with a CAC agent
-        or more than 4096 action tuples raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_analysis as ta
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return ta.equilibrium(self, agents=agents, start=start, policies=policies, tol=tol, tuple_policy=tuple_policy)
-
-    def greedy_attractors(self, start=None, weights="uniform", policies=False, tuple_policy=None):
-        """The attractor analysis for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.attractors,
-        thrl_tuple_attractors): GameBatch.attractors' outputs with the game's T action tuples as the state set
-        (n_states = T; policies=True adds tuple_rep, tuple_mu [G, T]) and start_mass, start_mass_other, start_reward in
-        place of the reset_* fields: weights is a weight per start tuple, "uniform" = 1 / T (a start drawn uniformly over
-        action profiles, not the environment's reset distribution), None = none, or T numbers.  start and tuple_policy
-        as in greedy_deviation; a game without a start tuple has rep_x0 = mu_x0 = slot_x0 = -1.  A batch with a CAC
-        agent or more than 4096 action tuples raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_analysis as ta
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return ta.attractors(self, start=start, weights=weights, policies=policies, tuple_policy=tuple_policy)
-
-    def greedy_stationary(self, noise_prob=None, start="reset", resolution=1024, tol=1e-12, max_iters=8192, pi=False,
-                          tuple_policy=None, cell_policy=None, n_games=None, tabs=None):
-        """Greedy play under demand noise for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_stationary.run,
-        thrl_price_policy + thrl_tuple_stationary): the long-run distribution over the tuple played and what it earns --
-        GameBatch.stationary's outputs with pi [G, T] over the action tuples, plus n_switch and unresolved [G]: a network's
-        strategy is sampled at the midpoints of `resolution` uniform cells of the price axis (beside the QTable agents'
-        breakpoints), and unresolved is the share of the axis on which that sampling may be wrong.  start: "reset", "state"
-        (the tuple played at the state the batch holds) or int [G] start tuples.  A batch with a CAC agent or more than
-        4096 action tuples or cells raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_stationary as ts
-        if not self.initialized:
-            raise ThrlError("GameBatch: call init_tables() or set_tables() first")
-        return ts.run(self, noise_prob=noise_prob, start=start, resolution=resolution, tol=tol, max_iters=max_iters, pi=pi,
-                      tuple_policy=tuple_policy, cell_policy=cell_policy, n_games=n_games, tabs=tabs)
-
-    def sampled_play(self, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None,
-                     tuple_policy=None, probs=None, dpolicy=None, tabs=None):
-        """The exact long-run profit of SAMPLED play (sampled_play.run, thrl_price_probs + thrl_sampled_chain): every
-        agent plays the way it was trained -- a Reinforce / ActorCritic agent samples its softmax, a QTable agent is
-        epsilon-greedy (epsilon: "current" = the batch's epsilon now, a number, one per agent, or an array [N, G]) --
-        with no demand noise, so the tuple played is a Markov chain on the game's T action tuples: iters, change, mass,
-        samp_price, agree [G] (the share of steps on which every agent plays its greedy action), samp_reward,
-        samp_action [N, G], with pi the distribution [G, T].  start: "uniform", "state" or int [G] start tuples.  A batch
-        with a CAC agent or more than 4096 action tuples raises ValueError; a working set above a CU's LDS is
-        THRL_ERR_UNSUPPORTED.  Nothing of the batch is written."""
-        from . import sampled_play as sp
-        return sp.run(self, epsilon=epsilon, start=start, tol=tol, max_iters=max_iters, pi=pi, n_games=n_games,
-                      tuple_policy=tuple_policy, probs=probs, dpolicy=dpolicy, tabs=tabs)
-
-    def track_convergence(self, window, every=1, snapshot=False):
-        """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
-        its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.
-        snapshot=True keeps each game's tables and state at its convergence (one more copy of q on the device).
-        Only reads the tables."""
-        from .convergence import Tracker
-        return Tracker(self, window, every, snapshot)
+    # deviation, equilibrium, crossplay, attractors, stationary, greedy_*, sampled_play, track_convergence: AnalysisMethods
 
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self):

@@ -30,18 +30,18 @@ Statistics that have no games are None.  Shards combine exactly: their per-game 
 order (combine) and summarised as one run.
 """
 import ctypes
-import json
 import math
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from ._lib import ThrlError
+from .analysis import QUANTILES, save_json  # noqa: F401  (cv.save_json stays a public name)
 
 DEFAULTS = dict(window=None, every=20, stop=None, snapshot=False)
 PERIODS = 100000                # Calvano et al.: 100,000 periods without a change of any greedy strategy
-QUANTILES = (0.25, 0.5, 0.75)
 FILES = {"converged_at": "conv_episode.npy", "conv_since": "conv_since.npy", "stable_since": "conv_stable_since.npy",
          "changes": "conv_changes.npy"}
 NEURAL_FOLLOW_UP = ("convergence tracking runs on QTable agents only; neural agents (greedy = argmax pi) are a "
@@ -50,9 +50,7 @@ NEURAL_FOLLOW_UP = ("convergence tracking runs on QTable agents only; neural age
 
 def check_config(config):
     """ValueError for a config with neural agents (the rule needs every agent's greedy table)."""
-    kinds = [a.get("name", "QTable") for a in config["agents"]]
-    if any(k != "QTable" for k in kinds):
-        raise ValueError("training.convergence: agents %s: %s" % (kinds, NEURAL_FOLLOW_UP))
+    an.check_qtable_only(config, "convergence", NEURAL_FOLLOW_UP)
 
 
 def default_window(config):
@@ -65,15 +63,7 @@ def parse_options(opt, config):
     """training.convergence (true or a dict) -> the dict with every key filled in: window W (episodes, default
     default_window), every (episodes between checks), stop (None or a fraction in (0, 1]), snapshot (bool)."""
     check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("training.convergence must be true or a dict, got %r" % (opt,))
-    bad = set(opt) - set(DEFAULTS)
-    if bad:
-        raise ValueError("training.convergence: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(DEFAULTS))))
-    out = dict(DEFAULTS)
-    out.update(opt)
+    out = an.options("convergence", opt, DEFAULTS)
     if out["window"] is None:
         out["window"] = default_window(config)
     for k in ("window", "every"):
@@ -212,15 +202,9 @@ class Tracker:
 
 
 # ---------------------------------------------------------------------------------------------- host side
-def _num(x):
-    return None if x is None or not np.isfinite(x) else float(x)
-
-
 def _stats(x, prefix):
-    out = {prefix + "_mean": _num(x.mean()) if x.size else None}
-    qs = np.quantile(x, QUANTILES) if x.size else [None] * len(QUANTILES)
-    for q, v in zip(QUANTILES, qs):
-        out["%s_q%d" % (prefix, round(q * 100))] = _num(v) if v is not None else None
+    out = {prefix + "_mean": an.mean(x)}
+    an.quantiles(out, prefix, x)
     return out
 
 
@@ -237,19 +221,18 @@ def summarize(games, ids, n_groups, window, episode_end):
         m = ids == k
         n = int(m.sum())
         c = m & (ca >= 0)
-        r = {"group": k, "games": n, "converged": int(c.sum()), "fraction": _num(c.sum() / n) if n else None}
+        r = {"group": k, "games": n, "converged": int(c.sum()), "fraction": an.num(c.sum() / n) if n else None}
         r.update(_stats(ca[c].astype(np.float64), "converged_at"))
         r.update(_stats(cs[c].astype(np.float64), "conv_since"))
         r["still_stable"] = int(np.sum(m & (int(episode_end) - ss >= int(window))))
-        r["changes_mean"] = _num(ch[m].mean()) if n else None
+        r["changes_mean"] = an.num(ch[m].mean()) if n else None
         out.append(r)
     return out
 
 
 def combine(parts):
     """Per-game arrays of disjoint shards (in global game order) as one run's: concatenated along the game axis."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=-1) for f in parts[0]}
+    return an.combine(parts)
 
 
 def describe(options, every, episodes_run, episode_end, stopped_early, summary):
@@ -257,11 +240,6 @@ def describe(options, every, episodes_run, episode_end, stopped_early, summary):
     return {"options": options, "every_used": int(every), "episodes_run": int(episodes_run),
             "episode_end": int(episode_end), "stopped_early": bool(stopped_early), "quantiles": list(QUANTILES),
             "summary": summary}
-
-
-def save_json(path, content):
-    with open(path, "w") as f:
-        json.dump(content, f, indent=2)
 
 
 def load_games(d):
@@ -286,7 +264,16 @@ def truncate_rows(path, rows):
     os.replace(tmp, path)
 
 
-def write_artefacts(exp_path, tracker, opt, every, ids, n_groups, episodes_run, stopped_early):
+def merged(shards, out, config, opt, ids, n_groups, first):
+    """convergence.json and conv_*.npy of a sharded run (launch.merge_analysis); what only a run knows (every_used,
+    episodes_run, episode_end, stopped_early) is shard 0's: every rank stops at the same episode."""
+    games = combine(load_games(s) for s in shards)
+    save_games(out, games)
+    summary = summarize(games, ids, n_groups, opt["window"], first["episode_end"])
+    return describe(opt, first["every_used"], first["episodes_run"], first["episode_end"], first["stopped_early"], summary)
+
+
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tracker, every, episodes_run, stopped_early):
     """train_one's training.convergence outputs: the conv_*.npy per-game arrays, convergence.json and convergence.pt."""
     games = tracker.to_numpy()
     save_games(exp_path, games)

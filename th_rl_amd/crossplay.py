@@ -24,13 +24,14 @@ tables of other ranks are not fetched -- so a sharded run's pairings are not the
 global game ids, so the merged files describe themselves.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from ._lib import ThrlError
+from .analysis import save_json  # noqa: F401  (xp.save_json stays a public name)
 from .deviation import LAM_BINS, QUANTILES, ROW_BUDGET, default_horizon, lam_bin_names, optimal, profit_gain
 
 DEFAULTS = dict(rounds=8, scheme="rotate", against="own", steps=0, horizon=None, seed=0)
@@ -43,25 +44,14 @@ NEURAL_FOLLOW_UP = ("cross-play runs on QTable agents only; neural agents (greed
 
 def check_config(config):
     """ValueError for a config with neural agents (cross-play needs every agent's greedy table)."""
-    kinds = [a.get("name", "QTable") for a in config["agents"]]
-    if any(k != "QTable" for k in kinds):
-        raise ValueError("training.crossplay: agents %s: %s" % (kinds, NEURAL_FOLLOW_UP))
+    an.check_qtable_only(config, "crossplay", NEURAL_FOLLOW_UP)
 
 
 def parse_options(opt, config):
     """training.crossplay (true or a dict) -> the dict with every key filled in: rounds, scheme, against, steps (the
     length of the response rows, 0 = none), horizon (None = deviation.default_horizon), seed, and tables when given."""
     check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("training.crossplay must be true or a dict, got %r" % (opt,))
-    known = set(DEFAULTS) | {"tables"}
-    bad = set(opt) - known
-    if bad:
-        raise ValueError("training.crossplay: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(known))))
-    out = dict(DEFAULTS)
-    out.update(opt)
+    out = an.options("crossplay", opt, DEFAULTS, tables=True)
     for k in ("rounds", "steps", "seed"):
         if isinstance(out[k], bool) or not isinstance(out[k], (int, np.integer)):
             raise ValueError("training.crossplay.%s must be an integer, got %r" % (k, out[k]))
@@ -80,8 +70,6 @@ def parse_options(opt, config):
         out["horizon"] = int(out["horizon"])
         if not 1 <= out["horizon"] <= _lib.DEV_MAX_HORIZON:
             raise ValueError("training.crossplay.horizon=%d out of [1, %d]" % (out["horizon"], _lib.DEV_MAX_HORIZON))
-    if "tables" in out and out["tables"] not in ("final", "converged"):
-        raise ValueError("training.crossplay.tables must be 'final' or 'converged', got %r" % (out["tables"],))
     return out
 
 
@@ -152,21 +140,11 @@ def policy_entries(batch):
     return sum(int(batch.cfg.n_states[i]) + 1 for i in range(batch.N))
 
 
-def _tables(batch, q):
-    if q is None:
-        return batch.q
-    if tuple(q.shape) != tuple(batch.q.shape) or q.dtype != batch.q.dtype or q.device != batch.q.device \
-            or not q.is_contiguous():
-        raise ThrlError("crossplay: q must be a contiguous %s tensor %s on %s"
-                        % (batch.q.dtype, tuple(batch.q.shape), batch.device))
-    return q
-
-
 def extract(batch, q=None):
     """The greedy policies of every game of `batch` (or of the tables q) as a device int16 tensor [G, P] holding
     uint16 entries, the layout of thrl_policy_track: thrl_crossplay's extraction pass with one throw-away match."""
     import torch
-    q = _tables(batch, q)
+    q = an.tables_tensor(batch, q, "crossplay")
     dev = batch.device
     with torch.cuda.device(dev):
         pol = torch.empty((batch.G, policy_entries(batch)), dtype=torch.int16, device=dev)
@@ -222,12 +200,9 @@ def run(batch, seats, steps=0, horizon=None, state0=None, rows=False, group_stat
     dev = batch.device
     given = policy is not None
     if given:
-        P = policy_entries(batch)
-        if tuple(policy.shape) != (G, P) or policy.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or policy.device != batch.q.device \
-                or not policy.is_contiguous():
-            raise ThrlError("crossplay: policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, P), dev))
+        an.check_policy(batch, policy, (G, policy_entries(batch)), "crossplay")
     else:
-        q = _tables(batch, q)
+        q = an.tables_tensor(batch, q, "crossplay")
     a = _lib.CrossplayArgs()
     a.n_games, a.n_matches, a.n_steps, a.horizon = G, M, K, H
     res = {f: [] for f in ("mu", "lam", "cycle_reward", "cycle_action")}
@@ -236,12 +211,7 @@ def run(batch, seats, steps=0, horizon=None, state0=None, rows=False, group_stat
         if not given:
             policy = torch.empty((G, policy_entries(batch)), dtype=torch.int16, device=dev)
         a.policy = policy.data_ptr()
-        s0 = None
-        if state0 is not None:
-            if isinstance(state0, torch.Tensor):
-                s0 = state0.to(device=dev, dtype=torch.float64).reshape(M).contiguous()
-            else:
-                s0 = torch.from_numpy(np.ascontiguousarray(np.asarray(state0, np.float64).reshape(M))).to(dev)
+        s0 = None if state0 is None else an.state0_tensor(batch, state0, M, "crossplay")
         st = group_stats.zeros(K, dev) if group_stats is not None and K > 0 else None
         chunk = max(1, min(K, int(budget) // (8 * N * M))) if want else 0
         for r, s in enumerate(rounds):
@@ -296,10 +266,6 @@ def run(batch, seats, steps=0, horizon=None, state0=None, rows=False, group_stat
 
 
 # ---------------------------------------------------------------------------------------------- host side
-def _num(x):
-    return None if x is None or not np.isfinite(x) else float(x)
-
-
 def summarize(games, self_play, ids, n_groups, nash, cartel):
     """The summary rows, one per (group A of seat 0, group B of the partners) in A-major order.  games: seats
     [R, N, M] (indices into `ids` and into self_play's game axis), mu, lam [R, M], cycle_reward [R, N, M];
@@ -332,16 +298,16 @@ def summarize(games, self_play, ids, n_groups, nash, cartel):
             qs = np.quantile(dk, QUANTILES) if dk.size else [None] * len(QUANTILES)
             both = cyc & (self_lam[seats[:, 0]] > 0)
             ds = self_delta[seats[:, 0]][both]
-            d_mean = _num(dk.mean()) if dk.size else None
-            s_mean = _num(ds.mean()) if ds.size else None
+            d_mean = an.num(dk.mean()) if dk.size else None
+            s_mean = an.num(ds.mean()) if ds.size else None
             gains = []
             for i in range(N):
                 ok = cyc & (self_lam[seats[:, i]] > 0)
                 diff = cr[:, i][ok] - self_cr[i][seats[:, i]][ok]
-                gains.append(_num(diff.mean()) if diff.size else None)
+                gains.append(an.num(diff.mean()) if diff.size else None)
             out.append({"group": ga, "partner_group": gb, "matches": int(m.sum()), "cycles": int(cyc.sum()),
                         "fixed_points": int(np.sum(lk == 1)), "lam_hist": hist, "delta_mean": d_mean,
-                        "delta_q25": _num(qs[0]), "delta_q50": _num(qs[1]), "delta_q75": _num(qs[2]),
+                        "delta_q25": an.num(qs[0]), "delta_q50": an.num(qs[1]), "delta_q75": an.num(qs[2]),
                         "delta_self_mean": s_mean,
                         "retained": d_mean / s_mean if d_mean is not None and s_mean is not None and s_mean > 0 else None,
                         "seat_gain": gains})
@@ -354,19 +320,13 @@ GAME_FILES = ("seats", "mu", "lam", "cycle_reward", "cycle_action")
 def combine(parts):
     """Per-match arrays of disjoint shards as one run's: concatenated along the match (= game) axis.  `seats` must hold
     global ids (load_games), so that they index the concatenation (local_seats)."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=-1) for f in parts[0]}
+    return an.combine(parts)
 
 
 def describe(options, nash, cartel, summary):
     """crossplay.json's content."""
     return {"options": options, "nash": nash, "cartel": cartel, "lam_bins": lam_bin_names(),
             "quantiles": list(QUANTILES), "summary": summary}
-
-
-def save_json(path, content):
-    with open(path, "w") as f:
-        json.dump(content, f, indent=2)
 
 
 # ---------------------------------------------------------------------------------------------- artefacts
@@ -409,6 +369,18 @@ def analyse(batch, ids, n_groups, opt, state0=None, q=None, policy=None, group_s
     return games, self_play
 
 
+def merged(shards, out, config, opt, ids, n_groups, first):
+    """crossplay.json and xplay_*.npy of a sharded run (launch.merge_analysis).  Every shard drew its partners INSIDE
+    the shard -- the tables of other ranks are not fetched -- so these are not the pairings of the unsharded run; the
+    saved seats are global game ids, so the merged files say who met whom."""
+    loaded = [load_games(s) for s in shards]
+    games, self_play = combine(g for g, _ in loaded), combine(s for _, s in loaded)
+    save_games(out, games, self_play)
+    nash, cartel = optimal(config)
+    offset = int(config.get("training", {}).get("game_offset", 0))
+    return describe(opt, nash, cartel, summarize(local_seats(games, offset), self_play, ids, n_groups, nash, cartel))
+
+
 def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=ROW_BUDGET,
                     q=None, state0=None):
     """train_one's training.crossplay outputs: the xplay_*.npy files, with a spec and steps > 0 the response rows'
@@ -422,11 +394,7 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, hist
     off = int(batch.game_offset)
     save_games(exp_path, dict(games, seats=games["seats"].astype(np.int64) + off), self_play)
     if spec is not None and opt["steps"] > 0:
-        files = trainer.group_stats_files(exp_path, "xplay", opt["steps"], spec, histograms)
-        trainer.write_group_stats(files, 0, games["group_stats"], spec.describe())
-        for arr in files.values():
-            if hasattr(arr, "flush"):
-                arr.flush()
+        trainer.save_group_stats(exp_path, "xplay", games["group_stats"], spec, histograms)
     summary = summarize(games, self_play, ids, n_groups, nash, cartel)
     opt = dict(opt, horizon_used=int(games["horizon"]), rounds_played=int(games["seats"].shape[0]))
     save_json(os.path.join(exp_path, "crossplay.json"), describe(opt, nash, cartel, summary))

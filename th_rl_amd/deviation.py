@@ -21,14 +21,15 @@ Statistics that have no games are None.  Shards combine exactly: their per-game 
 order (combine) and summarised as one run.
 """
 import ctypes
-import json
 import os
 import types
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from ._lib import ThrlError
+from .analysis import save_json  # noqa: F401  (dv.save_json stays a public name)
 
 DEFAULTS = dict(steps=32, dev_len=1, action="best_response", horizon=None)
 ROW_BUDGET = 256 << 20          # bytes per device row buffer and chunk (trainer.GAME_LOG_BUDGET)
@@ -57,9 +58,7 @@ def default_horizon(n_actions):
 
 def check_config(config):
     """ValueError for a config with neural agents (the analysis needs every agent's greedy table)."""
-    kinds = [a.get("name", "QTable") for a in config["agents"]]
-    if any(k != "QTable" for k in kinds):
-        raise ValueError("training.deviation: agents %s: %s" % (kinds, NEURAL_FOLLOW_UP))
+    an.check_qtable_only(config, "deviation", NEURAL_FOLLOW_UP)
 
 
 def action_index(action):
@@ -76,16 +75,7 @@ def parse_options(opt, config):
     steps K, dev_len L, action ('best_response' or an index), horizon (None = default_horizon)."""
     check_config(config)
     n = len(config["agents"])
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("training.deviation must be true or a dict, got %r" % (opt,))
-    known = {"agents", "steps", "dev_len", "action", "horizon", "tables"}
-    bad = set(opt) - known
-    if bad:
-        raise ValueError("training.deviation: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(known))))
-    out = dict(DEFAULTS, agents=list(range(n)))
-    out.update(opt)
+    out = an.options("deviation", opt, dict(DEFAULTS, agents=list(range(n))), tables=True)
     out["agents"] = [int(d) for d in out["agents"]]
     if not out["agents"] or any(not 0 <= d < n for d in out["agents"]):
         raise ValueError("training.deviation.agents %r: deviators must lie in [0, %d)" % (out["agents"], n))
@@ -102,8 +92,6 @@ def parse_options(opt, config):
         out["horizon"] = int(out["horizon"])
         if not 1 <= out["horizon"] <= _lib.DEV_MAX_HORIZON:
             raise ValueError("training.deviation.horizon=%d out of [1, %d]" % (out["horizon"], _lib.DEV_MAX_HORIZON))
-    if "tables" in out and out["tables"] not in ("final", "converged"):
-        raise ValueError("training.deviation.tables must be 'final' or 'converged', got %r" % (out["tables"],))
     return out
 
 
@@ -124,21 +112,12 @@ def run(batch, deviator=0, steps=32, dev_len=1, action="best_response", horizon=
     if group_stats is not None and group_stats.G != G:
         raise ThrlError("group_stats spec is for %d games, this batch has %d" % (group_stats.G, G))
     dev = batch.device
-    if q is None:
-        q = batch.q
-    elif tuple(q.shape) != tuple(batch.q.shape) or q.dtype != batch.q.dtype or q.device != batch.q.device \
-            or not q.is_contiguous():
-        raise ThrlError("deviation: q must be a contiguous %s tensor %s on %s" % (batch.q.dtype, tuple(batch.q.shape), dev))
+    q = an.tables_tensor(batch, q, "deviation")
     a = _lib.DeviationArgs()
     a.n_games, a.deviator, a.dev_len, a.n_steps, a.horizon = G, int(deviator), L, K, H
     a.dev_action = action_index(action)
     with torch.cuda.device(dev):
-        if state0 is None:
-            s0 = batch.state
-        elif isinstance(state0, torch.Tensor):
-            s0 = state0.to(device=dev, dtype=torch.float64).reshape(G).contiguous()
-        else:
-            s0 = torch.from_numpy(np.ascontiguousarray(np.asarray(state0, np.float64).reshape(G))).to(dev)
+        s0 = an.state0_tensor(batch, state0, G, "deviation")
         out = {f: torch.zeros((G,), dtype=torch.int32, device=dev) for f in INT_FIELDS}
         out.update(cycle_reward=torch.zeros((N, G), dtype=torch.float64, device=dev),
                    cycle_action=torch.zeros((N, G), dtype=torch.float64, device=dev),
@@ -204,10 +183,6 @@ def profit_gain(cycle_reward, nash, cartel):
     return (tot - float(nash)) / (float(cartel) - float(nash))
 
 
-def _num(x):
-    return None if x is None or not np.isfinite(x) else float(x)
-
-
 def summarize(games, ids, n_groups, nash, cartel, deviator):
     """One dict per group for one deviator: games = dict of per-game arrays (INT_FIELDS, gain [G], cycle_reward
     [N, G]) in global game order, ids = group id per game."""
@@ -227,28 +202,22 @@ def summarize(games, ids, n_groups, nash, cartel, deviator):
         out.append({"group": k, "deviator": int(deviator), "games": int(m.sum()), "cycles": int(np.sum(lk > 0)),
                     "fixed_points": int(np.sum(lk == 1)), "returned": int(np.sum(rk >= 0)),
                     "unprofitable": int(np.sum(gk < 0)), "lam_hist": hist,
-                    "ret_step_mean": _num(rk[rk >= 0].mean()) if np.any(rk >= 0) else None,
-                    "delta_mean": _num(dk.mean()) if dk.size else None,
-                    "delta_q25": _num(qs[0]), "delta_q50": _num(qs[1]), "delta_q75": _num(qs[2]),
-                    "gain_mean": _num(gk.mean()) if gk.size else None})
+                    "ret_step_mean": an.num(rk[rk >= 0].mean()) if np.any(rk >= 0) else None,
+                    "delta_mean": an.num(dk.mean()) if dk.size else None,
+                    "delta_q25": an.num(qs[0]), "delta_q50": an.num(qs[1]), "delta_q75": an.num(qs[2]),
+                    "gain_mean": an.num(gk.mean()) if gk.size else None})
     return out
 
 
 def combine(parts):
     """Per-game arrays of disjoint shards (in global game order) as one run's: concatenated along the game axis."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=-1) for f in parts[0]}
+    return an.combine(parts)
 
 
 def describe(options, nash, cartel, summary):
     """deviation.json's content."""
     return {"options": options, "nash": nash, "cartel": cartel, "lam_bins": lam_bin_names(),
             "quantiles": list(QUANTILES), "summary": summary}
-
-
-def save_json(path, content):
-    with open(path, "w") as f:
-        json.dump(content, f, indent=2)
 
 
 # ---------------------------------------------------------------------------------------------- artefacts
@@ -260,6 +229,16 @@ def load_games(d, deviator):
             "act_dev": post[3], "gain": np.load(os.path.join(d, "dev%d_gain.npy" % deviator)),
             "cycle_reward": np.load(os.path.join(d, "dev_cycle_reward.npy")),
             "cycle_action": np.load(os.path.join(d, "dev_cycle_action.npy"))}
+
+
+def merged(shards, out, config, opt, ids, n_groups, first):
+    """deviation.json of a sharded run (launch.merge_analysis): per deviator the shards' arrays concatenated in global
+    game order and summarised as one run."""
+    nash, cartel = optimal(config)
+    summary = []
+    for d in opt["agents"]:
+        summary += summarize(combine(load_games(s, d) for s in shards), ids, n_groups, nash, cartel, d)
+    return describe(opt, nash, cartel, summary)
 
 
 def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=ROW_BUDGET,
@@ -281,11 +260,7 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, hist
                 np.stack([r["mu_post"], r["lam_post"], r["ret_step"], r["act_dev"]]).astype(np.int32))
         np.save(os.path.join(exp_path, "dev%d_gain.npy" % d), r["gain"])
         if spec is not None:
-            files = trainer.group_stats_files(exp_path, "dev%d" % d, opt["steps"], spec, histograms)
-            trainer.write_group_stats(files, 0, r["group_stats"], spec.describe())
-            for arr in files.values():
-                if hasattr(arr, "flush"):
-                    arr.flush()
+            trainer.save_group_stats(exp_path, "dev%d" % d, r["group_stats"], spec, histograms)
         summary += summarize(r, ids, n_groups, nash, cartel, d)
     opt = dict(opt, horizon_used=int(r["horizon"]))
     save_json(os.path.join(exp_path, "deviation.json"), describe(opt, nash, cartel, summary))

@@ -23,18 +23,18 @@ those games).  Statistics that have no games are None.  Shards combine exactly: 
 in global game order (combine) and summarised as one run.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from ._lib import ThrlError
+from .analysis import QUANTILES, save_json  # noqa: F401  (eq.save_json stays a public name)
 
 DEFAULTS = dict(tol=0.0, policies=False)
 INT_FIELDS = ("iters", "n_diff_all", "n_diff_on")
 FLOAT_FIELDS = ("loss_all", "loss_on", "loss_all_mean", "loss_on_mean", "v_on")
-QUANTILES = (0.25, 0.5, 0.75)
 COLLUSIVE_GAIN = 0.5
 NEURAL_FOLLOW_UP = ("the equilibrium check runs on QTable agents only; neural agents (greedy = argmax pi) are a "
                     "follow-up on the mixed path's policy tables")
@@ -42,9 +42,7 @@ NEURAL_FOLLOW_UP = ("the equilibrium check runs on QTable agents only; neural ag
 
 def check_config(config):
     """ValueError for a config with neural agents (the check needs every agent's greedy table)."""
-    kinds = [a.get("name", "QTable") for a in config["agents"]]
-    if any(k != "QTable" for k in kinds):
-        raise ValueError("training.equilibrium: agents %s: %s" % (kinds, NEURAL_FOLLOW_UP))
+    an.check_qtable_only(config, "equilibrium", NEURAL_FOLLOW_UP)
 
 
 def check_gamma(gammas, what="gamma"):
@@ -61,16 +59,7 @@ def parse_options(opt, config):
     agents, a gamma outside [0, 1) in the config or in training.sweep.gamma."""
     check_config(config)
     n = len(config["agents"])
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("training.equilibrium must be true or a dict, got %r" % (opt,))
-    known = {"agents", "tol", "policies", "tables"}
-    bad = set(opt) - known
-    if bad:
-        raise ValueError("training.equilibrium: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(known))))
-    out = dict(DEFAULTS, agents=list(range(n)))
-    out.update(opt)
+    out = an.options("equilibrium", opt, dict(DEFAULTS, agents=list(range(n))), tables=True)
     out["agents"] = sorted(set(int(d) for d in out["agents"]))
     if not out["agents"] or any(not 0 <= d < n for d in out["agents"]):
         raise ValueError("training.equilibrium.agents %r: agents must lie in [0, %d)" % (out["agents"], n))
@@ -78,8 +67,6 @@ def parse_options(opt, config):
     if not out["tol"] >= 0.0:
         raise ValueError("training.equilibrium.tol=%r must be >= 0" % (out["tol"],))
     out["policies"] = bool(out["policies"])
-    if "tables" in out and out["tables"] not in ("final", "converged"):
-        raise ValueError("training.equilibrium.tables must be 'final' or 'converged', got %r" % (out["tables"],))
     sweep = (config.get("training") or {}).get("sweep") or {}
     for d in out["agents"]:
         if "gamma" in sweep:
@@ -102,14 +89,9 @@ def agents_mask(agents, n):
 # ---------------------------------------------------------------------------------------------- the device call
 def n_states(batch):
     """S of the batch's config (include/thrl.h "States"), from the library's own plan; no device work."""
-    s = ctypes.c_int32(-1)
     a = _lib.EquilibriumArgs()
     a.n_games, a.agents = 1, 1
-    a.n_states = ctypes.pointer(s)
-    rc = batch.L.thrl_equilibrium(ctypes.byref(batch.cfg), None, ctypes.byref(a), None)
-    if s.value < 0:
-        _lib.check(rc, "thrl_equilibrium")
-    return int(s.value)
+    return an.n_states(batch, "thrl_equilibrium", a)
 
 
 def run(batch, agents=None, state0=None, policies=False, tol=0.0, q=None):
@@ -120,21 +102,12 @@ def run(batch, agents=None, state0=None, policies=False, tol=0.0, q=None):
     G, N = batch.G, batch.N
     ag, mask = agents_mask(agents, N)
     dev = batch.device
-    if q is None:
-        q = batch.q
-    elif tuple(q.shape) != tuple(batch.q.shape) or q.dtype != batch.q.dtype or q.device != batch.q.device \
-            or not q.is_contiguous():
-        raise ThrlError("equilibrium: q must be a contiguous %s tensor %s on %s" % (batch.q.dtype, tuple(batch.q.shape), dev))
+    q = an.tables_tensor(batch, q, "equilibrium")
     S = n_states(batch)
     a = _lib.EquilibriumArgs()
     a.n_games, a.agents = G, mask
     with torch.cuda.device(dev):
-        if state0 is None:
-            s0 = batch.state
-        elif isinstance(state0, torch.Tensor):
-            s0 = state0.to(device=dev, dtype=torch.float64).reshape(G).contiguous()
-        else:
-            s0 = torch.from_numpy(np.ascontiguousarray(np.asarray(state0, np.float64).reshape(G))).to(dev)
+        s0 = an.state0_tensor(batch, state0, G, "equilibrium")
         gam = batch.sweep.get("gamma") if getattr(batch, "sweep", None) else None
         if gam is not None:
             sel = gam[ag]
@@ -176,14 +149,6 @@ def flags(games, agents, tol=0.0):
     return {"br_on": br_on, "br_all": br_all, "nash": br_on[solved].all(axis=0), "perfect": br_all[solved].all(axis=0)}
 
 
-def _num(x):
-    return None if x is None or not np.isfinite(x) else float(x)
-
-
-def _frac(mask):
-    return _num(mask.mean()) if mask.size else None
-
-
 def summarize(games, ids, n_groups, agents, tol=0.0, delta=None):
     """The summary rows: for every group one row per solved agent, then one row with agent None.  games = dict of
     per-game arrays in global game order, ids = group id per game, delta [G] = the profit gain per game or None."""
@@ -194,20 +159,17 @@ def summarize(games, ids, n_groups, agents, tol=0.0, delta=None):
     for k in range(int(n_groups)):
         m = ids == k
         for i in agents:
-            row = {"group": k, "agent": int(i), "games": int(m.sum()), "br_on": _frac(fl["br_on"][i][m]),
-                   "br_all": _frac(fl["br_all"][i][m]), "capped": int(np.sum(iters[i][m] == -1))}
+            row = {"group": k, "agent": int(i), "games": int(m.sum()), "br_on": an.frac(fl["br_on"][i][m]),
+                   "br_all": an.frac(fl["br_all"][i][m]), "capped": int(np.sum(iters[i][m] == -1))}
             for name in ("loss_on", "loss_all"):
                 x = np.asarray(games[name], np.float64)[i][m]
-                x = x[x > 0]
-                qs = np.quantile(x, QUANTILES) if x.size else [None] * len(QUANTILES)
-                for qq, v in zip(QUANTILES, qs):
-                    row["%s_q%d" % (name, int(round(qq * 100)))] = _num(v)
+                an.quantiles(row, name, x[x > 0])
             out.append(row)
-        row = {"group": k, "agent": None, "games": int(m.sum()), "nash": _frac(fl["nash"][m]),
-               "perfect": _frac(fl["perfect"][m]), "collusive": None, "nash_collusive": None, "perfect_collusive": None}
+        row = {"group": k, "agent": None, "games": int(m.sum()), "nash": an.frac(fl["nash"][m]),
+               "perfect": an.frac(fl["perfect"][m]), "collusive": None, "nash_collusive": None, "perfect_collusive": None}
         if delta is not None:
             c = m & (np.asarray(delta, np.float64) > COLLUSIVE_GAIN)
-            row.update(collusive=int(c.sum()), nash_collusive=_frac(fl["nash"][c]), perfect_collusive=_frac(fl["perfect"][c]))
+            row.update(collusive=int(c.sum()), nash_collusive=an.frac(fl["nash"][c]), perfect_collusive=an.frac(fl["perfect"][c]))
         out.append(row)
     return out
 
@@ -215,20 +177,13 @@ def summarize(games, ids, n_groups, agents, tol=0.0, delta=None):
 def combine(parts):
     """Per-game arrays of disjoint shards (in global game order) as one run's: concatenated along the game axis
     (axis 1 of the per-state [N, G, S] arrays, the last axis of the others)."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=1 if np.asarray(parts[0][f]).ndim == 3 else -1)
-            for f in parts[0]}
+    return an.combine(parts, other={"br_policy": 1, "v_opt": 1, "v_pi": 1})
 
 
 def describe(options, n_states, summary):
     """equilibrium.json's content."""
     return {"options": options, "n_states": int(n_states), "quantiles": list(QUANTILES),
             "collusive_gain": COLLUSIVE_GAIN, "summary": summary}
-
-
-def save_json(path, content):
-    with open(path, "w") as f:
-        json.dump(content, f, indent=2)
 
 
 # ---------------------------------------------------------------------------------------------- artefacts
@@ -271,6 +226,17 @@ def load_delta(d, config):
     from . import deviation as dv
     nash, cartel = dv.optimal(config)
     return dv.profit_gain(np.load(path), nash, cartel)
+
+
+def merged(shards, out, config, opt, ids, n_groups, first):
+    """equilibrium.json and eq_*.npy of a sharded run (launch.merge_analysis); the collusive fractions where the shards
+    had the deviation analysis's cycle rewards."""
+    games = combine(load_games(s) for s in shards)
+    save_games(out, games)
+    delta = None
+    if first["summary"] and first["summary"][-1]["collusive"] is not None:
+        delta = np.concatenate([load_delta(s, config) for s in shards])
+    return describe(opt, first["n_states"], summarize(games, ids, n_groups, opt["agents"], opt["tol"], delta))
 
 
 def write_artefacts(exp_path, batch, config, opt, ids, n_groups, q=None, state0=None):

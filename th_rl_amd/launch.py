@@ -12,17 +12,14 @@ shard checkpoint `--out/shard<r>/batch.pt`, and with training.game_logs its shar
 (`game_rewards.npy`, `game_actions.npy`, `game_ids.npy` with global ids; utils.game_log finds a game there).
 With training.group_stats, group ids come from the global sweep (or training.groups) before the cut, every shard
 writes its raw per-group statistics with histograms, and rank 0 merges them exactly into the top-level
-groups.json / group_*.npy (merge_group_stats); with training.deviation every shard writes its per-game deviation
-arrays, rank 0 merges the dev<d>_* statistics the same way and writes the top-level deviation.json (merge_deviation);
-with training.equilibrium rank 0 concatenates the shards' eq_*.npy and writes equilibrium.json (merge_equilibrium);
-with training.convergence every shard writes its per-game convergence arrays and rank 0 writes the top-level
-convergence.json and conv_*.npy (merge_convergence); with training.crossplay every shard draws its partners INSIDE the
-shard (the tables of other ranks are not fetched, so a sharded run's pairings are not the unsharded run's) and saves
-the seats as global game ids; rank 0 concatenates the shards' xplay_*.npy along the game axis and writes the top-level
-crossplay.json (merge_crossplay); with training.attractors rank 0 concatenates the shards' attr_*.npy and writes
-attractors.json (merge_attractors), and with training.stationary the shards' stat_*.npy and stationary.json
-(merge_stationary).  A convergence stop counts the games of every rank (the trainer
-all-reduces over the gloo group), so all ranks stop at the same episode.
+groups.json / group_*.npy (merge_group_stats), the dev<d>_* and xplay_* statistics of training.deviation and
+training.crossplay among them.  Every analysis of analysis.REGISTRY with a merge (convergence, deviation, equilibrium,
+crossplay, attractors, stationary) is written per shard, and rank 0 concatenates the shards' per-game arrays in global
+game order and writes the top-level <key>.json and .npy files (merge_analysis); the others are refused
+(check_launch_config).  With training.crossplay every shard draws its partners INSIDE the shard (the tables of other
+ranks are not fetched, so a sharded run's pairings are not the unsharded run's) and saves the seats as global game ids.
+A convergence stop counts the games of every rank (the trainer all-reduces over the gloo group), so all ranks stop at
+the same episode.
 """
 import argparse
 import json
@@ -47,6 +44,7 @@ def shard_training(config, rank, world):
     the table dtype (train_one's default is float64 for ONE game, float32 otherwise) and the Philox
     initialisation keyed by (seed, global game id) (train_one's one-game default draws the tables
     from numpy's global RNG instead).  Pure host logic (no GPU): tests/test_host_cpu.py."""
+    from th_rl_amd import analysis
     from th_rl_amd.sharding import shard_range
     training = dict(config.get("training", {}))
     total = int(training.get("n_games", world))
@@ -70,11 +68,8 @@ def shard_training(config, rank, world):
         opt = dict(parse_options(gs))
         opt.update(histograms=True, n_max=int(numpy.bincount(ids, minlength=n_groups).max()))
         training.update(group_stats=opt, groups=ids[offset:offset + n_local].tolist(), n_groups=int(n_groups))
-    dv = training.get("deviation")
-    cv = training.get("convergence") or training.get("equilibrium") or training.get("crossplay") \
-        or training.get("attractors") or training.get("stationary")
-    if ((dv is not None and dv is not False) or (cv is not None and cv is not False)) and (gs is None or gs is False):
-        # the per-group summaries of each shard's deviation.json / convergence.json use the global group ids too
+    if any(analysis.enabled(training, a.key) for a in analysis.REGISTRY if a.merge) and (gs is None or gs is False):
+        # the per-group summaries of each shard's <key>.json use the global group ids too
         from th_rl_amd.group_stats import assign_groups
         ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
                                          n_groups=training.get("n_groups"))
@@ -122,155 +117,33 @@ def merge_group_stats(config, out, world):
             ld = lambda f: numpy.load(os.path.join(d, "%s_%s.npy" % (prefix, f)), mmap_mode="r")
             # ~key(min) / key(max) of the shard's exact extremes: the same keys the kernel stored
             parts.append({"hist": ld("hist"), "sums": ld("sums"), "minmax": _keys(ld("min"), ld("max"))})
-        raw = merge(parts)
-        files = trainer.group_stats_files(out, prefix, raw["sums"].shape[0], spec, opt["histograms"])
-        trainer.write_group_stats(files, 0, raw, desc)
-        for a in files.values():
-            if hasattr(a, "flush"):
-                a.flush()
+        trainer.save_group_stats(out, prefix, merge(parts), spec, opt["histograms"])
 
 
-def merge_deviation(config, out, world):
-    """Rank 0: the top-level deviation.json of a sharded run from the shards' per-game arrays (deviation.combine:
-    the concatenation in global game order, summarised as one run)."""
-    from th_rl_amd import deviation as dv
+def merge_analysis(key, config, out, world):
+    """Rank 0: the top-level <key>.json and per-game .npy files of a sharded run for one analysis of analysis.REGISTRY
+    that has a merge: the shards' per-game arrays concatenated in global game order and summarised as one run, by the
+    analysis module's merged() hook.  What only a run knows (the record's `copy` keys, e.g. horizon_used, or tables
+    when the run tracks convergence) is taken from shard 0's JSON.  In cross-play every shard drew its partners INSIDE
+    the shard, so the merged pairings are not those of the unsharded run (crossplay.merged)."""
+    from th_rl_amd import analysis
     from th_rl_amd.group_stats import assign_groups
+    a = analysis.record(key)
+    if not a.merge:
+        raise ValueError("training.%s has no sharded merge" % key)
+    mod = analysis.module_of(a)
     training = config.get("training", {})
     total = int(training.get("n_games", world))
-    opt = dv.parse_options(training["deviation"], config)
-    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
-                                     n_groups=training.get("n_groups"))
-    nash, cartel = dv.optimal(config)
-    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
-    summary = []
-    for d in opt["agents"]:
-        games = dv.combine(dv.load_games(s, d) for s in shards)
-        summary += dv.summarize(games, ids, n_groups, nash, cartel, d)
-    with open(os.path.join(shards[0], "deviation.json")) as f:
-        first = json.load(f)["options"]
-    opt["horizon_used"] = first["horizon_used"]
-    if "tables" in first:       # recorded when the run tracks convergence
-        opt["tables"] = first["tables"]
-    dv.save_json(os.path.join(out, "deviation.json"), dv.describe(opt, nash, cartel, summary))
-
-
-def merge_equilibrium(config, out, world):
-    """Rank 0: the top-level equilibrium.json and eq_*.npy of a sharded run from the shards' per-game arrays
-    (equilibrium.combine: the concatenation in global game order, summarised as one run)."""
-    from th_rl_amd import equilibrium as eq
-    from th_rl_amd.group_stats import assign_groups
-    training = config.get("training", {})
-    total = int(training.get("n_games", world))
-    opt = eq.parse_options(training["equilibrium"], config)
+    opt = getattr(mod, a.parse)(training[key], config)
     ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
                                      n_groups=training.get("n_groups"))
     shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
-    games = eq.combine(eq.load_games(s) for s in shards)
-    eq.save_games(out, games)
-    with open(os.path.join(shards[0], "equilibrium.json")) as f:
+    with open(os.path.join(shards[0], key + ".json")) as f:
         first = json.load(f)
-    if "tables" in first["options"]:       # recorded when the run tracks convergence
-        opt["tables"] = first["options"]["tables"]
-    delta = None
-    if first["summary"] and first["summary"][-1]["collusive"] is not None:
-        deltas = [eq.load_delta(s, config) for s in shards]
-        delta = numpy.concatenate(deltas)
-    summary = eq.summarize(games, ids, n_groups, opt["agents"], opt["tol"], delta)
-    eq.save_json(os.path.join(out, "equilibrium.json"), eq.describe(opt, first["n_states"], summary))
-
-
-def merge_crossplay(config, out, world):
-    """Rank 0: the top-level crossplay.json and xplay_*.npy of a sharded run: the shards' arrays concatenated along
-    the game axis (crossplay.combine) and summarised as one run.  Every shard drew its partners INSIDE the shard -- the
-    tables of other ranks are not fetched -- so these are not the pairings of the unsharded run; the saved seats are
-    global game ids, so the merged files say who met whom."""
-    from th_rl_amd import crossplay as xp
-    from th_rl_amd.group_stats import assign_groups
-    training = config.get("training", {})
-    total = int(training.get("n_games", world))
-    opt = xp.parse_options(training["crossplay"], config)
-    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
-                                     n_groups=training.get("n_groups"))
-    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
-    loaded = [xp.load_games(s) for s in shards]
-    games, self_play = xp.combine(g for g, _ in loaded), xp.combine(s for _, s in loaded)
-    xp.save_games(out, games, self_play)
-    with open(os.path.join(shards[0], "crossplay.json")) as f:
-        first = json.load(f)
-    for k in ("horizon_used", "rounds_played", "tables"):
+    for k in a.copy:
         if k in first["options"]:
             opt[k] = first["options"][k]
-    nash, cartel = xp.optimal(config)
-    summary = xp.summarize(xp.local_seats(games, int(training.get("game_offset", 0))), self_play, ids, n_groups,
-                           nash, cartel)
-    xp.save_json(os.path.join(out, "crossplay.json"), xp.describe(opt, nash, cartel, summary))
-
-
-def merge_attractors(config, out, world):
-    """Rank 0: the top-level attractors.json and attr_*.npy of a sharded run from the shards' per-game arrays
-    (attractors.combine: the concatenation in global game order, summarised as one run)."""
-    from th_rl_amd import attractors as at
-    from th_rl_amd.group_stats import assign_groups
-    training = config.get("training", {})
-    total = int(training.get("n_games", world))
-    opt = at.parse_options(training["attractors"], config)
-    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
-                                     n_groups=training.get("n_groups"))
-    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
-    games = at.combine(at.load_games(s) for s in shards)
-    at.save_games(out, games)
-    with open(os.path.join(shards[0], "attractors.json")) as f:
-        first = json.load(f)
-    if "tables" in first["options"]:       # recorded when the run tracks convergence
-        opt["tables"] = first["options"]["tables"]
-    nash, cartel = at.optimal(config)
-    summary = at.summarize(games, ids, n_groups, nash, cartel)
-    at.save_json(os.path.join(out, "attractors.json"),
-                 at.describe(opt, first["n_states"], first["n_starts"], nash, cartel, summary))
-
-
-def merge_stationary(config, out, world):
-    """Rank 0: the top-level stationary.json and stat_*.npy of a sharded run from the shards' per-game arrays
-    (stationary.combine: the concatenation in global game order, summarised as one run)."""
-    from th_rl_amd import stationary as sn
-    from th_rl_amd.group_stats import assign_groups
-    training = config.get("training", {})
-    total = int(training.get("n_games", world))
-    opt = sn.parse_options(training["stationary"], config)
-    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
-                                     n_groups=training.get("n_groups"))
-    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
-    games = sn.combine(sn.load_games(s) for s in shards)
-    sn.save_games(out, games)
-    with open(os.path.join(shards[0], "stationary.json")) as f:
-        first = json.load(f)
-    if "tables" in first["options"]:       # recorded when the run tracks convergence
-        opt["tables"] = first["options"]["tables"]
-    nash, cartel = sn.optimal(config)
-    rr = sn.reset_reward_of(out, total) if training.get("attractors") else None       # merge_attractors ran before
-    summary = sn.summarize(games, ids, n_groups, nash, cartel, opt["max_iters"], reset_reward=rr)
-    sn.save_json(os.path.join(out, "stationary.json"), sn.describe(opt, first["n_cells"], nash, cartel, summary))
-
-
-def merge_convergence(config, out, world):
-    """Rank 0: the top-level convergence.json and conv_*.npy of a sharded run from the shards' per-game arrays
-    (convergence.combine: the concatenation in global game order, summarised as one run)."""
-    from th_rl_amd import convergence as cv
-    from th_rl_amd.group_stats import assign_groups
-    training = config.get("training", {})
-    total = int(training.get("n_games", world))
-    opt = cv.parse_options(training["convergence"], config)
-    ids, n_groups, _ = assign_groups(total, sweep=training.get("sweep"), groups=training.get("groups"),
-                                     n_groups=training.get("n_groups"))
-    shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
-    games = cv.combine(cv.load_games(s) for s in shards)
-    cv.save_games(out, games)
-    with open(os.path.join(shards[0], "convergence.json")) as f:
-        first = json.load(f)
-    summary = cv.summarize(games, ids, n_groups, opt["window"], first["episode_end"])
-    cv.save_json(os.path.join(out, "convergence.json"),
-                 cv.describe(opt, first["every_used"], first["episodes_run"], first["episode_end"],
-                             first["stopped_early"], summary))
+    analysis.save_json(os.path.join(out, key + ".json"), mod.merged(shards, out, config, opt, ids, n_groups, first))
 
 
 def _keys(vmin, vmax):
@@ -290,7 +163,7 @@ def effective_world(config, gpus):
 def _worker(rank, world, port, config, out, devices_available):
     import torch
     import torch.distributed as dist
-    from th_rl_amd import trainer
+    from th_rl_amd import analysis, trainer
     from th_rl_amd.sharding import aggregate_logs
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
@@ -321,29 +194,19 @@ def _worker(rank, world, port, config, out, devices_available):
         pandas.concat([rpd, apd], axis=1, keys=["rewards", "actions"]).to_csv(os.path.join(out, "log.csv"), index=None)
         if training.get("group_stats"):
             merge_group_stats(config, out, world)
-        if training.get("deviation"):
-            merge_deviation(config, out, world)
-        if training.get("convergence"):
-            merge_convergence(config, out, world)
-        if training.get("equilibrium"):
-            merge_equilibrium(config, out, world)
-        if training.get("crossplay"):
-            merge_crossplay(config, out, world)
-        if training.get("attractors"):
-            merge_attractors(config, out, world)
-        if training.get("stationary"):
-            merge_stationary(config, out, world)
+        for a in analysis.REGISTRY:      # in its order: stationary reads what the attractors' merge wrote
+            if a.merge and analysis.enabled(training, a.key):
+                merge_analysis(a.key, config, out, world)
     dist.destroy_process_group()
 
 
 def check_launch_config(config):
-    """ValueError for a training key that has no sharded form: training.greedy_cycles re-seats agents across games and
-    its merge over shards is not built, nor is that of training.greedy_deviation, training.greedy_equilibrium,
-    training.greedy_attractors, training.greedy_stationary and training.sampled_play."""
-    for key in ("greedy_cycles", "greedy_deviation", "greedy_equilibrium", "greedy_attractors", "greedy_stationary",
-                "sampled_play"):
-        gc = config.get("training", {}).get(key)
-        if gc is not None and gc is not False:
+    """ValueError for a training key that has no sharded form, the records of analysis.REGISTRY without a merge:
+    training.greedy_cycles re-seats agents across games and its merge over shards is not built, nor is that of the other
+    greedy_* keys and training.sampled_play."""
+    from th_rl_amd import analysis
+    for key in (a.key for a in analysis.REGISTRY if not a.merge):
+        if analysis.enabled(config.get("training", {}), key):
             raise ValueError("training.%s is not available under th_rl_amd.launch (sharded runs are not merged); "
                              "run it through th_rl_amd.main / trainer.train_one on one device" % key)
 

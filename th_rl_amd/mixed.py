@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ThrlError
+from .analysis import AnalysisMethods
 from .batched import _require_gpu, _torch
 from .nn import ActorCriticBatch, CACBatch, ReinforceBatch
 
@@ -71,7 +72,7 @@ def check_injection(inj, E, T, N, G, kinds, noise):
     return out
 
 
-class MixedGameBatch:
+class MixedGameBatch(AnalysisMethods):
     def __init__(self, config, n_games=1, device="cuda:0", dtype="float32", seed=0, game_offset=0, sweep=None):
         self.L = _lib.load()
         torch = _torch()
@@ -295,154 +296,9 @@ class MixedGameBatch:
             return mr.cpu().numpy(), ma.cpu().numpy(), st
         return mr.cpu().numpy(), ma.cpu().numpy()
 
+    # deviation, equilibrium, crossplay, attractors, stationary, greedy_*, sampled_play, track_convergence: AnalysisMethods
+
     # ------------------------------------------------------------------ checkpoint / resume
-    def deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, state0=None,
-                  rows=False, group_stats=None, budget=None):
-        """GameBatch.deviation for an all-QTable batch (the same table layout; train_one runs small float64
-        all-QTable batches here).  A batch with a neural agent raises ThrlError."""
-        from . import deviation as dv
-        if any(k != "QTable" for k in self.kinds):
-            raise ThrlError("MixedGameBatch.deviation: agents %s: %s" % (self.kinds, dv.NEURAL_FOLLOW_UP))
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
-                      state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
-
-    def equilibrium(self, agents=None, state0=None, policies=False, tol=0.0):
-        """GameBatch.equilibrium for an all-QTable batch (the same table layout).  A batch with a neural agent
-        raises ThrlError."""
-        from . import equilibrium as eq
-        if any(k != "QTable" for k in self.kinds):
-            raise ThrlError("MixedGameBatch.equilibrium: agents %s: %s" % (self.kinds, eq.NEURAL_FOLLOW_UP))
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
-
-    def crossplay(self, seats, steps=0, horizon=None, state0=None, rows=False, group_stats=None, q=None, policy=None,
-                  budget=None):
-        """GameBatch.crossplay for an all-QTable batch (the same table layout).  A batch with a neural agent raises
-        ThrlError."""
-        from . import crossplay as xp
-        if any(k != "QTable" for k in self.kinds):
-            raise ThrlError("MixedGameBatch.crossplay: agents %s: %s" % (self.kinds, xp.NEURAL_FOLLOW_UP))
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return xp.run(self, seats, steps=steps, horizon=horizon, state0=state0, rows=rows, group_stats=group_stats,
-                      q=q, policy=policy, budget=budget or xp.ROW_BUDGET)
-
-    def attractors(self, state0=None, policies=False, q=None, policy=None, reset=True, n_games=None):
-        """GameBatch.attractors for an all-QTable batch (the same table layout).  A batch with a neural agent raises
-        ThrlError."""
-        from . import attractors as at
-        if any(k != "QTable" for k in self.kinds):
-            raise ThrlError("MixedGameBatch.attractors: agents %s: %s" % (self.kinds, at.NEURAL_FOLLOW_UP))
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return at.run(self, state0=state0, policies=policies, q=q, policy=policy, reset=reset, n_games=n_games)
-
-    def stationary(self, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters=8192, pi=False, q=None,
-                   policy=None, n_games=None):
-        """GameBatch.stationary for an all-QTable batch (the same table layout).  A batch with a neural agent raises
-        ThrlError."""
-        from . import stationary as sn
-        if any(k != "QTable" for k in self.kinds):
-            raise ThrlError("MixedGameBatch.stationary: agents %s: %s" % (self.kinds, sn.NEURAL_FOLLOW_UP))
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return sn.run(self, noise_prob=noise_prob, start=start, state0=state0, tol=tol, max_iters=max_iters, pi=pi, q=q,
-                      policy=policy, n_games=n_games)
-
-    def greedy_cycles(self, seats=None, start=None, steps=0, rows=False, horizon=None, tuple_policy=None,
-                      group_stats=None, budget=None):
-        """The limit cycle of greedy play for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_play.run):
-        every agent's strategy as a table over the game's action tuples (thrl_tuple_policy), then a walk on tuple
-        indices (thrl_tuple_walk).  seats (default: every game's own agents) re-seat agents across games as
-        crossplay does; start (default: the tuple whose price is the state of seat 0's game, -1 when the state is
-        no tuple's price: that match gets mu = -1).  A batch with a CAC agent raises ValueError."""
-        from . import tuple_play as tp
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return tp.run(self, seats=seats, start=start, steps=steps, rows=rows, horizon=horizon,
-                      tuple_policy=tuple_policy, group_stats=group_stats, budget=budget or tp.ROW_BUDGET)
-
-    def greedy_deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", horizon=None, start=None,
-                         rows=False, group_stats=None, tuple_policy=None, budget=None):
-        """The deviation test for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.deviation,
-        thrl_tuple_deviation): MixedGameBatch.deviation's outputs on the strategies in tuple form, from the start tuples
-        `start` int [G] (default: the tuple whose price is the game's state; -1 = none, the game is refused with
-        mu = -1).  tuple_policy: the strategies of tuple_play.extract() (default: extracted here).  The gain is
-        discounted by the per-game sweep gamma, else by the deviator's own gamma.  A batch with a CAC agent or more than
-        4096 action tuples raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_analysis as ta
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return ta.deviation(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
-                            start=start, rows=rows, group_stats=group_stats, tuple_policy=tuple_policy,
-                            budget=budget or ta.dv.ROW_BUDGET)
-
-    def greedy_equilibrium(self, agents=None, start=None, policies=False, tol=0.0, tuple_policy=None):
-        """The equilibrium check for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.equilibrium,
-        thrl_tuple_equilibrium): MixedGameBatch.equilibrium's outputs with the game's T action tuples as the state set
-        (n_states = T; policies=True adds br_policy, v_opt, v_pi [N, G, T]).  start and tuple_policy as in
-        greedy_deviation; a game without a start tuple has mu = -1 and NaN on-path outputs.  A batch with a CAC agent
-        or more than 4096 action tuples raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_analysis as ta
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return ta.equilibrium(self, agents=agents, start=start, policies=policies, tol=tol, tuple_policy=tuple_policy)
-
-    def greedy_attractors(self, start=None, weights="uniform", policies=False, tuple_policy=None):
-        """The attractor analysis for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.attractors,
-        thrl_tuple_attractors): MixedGameBatch.attractors' outputs with the game's T action tuples as the state set
-        (n_states = T; policies=True adds tuple_rep, tuple_mu [G, T]) and start_mass, start_mass_other, start_reward in
-        place of the reset_* fields: weights is a weight per start tuple, "uniform" = 1 / T (a start drawn uniformly over
-        action profiles, not the environment's reset distribution), None = none, or T numbers.  start and tuple_policy
-        as in greedy_deviation; a game without a start tuple has rep_x0 = mu_x0 = slot_x0 = -1.  A batch with a CAC
-        agent or more than 4096 action tuples raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_analysis as ta
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return ta.attractors(self, start=start, weights=weights, policies=policies, tuple_policy=tuple_policy)
-
-    def greedy_stationary(self, noise_prob=None, start="reset", resolution=1024, tol=1e-12, max_iters=8192, pi=False,
-                          tuple_policy=None, cell_policy=None, n_games=None, tabs=None):
-        """Greedy play under demand noise for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_stationary.run,
-        thrl_price_policy + thrl_tuple_stationary): the long-run distribution over the tuple played and what it earns --
-        MixedGameBatch.stationary's outputs with pi [G, T] over the action tuples, plus n_switch and unresolved [G]: a network's
-        strategy is sampled at the midpoints of `resolution` uniform cells of the price axis (beside the QTable agents'
-        breakpoints), and unresolved is the share of the axis on which that sampling may be wrong.  start: "reset", "state"
-        (the tuple played at the state the batch holds) or int [G] start tuples.  A batch with a CAC agent or more than
-        4096 action tuples or cells raises ValueError.  Nothing of the batch is written."""
-        from . import tuple_stationary as ts
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return ts.run(self, noise_prob=noise_prob, start=start, resolution=resolution, tol=tol, max_iters=max_iters, pi=pi,
-                      tuple_policy=tuple_policy, cell_policy=cell_policy, n_games=n_games, tabs=tabs)
-
-    def sampled_play(self, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None,
-                     tuple_policy=None, probs=None, dpolicy=None, tabs=None):
-        """The exact long-run profit of SAMPLED play (sampled_play.run, thrl_price_probs + thrl_sampled_chain): every
-        agent plays the way it was trained -- a Reinforce / ActorCritic agent samples its softmax, a QTable agent is
-        epsilon-greedy (epsilon: "current" = the batch's epsilon now, a number, one per agent, or an array [N, G]) --
-        with no demand noise, so the tuple played is a Markov chain on the game's T action tuples: iters, change, mass,
-        samp_price, agree [G] (the share of steps on which every agent plays its greedy action), samp_reward,
-        samp_action [N, G], with pi the distribution [G, T].  start: "uniform", "state" or int [G] start tuples.  A batch
-        with a CAC agent or more than 4096 action tuples raises ValueError; a working set above a CU's LDS is
-        THRL_ERR_UNSUPPORTED.  Nothing of the batch is written."""
-        from . import sampled_play as sp
-        if not self.initialized:
-            raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
-        return sp.run(self, epsilon=epsilon, start=start, tol=tol, max_iters=max_iters, pi=pi, n_games=n_games,
-                      tuple_policy=tuple_policy, probs=probs, dpolicy=dpolicy, tabs=tabs)
-
-    def track_convergence(self, window, every=1, snapshot=False):
-        """GameBatch.track_convergence for an all-QTable batch (the same table layout; train_one runs small float64
-        all-QTable batches here).  A batch with a neural agent raises ThrlError."""
-        from . import convergence as cv
-        if any(k != "QTable" for k in self.kinds):
-            raise ThrlError("MixedGameBatch.track_convergence: agents %s: %s" % (self.kinds, cv.NEURAL_FOLLOW_UP))
-        return cv.Tracker(self, window, every, snapshot)
-
     def state_dict(self):
         """Everything a continued run needs (plain tensors / numbers: loads with weights_only=True)."""
         return dict(version=2, kind="mixed", n_games=self.G, kinds=list(self.kinds), shapes=[list(x) for x in self.shapes],

@@ -17,12 +17,12 @@ agree_mean and price_mean.  Demand noise, the reset distribution as a start, sha
 agents are out of scope.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from . import stationary as sn
 from . import tuple_play as tp
 from ._lib import ThrlError
@@ -50,15 +50,7 @@ def parse_options(opt, config):
     CU's LDS."""
     name = "training.sampled_play"
     tp.check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
-    bad = set(opt) - set(DEFAULTS)
-    if bad:
-        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(DEFAULTS))))
-    out = dict(DEFAULTS)
-    out.update(opt)
+    out = an.options("sampled_play", opt, DEFAULTS)
     e = out["epsilon"]
     if isinstance(e, (list, tuple)):
         if len(e) != len(config["agents"]):
@@ -236,13 +228,12 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
         if probs is None:
             probs = price_probs(batch, tabs["dprice"], n_games=G)
         if dpolicy is None:
-            if tuple_policy is not None and ts._is_policy(tuple_policy, (batch.G, N, T), sdev):
+            if tuple_policy is not None and an.is_policy(tuple_policy, (batch.G, N, T), sdev):
                 rep = torch.from_numpy(np.asarray(tabs["grp_perm"])[np.asarray(tabs["grp_first"])[:-1]].astype(np.int64))
                 dpolicy = tuple_policy[:G].index_select(2, rep.to(sdev)).contiguous()
             else:
                 dpolicy = ts.price_policy(batch, tabs["dprice"], n_games=G)
-        if not ts._is_policy(dpolicy, (G, N, D), sdev):
-            raise ThrlError("sampled_play: dpolicy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, D), dev))
+        an.check_policy(batch, dpolicy, (G, N, D), "sampled_play", "dpolicy")
         for i, k in enumerate(kinds):
             if k == "QTable":
                 continue
@@ -315,17 +306,17 @@ def summarize(games, ids, n_groups, nash, cartel, max_iters, cycle_reward=None):
         m = ids == k
         ms = m & solved
         row = {"group": k, "games": int(m.sum()),
-               "converged": sn._mean(solved[m] & (iters[m] < int(max_iters))) if m.any() else None}
-        sn._quantiles(row, "iters", iters[ms])
+               "converged": an.mean(solved[m] & (iters[m] < int(max_iters))) if m.any() else None}
+        an.quantiles(row, "iters", iters[ms])
         row["iters_max"] = int(iters[ms].max()) if ms.any() else None
-        row["delta_sampled_mean"] = sn._mean(delta[ms])
-        sn._quantiles(row, "delta_sampled", delta[ms])
-        row["agree_mean"] = sn._mean(agree[ms])
-        row["price_mean"] = sn._mean(price[ms])
+        row["delta_sampled_mean"] = an.mean(delta[ms])
+        an.quantiles(row, "delta_sampled", delta[ms])
+        row["agree_mean"] = an.mean(agree[ms])
+        row["price_mean"] = an.mean(price[ms])
         if dgreedy is not None:
             mg = ms & has
-            row["delta_greedy_mean"] = sn._mean(dgreedy[mg])
-            row["randomness_cost_mean"] = sn._mean(dgreedy[mg] - delta[mg])
+            row["delta_greedy_mean"] = an.mean(dgreedy[mg])
+            row["randomness_cost_mean"] = an.mean(dgreedy[mg] - delta[mg])
         out.append(row)
     return out
 
@@ -333,9 +324,7 @@ def summarize(games, ids, n_groups, nash, cartel, max_iters, cycle_reward=None):
 def combine(parts):
     """Per-game arrays of disjoint sets of games (in global game order) as one run's: concatenated along the game axis
     (axis 0 of pi [G, T], the last axis of the others)."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=0 if f == "pi" else -1)
-            for f in parts[0] if f in PER_GAME}
+    return an.combine(parts, other={"pi": 0}, only=PER_GAME)
 
 
 def describe(options, T, n_prices, nash, cartel, summary):
@@ -398,6 +387,5 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=No
     nash, cartel = optimal(config)
     cyc = greedy_cycles_of(exp_path, np.asarray(r["iters"]).size) if with_cycles else None
     summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"], cycle_reward=cyc)
-    with open(os.path.join(exp_path, "sampled_play.json"), "w") as f:
-        json.dump(describe(opt, r["T"], r["n_prices"], nash, cartel, summary), f, indent=2)
+    an.save_json(os.path.join(exp_path, "sampled_play.json"), describe(opt, r["T"], r["n_prices"], nash, cartel, summary))
     return r

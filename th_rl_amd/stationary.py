@@ -23,19 +23,19 @@ are None.  Shards combine exactly: their per-game arrays are concatenated in glo
 summarised as one run.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from ._lib import ThrlError
+from .analysis import QUANTILES, save_json  # noqa: F401  (sn.save_json stays a public name)
 from .attractors import encode64, policy_entries, starts
 from .deviation import optimal, profit_gain
 
 DEFAULTS = dict(noise_prob=None, start="reset", tol=1e-12, max_iters=8192, pi=False)
 STARTS = ("reset", "state")
-QUANTILES = (0.25, 0.5, 0.75)
 GAME_FLOAT = ("change", "mass", "stat_price")
 AGENT_FLOAT = ("stat_reward", "stat_action")
 NEURAL_FOLLOW_UP = ("the stationary analysis runs on QTable agents only; neural agents (greedy = argmax pi) are a "
@@ -44,9 +44,7 @@ NEURAL_FOLLOW_UP = ("the stationary analysis runs on QTable agents only; neural 
 
 def check_config(config):
     """ValueError for a config with neural agents (the analysis needs every agent's greedy table)."""
-    kinds = [a.get("name", "QTable") for a in config["agents"]]
-    if any(k != "QTable" for k in kinds):
-        raise ValueError("training.stationary: agents %s: %s" % (kinds, NEURAL_FOLLOW_UP))
+    an.check_qtable_only(config, "stationary", NEURAL_FOLLOW_UP)
 
 
 def _check_prob(p, what):
@@ -59,16 +57,7 @@ def parse_options(opt, config):
     """training.stationary (true or a dict) -> the dict with every key filled in: noise_prob (None = the run's own),
     start ('reset' or 'state'), tol, max_iters, pi (store the distributions), and tables when given."""
     check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("training.stationary must be true or a dict, got %r" % (opt,))
-    known = set(DEFAULTS) | {"tables"}
-    bad = set(opt) - known
-    if bad:
-        raise ValueError("training.stationary: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(known))))
-    out = dict(DEFAULTS)
-    out.update(opt)
+    out = an.options("stationary", opt, DEFAULTS, tables=True)
     if out["noise_prob"] is not None:
         out["noise_prob"] = _check_prob(out["noise_prob"], "training.stationary.noise_prob")
     else:       # the run's own noise: refuse a noise-free run before training, as the batch would after it
@@ -87,8 +76,6 @@ def parse_options(opt, config):
                          % (_lib.STAT_MAX_ITERS, out["max_iters"]))
     if not isinstance(out["pi"], bool):
         raise ValueError("training.stationary.pi must be true or false, got %r" % (out["pi"],))
-    if "tables" in out and out["tables"] not in ("final", "converged"):
-        raise ValueError("training.stationary.tables must be 'final' or 'converged', got %r" % (out["tables"],))
     return out
 
 
@@ -236,15 +223,9 @@ def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters
     given = policy is not None
     P = policy_entries(batch)
     if given:
-        if policy.dim() != 2 or policy.shape[0] < G or policy.shape[1] != P \
-                or policy.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) \
-                or policy.device != batch.q.device or not policy.is_contiguous():
-            raise ThrlError("stationary: policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, P), dev))
-    elif q is None:
-        q = batch.q
-    elif tuple(q.shape) != tuple(batch.q.shape) or q.dtype != batch.q.dtype or q.device != batch.q.device \
-            or not q.is_contiguous():
-        raise ThrlError("stationary: q must be a contiguous %s tensor %s on %s" % (batch.q.dtype, tuple(batch.q.shape), dev))
+        an.check_policy(batch, policy, (G, P), "stationary", more_games=True)
+    else:
+        q = an.tables_tensor(batch, q, "stationary")
     if tabs is None:
         tabs = tables(batch.config)
     J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
@@ -269,14 +250,7 @@ def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters
         else:
             a.noise_prob = p
         if start == "state":
-            if state0 is None:
-                s0 = batch.state[:G].contiguous()
-            elif isinstance(state0, torch.Tensor):
-                s0 = state0.to(device=dev, dtype=torch.float64).reshape(-1)[:G].contiguous()
-            else:
-                s0 = torch.from_numpy(np.ascontiguousarray(np.asarray(state0, np.float64).reshape(-1)[:G])).to(dev)
-            if s0.numel() != G:
-                raise ThrlError("stationary: state0 must hold %d prices" % G)
+            s0 = an.state0_tensor(batch, state0, G, "stationary")
             a.state0 = s0.data_ptr()
         if not given:
             policy = torch.empty((G, P), dtype=torch.int16, device=dev)
@@ -302,22 +276,6 @@ def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters
 
 
 # ---------------------------------------------------------------------------------------------- host side
-def _num(x):
-    return None if x is None or not np.isfinite(x) else float(x)
-
-
-def _mean(x):
-    x = np.asarray(x, np.float64)
-    return _num(x.mean()) if x.size else None
-
-
-def _quantiles(row, name, x):
-    x = np.asarray(x, np.float64)
-    qs = np.quantile(x, QUANTILES) if x.size else [None] * len(QUANTILES)
-    for qq, v in zip(QUANTILES, qs):
-        row["%s_q%d" % (name, int(round(qq * 100)))] = _num(v)
-
-
 def summarize(games, ids, n_groups, nash, cartel, max_iters, reset_reward=None):
     """The summary rows, one per group.  games = dict of per-game arrays in global game order, ids = group id per
     game, reset_reward [N, G] = the attractor analysis's, when the run has one."""
@@ -332,15 +290,15 @@ def summarize(games, ids, n_groups, nash, cartel, max_iters, reset_reward=None):
         m = ids == k
         ms = m & solved
         row = {"group": k, "games": int(m.sum()),
-               "converged": _mean(solved[m] & (iters[m] < int(max_iters))) if m.any() else None}
-        _quantiles(row, "iters", iters[ms])
+               "converged": an.mean(solved[m] & (iters[m] < int(max_iters))) if m.any() else None}
+        an.quantiles(row, "iters", iters[ms])
         row["iters_max"] = int(iters[ms].max()) if ms.any() else None
-        row["delta_noise_mean"] = _mean(delta[ms])
-        _quantiles(row, "delta_noise", delta[ms])
-        row["price_mean"] = _mean(price[ms])
+        row["delta_noise_mean"] = an.mean(delta[ms])
+        an.quantiles(row, "delta_noise", delta[ms])
+        row["price_mean"] = an.mean(price[ms])
         if dreset is not None:
-            row["delta_reset_mean"] = _mean(dreset[ms])
-            row["noise_cost_mean"] = _mean(dreset[ms] - delta[ms])
+            row["delta_reset_mean"] = an.mean(dreset[ms])
+            row["noise_cost_mean"] = an.mean(dreset[ms] - delta[ms])
         out.append(row)
     return out
 
@@ -351,20 +309,13 @@ PER_GAME = ("iters", "noise_prob") + GAME_FLOAT + AGENT_FLOAT + ("pi",)
 def combine(parts):
     """Per-game arrays of disjoint shards (in global game order) as one run's: concatenated along the game axis (axis
     0 of pi [G, J], the last axis of the others)."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=0 if f == "pi" else -1)
-            for f in parts[0] if f in PER_GAME}
+    return an.combine(parts, other={"pi": 0}, only=PER_GAME)
 
 
 def describe(options, n_cells, nash, cartel, summary):
     """stationary.json's content."""
     return {"options": options, "n_cells": int(n_cells), "nash": nash, "cartel": cartel, "quantiles": list(QUANTILES),
             "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)", "summary": summary}
-
-
-def save_json(path, content):
-    with open(path, "w") as f:
-        json.dump(content, f, indent=2)
 
 
 # ---------------------------------------------------------------------------------------------- artefacts
@@ -399,6 +350,17 @@ def reset_reward_of(d, n_games=None):
         return None
     rr = np.load(path)
     return rr if n_games is None or (rr.ndim == 2 and rr.shape[1] == int(n_games)) else None
+
+
+def merged(shards, out, config, opt, ids, n_groups, first):
+    """stationary.json and stat_*.npy of a sharded run (launch.merge_analysis); delta_reset_mean and noise_cost_mean
+    from the attractor analysis's merged reset_reward in `out`, which that key's merge wrote before."""
+    games = combine(load_games(s) for s in shards)
+    save_games(out, games)
+    nash, cartel = optimal(config)
+    rr = reset_reward_of(out, len(ids)) if an.enabled(config.get("training", {}), "attractors") else None
+    summary = summarize(games, ids, n_groups, nash, cartel, opt["max_iters"], reset_reward=rr)
+    return describe(opt, first["n_cells"], nash, cartel, summary)
 
 
 def write_artefacts(exp_path, batch, config, opt, ids, n_groups, q=None, state0=None, with_attractors=False):

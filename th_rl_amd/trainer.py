@@ -115,7 +115,7 @@ import pandas
 
 from th_rl_amd.environments import *  # noqa: F401,F403  (class names are eval'd, as in the reference)
 from th_rl_amd.agents import *        # noqa: F401,F403
-from th_rl_amd import _lib
+from th_rl_amd import _lib, analysis
 from th_rl_amd.batched import GameBatch
 
 
@@ -200,6 +200,15 @@ def write_group_stats(files, at, raw, describe):
         arr[at:at + k] = raw[f] if f in ("sums", "hist") else fin[f]
 
 
+def save_group_stats(exp_path, prefix, raw, spec, histograms):
+    """The whole <prefix>_*.npy of one raw output: an analysis's response rows, or a sharded run's merged statistics."""
+    files = group_stats_files(exp_path, prefix, raw["sums"].shape[0], spec, histograms)
+    write_group_stats(files, 0, raw, spec.describe())
+    for arr in files.values():
+        if hasattr(arr, "flush"):
+            arr.flush()
+
+
 def group_spec_of(config, training, n_games):
     """training.group_stats -> (GroupSpec of this run's games, options) or (None, None)."""
     opt = training.get("group_stats", None)
@@ -254,63 +263,14 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     all_tabular = all(isinstance(a, QTable) for a in agents)
 
     training = config.get("training", {})
-    dev_opt = None
-    if training.get("deviation") is not None and training.get("deviation") is not False:
-        from th_rl_amd.deviation import parse_options as deviation_options
-        dev_opt = deviation_options(training["deviation"], config)     # refuses neural agents before training
-    conv_opt = None
-    if training.get("convergence") is not None and training.get("convergence") is not False:
-        from th_rl_amd.convergence import parse_options as convergence_options
-        conv_opt = convergence_options(training["convergence"], config)   # refuses neural agents before training
-    if dev_opt is not None and dev_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
-        raise ValueError('training.deviation.tables = "converged" needs training.convergence with "snapshot": true')
-    eq_opt = None
-    if training.get("equilibrium") is not None and training.get("equilibrium") is not False:
-        from th_rl_amd.equilibrium import parse_options as equilibrium_options
-        eq_opt = equilibrium_options(training["equilibrium"], config)     # refuses neural agents and gamma >= 1
-    if eq_opt is not None and eq_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
-        raise ValueError('training.equilibrium.tables = "converged" needs training.convergence with "snapshot": true')
-    xp_opt = None
-    if training.get("crossplay") is not None and training.get("crossplay") is not False:
-        from th_rl_amd.crossplay import parse_options as crossplay_options
-        xp_opt = crossplay_options(training["crossplay"], config)         # refuses neural agents before training
-    if xp_opt is not None and xp_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
-        raise ValueError('training.crossplay.tables = "converged" needs training.convergence with "snapshot": true')
-    at_opt = None
-    if training.get("attractors") is not None and training.get("attractors") is not False:
-        from th_rl_amd.attractors import parse_options as attractors_options
-        at_opt = attractors_options(training["attractors"], config)       # refuses neural agents before training
-    if at_opt is not None and at_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
-        raise ValueError('training.attractors.tables = "converged" needs training.convergence with "snapshot": true')
-    st_opt = None
-    if training.get("stationary") is not None and training.get("stationary") is not False:
-        from th_rl_amd.stationary import parse_options as stationary_options
-        st_opt = stationary_options(training["stationary"], config)       # refuses neural agents before training
-    if st_opt is not None and st_opt.get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
-        raise ValueError('training.stationary.tables = "converged" needs training.convergence with "snapshot": true')
-    gc_opt = None
-    if training.get("greedy_cycles") is not None and training.get("greedy_cycles") is not False:
-        from th_rl_amd.tuple_play import parse_options as greedy_cycle_options
-        gc_opt = greedy_cycle_options(training["greedy_cycles"], config)  # refuses CAC and too many tuples before training
-    gdev_opt = geq_opt = None
-    if training.get("greedy_deviation") is not None and training.get("greedy_deviation") is not False:
-        from th_rl_amd.tuple_analysis import parse_deviation_options
-        gdev_opt = parse_deviation_options(training["greedy_deviation"], config)   # refuses CAC and too many tuples
-    if training.get("greedy_equilibrium") is not None and training.get("greedy_equilibrium") is not False:
-        from th_rl_amd.tuple_analysis import parse_equilibrium_options
-        geq_opt = parse_equilibrium_options(training["greedy_equilibrium"], config)   # ... and gamma >= 1
-    gat_opt = None
-    if training.get("greedy_attractors") is not None and training.get("greedy_attractors") is not False:
-        from th_rl_amd.tuple_analysis import parse_attractor_options
-        gat_opt = parse_attractor_options(training["greedy_attractors"], config)      # refuses CAC and too many tuples
-    gst_opt = None
-    if training.get("greedy_stationary") is not None and training.get("greedy_stationary") is not False:
-        from th_rl_amd.tuple_stationary import parse_options as greedy_stationary_options
-        gst_opt = greedy_stationary_options(training["greedy_stationary"], config)     # refuses CAC, too many tuples / cells
-    sp_opt = None
-    if training.get("sampled_play") is not None and training.get("sampled_play") is not False:
-        from th_rl_amd.sampled_play import parse_options as sampled_play_options
-        sp_opt = sampled_play_options(training["sampled_play"], config)     # refuses CAC, too many tuples, the working set
+    opts = {}       # key -> parsed options of every analysis asked for (analysis.REGISTRY), refused before training
+    for a in analysis.REGISTRY:
+        if analysis.enabled(training, a.key):
+            opts[a.key] = getattr(analysis.module_of(a), a.parse)(training[a.key], config)
+    conv_opt = opts.get("convergence")
+    for a in analysis.REGISTRY:
+        if a.converged and opts.get(a.key, {}).get("tables") == "converged" and not (conv_opt and conv_opt["snapshot"]):
+            raise ValueError('training.%s.tables = "converged" needs training.convergence with "snapshot": true' % a.key)
     epochs = training.get("epochs", 0)
     print_freq = training.get("print_freq", 500)
     n_games = int(training.get("n_games", 1))
@@ -391,6 +351,7 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         keep = None
 
     spec, gs_opt = group_spec_of(config, training, n_games)
+    xp_opt, gc_opt = opts.get("crossplay"), opts.get("greedy_cycles")
     if spec is not None and xp_opt is not None and xp_opt["steps"] > 0:
         from th_rl_amd.crossplay import MAX_POOLED_ROUNDS
         n_rounds = xp_opt["rounds"] * (spec.n_groups if xp_opt["against"] == "all" else 1)
@@ -509,160 +470,39 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             if hasattr(arr, "flush"):
                 arr.flush()
 
-    if tracker is not None:     # the convergence arrays and their per-group summary (convergence.py)
-        from th_rl_amd.convergence import write_artefacts as write_convergence
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        write_convergence(exp_path, tracker, conv_opt, conv_every, ids, n_groups, episodes_run, stopped_early)
-
-    if dev_opt is not None:     # the greedy policies' deviation analysis (deviation.py)
-        from th_rl_amd.deviation import write_artefacts
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        q_dev = s_dev = None
-        if tracker is not None:
-            dev_opt = dict(dev_opt, tables=dev_opt.get("tables", "final"))
-            if dev_opt["tables"] == "converged":
-                q_dev, s_dev = tracker.tables_at_convergence()
-        write_artefacts(exp_path, batch, config, dev_opt, ids, n_groups, spec=spec,
-                        histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET, q=q_dev, state0=s_dev)
-
-    if eq_opt is not None:      # are the greedy strategies an equilibrium (equilibrium.py)
-        from th_rl_amd.equilibrium import write_artefacts as write_equilibrium
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        q_eq = s_eq = None
-        if tracker is not None:
-            eq_opt = dict(eq_opt, tables=eq_opt.get("tables", "final"))
-            if eq_opt["tables"] == "converged":
-                q_eq, s_eq = tracker.tables_at_convergence()
-        write_equilibrium(exp_path, batch, config, eq_opt, ids, n_groups, q=q_eq, state0=s_eq)
-
-    if xp_opt is not None:      # do the greedy policies survive a change of partner (crossplay.py)
-        from th_rl_amd.crossplay import write_artefacts as write_crossplay
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        q_xp = s_xp = None
-        if tracker is not None:
-            xp_opt = dict(xp_opt, tables=xp_opt.get("tables", "final"))
-            if xp_opt["tables"] == "converged":
-                q_xp, s_xp = tracker.tables_at_convergence()
-        write_crossplay(exp_path, batch, config, xp_opt, ids, n_groups, spec=spec,
-                        histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET, q=q_xp, state0=s_xp)
-
-    if at_opt is not None:      # every limit cycle of the greedy strategies and its basin (attractors.py)
-        from th_rl_amd.attractors import write_artefacts as write_attractors
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        q_at = s_at = None
-        if tracker is not None:
-            at_opt = dict(at_opt, tables=at_opt.get("tables", "final"))
-            if at_opt["tables"] == "converged":
-                q_at, s_at = tracker.tables_at_convergence()
-        write_attractors(exp_path, batch, config, at_opt, ids, n_groups, q=q_at, state0=s_at)
-
-    if st_opt is not None:      # the long-run distribution of greedy play under demand noise (stationary.py)
-        from th_rl_amd.stationary import write_artefacts as write_stationary
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        q_st = s_st = None
-        if tracker is not None:
-            st_opt = dict(st_opt, tables=st_opt.get("tables", "final"))
-            if st_opt["tables"] == "converged":
-                q_st, s_st = tracker.tables_at_convergence()
-        write_stationary(exp_path, batch, config, st_opt, ids, n_groups, q=q_st, state0=s_st,
-                         with_attractors=at_opt is not None)
-
+    # the analyses asked for, in the registry's order: each reads the batch and writes its own artefacts
+    if spec is not None:
+        ids, n_groups = spec.ids, spec.n_groups
+    elif opts:
+        from th_rl_amd.group_stats import assign_groups
+        ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
+                                         n_groups=training.get("n_groups", None))
+    done = {}               # key -> what its writer returned: the per-run context later analyses read (Analysis.after)
+    converged = None        # (tables, start prices) at convergence, fetched once
     tuple_policy = None
-    if gc_opt is not None or gdev_opt is not None or geq_opt is not None or gat_opt is not None or gst_opt is not None:
+    if any(analysis.record(k).tuple_policy == "extract" for k in opts):
         from th_rl_amd.tuple_play import extract as extract_tuple_policy
         tuple_policy = extract_tuple_policy(batch)      # every agent's strategy in tuple form, once for all greedy_* keys
-
-    if gc_opt is not None:      # the limit cycle of greedy play, neural agents included (tuple_play.py)
-        from th_rl_amd.tuple_play import write_artefacts as write_greedy_cycles
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        write_greedy_cycles(exp_path, batch, config, gc_opt, ids, n_groups, spec=spec,
-                            histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET,
-                            tuple_policy=tuple_policy)
-
-    if gdev_opt is not None or geq_opt is not None:     # is a deviation punished, is the strategy a best response
-        from th_rl_amd import tuple_analysis            # (tuple_analysis.py: neural agents included)
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        cycle_reward = None
-        if gdev_opt is not None:
-            r_dev = tuple_analysis.write_deviation(exp_path, batch, config, gdev_opt, ids, n_groups, spec=spec,
-                                                   histograms=bool(gs_opt and gs_opt["histograms"]),
-                                                   budget=GAME_LOG_BUDGET, tuple_policy=tuple_policy)
-            if gdev_opt["horizon"] is None:             # the full cycle: the one the equilibrium check's path ends in
-                cycle_reward = r_dev["cycle_reward"]
-        if geq_opt is not None:
-            tuple_analysis.write_equilibrium(exp_path, batch, config, geq_opt, ids, n_groups, tuple_policy=tuple_policy,
-                                             cycle_reward=cycle_reward)
-
-    if gat_opt is not None:     # all limit cycles of the greedy map on tuples and their basins
-        from th_rl_amd import tuple_analysis
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        tuple_analysis.write_attractors(exp_path, batch, config, gat_opt, ids, n_groups, tuple_policy=tuple_policy)
-
-    if gst_opt is not None:     # the long-run distribution of greedy play under demand noise over the tuples played
-        from th_rl_amd import tuple_stationary
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        tuple_stationary.write_artefacts(exp_path, batch, config, gst_opt, ids, n_groups, tuple_policy=tuple_policy)
-
-    if sp_opt is not None:      # what the agents earn when they play the way they were trained: sampled, not greedy
-        from th_rl_amd import sampled_play
-        if spec is not None:
-            ids, n_groups = spec.ids, spec.n_groups
-        else:
-            from th_rl_amd.group_stats import assign_groups
-            ids, n_groups, _ = assign_groups(n_games, sweep=training.get("sweep", None), groups=training.get("groups", None),
-                                             n_groups=training.get("n_groups", None))
-        sampled_play.write_artefacts(exp_path, batch, config, sp_opt, ids, n_groups, tuple_policy=tuple_policy,
-                                     with_cycles=gc_opt is not None)
+    for a in analysis.REGISTRY:
+        if a.key not in opts:
+            continue
+        opt, kw = opts[a.key], {}
+        if a.key == "convergence":      # the one analysis that ran during training: its writer takes the tracker
+            kw.update(tracker=tracker, every=conv_every, episodes_run=episodes_run, stopped_early=stopped_early)
+        if a.converged:
+            kw.update(q=None, state0=None)
+            if tracker is not None:
+                opt = dict(opt, tables=opt.get("tables", "final"))
+                if opt["tables"] == "converged":
+                    converged = converged or tracker.tables_at_convergence()
+                    kw.update(q=converged[0], state0=converged[1])
+        if a.rows:
+            kw.update(spec=spec, histograms=bool(gs_opt and gs_opt["histograms"]), budget=GAME_LOG_BUDGET)
+        if a.tuple_policy:
+            kw.update(tuple_policy=tuple_policy)
+        kw.update({name: done.get(key) for name, key in a.after})
+        r = getattr(analysis.module_of(a), a.write)(exp_path, batch, config, opt, ids, n_groups, **kw)
+        done[a.key] = True if r is None else r
 
     if n_games > 1 or resume or training.get("checkpoint", False):
         batch.save(os.path.join(exp_path, "batch.pt"))

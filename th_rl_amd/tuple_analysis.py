@@ -21,12 +21,12 @@ by default 1 / T: a start drawn uniformly over action profiles, NOT the environm
 in tuple form is tuple_stationary.py.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from . import attractors as at
 from . import deviation as dv
 from . import equilibrium as eq
@@ -71,16 +71,7 @@ def parse_deviation_options(opt, config):
     name = "training.greedy_deviation"
     ps, _ = tp.check_config(config)
     n = len(ps)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
-    known = {"agents", "steps", "dev_len", "action", "horizon"}
-    bad = set(opt) - known
-    if bad:
-        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(known))))
-    out = dict(DEV_DEFAULTS, agents=list(range(n)))
-    out.update(opt)
+    out = an.options("greedy_deviation", opt, dict(DEV_DEFAULTS, agents=list(range(n))))
     out["agents"] = _agents(name, out["agents"], n)
     out["steps"], out["dev_len"] = _int(name + ".steps", out["steps"]), _int(name + ".dev_len", out["dev_len"])
     if not 1 <= out["dev_len"] <= out["steps"] <= _lib.DEV_MAX_STEPS:
@@ -105,16 +96,7 @@ def parse_equilibrium_options(opt, config):
     name = "training.greedy_equilibrium"
     ps, _ = tp.check_config(config)
     n = len(ps)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
-    known = {"agents", "tol", "policies"}
-    bad = set(opt) - known
-    if bad:
-        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(known))))
-    out = dict(EQ_DEFAULTS, agents=list(range(n)))
-    out.update(opt)
+    out = an.options("greedy_equilibrium", opt, dict(EQ_DEFAULTS, agents=list(range(n))))
     out["agents"] = sorted(set(_agents(name, out["agents"], n)))
     if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float, np.integer, np.floating)) \
             or not float(out["tol"]) >= 0.0:
@@ -160,15 +142,7 @@ def parse_attractor_options(opt, config):
     and more than tuple_play.MAX_TUPLES tuples."""
     name = "training.greedy_attractors"
     _, T = tp.check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
-    bad = set(opt) - set(ATTR_DEFAULTS)
-    if bad:
-        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(ATTR_DEFAULTS))))
-    out = dict(ATTR_DEFAULTS)
-    out.update(opt)
+    out = an.options("greedy_attractors", opt, ATTR_DEFAULTS)
     if not isinstance(out["policies"], (bool, np.bool_)):
         raise ValueError("%s.policies must be true or false, got %r" % (name, out["policies"]))
     out["policies"] = bool(out["policies"])
@@ -202,9 +176,8 @@ def _inputs(batch, tuple_policy, start, tabs):
     dev = batch.device
     if tuple_policy is None:
         tuple_policy = tp.extract(batch, tabs)
-    elif tuple(tuple_policy.shape) != (G, N, T) or tuple_policy.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) \
-            or tuple_policy.device != batch.state.device or not tuple_policy.is_contiguous():
-        raise ThrlError("tuple_analysis: tuple_policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, T), dev))
+    else:
+        an.check_policy(batch, tuple_policy, (G, N, T), "tuple_analysis", "tuple_policy")
     with torch.cuda.device(dev):
         if start is None:
             t0 = tp.start_tuples(batch.state, tabs).contiguous()
@@ -482,9 +455,9 @@ def write_attractors(exp_path, batch, config, opt, ids, n_groups, tuple_policy=N
     nash, cartel = dv.optimal(config)
     summary = summarize_attractors(r, ids, n_groups, nash, cartel)
     label = UNIFORM_LABEL if opt["weights"] == "uniform" else ("none" if opt["weights"] is None else "given per tuple")
-    with open(os.path.join(exp_path, "greedy_attractors.json"), "w") as f:
-        json.dump({"options": opt, "n_states": int(r["n_states"]), "keep": KEEP, "nash": nash, "cartel": cartel,
-                   "quantiles": list(at.QUANTILES), "start_weights": label, "summary": summary}, f, indent=2)
+    an.save_json(os.path.join(exp_path, "greedy_attractors.json"),
+                 {"options": opt, "n_states": int(r["n_states"]), "keep": KEEP, "nash": nash, "cartel": cartel,
+                  "quantiles": list(at.QUANTILES), "start_weights": label, "summary": summary})
     return r
 
 
@@ -511,23 +484,19 @@ def write_deviation(exp_path, batch, config, opt, ids, n_groups, spec=None, hist
                 np.stack([r["mu_post"], r["lam_post"], r["ret_step"], r["act_dev"]]).astype(np.int32))
         np.save(os.path.join(exp_path, "gdev%d_gain.npy" % d), r["gain"])
         if spec is not None:
-            files = trainer.group_stats_files(exp_path, "gdev%d" % d, opt["steps"], spec, histograms)
-            trainer.write_group_stats(files, 0, r["group_stats"], spec.describe())
-            for arr in files.values():
-                if hasattr(arr, "flush"):
-                    arr.flush()
+            trainer.save_group_stats(exp_path, "gdev%d" % d, r["group_stats"], spec, histograms)
         summary += summarize_deviation(r, ids, n_groups, nash, cartel, d)
-    opt = dict(opt, horizon_used=int(r["horizon"]))
-    with open(os.path.join(exp_path, "greedy_deviation.json"), "w") as f:
-        json.dump(dict(dv.describe(opt, nash, cartel, summary), T=int(tabs["T"])), f, indent=2)
-    return r
+    an.save_json(os.path.join(exp_path, "greedy_deviation.json"),
+                 dict(dv.describe(dict(opt, horizon_used=int(r["horizon"])), nash, cartel, summary), T=int(tabs["T"])))
+    return dict(r, full_cycle=opt["horizon"] is None)
 
 
-def write_equilibrium(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None, cycle_reward=None):
+def write_equilibrium(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None, deviation=None):
     """train_one's training.greedy_equilibrium outputs, with the shapes of equilibrium.save_games': geq_cycle.npy int32
     [3, G] (mu, lam, start), geq_iters [N, G], geq_diff [2, N, G], geq_loss [4, N, G], geq_value [N, G], with
-    policies geq_policy, geq_v_opt, geq_v_pi [N, G, T], and greedy_equilibrium.json.  cycle_reward [N, G]: the cycle
-    rewards of the same strategies and starts for the collusive fractions (default: one thrl_tuple_walk)."""
+    policies geq_policy, geq_v_opt, geq_v_pi [N, G, T], and greedy_equilibrium.json.  deviation: what write_deviation
+    returned for the same strategies and starts; with the full cycle (no horizon) its cycle rewards serve the collusive
+    fractions, else one thrl_tuple_walk finds them."""
     tabs = tp.tables(config)
     if tuple_policy is None:
         tuple_policy = tp.extract(batch, tabs)
@@ -543,11 +512,12 @@ def write_equilibrium(exp_path, batch, config, opt, ids, n_groups, tuple_policy=
         np.save(os.path.join(exp_path, "geq_policy.npy"), np.asarray(r["br_policy"], np.uint16))
         np.save(os.path.join(exp_path, "geq_v_opt.npy"), np.asarray(r["v_opt"], np.float64))
         np.save(os.path.join(exp_path, "geq_v_pi.npy"), np.asarray(r["v_pi"], np.float64))
-    if cycle_reward is None:
+    if deviation is not None and deviation["full_cycle"]:    # the cycle the equilibrium check's path ends in
+        cycle_reward = deviation["cycle_reward"]
+    else:
         cycle_reward = tp.run(batch, start=r["start"], tuple_policy=tuple_policy, tabs=tabs)["cycle_reward"]
     nash, cartel = dv.optimal(config)
     delta = np.where(r["lam"] > 0, dv.profit_gain(cycle_reward, nash, cartel), -np.inf)      # no path: not collusive
     summary = summarize_equilibrium(r, ids, n_groups, opt["agents"], opt["tol"], delta)
-    with open(os.path.join(exp_path, "greedy_equilibrium.json"), "w") as f:
-        json.dump(eq.describe(opt, r["n_states"], summary), f, indent=2)
+    an.save_json(os.path.join(exp_path, "greedy_equilibrium.json"), eq.describe(opt, r["n_states"], summary))
     return r

@@ -19,12 +19,12 @@ delta_mean / q25 / q50 / q75 (deviation.profit_gain); re-seated rounds are summa
 (delta_self_mean, retained, seat_gain) with no_start added.  Sharded runs (th_rl_amd.launch) are refused.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from ._lib import ThrlError
 from .deviation import LAM_BINS, QUANTILES, ROW_BUDGET, default_horizon, lam_bin_names, optimal, profit_gain
 
@@ -94,15 +94,7 @@ def parse_options(opt, config):
     group_stats, 0 = none), horizon (None = deviation.default_horizon)."""
     from .crossplay import AGAINST, SCHEMES
     check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("training.greedy_cycles must be true or a dict, got %r" % (opt,))
-    bad = set(opt) - set(DEFAULTS)
-    if bad:
-        raise ValueError("training.greedy_cycles: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(DEFAULTS))))
-    out = dict(DEFAULTS)
-    out.update(opt)
+    out = an.options("greedy_cycles", opt, DEFAULTS)
     for k in ("rounds", "steps", "seed"):
         if isinstance(out[k], bool) or not isinstance(out[k], (int, np.integer)):
             raise ValueError("training.greedy_cycles.%s must be an integer, got %r" % (k, out[k]))
@@ -232,9 +224,8 @@ def run(batch, seats=None, start=None, steps=0, rows=False, horizon=None, tuple_
     dev = batch.device
     if tuple_policy is None:
         tuple_policy = extract(batch, tabs)
-    elif tuple(tuple_policy.shape) != (G, N, T) or tuple_policy.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) \
-            or tuple_policy.device != batch.state.device or not tuple_policy.is_contiguous():
-        raise ThrlError("tuple_play: tuple_policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, T), dev))
+    else:
+        an.check_policy(batch, tuple_policy, (G, N, T), "tuple_play", "tuple_policy")
     a = _lib.TupleWalkArgs()
     a.n_games, a.n_matches, a.n_tuples, a.n_steps, a.horizon = G, M, T, K, H
     res = {f: [] for f in OUT + ("start",)}
@@ -312,10 +303,6 @@ def run(batch, seats=None, start=None, steps=0, rows=False, horizon=None, tuple_
 
 
 # ---------------------------------------------------------------------------------------------- host side
-def _num(x):
-    return None if x is None or not np.isfinite(x) else float(x)
-
-
 def summarize_self(self_play, ids, n_groups, nash, cartel):
     """One dict per group for the self-play round: self_play = mu, lam, start [G], cycle_reward [N, G]."""
     ids = np.asarray(ids, np.int64).reshape(-1)
@@ -332,8 +319,8 @@ def summarize_self(self_play, ids, n_groups, nash, cartel):
         qs = np.quantile(dk, QUANTILES) if dk.size else [None] * len(QUANTILES)
         out.append({"group": k, "matches": int(m.sum()), "no_start": int(np.sum(g & (start < 0))),
                     "cycles": int(np.sum(lk > 0)), "fixed_points": int(np.sum(lk == 1)), "lam_hist": hist,
-                    "delta_mean": _num(dk.mean()) if dk.size else None,
-                    "delta_q25": _num(qs[0]), "delta_q50": _num(qs[1]), "delta_q75": _num(qs[2])})
+                    "delta_mean": an.num(dk.mean()) if dk.size else None,
+                    "delta_q25": an.num(qs[0]), "delta_q50": an.num(qs[1]), "delta_q75": an.num(qs[2])})
     return out
 
 
@@ -359,8 +346,7 @@ def summarize(games, self_play, ids, n_groups, nash, cartel):
 def combine(parts):
     """Per-match arrays of disjoint sets of games as one run's: concatenated along the match (= game) axis.  `seats`
     must hold global ids."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=-1) for f in parts[0]}
+    return an.combine(parts)
 
 
 def describe(options, nash, cartel, T, self_summary, summary):
@@ -414,15 +400,10 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, spec=None, hist
     off = int(batch.game_offset)
     save_games(exp_path, dict(games, seats=games["seats"].astype(np.int64) + off))
     if pooled is not None:
-        files = trainer.group_stats_files(exp_path, "gcyc", opt["steps"], spec, histograms)
-        trainer.write_group_stats(files, 0, games["group_stats"], spec.describe())
-        for arr in files.values():
-            if hasattr(arr, "flush"):
-                arr.flush()
+        trainer.save_group_stats(exp_path, "gcyc", games["group_stats"], spec, histograms)
     self_play = {f: games[f][0] for f in OUT + ("start",)}
     rest = {f: games[f][1:] for f in OUT + ("start", "seats")}
     summary = summarize(rest, self_play, ids, n_groups, nash, cartel) if rest["seats"].shape[0] else []
     opt = dict(opt, horizon_used=int(games["horizon"]), rounds_played=int(games["seats"].shape[0]))
-    with open(os.path.join(exp_path, "greedy_cycles.json"), "w") as f:
-        json.dump(describe(opt, nash, cartel, tabs["T"], summarize_self(self_play, ids, n_groups, nash, cartel), summary),
-                  f, indent=2)
+    an.save_json(os.path.join(exp_path, "greedy_cycles.json"),
+                 describe(opt, nash, cartel, tabs["T"], summarize_self(self_play, ids, n_groups, nash, cartel), summary))

@@ -19,12 +19,12 @@ summarize() gives stationary.summarize's rows per group plus n_switch_max, unres
 runs (th_rl_amd.launch) are refused.
 """
 import ctypes
-import json
 import os
 
 import numpy as np
 
 from . import _lib
+from . import analysis as an
 from . import stationary as sn
 from . import tuple_play as tp
 from ._lib import ThrlError
@@ -50,15 +50,7 @@ def parse_options(opt, config):
     axis).  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples and more than MAX_CELLS cells."""
     name = "training.greedy_stationary"
     tp.check_config(config)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise ValueError("%s must be true or a dict, got %r" % (name, opt))
-    bad = set(opt) - set(DEFAULTS)
-    if bad:
-        raise ValueError("%s: unknown keys %s (known: %s)" % (name, sorted(bad), ", ".join(sorted(DEFAULTS))))
-    out = dict(DEFAULTS)
-    out.update(opt)
+    out = an.options("greedy_stationary", opt, DEFAULTS)
     if out["noise_prob"] is not None:
         out["noise_prob"] = sn._check_prob(out["noise_prob"], name + ".noise_prob")
     else:       # the run's own noise: refuse a noise-free run before training, as the batch would after it
@@ -159,12 +151,6 @@ def tables(config, resolution=DEFAULTS["resolution"]):
 
 
 # ---------------------------------------------------------------------------------------------- the device calls
-def _is_policy(x, shape, dev):
-    import torch
-    return tuple(x.shape) == shape and x.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)) \
-        and x.device == dev and x.is_contiguous()
-
-
 def price_policy(batch, price, per_game=False, n_games=None):
     """thrl_price_policy: what every agent of the first n_games (default all) games of `batch` plays at the prices
     `price` (J numbers shared by the games, or with per_game [G, J]: each game its own), as a device int16 tensor
@@ -248,12 +234,11 @@ def run(batch, noise_prob=None, start="reset", resolution=DEFAULTS["resolution"]
     sdev = batch.state.device
     if tuple_policy is None:
         tuple_policy = tp.extract(batch, tabs)
-    if not _is_policy(tuple_policy, (batch.G, N, T), sdev) and not _is_policy(tuple_policy, (G, N, T), sdev):
-        raise ThrlError("tuple_stationary: tuple_policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, T), dev))
+    if not an.is_policy(tuple_policy, (batch.G, N, T), sdev):
+        an.check_policy(batch, tuple_policy, (G, N, T), "tuple_stationary", "tuple_policy")
     if cell_policy is None:
         cell_policy = extract_cells(batch, tabs, n_games=G)
-    if not _is_policy(cell_policy, (G, N, J), sdev):
-        raise ThrlError("tuple_stationary: cell_policy must be a contiguous 16-bit integer tensor %s on %s" % ((G, N, J), dev))
+    an.check_policy(batch, cell_policy, (G, N, J), "tuple_stationary", "cell_policy")
     a = _lib.TupleStationaryArgs()
     a.n_games, a.n_tuples, a.n_cells, a.band_w, a.max_iters, a.tol = G, T, J, W, int(max_iters), float(tol)
     for i, k in enumerate(tp._kinds(batch)):
@@ -316,17 +301,15 @@ def summarize(games, ids, n_groups, nash, cartel, max_iters):
     for r in rows:
         m = ids == r["group"]
         r["n_switch_max"] = int(ns[m].max()) if m.any() else None
-        r["unresolved_mean"] = sn._mean(un[m])
-        r["unresolved_max"] = sn._num(un[m].max()) if m.any() else None
+        r["unresolved_mean"] = an.mean(un[m])
+        r["unresolved_max"] = an.num(un[m].max()) if m.any() else None
     return rows
 
 
 def combine(parts):
     """Per-game arrays of disjoint sets of games (in global game order) as one run's: concatenated along the game axis
     (axis 0 of pi [G, T], the last axis of the others)."""
-    parts = list(parts)
-    return {f: np.concatenate([np.asarray(p[f]) for p in parts], axis=0 if f == "pi" else -1)
-            for f in parts[0] if f in PER_GAME}
+    return an.combine(parts, other={"pi": 0}, only=PER_GAME)
 
 
 def describe(options, n_cells, T, nash, cartel, summary):
@@ -374,6 +357,5 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=No
     save_games(exp_path, r)
     nash, cartel = optimal(config)
     summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"])
-    with open(os.path.join(exp_path, "greedy_stationary.json"), "w") as f:
-        json.dump(describe(opt, r["n_cells"], r["T"], nash, cartel, summary), f, indent=2)
+    an.save_json(os.path.join(exp_path, "greedy_stationary.json"), describe(opt, r["n_cells"], r["T"], nash, cartel, summary))
     return r

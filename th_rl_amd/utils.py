@@ -135,6 +135,37 @@ def group_quantiles(exp_path, group, quantity="total", prefix="group"):
     return df
 
 
+def _load_json(d, name):
+    import json
+    with open(os.path.join(d, name)) as f:
+        return json.load(f)
+
+
+def _run_dirs(exp_path, probe, what, key, shards=True):
+    """The directories that hold an analysis's per-game arrays: exp_path when it has the file `probe`, else (with
+    shards) its shard* subdirectories that have it, in rank order (th_rl_amd.launch writes one set per rank).
+    KeyError when there is none."""
+    import glob
+    if os.path.isfile(os.path.join(exp_path, probe)):
+        return [exp_path]
+    dirs = []
+    if shards:
+        dirs = sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, probe))),
+                      key=lambda d: int(os.path.basename(d)[5:]))
+    if not dirs:
+        raise KeyError("no %s (%s) under %s (training.%s)" % (what, probe, exp_path, key))
+    return dirs
+
+
+def _game_offset(d, exp_path):
+    """The global id of the first game of run directory `d`: training.game_offset of its config.json (a shard's
+    shard_config.json), 0 without one."""
+    name = "shard_config.json" if d != exp_path else "config.json"
+    if not os.path.isfile(os.path.join(d, name)):
+        return 0
+    return int(_load_json(d, name).get("training", {}).get("game_offset", 0))
+
+
 def deviation_summary(exp_path):
     """A run's deviation analysis (training.deviation): deviation.json's summary as a DataFrame with one row per
     (group, deviator) -- games, cycles, fixed_points, returned, unprofitable, ret_step_mean, the profit gain's mean
@@ -143,9 +174,7 @@ def deviation_summary(exp_path):
     "dev<d>": group_quantiles(exp_path, group, "total", prefix="dev0") and group_log(exp_path, group, prefix="dev0"),
     one row per period after the shock.  mu and lam of deviation_games are those of equilibrium_games for the same run
     (same tables, same start prices, default horizon)."""
-    import json
-    with open(os.path.join(exp_path, "deviation.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "deviation.json")
     rows = []
     for r in desc["summary"]:
         r = dict(r)
@@ -161,22 +190,13 @@ def deviation_games(exp_path, deviator=0):
     """Per-game results of the deviation analysis for `deviator`, one row per game indexed by its GLOBAL id: mu, lam,
     mu_post, lam_post, ret_step, act_dev, gain, cycle_reward_<i> / cycle_action_<i> and the profit gain delta.  Reads
     exp_path's dev*.npy, or those of exp_path/shard*/ (th_rl_amd.launch writes one set per rank) in game order."""
-    import glob
-    import json
     from th_rl_amd import deviation as dv
-    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "dev_cycle.npy")) else \
-        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "dev_cycle.npy"))),
-               key=lambda d: int(os.path.basename(d)[5:]))
-    if not dirs:
-        raise KeyError("no deviation analysis (dev_cycle.npy) under %s (training.deviation)" % exp_path)
+    dirs = _run_dirs(exp_path, "dev_cycle.npy", "deviation analysis", "deviation")
     frames = []
     for d in dirs:
-        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
-        with open(cfg_path) as f:
-            config = json.load(f)
         g = dv.load_games(d, int(deviator))
-        nash, cartel = dv.optimal(config)
-        off = int(config.get("training", {}).get("game_offset", 0))
+        nash, cartel = dv.optimal(_load_json(d, "shard_config.json" if d != exp_path else "config.json"))
+        off = _game_offset(d, exp_path)
         n = g["gain"].shape[0]
         cols = {f: g[f] for f in dv.INT_FIELDS}
         cols["gain"] = g["gain"]
@@ -195,9 +215,7 @@ def equilibrium_summary(exp_path):
     NaN: the group's nash and perfect fractions and, when the run has training.deviation, collusive (games with
     profit gain above collusive_gain), nash_collusive and perfect_collusive.  mu and lam of equilibrium_games are those
     of deviation_games for the same run (same tables, same start prices, default horizon)."""
-    import json
-    with open(os.path.join(exp_path, "equilibrium.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "equilibrium.json")
     df = pandas.DataFrame(desc["summary"])
     df["n_states"] = int(desc["n_states"])
     df["tol"] = float(desc["options"]["tol"])
@@ -209,23 +227,12 @@ def equilibrium_games(exp_path, agent=0):
     iters, n_diff_all, n_diff_on, loss_all, loss_on, loss_all_mean, loss_on_mean, v_on, and the flags br_on, br_all
     (this agent) and nash, perfect (all solved agents) at the run's tol.  Reads exp_path's eq_*.npy, or those of
     exp_path/shard*/ in game order.  mu and lam equal deviation_games' for the same run."""
-    import glob
-    import json
     from th_rl_amd import equilibrium as eq
-    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "eq_cycle.npy")) else \
-        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "eq_cycle.npy"))),
-               key=lambda d: int(os.path.basename(d)[5:]))
-    if not dirs:
-        raise KeyError("no equilibrium check (eq_cycle.npy) under %s (training.equilibrium)" % exp_path)
+    dirs = _run_dirs(exp_path, "eq_cycle.npy", "equilibrium check", "equilibrium")
     frames = []
     for d in dirs:
-        with open(os.path.join(d, "equilibrium.json")) as f:
-            opt = json.load(f)["options"]
-        off = 0
-        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
-        if os.path.isfile(cfg_path):
-            with open(cfg_path) as f:
-                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        opt = _load_json(d, "equilibrium.json")["options"]
+        off = _game_offset(d, exp_path)
         g = eq.load_games(d)
         fl = eq.flags(g, opt["agents"], opt["tol"])
         cols = {"mu": g["mu"], "lam": g["lam"]}
@@ -242,9 +249,7 @@ def crossplay_summary(exp_path):
     seat 0, partner_group) -- matches, cycles, fixed_points, the cross-play profit gain's mean and quantiles (delta_*),
     delta_self_mean (the same games in self-play), retained, seat_gain_<i> and one lam_<bin> column per bin of the lam
     histogram -- plus Nash and Cartel.  In a sharded run the partners were drawn inside each shard."""
-    import json
-    with open(os.path.join(exp_path, "crossplay.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "crossplay.json")
     rows = []
     for r in desc["summary"]:
         r = dict(r)
@@ -263,18 +268,11 @@ def crossplay_games(exp_path, round=0):
     (global game ids), self_seat, mu, lam, cycle_reward_<i> / cycle_action_<i>, the profit gain delta, and the same
     game's self-play lam_self and delta_self.  Reads exp_path's xplay_*.npy, or those of exp_path/shard*/
     (th_rl_amd.launch writes one set per rank) in game order."""
-    import glob
-    import json
     from th_rl_amd import crossplay as xp
-    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "xplay_cycle.npy")) else \
-        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "xplay_cycle.npy"))),
-               key=lambda d: int(os.path.basename(d)[5:]))
-    if not dirs:
-        raise KeyError("no cross-play (xplay_cycle.npy) under %s (training.crossplay)" % exp_path)
+    dirs = _run_dirs(exp_path, "xplay_cycle.npy", "cross-play", "crossplay")
     frames = []
     for d in dirs:
-        with open(os.path.join(d, "crossplay.json")) as f:
-            desc = json.load(f)
+        desc = _load_json(d, "crossplay.json")
         g, sp = xp.load_games(d)
         r = int(round)
         if not 0 <= r < g["seats"].shape[0]:
@@ -299,9 +297,7 @@ def greedy_cycle_summary(exp_path):
     (delta_*) and one lam_<bin> column per bin of the lam histogram; the second one row per (group of seat 0,
     partner_group) over the re-seated rounds, with crossplay_summary's columns and no_start (empty without such
     rounds).  Both carry Nash and Cartel."""
-    import json
-    with open(os.path.join(exp_path, "greedy_cycles.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "greedy_cycles.json")
 
     def frame(rows):
         out = []
@@ -323,12 +319,9 @@ def greedy_cycle_games(exp_path, round=0):
     """Per-match results of round `round` of training.greedy_cycles (0 = every game's own agents, k >= 1 the k-th
     re-seating), one row per match indexed by the GLOBAL id of seat 0's game: seat_<i> (global game ids), start (the
     start tuple, -1 = none), mu, lam, cycle_start, cycle_reward_<i> / cycle_action_<i> and the profit gain delta."""
-    import json
     from th_rl_amd import tuple_play as tp
-    if not os.path.isfile(os.path.join(exp_path, "gcyc_cycle.npy")):
-        raise KeyError("no greedy cycles (gcyc_cycle.npy) under %s (training.greedy_cycles)" % exp_path)
-    with open(os.path.join(exp_path, "greedy_cycles.json")) as f:
-        desc = json.load(f)
+    _run_dirs(exp_path, "gcyc_cycle.npy", "greedy cycles", "greedy_cycles", shards=False)
+    desc = _load_json(exp_path, "greedy_cycles.json")
     g = tp.load_games(exp_path)
     r = int(round)
     if not 0 <= r < g["seats"].shape[0]:
@@ -349,9 +342,7 @@ def attractor_summary(exp_path):
     delta_reset_mean (profit gains of the training state's attractor, of the largest basin and in expectation over the
     environment's reset distribution), train_is_largest, train_mass_q*, luck_mean -- plus n_states, n_starts, Nash
     and Cartel."""
-    import json
-    with open(os.path.join(exp_path, "attractors.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "attractors.json")
     df = pandas.DataFrame(desc["summary"])
     df["n_states"], df["n_starts"] = int(desc["n_states"]), int(desc["n_starts"])
     df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
@@ -363,23 +354,12 @@ def attractor_games(exp_path):
     n_cycle_states, rep_x0, mu_x0, slot_x0, per kept slot k rep_<k>, lam_<k>, basin_<k>, delta_<k> (its profit gain, NaN
     past n_attr) and mass_<k>, and delta_train, delta_reset, mass_other.  Reads exp_path's attr_*.npy, or those of
     exp_path/shard*/ (th_rl_amd.launch writes one set per rank) in game order."""
-    import glob
-    import json
     from th_rl_amd import attractors as at
-    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "attr_games.npy")) else \
-        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "attr_games.npy"))),
-               key=lambda d: int(os.path.basename(d)[5:]))
-    if not dirs:
-        raise KeyError("no attractor analysis (attr_games.npy) under %s (training.attractors)" % exp_path)
+    dirs = _run_dirs(exp_path, "attr_games.npy", "attractor analysis", "attractors")
     frames = []
     for d in dirs:
-        with open(os.path.join(d, "attractors.json")) as f:
-            desc = json.load(f)
-        off = 0
-        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
-        if os.path.isfile(cfg_path):
-            with open(cfg_path) as f:
-                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        desc = _load_json(d, "attractors.json")
+        off = _game_offset(d, exp_path)
         g = at.load_games(d)
         gn = at.gains(g, desc["nash"], desc["cartel"])
         cols = {f: g[f] for f in at.GAME_INT}
@@ -406,9 +386,7 @@ def stationary_summary(exp_path):
     also carries the demand the noise removes), price_mean and, when attr_reset_reward.npy (training.attractors) is in
     the same directory, delta_reset_mean and noise_cost_mean = delta_reset - delta_noise -- plus n_cells, Nash and
     Cartel."""
-    import json
-    with open(os.path.join(exp_path, "stationary.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "stationary.json")
     df = pandas.DataFrame(desc["summary"])
     df["n_cells"] = int(desc["n_cells"])
     df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
@@ -420,23 +398,12 @@ def stationary_games(exp_path):
     noise_prob, price, reward_<i>, action_<i>, delta_noise (against the noise-free Nash / Cartel) and, with
     attr_reset_reward.npy beside them, delta_reset.  Reads exp_path's stat_*.npy, or those of exp_path/shard*/
     (th_rl_amd.launch writes one set per rank) in game order."""
-    import glob
-    import json
     from th_rl_amd import stationary as sn
-    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "stat_iters.npy")) else \
-        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "stat_iters.npy"))),
-               key=lambda d: int(os.path.basename(d)[5:]))
-    if not dirs:
-        raise KeyError("no stationary analysis (stat_iters.npy) under %s (training.stationary)" % exp_path)
+    dirs = _run_dirs(exp_path, "stat_iters.npy", "stationary analysis", "stationary")
     frames = []
     for d in dirs:
-        with open(os.path.join(d, "stationary.json")) as f:
-            desc = json.load(f)
-        off = 0
-        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
-        if os.path.isfile(cfg_path):
-            with open(cfg_path) as f:
-                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        desc = _load_json(d, "stationary.json")
+        off = _game_offset(d, exp_path)
         g = sn.load_games(d)
         cols = {"iters": g["iters"], "change": g["change"], "mass": g["mass"], "noise_prob": g["noise_prob"],
                 "price": g["stat_price"]}
@@ -456,9 +423,7 @@ def convergence_summary(exp_path):
     games, converged, fraction, converged_at_mean / q25 / q50 / q75, conv_since_mean / q25 / q50 / q75 (over the
     converged games), still_stable, changes_mean -- plus the run's window, every_used, episodes_run and
     stopped_early."""
-    import json
-    with open(os.path.join(exp_path, "convergence.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "convergence.json")
     df = pandas.DataFrame(desc["summary"])
     df["window"] = int(desc["options"]["window"])
     df["every_used"] = int(desc["every_used"])
@@ -470,21 +435,11 @@ def convergence_summary(exp_path):
 def convergence_games(exp_path):
     """Per-game convergence, one row per game indexed by its GLOBAL id: converged_at (-1 = never), conv_since,
     stable_since, changes.  Reads exp_path's conv_*.npy, or those of exp_path/shard*/ in game order."""
-    import glob
-    import json
     from th_rl_amd import convergence as cv
-    dirs = [exp_path] if os.path.isfile(os.path.join(exp_path, "conv_episode.npy")) else \
-        sorted((d for d in glob.glob(os.path.join(exp_path, "shard*")) if os.path.isfile(os.path.join(d, "conv_episode.npy"))),
-               key=lambda d: int(os.path.basename(d)[5:]))
-    if not dirs:
-        raise KeyError("no convergence arrays (conv_episode.npy) under %s (training.convergence)" % exp_path)
+    dirs = _run_dirs(exp_path, "conv_episode.npy", "convergence arrays", "convergence")
     frames = []
     for d in dirs:
-        off = 0
-        cfg_path = os.path.join(d, "shard_config.json" if d != exp_path else "config.json")
-        if os.path.isfile(cfg_path):
-            with open(cfg_path) as f:
-                off = int(json.load(f).get("training", {}).get("game_offset", 0))
+        off = _game_offset(d, exp_path)
         g = cv.load_games(d)
         n = g["converged_at"].shape[0]
         frames.append(pandas.DataFrame({f: g[f] for f in cv.FILES}, index=pandas.RangeIndex(off, off + n, name="game")))
@@ -495,9 +450,7 @@ def greedy_deviation_summary(exp_path):
     """A run's deviation test in tuple form (training.greedy_deviation, any mix of QTable / Reinforce / ActorCritic
     agents): greedy_deviation.json's summary as a DataFrame with deviation_summary's columns, one row per (group,
     deviator), plus no_start (the group's games whose state is no tuple's price: refused, lam = 0) and T."""
-    import json
-    with open(os.path.join(exp_path, "greedy_deviation.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "greedy_deviation.json")
     rows = []
     for r in desc["summary"]:
         r = dict(r)
@@ -513,18 +466,12 @@ def greedy_deviation_games(exp_path, deviator=0):
     """Per-game results of training.greedy_deviation for `deviator`, one row per game indexed by its GLOBAL id: start
     (the start tuple, -1 = none), mu, lam, mu_post, lam_post, ret_step, act_dev, gain, cycle_reward_<i> /
     cycle_action_<i> and the profit gain delta."""
-    import json
     from th_rl_amd import deviation as dv, tuple_analysis as ta
-    if not os.path.isfile(os.path.join(exp_path, "gdev_cycle.npy")):
-        raise KeyError("no deviation test in tuple form (gdev_cycle.npy) under %s (training.greedy_deviation)" % exp_path)
-    with open(os.path.join(exp_path, "greedy_deviation.json")) as f:
-        desc = json.load(f)
+    _run_dirs(exp_path, "gdev_cycle.npy", "deviation test in tuple form", "greedy_deviation", shards=False)
+    desc = _load_json(exp_path, "greedy_deviation.json")
     if int(deviator) not in desc["options"]["agents"]:
         raise KeyError("deviator %d was not analysed (agents %s)" % (int(deviator), desc["options"]["agents"]))
-    off = 0
-    if os.path.isfile(os.path.join(exp_path, "config.json")):
-        with open(os.path.join(exp_path, "config.json")) as f:
-            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    off = _game_offset(exp_path, exp_path)
     g = ta.load_deviation_games(exp_path, int(deviator))
     cols = {"start": g["start"]}
     cols.update({f: g[f] for f in dv.INT_FIELDS})
@@ -540,9 +487,7 @@ def greedy_deviation_games(exp_path, deviator=0):
 def greedy_equilibrium_summary(exp_path):
     """A run's equilibrium check in tuple form (training.greedy_equilibrium): greedy_equilibrium.json's summary as a
     DataFrame with equilibrium_summary's columns (n_states = T, the game's action tuples) plus no_start."""
-    import json
-    with open(os.path.join(exp_path, "greedy_equilibrium.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "greedy_equilibrium.json")
     df = pandas.DataFrame(desc["summary"])
     df["n_states"] = int(desc["n_states"])
     df["tol"] = float(desc["options"]["tol"])
@@ -553,16 +498,10 @@ def greedy_equilibrium_games(exp_path, agent=0):
     """Per-game results of training.greedy_equilibrium for `agent`, one row per game indexed by its GLOBAL id: start,
     mu, lam, equilibrium_games' columns for this agent and the flags br_on, br_all (this agent) and nash, perfect (all
     solved agents) at the run's tol."""
-    import json
     from th_rl_amd import equilibrium as eq, tuple_analysis as ta
-    if not os.path.isfile(os.path.join(exp_path, "geq_cycle.npy")):
-        raise KeyError("no equilibrium check in tuple form (geq_cycle.npy) under %s (training.greedy_equilibrium)" % exp_path)
-    with open(os.path.join(exp_path, "greedy_equilibrium.json")) as f:
-        opt = json.load(f)["options"]
-    off = 0
-    if os.path.isfile(os.path.join(exp_path, "config.json")):
-        with open(os.path.join(exp_path, "config.json")) as f:
-            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    _run_dirs(exp_path, "geq_cycle.npy", "equilibrium check in tuple form", "greedy_equilibrium", shards=False)
+    opt = _load_json(exp_path, "greedy_equilibrium.json")["options"]
+    off = _game_offset(exp_path, exp_path)
     g = ta.load_equilibrium_games(exp_path)
     fl = eq.flags(g, opt["agents"], opt["tol"])
     cols = {"start": g["start"], "mu": g["mu"], "lam": g["lam"]}
@@ -579,9 +518,7 @@ def greedy_attractor_summary(exp_path):
     profit gain in expectation over the start weights, by default a start drawn uniformly over action profiles -- not
     the environment's reset distribution) in place of delta_reset_mean, plus no_start, n_states (= T), Nash and
     Cartel."""
-    import json
-    with open(os.path.join(exp_path, "greedy_attractors.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "greedy_attractors.json")
     df = pandas.DataFrame(desc["summary"])
     df["n_states"] = int(desc["n_states"])
     df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
@@ -592,16 +529,10 @@ def greedy_attractor_games(exp_path):
     """Per-game results of training.greedy_attractors, one row per game indexed by its GLOBAL id: start (the training
     tuple, -1 = none), n_attr, mu_max, n_cycle_states, rep_x0, mu_x0, slot_x0, per kept slot k rep_<k>, lam_<k>,
     basin_<k>, delta_<k> (its profit gain, NaN past n_attr) and mass_<k>, and delta_train, delta_start, mass_other."""
-    import json
     from th_rl_amd import attractors as at, tuple_analysis as ta
-    if not os.path.isfile(os.path.join(exp_path, "gattr_games.npy")):
-        raise KeyError("no attractor analysis in tuple form (gattr_games.npy) under %s (training.greedy_attractors)" % exp_path)
-    with open(os.path.join(exp_path, "greedy_attractors.json")) as f:
-        desc = json.load(f)
-    off = 0
-    if os.path.isfile(os.path.join(exp_path, "config.json")):
-        with open(os.path.join(exp_path, "config.json")) as f:
-            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    _run_dirs(exp_path, "gattr_games.npy", "attractor analysis in tuple form", "greedy_attractors", shards=False)
+    desc = _load_json(exp_path, "greedy_attractors.json")
+    off = _game_offset(exp_path, exp_path)
     g = ta.load_attractor_games(exp_path)
     gn = ta.attractor_gains(g, desc["nash"], desc["cartel"])
     cols = {"start": g["start"]}
@@ -625,9 +556,7 @@ def greedy_stationary_summary(exp_path):
     of QTable / Reinforce / ActorCritic agents): greedy_stationary.json's summary as a DataFrame with
     stationary_summary's columns plus n_switch_max, unresolved_mean, unresolved_max (the share of the price axis on which
     a network's sampled strategy may differ from the true one), T, n_cells, Nash and Cartel."""
-    import json
-    with open(os.path.join(exp_path, "greedy_stationary.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "greedy_stationary.json")
     df = pandas.DataFrame(desc["summary"])
     df["T"], df["n_cells"] = int(desc["T"]), int(desc["n_cells"])
     df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
@@ -638,16 +567,10 @@ def greedy_stationary_games(exp_path):
     """Per-game results of training.greedy_stationary, one row per game indexed by its GLOBAL id: iters, change, mass,
     noise_prob, price, n_switch, unresolved, reward_<i>, action_<i>, delta_noise (against the noise-free Nash / Cartel)
     and, from the training state, start (the tuple played there)."""
-    import json
     from th_rl_amd import stationary as sn, tuple_stationary as ts
-    if not os.path.isfile(os.path.join(exp_path, "gstat_iters.npy")):
-        raise KeyError("no stationary analysis in tuple form (gstat_iters.npy) under %s (training.greedy_stationary)" % exp_path)
-    with open(os.path.join(exp_path, "greedy_stationary.json")) as f:
-        desc = json.load(f)
-    off = 0
-    if os.path.isfile(os.path.join(exp_path, "config.json")):
-        with open(os.path.join(exp_path, "config.json")) as f:
-            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    _run_dirs(exp_path, "gstat_iters.npy", "stationary analysis in tuple form", "greedy_stationary", shards=False)
+    desc = _load_json(exp_path, "greedy_stationary.json")
+    off = _game_offset(exp_path, exp_path)
     g = ts.load_games(exp_path)
     cols = {"iters": g["iters"], "change": g["change"], "mass": g["mass"], "noise_prob": g["noise_prob"],
             "price": g["stat_price"], "n_switch": g["n_switch"], "unresolved": g["unresolved"]}
@@ -667,9 +590,7 @@ def sampled_play_summary(exp_path):
     agree_mean (the share of steps on which every agent plays its greedy action), price_mean; where greedy_cycles ran in
     the same experiment also delta_greedy_mean and randomness_cost_mean = delta_greedy - delta_sampled; plus T,
     n_prices, Nash and Cartel."""
-    import json
-    with open(os.path.join(exp_path, "sampled_play.json")) as f:
-        desc = json.load(f)
+    desc = _load_json(exp_path, "sampled_play.json")
     df = pandas.DataFrame(desc["summary"])
     df["T"], df["n_prices"] = int(desc["T"]), int(desc["n_prices"])
     df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
@@ -680,17 +601,11 @@ def sampled_play_games(exp_path):
     """Per-game results of training.sampled_play, one row per game indexed by its GLOBAL id: iters, change, mass, price,
     agree, reward_<i>, action_<i>, epsilon_<i>, delta_sampled (the profit gain, as stationary_games computes
     delta_noise) and, from the training state, start (the tuple played there)."""
-    import json
     from th_rl_amd import sampled_play as sp
     from th_rl_amd.deviation import profit_gain
-    if not os.path.isfile(os.path.join(exp_path, "splay_iters.npy")):
-        raise KeyError("no sampled-play analysis (splay_iters.npy) under %s (training.sampled_play)" % exp_path)
-    with open(os.path.join(exp_path, "sampled_play.json")) as f:
-        desc = json.load(f)
-    off = 0
-    if os.path.isfile(os.path.join(exp_path, "config.json")):
-        with open(os.path.join(exp_path, "config.json")) as f:
-            off = int(json.load(f).get("training", {}).get("game_offset", 0))
+    _run_dirs(exp_path, "splay_iters.npy", "sampled-play analysis", "sampled_play", shards=False)
+    desc = _load_json(exp_path, "sampled_play.json")
+    off = _game_offset(exp_path, exp_path)
     g = sp.load_games(exp_path)
     cols = {"iters": g["iters"], "change": g["change"], "mass": g["mass"], "price": g["samp_price"], "agree": g["agree"]}
     for i in range(g["samp_reward"].shape[0]):
