@@ -175,6 +175,14 @@ size_t thrl_replay_mem_bytes(const thrl_cfg* cfg);
 size_t thrl_workspace_bytes(const thrl_cfg* cfg);
 /* which kernel THRL_KERNEL_AUTO would pick for this config (thrl_kernel) */
 int    thrl_select_kernel(const thrl_cfg* cfg, int injected);
+/* Host-only query: 1 when a launch of the wave kernel's plain float32 variant on this config builds its play tables in
+ * closed form -- on the payoff grid the next row (float32 and float64 encode alike) is the local row
+ * c - m0 * a0 - m1 * a1 for every action pair, and the config is noise-free with float32 tables, at most 62 reachable
+ * rows and one episode per training cycle; 0 otherwise (the payoff look-up table is used).  Same results either way.
+ * The answer is about the config: calls that run the GREEDY or a sweep variant, and the timing-only ablation builds
+ * (thrl_ablate_mask() != 0), use the look-up table whatever it says.
+ * out_c_m0_m1 (may be NULL) receives c, m0, m1 when the answer is 1. */
+int    thrl_wave_play_form(const thrl_cfg* cfg, int out_c_m0_m1[3]);
 /* Training cycle of the wave kernel: the replay buffers (buffers.py:12-19) reach min_memory every k-th
  * episode (agents.py:60), k = ceil(min_memory / max_steps); a call runs on the wave kernel when its
  * n_episodes is a multiple of k and the buffers are empty on entry (thrl_run.mem_count == 0), otherwise on

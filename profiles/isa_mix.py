@@ -10,7 +10,7 @@ operation whose sources are all VGPRs issues every ~2.3 cycles per SIMD, everyth
 float64) every ~4.1, v_permlane32_swap 8.1.  `SQ_ACTIVE_INST_VALU` cannot tell them apart either: it counts
 exactly 4 cycles per instruction of ANY class (8 for the swap) -- measured under the same microbenchmark,
 profiles/r03_ubench_pmc_summary.csv.  So the mix comes from the ISA: this script compiles the translation unit of
-the headline variant (k_wave_episodes<float,2,1,false,false,false,false>, thrl_wave_f32.hip) to assembly with the
+the headline variant (k_wave_episodes<float,2,1,false,false,false,false,false,true>, thrl_wave_f32a.hip) to assembly with the
 library's own flags and classifies every VALU instruction by its operand form.  The hot loops are straight-line
 unrolled code, so the static mix of the kernel body is used as the estimate of the dynamic one; bench.py prints the
 resulting price together with the two bounds (everything fast / everything slow).
@@ -27,7 +27,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # (translation unit, regular expression over the mangled kernel name, key in the output)
-KERNELS = [("thrl_wave_f32.hip", r"k_wave_episodesIfLi2ELi1ELb0ELb0ELb0ELb0E(Lb0E)*E", "k_wave_episodes<float,2,1> (headline)"),
+# (the headline configuration's payoff grid is affine: its launches run the closed-form instantiation of thrl_wave_f32a.hip,
+#  AFFINE = the last template flag; the payoff-LUT instantiation of thrl_wave_f32.hip is listed beside it)
+KERNELS = [("thrl_wave_f32a.hip", r"k_wave_episodesIfLi2ELi1ELb0ELb0ELb0ELb0ELb0ELb1EE", "k_wave_episodes<float,2,1> (headline)"),
+           ("thrl_wave_f32.hip", r"k_wave_episodesIfLi2ELi1ELb0ELb0ELb0ELb0E(Lb0E)*E", "k_wave_episodes<float,2,1> (payoff LUT)"),
            ("thrl_mixed.hip", "k_mixed_waveIfLi1ELi24ELi2ELb0ELi2EE", "k_mixed_wave<float,NR=1,24,2,table> (QTable vs Reinforce)"),
            ("thrl_mixed.hip", "k_mixed_waveIfLi2ELi24ELi2ELb0ELi1EE", "k_mixed_wave<float,NR=2,24,2,memo> (2 x Reinforce)"),
            ("thrl_nn.hip", "k_nn_reinforce_trainILi24ELb0EE", "k_nn_reinforce_train<24,false>"),

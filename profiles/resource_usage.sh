@@ -6,7 +6,7 @@
 src=${1:-$(dirname "$0")/../th_rl_amd/csrc}
 tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
 cd "$src" || exit 1
-for f in thrl_wave_f32.hip thrl_wave_f32c.hip thrl_wave_f32g.hip thrl_wave_f32n.hip thrl_wave_f32nc.hip thrl_wave_f32s.hip \
+for f in thrl_wave_f32.hip thrl_wave_f32a.hip thrl_wave_f32c.hip thrl_wave_f32g.hip thrl_wave_f32n.hip thrl_wave_f32nc.hip thrl_wave_f32s.hip \
          thrl_wave_f64.hip thrl_wave_f64c.hip thrl_wave_f64g.hip thrl_wave_f64n.hip thrl_wave_f64nc.hip thrl_wave_f64s.hip \
          thrl_tuple_f32.hip thrl_tuple_f64.hip thrl_tuple_f32_noise.hip thrl_tuple_f64_noise.hip thrl_tuple_f32_sweep.hip \
          thrl_tuple_f64_sweep.hip; do

@@ -337,7 +337,7 @@ class SampledChainArgs(ctypes.Structure):
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
-    "thrl_replay_mem_bytes", "thrl_workspace_bytes", "thrl_select_kernel", "thrl_training_cycle", "thrl_qtable_init",
+    "thrl_replay_mem_bytes", "thrl_workspace_bytes", "thrl_select_kernel", "thrl_wave_play_form", "thrl_training_cycle", "thrl_qtable_init",
     "thrl_qtable_episodes", "thrl_play_greedy", "thrl_op_sample_action", "thrl_op_encode", "thrl_op_scale",
     "thrl_op_env_step", "thrl_op_td_update",
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
@@ -393,6 +393,9 @@ def load():
     L.thrl_table_offset.argtypes = [cfgp, ctypes.c_int]
     L.thrl_select_kernel.restype = ctypes.c_int
     L.thrl_select_kernel.argtypes = [cfgp, ctypes.c_int]
+    if hasattr(L, "thrl_wave_play_form"):       # (an older build loaded through THRL_LIB for an A/B run lacks it)
+        L.thrl_wave_play_form.restype = ctypes.c_int
+        L.thrl_wave_play_form.argtypes = [cfgp, ctypes.POINTER(ctypes.c_int * 3)]
     L.thrl_training_cycle.restype = ctypes.c_int
     L.thrl_training_cycle.argtypes = [cfgp]
     L.thrl_qtable_init.restype = ctypes.c_int

@@ -156,6 +156,9 @@ struct WavePlan {
     int row_lo, win_rows;
     int epk, replay_from;           // training cycle: episodes per train_net that trains, first kept transition
     int lut_bytes, game_lds_bytes, waves_per_block, blocks_per_cu;
+    // closed-form play tables (thrl_wave_kernel.h play_affine): both encodes of every action pair's price are the local row
+    // aff_c - aff_m0 * a0 - aff_m1 * a1, and the configuration is one the plain float32 kernel with one row register plays
+    int affine, aff_c, aff_m0, aff_m1;
 };
 
 // Per-device figures the launch geometry needs.  A read-only cache keyed by the HIP device id (filled
@@ -198,6 +201,15 @@ int env_wave_cap() {
     return cap;
 }
 
+// THRL_WAVE_AFFINE=0: diagnostic switch, keeps affine payoff grids on the payoff-LUT path (A/B runs inside one build);
+// read ONCE per process
+bool env_wave_affine() {
+    static std::once_flag once;
+    static bool on = true;
+    std::call_once(once, [] { if (const char* e = getenv("THRL_WAVE_AFFINE")) on = atoi(e) != 0; });
+    return on;
+}
+
 // Can the fused wave kernel run this config?  (DESIGN.md "wave kernel: eligibility")
 WavePlan plan_wave(const thrl_cfg* c, const thrl_run* run, bool injected) {
     WavePlan p;
@@ -232,6 +244,10 @@ WavePlan plan_wave(const thrl_cfg* c, const thrl_run* run, bool injected) {
     // of the price on the whole action grid; with noise the intercept ranges over [0.7a, a).
     int lo = 1 << 30, hi = -1;
     const double ratio = c->env_a / c->env_b;
+    // is the row affine in the action indices, row = rc - rm0 * a0 - rm1 * a1, under both encodes?  (noise-free price only;
+    // the slopes come from the pairs (1, 0) and (0, 1), every pair is then tested against them)
+    bool affine = !(c->noise_prob > 0.0);
+    int rc = 0, rm0 = 0, rm1 = 0;
     for (int a0 = 0; a0 < A; a0++)
         for (int a1 = 0; a1 < A; a1++) {
             double Q = 0.0;
@@ -248,6 +264,12 @@ WavePlan plan_wave(const thrl_cfg* c, const thrl_run* run, bool injected) {
                 if (r32 < lo) lo = r32;
                 if (r64 > hi) hi = r64;
                 if (r32 > hi) hi = r32;
+                if (z == 0 && affine) {                              // (a1 is the inner loop: (0,0), (0,1) ... come first)
+                    if (a0 == 0 && a1 == 0) rc = r32;
+                    else if (a0 == 0 && a1 == 1) rm1 = rc - r32;
+                    else if (a0 == 1 && a1 == 0) rm0 = rc - r32;
+                    if (r32 != r64 || r32 != rc - rm0 * a0 - rm1 * a1) affine = false;
+                }
             }
         }
     p.row_lo = lo;
@@ -257,6 +279,13 @@ WavePlan plan_wave(const thrl_cfg* c, const thrl_run* run, bool injected) {
     p.lut_bytes = L.lds_bytes;          // LDS-staged part of the LUT image
     p.game_lds_bytes = 2 * (p.win_rows + 2) * A * (c->q_dtype == 1 ? 8 : 4);
     if (c->q_dtype == 0 && !(c->noise_prob > 0.0)) p.game_lds_bytes += 256;       // per-step words of half a segment (thrl_wave_kernel.h kLdsMK)
+    // Closed-form play tables where the kLdsMK path would run outside training cycles: float32 tables, no noise, one row
+    // register, one episode per cycle with nothing dropped.  (Sweeps and the GREEDY variant are decided per call: launch_wave.)
+    // Non-negative slopes and rc - lo < 62 make every byte of the packed arithmetic stay inside its byte.
+    if (affine && rm0 >= 0 && rm1 >= 0 && c->q_dtype == 0 && p.win_rows + 2 <= 64 && p.epk == 1 && p.replay_from == 0 &&
+        rc - lo >= 0 && rc - lo < p.win_rows && rc - rm0 * (A - 1) - rm1 * (A - 1) >= lo && env_wave_affine()) {
+        p.affine = 1; p.aff_c = rc - lo; p.aff_m0 = rm0; p.aff_m1 = rm1;
+    }
     // choose waves/block to maximise resident waves per CU (LDS-bound); a block may take the whole CU's LDS
     int best_w = 0, best_total = 0, best_b = 0;
     const DevInfo dv = dev_info();
@@ -506,6 +535,14 @@ int thrl_select_kernel(const thrl_cfg* c, int injected) {
     return THRL_KERNEL_WAVE;
 }
 
+int thrl_wave_play_form(const thrl_cfg* c, int out_c_m0_m1[3]) {
+    if (validate(c) != THRL_OK) return 0;
+    const WavePlan p = plan_wave(c, nullptr, false);
+    if (!p.ok || !p.affine) return 0;
+    if (out_c_m0_m1) { out_c_m0_m1[0] = p.aff_c; out_c_m0_m1[1] = p.aff_m0; out_c_m0_m1[2] = p.aff_m1; }
+    return 1;
+}
+
 int thrl_training_cycle(const thrl_cfg* c) {
     if (validate(c) != THRL_OK) return 0;
     const WavePlan p = plan_wave(c, nullptr, false);
@@ -605,6 +642,7 @@ static int run_wave(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run, con
     a.G = c->n_games; a.T = c->max_steps; a.A = c->n_actions[0]; a.rows = c->n_states[0] + 1;
     a.row_lo = p.row_lo; a.win_rows = p.win_rows;
     a.epk = p.epk; a.replay_from = p.replay_from;
+    a.aff_on = p.affine; a.aff_c = p.aff_c; a.aff_m0 = p.aff_m0; a.aff_m1 = p.aff_m1;
     a.waves_per_block = p.waves_per_block;
     a.force_variant = force_variant;
     a.lut_bytes = p.lut_bytes; a.game_lds_bytes = p.game_lds_bytes;

@@ -96,6 +96,9 @@ struct WaveArgs {
     double* sw_eps; const double* sw_noise_prob;
     uint64_t seed, game_offset, first_episode;
     double eps[kWaveMaxEpisodes][2];
+    // closed-form play tables (thrl_api.hip plan_wave): on this payoff grid both encodes of the price are
+    // local row = aff_c - aff_m0 * a0 - aff_m1 * a1 for every action pair (at the end: the offsets above stay)
+    int32_t aff_on, aff_c, aff_m0, aff_m1;
 };
 
 // ---- fused kernel for 1-4 QTable agents with individual grids (thrl_tuple_kernel.h): state = action tuple
@@ -187,6 +190,7 @@ int launch_wave_lut(const WaveArgs& a, unsigned char* out, hipStream_t s);
 int launch_wave(const WaveArgs& a, int q_dtype, int grid, int block, size_t lds_bytes, hipStream_t s);
 // one translation unit per (table type, NOISE, SWEEP) family of k_wave_episodes instantiations
 int launch_wave_f32_plain(const WaveArgs& a, int grid, int block, size_t lds_bytes, hipStream_t s);
+int launch_wave_f32_plain_affine(const WaveArgs& a, int grid, int block, size_t lds_bytes, hipStream_t s);   // WaveArgs.aff_on: closed-form play tables
 int launch_wave_f32_noise(const WaveArgs& a, int grid, int block, size_t lds_bytes, hipStream_t s);
 int launch_wave_f32_sweep(const WaveArgs& a, int grid, int block, size_t lds_bytes, hipStream_t s);
 int launch_wave_f64_plain(const WaveArgs& a, int grid, int block, size_t lds_bytes, hipStream_t s);

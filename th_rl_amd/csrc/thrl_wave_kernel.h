@@ -566,6 +566,125 @@ __device__ __forceinline__ void cyclic_segment(const BlockOps<QT>& ops0, unsigne
     }
 }
 
+// ---- play phase of the AFFINE variants: one segment (up to 64 steps) of an episode ----------------------------------
+// On an affine payoff grid (thrl_api.hip plan_wave) the row after an action pair is  c - m0*a0 - m1*a1  (local rows,
+// float32 and float64 encodes alike), so "the next row if step t were played in row r" is
+//     nsr_t[r] = kb_t - (g0[r] & m0b_t) - (g1[r] & m1b_t)
+// with, per row r,  g_i[r] = m_i * (greedy action of agent i in row r)  and, per step t,
+//     m_ib_t = agent i explores in step t ? 0 : 0xFF,     kb_t = c - (explore0 ? m0*c0 : 0) - (explore1 ? m1*c1 : 0).
+// All of these are bytes (<= c <= 61), so the tables of FOUR consecutive steps are one dword per row: the step-side bytes of
+// steps 4g..4g+3 sit in three dwords (M0q, M1q, Kq) of the wave's 256-byte LDS area, 16 bytes per group, written once per
+// segment with byte stores (lane = step); a group's table is then
+//     Tq = Kq - (G0q & M0q) - (G1q & M1q)                 (lane = row; G_iq = g_i[r] in all four bytes)
+// after ONE uniform-address LDS read: two ands and two subtractions on VGPRs, no gather from the payoff LUT.
+// No borrow crosses a byte: in every byte  kb - (g0 & m0b)  and  kb - (g0 & m0b) - (g1 & m1b)  are at least the row that
+// the action pair (explore ? choice : greedy) leads to, which the plan guarantees to be >= 0 for every pair -- whatever
+// the neighbouring bytes hold.  (hipcc reassociates to Kq - ((G0q & M0q) + (G1q & M1q)): the same value mod 2^32, and the
+// sum is at most kb <= c in every byte, so it does not carry either.)  tests/test_wave_affine_host.py enumerates this.
+// Chain: byte j of Tq, read at the lane of the current row, is the row after step 4g+j; v_readlane takes the low six bits
+// of its lane select.  The four rows the steps were played in are recorded as the bytes of ONE word in lane 4g
+// (assembled on the scalar unit) and unpacked lane-parallel after the chain.
+// s: play row | train row << 8 on entry (they differ only in a launch's first step from a continuous price) and on exit;
+// returns seq: lane t = the state step t was played in, in the same 16-bit form.
+__device__ __forceinline__ uint32_t pack16(uint32_t lo, uint32_t hi) {      // lo | hi << 16 of two values < 2^16: one s_pack
+    typedef unsigned short v2h __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, v2h{(unsigned short)lo, (unsigned short)hi});
+}
+// lane L (an immediate) of `old` replaced by the uniform value `val`
+template <int L>
+__device__ __forceinline__ uint32_t writelane_imm(uint32_t old, uint32_t val) {
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(val), "n"(L));
+    return old;
+}
+template <int T0>
+__device__ __forceinline__ void chain_group_affine(uint32_t& sq, uint32_t& sc, uint32_t Tq) {
+    const uint32_t s1 = readlane_u(Tq, (int)sc) & 0xFFu;
+    const uint32_t s2 = (readlane_u(Tq, (int)s1) >> 8) & 0xFFu;
+    const uint32_t s3 = (readlane_u(Tq, (int)s2) >> 16) & 0xFFu;
+    const uint32_t s4 = readlane_u(Tq, (int)s3) >> 24;
+    const uint32_t w = pack16(sc, s2) | (pack16(s1, s3) << 8);                // s0 | s1 << 8 | s2 << 16 | s3 << 24
+    sq = writelane_imm<T0>(sq, w);
+    sc = s4;
+}
+__device__ __forceinline__ uint32_t play_affine(int seg, int n, int lane, uint32_t rw, uint32_t G0q, uint32_t G1q, unsigned mk_addr,
+                                                int c, int m0, int m1, int& s) {
+    const int s_entry = __builtin_amdgcn_readfirstlane(s);       // ("s" operands must be provably uniform)
+    {   // step side (lane = step): three bytes per step
+        const uint32_t kb = (uint32_t)c - ((rw & 1u) ? ((rw >> 8) & 0xFFu) * (uint32_t)m0 : 0u)
+                                        - ((rw & 2u) ? ((rw >> 16) & 0xFFu) * (uint32_t)m1 : 0u);
+        const unsigned ad = mk_addr + 16u * (unsigned)(lane >> 2) + (unsigned)(lane & 3);
+        lds_store<unsigned char>(ad, (rw & 1u) ? (unsigned char)0 : (unsigned char)0xFF);
+        lds_store<unsigned char>(ad + 4u, (rw & 2u) ? (unsigned char)0 : (unsigned char)0xFF);
+        lds_store<unsigned char>(ad + 8u, (unsigned char)kb);
+        __builtin_amdgcn_wave_barrier();
+    }
+    // the area is 8-byte aligned (plan_wave): two adjacent 8-byte reads, which hipcc issues as one ds_read2_b64
+    struct Q4 { v2u lo, hi; };
+    auto loadq = [&](int g) {
+        Q4 q;
+        q.lo = lds_load<v2u>(mk_addr + 16u * (unsigned)g);
+        q.hi = lds_load<v2u>(mk_addr + 16u * (unsigned)g + 8u);
+        return q;
+    };
+    auto make = [&](const Q4& q) {
+        asm volatile("" :: "v"(q.hi.y));      // (keeps the second read 8 bytes wide, so that the two merge)
+        return q.hi.x - (G0q & q.lo.x) - (G1q & q.lo.y);
+    };
+    uint32_t sq = 0u, sq_tail = 0u;           // sq: lane 4g = the four states of full group g; sq_tail: one state per lane
+    uint32_t sc = (uint32_t)s_entry & 0xFFu;     // the chain runs on the play row
+    // One group's chain.  The scheduling barriers around it keep the LDS read issued in front of it and the table built
+    // behind it where they are written: hipcc otherwise sinks the read to its first use and the chain waits for the LDS there.
+    auto chain4 = [&](auto t0c, const int nn, const uint32_t Tq) {
+        constexpr int t0 = decltype(t0c)::value;
+        __builtin_amdgcn_sched_barrier(0);
+        if (t0 + 4 <= nn) chain_group_affine<t0>(sq, sc, Tq);
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (t0 + j < nn) {
+                    sq_tail = writelane_u(sq_tail, sc * 0x101u, t0 + j);
+                    sc = (readlane_u(Tq, (int)sc) >> (8 * j)) & 0xFFu;
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // Pipeline: the step bytes of group g+2 are requested before group g's chain, and the table of group g+1 is built from
+    // bytes requested a whole chain earlier, right after group g's chain.  (Entering THRL_PLAYA2(G): Ta = table of group G,
+    // qb = bytes of group G+1.)
+    Q4 qa = loadq(0), qb = loadq(1);
+    uint32_t Ta = make(qa), Tb = 0u;
+#define THRL_PLAYA2(G, N_)                                                                   \
+    if ((G) * 4 < (N_)) {                                                                    \
+        if ((G) * 4 + 8 < (N_)) qa = loadq((G) + 2 < 15 ? (G) + 2 : 15);                     \
+        chain4(std::integral_constant<int, (G) * 4>(), (N_), Ta);                            \
+        if ((G) * 4 + 4 < (N_)) {                                                            \
+            Tb = make(qb);                                                                   \
+            if ((G) * 4 + 12 < (N_)) qb = loadq((G) + 3 < 15 ? (G) + 3 : 15);                \
+            chain4(std::integral_constant<int, (G) * 4 + 4>(), (N_), Tb);                    \
+            if ((G) * 4 + 8 < (N_)) Ta = make(qa);                                           \
+        }                                                                                    \
+    }
+#define THRL_PLAYA16(N_)                                                                     \
+    THRL_PLAYA2(0, N_) THRL_PLAYA2(2, N_) THRL_PLAYA2(4, N_) THRL_PLAYA2(6, N_)              \
+    THRL_PLAYA2(8, N_) THRL_PLAYA2(10, N_) THRL_PLAYA2(12, N_) THRL_PLAYA2(14, N_)
+    // full segments and the 36-step second segment of a 100-step episode run copies without the tests
+    if (n == 64) { THRL_PLAYA16(64) } else if (n == 36) { THRL_PLAYA16(36) } else { THRL_PLAYA16(n) }
+#undef THRL_PLAYA16
+#undef THRL_PLAYA2
+    s = (int)(sc * 0x101u);                    // after a step the play and the train row are the same
+    // unpack: lane t takes byte t & 3 of its quad's first lane
+    // (the s_nop: a DPP read of a VGPR that the chain's last v_writelane may just have written needs 2 wait states, and hipcc
+    //  does not look inside asm statements)
+    uint32_t qd;
+    asm("s_nop 1\n\tv_mov_b32_dpp %0, %1 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf" : "=v"(qd) : "v"(sq));
+    const uint32_t un = ((qd >> (8u * (unsigned)(lane & 3))) & 0xFFu) * 0x101u;
+    uint32_t out = lane < (n & ~3) ? un : sq_tail;
+    // the first step of the episode carries the entry state's own train row
+    if (seg == 0) out = writelane_imm<0>(out, (uint32_t)s_entry);
+    return out;
+}
+
 // LDS capacity allows 20 resident waves per CU for the headline window in float32, i.e. 5 per
 // SIMD: keep the register allocation at <= 96 VGPRs there (NSEG <= 2).  float64 tables are twice
 // the size (11 games per CU), so the register budget is relaxed there.
@@ -575,11 +694,16 @@ __device__ __forceinline__ void cyclic_segment(const BlockOps<QT>& ops0, unsigne
 // so the headline variant carries none of that state.
 // LOG: per-game log rows (thrl_buffers.game_reward_log / game_action_log).  A template flag, so the unlogged
 // variants compile exactly as without the store: with a run-time null test the headline launch lost 1.8 %.
-template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY = false, bool LOG = false>
+// AFFINE: closed-form play tables (WaveArgs.aff_*; plain float32 variants with one row register only): on a payoff grid
+// whose next row is affine in the two action indices, phases (b, c) build the next-row tables of four steps at once by
+// byte-parallel integer arithmetic instead of four gathers from the payoff LUT (play_affine below).
+template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY = false, bool LOG = false, bool AFFINE = false>
 __global__ void __launch_bounds__(1024)
 __attribute__((amdgpu_waves_per_eu(sizeof(QT) == 8 ? 3 : (NOISE ? 4 : (NSEG <= 2 ? 5 : 4)))))
 k_wave_episodes(const WaveArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(!AFFINE || (sizeof(QT) == 4 && !NOISE && !SWEEP && !CYCLE && !GREEDY && NRSEG == 1 && kAblate == 0),
+                  "closed-form play tables: plain float32 variants with one row register");
     constexpr bool kUnrollReplay = NSEG <= 2 && !(NOISE && sizeof(QT) == 8);     // (hipcc 7.2 cannot compile the unrolled float64 noise variant)
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -724,6 +848,7 @@ k_wave_episodes(const WaveArgs a) {
             //          two greedy byte offsets into the u16 payoff LUT: agent 0's (a0*A*2) in the low
             //          half, agent 1's (a1*2) in the high half.
             uint32_t AM[NRSEG], R[NRSEG];
+            uint32_t G0q = 0u, G1q = 0u;   // AFFINE: the row's greedy terms m0 * i0 and m1 * i1, each in all four bytes
 #pragma unroll
             for (int k = 0; k < NRSEG; k++) {
                 const int row = min(lane + 64 * k, W + 1);
@@ -755,6 +880,10 @@ k_wave_episodes(const WaveArgs a) {
                 if (kAblate & 16) { i0 = (uint32_t)(lane * 5) % (uint32_t)A; i1 = (uint32_t)(lane * 3) % (uint32_t)A; }
                 AM[k] = i0 | (i1 << 8);
                 R[k] = (i0 * (uint32_t)A * 2u) | (i1 << 17);
+                if constexpr (AFFINE) {                       // m * i <= aff_c <= 61: the product stays inside each byte
+                    G0q = i0 * ((uint32_t)a.aff_m0 * 0x01010101u);
+                    G1q = i1 * ((uint32_t)a.aff_m1 * 0x01010101u);
+                }
             }
             // "next row if a step in which NOBODY explores is played in row r": one table for the whole episode
             // (the tables are frozen during play).  A group of four such steps needs no per-step table at all --
@@ -820,6 +949,9 @@ k_wave_episodes(const WaveArgs a) {
                     nav[seg] = na;
                 }
                 rwv[seg] = rw;
+                if constexpr (AFFINE) {
+                    seq[seg] = play_affine(seg, n, lane, rw, G0q, G1q, mk_addr, a.aff_c, a.aff_m0, a.aff_m1, s);
+                } else {
                 // Per step (lane = step), what turns the rows' greedy offsets R into the LUT address of
                 // "the next row if this step were played in row r":
                 //   Mv keeps agent i's half of R iff agent i does NOT explore in this step,
@@ -995,6 +1127,7 @@ k_wave_episodes(const WaveArgs a) {
                     const uint32_t un = (lane & 1) ? (prev >> 16) : (sq & 0xFFFFu);
                     seq[seg] = lane < packed_end ? un : sq_tail;
                 }
+                }   // !AFFINE
             }
             const int s_end = s;
 
@@ -1334,9 +1467,9 @@ k_wave_episodes(const WaveArgs a) {
     a.partial[(size_t)wave_gid * 128 + 64 + lane] = acc_hi;
 }
 
-template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY, bool LOG>
+template <typename QT, int NSEG, int NRSEG, bool NOISE, bool SWEEP, bool CYCLE, bool GREEDY, bool LOG, bool AFFINE = false>
 static int launch_wave_t(const WaveArgs& a, int grid, int block, size_t lds, hipStream_t s) {
-    auto kern = k_wave_episodes<QT, NSEG, NRSEG, NOISE, SWEEP, CYCLE, GREEDY, LOG>;
+    auto kern = k_wave_episodes<QT, NSEG, NRSEG, NOISE, SWEEP, CYCLE, GREEDY, LOG, AFFINE>;
     if (lds > 64 * 1024) {                       // beyond the default dynamic-LDS limit (float64 tables: one block per CU)
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
