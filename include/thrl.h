@@ -1481,6 +1481,123 @@ typedef struct {
 } thrl_sampled_chain_args;
 int thrl_sampled_chain(const thrl_cfg* cfg, const thrl_sampled_chain_args* args, void* stream);
 
+/*
+ * thrl_sampled_noise_chain: sampled play UNDER DEMAND NOISE, the environment the reference ships
+ * (NoisyPriceState, noise_prob = 0.05): thrl_sampled_chain's chain of stochastic policies combined with
+ * thrl_tuple_stationary's model of the redrawn price.  With probability q = 1 - p the price after tuple t is its
+ * noise-free price (one of the D distinct prices); with probability p it is uniform on [0.7 a - u(t), a - u(t)) clipped
+ * at 0, where a network's probabilities live on a continuum: they are taken at Jn quadrature NODES.  Of a valid cfg
+ * only n_agents and n_actions are used; nothing of a batch is read or written, every input is read only.  G, T, D,
+ * a_i(t) and the ground rules are thrl_sampled_chain's: all arithmetic float64, every operation rounded once, every sum
+ * in the order written here.
+ *
+ * Nodes, computed by the caller (th_rl_amd.sampled_play.noise_tables) and only read here.  xn[0] = 0.0, the atom of the
+ * prices clipped to 0; xn[1 + k] = cell_x[k], the midpoints of thrl_tuple_stationary's J cells: Jn = args.n_nodes =
+ * J + 1 in [2, THRL_STAT_MAX_CELLS].  xn is what the caller hands to thrl_price_probs and thrl_price_policy and is not
+ * an argument here.  nn(t, 0) = z(t) / width, nn(t, 1 + k) = len_k(t) / width with thrl_tuple_stationary's len_k, z and
+ * width (the clipped mass has its own node instead of being lumped into cell 0), given as band_lo (device int32 [T]) and
+ * band (device double [T][W], W = args.band_w >= 1): nn(t, j) = band[t][j - band_lo[t]] for band_lo[t] <= j <
+ * band_lo[t] + W, else 0; any band_lo is safe.  noise_price (device double [T]) and noise_reward (device double [N][T])
+ * are thrl_tuple_stationary's.  node_w (device double [Jn]): 0 for the atom, cell_w for the cells.  grp_first,
+ * grp_perm, reward, scaled and price are thrl_sampled_chain's.
+ *
+ * Inputs per game.  prob[i], dpolicy, eps / eps_g exactly as in thrl_sampled_chain.  nprob[i] for the neural agents:
+ * device float32 [G][Jn][A_i], thrl_price_probs at xn (4-byte alignment suffices).  npolicy (device uint16 [G][N][Jn]),
+ * thrl_price_policy at xn, gn_i(j) = min(npolicy[g][i][j], A_i - 1): a QTable agent's greedy action is exact on every
+ * node (the atom sits in the row of cell 0).  noise_prob, or noise_prob_g (device double [G]) which then replaces it:
+ * p in [0, 1], zero allowed.  A scalar outside [0, 1] (NaN included) is THRL_ERR_BAD_CONFIG; such an entry of
+ * noise_prob_g or eps_g refuses that game only: iters = -1 and zeros.
+ *
+ * Probabilities.  P_i(k|d), S_i(d), Z(d) are thrl_sampled_chain's; Pn_i(k|j), Sn_i(j), Zn(j) are the same definitions
+ * on the node rows (nprob, gn).
+ *
+ * Start.  m_0 = 1 / T on every tuple; with THRL_SPN_START_TUPLE the unit mass on start[g] (outside [0, T): refused);
+ * with THRL_SPN_START_RESET the tuple played at a uniform price on [0, a):
+ *   m_0(t') = sum_j (((node_w(j) / Zn(j)) * Pn_0(a_0(t')|j)) * Pn_1(a_1(t')|j)) * ...   ascending j from 0.0, a j with
+ *             node_w(j) == 0 skipped
+ *
+ * One step from m:
+ *   M(d)   = sum over the t with row(t) = d of m(t)         ascending t from 0.0;   W(d) = M(d) / Z(d)
+ *   nu(j)  = sum_t m(t) * nn(t, j)                          ascending t from 0.0 (zero terms change nothing);
+ *   V(j)   = nu(j) / Zn(j)
+ *   Sd(t') = sum_d ((W(d) * P_0(a_0(t')|d)) * P_1(a_1(t')|d)) * ...      ascending d, a d with W(d) == 0.0 skipped
+ *   Sn(t') = sum_j ((V(j) * Pn_0(a_0(t')|j)) * Pn_1(a_1(t')|j)) * ...    ascending j, a j with V(j) == 0.0 skipped
+ *   s(t')  = q * Sd(t') + p * Sn(t')                        q = 1 - p
+ *   m'(t') = 0.5 * m(t') + 0.5 * s(t');   chg = max_t |m'(t) - m(t)|
+ * Stop after the first step with chg <= args.tol, or after args.max_iters steps.  With p = 0, s = 1.0 * Sd + 0.0 * Sn =
+ * Sd exactly: every output then has the bits of thrl_sampled_chain.
+ *
+ * Outputs, per game, from the last iterate (M, W, nu, V recomputed from it), every sum in ascending index from 0.0:
+ *   iters, change, mass  as in thrl_sampled_chain
+ *   samp_reward[i][g]    sum_t m(t) * (q * reward_i(t) + p * noise_reward_i(t))
+ *   samp_action[i][g]    sum_t m(t) * scaled_i(t)
+ *   samp_price[g]        sum_t m(t) * (q * price(t) + p * noise_price(t))
+ *   agree[g]             q * (sum_d ((W(d) * P_0(g_0(d)|d)) * ...)) + p * (sum_j ((V(j) * Pn_0(gn_0(j)|j)) * ...)),
+ *                        every index included
+ *   pi (optional, double [G][T])   m itself
+ *   max_jump (optional, double [G]), for EVERY game, refused or not: the maximum over the neural agents i, the adjacent
+ *                        nodes 1 <= j < Jn - 1 and the actions k of |Pn_i(k|j + 1) - Pn_i(k|j)| (the difference of the
+ *                        two float32 values in float64); 0 without a neural agent.  It is the midpoint rule's honesty
+ *                        figure: the quadrature takes a network's row as constant across a cell.
+ *
+ * Working set.  One 256-thread block per game in LDS: thrl_sampled_chain's working set, V (8 Jn), 2 Jn bytes per QTable
+ * agent (its node entries), and per neural agent two tile buffers of 4 (THRL_SPN_TILE A_i + 3) bytes: the node rows
+ * (4 Jn A_i bytes) are streamed through them in ascending j and Zn(j) is recomputed from the resident tile, not kept:
+ *   thrl_sampled_chain's sum + r16(8 Jn) + sum of r16(2 Jn) (QTable i) + sum of 2 r16(4 (64 A_i + 3)) (neural i)
+ * Above THRL_SP_MAX_LDS or the device's own limit the call returns THRL_ERR_UNSUPPORTED without launching.  QTable 21 x
+ * Reinforce 21 at Jn = 1,121 takes 79,232 bytes (two blocks per 160 KB CU); against a 32-action network at Jn = 1,121 a
+ * QTable of 27 actions (T = 864, D = 724, 153,696 bytes) fits and one of 28 (T = D = 896, 179,728 bytes) does not.
+ *
+ * Returns as thrl_sampled_chain, and THRL_ERR_BAD_CONFIG for n_nodes < 2, band_w < 1, a scalar noise_prob outside
+ * [0, 1] or NaN, or both start flags; THRL_ERR_UNSUPPORTED for n_nodes > THRL_STAT_MAX_CELLS or the working set;
+ * THRL_ERR_NULL for a missing nprob[i] of a neural agent, npolicy, band_lo, band, noise_price, noise_reward or node_w.
+ * Everything is decided from the shape before any pointer is dereferenced.
+ */
+#define THRL_SPN_START_TUPLE 1
+#define THRL_SPN_START_RESET 2
+#define THRL_SPN_TILE 64
+typedef struct {
+    int32_t n_games;                 /* G >= 1                                           */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t n_prices;                /* D in [1, T]: the distinct prices                 */
+    int32_t n_nodes;                 /* Jn in [2, THRL_STAT_MAX_CELLS]                   */
+    int32_t band_w;                  /* W >= 1                                           */
+    int32_t max_iters;               /* in [1, THRL_STAT_MAX_ITERS]                      */
+    int32_t flags;                   /* THRL_SPN_START_TUPLE or THRL_SPN_START_RESET     */
+    int32_t reserved;                /* 0                                                */
+    int32_t kind[THRL_MAXA];         /* 0 = QTable, 1 = Reinforce, 2 = ActorCritic (3 = CAC is refused) */
+    double  eps[THRL_MAXA];          /* QTable agents' epsilon in [0, 1], read when eps_g is NULL */
+    double  tol;                     /* >= 0                                             */
+    double  noise_prob;              /* in [0, 1], read when noise_prob_g is NULL        */
+    const double* eps_g;             /* device [N][G] or NULL                            */
+    const double* noise_prob_g;      /* device [G] or NULL                               */
+    const int32_t* start;            /* device [G], with THRL_SPN_START_TUPLE            */
+    const float* prob[THRL_MAXA];    /* device [G][D][A_i] for the neural agents         */
+    const float* nprob[THRL_MAXA];   /* device [G][Jn][A_i] for the neural agents        */
+    const uint16_t* dpolicy;         /* device [G][N][D]                                 */
+    const uint16_t* npolicy;         /* device [G][N][Jn]                                */
+    const int32_t* grp_first;        /* device [D + 1]                                   */
+    const int32_t* grp_perm;         /* device [T]                                       */
+    const double* reward;            /* device [N][T]                                    */
+    const double* scaled;            /* device [N][T]                                    */
+    const double* price;             /* device [T]                                       */
+    const int32_t* band_lo;          /* device [T]                                       */
+    const double* band;              /* device [T][W]                                    */
+    const double* noise_price;       /* device [T]                                       */
+    const double* noise_reward;      /* device [N][T]                                    */
+    const double* node_w;            /* device [Jn]                                      */
+    int32_t* iters;                  /* device [G]                                       */
+    double*  change;                 /* device [G]                                       */
+    double*  mass;                   /* device [G]                                       */
+    double*  samp_reward;            /* device [N][G]                                    */
+    double*  samp_action;            /* device [N][G]                                    */
+    double*  samp_price;             /* device [G]                                       */
+    double*  agree;                  /* device [G]                                       */
+    double*  pi;                     /* device [G][T] or NULL                            */
+    double*  max_jump;               /* device [G] or NULL                               */
+} thrl_sampled_noise_chain_args;
+int thrl_sampled_noise_chain(const thrl_cfg* cfg, const thrl_sampled_noise_chain_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -334,6 +334,30 @@ class SampledChainArgs(ctypes.Structure):
     ]
 
 
+SPN_START_TUPLE = 1
+SPN_START_RESET = 2
+SPN_TILE = 64
+
+
+class SampledNoiseChainArgs(ctypes.Structure):
+    """thrl_sampled_noise_chain_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("n_prices", ctypes.c_int32), ("n_nodes", ctypes.c_int32),
+        ("band_w", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("kind", ctypes.c_int32 * MAXA), ("eps", ctypes.c_double * MAXA), ("tol", ctypes.c_double),
+        ("noise_prob", ctypes.c_double),
+        ("eps_g", ctypes.c_void_p), ("noise_prob_g", ctypes.c_void_p), ("start", ctypes.c_void_p),
+        ("prob", ctypes.c_void_p * MAXA), ("nprob", ctypes.c_void_p * MAXA),
+        ("dpolicy", ctypes.c_void_p), ("npolicy", ctypes.c_void_p), ("grp_first", ctypes.c_void_p), ("grp_perm", ctypes.c_void_p),
+        ("reward", ctypes.c_void_p), ("scaled", ctypes.c_void_p), ("price", ctypes.c_void_p),
+        ("band_lo", ctypes.c_void_p), ("band", ctypes.c_void_p), ("noise_price", ctypes.c_void_p),
+        ("noise_reward", ctypes.c_void_p), ("node_w", ctypes.c_void_p),
+        ("iters", ctypes.c_void_p), ("change", ctypes.c_void_p), ("mass", ctypes.c_void_p),
+        ("samp_reward", ctypes.c_void_p), ("samp_action", ctypes.c_void_p), ("samp_price", ctypes.c_void_p),
+        ("agree", ctypes.c_void_p), ("pi", ctypes.c_void_p), ("max_jump", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -346,6 +370,7 @@ SYMBOLS = [
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
     "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary", "thrl_price_probs", "thrl_sampled_chain",
+    "thrl_sampled_noise_chain",
 ]
 CAC_PARAMS = 1283
 
@@ -477,6 +502,8 @@ def load():
     L.thrl_price_probs.argtypes = [cfgp, ctypes.POINTER(PriceProbsArgs), vp]
     L.thrl_sampled_chain.restype = ctypes.c_int
     L.thrl_sampled_chain.argtypes = [cfgp, ctypes.POINTER(SampledChainArgs), vp]
+    L.thrl_sampled_noise_chain.restype = ctypes.c_int
+    L.thrl_sampled_noise_chain.argtypes = [cfgp, ctypes.POINTER(SampledNoiseChainArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -351,7 +351,8 @@ class AnalysisMethods:
                       tuple_policy=tuple_policy, cell_policy=cell_policy, n_games=n_games, tabs=tabs)
 
     def sampled_play(self, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None,
-                     tuple_policy=None, probs=None, dpolicy=None, tabs=None):
+                     tuple_policy=None, probs=None, dpolicy=None, tabs=None, noise_prob=0.0, resolution=1024, nprobs=None,
+                     npolicy=None):
         """The exact long-run profit of SAMPLED play (sampled_play.run, thrl_price_probs + thrl_sampled_chain): every
         agent plays the way it was trained -- a Reinforce / ActorCritic agent samples its softmax, a QTable agent is
         epsilon-greedy (epsilon: "current" = the batch's epsilon now, a number, one per agent, or an array [N, G]) --
@@ -359,11 +360,15 @@ class AnalysisMethods:
         samp_price, agree [G] (the share of steps on which every agent plays its greedy action), samp_reward,
         samp_action [N, G], with pi the distribution [G, T].  start: "uniform", "state" or int [G] start tuples.  A batch
         with a CAC agent or more than 4096 action tuples raises ValueError; a working set above a CU's LDS is
-        THRL_ERR_UNSUPPORTED."""
+        THRL_ERR_UNSUPPORTED.  Under demand noise (noise_prob: a number in (0, 1], an array [G], or None = the batch's
+        own; the number 0.0, the default, is the noise-free call; thrl_sampled_noise_chain) the price is redrawn with that probability and the networks are taken at the
+        nodes of `resolution` uniform cells of the price axis (nprobs, npolicy: the strategies there); there start "reset" is
+        the environment's reset distribution; the result also holds noise_prob and max_jump [G]."""
         from . import sampled_play as sp
         self._ready()
         return sp.run(self, epsilon=epsilon, start=start, tol=tol, max_iters=max_iters, pi=pi, n_games=n_games,
-                      tuple_policy=tuple_policy, probs=probs, dpolicy=dpolicy, tabs=tabs)
+                      tuple_policy=tuple_policy, probs=probs, dpolicy=dpolicy, tabs=tabs, noise_prob=noise_prob,
+                      resolution=resolution, nprobs=nprobs, npolicy=npolicy)
 
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),

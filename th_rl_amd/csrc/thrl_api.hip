@@ -21,6 +21,7 @@
 #include "thrl_tuple_attractors.h"
 #include "thrl_tuple_play.h"
 #include "thrl_sampled.h"
+#include "thrl_sampled_noise.h"
 #include "thrl_tuple_stationary.h"
 #include "thrl_wave_lut.h"
 
@@ -2084,6 +2085,88 @@ int thrl_sampled_chain(const thrl_cfg* c, const thrl_sampled_chain_args* x, void
     const int grid = (int)(want < a.G ? want : a.G);
     const int e = thrl::launch_sampled_chain(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_sp_chain launch") : THRL_OK;
+}
+
+int thrl_sampled_noise_chain(const thrl_cfg* c, const thrl_sampled_noise_chain_args* x, void* stream) {
+    static_assert(THRL_SPN_TILE == thrl::kSpnTile, "include/thrl.h and thrl_sampled_noise.h disagree on the tile");
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // every host-visible argument is checked, and the working set planned, before any pointer is looked at
+    if (x->n_games < 1) return fail(THRL_ERR_BAD_CONFIG, "n_games=%d must be >= 1", x->n_games);
+    if (x->flags & ~(THRL_SPN_START_TUPLE | THRL_SPN_START_RESET)) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if ((x->flags & THRL_SPN_START_TUPLE) && (x->flags & THRL_SPN_START_RESET))
+        return fail(THRL_ERR_BAD_CONFIG, "THRL_SPN_START_TUPLE and THRL_SPN_START_RESET are both set");
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (x->n_prices < 1 || x->n_prices > x->n_tuples)
+        return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", x->n_prices, x->n_tuples);
+    if (x->n_nodes < 2 || x->band_w < 1)
+        return fail(THRL_ERR_BAD_CONFIG, "n_nodes=%d must be >= 2 and band_w=%d >= 1", x->n_nodes, x->band_w);
+    if (x->max_iters < 1 || x->max_iters > THRL_STAT_MAX_ITERS)
+        return fail(THRL_ERR_BAD_CONFIG, "max_iters=%d out of [1,%d]", x->max_iters, THRL_STAT_MAX_ITERS);
+    if (!(x->tol >= 0.0)) return fail(THRL_ERR_BAD_CONFIG, "tol=%g must be >= 0", x->tol);
+    if (!x->eps_g)
+        for (int i = 0; i < N; i++)
+            if (x->kind[i] == 0 && !(x->eps[i] >= 0.0 && x->eps[i] <= 1.0))
+                return fail(THRL_ERR_BAD_CONFIG, "eps[%d]=%g out of [0, 1]", i, x->eps[i]);
+    if (!x->noise_prob_g && !(x->noise_prob >= 0.0 && x->noise_prob <= 1.0))
+        return fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of [0, 1]", x->noise_prob);
+    if (x->n_nodes > THRL_STAT_MAX_CELLS)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_noise_chain: n_nodes=%d, at most %d", x->n_nodes, THRL_STAT_MAX_CELLS);
+    thrl::SpnArgs a;
+    memset(&a, 0, sizeof(a));
+    SpArgs& sa = a.sp;
+    sa.G = x->n_games; sa.N = N; sa.T = x->n_tuples; sa.D = x->n_prices;
+    sa.max_iters = x->max_iters; sa.start_tuple = (x->flags & THRL_SPN_START_TUPLE) != 0;
+    sa.tol = x->tol;
+    a.Jn = x->n_nodes; a.W = x->band_w; a.start_reset = (x->flags & THRL_SPN_START_RESET) != 0;
+    a.noise_prob = x->noise_prob;
+    int ts = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        sa.kind[i] = x->kind[i];
+        sa.n_actions[i] = c->n_actions[i];
+        sa.tstride[i] = ts;
+        ts *= c->n_actions[i];
+        sa.eps[i] = x->eps[i];
+        sa.prob[i] = x->prob[i];
+        a.nprob[i] = x->nprob[i];
+    }
+    const int64_t lds = thrl::spn_layout(a);         // the working set of include/thrl.h
+    if (lds > THRL_SP_MAX_LDS)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_noise_chain: %lld bytes of LDS per game (T=%d, n_prices=%d, n_nodes=%d), at most %d",
+                    (long long)lds, sa.T, sa.D, a.Jn, THRL_SP_MAX_LDS);
+    for (int i = 0; i < N; i++)
+        if (x->kind[i] != 0 && (!x->prob[i] || !x->nprob[i])) return fail(THRL_ERR_NULL, "prob[%d] / nprob[%d] is NULL", i, i);
+    if (!x->dpolicy || !x->npolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->scaled || !x->price)
+        return fail(THRL_ERR_NULL, "dpolicy / npolicy / grp_first / grp_perm / reward / scaled / price is NULL");
+    if (!x->band_lo || !x->band || !x->noise_price || !x->noise_reward || !x->node_w)
+        return fail(THRL_ERR_NULL, "band_lo / band / noise_price / noise_reward / node_w is NULL");
+    if (!x->iters || !x->change || !x->mass || !x->samp_reward || !x->samp_action || !x->samp_price || !x->agree)
+        return fail(THRL_ERR_NULL, "iters / change / mass / samp_reward / samp_action / samp_price / agree is NULL");
+    if (sa.start_tuple && !x->start) return fail(THRL_ERR_NULL, "start is NULL with THRL_SPN_START_TUPLE");
+    sa.eps_g = x->eps_g; sa.start = x->start; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm;
+    sa.reward = x->reward; sa.scaled = x->scaled; sa.price = x->price;
+    sa.iters = x->iters; sa.change = x->change; sa.mass = x->mass; sa.samp_reward = x->samp_reward;
+    sa.samp_action = x->samp_action; sa.samp_price = x->samp_price; sa.agree = x->agree; sa.pi = x->pi;
+    a.noise_prob_g = x->noise_prob_g; a.npolicy = x->npolicy; a.band_lo = x->band_lo; a.band = x->band;
+    a.noise_price = x->noise_price; a.noise_reward = x->noise_reward; a.node_w = x->node_w; a.max_jump = x->max_jump;
+    int dev = 0, cus = 0, lds_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
+        || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess)
+        return hip_fail((int)hipGetLastError(), "device attributes");
+    if (lds_cu > 0 && sa.lds_bytes > lds_cu)
+        return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_noise_chain: %d bytes of LDS per game (T=%d, n_prices=%d, n_nodes=%d), the device has %d",
+                    sa.lds_bytes, sa.T, sa.D, a.Jn, lds_cu);
+    int per_cu = kSpMaxBlocksPerCu;
+    if (lds_cu > 0 && lds_cu / sa.lds_bytes < per_cu) per_cu = lds_cu / sa.lds_bytes > 0 ? lds_cu / sa.lds_bytes : 1;
+    const int64_t want = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+    const int grid = (int)(want < sa.G ? want : sa.G);
+    const int e = thrl::launch_sampled_noise_chain(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_spn_jump / k_spn_chain launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -14,27 +14,11 @@
 //   follow k_ts_chain: chunks of 64 tuples, one lane per tuple for the products, then one lane per output reading them
 //   back in ascending t; `agree` is one more lane over the D terms parked in the dead iterate.
 //   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
-#include "thrl_sampled.h"
+#include "thrl_sampled_dev.h"
 
 namespace thrl {
 
 namespace {
-
-struct SpCst {                                   // per game, per QTable agent: eps / A and (1 - eps) + eps / A
-    double lo[kSpMaxA], hi[kSpMaxA];
-    double red[16];                              // the second level of the maximum
-};
-
-// M(d) over the tuples of price d in ascending t, W(d) = M(d) / Z(d)
-__device__ __forceinline__ void sp_weights(const SpArgs& a, const double* m, const uint16_t* first, const uint16_t* perm,
-                                           const double* Z, double* W, int tid) {
-    for (int d = tid; d < a.D; d += kSpBlock) {
-        double M = 0.0;
-        const int e = first[d + 1];
-        for (int s = first[d]; s < e; s++) M = __dadd_rn(M, m[perm[s]]);
-        W[d] = __ddiv_rn(M, Z[d]);
-    }
-}
 
 template <int MAXN>
 __device__ __forceinline__ void sp_block(const SpArgs& a, unsigned char* s_mem, int tid, int bid, int nblk) {

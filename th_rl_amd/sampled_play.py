@@ -13,8 +13,16 @@ the tuples by price); the device only reads them.  price_probs() evaluates the n
 run() iterates the chain and returns per game (definitions in include/thrl.h) iters, change, mass, samp_price, agree [G],
 samp_reward, samp_action [N, G], optionally pi [G, T].  `agree` is the long-run share of steps on which every agent plays
 its greedy action.  summarize() gives per group converged, iters_*, delta_sampled_* (the profit gain of sampled play),
-agree_mean and price_mean.  Demand noise, the reset distribution as a start, sharded runs (th_rl_amd.launch) and CAC
-agents are out of scope.
+agree_mean and price_mean.  Sharded runs (th_rl_amd.launch) and CAC agents are out of scope.
+
+Under demand noise (noise_prob > 0, NoisyPriceState) the next price is with probability p uniform on the tuple's band
+of the price axis (tuple_stationary.py), where a network's probabilities live on a continuum: noise_tables(config,
+resolution) gives the quadrature nodes (price 0, the atom of the clipped prices, and tuple_stationary's cell midpoints)
+with their weights per tuple, and run(noise_prob=..., resolution=...) iterates thrl_sampled_noise_chain, which combines
+both halves of the step; there start="reset" is the environment's reset distribution.  max_jump per game, the largest change
+of a network's probability between adjacent nodes, says how honest the midpoint rule is.  With noise_prob = 0.0, the
+default, everything here is the noise-free call as it was (and "reset" is no start of it); in train_one the noisy mode is
+the sub-dict "noise" of training.sampled_play, so that every option dict valid before parses to what it did.
 """
 import ctypes
 import os
@@ -29,12 +37,16 @@ from ._lib import ThrlError
 from .deviation import optimal, profit_gain
 
 DEFAULTS = dict(epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False)
+NOISE_DEFAULTS = dict(noise_prob=None, resolution=1024)
 STARTS = ("uniform", "state")
+NOISE_STARTS = STARTS + ("reset",)
+MAX_CELLS = _lib.STAT_MAX_CELLS
+TILE = _lib.SPN_TILE
 MAX_PRICES = _lib.STAT_MAX_CELLS
 MAX_LDS = _lib.SP_MAX_LDS
 GAME_FLOAT = ("change", "mass", "samp_price", "agree")
 AGENT_FLOAT = ("samp_reward", "samp_action")
-PER_GAME = ("iters", "start", "epsilon") + GAME_FLOAT + AGENT_FLOAT + ("pi",)
+PER_GAME = ("iters", "start", "epsilon", "noise_prob", "max_jump") + GAME_FLOAT + AGENT_FLOAT + ("pi",)
 
 
 def _check_eps(e, what):
@@ -46,10 +58,21 @@ def _check_eps(e, what):
 def parse_options(opt, config):
     """training.sampled_play (true or a dict) -> the dict with every key filled in: epsilon ("current": the QTable
     agents' epsilon where training stopped; a number, or one per agent), start ("uniform" or "state"), tol, max_iters,
-    pi (store the distributions).  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples and a working set above a
-    CU's LDS."""
+    pi (store the distributions).  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
+    run's own noise, refused for a noise-free run as training.greedy_stationary does; "resolution": the uniform cuts of
+    the price axis behind the nodes}) asks for play under demand noise; it stays in the result, filled in, only when
+    given, and with it start may be "reset".  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples, more than
+    MAX_CELLS - 1 cells and a working set above a CU's LDS."""
     name = "training.sampled_play"
     tp.check_config(config)
+    noise = None
+    if isinstance(opt, dict) and "noise" in opt:
+        opt = dict(opt)
+        noise = opt.pop("noise")
+        if noise is None or noise is False:
+            noise = None
+        else:
+            noise = an.options("sampled_play.noise", noise, NOISE_DEFAULTS)
     out = an.options("sampled_play", opt, DEFAULTS)
     e = out["epsilon"]
     if isinstance(e, (list, tuple)):
@@ -58,8 +81,9 @@ def parse_options(opt, config):
         out["epsilon"] = [_check_eps(x, name + ".epsilon") for x in e]
     elif e != "current":
         out["epsilon"] = _check_eps(e, name + ".epsilon")
-    if out["start"] not in STARTS:
-        raise ValueError("%s.start must be one of %s, got %r" % (name, STARTS, out["start"]))
+    starts = STARTS if noise is None else NOISE_STARTS
+    if out["start"] not in starts:
+        raise ValueError("%s.start must be one of %s, got %r" % (name, starts, out["start"]))
     if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float)) or not out["tol"] >= 0.0:
         raise ValueError("%s.tol must be a number >= 0, got %r" % (name, out["tol"]))
     out["tol"] = float(out["tol"])
@@ -72,7 +96,32 @@ def parse_options(opt, config):
     if not ws["fits"]:
         raise ValueError("%s: a game's working set is %d bytes (T=%d, D=%d), a CU's LDS holds %d"
                          % (name, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
+    if noise is not None:
+        from . import tuple_stationary as ts
+        if noise["noise_prob"] is None:     # the run's own noise: refuse a noise-free run before training
+            env = dict(_lib.ENV_DEFAULTS, **config["environment"])
+            sweep = config.get("training", {}).get("sweep") or {}
+            if float(env["noise_prob"]) == 0.0 and "noise_prob" not in sweep:
+                raise ValueError("%s.noise: the environment has noise_prob = 0: give the noise_prob to analyse" % name)
+        else:
+            noise["noise_prob"] = _check_eps(noise["noise_prob"], name + ".noise.noise_prob")
+        noise["resolution"] = ts._check_resolution(noise["resolution"], name + ".noise.resolution")
+        try:
+            ws = working_set(config, resolution=noise["resolution"])
+        except ValueError as e:
+            raise ValueError("%s.noise: %s" % (name, e))
+        if not ws["fits"]:
+            raise ValueError("%s.noise: under noise a game's working set is %d bytes (T=%d, D=%d, Jn=%d), a CU's LDS holds %d"
+                             % (name, ws["bytes"], ws["T"], ws["D"], ws["Jn"], MAX_LDS))
+        out["noise"] = noise
     return out
+
+
+def noisy(noise_prob):
+    """True when thrl_sampled_noise_chain runs: any noise_prob (None, an array, a number) but the number 0.0."""
+    plain = isinstance(noise_prob, (int, float, np.integer, np.floating)) and not isinstance(noise_prob, bool) \
+        and float(noise_prob) == 0.0
+    return not plain
 
 
 # ---------------------------------------------------------------------------------------------- the per-config tables
@@ -100,17 +149,58 @@ def _r16(x):
     return (int(x) + 15) & ~15
 
 
-def working_set(config, tabs=None):
+def working_set(config, tabs=None, resolution=None, n_nodes=None):
     """The LDS bytes one game takes in thrl_sampled_chain, by include/thrl.h's formula: the sum of r16(x) over 8 T, 8 T
     (the iterates), 8 D, 8 D (W, Z), 4 D A_i per network, 2 D per QTable agent, 2 (D + 1), 2 T (the grouping),
-    512 (2 N + 2) (staging) and 256 (constants).  Returns dict(bytes, T, D, fits): fits = within a CU's 160 KB."""
+    512 (2 N + 2) (staging) and 256 (constants).  Returns dict(bytes, T, D, fits): fits = within a CU's 160 KB.  With
+    resolution (or n_nodes) the working set of thrl_sampled_noise_chain (spn_layout): beside that, r16(8 Jn) for V,
+    r16(2 Jn) per QTable agent and two tile buffers of r16(4 (TILE A_i + 3)) per network; the dict also holds Jn.
+    More than MAX_CELLS - 1 cells is a ValueError."""
     tabs = tables(config) if tabs is None else tabs
     T, D, N = int(tabs["n_tuples"]), int(tabs["n_prices"]), len(tabs["kinds"])
     b = 2 * _r16(8 * T) + 2 * _r16(8 * D)
     for kind, A in zip(tabs["kinds"], tabs["n_actions"]):
         b += _r16(2 * D) if kind == "QTable" else _r16(4 * D * int(A))
     b += _r16(2 * (D + 1)) + _r16(2 * T) + _r16(512 * (2 * N + 2)) + 256
-    return dict(bytes=int(b), T=T, D=D, fits=b <= MAX_LDS)
+    if resolution is None and n_nodes is None:
+        return dict(bytes=int(b), T=T, D=D, fits=b <= MAX_LDS)
+    Jn = int(n_nodes) if n_nodes is not None else n_nodes_of(config, resolution)
+    b += _r16(8 * Jn)
+    for kind, A in zip(tabs["kinds"], tabs["n_actions"]):
+        b += _r16(2 * Jn) if kind == "QTable" else 2 * _r16(4 * (TILE * int(A) + 3))
+    return dict(bytes=int(b), T=T, D=D, Jn=Jn, fits=b <= MAX_LDS)
+
+
+def n_nodes_of(config, resolution):
+    """Jn = the cells of tuple_stationary.cuts(config, resolution) plus the atom; ValueError above MAX_CELLS."""
+    from . import tuple_stationary as ts
+    J = int(ts.cuts(config, resolution).size - 1)
+    if J + 1 > MAX_CELLS:
+        raise ValueError("sampled_play: resolution=%d gives %d cells, at most %d (the atom of the clipped prices is one "
+                         "more node)" % (resolution, J, MAX_CELLS - 1))
+    return J + 1
+
+
+def noise_tables(config, resolution=NOISE_DEFAULTS["resolution"], tabs=None):
+    """The per-config tables of thrl_sampled_noise_chain (include/thrl.h): tables(config)'s arrays, and over the nodes
+    xn [Jn] (0.0, the atom of the prices clipped to 0, then tuple_stationary's cell midpoints): node_w [Jn] (0, then
+    cell_w), nn [T, Jn] (nn(t, 0) = z(t) / width, nn(t, 1 + k) = len_k(t) / width with tuple_stationary's len_k, z and
+    width) as band_lo int32 [T] and band [T, W]; noise_price [T] and noise_reward [N, T] (tuple_stationary.tables');
+    n_nodes, n_cells, band_w, resolution."""
+    from . import tuple_stationary as ts
+    out = dict(tables(config) if tabs is None else tabs)
+    Jn = n_nodes_of(config, resolution)
+    c = ts.cuts(config, resolution)
+    geo = ts.noise_geometry(config, tp.tables(config), c)
+    nn = np.concatenate([geo["z"][:, None], geo["length"]], axis=1) / geo["width"]
+    band_lo, band = ts.band_of(nn)
+    nprice = np.ascontiguousarray(geo["noise_price"])
+    out.update(xn=np.concatenate([[0.0], geo["cell_x"]]), node_w=np.concatenate([[0.0], geo["cell_w"]]), nn=nn,
+               band_lo=band_lo, band=band, noise_price=nprice,
+               noise_reward=np.ascontiguousarray(nprice[None, :] * geo["quantity"]), cell_x=np.ascontiguousarray(geo["cell_x"]),
+               cell_w=np.ascontiguousarray(geo["cell_w"]), n_nodes=Jn, n_cells=Jn - 1, band_w=int(band.shape[1]),
+               resolution=int(resolution))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- the device calls
@@ -184,39 +274,86 @@ def resolve_epsilon(batch, epsilon, G):
     return e, None
 
 
+def resolve_noise(batch, noise_prob, G):
+    """(scalar or None, device float64 [G] or None) for run()'s noise_prob: None = the batch's per-game sweep array if it
+    has one, else the config's value (0 asks for an explicit one, as stationary.resolve_noise does); a number in [0, 1];
+    or an array / tensor [G] (device data: an entry outside [0, 1] refuses that game)."""
+    import torch
+    if noise_prob is None:
+        sw = getattr(batch, "sweep", None) or {}
+        if "noise_prob" in sw:
+            return None, sw["noise_prob"][:G].to(torch.float64).contiguous()
+        noise_prob = float(batch.cfg.noise_prob)
+        if noise_prob == 0.0:
+            raise ThrlError("sampled_play: the batch was configured without env noise (noise_prob = 0): pass the "
+                            "noise_prob to analyse explicitly")
+    if isinstance(noise_prob, torch.Tensor):
+        arr = noise_prob.to(device=batch.device, dtype=torch.float64).reshape(-1)[:G].contiguous()
+    elif np.ndim(noise_prob) > 0:
+        arr = torch.from_numpy(np.ascontiguousarray(np.asarray(noise_prob, np.float64).reshape(-1)[:G])).to(batch.device)
+    else:
+        p = float(noise_prob)
+        if not 0.0 <= p <= 1.0:
+            raise ThrlError("sampled_play: noise_prob=%r out of [0, 1]" % (noise_prob,))
+        return p, None
+    if arr.numel() != G:
+        raise ThrlError("sampled_play: noise_prob must hold %d values" % G)
+    return None, arr
+
+
 def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None, tuple_policy=None,
-        probs=None, dpolicy=None, tabs=None):
+        probs=None, dpolicy=None, tabs=None, noise_prob=0.0, resolution=NOISE_DEFAULTS["resolution"], nprobs=None, npolicy=None):
     """thrl_sampled_chain for the first n_games (default all) games of `batch` (a MixedGameBatch of QTable / Reinforce /
     ActorCritic agents, or a GameBatch).  epsilon: resolve_epsilon's rules.  start: "uniform" (1 / T on every tuple),
     "state" (the tuple whose price is the state the batch holds, tuple_play.start_tuples; a game whose state is no
     tuple's price is refused with iters = -1), or int [G] start tuples (outside [0, T): refused).  probs / dpolicy: the
     strategies at tabs["dprice"] ({i: float32 [G, D, A_i]} of price_probs, int16 [G, N, D] of
     tuple_stationary.price_policy; default: evaluated here; tuple_policy, tuple_play.extract()'s tensor, gives dpolicy
-    without a device call, the tuple prices being the distinct prices repeated).  Returns a dict of numpy arrays."""
+    without a device call, the tuple prices being the distinct prices repeated).
+
+    noise_prob = 0.0 (the number) is that call and nothing else.  Otherwise thrl_sampled_noise_chain runs: noise_prob a
+    number in (0, 1], an array [G] with entries in [0, 1] (zeros: the noise-free chain through the noisy call), or None
+    (the batch's own: resolve_noise); start may then be "reset" = the tuple played at a uniform price on [0, a); resolution: the uniform cuts behind the nodes; tabs: noise_tables(batch.config,
+    resolution); nprobs / npolicy: the strategies at tabs["xn"] ({i: float32 [G, Jn, A_i]} of price_probs, int16
+    [G, N, Jn] of tuple_stationary.price_policy; default: evaluated here).  The result then also holds noise_prob and
+    max_jump [G], n_nodes and resolution.  Returns a dict of numpy arrays."""
     import torch
     from . import tuple_stationary as ts
     N = batch.N
     G = _games(batch, n_games)
     given_start = not isinstance(start, str)
-    if not given_start and start not in STARTS:
-        raise ThrlError("sampled_play: start must be one of %s or an array of tuples, got %r" % (STARTS, start))
+    noise = noisy(noise_prob)
+    starts = NOISE_STARTS if noise else STARTS
+    if not given_start and start not in starts:
+        raise ThrlError("sampled_play: start must be one of %s or an array of tuples, got %r" % (starts, start))
     if isinstance(max_iters, bool) or not 1 <= int(max_iters) <= _lib.STAT_MAX_ITERS:
         raise ThrlError("sampled_play: max_iters=%r out of [1, %d]" % (max_iters, _lib.STAT_MAX_ITERS))
+    if noise and (tabs is None or "xn" not in tabs):
+        tabs = noise_tables(batch.config, resolution, tabs=tabs)
     if tabs is None:
         tabs = tables(batch.config)
     tp._batch_tables(batch, tabs)
-    ws = working_set(batch.config, tabs)
-    if not ws["fits"]:                                   # what thrl_sampled_chain answers from the shape alone
-        err = ThrlError("thrl_sampled_chain refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d), at most %d"
-                        % (_lib.ERR_UNSUPPORTED, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
+    Jn, call = (int(tabs["n_nodes"]), "thrl_sampled_noise_chain") if noise else (None, "thrl_sampled_chain")
+    ws = working_set(batch.config, tabs, n_nodes=Jn)
+    if not ws["fits"]:                                   # what the call answers from the shape alone
+        err = ThrlError("%s refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d%s), at most %d"
+                        % (call, _lib.ERR_UNSUPPORTED, ws["bytes"], ws["T"], ws["D"], ", n_nodes=%d" % Jn if noise else "",
+                           MAX_LDS))
         err.code = _lib.ERR_UNSUPPORTED
         raise err
     kinds = tp._kinds(batch)
     dev = batch.device
     sdev = batch.state.device
     T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
-    a = _lib.SampledChainArgs()
+    a = _lib.SampledNoiseChainArgs() if noise else _lib.SampledChainArgs()
     a.n_games, a.n_tuples, a.n_prices, a.max_iters, a.tol = G, T, D, int(max_iters), float(tol)
+    tab_list = [("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32), ("reward", (N, T), np.float64),
+                ("scaled", (N, T), np.float64), ("price", (T,), np.float64)]
+    if noise:
+        W = int(tabs["band_w"])
+        a.n_nodes, a.band_w = Jn, W
+        tab_list += [("band_lo", (T,), np.int32), ("band", (T, W), np.float64), ("noise_price", (T,), np.float64),
+                     ("noise_reward", (N, T), np.float64), ("node_w", (Jn,), np.float64)]
     for i, k in enumerate(kinds):
         a.kind[i] = tp.KINDS[k]
     with torch.cuda.device(dev):
@@ -243,9 +380,30 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
                 raise ThrlError("sampled_play: probs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
             a.prob[i] = p.data_ptr()
         a.dpolicy = dpolicy.data_ptr()
+        p_noise = p_g = None
+        if noise:
+            p_noise, p_g = resolve_noise(batch, noise_prob, G)
+            if p_g is not None:
+                a.noise_prob_g = p_g.data_ptr()
+            else:
+                a.noise_prob = p_noise
+            if nprobs is None:
+                nprobs = price_probs(batch, tabs["xn"], n_games=G)
+            if npolicy is None:
+                npolicy = ts.price_policy(batch, tabs["xn"], n_games=G)
+            an.check_policy(batch, npolicy, (G, N, Jn), "sampled_play", "npolicy")
+            for i, k in enumerate(kinds):
+                if k == "QTable":
+                    continue
+                pn = nprobs.get(i)
+                shape = (G, Jn, int(batch.cfg.n_actions[i]))
+                if pn is None or tuple(pn.shape) != shape or pn.dtype != torch.float32 or pn.device != sdev \
+                        or not pn.is_contiguous():
+                    raise ThrlError("sampled_play: nprobs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
+                a.nprob[i] = pn.data_ptr()
+            a.npolicy = npolicy.data_ptr()
         keep = {}
-        for f, shape, dt in (("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32), ("reward", (N, T), np.float64),
-                             ("scaled", (N, T), np.float64), ("price", (T,), np.float64)):
+        for f, shape, dt in tab_list:
             x = np.ascontiguousarray(tabs[f], dt)
             if x.shape != shape:
                 raise ThrlError("sampled_play: table %s has shape %s, expected %s" % (f, x.shape, shape))
@@ -261,8 +419,10 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
                 raise ThrlError("sampled_play: start must hold %d tuples" % G)
         elif start == "state":
             t0 = tp.start_tuples(batch.state[:G], tabs).to(torch.int32).contiguous()
+        elif start == "reset":
+            a.flags = _lib.SPN_START_RESET
         if t0 is not None:
-            a.flags = _lib.SP_START_TUPLE
+            a.flags = _lib.SP_START_TUPLE                # THRL_SPN_START_TUPLE has the same value
             a.start = t0.data_ptr()
         f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
         out = {"iters": torch.zeros((G,), dtype=torch.int32, device=dev)}
@@ -270,26 +430,34 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
         out.update({f: f64(N, G) for f in AGENT_FLOAT})
         if pi:
             out["pi"] = f64(G, T)
+        if noise:
+            out["max_jump"] = f64(G)
         for f, t in out.items():
             setattr(a, f, t.data_ptr())
-        _lib.check(batch.L.thrl_sampled_chain(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
-                   "thrl_sampled_chain")
+        _lib.check(getattr(batch.L, call)(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()), call)
         torch.cuda.synchronize(dev)
         res = {f: t.cpu().numpy() for f, t in out.items()}
         res["epsilon"] = np.repeat(np.asarray(eps, np.float64)[:, None], G, axis=1) if eps_g is None else eps_g.cpu().numpy()
         if t0 is not None:
             res["start"] = t0.cpu().numpy()
+        if noise:
+            res["noise_prob"] = np.full(G, p_noise, np.float64) if p_g is None else p_g.cpu().numpy()
     res["T"], res["n_prices"], res["max_iters"], res["lds_bytes"] = T, D, int(max_iters), ws["bytes"]
+    if noise:
+        res["n_nodes"], res["resolution"] = Jn, int(tabs.get("resolution", resolution))
     return res
 
 
 # ---------------------------------------------------------------------------------------------- host side
-def summarize(games, ids, n_groups, nash, cartel, max_iters, cycle_reward=None):
+def summarize(games, ids, n_groups, nash, cartel, max_iters, cycle_reward=None, greedy_noise=None):
     """The summary rows, one per group: games, converged (solved and stopped before max_iters), iters_q25 / q50 / q75 /
     max, delta_sampled_mean / q25 / q50 / q75 (the profit gain of samp_reward, deviation.profit_gain), agree_mean,
     price_mean over the solved games.  cycle_reward [N, G] with lam [G] (the greedy cycles of the same run, where it has
     them): also delta_greedy_mean and randomness_cost_mean = delta_greedy - delta_sampled over the solved games that
-    have a greedy cycle."""
+    have a greedy cycle.  Games with max_jump (the noisy mode): also max_jump_max over the group's games, solved or not.
+    greedy_noise (stat_reward [N, G], iters [G]: greedy play under the same noise, training.greedy_stationary of the
+    same run): also delta_greedy_noise_mean and randomness_cost_noise_mean = delta_noise(greedy) - delta_sampled over the
+    games solved by both."""
     ids = np.asarray(ids, np.int64).reshape(-1)
     iters = np.asarray(games["iters"], np.int64)
     solved = iters >= 0
@@ -301,6 +469,12 @@ def summarize(games, ids, n_groups, nash, cartel, max_iters, cycle_reward=None):
         cr, lam = cycle_reward
         dgreedy = profit_gain(np.asarray(cr, np.float64), nash, cartel)
         has = np.asarray(lam).reshape(-1) > 0
+    jump = np.asarray(games["max_jump"], np.float64) if "max_jump" in games else None
+    dnoise = hasn = None
+    if greedy_noise is not None:
+        sr, git = greedy_noise
+        dnoise = profit_gain(np.asarray(sr, np.float64), nash, cartel)
+        hasn = np.asarray(git).reshape(-1) >= 0
     out = []
     for k in range(int(n_groups)):
         m = ids == k
@@ -317,6 +491,12 @@ def summarize(games, ids, n_groups, nash, cartel, max_iters, cycle_reward=None):
             mg = ms & has
             row["delta_greedy_mean"] = an.mean(dgreedy[mg])
             row["randomness_cost_mean"] = an.mean(dgreedy[mg] - delta[mg])
+        if jump is not None:
+            row["max_jump_max"] = an.num(jump[m].max()) if m.any() else None
+        if dnoise is not None:
+            mn = ms & hasn
+            row["delta_greedy_noise_mean"] = an.mean(dnoise[mn])
+            row["randomness_cost_noise_mean"] = an.mean(dnoise[mn] - delta[mn])
         out.append(row)
     return out
 
@@ -327,23 +507,27 @@ def combine(parts):
     return an.combine(parts, other={"pi": 0}, only=PER_GAME)
 
 
-def describe(options, T, n_prices, nash, cartel, summary):
-    """sampled_play.json's content."""
-    return {"options": options, "T": int(T), "n_prices": int(n_prices), "nash": nash, "cartel": cartel,
-            "quantiles": list(sn.QUANTILES), "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)",
-            "summary": summary}
+def describe(options, T, n_prices, nash, cartel, summary, n_nodes=None):
+    """sampled_play.json's content (n_nodes: the noisy mode's)."""
+    d = {"options": options, "T": int(T), "n_prices": int(n_prices), "nash": nash, "cartel": cartel,
+         "quantiles": list(sn.QUANTILES), "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)",
+         "summary": summary}
+    if n_nodes is not None:
+        d["n_nodes"] = int(n_nodes)
+    return d
 
 
 def save_games(d, r):
     """splay_iters int32 [G], splay_games float64 [4, G] (change, mass, samp_price, agree), splay_reward, splay_action and
     splay_epsilon float64 [N, G]; from start tuples splay_start int32 [G]; with the distributions splay_pi float64
-    [G, T]."""
+    [G, T]; in the noisy mode splay_noise_prob and splay_max_jump float64 [G]."""
     np.save(os.path.join(d, "splay_iters.npy"), np.asarray(r["iters"], np.int32))
     np.save(os.path.join(d, "splay_games.npy"), np.stack([np.asarray(r[f], np.float64) for f in GAME_FLOAT]))
     np.save(os.path.join(d, "splay_reward.npy"), np.asarray(r["samp_reward"], np.float64))
     np.save(os.path.join(d, "splay_action.npy"), np.asarray(r["samp_action"], np.float64))
     np.save(os.path.join(d, "splay_epsilon.npy"), np.asarray(r["epsilon"], np.float64))
-    for f, name in (("start", "splay_start.npy"), ("pi", "splay_pi.npy")):
+    for f, name in (("start", "splay_start.npy"), ("pi", "splay_pi.npy"), ("noise_prob", "splay_noise_prob.npy"),
+                    ("max_jump", "splay_max_jump.npy")):
         path = os.path.join(d, name)
         if f in r:
             np.save(path, np.asarray(r[f], np.int32 if f == "start" else np.float64))
@@ -358,7 +542,8 @@ def load_games(d):
     g.update({f: gm[k] for k, f in enumerate(GAME_FLOAT)})
     g.update(samp_reward=np.load(os.path.join(d, "splay_reward.npy")), samp_action=np.load(os.path.join(d, "splay_action.npy")),
              epsilon=np.load(os.path.join(d, "splay_epsilon.npy")))
-    for f, name in (("start", "splay_start.npy"), ("pi", "splay_pi.npy")):
+    for f, name in (("start", "splay_start.npy"), ("pi", "splay_pi.npy"), ("noise_prob", "splay_noise_prob.npy"),
+                    ("max_jump", "splay_max_jump.npy")):
         if os.path.isfile(os.path.join(d, name)):
             g[f] = np.load(os.path.join(d, name))
     return g
@@ -376,16 +561,36 @@ def greedy_cycles_of(d, n_games):
     return cr[0], cyc[0, 1]
 
 
+def greedy_noise_of(d, noise_prob):
+    """(stat_reward [N, G], iters [G]) of training.greedy_stationary in the same directory when it analysed the same noise
+    probabilities per game as noise_prob [G], else None."""
+    if not os.path.isfile(os.path.join(d, "greedy_stationary.json")) or not os.path.isfile(os.path.join(d, "gstat_iters.npy")):
+        return None
+    from . import tuple_stationary as ts
+    g = ts.load_games(d)
+    p = np.asarray(noise_prob, np.float64).reshape(-1)
+    if g["noise_prob"].shape != p.shape or not np.array_equal(g["noise_prob"], p):
+        return None
+    return g["stat_reward"], g["iters"]
+
+
 def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None, with_cycles=False):
     """train_one's training.sampled_play outputs: the per-game splay_*.npy files and sampled_play.json.  with_cycles:
     this run wrote the gcyc_* files (training.greedy_cycles) just before; only then does the summary carry
     delta_greedy_mean and randomness_cost_mean."""
-    tabs = tables(config)
+    noise = opt.get("noise")
+    tabs = noise_tables(config, noise["resolution"]) if noise else tables(config)
+    noise_prob = 0.0
+    if noise:       # a number goes per game, so that 0.0 too takes the noisy call and writes its files
+        p = noise["noise_prob"]
+        noise_prob = None if p is None else np.full(batch.G, float(p))
     r = run(batch, epsilon=opt["epsilon"], start=opt["start"], tol=opt["tol"], max_iters=opt["max_iters"], pi=opt["pi"],
-            tuple_policy=tuple_policy, tabs=tabs)
+            tuple_policy=tuple_policy, tabs=tabs, noise_prob=noise_prob)
     save_games(exp_path, r)
     nash, cartel = optimal(config)
     cyc = greedy_cycles_of(exp_path, np.asarray(r["iters"]).size) if with_cycles else None
-    summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"], cycle_reward=cyc)
-    an.save_json(os.path.join(exp_path, "sampled_play.json"), describe(opt, r["T"], r["n_prices"], nash, cartel, summary))
+    gn = greedy_noise_of(exp_path, r["noise_prob"]) if noise else None
+    summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"], cycle_reward=cyc, greedy_noise=gn)
+    an.save_json(os.path.join(exp_path, "sampled_play.json"),
+                 describe(opt, r["T"], r["n_prices"], nash, cartel, summary, n_nodes=r.get("n_nodes")))
     return r

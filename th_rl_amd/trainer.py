@@ -61,7 +61,9 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                  "sampled_play": null,  # true or {"epsilon": "current", "start": "uniform" | "state", "tol": 1e-12,
                                       # "max_iters": 8192, "pi": false}: after training the exact long-run profit of
                                       # SAMPLED play, the way the agents were trained (sampled_play.py: a network samples
-                                      # its softmax, a QTable agent is epsilon-greedy; no demand noise), for any mix of
+                                      # its softmax, a QTable agent is epsilon-greedy; with the further key "noise": true or
+                                      # {"noise_prob": null (the run's own) | p, "resolution": 1024} under demand noise, where
+                                      # "start" may be "reset": also splay_noise_prob.npy / splay_max_jump.npy [G]), for any mix of
                                       # QTable, Reinforce and ActorCritic agents: sampled_play.json, splay_iters.npy int32
                                       # [G], splay_games.npy [4, G] (change, mass, price, agree), splay_reward.npy /
                                       # splay_action.npy / splay_epsilon.npy [N, G]; with pi splay_pi.npy [G, T]

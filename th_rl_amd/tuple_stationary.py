@@ -109,15 +109,11 @@ def cuts(config, resolution):
     return c
 
 
-def tables(config, resolution=DEFAULTS["resolution"]):
-    """The per-config tables of thrl_tuple_stationary (include/thrl.h) as a dict of numpy arrays: cuts [J + 1], cell_w
-    [J] (length / a), cell_x [J] (the midpoints the strategies are sampled at); tuple_play.tables' T, n_actions, kinds,
-    price [T], reward and scaled [N, T]; band_lo int32 [T], band [T, W], noise_price [T], noise_reward [N, T] by the
-    formulas of thrl_stationary's tables over these cells; n_cells, n_tuples, band_w, resolution.  More than MAX_CELLS
-    cells is a ValueError that names the resolution."""
-    t = tp.tables(config)
-    c = cuts(config, resolution)
-    J = int(c.size - 1)
+def noise_geometry(config, t, c):
+    """What the redrawn price of every tuple covers of the cells with the ends c: dict(length [T, J], the length of
+    [0.7 a - u(t), a - u(t)) inside each cell; z [T], the length clipped to price 0; width = 0.3 a; noise_price [T];
+    quantity [N, T]; cell_w and cell_x [J]).  tables() lumps z into cell 0; sampled_play.noise_tables gives it a node of
+    its own."""
     env = dict(_lib.ENV_DEFAULTS, **config["environment"])
     a, b = float(env["a"]), float(env["b"])
     # u(t): the amount env_step subtracts from the intercept, from tuple_play's quantities
@@ -133,18 +129,41 @@ def tables(config, resolution=DEFAULTS["resolution"]):
     lo, hi, width = noise_lo - u, a - u, a - noise_lo
     length = np.maximum(0.0, np.minimum(c[None, 1:], hi[:, None]) - np.maximum(c[None, :-1], lo[:, None]))
     z = np.maximum(0.0, -lo) - np.maximum(0.0, -hi)
-    length[:, 0] = length[:, 0] + z
-    n = length / width
+    nprice = np.where(lo >= 0.0, (lo + hi) / 2.0, np.where(hi <= 0.0, 0.0, hi * hi / (2.0 * width)))
+    return dict(length=length, z=z, width=width, noise_price=nprice, quantity=quantity, cell_w=w, cell_x=x, u=u, a=a)
+
+
+def band_of(n):
+    """(band_lo int32 [T], band [T, W]) of the weights n [T, J]: every row from its first to its last non-zero entry,
+    padded with zeros to the widest."""
+    T, J = n.shape
     nz = n > 0.0
     first = np.where(nz.any(axis=1), nz.argmax(axis=1), 0)
     last = np.where(nz.any(axis=1), J - 1 - nz[:, ::-1].argmax(axis=1), 0)
     W = int((last - first + 1).max())
-    pad = np.concatenate([n, np.zeros((t["T"], W))], axis=1)
-    band = pad[np.arange(t["T"])[:, None], first[:, None] + np.arange(W)[None, :]]
-    nprice = np.where(lo >= 0.0, (lo + hi) / 2.0, np.where(hi <= 0.0, 0.0, hi * hi / (2.0 * width)))
+    pad = np.concatenate([n, np.zeros((T, W))], axis=1)
+    band = pad[np.arange(T)[:, None], first[:, None] + np.arange(W)[None, :]]
+    return first.astype(np.int32), np.ascontiguousarray(band, np.float64)
+
+
+def tables(config, resolution=DEFAULTS["resolution"]):
+    """The per-config tables of thrl_tuple_stationary (include/thrl.h) as a dict of numpy arrays: cuts [J + 1], cell_w
+    [J] (length / a), cell_x [J] (the midpoints the strategies are sampled at); tuple_play.tables' T, n_actions, kinds,
+    price [T], reward and scaled [N, T]; band_lo int32 [T], band [T, W], noise_price [T], noise_reward [N, T] by the
+    formulas of thrl_stationary's tables over these cells; n_cells, n_tuples, band_w, resolution.  More than MAX_CELLS
+    cells is a ValueError that names the resolution."""
+    t = tp.tables(config)
+    c = cuts(config, resolution)
+    J = int(c.size - 1)
+    geo = noise_geometry(config, t, c)
+    length, width, w, x, nprice, quantity = (geo[f] for f in ("length", "width", "cell_w", "cell_x", "noise_price", "quantity"))
+    length[:, 0] = length[:, 0] + geo["z"]
+    n = length / width
+    first, band = band_of(n)
+    W = int(band.shape[1])
     out = dict(t)
-    out.update(cuts=c, cell_w=np.ascontiguousarray(w), cell_x=np.ascontiguousarray(x), band_lo=first.astype(np.int32),
-               band=np.ascontiguousarray(band, np.float64), noise_price=np.ascontiguousarray(nprice),
+    out.update(cuts=c, cell_w=np.ascontiguousarray(w), cell_x=np.ascontiguousarray(x), band_lo=first,
+               band=band, noise_price=np.ascontiguousarray(nprice),
                noise_reward=np.ascontiguousarray(nprice[None, :] * quantity), n_cells=J, n_tuples=int(t["T"]), band_w=W,
                resolution=int(resolution))
     return out

@@ -589,10 +589,13 @@ def sampled_play_summary(exp_path):
     DataFrame, one row per group: games, converged, iters_*, delta_sampled_* (the profit gain of sampled play),
     agree_mean (the share of steps on which every agent plays its greedy action), price_mean; where greedy_cycles ran in
     the same experiment also delta_greedy_mean and randomness_cost_mean = delta_greedy - delta_sampled; plus T,
-    n_prices, Nash and Cartel."""
+    n_prices, Nash and Cartel.  Under demand noise also max_jump_max, n_nodes, and where greedy_stationary analysed the
+    same noise delta_greedy_noise_mean and randomness_cost_noise_mean."""
     desc = _load_json(exp_path, "sampled_play.json")
     df = pandas.DataFrame(desc["summary"])
     df["T"], df["n_prices"] = int(desc["T"]), int(desc["n_prices"])
+    if "n_nodes" in desc:
+        df["n_nodes"] = int(desc["n_nodes"])
     df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
     return df
 
@@ -600,7 +603,8 @@ def sampled_play_summary(exp_path):
 def sampled_play_games(exp_path):
     """Per-game results of training.sampled_play, one row per game indexed by its GLOBAL id: iters, change, mass, price,
     agree, reward_<i>, action_<i>, epsilon_<i>, delta_sampled (the profit gain, as stationary_games computes
-    delta_noise) and, from the training state, start (the tuple played there)."""
+    delta_noise) and, from the training state, start (the tuple played there); under demand noise also noise_prob and
+    max_jump."""
     from th_rl_amd import sampled_play as sp
     from th_rl_amd.deviation import profit_gain
     _run_dirs(exp_path, "splay_iters.npy", "sampled-play analysis", "sampled_play", shards=False)
@@ -612,7 +616,8 @@ def sampled_play_games(exp_path):
         cols["reward_%d" % i], cols["action_%d" % i] = g["samp_reward"][i], g["samp_action"][i]
         cols["epsilon_%d" % i] = g["epsilon"][i]
     cols["delta_sampled"] = profit_gain(g["samp_reward"], desc["nash"], desc["cartel"])
-    if "start" in g:
-        cols["start"] = g["start"]
+    for f in ("start", "noise_prob", "max_jump"):
+        if f in g:
+            cols[f] = g[f]
     n = g["iters"].shape[0]
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
