@@ -446,7 +446,7 @@ constexpr size_t kLutRegion = 16384;            // workspace bytes reserved for 
 // Workspace of the wave kernel, sized from the config and the current device:
 //   [0, kLutRegion)   payoff-LUT image (+ the launch's work counter in its last 64 bytes)
 //   partial           [total_waves][kWaveMaxEpisodes][4] fixed-point log sums
-//   tlog              [total_waves][kWaveMaxEpisodes][NSEG][64] packed transitions (visit counters)
+//   tlog              [total_waves][kWaveMaxEpisodes][NSEG][64] cell words of the transitions (visit counters)
 // total_waves = the persistent grid: resident blocks per CU x CUs, or fewer when G is small.
 struct WaveWs { int grid, total_waves; size_t partial_off, tlog_off, bytes; };
 WaveWs wave_workspace(const thrl_cfg* c, const WavePlan& p) {

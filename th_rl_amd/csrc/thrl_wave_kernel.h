@@ -74,6 +74,21 @@ __device__ __forceinline__ void lds_store(unsigned addr, QT v) {
     *(lds_t*)(uintptr_t)addr = v;
 }
 
+// The visit histogram overlays the tables: its accesses carry may_alias types (no type-based reordering against the
+// tables' float / double accesses or against each other).
+// += 1 on a u32 in LDS, no return value (ds_add_u32)
+__device__ __forceinline__ void lds_inc(unsigned addr) {
+    typedef unsigned __attribute__((may_alias)) u32_alias;
+    typedef __attribute__((address_space(3))) u32_alias lds_u32;
+    __hip_atomic_fetch_add((lds_u32*)(uintptr_t)addr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+// 8 zero bytes at an 8-byte aligned LDS address (ds_write_b64)
+__device__ __forceinline__ void lds_zero8(unsigned addr) {
+    typedef unsigned long long __attribute__((may_alias)) u64_alias;
+    typedef __attribute__((address_space(3))) u64_alias lds_u64;
+    *(lds_u64*)(uintptr_t)addr = 0ull;
+}
+
 __device__ __forceinline__ unsigned bperm(unsigned byte_sel, unsigned v) {
     return (unsigned)__builtin_amdgcn_ds_bpermute((int)byte_sel, (int)v);
 }
@@ -1134,6 +1149,12 @@ k_wave_episodes(const WaveArgs a) {
             // ---- (d1) lane-parallel (lane = step): actions, old-value snapshot
             //      (agents.py:67) for ALL steps before any TD write
             uint32_t act[NSEG];            // a0 | a1<<8 | train_row<<16 | next_row<<24
+            // the cell word of a transition: off0 | off1 << 16, the byte offsets from tab0 of the u32 visit-histogram cells
+            // of the two rewritten table cells, off0 = 4*(srow*A + a0), off1 = 4*((W+2)*A + srow*A + a1) <= 4*8191.  A table
+            // cell's own offset is the same (float32) or twice that (float64).  One word serves the old-value snapshot, the
+            // replay store address and the visit log; 0xFFFFFFFF is no cell word (the log's "not counted" marker).
+            uint32_t cwv[NSEG];
+            constexpr unsigned kCellScale = (unsigned)sizeof(QT) / 4u;
             Snapshot<QT> snap[NSEG];       // (1-alpha)*old_value, halves packed per 32 steps
 #pragma unroll
             for (int seg = 0; seg < NSEG; seg++) {
@@ -1147,12 +1168,19 @@ k_wave_episodes(const WaveArgs a) {
                 const uint32_t gam = gather_row<NRSEG>(AM, my_s);
                 uint32_t a0 = (rw & 1u) ? ((rw >> 8) & 0xFFu) : (gam & 0xFFu);
                 uint32_t a1 = (rw & 2u) ? ((rw >> 16) & 0xFFu) : (gam >> 8);
-                uint32_t nxt = (uint32_t)__shfl_down((int)seq[seg], 1, 64);
+                // next step's word: wave_shl:1 gives lane t the value of lane t+1.  Like the gather above this needs ALL 64 lanes
+                // active (a DPP lane whose source lane is inactive is not written), so it must stay outside divergent control;
+                // lane 63 has no source and keeps its own word, which is never used as it is: fixed up below, replaced by s_end, or not valid
+                uint32_t nxt = dpp_mov32<0x130>(seq[seg]);
                 if (seg + 1 < NSEG) { if (lane == 63) nxt = readlane_u(seq[seg + 1 < NSEG ? seg + 1 : seg], 0); }
                 const uint32_t ns = (tt + 1 < T) ? ((nxt >> 8) & 0xFFu) : ((uint32_t)s_end >> 8);
                 uint32_t srow = my_train;
                 if (!valid) { a0 = 0; a1 = 0; srow = 0; }
-                snap[seg].set(oma0, tab0[srow * A + a0], oma1, tab1[srow * A + a1]);
+                const uint32_t rowc = __umul24(srow, (uint32_t)A);
+                const uint32_t cw = ((rowc + a0) | ((rowc + a1 + (uint32_t)((W + 2) * A)) << 16)) << 2;
+                cwv[seg] = cw;
+                snap[seg].set(oma0, lds_load<QT>(tab0_off + (cw & 0xFFFFu) * kCellScale),
+                              oma1, lds_load<QT>(tab0_off + (cw >> 16) * kCellScale));
                 act[seg] = a0 | (a1 << 8) | (srow << 16) | (ns << 24);
             }
             __builtin_amdgcn_wave_barrier();
@@ -1183,7 +1211,6 @@ k_wave_episodes(const WaveArgs a) {
                 const int tt = seg * 64 + lane;
                 const bool valid = tt < T;
                 const uint32_t a0 = act[seg] & 0xFFu, a1 = (act[seg] >> 8) & 0xFFu;
-                const uint32_t srow = (act[seg] >> 16) & 0xFFu;
                 // NoisyPriceState.step (environments.py:25-39) from the staged quantities A_i = (a/b)*scaled_i:
                 // three float64 operations per 64 steps instead of a gather from the L2-resident price table
                 const double aq0 = lut_aq[a0], aq1 = lut_aq[A + a1];
@@ -1197,8 +1224,7 @@ k_wave_episodes(const WaveArgs a) {
                     last_price = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(price), ll),
                                                   __builtin_amdgcn_readlane(__double2loint(price), ll));
                 }
-                const v2u woq = pack_halves(tab0_off + (srow * A + a0) * (unsigned)sizeof(QT),
-                                            tab1_off + (srow * A + a1) * (unsigned)sizeof(QT));
+                const v2u woq = pack_halves(tab0_off + (cwv[seg] & 0xFFFFu) * kCellScale, tab0_off + (cwv[seg] >> 16) * kCellScale);
                 if (epk == 1) {
                     if (valid) {
                         lr0 += r0d; lr1 += r1d;          // divided by T once per episode below
@@ -1215,11 +1241,11 @@ k_wave_episodes(const WaveArgs a) {
                         log_into(e + j, m ? r0d : 0.0, m ? r1d : 0.0, m ? s0 : 0.0, m ? s1 : 0.0, j * Tenv >= seg * 64);
                     }
                 }
-                // visit counters (agents.py:76): the packed transition word goes to this wave's
-                // log (coalesced, L2-resident); the counts are built per game below
+                // visit counters (agents.py:76): the cell word goes to this wave's log (coalesced, L2-resident); the
+                // counts are built per game below.  Only transitions still in the deque when it trains are counted.
                 if (a.counter && !(kAblate & 32))
                     a.tlog[(((size_t)wave_gid * kWaveMaxEpisodes + e) * NSEG + seg) * 64 + lane] =
-                        valid ? act[seg] : 0xFFFFFFFFu;
+                        (valid && tt >= replay_from) ? cwv[seg] : 0xFFFFFFFFu;
 
                 // ---- replay schedule of this segment's 16 groups of four transitions, lane-parallel.
                 //      Transition j may share a pass with an earlier transition i of its group unless it
@@ -1382,18 +1408,18 @@ k_wave_episodes(const WaveArgs a) {
 
         // ---- visit counters of this game (agents.py:76).  The tables are back in HBM, so
         //      the wave's LDS region is free: build the launch's visit histogram there
-        //      (u16 pairs in dwords, ds_add_u32; E*T <= 32*256 < 65536 so no carry) from the
+        //      (one u32 per cell at the cell words' offsets, ds_add_u32 of 1) from the
         //      transition log, then apply it to the counter window with plain coalesced
         //      read-add-write -- this game's counters belong to this wave alone, so no
         //      global atomics are needed (2e9 scattered atomics per launch were a 70 ms floor).
         if (a.counter && !(kAblate & 32)) {
             const int cells = (W + 2) * A;                       // per agent
-            const int hw = (cells + 1) >> 1;                     // dwords per agent
             // may_alias: the histogram overlays the tables (no type-based reordering)
             typedef unsigned __attribute__((may_alias)) hist_u32;
-            hist_u32* hist = reinterpret_cast<hist_u32*>(tab0);   // 2*hw dwords <= 2*cells table elements
+            hist_u32* hist = reinterpret_cast<hist_u32*>(tab0);   // 2*cells dwords: agent 0's cells, then agent 1's
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            for (int k = lane; k < 2 * hw; k += 64) hist[k] = 0u;
+            // (the region is 8-byte aligned: 2*cells dwords = cells 8-byte stores)
+            for (int k = lane; k < cells; k += 64) lds_zero8(tab0_off + 8u * (unsigned)k);
             __builtin_amdgcn_wave_barrier();
             // log read-back: 4 episodes' loads in flight at a time (sc1 = L2-served: the wave
             // reads what it stored itself)
@@ -1412,13 +1438,9 @@ k_wave_episodes(const WaveArgs a) {
 #pragma unroll
                     for (int seg = 0; seg < NSEG; seg++) {
                         const unsigned ww = w[j][seg];
-                        // only transitions still in the deque when it trained were counted (agents.py:76)
-                        if (c0 + j < n_cycles && ww != 0xFFFFFFFFu && seg * 64 + lane >= replay_from) {
-                            const unsigned srow = (ww >> 16) & 0xFFu;
-                            const unsigned c0_ = srow * (unsigned)A + (ww & 0xFFu);
-                            const unsigned c1_ = srow * (unsigned)A + ((ww >> 8) & 0xFFu);
-                            __hip_atomic_fetch_add(&hist[c0_ >> 1], 1u << ((c0_ & 1u) << 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                            __hip_atomic_fetch_add(&hist[hw + (c1_ >> 1)], 1u << ((c1_ & 1u) << 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        if (c0 + j < n_cycles && ww != 0xFFFFFFFFu) {
+                            lds_inc(tab0_off + (ww & 0xFFFFu));
+                            lds_inc(tab0_off + (ww >> 16));
                         }
                     }
             }
@@ -1441,8 +1463,7 @@ k_wave_episodes(const WaveArgs a) {
                 for (int j = 0; j < 8; j++) {
                     const int k = k0 + j * 64 + lane;
                     if (k < nwin) {
-                        const unsigned n0 = (hist[k >> 1] >> ((k & 1) << 4)) & 0xFFFFu;
-                        const unsigned n1 = (hist[hw + (k >> 1)] >> ((k & 1) << 4)) & 0xFFFFu;
+                        const unsigned n0 = hist[k], n1 = hist[cells + k];
                         if (n0) cw0[lo * A + k] = c0v[j] + (int32_t)n0;
                         if (n1) cw1[lo * A + k] = c1v[j] + (int32_t)n1;
                     }
@@ -1453,8 +1474,7 @@ k_wave_episodes(const WaveArgs a) {
                 const int grow_ = which ? spill1 : spill0;
                 const int k = nwin + lane;
                 if (grow_ >= 0) {
-                    const unsigned n0 = (hist[k >> 1] >> ((k & 1) << 4)) & 0xFFFFu;
-                    const unsigned n1 = (hist[hw + (k >> 1)] >> ((k & 1) << 4)) & 0xFFFFu;
+                    const unsigned n0 = hist[k], n1 = hist[cells + k];
                     if (n0) cw0[grow_ * A + col] += (int32_t)n0;
                     if (n1) cw1[grow_ * A + col] += (int32_t)n1;
                 }
