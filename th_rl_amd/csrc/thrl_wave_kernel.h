@@ -1409,9 +1409,10 @@ k_wave_episodes(const WaveArgs a) {
         // ---- visit counters of this game (agents.py:76).  The tables are back in HBM, so
         //      the wave's LDS region is free: build the launch's visit histogram there
         //      (one u32 per cell at the cell words' offsets, ds_add_u32 of 1) from the
-        //      transition log, then apply it to the counter window with plain coalesced
-        //      read-add-write -- this game's counters belong to this wave alone, so no
-        //      global atomics are needed (2e9 scattered atomics per launch were a 70 ms floor).
+        //      transition log, then add its non-zero cells to the counter window with no-return atomic adds
+        //      (relaxed, agent scope): consecutive cells, so coalesced, and no load whose return the wave would
+        //      have to wait for.  At most one add per cell, game and launch -- not one per transition
+        //      (2e9 scattered atomics per launch were a 70 ms floor).
         if (a.counter && !(kAblate & 32)) {
             const int cells = (W + 2) * A;                       // per agent
             // may_alias: the histogram overlays the tables (no type-based reordering)
@@ -1450,33 +1451,19 @@ k_wave_episodes(const WaveArgs a) {
             int32_t* cw0 = a.counter + (int64_t)g * a.stride + p0.table_off;
             int32_t* cw1 = a.counter + (int64_t)g * a.stride + p1.table_off;
             const int nwin = W * A;
-            // all counter loads of a batch in flight before the first store (one HBM round trip per 512
-            // cells instead of one per 64)
-            for (int k0 = 0; k0 < nwin; k0 += 512) {
-                int32_t c0v[8], c1v[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int k = min(k0 + j * 64 + lane, nwin - 1);
-                    c0v[j] = cw0[lo * A + k]; c1v[j] = cw1[lo * A + k];
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int k = k0 + j * 64 + lane;
-                    if (k < nwin) {
-                        const unsigned n0 = hist[k], n1 = hist[cells + k];
-                        if (n0) cw0[lo * A + k] = c0v[j] + (int32_t)n0;
-                        if (n1) cw1[lo * A + k] = c1v[j] + (int32_t)n1;
-                    }
-                }
+            auto add = [](int32_t* p, unsigned n) {
+                if (n) __hip_atomic_fetch_add(p, (int32_t)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            };
+            for (int k = lane; k < nwin; k += 64) {
+                add(cw0 + lo * A + k, hist[k]);
+                add(cw1 + lo * A + k, hist[cells + k]);
             }
             if (lane < 2 * A) {
                 const int which = lane >= A, col = lane - which * A;
                 const int grow_ = which ? spill1 : spill0;
-                const int k = nwin + lane;
                 if (grow_ >= 0) {
-                    const unsigned n0 = hist[k], n1 = hist[cells + k];
-                    if (n0) cw0[grow_ * A + col] += (int32_t)n0;
-                    if (n1) cw1[grow_ * A + col] += (int32_t)n1;
+                    add(cw0 + grow_ * A + col, hist[nwin + lane]);
+                    add(cw1 + grow_ * A + col, hist[cells + nwin + lane]);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
