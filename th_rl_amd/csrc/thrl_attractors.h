@@ -1,6 +1,6 @@
 // thrl_attractors.h -- launch arguments of the attractor-analysis kernel (thrl_attractors, include/thrl.h).
-// thrl_api.hip validates, takes the per-config plan of thrl_equilibrium (tuple LUTs, state rows) from its cache and
-// lays out LDS; thrl_attractors.hip holds the kernel.
+// thrl_api_analysis.hip validates and takes the per-config plan of thrl_equilibrium (tuple LUTs, state rows) from its
+// cache, attr_layout() lays out LDS; thrl_attractors.hip holds the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,6 +37,35 @@ struct AttrArgs {
     double *reset_mass, *reset_mass_other, *reset_reward;
     uint16_t *state_rep, *state_mu;
 };
+
+// LDS of a block: 8-byte arrays first, then 4-byte, then 2-byte.  Returns the bytes without the reward LUT (refused over the budget).
+inline int64_t attr_layout(AttrArgs& a) {
+    const int S = a.S, T = a.T, N = a.N;
+    const int64_t fixed = 8 * 64 * (int64_t)(1 + N) + 4 * (2 * (int64_t)S + THRL_MAXA + THRL_ATTR_KEEP + 64)
+                          + 2 * ((int64_t)T + (int64_t)N * S + THRL_MAXA + (int64_t)(a.L + 1) * S + 7 * (int64_t)S) + 64;
+    a.lut_lds = fixed + 8 * (int64_t)N * T <= kAttrLdsBudget;
+    int off = 0;
+    a.o_rew = off; off += a.lut_lds ? 8 * N * T : 0;
+    a.o_cw = off; off += 8 * 64;
+    a.o_cprod = off; off += 8 * 64 * N;
+    a.o_basin = off; off += 4 * S;
+    a.o_lamc = off; off += 4 * S;
+    a.o_x0row = off; off += 4 * THRL_MAXA;
+    a.o_sel = off; off += 4 * THRL_ATTR_KEEP;
+    a.o_cslot = off; off += 4 * 64;
+    a.o_sid = off; off += 2 * T;
+    a.o_pol = off; off += 2 * (N * S + THRL_MAXA);
+    a.o_lev = off; off += 2 * (a.L + 1) * S;
+    a.o_ma = off; off += 2 * S;
+    a.o_mb = off; off += 2 * S;
+    a.o_rep = off; off += 2 * S;
+    a.o_mu = off; off += 2 * S;
+    a.o_on = off; off += 2 * S;
+    a.o_tup = off; off += 2 * S;
+    a.o_slot = off; off += 2 * S;
+    a.lds_bytes = (off + 15) & ~15;
+    return fixed;
+}
 
 int launch_attractors(const AttrArgs& a, int grid, hipStream_t s);
 

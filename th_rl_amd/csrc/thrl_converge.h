@@ -1,5 +1,5 @@
 // thrl_converge.h -- launch arguments of the convergence-tracking kernel (thrl_policy_track, include/thrl.h).
-// thrl_api.hip validates and plans; thrl_converge.hip holds the kernel.
+// thrl_api_analysis.hip validates and plans; thrl_converge.hip holds the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // thrl_crossplay.h -- launch arguments of the cross-play kernels (thrl_crossplay, include/thrl.h).
-// thrl_api.hip validates and plans; thrl_crossplay.hip holds the kernels.
+// thrl_api_analysis.hip validates and plans; thrl_crossplay.hip holds the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // thrl_deviation.h -- launch arguments of the deviation-analysis kernel (thrl_deviation, include/thrl.h).
-// thrl_api.hip validates and plans; thrl_deviation.hip holds the kernel.
+// thrl_api_analysis.hip validates and plans; thrl_deviation.hip holds the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

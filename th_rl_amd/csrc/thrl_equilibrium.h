@@ -1,6 +1,6 @@
 // thrl_equilibrium.h -- launch arguments of the equilibrium-check kernel (thrl_equilibrium, include/thrl.h).
-// thrl_api.hip validates, builds the per-config plan (tuple LUTs, state rows) and lays out LDS; thrl_equilibrium.hip
-// holds the kernel.
+// thrl_api_analysis.hip validates and builds the per-config plan (tuple LUTs, state rows), eq_layout() lays out LDS;
+// thrl_equilibrium.hip holds the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +34,29 @@ struct EqArgs {
     uint16_t* br_policy;
     double *v_opt, *v_pi;
 };
+
+// LDS of a block: 8-byte arrays first, then 4-byte, then 2-byte (lds_bytes over the budget is refused by the caller)
+inline void eq_layout(EqArgs& a) {
+    const int S = a.S, T = a.T, N = a.N;
+    const int64_t fixed = 3 * 8 * (int64_t)S + 4 * (int64_t)S + 4 * THRL_MAXA
+                          + 2 * ((int64_t)T + (int64_t)N * S + THRL_MAXA + 5 * (int64_t)S) + 64;
+    a.lut_lds = fixed + 8 * (int64_t)N * T <= kEqLdsBudget;
+    int off = 0;
+    a.o_va = off; off += 8 * S;
+    a.o_vb = off; off += 8 * S;
+    a.o_vpi = off; off += 8 * S;
+    a.o_rew = off; off += a.lut_lds ? 8 * N * T : 0;
+    a.o_base = off; off += 4 * S;
+    a.o_x0row = off; off += 4 * THRL_MAXA;
+    a.o_sid = off; off += 2 * T;
+    a.o_first = off; off += 2 * S;
+    a.o_pol = off; off += 2 * (N * S + THRL_MAXA);
+    a.o_sigma = off; off += 2 * S;
+    a.o_jn = off; off += 2 * S;
+    a.o_na = off; off += 2 * S;
+    a.o_nb = off; off += 2 * S;
+    a.lds_bytes = (off + 15) & ~15;
+}
 
 int launch_equilibrium(const EqArgs& a, int q_dtype, int grid, hipStream_t s);
 

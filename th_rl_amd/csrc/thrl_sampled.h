@@ -1,5 +1,5 @@
-// thrl_sampled.h -- launch arguments of sampled play (thrl_sampled_chain, include/thrl.h).  thrl_api.hip validates and
-// lays out LDS; thrl_sampled.hip holds the kernel.
+// thrl_sampled.h -- launch arguments of sampled play (thrl_sampled_chain, include/thrl.h).  thrl_api_analysis.hip validates;
+// sp_layout() is the one place the LDS layout is written down; thrl_sampled.hip holds the kernel.
 #pragma once
 #ifndef THRL_SP_HOST_BUILD
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // thrl_sampled_noise.h -- launch arguments of sampled play under demand noise (thrl_sampled_noise_chain, include/thrl.h).
-// thrl_api.hip validates; spn_layout() is the one place the LDS layout is written down (the API's plan, the header's
+// thrl_api_analysis.hip validates; spn_layout() is the one place the LDS layout is written down (the API's plan, the header's
 // text and th_rl_amd.sampled_play.working_set follow it); thrl_sampled_noise.hip holds the kernels.
 #pragma once
 #include "thrl_sampled.h"

@@ -1,6 +1,6 @@
 // thrl_stationary.h -- launch arguments of the stationary-distribution kernel (thrl_stationary, include/thrl.h).
-// thrl_api.hip validates, takes the per-config plan of thrl_equilibrium (the rewards per tuple) from its cache and
-// lays out LDS; thrl_stationary.hip holds the kernel.
+// thrl_api_analysis.hip validates and takes the per-config plan of thrl_equilibrium (the rewards per tuple) from its
+// cache, stat_layout() lays out LDS; thrl_stationary.hip holds the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,6 +40,25 @@ struct StatArgs {
     int32_t* iters;
     double *change, *mass, *stat_reward, *stat_action, *stat_price, *pi;
 };
+
+// LDS of a block, from N and J: 8-byte arrays first, then 4-byte, then 2-byte.  Returns the bytes without the per-cell
+// tables (the two iterates, the staging of the ordered sums, the tuple per cell: refused over the budget).
+inline int64_t stat_layout(StatArgs& a) {
+    const int N = a.N;
+    const int64_t J = a.J;
+    const int64_t need = 8 * 2 * J + 8 * 64 * (int64_t)(2 * N + 2) + 2 * J + 16;
+    a.cell_lds = need + 10 * J <= kStatLdsBudget;
+    int off = 0;
+    a.o_mua = off; off += 8 * a.J;
+    a.o_mub = off; off += 8 * a.J;
+    a.o_prod = off; off += 8 * 64 * (2 * N + 2);
+    a.o_boff = off; off += a.cell_lds ? 4 * a.J : 0;
+    a.o_blo = off; off += a.cell_lds ? 4 * a.J : 0;
+    a.o_det = off; off += a.cell_lds ? 2 * a.J : 0;
+    a.o_tup = off; off += 2 * a.J;
+    a.lds_bytes = (off + 15) & ~15;
+    return need;
+}
 
 int launch_stationary(const StatArgs& a, int grid, hipStream_t s);
 

@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(kStatsBlock) k_group_stats(const StatsArgs a) 
 
 }  // namespace
 
-// Launch for an args block thrl_group_stats (thrl_api.hip) has validated.  Geometry: tiles of perm positions
+// Launch for an args block thrl_group_stats (thrl_api_analysis.hip) has validated.  Geometry: tiles of perm positions
 // on x, (episode, quantity) pairs on y, sized so the grid holds a few thousand blocks; results do not depend on it.
 int launch_group_stats(const thrl_group_stats_args* g, hipStream_t s) {
     StatsArgs a;

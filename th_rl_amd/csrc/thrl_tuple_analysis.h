@@ -1,6 +1,6 @@
 // thrl_tuple_analysis.h -- launch arguments of the deviation test and the equilibrium check in tuple form
-// (thrl_tuple_deviation, thrl_tuple_equilibrium, include/thrl.h).  thrl_api.hip validates and plans LDS;
-// thrl_tuple_analysis.hip holds the kernels.
+// (thrl_tuple_deviation, thrl_tuple_equilibrium, include/thrl.h).  thrl_api_analysis.hip validates and plans the grid,
+// ta_eq_layout() lays out the equilibrium block's LDS; thrl_tuple_analysis.hip holds the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,6 +52,25 @@ struct TaEqArgs {
     uint16_t* br_policy;
     double *v_opt, *v_pi;
 };
+
+// LDS of an equilibrium block: 8-byte arrays first, then 2-byte (each padded to 16 bytes), then the fixed words: at most
+// kTaEqLdsPerTuple * T + kTaEqLdsFixed + 144 bytes, 144.3 KB at T = 4096, whatever N is
+inline void ta_eq_layout(TaEqArgs& a) {
+    const int T = a.T;
+    const int b8 = (8 * T + 15) & ~15, b2 = (2 * T + 15) & ~15;
+    int off = 0;
+    a.o_va = off; off += b8;
+    a.o_vb = off; off += b8;
+    a.o_rew = off; off += b8;
+    a.o_na = off; off += b2;
+    a.o_nb = off; off += b2;
+    a.o_sigma = off; off += b2;
+    a.o_jn = off; off += b2;
+    a.o_mark = off; off += b2;
+    a.o_base = off; off += b2;
+    a.o_misc = off; off += kTaEqLdsFixed;
+    a.lds_bytes = off;
+}
 
 int launch_ta_deviation(const TaDevArgs& a, hipStream_t s);
 int launch_ta_equilibrium(const TaEqArgs& a, int grid, hipStream_t s);

@@ -1,5 +1,5 @@
 // thrl_tuple_play.h -- launch arguments of the tuple-policy kernels (thrl_tuple_policy, thrl_tuple_walk,
-// include/thrl.h).  thrl_api.hip validates and plans; thrl_tuple_play.hip holds the kernels.
+// include/thrl.h).  thrl_api_analysis.hip validates and plans; thrl_tuple_play.hip holds the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

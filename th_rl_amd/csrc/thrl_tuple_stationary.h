@@ -1,5 +1,5 @@
 // thrl_tuple_stationary.h -- launch arguments of the stationary analysis in tuple form (thrl_tuple_stationary,
-// include/thrl.h).  thrl_api.hip validates and lays out LDS; thrl_tuple_stationary.hip holds the kernels.
+// include/thrl.h).  thrl_api_analysis.hip validates, ts_layout() lays out LDS; thrl_tuple_stationary.hip holds the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +39,22 @@ struct TsArgs {
     int32_t* n_switch;
     double* unresolved;
 };
+
+// LDS of a block (the working set of include/thrl.h): 8-byte arrays first, nu directly behind the second iterate,
+// then the 2-byte arrays of the two groupings
+inline void ts_layout(TsArgs& a) {
+    const int T = a.T, J = a.J, N = a.N;
+    int off = 0;
+    a.o_ma = off; off += 8 * T;
+    a.o_mb = off; off += 8 * T;
+    a.o_nu = off; off += 8 * J;
+    a.o_prod = off; off += 8 * 64 * (2 * N + 2);
+    a.o_permk = off; off += 2 * J;
+    a.o_startk = off; off += 2 * (T + 1);
+    a.o_permt = off; off += 2 * T;
+    a.o_startt = off; off += 2 * (T + 1);
+    a.lds_bytes = (off + 15) & ~15;
+}
 
 int launch_tuple_stationary(const TsArgs& a, int grid, hipStream_t s);
 
