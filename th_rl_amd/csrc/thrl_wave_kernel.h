@@ -26,7 +26,10 @@
 //     A pass is legal when no transition in it reads a row, or rewrites a cell, that an earlier
 //     transition of the same pass writes; the schedule (where a group of four must be cut into
 //     several passes) is computed lane-parallel before the loop, so results are exactly those of the
-//     serial loop;
+//     serial loop.  The schedule also numbers every transition's pass (its "key"): a pass stores through the lanes
+//     whose key matches (the compare writes EXEC), pass 0 of a group runs unconditionally, and one scalar test of
+//     the group's cut bits finds the groups that need further passes -- no ranges, no ballots, no scalar loop
+//     control in the hazard-free group;
 //   * the kernel is bound by the number of instructions a wave issues, so the hot loops are
 //     straight-line code: the play loop is unrolled over a segment's 16 groups of four steps and the replay
 //     loop over a block's 8 groups (step / lane numbers are immediates), with copies for full segments and
@@ -36,6 +39,7 @@
 //     (a converged game) is replayed as a recurrence in registers (cyclic_segment).
 #pragma once
 #include <type_traits>
+#include <utility>
 #include "thrl_kernels.h"
 #include "thrl_wave_lut.h"
 
@@ -138,6 +142,38 @@ __device__ __forceinline__ void store_where(unsigned long long mask, unsigned ad
     asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tds_write_b64 %2, %3\n\ts_mov_b64 exec, %0"
                  : "=&s"(save) : "s"(mask), "v"(addr), "v"(v) : "memory");
 }
+// LDS store by the lanes whose replay key (phase (d2): 4 * group + pass number of the lane's transition) equals
+// `want`, for code that is only reached with all 64 lanes active: the compare writes EXEC itself (v_cmpx; on gfx9 it
+// writes VCC too) and EXEC is set back to all ones, no save and no restore.  No lane may match: the store then does
+// nothing.  IMM >= 0: `want` as an inline constant (0..64), else the scalar `want`.
+// Wait states (CDNA3/4 ISA guide, "manually inserted wait states"; hipcc does not look inside asm):
+//   * "VALU writes EXEC -> VALU DPP op: 5": the next DPP operation is the row maximum of the next pass, behind this
+//     store, the s_mov, that pass's row reads (>= 2), their s_waitcnt and a v_max: >= 6 states;
+//   * "VALU writes SGPR/VCC -> v_readlane / v_writelane with that register as lane select: 4": no lane select in the
+//     replay is VCC (immediates, or SGPRs written by the scalar unit);
+//   * "VALU writes VCC -> v_div_fmas: 4": the replay has none.
+// Neither the LDS store's use of the EXEC a VALU has just written nor the scalar write of EXEC has an entry.
+template <int IMM>
+__device__ __forceinline__ void store_key(unsigned key, unsigned want, unsigned addr, float v) {
+    if constexpr (IMM >= 0)
+        asm volatile("v_cmpx_eq_u32 vcc, %0, %1\n\tds_write_b32 %2, %3\n\ts_mov_b64 exec, -1"
+                     :: "n"(IMM), "v"(key), "v"(addr), "v"(v) : "memory", "vcc");
+    else
+        asm volatile("v_cmpx_eq_u32 vcc, %0, %1\n\tds_write_b32 %2, %3\n\ts_mov_b64 exec, -1"
+                     :: "s"(want), "v"(key), "v"(addr), "v"(v) : "memory", "vcc");
+}
+template <int IMM>
+__device__ __forceinline__ void store_key(unsigned key, unsigned want, unsigned addr, double v) {
+    if constexpr (IMM >= 0)
+        asm volatile("v_cmpx_eq_u32 vcc, %0, %1\n\tds_write_b64 %2, %3\n\ts_mov_b64 exec, -1"
+                     :: "n"(IMM), "v"(key), "v"(addr), "v"(v) : "memory", "vcc");
+    else
+        asm volatile("v_cmpx_eq_u32 vcc, %0, %1\n\tds_write_b64 %2, %3\n\ts_mov_b64 exec, -1"
+                     :: "s"(want), "v"(key), "v"(addr), "v"(v) : "memory", "vcc");
+}
+// Packing of the key into the upper bits of a transition's LDS store address (a byte address below 2^18: 160 KB)
+constexpr unsigned kKeyShift = 25;
+constexpr unsigned kKeyNone = 0x7Fu;            // a transition that does not train: no pass has this key (passes: 0..31)
 // the value of the lane 8 further on in the same 16-lane row (row_ror:8): swaps the two 8-lane groups of a row
 __device__ __forceinline__ float dpp_ror8(float v) { return __builtin_bit_cast(float, dpp_mov32<0x128>(__builtin_bit_cast(uint32_t, v))); }
 __device__ __forceinline__ double dpp_ror8(double v) { return dpp_mov64<0x128>(v); }
@@ -433,11 +469,14 @@ template <> struct HP<double> {
 //              is four dependent (row max, TD value) pairs on one cell; here the row is read once, split
 //              into "the cell" and "max of the rest", and the four pairs run in registers: one store.
 //   ops, wo  operands / LDS store address of transition 4*(lane&7) + ((lane>>3)&3) ("exec layout")
-template <typename QT, int RDN, bool FIXED_POINTS, bool PER2>
-__device__ __forceinline__ void replay_group(int gi, uint32_t P, int lane_base, int nsub, const BlockOps<QT>& ops, unsigned wo,
-                                             unsigned rd_base, unsigned row_shift, unsigned my_step,
+//   key      (exec layout) 4 * (the transition's group) + the number of the pass it is stored in, or kKeyNone
+// GI >= 0: the group number as a compile-time constant (the unrolled copies), else gi_rt.
+template <typename QT, int RDN, bool FIXED_POINTS, bool PER2, int GI>
+__device__ __forceinline__ void replay_group(int gi_rt, uint32_t P, int lane_base, int nsub, const BlockOps<QT>& ops, unsigned wo,
+                                             unsigned key, unsigned rd_base, unsigned row_shift, unsigned my_step,
                                              unsigned row_bytes, QT alpha_gamma, QT alpha, QT gamma, bool upper_half,
                                              int block_step0, int replay_from) {
+    const int gi = GI >= 0 ? GI : gi_rt;
     // transitions that had already dropped out of the deque when the buffer trained are skipped
     const int first = replay_from - (block_step0 + gi * 4);      // <= 0: the whole group trains
     if (first >= 4) return;
@@ -496,50 +535,65 @@ __device__ __forceinline__ void replay_group(int gi, uint32_t P, int lane_base, 
         __builtin_amdgcn_wave_barrier();
         return;
     }
-    const uint32_t cuts = (((sP >> 28) & 7u) << 1) | (1u << nv);       // bit j: a pass ends before transition j
-    int lo = max(first, 0);
-    if (lo >= nv) return;
-    const unsigned d_in_group = my_step - (unsigned)(gi * 4);            // 0..3 in the lanes that hold this group's transitions
-    do {
-        const int hi = lo + 1 + __builtin_ctz(cuts >> (lo + 1));
+    // The ordinary passes.  Pass k holds the transitions between the k-th and the (k+1)-th cut of the group, exactly
+    // the serial loop's [lo, hi) ranges in the same order; phase (d2) has numbered them per lane (the key), has kept
+    // only the cuts between two transitions that train, and has given the others no key.  So pass 0 runs
+    // unconditionally, one scalar test of the cut bits finds the groups that need more, and a pass is row reads,
+    // row maximum, TD value and the store by the lanes whose key matches: no range, no ballot, no EXEC bookkeeping.
+    auto td_value = [&]() -> QT {
         QT m = lds_load<QT>(ad[0]);
 #pragma unroll
         for (int i = 1; i < RDN; i++) m = max_of(m, lds_load<QT>(ad[i]));
         m = group8_allmax(m);
-        const QT val = ops.value(m, alpha_gamma, alpha, gamma);
-        store_where(__ballot((unsigned)(d_in_group - (unsigned)lo) < (unsigned)(hi - lo)), wo, val);
-        __builtin_amdgcn_wave_barrier();
-        lo = hi;
-    } while (lo < nv);
+        return ops.value(m, alpha_gamma, alpha, gamma);
+    };
+    store_key<(GI >= 0 ? 4 * GI : -1)>(key, (unsigned)(gi * 4), wo, td_value());
+    __builtin_amdgcn_wave_barrier();
+    if (sP & 0x70000000u) {
+        unsigned k = (unsigned)(gi * 4 + 1);
+        const unsigned last = (unsigned)(gi * 4) + (unsigned)__builtin_popcount((sP >> 28) & 7u);
+        do {
+            store_key<-1>(key, k, wo, td_value());
+            __builtin_amdgcn_wave_barrier();
+        } while (++k <= last);
+    }
+}
+// the block's groups GI... as straight-line code; BOUNDED: stop at the first group behind the block's end
+template <typename QT, int RDN, bool FIXED_POINTS, bool PER2, bool BOUNDED, int... GI>
+__device__ __forceinline__ void replay_groups(std::integer_sequence<int, GI...>, uint32_t P, int lane_base, int nsub, const BlockOps<QT>& ops,
+                                              unsigned wo, unsigned key, unsigned rd_base, unsigned row_shift, unsigned my_step,
+                                              unsigned row_bytes, QT alpha_gamma, QT alpha, QT gamma, bool upper_half,
+                                              int block_step0, int replay_from) {
+    (void)(((!BOUNDED || GI * 4 < nsub) &&
+            (replay_group<QT, RDN, FIXED_POINTS, PER2, GI>(GI, P, lane_base, nsub, ops, wo, key, rd_base, row_shift, my_step, row_bytes,
+                                                           alpha_gamma, alpha, gamma, upper_half, block_step0, replay_from), true)) && ...);
 }
 // UNROLL: the block's 8 groups as straight-line code (group numbers become immediates, no loop control):
 // every variant with <= 128 steps per cycle except float64 + noise (hipcc 7.2 fails on that one: "illegal VGPR to SGPR copy").
+//   wo_key   (exec layout) LDS store address of the lane's transition | its replay key << kKeyShift
 template <typename QT, int RDN, bool FIXED_POINTS, bool UNROLL, bool PER2>
-__device__ __forceinline__ void replay_block(uint32_t P, int lane_base, int nsub, const BlockOps<QT>& ops, unsigned wo,
+__device__ __forceinline__ void replay_block(uint32_t P, int lane_base, int nsub, const BlockOps<QT>& ops, unsigned wo_key,
                                              unsigned rd_base, unsigned row_shift, unsigned my_step,
                                              unsigned row_bytes, QT alpha_gamma, QT alpha, QT gamma, bool upper_half,
                                              int block_step0, int replay_from) {
-    if (kAblate & 1) { ops.keep(); asm volatile("" :: "v"(wo), "v"(P)); return; }
+    if (kAblate & 1) { ops.keep(); asm volatile("" :: "v"(wo_key), "v"(P)); return; }
+    const unsigned key = wo_key >> kKeyShift, wo = wo_key & ((1u << kKeyShift) - 1u);
     if (UNROLL) {
         if (nsub == 32) {
-            // a full block (three of the four blocks of a 100-step episode): every "is this group / transition
+            // a full block (three of the four blocks of a 100-step episode): every "is this group
             // inside the block" test folds away
-#pragma unroll
-            for (int gi = 0; gi < 8; gi++)
-                replay_group<QT, RDN, FIXED_POINTS, PER2>(gi, P, lane_base, 32, ops, wo, rd_base, row_shift, my_step, row_bytes,
-                                                    alpha_gamma, alpha, gamma, upper_half, block_step0, replay_from);
+            replay_groups<QT, RDN, FIXED_POINTS, PER2, false>(std::make_integer_sequence<int, 8>{}, P, lane_base, 32, ops, wo, key, rd_base,
+                                                              row_shift, my_step, row_bytes, alpha_gamma, alpha, gamma, upper_half,
+                                                              block_step0, replay_from);
             return;
         }
-#pragma unroll
-        for (int gi = 0; gi < 8; gi++) {
-            if (gi * 4 >= nsub) break;
-            replay_group<QT, RDN, FIXED_POINTS, PER2>(gi, P, lane_base, nsub, ops, wo, rd_base, row_shift, my_step, row_bytes,
-                                                alpha_gamma, alpha, gamma, upper_half, block_step0, replay_from);
-        }
+        replay_groups<QT, RDN, FIXED_POINTS, PER2, true>(std::make_integer_sequence<int, 8>{}, P, lane_base, nsub, ops, wo, key, rd_base,
+                                                         row_shift, my_step, row_bytes, alpha_gamma, alpha, gamma, upper_half,
+                                                         block_step0, replay_from);
     } else {
         for (int gi = 0; gi * 4 < nsub; gi++)
-            replay_group<QT, RDN, FIXED_POINTS, PER2>(gi, P, lane_base, nsub, ops, wo, rd_base, row_shift, my_step, row_bytes,
-                                                alpha_gamma, alpha, gamma, upper_half, block_step0, replay_from);
+            replay_group<QT, RDN, FIXED_POINTS, PER2, -1>(gi, P, lane_base, nsub, ops, wo, key, rd_base, row_shift, my_step, row_bytes,
+                                                          alpha_gamma, alpha, gamma, upper_half, block_step0, replay_from);
     }
 }
 
@@ -1224,7 +1278,6 @@ k_wave_episodes(const WaveArgs a) {
                     last_price = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(price), ll),
                                                   __builtin_amdgcn_readlane(__double2loint(price), ll));
                 }
-                const v2u woq = pack_halves(tab0_off + (cwv[seg] & 0xFFFFu) * kCellScale, tab0_off + (cwv[seg] >> 16) * kCellScale);
                 if (epk == 1) {
                     if (valid) {
                         lr0 += r0d; lr1 += r1d;          // divided by T once per episode below
@@ -1243,16 +1296,23 @@ k_wave_episodes(const WaveArgs a) {
                 }
                 // visit counters (agents.py:76): the cell word goes to this wave's log (coalesced, L2-resident); the
                 // counts are built per game below.  Only transitions still in the deque when it trains are counted.
+                const bool trains = valid && tt >= replay_from;
                 if (a.counter && !(kAblate & 32))
                     a.tlog[(((size_t)wave_gid * kWaveMaxEpisodes + e) * NSEG + seg) * 64 + lane] =
-                        (valid && tt >= replay_from) ? cwv[seg] : 0xFFFFFFFFu;
+                        trains ? cwv[seg] : 0xFFFFFFFFu;
 
                 // ---- replay schedule of this segment's 16 groups of four transitions, lane-parallel.
                 //      Transition j may share a pass with an earlier transition i of its group unless it
                 //      reads the row i writes (live next_max, agents.py:71) or rewrites i's cell (:75).
-                uint32_t P;
+                //      A cut only counts between two transitions that both train (bit t of `pairs`: t - 1 and t do): the
+                //      serial loop never looks at a cut at or in front of its first transition, or behind its last.
+                //      cutq = the counted cut bits of the lane's group, in all four lanes of the quad.
+                uint32_t P, cutq;
                 bool any_fixed;
-                if (kAblate & 128) { P = (act[seg] >> 24) * 0x204081u; any_fixed = false; }
+                //      (without CYCLE nothing is dropped in front, and step 0 is no cut position)
+                const unsigned long long pairs = __ballot(CYCLE ? (valid && tt > replay_from) : valid);
+                const uint32_t quad0 = (uint32_t)lane & 60u;
+                if (kAblate & 128) { P = (act[seg] >> 24) * 0x204081u; any_fixed = false; cutq = 0u; }
                 else if constexpr (kMaskSched) {
                     // x_i = my word ^ the word of position i of my quad (DPP folded into the xor): every test below is a
                     // byte-field zero test of x_i.  With d = my next row ^ my row, "my next row == its row" is
@@ -1274,13 +1334,14 @@ k_wave_episodes(const WaveArgs a) {
                     const unsigned long long C3 = ((H2 >> 3) | (((H1 >> 3) | ((H0 >> 3) & ~C1)) & ~C2)) & M;
                     // four identical transitions that stay in their row: position 3 equals positions 0-2, position 0 stays
                     const unsigned long long F = (__ballot((x0 | x1 | x2) == 0u) >> 3) & __ballot(d == 0u) & M;
-                    const unsigned long long sched = C1 | (C2 << 1) | (C3 << 2) | (F << 3);
+                    const unsigned long long sched = (C1 & (pairs >> 1)) | ((C2 & (pairs >> 2)) << 1) | ((C3 & (pairs >> 3)) << 2) | (F << 3);
                     any_fixed = F != 0ull;
                     // the four next rows, 7 bits each: every lane shifts its own into place, two DPP ors collect the quad's
                     uint32_t rows = (w >> 24) << (7u * ((uint32_t)lane & 3u));
                     rows |= dpp_src<0xB1>(rows);                                   // quad_perm [1,0,3,2]
                     rows |= dpp_src<0x4E>(rows);                                   // quad_perm [2,3,0,1]
-                    P = ((uint32_t)(sched >> lane) << 28) | rows;                  // (read from lanes 4g only)
+                    cutq = (uint32_t)(sched >> quad0);                             // bits 0-2 cuts, bit 3 fixed point, then the next group's
+                    P = (cutq << 28) | rows;                                       // (read from lanes 4g only)
                 } else {
                     const uint32_t w = act[seg];
                     const uint32_t b0 = dpp_mov32<0x00>(w), b1 = dpp_mov32<0x55>(w), b2 = dpp_mov32<0xAA>(w),
@@ -1307,10 +1368,19 @@ k_wave_episodes(const WaveArgs a) {
                     const uint32_t same4 = ((quad_quiet && b0 == b1 && b1 == b2 && b2 == b3 && (b0 >> 24) == ((b0 >> 16) & 0xFFu)) ||
                                             (GREEDY && b0 == b2 && b1 == b3 && (b0 >> 24) == ((b1 >> 16) & 0xFFu) &&
                                              (b1 >> 24) == ((b0 >> 16) & 0xFFu) && (b0 >> 24) != (b1 >> 24))) ? 1u : 0u;
+                    cutq = (c1 | (c2 << 1) | (c3 << 2)) & ((uint32_t)(pairs >> quad0) >> 1);
                     P = (b0 >> 24) | ((b1 >> 24) << 7) | ((b2 >> 24) << 14) | ((b3 >> 24) << 21) |
-                        ((c1 | (c2 << 1) | (c3 << 2)) << 28) | (same4 << 31);
+                        (cutq << 28) | (same4 << 31);
                     any_fixed = __ballot((P >> 31) != 0u) != 0ull;
                 }
+
+                // The replay key of this lane's transition: 4 * (its group's number in its 32-transition block) + the
+                // number of its pass = the counted cuts in front of it in its group; kKeyNone if it does not train
+                // (behind the cycle's end, or dropped from the deque).  It travels to the exec layout in the upper bits
+                // of the store address (below 2^18), through the one ds_bpermute per block that the address takes anyway.
+                const uint32_t pass_no = (uint32_t)__builtin_popcount(cutq & ((1u << ((uint32_t)lane & 3u)) - 1u));
+                const uint32_t key_base = tab0_off + ((trains ? (quad0 & 28u) + pass_no : kKeyNone) << kKeyShift);
+                const v2u woq = pack_halves(key_base + (cwv[seg] & 0xFFFFu) * kCellScale, key_base + (cwv[seg] >> 16) * kCellScale);
 
                 // ---- (e) replay (agents.py:68-76): live next_max, writes in transition order
                 // GREEDY variants: a converged game repeats ONE transition all segment long (a fixed point of the
@@ -1348,10 +1418,11 @@ k_wave_episodes(const WaveArgs a) {
                             seg_done = true;
                             const BlockOps<QT> ops0 = make_ops(snap[seg], 0, r0d, r1d, alpha_h);      // step layout: lane 32h + t
                             const unsigned tabh = half ? tab1_off : tab0_off;
-                            if (period == 1) cyclic_segment<QT, 1>(ops0, woq.x, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
-                            else if (period == 2) cyclic_segment<QT, 2>(ops0, woq.x, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
-                            else if (period == 3) cyclic_segment<QT, 3>(ops0, woq.x, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
-                            else cyclic_segment<QT, 4>(ops0, woq.x, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
+                            const unsigned wo_step = woq.x & ((1u << kKeyShift) - 1u);            // (without the replay key)
+                            if (period == 1) cyclic_segment<QT, 1>(ops0, wo_step, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
+                            else if (period == 2) cyclic_segment<QT, 2>(ops0, wo_step, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
+                            else if (period == 3) cyclic_segment<QT, 3>(ops0, wo_step, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
+                            else cyclic_segment<QT, 4>(ops0, wo_step, W, nseg, lane, tabh, A, row_bytes, ag_h, alpha_h, gamma_h);
                             __builtin_amdgcn_wave_barrier();
                         }
                     }
