@@ -2,7 +2,9 @@
 oracle and the reference-generated fixture G7.  float32 tolerances (torch's summation order is
 unspecified): probabilities rtol 2e-5 (at the initial weight scale; the derived bound of
 tests/policy_reference.py otherwise, see tests/test_gpu_policy.py), clipped gradients rtol 2e-4 + atol 2e-6, Adam
-moments rtol 1e-3, parameters atol 5e-6 except Adam's sign-sensitive near-zero-gradient elements (<= 0.2 %)."""
+moments rtol 1e-3, parameters atol 5e-6 except Adam's sign-sensitive near-zero-gradient elements (<= 0.2 %).
+The tests here run ActorCritic and CAC in the clipped, critic-dominated regime only (fc_v at its initial bias), where the
+entropy term is below the tolerance; tests/test_gpu_update_terms.py pins each term of the three updates."""
 import os
 
 import numpy as np
