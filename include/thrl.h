@@ -566,9 +566,10 @@ int thrl_policy_track(const thrl_cfg* cfg, const void* q, const thrl_policy_trac
  * Equilibrium check of the greedy strategies (Calvano et al., AER 2020, equilibrium play and "Q-loss"): hold the
  * rivals' greedy strategies fixed, solve agent i's dynamic problem exactly, and report whether its own greedy
  * strategy is a best response on the path greedy play follows (Nash) and in every state (subgame perfect), and how
- * much value it gives up if not.  No reference counterpart.  QTable agents only, no env noise (intercept env_a);
- * q, and everything else of the batch, is read only.  Every [.][G] array has G = args.n_games: the first n_games
- * games of q.  All arithmetic is float64, every operation rounded once, in the order written here.
+ * much value it gives up if not.  No reference counterpart.  QTable agents only, no env noise (intercept env_a;
+ * thrl_equilibrium_noise below is the check under noise); q, and everything else of the batch, is read only.  Every
+ * [.][G] array has G = args.n_games: the first n_games games of q.  All arithmetic is float64, every operation rounded
+ * once, in the order written here.
  *
  * States.  Action tuples t = (a_0 .. a_{N-1}) are numbered with agent 0 slowest, T = prod_i n_actions_i of them.
  * Tuple t gives the price p(t) (scale_action, env_step) with rewards r_i(t), and the row tuple
@@ -902,6 +903,111 @@ typedef struct {
     double*  pi;                     /* device [G][J] or NULL                            */
 } thrl_stationary_args;
 int thrl_stationary(const thrl_cfg* cfg, const void* q, const thrl_stationary_args* args, void* stream);
+
+/*
+ * Equilibrium check under demand noise: thrl_equilibrium's question -- is agent i's greedy strategy a best response to
+ * the rivals' greedy strategies, and which share of the attainable value does it give up if not -- in the environment
+ * of thrl_stationary, where the demand intercept is redrawn with probability p at every step.  Under noise a game does
+ * not follow one path into one cycle: every price cell is reachable, the continuation value of an action is an
+ * expectation over where a shock puts the price, and a strategy's value solves a linear system on the cells.  There is
+ * no path, so there are no on-path outputs; the long-run distribution over the cells (thrl_stationary's pi) may be handed
+ * in as weights.  No reference counterpart.  QTable agents only; q, and everything else of the batch, is read only.
+ * Every [.][G] array has G = args.n_games: the first n_games games of q.  All arithmetic is float64, every operation
+ * rounded once, in the order written here.
+ *
+ * Cells, tuples, per-config tables, noise probability, policies: thrl_stationary's, word for word (cell_rows, det_cell,
+ * band_lo, band, noise_reward with J = n_cells and W = band_w; r_i(t) from the cached per-config plan; p_g and q_g = 1 -
+ * p_g; policy with or without THRL_EQN_POLICY_GIVEN; t_g(k) = the tuple of the clamped policy entries at
+ * cell_rows[.][k]).  cell_w and noise_price are not read.  *n_tuples (HOST, optional) receives T as soon as cfg is
+ * accepted.
+ *
+ * Agent i's problem in game g, with p = p_g, q = q_g, gamma = sweep_gamma[i][g] when given, else cfg.gamma[i] (the
+ * rules of thrl_equilibrium: without sweep_gamma a cfg.gamma[i] outside [0, 1) of a selected agent is
+ * THRL_ERR_BAD_CONFIG).  pi_i(k) = agent i's action in t_g(k); t(k, a) = t_g(k) with a in place i.
+ *   R(k, a) = q * r_i(t) + p * noise_reward_i(t)  with t = t(k, a)  (thrl_stationary's expected reward)
+ *   z_V(t)  = q * V[det_cell(t)] + p * b,  b = the sum over w = 0 .. W-1, ascending, from 0.0, of
+ *             band[t][w] * V[band_lo[t] + w]; terms whose cell band_lo[t] + w lies outside [0, J) are skipped, and the
+ *             q term is +0.0 where det_cell(t) lies outside [0, J) (it is still added).  z depends on the tuple alone.
+ *
+ * Evaluation of a strategy sigma from a start V^0 (Jacobi, all cells from the old iterate):
+ *   V^{m+1}(k) = R(k, sigma(k)) + gamma * z_{V^m}(t(k, sigma(k)))
+ *   chg_m = max_k |V^{m+1}(k) - V^m(k)|
+ * Stop after the first sweep with chg <= eval_tol.  An evaluation that has made max_sweeps sweeps without that is
+ * CAPPED.  The iterates contract with factor gamma in the maximum norm, so a stopped evaluation is within
+ * gamma / (1 - gamma) * eval_tol of the strategy's true value.
+ *
+ * Policy iteration from the agent's own strategy: sigma_0 = pi_i, V^0 = 0 in round 0, the previous round's V after it.
+ * Round n = 0, 1, ..: V_n = evaluation of sigma_n; if n == THRL_EQ_MAX_ITERS the (agent, game) is capped;
+ *   Q(k, a) = R(k, a) + gamma * z_{V_n}(t(k, a))
+ *   margin = ((2 * gamma) * gamma) * eval_tol / (1 - gamma)    (three products left to right, then one division)
+ *   sigma_{n+1}(k) = sigma_n(k) unless max_a Q(k, a) > Q(k, sigma_n(k)) + margin, then the first maximum (strict >, a
+ *   ascending); if no cell changed stop with iters = n.
+ * Why the margin: both Q(k, a) and Q(k, sigma_n(k)) carry gamma times the evaluation's error, at most gamma^2 / (1 -
+ * gamma) * eval_tol each, so a difference above 2 gamma^2 / (1 - gamma) * eval_tol is an improvement of the true values
+ * and the iteration cannot cycle on evaluation error.  With eval_tol = 0 the margin is 0 and the rule is
+ * thrl_equilibrium's keep-the-incumbent rule.  V_pi = V_0, V* = the last V_n, sigma* = the last strategy,
+ *   loss(k) = 0.0 where V*(k) == V_pi(k) or V*(k) == 0, else (V*(k) - V_pi(k)) / V*(k).
+ *
+ * Outputs, per selected agent i (bit i of agents) and game; entries of agents not selected are not written:
+ *   iters            the rounds n (0: pi_i is a best response in every cell), -1 when not solved
+ *   sweeps           all evaluation sweeps of the (agent, game)
+ *   n_diff_all       cells with sigma*(k) != pi_i(k)
+ *   loss_all         the largest loss(k);  loss_all_mean = (sum of loss(k) over ascending k from 0.0) / J
+ *   with weights (device double [G][J], e.g. thrl_stationary's pi; NULL: the three outputs are not written), each a sum
+ *   over ascending k from 0.0:
+ *     loss_w = sum w(k) * loss(k),  diff_w = sum of w(k) over the cells with sigma*(k) != pi_i(k) (+0.0 elsewhere),
+ *     v_w = sum w(k) * V_pi(k)
+ *   br_policy, v_opt, v_pi   optional [N][G][J]: sigma*, V*, V_pi per cell
+ *
+ * Games that are not solved; no other game is affected.  An entry of noise_prob_g outside (0, 1] (NaN included):
+ * iters = -1 and zeros in every output of every selected agent, the optional ones included (thrl_stationary's rule).
+ * Otherwise a gamma outside [0, 1) (NaN included), or a capped (agent, game): iters = -1, n_diff_all = 0, sweeps = the
+ * sweeps made, NaN in every float64 output of that agent, and br_policy = pi_i (thrl_equilibrium's rule).
+ *
+ * Limits: T <= THRL_EQ_MAX_TUPLES, J <= THRL_STAT_MAX_CELLS and a game's working set in one block's 64 KB of LDS:
+ * 50 J + 2064 bytes (three value arrays, the strategy, its reward, successor and band place per cell, the tuples, and
+ * 2,048 bytes of staging); otherwise THRL_ERR_UNSUPPORTED.  J = 1,269 fits.  Where 8 T more bytes fit, z is staged per
+ * tuple.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games outside [1, cfg.n_games], agents == 0 or with a bit >= N, a flag other than
+ * THRL_EQN_POLICY_GIVEN, gamma as above, n_cells < 1, band_w < 1, max_sweeps outside [1, THRL_STAT_MAX_ITERS],
+ * eval_tol < 0 or NaN, or a host-visible noise_prob outside (0, 1]; THRL_ERR_UNSUPPORTED for the limits; THRL_ERR_NULL
+ * for a missing table (cell_rows, det_cell, band_lo, band, noise_reward), policy, iters, sweeps, n_diff_all, loss_all or
+ * loss_all_mean, with weights a missing loss_w, diff_w or v_w, or a missing q without THRL_EQN_POLICY_GIVEN.
+ */
+#define THRL_EQN_POLICY_GIVEN 1
+typedef struct {
+    int32_t n_games;                 /* G in [1, cfg.n_games]                            */
+    int32_t agents;                  /* bit i set: solve agent i                         */
+    int32_t flags;                   /* 0 or THRL_EQN_POLICY_GIVEN                       */
+    int32_t n_cells;                 /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t band_w;                  /* W >= 1                                           */
+    int32_t max_sweeps;              /* in [1, THRL_STAT_MAX_ITERS], per evaluation      */
+    double  noise_prob;              /* p in (0, 1], read when noise_prob_g is NULL      */
+    double  eval_tol;                /* >= 0                                             */
+    const double* noise_prob_g;      /* device [G] or NULL                               */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    uint16_t* policy;                /* device [G][P]: out without the flag, in with it  */
+    const int32_t* cell_rows;        /* device [N][J]                                    */
+    const int32_t* det_cell;         /* device [T]                                       */
+    const int32_t* band_lo;          /* device [T]                                       */
+    const double* band;              /* device [T][W]                                    */
+    const double* noise_reward;      /* device [N][T]                                    */
+    const double* weights;           /* device [G][J] or NULL                            */
+    int32_t* n_tuples;               /* HOST [1] <- T, or NULL                           */
+    int32_t* iters;                  /* device [N][G]                                    */
+    int32_t* sweeps;                 /* device [N][G]                                    */
+    int32_t* n_diff_all;             /* device [N][G]                                    */
+    double*  loss_all;               /* device [N][G]                                    */
+    double*  loss_all_mean;          /* device [N][G]                                    */
+    double*  loss_w;                 /* device [N][G], with weights                      */
+    double*  diff_w;                 /* device [N][G], with weights                      */
+    double*  v_w;                    /* device [N][G], with weights                      */
+    uint16_t* br_policy;             /* device [N][G][J] or NULL                         */
+    double*  v_opt;                  /* device [N][G][J] or NULL                         */
+    double*  v_pi;                   /* device [N][G][J] or NULL                         */
+} thrl_equilibrium_noise_args;
+int thrl_equilibrium_noise(const thrl_cfg* cfg, const void* q, const thrl_equilibrium_noise_args* args, void* stream);
 
 /*
  * Strategies as tables over the game's action tuples, for ANY discrete agent: QTable, Reinforce, ActorCritic.  No

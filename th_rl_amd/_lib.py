@@ -204,6 +204,26 @@ class StationaryArgs(ctypes.Structure):
     ]
 
 
+EQN_POLICY_GIVEN = 1
+
+
+class EquilibriumNoiseArgs(ctypes.Structure):
+    """thrl_equilibrium_noise_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("agents", ctypes.c_int32), ("flags", ctypes.c_int32), ("n_cells", ctypes.c_int32),
+        ("band_w", ctypes.c_int32), ("max_sweeps", ctypes.c_int32),
+        ("noise_prob", ctypes.c_double), ("eval_tol", ctypes.c_double),
+        ("noise_prob_g", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p), ("policy", ctypes.c_void_p),
+        ("cell_rows", ctypes.c_void_p), ("det_cell", ctypes.c_void_p), ("band_lo", ctypes.c_void_p),
+        ("band", ctypes.c_void_p), ("noise_reward", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+        ("n_tuples", ctypes.POINTER(ctypes.c_int32)),
+        ("iters", ctypes.c_void_p), ("sweeps", ctypes.c_void_p), ("n_diff_all", ctypes.c_void_p),
+        ("loss_all", ctypes.c_void_p), ("loss_all_mean", ctypes.c_void_p), ("loss_w", ctypes.c_void_p),
+        ("diff_w", ctypes.c_void_p), ("v_w", ctypes.c_void_p),
+        ("br_policy", ctypes.c_void_p), ("v_opt", ctypes.c_void_p), ("v_pi", ctypes.c_void_p),
+    ]
+
+
 TP_MAX_TUPLES = 4096
 
 
@@ -368,6 +388,7 @@ SYMBOLS = [
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
+    "thrl_equilibrium_noise",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
     "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary", "thrl_price_probs", "thrl_sampled_chain",
     "thrl_sampled_noise_chain",
@@ -484,6 +505,8 @@ def load():
     L.thrl_attractors.argtypes = [cfgp, vp, ctypes.POINTER(AttractorsArgs), vp]
     L.thrl_stationary.restype = ctypes.c_int
     L.thrl_stationary.argtypes = [cfgp, vp, ctypes.POINTER(StationaryArgs), vp]
+    L.thrl_equilibrium_noise.restype = ctypes.c_int
+    L.thrl_equilibrium_noise.argtypes = [cfgp, vp, ctypes.POINTER(EquilibriumNoiseArgs), vp]
     L.thrl_tuple_policy.restype = ctypes.c_int
     L.thrl_tuple_policy.argtypes = [cfgp, vp, ctypes.POINTER(TuplePolicyArgs), vp]
     L.thrl_tuple_walk.restype = ctypes.c_int

@@ -194,7 +194,7 @@ def n_states(batch, call, args):
 
 # ---------------------------------------------------------------------------------------------- the batch methods
 class AnalysisMethods:
-    """The analysis methods of GameBatch and MixedGameBatch.  The QTable analyses (deviation, equilibrium, crossplay,
+    """The analysis methods of GameBatch and MixedGameBatch.  The QTable analyses (deviation, equilibrium(_noise), crossplay,
     attractors, stationary, track_convergence) read the tables, which both classes lay out alike; a MixedGameBatch with a
     neural agent raises ThrlError there, and its greedy_* / sampled_play methods are the ones for any mix of QTable,
     Reinforce and ActorCritic agents.  Tables, counters, state, epsilon and the episode index are never touched."""
@@ -235,6 +235,24 @@ class AnalysisMethods:
         self._qtable_only("equilibrium", eq.NEURAL_FOLLOW_UP)
         self._ready()
         return eq.run(self, agents=agents, state0=state0, policies=policies, tol=tol)
+
+    def equilibrium_noise(self, agents=None, noise_prob=None, eval_tol=1e-12, max_sweeps=8192, policies=False, tol=0.0,
+                          q=None, policy=None, weights="stationary", n_games=None, tabs=None):
+        """The equilibrium check UNDER DEMAND NOISE (thrl_equilibrium_noise; definitions in include/thrl.h): for each
+        agent in `agents` (default all) the exact best response to the others' greedy strategies in the environment of
+        stationary(), where every price cell is reachable and a strategy's value solves a linear system on the cells
+        (Jacobi sweeps to eval_tol, at most max_sweeps per evaluation; policy iteration with a margin that evaluation
+        error cannot cross).  Returns a dict of numpy arrays: iters (-1: not solved or capped), sweeps, n_diff_all,
+        loss_all, loss_all_mean [N, G]; with weights loss_w, diff_w, v_w [N, G] (weights: "stationary" = each game's
+        long-run distribution over the cells, stationary(pi=True, start="reset") at the same noise and policy -- its last
+        iterate also where that iteration stopped at its step limit; None; or [G, J] values); the host-side flags br_all, br_w [N, G] and perfect [G] for the tolerance `tol`; noise_prob [G],
+        n_cells, agents.  policies=True adds br_policy (uint16), v_opt, v_pi [N, G, J].  noise_prob, q, policy, n_games
+        and tabs as in stationary(); the per-game sweep gamma is each game's discount factor."""
+        from . import equilibrium as eq
+        self._qtable_only("equilibrium_noise", eq.NEURAL_FOLLOW_UP)
+        self._ready()
+        return eq.run_noise(self, agents=agents, noise_prob=noise_prob, eval_tol=eval_tol, max_sweeps=max_sweeps,
+                            policies=policies, tol=tol, q=q, policy=policy, weights=weights, n_games=n_games, tabs=tabs)
 
     def crossplay(self, seats, steps=0, horizon=None, state0=None, rows=False, group_stats=None, q=None, policy=None,
                   budget=None):

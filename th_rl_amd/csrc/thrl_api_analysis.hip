@@ -15,6 +15,7 @@
 #include "thrl_crossplay.h"
 #include "thrl_deviation.h"
 #include "thrl_equilibrium.h"
+#include "thrl_equilibrium_noise.h"
 #include "thrl_host.h"
 #include "thrl_tuple_analysis.h"
 #include "thrl_tuple_attractors.h"
@@ -72,11 +73,39 @@ int check_deviation(const thrl_cfg* c, int deviator, int dev_len, int n_steps, i
                     deviator, c->n_actions[deviator]);
     return THRL_OK;
 }
-int check_iters_tol(int max_iters, double tol) {
+int check_iters_tol(int max_iters, double tol, const char* iters_name = "max_iters", const char* tol_name = "tol") {
     if (max_iters < 1 || max_iters > THRL_STAT_MAX_ITERS)
-        return fail(THRL_ERR_BAD_CONFIG, "max_iters=%d out of [1,%d]", max_iters, THRL_STAT_MAX_ITERS);
-    return tol >= 0.0 ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "tol=%g must be >= 0", tol);
+        return fail(THRL_ERR_BAD_CONFIG, "%s=%d out of [1,%d]", iters_name, max_iters, THRL_STAT_MAX_ITERS);
+    return tol >= 0.0 ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "%s=%g must be >= 0", tol_name, tol);
 }
+// ---- the checks of the two calls on the cells of noisy play (thrl_stationary, thrl_equilibrium_noise), `call` their name
+int check_tuple_limit(const thrl_cfg* c, const char* call, int* T) {   // T = prod n_actions needs no plan
+    int64_t T64 = 1;
+    for (int i = 0; i < c->n_agents; i++) {
+        T64 *= c->n_actions[i];
+        if (T64 > THRL_EQ_MAX_TUPLES)
+            return fail(THRL_ERR_UNSUPPORTED, "%s: more than %d action tuples (prod n_actions)", call, THRL_EQ_MAX_TUPLES);
+    }
+    *T = (int)T64;
+    return THRL_OK;
+}
+int check_cells_band(int n_cells, int band_w) {
+    const bool ok = n_cells >= 1 && band_w >= 1;
+    return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "n_cells=%d and band_w=%d must be >= 1", n_cells, band_w);
+}
+int check_noise_prob(const double* noise_prob_g, double noise_prob) {  // the host-visible value; the array is the device's
+    const bool ok = noise_prob_g || (noise_prob > 0.0 && noise_prob <= 1.0);
+    return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of (0, 1]", noise_prob);
+}
+int check_cell_limit(const char* call, int n_cells) {
+    const bool ok = n_cells <= THRL_STAT_MAX_CELLS;
+    return ok ? THRL_OK : fail(THRL_ERR_UNSUPPORTED, "%s: n_cells=%d, at most %d", call, n_cells, THRL_STAT_MAX_CELLS);
+}
+int lds_refusal(const char* call, int64_t need, int N, int n_cells) {
+    return fail(THRL_ERR_UNSUPPORTED, "%s: %lld bytes of LDS per game (N=%d, n_cells=%d)", call, (long long)need, N, n_cells);
+}
+int missing(const char* names) { return fail(THRL_ERR_NULL, "%s is NULL", names); }
+int missing_q(const char* flag) { return fail(THRL_ERR_NULL, "q is NULL without %s", flag); }
 int check_eps(int N, const int32_t* kind, const double* eps) {  // the scalar epsilons of the QTable agents (no eps_g)
     for (int i = 0; i < N; i++)
         if (kind[i] == 0 && !(eps[i] >= 0.0 && eps[i] <= 1.0))
@@ -1029,41 +1058,30 @@ int thrl_stationary(const thrl_cfg* c, const void* q, const thrl_stationary_args
     const int N = c->n_agents;
     // T is the product of the action counts: the tuple limit and *n_tuples need no plan, and every host-visible
     // argument is checked before the device is touched (the plan is fetched, and cached, only by a call that launches)
-    int64_t T64 = 1;
-    for (int i = 0; i < N; i++) {
-        T64 *= c->n_actions[i];
-        if (T64 > THRL_EQ_MAX_TUPLES)
-            return fail(THRL_ERR_UNSUPPORTED, "thrl_stationary: more than %d action tuples (prod n_actions)",
-                        THRL_EQ_MAX_TUPLES);
-    }
-    const int T = (int)T64;
+    int T = 0;
+    if ((rc = check_tuple_limit(c, "thrl_stationary", &T)) != THRL_OK) return rc;
     if (x->n_tuples) *x->n_tuples = T;
     if ((rc = check_games_of(x->n_games, c)) != THRL_OK) return rc;
     if (x->flags & ~(THRL_STAT_POLICY_GIVEN | THRL_STAT_START_STATE))
         return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
-    if (x->n_cells < 1 || x->band_w < 1)
-        return fail(THRL_ERR_BAD_CONFIG, "n_cells=%d and band_w=%d must be >= 1", x->n_cells, x->band_w);
+    if ((rc = check_cells_band(x->n_cells, x->band_w)) != THRL_OK) return rc;
     if ((rc = check_iters_tol(x->max_iters, x->tol)) != THRL_OK) return rc;
-    if (!x->noise_prob_g && !(x->noise_prob > 0.0 && x->noise_prob <= 1.0))
-        return fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of (0, 1]", x->noise_prob);
-    if (x->n_cells > THRL_STAT_MAX_CELLS)
-        return fail(THRL_ERR_UNSUPPORTED, "thrl_stationary: n_cells=%d, at most %d", x->n_cells, THRL_STAT_MAX_CELLS);
+    if ((rc = check_noise_prob(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
+    if ((rc = check_cell_limit("thrl_stationary", x->n_cells)) != THRL_OK) return rc;
     // LDS of a block: the two iterates, the staging of the ordered sums and the tuple per cell must fit
     StatArgs a;
     memset(&a, 0, sizeof(a));
     a.N = N; a.J = x->n_cells;
     const int64_t need = thrl::stat_layout(a);
-    if (need > kStatLdsBudget)
-        return fail(THRL_ERR_UNSUPPORTED, "thrl_stationary: %lld bytes of LDS per game (N=%d, n_cells=%d)", (long long)need,
-                    N, x->n_cells);
+    if (need > kStatLdsBudget) return lds_refusal("thrl_stationary", need, N, x->n_cells);
     const bool given = (x->flags & THRL_STAT_POLICY_GIVEN) != 0;
     const bool start_state = (x->flags & THRL_STAT_START_STATE) != 0;
     if (!x->cell_rows || !x->cell_w || !x->det_cell || !x->band_lo || !x->band || !x->noise_reward || !x->noise_price)
-        return fail(THRL_ERR_NULL, "cell_rows / cell_w / det_cell / band_lo / band / noise_reward / noise_price is NULL");
+        return missing("cell_rows / cell_w / det_cell / band_lo / band / noise_reward / noise_price");
     if (!x->policy || !x->iters || !x->change || !x->mass || !x->stat_reward || !x->stat_action || !x->stat_price)
-        return fail(THRL_ERR_NULL, "policy / iters / change / mass / stat_reward / stat_action / stat_price is NULL");
+        return missing("policy / iters / change / mass / stat_reward / stat_action / stat_price");
     if (start_state && !x->state0) return fail(THRL_ERR_NULL, "state0 is NULL with THRL_STAT_START_STATE");
-    if (!given && !q) return fail(THRL_ERR_NULL, "q is NULL without THRL_STAT_POLICY_GIVEN");
+    if (!given && !q) return missing_q("THRL_STAT_POLICY_GIVEN");
 
     a.G = x->n_games; a.T = T; a.W = x->band_w;
     a.max_iters = x->max_iters; a.start_state = start_state;
@@ -1092,6 +1110,66 @@ int thrl_stationary(const thrl_cfg* c, const void* q, const thrl_stationary_args
     const int grid = grid_for(cus, lds_cu, a.lds_bytes, kStatMaxBlocksPerCu, a.G);
     const int e = thrl::launch_stationary(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_stationary launch") : THRL_OK;
+}
+
+int thrl_equilibrium_noise(const thrl_cfg* c, const void* q, const thrl_equilibrium_noise_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_stationary's checks in its order, with the agents and their gammas as thrl_equilibrium checks them
+    int T = 0;
+    if ((rc = check_tuple_limit(c, "thrl_equilibrium_noise", &T)) != THRL_OK) return rc;
+    if (x->n_tuples) *x->n_tuples = T;
+    if ((rc = check_games_of(x->n_games, c)) != THRL_OK) return rc;
+    if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
+    if (x->flags & ~THRL_EQN_POLICY_GIVEN) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (!x->sweep_gamma && (rc = check_gamma(c, x->agents)) != THRL_OK) return rc;
+    if ((rc = check_cells_band(x->n_cells, x->band_w)) != THRL_OK) return rc;
+    if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
+    if ((rc = check_noise_prob(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
+    if ((rc = check_cell_limit("thrl_equilibrium_noise", x->n_cells)) != THRL_OK) return rc;
+    EqnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.J = x->n_cells; a.T = T;
+    const int64_t need = thrl::eqn_layout(a);
+    if (need > kEqnLdsBudget) return lds_refusal("thrl_equilibrium_noise", need, N, x->n_cells);
+    const bool given = (x->flags & THRL_EQN_POLICY_GIVEN) != 0;
+    if (!x->cell_rows || !x->det_cell || !x->band_lo || !x->band || !x->noise_reward)
+        return missing("cell_rows / det_cell / band_lo / band / noise_reward");
+    if (!x->policy || !x->iters || !x->sweeps || !x->n_diff_all || !x->loss_all || !x->loss_all_mean)
+        return missing("policy / iters / sweeps / n_diff_all / loss_all / loss_all_mean");
+    if (x->weights && (!x->loss_w || !x->diff_w || !x->v_w)) return missing("with weights, loss_w / diff_w / v_w");
+    if (!given && !q) return missing_q("THRL_EQN_POLICY_GIVEN");
+
+    a.G = x->n_games; a.W = x->band_w; a.agents = x->agents;
+    a.max_sweeps = x->max_sweeps;
+    a.noise_prob = x->noise_prob; a.eval_tol = x->eval_tol;
+    fill_agents(c, a.ag, nullptr);
+    tuple_strides(c, nullptr, a.tstride);
+    a.P = table_rows(a.ag, N, a.row_off, nullptr, nullptr);
+    int devs = 0;
+    if (hipGetDeviceCount(&devs) != hipSuccess || devs <= 0) {
+        (void)hipGetLastError();
+        return hip_fail((int)hipErrorNoDevice, "thrl_equilibrium_noise");
+    }
+    EqSlot sl;
+    if ((rc = eq_cached_plan(c, sl)) != THRL_OK) return rc;
+
+    if (!given && (rc = extract_policies(c, q, x->n_games, x->policy, stream)) != THRL_OK) return rc;
+
+    a.policy = x->policy; a.noise_prob_g = x->noise_prob_g; a.sweep_gamma = x->sweep_gamma;
+    a.rew = (const double*)sl.mem;
+    a.cell_rows = x->cell_rows; a.det_cell = x->det_cell; a.band_lo = x->band_lo; a.band = x->band;
+    a.noise_reward = x->noise_reward; a.weights = x->weights;
+    a.iters = x->iters; a.sweeps = x->sweeps; a.n_diff_all = x->n_diff_all;
+    a.loss_all = x->loss_all; a.loss_all_mean = x->loss_all_mean; a.loss_w = x->loss_w; a.diff_w = x->diff_w; a.v_w = x->v_w;
+    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+    int cus = 0, lds_cu = 0;
+    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
+    const int grid = grid_for(cus, lds_cu, a.lds_bytes, kEqnMaxBlocksPerCu, a.G);
+    const int e = thrl::launch_equilibrium_noise(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_equilibrium_noise launch") : THRL_OK;
 }
 
 }  // extern "C"

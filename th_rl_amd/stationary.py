@@ -47,7 +47,7 @@ def check_config(config):
     an.check_qtable_only(config, "stationary", NEURAL_FOLLOW_UP)
 
 
-def _check_prob(p, what):
+def check_prob(p, what):
     if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 < float(p) <= 1.0:
         raise ValueError("%s must be a number in (0, 1], got %r" % (what, p))
     return float(p)
@@ -59,7 +59,7 @@ def parse_options(opt, config):
     check_config(config)
     out = an.options("stationary", opt, DEFAULTS, tables=True)
     if out["noise_prob"] is not None:
-        out["noise_prob"] = _check_prob(out["noise_prob"], "training.stationary.noise_prob")
+        out["noise_prob"] = check_prob(out["noise_prob"], "training.stationary.noise_prob")
     else:       # the run's own noise: refuse a noise-free run before training, as the batch would after it
         env = dict(_lib.ENV_DEFAULTS, **config["environment"])
         sweep = config.get("training", {}).get("sweep") or {}

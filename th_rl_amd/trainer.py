@@ -28,7 +28,11 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                      # smooths each run with ewm(halflife=1000) first; that is not done here).
                  "equilibrium": null,  # true or {"agents": [all], "tol": 0.0, "policies": false, "tables": "final"}: after
                                        # training (and the deviation analysis) the equilibrium check of the greedy
-                                       # strategies (equilibrium.py, QTable agents only): equilibrium.json, eq_*.npy
+                                       # strategies (equilibrium.py, QTable agents only): equilibrium.json, eq_*.npy;
+                                       # "noise": true or {"noise_prob": null, "eval_tol": 1e-12, "max_sweeps": 8192}
+                                       # adds the check UNDER DEMAND NOISE (noise_prob null = the run's own), weighted
+                                       # by the long-run distribution of noisy greedy play: equilibrium_noise.json,
+                                       # eqn_*.npy
                  "crossplay": null,  # true or {"rounds": 8, "scheme": "rotate" | "random", "against": "own" | "all",
                                      # "steps": 0, "horizon": null, "seed": 0, "tables": "final" | "converged"}: after
                                      # training (and the equilibrium check) greedy play between agents of DIFFERENT

@@ -52,7 +52,7 @@ def parse_options(opt, config):
     tp.check_config(config)
     out = an.options("greedy_stationary", opt, DEFAULTS)
     if out["noise_prob"] is not None:
-        out["noise_prob"] = sn._check_prob(out["noise_prob"], name + ".noise_prob")
+        out["noise_prob"] = sn.check_prob(out["noise_prob"], name + ".noise_prob")
     else:       # the run's own noise: refuse a noise-free run before training, as the batch would after it
         env = dict(_lib.ENV_DEFAULTS, **config["environment"])
         sweep = config.get("training", {}).get("sweep") or {}

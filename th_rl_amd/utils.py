@@ -244,6 +244,48 @@ def equilibrium_games(exp_path, agent=0):
     return pandas.concat(frames)
 
 
+def equilibrium_noise_summary(exp_path):
+    """A run's equilibrium check under demand noise (training.equilibrium with "noise"): equilibrium_noise.json's
+    summary as a DataFrame.  Rows with an agent: games, capped, br_all, br_w (fractions of games in which the agent's
+    greedy strategy is a best response in every cell / where noisy greedy play is in the long run), loss_all_q* /
+    loss_w_q* (over the games with a positive loss), diff_w_mean, sweeps_max.  Rows with agent NaN: the group's perfect
+    fraction."""
+    if not os.path.isfile(os.path.join(exp_path, "equilibrium_noise.json")):
+        raise KeyError("no equilibrium check under noise (equilibrium_noise.json) under %s (training.equilibrium.noise)"
+                       % exp_path)
+    desc = _load_json(exp_path, "equilibrium_noise.json")
+    df = pandas.DataFrame(desc["summary"])
+    df["n_cells"] = int(desc["n_cells"])
+    df["tol"] = float(desc["options"]["tol"])
+    return df
+
+
+def equilibrium_noise_games(exp_path, agent=0):
+    """Per-game results of the equilibrium check under demand noise for `agent`, one row per game indexed by its GLOBAL
+    id: noise_prob, iters, sweeps, n_diff_all, loss_all, loss_all_mean, loss_w, diff_w, v_w, and the flags br_all, br_w
+    (this agent) and perfect (all solved agents) at the run's tol.  Reads exp_path's eqn_*.npy, or those of
+    exp_path/shard*/ in game order."""
+    from th_rl_amd import equilibrium as eq
+    dirs = _run_dirs(exp_path, "eqn_iters.npy", "equilibrium check under noise", "equilibrium.noise")
+    frames = []
+    for d in dirs:
+        opt = _load_json(d, "equilibrium_noise.json")["options"]
+        off = _game_offset(d, exp_path)
+        g = eq.load_noise_games(d)
+        fl = eq.flags_noise(g, opt["agents"], opt["tol"])
+        cols = {"noise_prob": g["noise_prob"]}
+        for f in eq.NOISE_INT + eq.NOISE_FLOAT + eq.NOISE_WEIGHTED:
+            if f in g:
+                cols[f] = g[f][int(agent)]
+        cols["br_all"] = fl["br_all"][int(agent)]
+        if "br_w" in fl:
+            cols["br_w"] = fl["br_w"][int(agent)]
+        cols["perfect"] = fl["perfect"]
+        n = g["noise_prob"].shape[0]
+        frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
+    return pandas.concat(frames)
+
+
 def crossplay_summary(exp_path):
     """A run's cross-play (training.crossplay): crossplay.json's summary as a DataFrame with one row per (group of
     seat 0, partner_group) -- matches, cycles, fixed_points, the cross-play profit gain's mean and quantiles (delta_*),
