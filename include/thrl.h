@@ -1453,6 +1453,114 @@ typedef struct {
 int thrl_tuple_stationary(const thrl_cfg* cfg, const thrl_tuple_stationary_args* args, void* stream);
 
 /*
+ * thrl_tuple_equilibrium_noise: the equilibrium check under demand noise (thrl_equilibrium_noise) for ANY mix of
+ * QTable, Reinforce and ActorCritic agents: is agent i's strategy a best response to the rivals' strategies in the
+ * environment of thrl_tuple_stationary, and which share of the attainable value does it give up if not.  No reference
+ * counterpart.  The world is thrl_tuple_stationary's, unchanged: the action tuples t < T = args.n_tuples, tuple_policy
+ * [G][N][T] (the strategies evaluated exactly at each tuple's noise-free price), cell_policy [G][N][J] (the strategies
+ * sampled at the midpoints of the J = args.n_cells cells), the per-config tables reward, band_lo, band (W = band_w) and
+ * noise_reward, n(t, k), p_g and q_g = 1 - p_g with thrl_stationary's host-visible and per-game rules; entries of the
+ * strategies at or above n_actions_i are clamped to n_actions_i - 1.  Of a valid cfg only n_agents and n_actions are
+ * used; nothing of a batch is read or written, every input is read only.  All arithmetic is float64, every operation
+ * rounded once, in the order written here.
+ *
+ * States.  An agent sees the price.  The prices that occur are the T noise-free tuple prices, each reached with
+ * probability q after its tuple, and the continuum reached after a shock, lumped into the J cells.  The state set is
+ * S = T + J, the tuple-states first: state s < T is tuple-state t = s, state s >= T is cell-state k = s - T.
+ *   tuple-state t: the price is exactly tuple t's; the tuple played there is F_g(t) (thrl_tuple_stationary)
+ *   cell-state k:  the price lies in cell k; the tuple played there is tau_g(k)
+ * A value function V has the parts V_T [T] and V_J [J].  pi_i(s) = agent i's action in the tuple played at s;
+ * t(s, a) = that tuple with a in place i.  Agent i's problem in game g, with p = p_g, q = q_g, gamma =
+ * sweep_gamma[i][g] when given, else args.gamma[i] (without sweep_gamma an args.gamma[i] outside [0, 1) of a selected
+ * agent is THRL_ERR_BAD_CONFIG; cfg.gamma is not read: a network's gamma is not the placeholder table slot's):
+ *   R(s, a) = q * reward_i(t) + p * noise_reward_i(t)  with t = t(s, a)
+ *   z_V(t)  = q * V_T[t] + p * b,  b = the sum over w = 0 .. W-1, ascending, from 0.0, of
+ *             band[t][w] * V_J[band_lo[t] + w]; terms whose cell band_lo[t] + w lies outside [0, J) are skipped.
+ * Both depend on the tuple alone.
+ *
+ * Solver: thrl_equilibrium_noise's, word for word, with s over the S states in place of its cells k: the evaluation of
+ * a strategy by Jacobi sweeps, V^{m+1}(s) = R(s, sigma(s)) + gamma * z_{V^m}(t(s, sigma(s))), chg_m = max_s |V^{m+1}(s)
+ * - V^m(s)|, stopped after the first sweep with chg <= eval_tol and CAPPED after max_sweeps sweeps without that; policy
+ * iteration from sigma_0 = pi_i and V^0 = 0 (the previous round's V after round 0) with Q(s, a) = R(s, a) + gamma *
+ * z_{V_n}(t(s, a)), margin = ((2 * gamma) * gamma) * eval_tol / (1 - gamma), the keep-the-incumbent / first-maximum
+ * rule, the cap THRL_EQ_MAX_ITERS on the rounds, V_pi = V_0, V* = the last V_n, sigma* = the last strategy and
+ *   loss(s) = 0.0 where V*(s) == V_pi(s) or V*(s) == 0, else (V*(s) - V_pi(s)) / V*(s).
+ * A best response may act differently at a tuple's exact price than in the cell around it: the two are different
+ * states, in which the rivals (whose strategies are sampled at the cell's midpoint) may act differently too.
+ *
+ * Outputs, per selected agent i (bit i of agents) and game; entries of agents not selected are not written:
+ *   iters, sweeps      the rounds n (-1 when not solved) and all evaluation sweeps of the (agent, game)
+ *   n_diff_tuples      tuple-states with sigma*(s) != pi_i(s);  n_diff_cells the same over the cell-states
+ *   loss_all           the largest loss(s) over all S states
+ *   loss_tuples_mean   (sum of loss(s) over the tuple-states, ascending from 0.0) / T
+ *   loss_cells_mean    (sum of loss(s) over the cell-states, ascending from 0.0) / J
+ *   with pi (device double [G][T], thrl_tuple_stationary's long-run distribution over the tuple played, finite; NULL:
+ *   the three outputs are not written) the weights say where decisions are made in the long run:
+ *     w(t) = q_g * pi(t) at tuple-state t;  w(k) = p_g * nu(k) at cell-state k, nu(k) = the sum over ascending t from 0.0
+ *     of pi(t) * n(t, k) over the t with 0 <= k - band_lo[t] < W (elsewhere n(t, k) = 0: the term is skipped)
+ *     loss_w = sum w(s) * loss(s),  diff_w = sum of w(s) over the states with sigma*(s) != pi_i(s) (+0.0 elsewhere),
+ *     v_w = sum w(s) * V_pi(s); each one sum from 0.0 over the tuple-states first, then the cells, ascending
+ *   br_policy (uint16), v_opt, v_pi   optional [N][G][S]: sigma*, V*, V_pi per state, tuple-states first
+ *
+ * Games that are not solved, as in thrl_equilibrium_noise; no other game is affected.  An entry of noise_prob_g outside
+ * (0, 1] (NaN included): iters = -1 and zeros in every output of every selected agent, the optional ones included.
+ * Otherwise a gamma outside [0, 1) (NaN included), or a capped (agent, game): iters = -1, n_diff_tuples = n_diff_cells
+ * = 0, sweeps = the sweeps made, NaN in every float64 output of that agent, and br_policy = pi_i.
+ *
+ * Working set.  A game is solved by one wavefront in LDS: three value arrays over the states (24 S bytes), the tuple
+ * played at a state by the incumbent and by the current strategy (4 S), R and R + gamma * z per tuple (16 T) and 2,048
+ * bytes of staging, the sum rounded up to 16 bytes: 44 T + 28 J + 2048.  A sweep computes z once per tuple (T (W + 1)
+ * multiply-adds) and reads it back per state.  Above THRL_TEN_MAX_LDS = 160 KB (a CU's LDS on CDNA4), or the device's
+ * own limit, the call returns THRL_ERR_UNSUPPORTED without launching: T = 441 with J = 4096 fits (136,144 bytes), T = J
+ * = 2,247 fits, T = J = 4096 (296,960 bytes) does not.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games < 1, flags or reserved != 0, agents == 0 or with a bit >= N, a kind outside
+ * [0, 3], n_tuples < 1 or n_tuples != prod_i n_actions_i, gamma as above, n_cells < 1, band_w < 1, max_sweeps outside
+ * [1, THRL_STAT_MAX_ITERS], eval_tol < 0 or NaN, or a host-visible noise_prob outside (0, 1]; THRL_ERR_UNSUPPORTED for
+ * a CAC agent (kind 3), n_tuples > THRL_TP_MAX_TUPLES, n_cells > THRL_STAT_MAX_CELLS or the working set; THRL_ERR_NULL
+ * for a missing cfg, args, tuple_policy, cell_policy, table (reward, band_lo, band, noise_reward), iters, sweeps,
+ * n_diff_tuples, n_diff_cells, loss_all, loss_tuples_mean or loss_cells_mean, or with pi a missing loss_w, diff_w or v_w.
+ */
+#define THRL_TEN_MAX_LDS (160 * 1024)
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of tuple_policy and cell_policy    */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t n_cells;                 /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t band_w;                  /* W >= 1                                           */
+    int32_t max_sweeps;              /* in [1, THRL_STAT_MAX_ITERS], per evaluation      */
+    int32_t agents;                  /* bit i set: solve agent i                         */
+    int32_t flags;                   /* 0                                                */
+    int32_t reserved;                /* 0                                                */
+    int32_t kind[THRL_MAXA];         /* 0 = QTable, 1 = Reinforce, 2 = ActorCritic       */
+    double  gamma[THRL_MAXA];        /* in [0, 1), read when sweep_gamma is NULL         */
+    double  noise_prob;              /* p in (0, 1], read when noise_prob_g is NULL      */
+    double  eval_tol;                /* >= 0                                             */
+    const double* noise_prob_g;      /* device [G] or NULL                               */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    const uint16_t* tuple_policy;    /* device [G][N][T]                                 */
+    const uint16_t* cell_policy;     /* device [G][N][J]                                 */
+    const double* reward;            /* device [N][T]                                    */
+    const int32_t* band_lo;          /* device [T]                                       */
+    const double* band;              /* device [T][W]                                    */
+    const double* noise_reward;      /* device [N][T]                                    */
+    const double* pi;                /* device [G][T] or NULL                            */
+    int32_t* iters;                  /* device [N][G]                                    */
+    int32_t* sweeps;                 /* device [N][G]                                    */
+    int32_t* n_diff_tuples;          /* device [N][G]                                    */
+    int32_t* n_diff_cells;           /* device [N][G]                                    */
+    double*  loss_all;               /* device [N][G]                                    */
+    double*  loss_tuples_mean;       /* device [N][G]                                    */
+    double*  loss_cells_mean;        /* device [N][G]                                    */
+    double*  loss_w;                 /* device [N][G], with pi                           */
+    double*  diff_w;                 /* device [N][G], with pi                           */
+    double*  v_w;                    /* device [N][G], with pi                           */
+    uint16_t* br_policy;             /* device [N][G][T + J] or NULL                     */
+    double*  v_opt;                  /* device [N][G][T + J] or NULL                     */
+    double*  v_pi;                   /* device [N][G][T + J] or NULL                     */
+} thrl_tuple_equilibrium_noise_args;
+int thrl_tuple_equilibrium_noise(const thrl_cfg* cfg, const thrl_tuple_equilibrium_noise_args* args, void* stream);
+
+/*
  * thrl_price_probs: the action PROBABILITIES of the neural agents at a free list of prices, where thrl_price_policy
  * gives their greedy action.  No reference counterpart.  For every agent i with kind[i] = 1 / 2 (Reinforce /
  * ActorCritic) the call writes prob[i] (device float32 [G][J][A_i], G = args.n_games in [1, cfg.n_games], J =

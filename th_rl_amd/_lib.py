@@ -326,6 +326,27 @@ class TupleStationaryArgs(ctypes.Structure):
     ]
 
 
+TEN_MAX_LDS = 160 * 1024
+
+
+class TupleEquilibriumNoiseArgs(ctypes.Structure):
+    """thrl_tuple_equilibrium_noise_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("n_cells", ctypes.c_int32), ("band_w", ctypes.c_int32),
+        ("max_sweeps", ctypes.c_int32), ("agents", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("kind", ctypes.c_int32 * MAXA), ("gamma", ctypes.c_double * MAXA),
+        ("noise_prob", ctypes.c_double), ("eval_tol", ctypes.c_double),
+        ("noise_prob_g", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p),
+        ("cell_policy", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("band_lo", ctypes.c_void_p),
+        ("band", ctypes.c_void_p), ("noise_reward", ctypes.c_void_p), ("pi", ctypes.c_void_p),
+        ("iters", ctypes.c_void_p), ("sweeps", ctypes.c_void_p), ("n_diff_tuples", ctypes.c_void_p),
+        ("n_diff_cells", ctypes.c_void_p),
+        ("loss_all", ctypes.c_void_p), ("loss_tuples_mean", ctypes.c_void_p), ("loss_cells_mean", ctypes.c_void_p),
+        ("loss_w", ctypes.c_void_p), ("diff_w", ctypes.c_void_p), ("v_w", ctypes.c_void_p),
+        ("br_policy", ctypes.c_void_p), ("v_opt", ctypes.c_void_p), ("v_pi", ctypes.c_void_p),
+    ]
+
+
 SP_START_TUPLE = 1
 SP_MAX_LDS = 160 * 1024
 
@@ -390,7 +411,7 @@ SYMBOLS = [
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
     "thrl_equilibrium_noise",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
-    "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary", "thrl_price_probs", "thrl_sampled_chain",
+    "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary", "thrl_tuple_equilibrium_noise", "thrl_price_probs", "thrl_sampled_chain",
     "thrl_sampled_noise_chain",
 ]
 CAC_PARAMS = 1283
@@ -521,6 +542,8 @@ def load():
     L.thrl_price_policy.argtypes = [cfgp, vp, ctypes.POINTER(PricePolicyArgs), vp]
     L.thrl_tuple_stationary.restype = ctypes.c_int
     L.thrl_tuple_stationary.argtypes = [cfgp, ctypes.POINTER(TupleStationaryArgs), vp]
+    L.thrl_tuple_equilibrium_noise.restype = ctypes.c_int
+    L.thrl_tuple_equilibrium_noise.argtypes = [cfgp, ctypes.POINTER(TupleEquilibriumNoiseArgs), vp]
     L.thrl_price_probs.restype = ctypes.c_int
     L.thrl_price_probs.argtypes = [cfgp, ctypes.POINTER(PriceProbsArgs), vp]
     L.thrl_sampled_chain.restype = ctypes.c_int

@@ -342,6 +342,32 @@ class AnalysisMethods:
         self._ready()
         return ta.equilibrium(self, agents=agents, start=start, policies=policies, tol=tol, tuple_policy=tuple_policy)
 
+    def greedy_equilibrium_noise(self, agents=None, noise_prob=None, resolution=1024, eval_tol=1e-12, max_sweeps=8192,
+                                 policies=False, tol=0.0, tuple_policy=None, cell_policy=None, weights="stationary",
+                                 n_games=None, tabs=None):
+        """The equilibrium check UNDER DEMAND NOISE for ANY mix of QTable, Reinforce and ActorCritic agents
+        (tuple_analysis.equilibrium_noise, thrl_tuple_equilibrium_noise; definitions in include/thrl.h): for each agent
+        in `agents` (default all) the exact best response to the others' strategies in the environment of
+        greedy_stationary(), on the S = T + J states "the price is exactly tuple t's" (the strategies of
+        tuple_play.extract()) and "the price lies in cell k" (the strategies sampled at the midpoints of `resolution`
+        uniform cells beside the QTable agents' breakpoints): Jacobi sweeps to eval_tol, at most max_sweeps per
+        evaluation, policy iteration with a margin that evaluation error cannot cross.  Returns a dict of numpy arrays:
+        iters (-1: not solved or capped), sweeps, n_diff_tuples, n_diff_cells, loss_all, loss_tuples_mean,
+        loss_cells_mean [N, G]; with weights loss_w, diff_w, v_w [N, G] and pi [G, T] (weights: "stationary" = each
+        game's long-run distribution over the tuple played, greedy_stationary(pi=True, start="reset") on the same tables
+        and strategies -- its last iterate also where that iteration stopped at its step limit; None; or [G, T] values),
+        from which the kernel derives where decisions are made in the long run; the host-side flags br_all, br_w [N, G]
+        and perfect [G] for the tolerance `tol`; noise_prob [G], n_cells, T, n_states, agents.  policies=True adds
+        br_policy (uint16), v_opt, v_pi [N, G, T + J], tuple-states first.  noise_prob, tuple_policy, cell_policy, n_games
+        and tabs as in greedy_stationary(); the per-game sweep gamma is each game's discount factor, else the agent's
+        own gamma.  A batch with a CAC agent or more than 4096 action tuples or cells raises ValueError; a working set
+        above a CU's LDS is THRL_ERR_UNSUPPORTED."""
+        from . import tuple_analysis as ta
+        self._ready()
+        return ta.equilibrium_noise(self, agents=agents, noise_prob=noise_prob, resolution=resolution, eval_tol=eval_tol,
+                                    max_sweeps=max_sweeps, policies=policies, tol=tol, tuple_policy=tuple_policy,
+                                    cell_policy=cell_policy, weights=weights, n_games=n_games, tabs=tabs)
+
     def greedy_attractors(self, start=None, weights="uniform", policies=False, tuple_policy=None):
         """The attractor analysis for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.attractors,
         thrl_tuple_attractors): attractors' outputs with the game's T action tuples as the state set

@@ -19,6 +19,7 @@
 #include "thrl_host.h"
 #include "thrl_tuple_analysis.h"
 #include "thrl_tuple_attractors.h"
+#include "thrl_tuple_equilibrium_noise.h"
 #include "thrl_tuple_play.h"
 #include "thrl_sampled.h"
 #include "thrl_sampled_noise.h"
@@ -116,12 +117,13 @@ int check_agents_mask(int agents, int N) {
     const bool ok = agents != 0 && !(agents & ~((1 << N) - 1));
     return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "agents=0x%x: a non-empty mask of agents in [0,%d)", agents, N);
 }
-int check_gamma(const thrl_cfg* c, int agents) {                // the config's gammas of the solved agents (no sweep_gamma)
-    for (int i = 0; i < c->n_agents; i++)
-        if (((agents >> i) & 1) && !(c->gamma[i] >= 0.0 && c->gamma[i] < 1.0))
-            return fail(THRL_ERR_BAD_CONFIG, "agent %d: gamma=%g: the equilibrium check needs gamma in [0, 1)", i, c->gamma[i]);
+int check_gamma(const double* gamma, int N, int agents) {       // the host's gammas of the solved agents (no sweep_gamma)
+    for (int i = 0; i < N; i++)
+        if (((agents >> i) & 1) && !(gamma[i] >= 0.0 && gamma[i] < 1.0))
+            return fail(THRL_ERR_BAD_CONFIG, "agent %d: gamma=%g: the equilibrium check needs gamma in [0, 1)", i, gamma[i]);
     return THRL_OK;
 }
+int check_gamma(const thrl_cfg* c, int agents) { return check_gamma(c->gamma, c->n_agents, agents); }   // the config's
 
 // ---- planning that several entry points share
 // tstride[i] = prod_{j > i} n_actions[j] (agent 0 slowest); n_actions may be NULL where the Args carry AgentParams
@@ -646,6 +648,55 @@ int thrl_tuple_stationary(const thrl_cfg* c, const thrl_tuple_stationary_args* x
     const int grid = grid_for(cus, lds_cu, a.lds_bytes, kTsMaxBlocksPerCu, a.G);
     const int e = thrl::launch_tuple_stationary(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_ts_switch / k_ts_chain launch") : THRL_OK;
+}
+
+int thrl_tuple_equilibrium_noise(const thrl_cfg* c, const thrl_tuple_equilibrium_noise_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_tuple_stationary's checks in its order, with the agents and their gammas as thrl_equilibrium_noise checks them;
+    // every host-visible argument is checked before the device is touched
+    if ((rc = check_games(x->n_games)) != THRL_OK) return rc;
+    if (x->flags != 0) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (!x->sweep_gamma && (rc = check_gamma(x->gamma, N, x->agents)) != THRL_OK) return rc;
+    if ((rc = check_cells_band(x->n_cells, x->band_w)) != THRL_OK) return rc;
+    if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
+    if ((rc = check_noise_prob(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
+    if ((rc = check_cell_limit("thrl_tuple_equilibrium_noise", x->n_cells)) != THRL_OK) return rc;
+    TenArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples; a.J = x->n_cells; a.W = x->band_w;
+    const int64_t need = thrl::ten_layout(a);            // the working set of include/thrl.h
+    if (need > THRL_TEN_MAX_LDS) return lds_refusal("thrl_tuple_equilibrium_noise", need, N, x->n_cells);
+    if (!x->tuple_policy || !x->cell_policy || !x->reward || !x->band_lo || !x->band || !x->noise_reward)
+        return missing("tuple_policy / cell_policy / reward / band_lo / band / noise_reward");
+    if (!x->iters || !x->sweeps || !x->n_diff_tuples || !x->n_diff_cells || !x->loss_all || !x->loss_tuples_mean
+        || !x->loss_cells_mean)
+        return missing("iters / sweeps / n_diff_tuples / n_diff_cells / loss_all / loss_tuples_mean / loss_cells_mean");
+    if (x->pi && (!x->loss_w || !x->diff_w || !x->v_w)) return missing("with pi, loss_w / diff_w / v_w");
+
+    a.agents = x->agents; a.max_sweeps = x->max_sweeps;
+    a.noise_prob = x->noise_prob; a.eval_tol = x->eval_tol;
+    tuple_strides(c, a.n_actions, a.tstride);
+    for (int i = 0; i < N; i++) a.gamma[i] = x->gamma[i];
+    a.noise_prob_g = x->noise_prob_g; a.sweep_gamma = x->sweep_gamma;
+    a.tuple_policy = x->tuple_policy; a.cell_policy = x->cell_policy; a.reward = x->reward;
+    a.band_lo = x->band_lo; a.band = x->band; a.noise_reward = x->noise_reward; a.pi = x->pi;
+    a.iters = x->iters; a.sweeps = x->sweeps; a.n_diff_tuples = x->n_diff_tuples; a.n_diff_cells = x->n_diff_cells;
+    a.loss_all = x->loss_all; a.loss_tuples_mean = x->loss_tuples_mean; a.loss_cells_mean = x->loss_cells_mean;
+    a.loss_w = x->loss_w; a.diff_w = x->diff_w; a.v_w = x->v_w;
+    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+    int cus = 0, lds_cu = 0;
+    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
+    if (lds_cu > 0 && a.lds_bytes > lds_cu) return lds_refusal("thrl_tuple_equilibrium_noise", need, N, x->n_cells);
+    const int grid = grid_for(cus, lds_cu, a.lds_bytes, kTenMaxBlocksPerCu, a.G);
+    const int e = thrl::launch_tuple_equilibrium_noise(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_tuple_equilibrium_noise launch") : THRL_OK;
 }
 
 int thrl_price_probs(const thrl_cfg* c, const thrl_price_probs_args* x, void* stream) {

@@ -19,6 +19,14 @@ start_mass_other, start_reward in place of the reset_* fields: the environment's
 [0, a), would need a network's action at a continuum of prices, so its place is taken by a weight per start tuple,
 by default 1 / T: a start drawn uniformly over action profiles, NOT the environment's reset.  The stationary analysis
 in tuple form is tuple_stationary.py.
+
+Under demand noise (thrl_tuple_equilibrium_noise; the option "noise" of training.greedy_equilibrium) the equilibrium
+check is asked in the environment of tuple_stationary.py, on the S = T + J states "the price is exactly tuple t's" and
+"the price lies in cell k": equilibrium_noise() gives iters, sweeps, n_diff_tuples, n_diff_cells, loss_all,
+loss_tuples_mean, loss_cells_mean [N, G] and, weighted by where decisions are made in the long run (from
+tuple_stationary.run's pi, or a pi of the caller's), loss_w, diff_w, v_w [N, G], with equilibrium.flags_noise's br_all,
+br_w and perfect.  The noise-free artefacts are what they were; the noisy ones are geqn_*.npy and
+greedy_equilibrium_noise.json.
 """
 import ctypes
 import os
@@ -35,6 +43,10 @@ from ._lib import ThrlError
 
 DEV_DEFAULTS = dict(dv.DEFAULTS)
 EQ_DEFAULTS = dict(eq.DEFAULTS)
+NOISE_DEFAULTS = dict(eq.NOISE_DEFAULTS, resolution=1024)
+NOISE_INT = ("iters", "sweeps", "n_diff_tuples", "n_diff_cells")
+NOISE_FLOAT = ("loss_all", "loss_tuples_mean", "loss_cells_mean")
+NOISE_WEIGHTED = eq.NOISE_WEIGHTED
 ATTR_DEFAULTS = dict(policies=False, weights="uniform")
 KEEP = at.KEEP
 START_FIELDS = ("start_mass", "start_mass_other", "start_reward")
@@ -96,6 +108,11 @@ def parse_equilibrium_options(opt, config):
     name = "training.greedy_equilibrium"
     ps, _ = tp.check_config(config)
     n = len(ps)
+    noise = None
+    if isinstance(opt, dict) and "noise" in opt:
+        opt = dict(opt)
+        noise = opt.pop("noise")
+        noise = None if noise is None or noise is False else parse_equilibrium_noise(noise, config)
     out = an.options("greedy_equilibrium", opt, dict(EQ_DEFAULTS, agents=list(range(n))))
     out["agents"] = sorted(set(_agents(name, out["agents"], n)))
     if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float, np.integer, np.floating)) \
@@ -116,6 +133,28 @@ def parse_equilibrium_options(opt, config):
                 eq.check_gamma([gammas[d]], "agents[%d].gamma" % d)
         except ValueError as e:
             raise ValueError(str(e).replace("training.equilibrium", name))
+    if noise is not None:
+        out["noise"] = noise
+    return out
+
+
+def parse_equilibrium_noise(noise, config):
+    """training.greedy_equilibrium.noise (true or a dict) -> the dict with every key filled in: equilibrium.parse_noise's
+    noise_prob (None = the run's own noise, refused for a noise-free run), eval_tol and max_sweeps, and resolution
+    (tuple_stationary's uniform cuts of the price axis; more than its MAX_CELLS cells is refused before training)."""
+    from . import tuple_stationary as ts
+    name = "training.greedy_equilibrium.noise"
+    out = an.options("greedy_equilibrium.noise", noise, NOISE_DEFAULTS)
+    resolution = out.pop("resolution")
+    try:
+        out = eq.parse_noise(out, config)
+    except ValueError as e:
+        raise ValueError(str(e).replace("training.equilibrium.noise", name))
+    out["resolution"] = ts._check_resolution(resolution, name + ".resolution")
+    try:
+        ts.cuts(config, out["resolution"])
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e))
     return out
 
 
@@ -342,7 +381,153 @@ def attractors(batch, start=None, weights="uniform", policies=False, tuple_polic
     return res
 
 
+def equilibrium_noise(batch, agents=None, noise_prob=None, resolution=NOISE_DEFAULTS["resolution"], eval_tol=1e-12,
+                      max_sweeps=8192, policies=False, tol=0.0, tuple_policy=None, cell_policy=None, weights="stationary",
+                      n_games=None, tabs=None):
+    """thrl_tuple_equilibrium_noise for the first n_games (default all) games of `batch` (see
+    AnalysisMethods.greedy_equilibrium_noise).  tabs: tuple_stationary.tables(batch.config, resolution).  tuple_policy /
+    cell_policy: the strategies of tuple_play.extract() / tuple_stationary.extract_cells() (default: extracted here, once,
+    for this call and for the stationary one).  weights="stationary": tuple_stationary.run(pi=True, start="reset", tol
+    1e-12, at most 8192 steps) on the same tables and strategies gives pi [G, T]; a game whose iteration stopped at its
+    step limit is weighted by its last iterate all the same, and a game that iteration did not solve by zeros.  Returns
+    a dict of numpy arrays."""
+    import torch
+    from . import stationary as sn
+    from . import tuple_stationary as ts
+    N = batch.N
+    G = batch.G if n_games is None else int(n_games)
+    if not 1 <= G <= batch.G:
+        raise ThrlError("greedy_equilibrium_noise: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    ag, mask = eq.agents_mask(agents, N)
+    if tabs is None:
+        tabs = ts.tables(batch.config, resolution)
+    tp._batch_tables(batch, tabs)
+    dev = batch.device
+    J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
+    S = T + J
+    shapes = dict(reward=(N, T), band_lo=(T,), band=(T, W), noise_reward=(N, T))
+    if tuple_policy is None:
+        tuple_policy = tp.extract(batch, tabs)
+    if not an.is_policy(tuple_policy, (batch.G, N, T), batch.state.device):
+        an.check_policy(batch, tuple_policy, (G, N, T), "greedy_equilibrium_noise", "tuple_policy")
+    if cell_policy is None:
+        cell_policy = ts.extract_cells(batch, tabs, n_games=G)
+    an.check_policy(batch, cell_policy, (G, N, J), "greedy_equilibrium_noise", "cell_policy")
+    a = _lib.TupleEquilibriumNoiseArgs()
+    a.n_games, a.n_tuples, a.n_cells, a.band_w, a.agents = G, T, J, W, mask
+    a.max_sweeps, a.eval_tol = int(max_sweeps), float(eval_tol)
+    nn = getattr(batch, "nn", None) or {}
+    for i, k in enumerate(tp._kinds(batch)):
+        a.kind[i] = tp.KINDS[k]
+        a.gamma[i] = float(nn[i].gamma) if i in nn else float(batch.cfg.gamma[i])
+    with torch.cuda.device(dev):
+        p, p_g = sn.resolve_noise(batch, noise_prob, G)
+        pi = None
+        if isinstance(weights, str):
+            if weights != "stationary":
+                raise ThrlError("greedy_equilibrium_noise: weights must be 'stationary', None or a [G, T] array, got %r"
+                                % (weights,))
+            st = ts.run(batch, noise_prob=noise_prob, start="reset", pi=True, tuple_policy=tuple_policy,
+                        cell_policy=cell_policy, n_games=G, tabs=tabs)
+            pi = torch.from_numpy(np.ascontiguousarray(st["pi"])).to(dev)
+        elif weights is not None:
+            if isinstance(weights, torch.Tensor):
+                pi = weights.to(device=dev, dtype=torch.float64).contiguous()
+            else:
+                pi = torch.from_numpy(np.ascontiguousarray(np.asarray(weights, np.float64))).to(dev)
+            if tuple(pi.shape) != (G, T):
+                raise ThrlError("greedy_equilibrium_noise: weights must be shaped %s, got %s" % ((G, T), tuple(pi.shape)))
+        keep = {}
+        for f, shape in shapes.items():
+            x = np.ascontiguousarray(tabs[f], np.int32 if f == "band_lo" else np.float64)
+            if x.shape != shape:
+                raise ThrlError("greedy_equilibrium_noise: table %s has shape %s, expected %s" % (f, x.shape, shape))
+            keep[f] = torch.from_numpy(x).to(dev)
+            setattr(a, f, keep[f].data_ptr())
+        if p_g is not None:
+            a.noise_prob_g = p_g.data_ptr()
+        else:
+            a.noise_prob = p
+        gam = batch.sweep.get("gamma") if getattr(batch, "sweep", None) else None
+        if gam is not None:
+            gam = gam[:, :G].contiguous()
+            a.sweep_gamma = gam.data_ptr()
+        a.tuple_policy, a.cell_policy = tuple_policy.data_ptr(), cell_policy.data_ptr()
+        out = {f: torch.zeros((N, G), dtype=torch.int32, device=dev) for f in NOISE_INT}
+        out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in NOISE_FLOAT})
+        if pi is not None:
+            a.pi = pi.data_ptr()
+            out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in NOISE_WEIGHTED})
+        if policies:
+            out["br_policy"] = torch.zeros((N, G, S), dtype=torch.int16, device=dev)
+            out["v_opt"] = torch.zeros((N, G, S), dtype=torch.float64, device=dev)
+            out["v_pi"] = torch.zeros((N, G, S), dtype=torch.float64, device=dev)
+        for f, t in out.items():
+            setattr(a, f, t.data_ptr())
+        _lib.check(batch.L.thrl_tuple_equilibrium_noise(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                   "thrl_tuple_equilibrium_noise")
+        torch.cuda.synchronize(dev)
+        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res["noise_prob"] = np.full(G, p, np.float64) if p_g is None else p_g.cpu().numpy()
+        if pi is not None:
+            res["pi"] = pi.cpu().numpy()
+    if policies:
+        res["br_policy"] = res["br_policy"].view(np.uint16)
+    res["agents"], res["n_cells"], res["T"], res["n_states"], res["tol"] = ag, J, T, S, float(tol)
+    res["eval_tol"], res["max_sweeps"] = float(eval_tol), int(max_sweeps)
+    res["resolution"] = int(tabs.get("resolution", resolution))
+    res.update(eq.flags_noise(res, ag, tol))
+    return res
+
+
 # ---------------------------------------------------------------------------------------------- host side
+def summarize_equilibrium_noise(games, ids, n_groups, agents, tol=0.0):
+    """equilibrium.summarize_noise's rows (per (group, agent): games, capped, br_all, br_w, the quantiles of loss_all and
+    loss_w over the games where they are positive, diff_w_mean, sweeps_max; per group: perfect) with, per agent,
+    diff_tuples_mean and diff_cells_mean (the mean counts of differing tuple-states and cell-states over the solved
+    games) added."""
+    rows = eq.summarize_noise(games, ids, n_groups, agents, tol)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    iters = np.asarray(games["iters"])
+    for r in rows:
+        if r["agent"] is not None:
+            ok = (ids == r["group"]) & (iters[r["agent"]] >= 0)
+            r["diff_tuples_mean"] = an.mean(np.asarray(games["n_diff_tuples"])[r["agent"]][ok])
+            r["diff_cells_mean"] = an.mean(np.asarray(games["n_diff_cells"])[r["agent"]][ok])
+    return rows
+
+
+def save_equilibrium_noise_games(d, r):
+    """geqn_iters int32 [4, N, G] (iters, sweeps, n_diff_tuples, n_diff_cells), geqn_loss float64 [3, N, G] (loss_all,
+    loss_tuples_mean, loss_cells_mean), geqn_prob float64 [G] (the noise probabilities analysed); with weights
+    geqn_weighted float64 [3, N, G] (loss_w, diff_w, v_w); with per-state arrays geqn_policy uint16, geqn_v_opt and
+    geqn_v_pi float64 [N, G, T + J], tuple-states first."""
+    np.save(os.path.join(d, "geqn_iters.npy"), np.stack([r[f] for f in NOISE_INT]).astype(np.int32))
+    np.save(os.path.join(d, "geqn_loss.npy"), np.stack([r[f] for f in NOISE_FLOAT]).astype(np.float64))
+    np.save(os.path.join(d, "geqn_prob.npy"), np.asarray(r["noise_prob"], np.float64))
+    if "loss_w" in r:
+        np.save(os.path.join(d, "geqn_weighted.npy"), np.stack([r[f] for f in NOISE_WEIGHTED]).astype(np.float64))
+    if "br_policy" in r:
+        np.save(os.path.join(d, "geqn_policy.npy"), np.asarray(r["br_policy"], np.uint16))
+        np.save(os.path.join(d, "geqn_v_opt.npy"), np.asarray(r["v_opt"], np.float64))
+        np.save(os.path.join(d, "geqn_v_pi.npy"), np.asarray(r["v_pi"], np.float64))
+
+
+def load_equilibrium_noise_games(d):
+    """The per-game arrays of the check under noise a run directory holds (training.greedy_equilibrium.noise)."""
+    it, loss = np.load(os.path.join(d, "geqn_iters.npy")), np.load(os.path.join(d, "geqn_loss.npy"))
+    g = {f: it[k] for k, f in enumerate(NOISE_INT)}
+    g.update({f: loss[k] for k, f in enumerate(NOISE_FLOAT)})
+    g["noise_prob"] = np.load(os.path.join(d, "geqn_prob.npy"))
+    if os.path.isfile(os.path.join(d, "geqn_weighted.npy")):
+        w = np.load(os.path.join(d, "geqn_weighted.npy"))
+        g.update({f: w[k] for k, f in enumerate(NOISE_WEIGHTED)})
+    if os.path.isfile(os.path.join(d, "geqn_policy.npy")):
+        g.update(br_policy=np.load(os.path.join(d, "geqn_policy.npy")), v_opt=np.load(os.path.join(d, "geqn_v_opt.npy")),
+                 v_pi=np.load(os.path.join(d, "geqn_v_pi.npy")))
+    return g
+
+
 def _no_start(rows, start, ids):
     ids = np.asarray(ids, np.int64).reshape(-1)
     start = np.asarray(start).reshape(-1)
@@ -520,4 +705,16 @@ def write_equilibrium(exp_path, batch, config, opt, ids, n_groups, tuple_policy=
     delta = np.where(r["lam"] > 0, dv.profit_gain(cycle_reward, nash, cartel), -np.inf)      # no path: not collusive
     summary = summarize_equilibrium(r, ids, n_groups, opt["agents"], opt["tol"], delta)
     an.save_json(os.path.join(exp_path, "greedy_equilibrium.json"), eq.describe(opt, r["n_states"], summary))
+    if opt.get("noise"):        # the check under demand noise after it; what is above is what it is without the option
+        from . import tuple_stationary as ts
+        nz = opt["noise"]
+        rn = equilibrium_noise(batch, agents=opt["agents"], noise_prob=nz["noise_prob"], eval_tol=nz["eval_tol"],
+                               max_sweeps=nz["max_sweeps"], policies=opt["policies"], tol=opt["tol"],
+                               tuple_policy=tuple_policy, tabs=ts.tables(config, nz["resolution"]))
+        save_equilibrium_noise_games(exp_path, rn)
+        rows = summarize_equilibrium_noise(rn, ids, n_groups, opt["agents"], opt["tol"])
+        an.save_json(os.path.join(exp_path, "greedy_equilibrium_noise.json"),
+                     {"options": opt, "n_cells": int(rn["n_cells"]), "T": int(rn["T"]), "quantiles": list(an.QUANTILES),
+                      "summary": [x for x in rows if x["agent"] is not None],
+                      "perfect": [x for x in rows if x["agent"] is None]})
     return r

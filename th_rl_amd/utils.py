@@ -554,6 +554,46 @@ def greedy_equilibrium_games(exp_path, agent=0):
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
 
 
+def greedy_equilibrium_noise_summary(exp_path):
+    """A run's equilibrium check under demand noise in tuple form (training.greedy_equilibrium with "noise"):
+    greedy_equilibrium_noise.json as a DataFrame.  Rows with an agent: games, capped, br_all, br_w (fractions of games in
+    which the agent's strategy is a best response in every state / where noisy play makes its decisions in the long
+    run), loss_all_q* / loss_w_q* (over the games with a positive loss), diff_w_mean, sweeps_max, diff_tuples_mean,
+    diff_cells_mean.  Rows with agent NaN: the group's perfect fraction."""
+    if not os.path.isfile(os.path.join(exp_path, "greedy_equilibrium_noise.json")):
+        raise KeyError("no equilibrium check under noise in tuple form (greedy_equilibrium_noise.json) under %s "
+                       "(training.greedy_equilibrium.noise)" % exp_path)
+    desc = _load_json(exp_path, "greedy_equilibrium_noise.json")
+    df = pandas.DataFrame(desc["summary"] + desc["perfect"])
+    df["n_cells"], df["T"] = int(desc["n_cells"]), int(desc["T"])
+    df["tol"] = float(desc["options"]["tol"])
+    return df
+
+
+def greedy_equilibrium_noise_games(exp_path, agent=0):
+    """Per-game results of the equilibrium check under demand noise in tuple form for `agent`, one row per game indexed
+    by its GLOBAL id: noise_prob, iters, sweeps, n_diff_tuples, n_diff_cells, loss_all, loss_tuples_mean,
+    loss_cells_mean, loss_w, diff_w, v_w, and the flags br_all, br_w (this agent) and perfect (all solved agents) at the
+    run's tol."""
+    from th_rl_amd import equilibrium as eq, tuple_analysis as ta
+    _run_dirs(exp_path, "geqn_iters.npy", "equilibrium check under noise in tuple form", "greedy_equilibrium.noise",
+              shards=False)
+    opt = _load_json(exp_path, "greedy_equilibrium_noise.json")["options"]
+    off = _game_offset(exp_path, exp_path)
+    g = ta.load_equilibrium_noise_games(exp_path)
+    fl = eq.flags_noise(g, opt["agents"], opt["tol"])
+    cols = {"noise_prob": g["noise_prob"]}
+    for f in ta.NOISE_INT + ta.NOISE_FLOAT + ta.NOISE_WEIGHTED:
+        if f in g:
+            cols[f] = g[f][int(agent)]
+    cols["br_all"] = fl["br_all"][int(agent)]
+    if "br_w" in fl:
+        cols["br_w"] = fl["br_w"][int(agent)]
+    cols["perfect"] = fl["perfect"]
+    n = g["noise_prob"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
 def greedy_attractor_summary(exp_path):
     """A run's attractor analysis in tuple form (training.greedy_attractors, any mix of QTable / Reinforce / ActorCritic
     agents): greedy_attractors.json's summary as a DataFrame with attractor_summary's columns, delta_start_mean (the
