@@ -461,6 +461,46 @@ typedef struct {
 int thrl_group_stats(const thrl_group_stats_args* args, void* stream);
 
 /*
+ * Exponentially weighted mean of per-game episode rows, carried across calls: the smoothing the reference applies to
+ * each run's learning curve before it takes statistics over runs (utils.py:20-21 load_experiment, and
+ * plot_learning_curve_conf / plot_learning_curve_sweep: log[...].ewm(halflife=1000).mean(), pandas' adjust=True
+ * form).  The smoothed rows keep the episode-row layout, so thrl_group_stats reduces them as they are; its "total" is
+ * then the sum of the smoothed rewards in agent order, the reference's .ewm().mean().sum(axis=1).
+ *
+ * Definition, float64, every operation rounded once (no fma).  The caller computes alpha = 1 - exp(log(0.5) / halflife)
+ * and decay = 1 - alpha in double, in that order.  For row t = 0, 1, ... since the state was fresh, each of the 2N
+ * state rows j (reward_0..reward_{N-1}, action_0..action_{N-1}) and each game g:
+ *   num_t = x_t + decay * num_{t-1}    (num_{-1} = 0; the product is rounded, then the sum)
+ *   den_t = 1   + decay * den_{t-1}    (den_{-1} = 0; the same for every game, so it is a host double)
+ *   y_t   = num_t / den_t
+ * The loop over the rows is sequential in every thread, so the result is bit-identical however the rows are cut into
+ * calls: pass state_out and *den_out of one call as state_in and den of the next.  A non-finite x makes that game's
+ * num non-finite from then on (pandas skips a NaN; this does not); thrl_group_stats counts such values in its
+ * overflow bin.
+ *
+ * One thread per (state row, game), lanes consecutive in g; the cost is one read and one write of the rows.
+ * n_episodes = 0 is accepted after the checks and does nothing: no array is read or written and *den_out = den.
+ * Each output may be exactly its input (in place); any other overlap between an output and an input or another
+ * output is refused, as is a state_out that overlaps state_in without being equal to it.
+ */
+typedef struct {
+    int32_t n_games;                 /* G: columns of the rows, >= 1                     */
+    int32_t n_agents;                /* N in 1..THRL_MAXA                                */
+    int32_t n_episodes;              /* E: rows of this call, >= 0                       */
+    int32_t reserved;                /* 0                                                */
+    double decay;                    /* in (0, 1)                                        */
+    double den;                      /* denominator before the first row: finite, >= 0; 0 = fresh */
+    const double* reward_rows;       /* device [E][N][G]                                 */
+    const double* action_rows;       /* device [E][N][G]                                 */
+    double* reward_out;              /* device [E][N][G]; may be reward_rows             */
+    double* action_out;              /* device [E][N][G]; may be action_rows             */
+    const double* state_in;          /* device [2N][G]: num before the first row; NULL = zeros */
+    double* state_out;               /* device [2N][G]: num after the last row; may be state_in */
+    double* den_out;                 /* HOST, optional: denominator after the last row   */
+} thrl_ewm_rows_args;
+int thrl_ewm_rows(const thrl_ewm_rows_args* args, void* stream);
+
+/*
  * Deviation analysis of the greedy policies (the test of Calvano, Calzolari, Denicolo, Pastorello, "Artificial
  * Intelligence, Algorithmic Pricing, and Collusion", AER 2020).  No reference counterpart: it extends
  * utils.play_game (utils.py:27-47).  QTable agents only; q, and everything else of the batch, is left untouched.

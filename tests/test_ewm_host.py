@@ -1,0 +1,233 @@
+"""Host side of the smoothed learning curves (training.group_stats.smooth, thrl_ewm_rows): the numpy restatement
+against pandas' ewm on the reference's own curves, its invariance to the cut of the rows, option parsing, the struct
+layout, every refusal of the entry point (through the library loaded without a GPU) and the trainer / launch
+plumbing that needs no device.  No GPU."""
+import ctypes
+import json
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from th_rl_amd import group_stats as gs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "g13_ewm_curves.npz")
+AG = dict(name="QTable", gamma=0.95, actions=21, states=100, action_range=[0.2, 0.4])
+ENV = dict(name="NoisyPriceState", noise_prob=0, a=10, b=1, nplayers=2, max_steps=100)
+CFG = {"agents": [dict(AG), dict(AG)], "environment": dict(ENV)}
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from th_rl_amd import build, _lib
+    build.build()          # hipcc cross-compiles gfx950 without a GPU
+    return _lib.load()
+
+
+def _rel(got, want):
+    """Largest relative error; where the reference is exactly 0 the value has to be 0 too (the reference reads the
+    second header line of log.csv as its first data row, 0 and 1: that row is part of the fixture)."""
+    diff, mag = np.abs(got - want), np.abs(want)
+    return float(np.max(np.where(mag > 0, diff / np.where(mag > 0, mag, 1.0), np.where(diff == 0, 0.0, np.inf))))
+
+
+# ------------------------------------------------------------------------------------------------ the definition
+def test_ewm_host_matches_the_reference_curves(golden):
+    """load_experiment's frames of the committed reference run: 201 rows, halflife 1000.  Three roundings per row
+    on a decaying sum: the error stays below E * 2^-52 = 5.7e-14 for E <= 256, so 1e-13."""
+    rew = golden["log_rewards"][:, :, None]                     # [E, N, G = 1]
+    act = golden["log_actions"][:, :, None]
+    assert rew.shape == (201, 2, 1) and float(golden["halflife"]) == 1000.0
+    s_r, s_a, state, den = gs.ewm_host(rew, act, 1000.0)
+    err = max(_rel(s_r[:, :, 0], golden["rewards"]), _rel(s_a[:, :, 0], golden["actions"]))
+    print("ewm_host vs load_experiment, h=1000, 201 rows: max rel err %.3g" % err)
+    assert err <= 1e-13
+    assert state.shape == (4, 1) and den > 0.0
+
+
+@pytest.mark.parametrize("h", [1, 3, 8])
+def test_ewm_host_matches_pandas_short_halflives(golden, h):
+    x = golden["x"]                                             # [64, 4]: two "agents", two "games"
+    rew, act = x[:, :2, None], x[:, 2:, None]
+    s_r, s_a, _, _ = gs.ewm_host(rew, act, float(h))
+    got = np.concatenate([s_r[:, :, 0], s_a[:, :, 0]], axis=1)
+    err = _rel(got, golden["ewm_h%d" % h])
+    print("ewm_host vs pandas, h=%d, 64 rows: max rel err %.3g" % (h, err))
+    assert err <= 1e-13
+
+
+def test_ewm_host_cut_is_bit_identical():
+    rs = np.random.RandomState(5)
+    rew, act = rs.uniform(0, 25, (12, 2, 7)), rs.uniform(0.2, 0.4, (12, 2, 7))
+    full = gs.ewm_host(rew, act, 3.0)
+    a = gs.ewm_host(rew[:5], act[:5], 3.0)
+    b = gs.ewm_host(rew[5:], act[5:], 3.0, state=a[2], den=a[3])
+    assert np.array_equal(np.concatenate([a[0], b[0]]), full[0])
+    assert np.array_equal(np.concatenate([a[1], b[1]]), full[1])
+    assert np.array_equal(b[2], full[2]) and b[3] == full[3]
+    # the first row is the input itself, and a non-finite value stays (pandas would skip it)
+    assert np.array_equal(full[0][0], rew[0])
+    rew[3, 0, 2] = np.nan
+    bad = gs.ewm_host(rew, act, 3.0)[0]
+    assert np.isnan(bad[3:, 0, 2]).all() and np.isfinite(bad[:3, 0, 2]).all() and np.isfinite(bad[:, 1, :]).all()
+
+
+def test_decay_definition():
+    import math
+    alpha, d = gs.ewm_decay(1000.0)
+    assert alpha == 1.0 - math.exp(math.log(0.5) / 1000.0) and d == 1.0 - alpha
+    assert abs(d ** 1000 - 0.5) < 1e-12
+
+
+# ------------------------------------------------------------------------------------------------ options
+def test_smooth_option_parsing():
+    assert gs.parse_options({"smooth": 1000})["smooth"] == {"halflife": 1000.0}
+    assert gs.parse_options({"smooth": 2.5})["smooth"] == {"halflife": 2.5}
+    assert gs.parse_options({"smooth": {"halflife": 8}})["smooth"] == {"halflife": 8.0}
+    again = gs.parse_options(gs.parse_options({"smooth": 8, "bins": 16}))      # a parsed dict parses to itself
+    assert again["smooth"] == {"halflife": 8.0} and again["bins"] == 16
+    for bad in (0, -1, float("nan"), float("inf"), "1000", True, [3], {"halflife": 0}, {"half": 3}, {}):
+        with pytest.raises(ValueError):
+            gs.parse_options({"smooth": bad})
+    with pytest.raises(ValueError, match="unknown keys"):
+        gs.parse_options({"smoothing": 3})
+
+
+def test_off_is_unchanged():
+    """Without the option nothing the run writes changes: the parsed dict and groups.json's content have no new key."""
+    want = dict(bins=256, quantiles=[0.25, 0.5, 0.75], histograms=False, greedy_iters=0, ranges={}, n_max=None)
+    assert gs.parse_options(True) == want
+    assert gs.parse_options({"smooth": None}) == want
+    spec = gs.GroupSpec.from_config(CFG, 6, True)
+    assert spec.smooth is None
+    assert sorted(spec.describe()) == ["bins", "groups", "n_max", "quantiles", "quantities", "ranges", "scales"]
+    on = gs.GroupSpec.from_config(CFG, 6, {"smooth": 1000})
+    d = on.describe()
+    assert d["smooth"] == {"halflife": 1000.0, "decay": gs.ewm_decay(1000.0)[1]}
+    d.pop("smooth")
+    assert d == spec.describe()
+
+
+# ------------------------------------------------------------------------------------------------ the ABI
+FIELDS = ("n_games", "n_agents", "n_episodes", "reserved", "decay", "den", "reward_rows", "action_rows", "reward_out",
+          "action_out", "state_in", "state_out", "den_out")
+
+
+def test_args_struct_matches_header():
+    from th_rl_amd import _lib
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "thrl.h"\nint main(){printf("%zu %d"'
+           + "".join(' " %zu"' for _ in FIELDS) + ',sizeof(thrl_ewm_rows_args),THRL_ABI_VERSION'
+           + "".join(",offsetof(thrl_ewm_rows_args,%s)" % f for f in FIELDS) + ');return 0;}\n')
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "s.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
+        got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
+    assert got == [ctypes.sizeof(_lib.EwmRowsArgs), 3] + [getattr(_lib.EwmRowsArgs, f).offset for f in FIELDS]
+    assert [f for f, _ in _lib.EwmRowsArgs._fields_] == list(FIELDS)
+    assert "thrl_ewm_rows" in _lib.SYMBOLS and _lib.ABI_VERSION == 3
+
+
+def _args(**kw):
+    """A call that would pass every check but the last NULL check: the pointers are made-up addresses that nothing
+    dereferences, and state_out stays NULL, so no case here can reach a launch."""
+    from th_rl_amd import _lib
+    a = _lib.EwmRowsArgs()
+    a.n_games, a.n_agents, a.n_episodes, a.reserved = 8, 2, 4, 0
+    a.decay, a.den = 0.5, 0.0
+    rows = 4 * 2 * 8 * 8                                        # bytes of one [E][N][G] array
+    a.reward_rows, a.action_rows = 0x100000, 0x100000 + rows
+    a.reward_out, a.action_out = 0x100000, 0x100000 + rows      # in place
+    a.state_in, a.state_out = None, None
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_entry_point_refusals(lib):
+    call = lambda a: lib.thrl_ewm_rows(ctypes.byref(a), None)
+    err = lambda: lib.thrl_last_error().decode()
+    assert lib.thrl_ewm_rows(None, None) == -2 and "args" in err()
+    # the baseline reaches the last NULL check, and only that
+    assert call(_args()) == -2 and "state_out" in err()
+    for k in ("reward_rows", "action_rows", "reward_out", "action_out"):
+        assert call(_args(**{k: None})) == -2 and k in err(), k
+    assert call(_args(n_games=0)) == -1 and "n_games=0" in err()
+    assert call(_args(n_agents=0)) == -1 and "n_agents=0" in err()
+    assert call(_args(n_agents=9)) == -1 and "n_agents=9" in err()
+    assert call(_args(n_episodes=-1)) == -1 and "n_episodes=-1" in err()
+    assert call(_args(reserved=1)) == -1 and "reserved" in err()
+    for d in (0.0, 1.0, float("nan"), -0.5, 1.5):
+        assert call(_args(decay=d)) == -1 and "decay" in err(), d
+    for d in (-1.0, float("nan"), float("inf")):
+        assert call(_args(den=d)) == -1 and "den" in err(), d
+    # outputs that overlap their inputs without being them, each other, or the other's input
+    assert call(_args(reward_out=0x100000 + 8)) == -1 and "overlap" in err()
+    assert call(_args(action_out=0x100000 + 4 * 2 * 8 * 8 - 8)) == -1 and "overlap" in err()
+    assert call(_args(reward_out=0x900000, action_out=0x900000 + 64)) == -1 and "overlap" in err()
+    assert call(_args(reward_out=0x100000 + 4 * 2 * 8 * 8)) == -1 and "overlap" in err()
+    # out of place and disjoint passes these checks, as does n_episodes = 0 with the same made-up addresses
+    assert call(_args(reward_out=0x900000, action_out=0xA00000)) == -2 and "state_out" in err()
+    assert call(_args(n_episodes=0, reward_out=0x100000 + 8)) == -2 and "state_out" in err()
+
+
+# ------------------------------------------------------------------------------------------------ launch, trainer
+def _cfg(**training):
+    return dict(CFG, training=dict({"seed": 1, "epochs": 2}, **training))
+
+
+def test_shard_training_carries_the_option():
+    from th_rl_amd.launch import shard_training
+    for world in (1, 2):
+        for r in range(world):
+            tr, _, _ = shard_training(_cfg(n_games=10, group_stats={"smooth": 1000, "bins": 32}), r, world)
+            assert tr["group_stats"]["smooth"] == {"halflife": 1000.0} and tr["group_stats"]["histograms"] is True
+            assert gs.parse_options(tr["group_stats"])["smooth"] == {"halflife": 1000.0}
+    tr, _, _ = shard_training(_cfg(n_games=10, group_stats=True), 0, 2)
+    assert "smooth" not in tr["group_stats"]
+
+
+def test_train_one_refuses_smooth_with_resume(tmp_path):
+    from th_rl_amd import trainer
+    cfg = _cfg(n_games=4, resume=str(tmp_path / "no_such_batch.pt"), group_stats={"smooth": 3})
+    (tmp_path / "c.json").write_text(json.dumps(cfg))
+    with pytest.raises(ValueError, match="not checkpointed"):
+        trainer.train_one(str(tmp_path / "run"), str(tmp_path / "c.json"))
+
+
+def test_run_refuses_a_smoother_with_nowhere_to_go():
+    from th_rl_amd._lib import ThrlError
+    from th_rl_amd.batched import check_smooth
+
+    class S:
+        N, G = 2, 8
+    with pytest.raises(ThrlError, match="group_stats or per_game_logs"):
+        check_smooth(S(), 2, 8, False, None)
+    with pytest.raises(ThrlError, match="2 agents x 8 games"):
+        check_smooth(S(), 2, 9, True, None)
+    check_smooth(S(), 2, 8, True, None)
+    check_smooth(None, 2, 8, False, None)
+
+
+def test_game_log_smooth_keyword(tmp_path):
+    from th_rl_amd import utils
+    rs = np.random.RandomState(0)
+    d = tmp_path / "exp"
+    os.makedirs(d)
+    np.save(d / "game_ids.npy", np.array([4, 5, 6]))
+    raw, sm = rs.uniform(size=(5, 2, 3)), rs.uniform(size=(5, 2, 3))
+    np.save(d / "game_rewards.npy", raw); np.save(d / "game_actions.npy", raw + 1)
+    assert np.array_equal(utils.game_log(str(d), 5).to_numpy()[:, :2], raw[:, :, 1])
+    with pytest.raises(KeyError, match="smooth"):
+        utils.game_log(str(d), 5, smooth=True)
+    np.save(d / "game_rewards_smooth.npy", sm); np.save(d / "game_actions_smooth.npy", sm + 1)
+    got = utils.game_log(str(d), 6, smooth=True)
+    assert list(got.columns) == [("rewards", 0), ("rewards", 1), ("actions", 0), ("actions", 1)]
+    assert np.array_equal(got.to_numpy(), np.concatenate([sm[:, :, 2], sm[:, :, 2] + 1], axis=1))

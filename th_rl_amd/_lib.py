@@ -97,6 +97,17 @@ class GroupStatsArgs(ctypes.Structure):
     ]
 
 
+class EwmRowsArgs(ctypes.Structure):
+    """thrl_ewm_rows_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_agents", ctypes.c_int32), ("n_episodes", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("decay", ctypes.c_double), ("den", ctypes.c_double),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p),
+        ("reward_out", ctypes.c_void_p), ("action_out", ctypes.c_void_p),
+        ("state_in", ctypes.c_void_p), ("state_out", ctypes.c_void_p), ("den_out", ctypes.POINTER(ctypes.c_double)),
+    ]
+
+
 DEV_MAX_STEPS = 1 << 20
 DEV_MAX_HORIZON = 1 << 24
 
@@ -407,7 +418,7 @@ SYMBOLS = [
     "thrl_op_env_step", "thrl_op_td_update",
     "thrl_nn_param_count", "thrl_nn_init", "thrl_nn_act", "thrl_nn_reinforce_train", "thrl_op_draws",
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
-    "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_deviation",
+    "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_ewm_rows", "thrl_deviation",
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
     "thrl_equilibrium_noise",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
@@ -514,6 +525,8 @@ def load():
     L.thrl_mixed_episodes.argtypes = [cfgp, ctypes.POINTER(Mixed), vp, vp, vp, ctypes.POINTER(Run), vp, vp, vp]
     L.thrl_group_stats.restype = ctypes.c_int
     L.thrl_group_stats.argtypes = [ctypes.POINTER(GroupStatsArgs), vp]
+    L.thrl_ewm_rows.restype = ctypes.c_int
+    L.thrl_ewm_rows.argtypes = [ctypes.POINTER(EwmRowsArgs), vp]
     L.thrl_deviation.restype = ctypes.c_int
     L.thrl_deviation.argtypes = [cfgp, vp, ctypes.POINTER(DeviationArgs), vp]
     L.thrl_policy_track.restype = ctypes.c_int

@@ -38,6 +38,17 @@ def _require_gpu(device):
     return torch.device(device)
 
 
+def check_smooth(smooth, n_agents, n_games, per_game_logs, group_stats):
+    """run(smooth=...) of both batch classes: a Smoother of this batch's games, with something to show for it."""
+    if smooth is None:
+        return
+    if group_stats is None and not per_game_logs:
+        raise ThrlError("smooth needs group_stats or per_game_logs: the smoothed rows would go nowhere")
+    if (smooth.N, smooth.G) != (int(n_agents), int(n_games)):
+        raise ThrlError("smoother is for %d agents x %d games, this batch has %d x %d"
+                        % (smooth.N, smooth.G, n_agents, n_games))
+
+
 class GameBatch(AnalysisMethods):
     def __init__(self, config, n_games=1, device="cuda:0", dtype="float32", seed=0, game_offset=0,
                  kernel="auto", counters=True, sweep=None):
@@ -147,7 +158,8 @@ class GameBatch(AnalysisMethods):
         return self
 
     # ------------------------------------------------------------------ the hot path
-    def run(self, n_episodes, inj=None, per_game_logs=False, sync=True, logs=True, keep_games=None, group_stats=None):
+    def run(self, n_episodes, inj=None, per_game_logs=False, sync=True, logs=True, keep_games=None, group_stats=None,
+            smooth=None):
         """n_episodes of trainer.train_one's loop for all games.  Returns a dict with
         reward_log / action_log [E, N] (mean over games) as numpy (or device tensors
         when sync=False).  per_game_logs=True adds game_reward_log / game_action_log [E, N, G]
@@ -156,11 +168,17 @@ class GameBatch(AnalysisMethods):
         device before the copy, [E, N, len(keep_games)].  group_stats (a group_stats.GroupSpec of this batch's games):
         the kernel writes the per-game rows into device scratch, thrl_group_stats reduces them on the same stream, and
         out["group_stats"] holds the chunk's hist / sums / minmax (group_stats.to_numpy; device tensors when
-        sync=False).  The rows cross to the host only when per_game_logs asks for them."""
+        sync=False).  The rows cross to the host only when per_game_logs asks for them.  smooth (a
+        group_stats.Smoother of this batch's games; needs group_stats or per_game_logs): once the raw rows have been
+        reduced (and copied, when they were asked for) thrl_ewm_rows smooths them on the same stream, carrying the
+        smoother's state from the launch before; the smoothed rows are reduced the same way into
+        out["group_stats_smooth"], and with per_game_logs they are returned as game_reward_smooth / game_action_smooth
+        (keep_games applies)."""
         torch = _torch()
         if not self.initialized:
             raise ThrlError("GameBatch: call init_tables() or set_tables() first")
         E, N, G, T = int(n_episodes), self.N, self.G, self.T
+        check_smooth(smooth, N, G, per_game_logs, group_stats)
         b = _lib.Buffers()
         keep = []
         with torch.cuda.device(self.device):
@@ -224,18 +242,36 @@ class GameBatch(AnalysisMethods):
             out = dict(kernel=self.last_kernel)
             if group_stats is not None:
                 st = group_stats.reduce(self.L, g_r, g_a, E, group_stats.zeros(E, self.device), self._stream())
+            def pick(t):
+                return t if keep_games is None else t.index_select(2, keep_games)
             if sync:
                 torch.cuda.synchronize(self.device)
                 if logs:
                     out["reward_log"], out["action_log"] = r_log.cpu().numpy(), a_log.cpu().numpy()
                 if per_game_logs:
-                    if keep_games is not None:
-                        g_r, g_a = g_r.index_select(2, keep_games), g_a.index_select(2, keep_games)
-                    out["game_reward_log"], out["game_action_log"] = g_r.cpu().numpy(), g_a.cpu().numpy()
+                    out["game_reward_log"], out["game_action_log"] = pick(g_r).cpu().numpy(), pick(g_a).cpu().numpy()
                 if group_stats is not None:
                     from .group_stats import to_numpy
                     out["group_stats"] = to_numpy(st)
+                if smooth is not None:      # in place: the raw rows are reduced, and on the host if they were wanted
+                    smooth.apply(self.L, g_r, g_a, E, self._stream())
+                    if group_stats is not None:
+                        out["group_stats_smooth"] = to_numpy(group_stats.reduce(
+                            self.L, g_r, g_a, E, group_stats.zeros(E, self.device), self._stream()))
+                    if per_game_logs:
+                        out["game_reward_smooth"], out["game_action_smooth"] = (pick(g_r).cpu().numpy(),
+                                                                                pick(g_a).cpu().numpy())
             else:
+                if smooth is not None:      # the raw rows stay on the device for the caller: smooth into a second pair
+                    s_r, s_a = smooth.apply(self.L, g_r, g_a, E, self._stream(),
+                                            out=(torch.empty_like(g_r), torch.empty_like(g_a)) if per_game_logs else None)
+                    if group_stats is not None:
+                        out["group_stats_smooth"] = group_stats.reduce(self.L, s_r, s_a, E,
+                                                                       group_stats.zeros(E, self.device), self._stream())
+                    if per_game_logs:
+                        out.update(game_reward_smooth=s_r, game_action_smooth=s_a)
+                    else:
+                        keep += [s_r, s_a]
                 if not per_game_logs:
                     keep += [g_r, g_a]
                     g_r = g_a = None

@@ -5,8 +5,12 @@ reference's analysis plots per config (utils.py plot_learning_curve_conf / plot_
 plot_sweep_conf / plot_mean_conf).
 
 Quantities, Q = 2N + 1 per game and episode: reward_i (i < N), action_i (i < N), total = sum_i reward_i.  The values
-are the per-epoch ones: the reference smooths each run's curve with ewm(halflife=1000) before its quantiles; that
-smoothing is not applied here.
+are the per-epoch ones.  The reference smooths each run's curve with ewm(halflife=1000) before its quantiles; that
+smoothing is off by default and is asked for with the option "smooth" (a halflife): thrl_ewm_rows then smooths every
+game's rows on the device (Smoother; pandas' ewm(halflife=h, adjust=True).mean(), except that a non-finite value is
+not skipped as pandas skips a NaN: it makes that game's smoothed values non-finite from then on, and those land in the
+overflow bin), the same reduction runs on the smoothed rows, and the run writes a second set of statistics under the
+prefix "group_smooth".  Its "total" is the sum of the smoothed rewards in agent order.
 
 Quantiles from the histogram: with n values in a cell and target t = q * n, take the first bin whose cumulative
 count reaches t and interpolate linearly inside it, lower edge + (t - count below) / count in bin * bin width,
@@ -43,7 +47,7 @@ def parse_options(opt):
         opt = {}
     if not isinstance(opt, dict):
         raise ValueError("training.group_stats must be true or a dict, got %r" % (opt,))
-    known = {"bins", "quantiles", "histograms", "greedy_iters", "ranges", "n_max"}
+    known = {"bins", "quantiles", "histograms", "greedy_iters", "ranges", "n_max", "smooth"}
     bad = set(opt) - known
     if bad:
         raise ValueError("training.group_stats: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(sorted(known))))
@@ -58,7 +62,25 @@ def parse_options(opt):
         raise ValueError("training.group_stats.quantiles must lie in [0, 1]")
     out["greedy_iters"] = int(out["greedy_iters"])
     out["histograms"] = bool(out["histograms"])
+    if out.get("smooth") is None:       # off: the dict is what it was before the option existed
+        out.pop("smooth", None)
+    else:
+        out["smooth"] = {"halflife": parse_halflife(out["smooth"])}
     return out
+
+
+def parse_halflife(v):
+    """training.group_stats.smooth (a number or {"halflife": h}) -> h as a float; finite and > 0."""
+    if isinstance(v, dict):
+        if set(v) - {"halflife", "decay"} or "halflife" not in v:
+            raise ValueError("training.group_stats.smooth: a dict must be {\"halflife\": h}, got keys %s" % sorted(v))
+        v = v["halflife"]
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError("training.group_stats.smooth must be a halflife (a number or {\"halflife\": h}), got %r" % (v,))
+    h = float(v)
+    if not (math.isfinite(h) and h > 0.0):
+        raise ValueError("training.group_stats.smooth: halflife=%r must be finite and > 0" % (v,))
+    return h
 
 
 # ---------------------------------------------------------------------------------------------- groups
@@ -162,7 +184,7 @@ class GroupSpec:
     fixed-point scales, so shards' sums add."""
 
     def __init__(self, n_agents, ids, n_groups, ranges, bins=DEFAULT_BINS, quantiles=DEFAULT_QUANTILES, n_max=None,
-                 values=None):
+                 values=None, smooth=None):
         self.N = int(n_agents)
         self.Q = 2 * self.N + 1
         self.ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
@@ -188,6 +210,7 @@ class GroupSpec:
         self.perm = np.argsort(self.ids, kind="stable").astype(np.int32)
         self.seg_off = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
         self.values = values if values is not None else [{} for _ in range(self.n_groups)]
+        self.smooth = None if smooth is None else parse_halflife(smooth)       # the halflife, or None = off
         self._dev = {}
 
     @classmethod
@@ -195,14 +218,17 @@ class GroupSpec:
         opt = parse_options(options)
         ids, ng, values = assign_groups(n_games, sweep=sweep, groups=groups, n_groups=n_groups)
         return cls(len(config["agents"]), ids, ng, resolve_ranges(config, opt["ranges"]), bins=opt["bins"],
-                   quantiles=opt["quantiles"], n_max=opt["n_max"], values=values)
+                   quantiles=opt["quantiles"], n_max=opt["n_max"], values=values, smooth=opt.get("smooth"))
 
     def describe(self):
         """groups.json's content."""
-        return {"quantities": quantity_names(self.N), "bins": self.bins, "quantiles": self.quantiles,
-                "ranges": self.ranges, "scales": self.scale.tolist(), "n_max": self.n_max,
-                "groups": [{"id": k, "games": int(self.counts[k]), "values": self.values[k]}
-                           for k in range(self.n_groups)]}
+        d = {"quantities": quantity_names(self.N), "bins": self.bins, "quantiles": self.quantiles,
+             "ranges": self.ranges, "scales": self.scale.tolist(), "n_max": self.n_max,
+             "groups": [{"id": k, "games": int(self.counts[k]), "values": self.values[k]}
+                        for k in range(self.n_groups)]}
+        if self.smooth is not None:
+            d["smooth"] = {"halflife": self.smooth, "decay": ewm_decay(self.smooth)[1]}
+        return d
 
     # ------------------------------------------------------------------ device
     def zeros(self, E, device):
@@ -241,6 +267,75 @@ class GroupSpec:
             raise ThrlError("group stats: rows / outputs do not match the spec")
         _lib.check(L.thrl_group_stats(ctypes.byref(a), stream), "thrl_group_stats")
         return out
+
+
+# ---------------------------------------------------------------------------------------------- smoothing
+def ewm_decay(halflife):
+    """(alpha, decay) of pandas' ewm(halflife=h): alpha = 1 - exp(log(0.5) / h) and decay = 1 - alpha, in double, in
+    that order (include/thrl.h)."""
+    alpha = 1.0 - math.exp(math.log(0.5) / float(halflife))
+    return alpha, 1.0 - alpha
+
+
+class Smoother:
+    """The exponentially weighted mean of one run's (or one shard's) per-game rows, carried across launches
+    (thrl_ewm_rows): state [2N][G] on the device (the numerators of reward_0..reward_{N-1}, action_0..action_{N-1}),
+    den (the denominator, the same for every game) and rows (how many rows have gone through).  One Smoother lives
+    as long as the curve it smooths; the result does not depend on how the rows are cut into apply() calls."""
+
+    def __init__(self, n_agents, n_games, halflife, device):
+        import torch
+        self.N, self.G = int(n_agents), int(n_games)
+        self.halflife = parse_halflife(halflife)
+        self.alpha, self.decay = ewm_decay(self.halflife)
+        self.state = torch.zeros((2 * self.N, self.G), dtype=torch.float64, device=device)
+        self.den = 0.0
+        self.rows = 0
+
+    def apply(self, L, rew, act, E, stream, out=None):
+        """Smooth rows 0..E of device rows rew / act [>= E][N][G] (float64, contiguous) in place, or into
+        out = (reward_out, action_out) of the same layout, on `stream` (a ctypes void pointer).  Returns the two
+        tensors that hold the smoothed rows."""
+        o_r, o_a = (rew, act) if out is None else out
+        if int(E) == 0:
+            return o_r, o_a
+        for t in (rew, act, o_r, o_a):
+            if t.shape[1:] != (self.N, self.G) or t.shape[0] < E or str(t.dtype) != "torch.float64" \
+                    or not t.is_contiguous() or t.device != self.state.device:
+                raise ThrlError("smoother: rows must be contiguous float64 [>= %d][%d][%d] on %s"
+                                % (E, self.N, self.G, self.state.device))
+        a = _lib.EwmRowsArgs()
+        a.n_games, a.n_agents, a.n_episodes = self.G, self.N, int(E)
+        a.decay, a.den = self.decay, self.den
+        a.reward_rows, a.action_rows = rew.data_ptr(), act.data_ptr()
+        a.reward_out, a.action_out = o_r.data_ptr(), o_a.data_ptr()
+        a.state_in = a.state_out = self.state.data_ptr()
+        den = ctypes.c_double(self.den)
+        a.den_out = ctypes.pointer(den)
+        _lib.check(L.thrl_ewm_rows(ctypes.byref(a), stream), "thrl_ewm_rows")
+        self.den = float(den.value)
+        self.rows += int(E)
+        return o_r, o_a
+
+
+def ewm_host(rew, act, halflife, state=None, den=0.0):
+    """numpy restatement of thrl_ewm_rows (the same float64 operations in the same order) of rows [E][N][G]:
+    (smoothed rewards, smoothed actions, new state [2N][G], new den).  state / den: what an earlier call returned
+    (None / 0 = fresh)."""
+    rew = np.asarray(rew, np.float64)
+    act = np.asarray(act, np.float64)
+    E, N, G = rew.shape
+    _, d = ewm_decay(halflife)
+    num = np.zeros((2 * N, G)) if state is None else np.array(state, np.float64).reshape(2 * N, G)
+    den = float(den)
+    x = np.concatenate([rew, act], axis=1)                       # [E, 2N, G]
+    y = np.empty_like(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for e in range(E):
+            num = x[e] + d * num                                # the product is rounded, then the sum
+            den = 1.0 + d * den
+            y[e] = num / den
+    return y[:, :N], y[:, N:], num, den
 
 
 def to_numpy(stats):

@@ -13,7 +13,8 @@ shard checkpoint `--out/shard<r>/batch.pt`, and with training.game_logs its shar
 With training.group_stats, group ids come from the global sweep (or training.groups) before the cut, every shard
 writes its raw per-group statistics with histograms, and rank 0 merges them exactly into the top-level
 groups.json / group_*.npy (merge_group_stats), the dev<d>_* and xplay_* statistics of training.deviation and
-training.crossplay among them.  Every analysis of analysis.REGISTRY with a merge (convergence, deviation, equilibrium,
+training.crossplay among them, and with group_stats.smooth the group_smooth_*.npy of the smoothed curves: every shard
+keeps the smoothing state of its own games, so the merged statistics are the single-process ones bit for bit.  Every analysis of analysis.REGISTRY with a merge (convergence, deviation, equilibrium,
 crossplay, attractors, stationary) is written per shard, and rank 0 concatenates the shards' per-game arrays in global
 game order and writes the top-level <key>.json and .npy files (merge_analysis); the others are refused
 (check_launch_config).  With training.crossplay every shard draws its partners INSIDE the shard (the tables of other
@@ -102,6 +103,8 @@ def merge_group_stats(config, out, world):
     save_json(os.path.join(out, "groups.json"), desc)
     shards = [os.path.join(out, "shard%d" % r) for r in range(world)]
     prefixes = ["group"] + (["greedy"] if opt["greedy_iters"] > 0 else [])
+    if opt.get("smooth") is not None:       # every shard smoothed its own games (they are disjoint): merged like the raw ones
+        prefixes.append("group_smooth")
     dv = training.get("deviation")
     if dv is not None and dv is not False:
         from th_rl_amd.deviation import parse_options as deviation_options

@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import ThrlError
 from .analysis import AnalysisMethods
-from .batched import _require_gpu, _torch
+from .batched import _require_gpu, _torch, check_smooth
 from .nn import ActorCriticBatch, CACBatch, ReinforceBatch
 
 NN_DEFAULTS = dict(states=4, actions=2, action_range=[0, 1], gamma=0.98, capacity=50000, min_memory=1000,
@@ -364,7 +364,7 @@ class MixedGameBatch(AnalysisMethods):
         idx = (torch.arange(n, device=self.device) + start) % cap
         return n, {k: v.index_select(1, idx).contiguous() for k, v in b.items()}
 
-    def run(self, n_episodes, fused=None, per_game_logs=True, keep_games=None, group_stats=None, inj=None):
+    def run(self, n_episodes, fused=None, per_game_logs=True, keep_games=None, group_stats=None, inj=None, smooth=None):
         """n_episodes for all games.  fused=True: thrl_mixed_episodes, one launch per run of episodes
         between network updates; fused=False: the per-call operator loop (same results); None
         (default): fused unless the library reports the configuration as unsupported by that kernel
@@ -377,35 +377,43 @@ class MixedGameBatch(AnalysisMethods):
         agents, the sampled actions `action` [E, T, N, G] of the Reinforce / ActorCritic agents and the env's
         `noise_u`, `noise_a` [E, T, G].  Entries of u / choice in a neural agent's slot and of action in a QTable's are
         not read.  All three paths take it; prices, rewards, replay rings, tables and counters are then the
-        reference's exactly, the network parameters to float32 rounding of the update kernels."""
+        reference's exactly, the network parameters to float32 rounding of the update kernels.
+        smooth (a group_stats.Smoother of this batch's games; needs group_stats or per_game_logs): once the raw rows
+        have been reduced (and copied, when they were asked for) thrl_ewm_rows smooths them in place on the same
+        stream, carrying the smoother's state from the launch before; the smoothed rows are reduced the same way into
+        out["group_stats_smooth"] and, where the raw rows are returned, returned as game_reward_smooth /
+        game_action_smooth (keep_games applies).  Both paths take it."""
+        check_smooth(smooth, self.N, self.G, per_game_logs or fused is False, group_stats)
         if inj is not None:
             inj = check_injection(inj, int(n_episodes), self.T, self.N, self.G, self.kinds, self.cfg.noise_prob > 0)
         if fused is None:
             first = self.episode
             try:
-                return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats, inj)
+                return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats, inj, smooth)
             except ThrlError as e:
                 # fall back only if the episode kernel itself refused the configuration, i.e. before any
                 # launch changed tables / buffers / episode index
                 if e.code != _lib.ERR_UNSUPPORTED or self.episode != first or self._fused_launched:
                     raise
-                return self._keep(self._run_unfused(int(n_episodes), group_stats, inj), keep_games)
+                return self._keep(self._run_unfused(int(n_episodes), group_stats, inj, smooth), keep_games)
         if fused:
-            return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats, inj)
-        return self._keep(self._run_unfused(int(n_episodes), group_stats, inj), keep_games)
+            return self._run_fused(int(n_episodes), per_game_logs, keep_games, group_stats, inj, smooth)
+        return self._keep(self._run_unfused(int(n_episodes), group_stats, inj, smooth), keep_games)
 
     @staticmethod
     def _keep(out, keep_games):
         if keep_games is not None:          # (the operator loop's rows are on the host already)
             idx = keep_games.cpu().numpy()
-            out["game_reward_log"], out["game_action_log"] = out["game_reward_log"][:, :, idx], out["game_action_log"][:, :, idx]
+            for k in ("game_reward_log", "game_action_log", "game_reward_smooth", "game_action_smooth"):
+                if k in out:
+                    out[k] = out[k][:, :, idx]
         return out
 
     def _inj_to_device(self, inj):
         torch = _torch()
         return {k: torch.from_numpy(v).to(self.device) for k, v in inj.items()}
 
-    def _run_fused(self, E, per_game_logs=True, keep_games=None, group_stats=None, inj=None):
+    def _run_fused(self, E, per_game_logs=True, keep_games=None, group_stats=None, inj=None, smooth=None):
         """per_game_logs=False keeps only the mean over games (reduced on the device, launch by launch):
         what train_one needs, without E x N x G arrays crossing to the host."""
         torch = _torch()
@@ -422,6 +430,7 @@ class MixedGameBatch(AnalysisMethods):
             rmean = torch.zeros((E, N), dtype=torch.float64, device=self.device)
             amean = torch.zeros((E, N), dtype=torch.float64, device=self.device)
             st = group_stats.zeros(E, self.device) if group_stats is not None else None
+            st_s = group_stats.zeros(E, self.device) if group_stats is not None and smooth is not None else None
             if not hasattr(self, "_scratch"):
                 self._scratch = [torch.zeros_like(b["price"]) if self.kinds[i] == "QTable" else None
                                  for i, b in enumerate(self.buf)]
@@ -475,6 +484,11 @@ class MixedGameBatch(AnalysisMethods):
                 amean[done:done + k] = alog[base:base + k].mean(dim=2)
                 if st is not None:
                     group_stats.reduce(self.L, rlog[base:base + k], alog[base:base + k], k, st, self._stream(), at=done)
+                if smooth is not None and not per_game_logs:
+                    # the launch's rows are reduced and the next launch overwrites them: smooth them in place now
+                    # (with per_game_logs all E rows are smoothed at the end, once the raw ones are on the host)
+                    smooth.apply(self.L, rlog[:k], alog[:k], k, self._stream())
+                    group_stats.reduce(self.L, rlog[:k], alog[:k], k, st_s, self._stream(), at=done)
                 self.eps = [r.eps[i] for i in range(N)] + self.eps[N:]
                 self.count = [mx.count[i] for i in range(N)]
                 self.episode += k
@@ -488,16 +502,23 @@ class MixedGameBatch(AnalysisMethods):
             torch.cuda.synchronize(self.device)
             out = dict(kernel="mixed-fused", episode_kernel=self.last_episode_kernel, reward_log=rmean.cpu().numpy(),
                        action_log=amean.cpu().numpy())
+            def pick(t):
+                return t if keep_games is None else t.index_select(2, keep_games)
             if per_game_logs:
-                if keep_games is not None:
-                    rlog, alog = rlog.index_select(2, keep_games), alog.index_select(2, keep_games)
-                out.update(game_reward_log=rlog.cpu().numpy(), game_action_log=alog.cpu().numpy())
+                out.update(game_reward_log=pick(rlog).cpu().numpy(), game_action_log=pick(alog).cpu().numpy())
             if st is not None:
                 from .group_stats import to_numpy
                 out["group_stats"] = to_numpy(st)
+            if smooth is not None and per_game_logs:
+                smooth.apply(self.L, rlog, alog, E, self._stream())
+                if st_s is not None:
+                    group_stats.reduce(self.L, rlog, alog, E, st_s, self._stream())
+                out.update(game_reward_smooth=pick(rlog).cpu().numpy(), game_action_smooth=pick(alog).cpu().numpy())
+            if st_s is not None:
+                out["group_stats_smooth"] = to_numpy(st_s)
         return out
 
-    def _run_unfused(self, n_episodes, group_stats=None, inj=None):
+    def _run_unfused(self, n_episodes, group_stats=None, inj=None, smooth=None):
         torch = _torch()
         if not self.initialized:
             raise ThrlError("MixedGameBatch: call init_tables() or set_tables() first")
@@ -593,6 +614,12 @@ class MixedGameBatch(AnalysisMethods):
             out = dict(game_reward_log=rlog.cpu().numpy(), game_action_log=alog.cpu().numpy(), kernel="unfused")
             if group_stats is not None:
                 out["group_stats"] = to_numpy(st)
+            if smooth is not None:          # in place: the raw rows are reduced and on the host
+                smooth.apply(L, rlog, alog, E, self._stream())
+                if group_stats is not None:
+                    out["group_stats_smooth"] = to_numpy(group_stats.reduce(L, rlog, alog, E, group_stats.zeros(E, self.device),
+                                                                            self._stream()))
+                out.update(game_reward_smooth=rlog.cpu().numpy(), game_action_smooth=alog.cpu().numpy())
         out["reward_log"] = out["game_reward_log"].mean(axis=2)
         out["action_log"] = out["game_action_log"].mean(axis=2)
         return out

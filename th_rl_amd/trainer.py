@@ -24,8 +24,14 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                      # group_quantiles.npy [epochs, n_groups, Q, n_q], group_sums.npy int64 [.., Q, 2],
                                      # with histograms group_hist.npy uint32 [.., Q, bins + 2]; greedy_iters k > 0 adds
                                      # the same greedy_*.npy of play_greedy's rows ([k, ...]).  Q = 2N + 1 quantities:
-                                     # reward_i, action_i, total.  Quantiles are of the per-epoch values (the reference
-                                     # smooths each run with ewm(halflife=1000) first; that is not done here).
+                                     # reward_i, action_i, total.  Quantiles are of the per-epoch values; the reference
+                                     # smooths each run with ewm(halflife=1000) first, which is off by default:
+                                     # "smooth": 1000 (a halflife, or {"halflife": 1000}) smooths every game's curve on
+                                     # the device (thrl_ewm_rows, pandas' ewm(halflife=h).mean(); one state for the whole
+                                     # run) and adds the same files for the smoothed curves, group_smooth_*.npy, and
+                                     # with game_logs game_rewards_smooth.npy / game_actions_smooth.npy; groups.json
+                                     # gains "smooth": {"halflife", "decay"}.  Not with "resume": the smoothing state
+                                     # is not checkpointed.
                  "equilibrium": null,  # true or {"agents": [all], "tol": 0.0, "policies": false, "tables": "final"}: after
                                        # training (and the deviation analysis) the equilibrium check of the greedy
                                        # strategies (equilibrium.py, QTable agents only): equilibrium.json, eq_*.npy;
@@ -108,7 +114,7 @@ reference's four artefacts for game 0 (`<i>.npy`, `<i>_counter.npy`, `config.jso
 `log.csv` -- the log is the MEAN over games), plus `batch.pt` with all games when
 n_games > 1, with "game_logs" the kept games' own curves (game_rewards.npy, game_actions.npy,
 game_ids.npy), and with "group_stats" the per-group statistics (groups.json, group_*.npy; utils.group_log and
-utils.group_quantiles read them).  There is no CPU fallback: without the HIP library or a GPU this raises.
+utils.group_quantiles read them; with its "smooth" also those of the smoothed curves, group_smooth_*.npy).  There is no CPU fallback: without the HIP library or a GPU this raises.
 """
 import json
 import os
@@ -289,6 +295,11 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     names = [a["name"] for a in config["agents"]]
 
     resume = training.get("resume", None)
+    if resume and training.get("group_stats", None) not in (None, False):
+        from th_rl_amd.group_stats import parse_options
+        if parse_options(training["group_stats"]).get("smooth") is not None:
+            raise ValueError("training.group_stats.smooth with training.resume: the smoothing state is not checkpointed, "
+                             "so a continued run cannot carry the curve on")
     # Small all-QTable batches in float64 (the default for ONE game = the reference's own use), and those
     # the LDS-resident wave kernel cannot take (other than 2 agents, per-agent grids, T < min_memory), run one
     # wavefront per game through the mixed-agent episode kernel: it keeps train_one's per-step log arithmetic
@@ -357,6 +368,14 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         keep = None
 
     spec, gs_opt = group_spec_of(config, training, n_games)
+    smoother = None
+    if spec is not None and spec.smooth is not None:
+        from th_rl_amd.group_stats import Smoother
+        smoother = Smoother(len(agents), n_games, spec.smooth, batch.device)    # one for the whole run
+        gsm_files = group_stats_files(exp_path, "group_smooth", epochs, spec, gs_opt["histograms"])
+        if game_logs is not None:
+            g_rew_s = _npy_out(os.path.join(exp_path, "game_rewards_smooth.npy"), (epochs, len(agents), len(gids)))
+            g_act_s = _npy_out(os.path.join(exp_path, "game_actions_smooth.npy"), (epochs, len(agents), len(gids)))
     xp_opt, gc_opt = opts.get("crossplay"), opts.get("greedy_cycles")
     if spec is not None and xp_opt is not None and xp_opt["steps"] > 0:
         from th_rl_amd.crossplay import MAX_POOLED_ROUNDS
@@ -387,7 +406,8 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
         d = 0
         while d < n:
             k = min(sub, n - d)
-            out = batch.run(k, per_game_logs=game_logs is not None, keep_games=keep, group_stats=spec)
+            kw = {} if smoother is None else {"smooth": smoother}
+            out = batch.run(k, per_game_logs=game_logs is not None, keep_games=keep, group_stats=spec, **kw)
             rewards_log[at + d:at + d + k] = out["reward_log"]
             actions_log[at + d:at + d + k] = out["action_log"]
             if game_logs is not None:
@@ -395,6 +415,11 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
                 g_act[at + d:at + d + k] = out["game_action_log"]
             if spec is not None:
                 write_group_stats(g_files, at + d, out["group_stats"], spec.describe())
+            if smoother is not None:
+                write_group_stats(gsm_files, at + d, out["group_stats_smooth"], spec.describe())
+                if game_logs is not None:
+                    g_rew_s[at + d:at + d + k] = out["game_reward_smooth"]
+                    g_act_s[at + d:at + d + k] = out["game_action_smooth"]
             d += k
 
     t = time.time()
@@ -451,18 +476,30 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
     if game_logs is not None and g_rew.size:
         g_rew.flush()
         g_act.flush()
+        if smoother is not None:
+            g_rew_s.flush()
+            g_act_s.flush()
     if stopped_early:       # every per-epoch artefact has episodes_run rows
         from th_rl_amd.convergence import truncate_rows
         per_epoch = []
         if game_logs is not None:
             g_rew = g_act = None
             per_epoch += ["game_rewards.npy", "game_actions.npy"]
+            if smoother is not None:
+                g_rew_s = g_act_s = None
+                per_epoch += ["game_rewards_smooth.npy", "game_actions_smooth.npy"]
         if spec is not None:
             for f in list(g_files):
                 if hasattr(g_files[f], "flush"):
                     g_files[f].flush()
                 g_files[f] = None
                 per_epoch.append("group_%s.npy" % f)
+            if smoother is not None:
+                for f in list(gsm_files):
+                    if hasattr(gsm_files[f], "flush"):
+                        gsm_files[f].flush()
+                    gsm_files[f] = None
+                    per_epoch.append("group_smooth_%s.npy" % f)
         for name in per_epoch:
             truncate_rows(os.path.join(exp_path, name), episodes_run)
     if spec is not None:
@@ -472,6 +509,8 @@ def train_one(exp_path, configpath, loadonly=False, print_eps=False):
             gr_files = group_stats_files(exp_path, "greedy", it, spec, gs_opt["histograms"])
             write_group_stats(gr_files, 0, raw, spec.describe())
             g_files.update({"greedy_" + f: a for f, a in gr_files.items()})
+        if smoother is not None:
+            g_files.update({"smooth_" + f: a for f, a in gsm_files.items()})
         for arr in g_files.values():
             if hasattr(arr, "flush"):
                 arr.flush()

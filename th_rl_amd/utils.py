@@ -45,10 +45,13 @@ def play_game_batched(batch, iters=1, state0=None):
     return batch.play_greedy(iters=iters, state0=state0)
 
 
-def game_log(exp_path, game_id):
+def game_log(exp_path, game_id, smooth=False):
     """One game's learning curve from a run trained with training.game_logs: a DataFrame with log.csv's columns
     (rewards / actions x agent, as train_one builds it) and one row per epoch.  The game is looked up by its GLOBAL
-    id in exp_path's game_ids.npy and in those of exp_path/shard*/ (th_rl_amd.launch writes one set per rank)."""
+    id in exp_path's game_ids.npy and in those of exp_path/shard*/ (th_rl_amd.launch writes one set per rank).
+    smooth=True: the curve smoothed on the device (game_rewards_smooth.npy / game_actions_smooth.npy of a run that
+    also had training.group_stats.smooth), what the reference's load_experiment returns for a single run."""
+    suffix = "_smooth" if smooth else ""
     import glob
     dirs = [exp_path] + sorted(glob.glob(os.path.join(exp_path, "shard*")))
     for d in dirs:
@@ -58,8 +61,11 @@ def game_log(exp_path, game_id):
         hit = numpy.flatnonzero(numpy.load(ids_path) == int(game_id))
         if hit.size:
             k = int(hit[0])
-            rew = numpy.load(os.path.join(d, "game_rewards.npy"), mmap_mode="r")[:, :, k]
-            act = numpy.load(os.path.join(d, "game_actions.npy"), mmap_mode="r")[:, :, k]
+            if smooth and not os.path.isfile(os.path.join(d, "game_rewards_smooth.npy")):
+                raise KeyError("game %d has no smoothed per-game log under %s (training.group_stats.smooth)"
+                               % (int(game_id), d))
+            rew = numpy.load(os.path.join(d, "game_rewards%s.npy" % suffix), mmap_mode="r")[:, :, k]
+            act = numpy.load(os.path.join(d, "game_actions%s.npy" % suffix), mmap_mode="r")[:, :, k]
             n = rew.shape[1]
             rpd = pandas.DataFrame(data=numpy.array(rew), columns=numpy.arange(n))
             apd = pandas.DataFrame(data=numpy.array(act), columns=numpy.arange(n))
@@ -69,7 +75,7 @@ def game_log(exp_path, game_id):
 
 def load_group_stats(exp_path, prefix="group"):
     """(describe, fields) of a run trained with training.group_stats: groups.json and the group_*.npy (prefix
-    "greedy": greedy_*.npy) of exp_path; when exp_path has none but exp_path/shard*/ do (a sharded run stopped before
+    "greedy": greedy_*.npy; "group_smooth": those of the smoothed curves, training.group_stats.smooth) of exp_path; when exp_path has none but exp_path/shard*/ do (a sharded run stopped before
     rank 0 merged them), the shards' raw outputs merged exactly (group_stats.merge)."""
     import glob
     import json
@@ -97,7 +103,8 @@ def load_group_stats(exp_path, prefix="group"):
 
 def group_log(exp_path, group, prefix="group"):
     """Group `group`'s mean curve over its games, with log.csv's columns (rewards / actions x agent), one row per
-    epoch (prefix "greedy": per greedy iteration)."""
+    epoch (prefix "greedy": per greedy iteration; prefix "group_smooth": the mean over the group's games of the curves
+    smoothed per game, with training.group_stats.smooth)."""
     desc, f = load_group_stats(exp_path, prefix)
     n = (len(desc["quantities"]) - 1) // 2
     m = numpy.array(f["mean"][:, int(group), :])
@@ -113,7 +120,9 @@ def _quantile_column(q):
 def group_quantiles(exp_path, group, quantity="total", prefix="group"):
     """utils.plot_learning_curve_conf's data for one group: a DataFrame with one column per configured quantile
     ("25th", "median", "75th" for the default [0.25, 0.5, 0.75]) of `quantity` over the group's games, one row per
-    epoch, plus "Nash" and "Cartel" from environment.get_optimal() (the reference hard-codes 22.22 and 25)."""
+    epoch, plus "Nash" and "Cartel" from environment.get_optimal() (the reference hard-codes 22.22 and 25).  The
+    reference smooths every run's curve before it takes these quantiles: prefix="group_smooth" (a run with
+    training.group_stats.smooth, halflife 1000 for the reference's) gives the quantiles of the smoothed curves."""
     desc, f = load_group_stats(exp_path, prefix)
     names = desc["quantities"]
     if quantity not in names:
