@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -28,7 +29,7 @@
 
 enum Cls { V_AND, V_AND_E64, V_AND_SGPR, V_ADD_U32, V_MOV, V_LSHL, V_ADD_F32, V_MUL_F32, V_FMAC_F32, V_PK_FMA_F32, V_ADD3, V_CNDMASK_E64, V_CNDMASK_E64_VCC, V_CNDMASK_NEWDST, V_CNDMASK_AFTER_CMP, V_MUL_LO_U32, V_MUL_HI_U32, V_XOR, V_CVT_F64_U32, V_CMP_LT_F64, CHAIN4,
            V_ADD_SDWA, V_MAD_U24, V_FMA_F32, V_MAX_DPP, V_MOV_DPP_SHR, V_CNDMASK, V_READLANE, V_WRITELANE, V_PERMLANE32,
-           V_FMA_F64, V_ADD_F64, V_MUL_F64, V_MAX3_F32, V_CMP_F32, S_ADD, S_NOP0, S_PACK, DS_READ_U16, DS_READ_B32, DS_READ2_B32, DS_BPERMUTE,
+           V_FMA_F64, V_ADD_F64, V_MUL_F64, V_MAX3_F32, V_CMP_F32, V_BITOP3, V_BITOP3_SGPR, V_MAD_U64_U32, V_MAD_U64_U32_SGPR, S_ADD, S_NOP0, S_PACK, DS_READ_U16, DS_READ_B32, DS_READ2_B32, DS_BPERMUTE, DS_SWIZZLE,
            MIX_VALU_SALU, MIX_VALU_LDS, MIX_CND_AND_1_1, MIX_CND_AND_1_3, N_CLS };
 static const char* kNames[N_CLS] = {"v_and_b32", "v_and_b32_e64 (VOP3 encoding)", "v_and_b32 (SGPR src0)", "v_add_u32", "v_mov_b32", "v_lshlrev_b32",
                                     "v_add_f32", "v_mul_f32", "v_fmac_f32 (VOP2)", "v_pk_fma_f32", "v_add3_u32", "v_cndmask_b32_e64 (SGPR-pair mask)", "v_cndmask_b32_e64 (mask = vcc)", "v_cndmask_b32 vcc, dst != src", "v_cmp_gt_f32 vcc + 7 v_cndmask_b32 vcc",
@@ -36,8 +37,9 @@ static const char* kNames[N_CLS] = {"v_and_b32", "v_and_b32_e64 (VOP3 encoding)"
                                     "play chain group: 4 dependent v_readlane + 2 s_pack + 2 v_writelane + s_nop pads (12 instructions = 4 steps)",
                                     "v_add_u32_sdwa", "v_mad_u32_u24", "v_fma_f32", "v_max_f32_dpp(quad_perm)", "v_mov_b32_dpp(row_shr:1)",
                                     "v_cndmask_b32", "v_readlane_b32", "v_writelane_b32", "v_permlane32_swap_b32", "v_fma_f64", "v_add_f64", "v_mul_f64",
-                                    "v_max3_f32", "v_cmp_gt_f32(->vcc)", "s_add_u32", "s_nop 0", "s_pack_ll_b32_b16", "ds_read_u16", "ds_read_b32",
-                                    "ds_read2_b32", "ds_bpermute_b32", "mix: v_and_b32 + s_add_u32 (1:1)", "mix: 3 v_and_b32 + 1 ds_read_b32",
+                                    "v_max3_f32", "v_cmp_gt_f32(->vcc)", "v_bitop3_b32 (0x96, all VGPR)", "v_bitop3_b32 (0x96, one SGPR source)",
+                                    "v_mad_u64_u32", "v_mad_u64_u32 (SGPR src0)", "s_add_u32", "s_nop 0", "s_pack_ll_b32_b16", "ds_read_u16", "ds_read_b32",
+                                    "ds_read2_b32", "ds_bpermute_b32", "ds_swizzle_b32 (broadcast in 8)", "mix: v_and_b32 + s_add_u32 (1:1)", "mix: 3 v_and_b32 + 1 ds_read_b32",
                                     "mix: v_cndmask_b32 (vcc) + v_and_b32 (1:1)", "mix: v_cndmask_b32 (vcc) + 3 v_and_b32"};
 
 // 8 instructions of class C on 8 independent registers
@@ -84,6 +86,8 @@ static const char* kNames[N_CLS] = {"v_and_b32", "v_and_b32_e64 (VOP3 encoding)"
 #define I_FMA64(k) "v_fma_f64 %" #k ", %" #k ", %8, %8\n\t"
 #define I_ADD64(k) "v_add_f64 %" #k ", %" #k ", %8\n\t"
 #define I_MUL64(k) "v_mul_f64 %" #k ", %" #k ", %8\n\t"
+#define I_BOP3(k) "v_bitop3_b32 %" #k ", %" #k ", %8, %8 bitop3:0x96\n\t"
+#define I_BOP3S(k) "v_bitop3_b32 %" #k ", %" #k ", %9, %8 bitop3:0x96\n\t"
 #define I_RL(k)    "v_readlane_b32 %" #k ", %9, 5\n\t"
 #define I_SADD(k)  "s_add_u32 %" #k ", %" #k ", %8\n\t"
 #define I_SNOP(k)  "s_nop 0\n\t"
@@ -91,6 +95,7 @@ static const char* kNames[N_CLS] = {"v_and_b32", "v_and_b32_e64 (VOP3 encoding)"
 #define I_DSU16(k) "ds_read_u16 %" #k ", %10\n\t"
 #define I_DSB32(k) "ds_read_b32 %" #k ", %10\n\t"
 #define I_DSBP(k)  "ds_bpermute_b32 %" #k ", %10, %8\n\t"
+#define I_DSSWZ(k) "ds_swizzle_b32 %" #k ", %" #k " offset:swizzle(BROADCAST,8,3)\n\t"
 #define I_MIXVS(k) "v_and_b32 %" #k ", %9, %" #k "\n\ts_add_u32 %8, %8, 1\n\t"
 
 template <int C>
@@ -179,6 +184,20 @@ __global__ void __launch_bounds__(256) k_issue(int iters, uint64_t* out) {
             }
             else if (C == V_MAX3_F32) V8(I_MAX3);
             else if (C == V_CMP_F32) V8(I_CMP);
+            else if (C == V_BITOP3) V8(I_BOP3);
+            else if (C == V_BITOP3_SGPR) V8(I_BOP3S);
+            else if (C == V_MAD_U64_U32 || C == V_MAD_U64_U32_SGPR) {
+                // 64-bit product of two 32-bit sources, no addend (Philox's form); four destination pairs in rotation,
+                // the sources are never a destination
+                if (C == V_MAD_U64_U32)
+                    asm volatile("v_mad_u64_u32 %0, vcc, %4, %5, 0\n\tv_mad_u64_u32 %1, vcc, %4, %5, 0\n\tv_mad_u64_u32 %2, vcc, %4, %5, 0\n\tv_mad_u64_u32 %3, vcc, %4, %5, 0\n\t"
+                                 "v_mad_u64_u32 %0, vcc, %5, %4, 0\n\tv_mad_u64_u32 %1, vcc, %5, %4, 0\n\tv_mad_u64_u32 %2, vcc, %5, %4, 0\n\tv_mad_u64_u32 %3, vcc, %5, %4, 0\n\t"
+                                 : "+v"(*(uint64_t*)&v[0]), "+v"(*(uint64_t*)&v[2]), "+v"(*(uint64_t*)&v[4]), "+v"(*(uint64_t*)&v[6]) : "v"(x), "v"(ldsa) : "vcc");
+                else
+                    asm volatile("v_mad_u64_u32 %0, vcc, %4, %5, 0\n\tv_mad_u64_u32 %1, vcc, %4, %5, 0\n\tv_mad_u64_u32 %2, vcc, %4, %5, 0\n\tv_mad_u64_u32 %3, vcc, %4, %5, 0\n\t"
+                                 "v_mad_u64_u32 %0, vcc, %4, %6, 0\n\tv_mad_u64_u32 %1, vcc, %4, %6, 0\n\tv_mad_u64_u32 %2, vcc, %4, %6, 0\n\tv_mad_u64_u32 %3, vcc, %4, %6, 0\n\t"
+                                 : "+v"(*(uint64_t*)&v[0]), "+v"(*(uint64_t*)&v[2]), "+v"(*(uint64_t*)&v[4]), "+v"(*(uint64_t*)&v[6]) : "s"(sx), "v"(x), "v"(ldsa) : "vcc");
+            }
             else if (C == V_FMA_F64) D8(I_FMA64);
             else if (C == V_ADD_F64) D8(I_ADD64);
             else if (C == V_MUL_F64) D8(I_MUL64);
@@ -196,6 +215,7 @@ __global__ void __launch_bounds__(256) k_issue(int iters, uint64_t* out) {
                              : "+v"(*(uint64_t*)&v[0]), "+v"(*(uint64_t*)&v[2]), "+v"(*(uint64_t*)&v[4]), "+v"(*(uint64_t*)&v[6]) : "v"(ldsa) : "memory");
             }
             else if (C == DS_BPERMUTE) { V8(I_DSBP); }
+            else if (C == DS_SWIZZLE) { V8(I_DSSWZ); }
             else if (C == MIX_VALU_SALU) {
                 asm volatile(I_MIXVS(0) I_MIXVS(1) I_MIXVS(2) I_MIXVS(3)
                              : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+s"(s[0])
@@ -247,6 +267,7 @@ static int per_iter(int c) {
 
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 4000;
+    const char* only = argc > 2 ? argv[2] : nullptr;            // classes whose name contains this string
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
@@ -261,6 +282,7 @@ int main(int argc, char** argv) {
            prop.gcnArchName, cus, lds_cu, iters, iters * 128);
     bool first = true;
     for (int c = 0; c < N_CLS; c++) {
+        if (only && !strstr(kNames[c], only)) continue;
         for (int wi = 0; wi < (int)(sizeof(Ws) / sizeof(Ws[0])); wi++) {
             const int W = Ws[wi];
             // exactly W blocks of 4 waves per CU: LDS per block just under lds_cu / W, more than lds_cu / (W + 1)

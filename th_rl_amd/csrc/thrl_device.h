@@ -47,6 +47,39 @@ __device__ __forceinline__ u32x4 draw(uint64_t seed, uint64_t game, uint32_t epi
                          (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
+// a ^ b ^ c in one instruction: v_bitop3_b32 with truth table 0x96 (hipcc does not form it from the two xors)
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+    return (uint32_t)__builtin_amdgcn_bitop3_b32((int)a, (int)b, (int)c, 0x96);
+}
+// The same function, bit for bit, for a wave whose lanes differ in the counter only (one step per lane: game, episode,
+// stream and key are wave-uniform).  From round PLAIN on both xor terms `hi ^ c ^ k` have two per-lane words and the
+// round key in an SGPR; written as two xors that is one slow-class instruction (SGPR source) and one fast one, as
+// xor3 it is one.  The rounds before keep the plain form: their uniform terms fold on the scalar unit.
+template <int PLAIN>
+__device__ __forceinline__ u32x4 philox4x32_10_lanes(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                                     uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
+        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        const uint32_t n0 = r < PLAIN ? hi1 ^ c1 ^ k0 : xor3(hi1, c1, k0);
+        const uint32_t n2 = r < PLAIN ? hi0 ^ c3 ^ k1 : xor3(hi0, c3, k1);
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return u32x4{c0, c1, c2, c3};
+}
+// draw() with the step per lane and everything else wave-uniform (round 0 multiplies the uniform game word and
+// xors uniform words; round 1 still has one uniform word in each term)
+__device__ __forceinline__ u32x4 draw_lanes(uint64_t seed, uint64_t game, uint32_t episode, uint32_t step,
+                                            uint32_t stream) {
+    return philox4x32_10_lanes<2>(step, episode, (uint32_t)game,
+                                  (uint32_t)((game >> 32) & 0xFFFFFFu) | (stream << 24),
+                                  (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
 __device__ __forceinline__ double u01_32(uint32_t x) { return __dmul_rn((double)x, 0x1p-32); }
 __device__ __forceinline__ double u01_53(uint32_t hi, uint32_t lo) {
     return __dmul_rn(__dadd_rn(__dmul_rn((double)(hi >> 5), 67108864.0), (double)(lo >> 6)), 0x1p-53);

@@ -999,7 +999,7 @@ k_wave_episodes(const WaveArgs a) {
                     uint32_t seed_lo = (uint32_t)a.seed, seed_hi = (uint32_t)(a.seed >> 32);
                     asm volatile("" : "+s"(seed_lo), "+s"(seed_hi));
                     const uint64_t seed_here = ((uint64_t)seed_hi << 32) | seed_lo;
-                    const u32x4 x = draw(seed_here, gid, eg + (uint32_t)ep, st_in_ep, 0u);
+                    const u32x4 x = draw_lanes(seed_here, gid, eg + (uint32_t)ep, st_in_ep, 0u);
                     const uint32_t ex0 = u01_32(x.x) < eps0 ? 1u : 0u;
                     const uint32_t ex1 = u01_32(x.z) < eps1 ? 2u : 0u;
                     rw = ex0 | ex1 | (__umulhi(x.y, (uint32_t)A) << 8) | (__umulhi(x.w, (uint32_t)A) << 16);
