@@ -1,6 +1,13 @@
 """What the post-training analyses share: the one table of `training` keys (REGISTRY), the host-side helpers every
 analysis module used to carry a copy of, and the analysis methods of GameBatch and MixedGameBatch (AnalysisMethods).
 
+The helpers come in three sections.  "summaries and JSON": num, mean, frac, quantiles, save_json, combine.  "options":
+options, check_qtable_only, and for the long-run chain analyses (stationary, tuple_stationary, sampled_play)
+check_own_noise and chain_options.  "device arguments": what a run() does around its library call -- games (n_games ->
+G), state0_tensor, start_tensor, tables_tensor, check_policy, resolve_noise, bind_tables (the per-config tables, checked
+and uploaded), outputs / bind / fetch (the output dict).  Each takes the caller's message prefix, so an error names the
+analysis that raised it.
+
 REGISTRY is read by trainer.train_one (parse the options before training, write the artefacts after it),
 launch (which keys merge over shards and how) and the tests; utils has `<reader>_summary` / `<reader>_games` per record.
 Order is execution order: a later analysis may read what an earlier one left (`after`).
@@ -137,7 +144,110 @@ def options(key, opt, defaults, tables=False):
     return out
 
 
+def check_own_noise(config, name):
+    """ValueError when `name` asks for the run's own noise and the run has none: refused before training, as the
+    batch would after it."""
+    env = dict(_lib.ENV_DEFAULTS, **config["environment"])
+    sweep = config.get("training", {}).get("sweep") or {}
+    if float(env["noise_prob"]) == 0.0 and "noise_prob" not in sweep:
+        raise ValueError("%s: the environment has noise_prob = 0: give the noise_prob to analyse" % name)
+
+
+def chain_options(out, name, starts):
+    """The checks a chain analysis's parsed options share: start in `starts`, tol a number >= 0 (made a float),
+    max_iters an integer in [1, STAT_MAX_ITERS], pi a bool."""
+    if out["start"] not in starts:
+        raise ValueError("%s.start must be one of %s, got %r" % (name, starts, out["start"]))
+    if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float)) or not out["tol"] >= 0.0:
+        raise ValueError("%s.tol must be a number >= 0, got %r" % (name, out["tol"]))
+    out["tol"] = float(out["tol"])
+    if isinstance(out["max_iters"], bool) or not isinstance(out["max_iters"], int) \
+            or not 1 <= out["max_iters"] <= _lib.STAT_MAX_ITERS:
+        raise ValueError("%s.max_iters must be an integer in [1, %d], got %r" % (name, _lib.STAT_MAX_ITERS, out["max_iters"]))
+    if not isinstance(out["pi"], bool):
+        raise ValueError("%s.pi must be true or false, got %r" % (name, out["pi"]))
+
+
 # ---------------------------------------------------------------------------------------------- device arguments
+def games(batch, n_games, what):
+    """G: the first n_games (default all) games of the batch."""
+    G = batch.G if n_games is None else int(n_games)
+    if not 1 <= G <= batch.G:
+        raise ThrlError("%s: n_games=%r out of [1, %d]" % (what, n_games, batch.G))
+    return G
+
+
+def start_tensor(start, G, dev, what):
+    """Given start tuples (a tensor or an array) as a contiguous device int32 tensor [G]."""
+    import torch
+    if isinstance(start, torch.Tensor):
+        t0 = start.to(device=dev, dtype=torch.int32).reshape(-1)[:G].contiguous()
+    else:
+        t0 = torch.from_numpy(np.ascontiguousarray(np.asarray(start).reshape(-1)[:G].astype(np.int32))).to(dev)
+    if t0.numel() != G:
+        raise ThrlError("%s: start must hold %d tuples" % (what, G))
+    return t0
+
+
+def resolve_noise(batch, noise_prob, G, what, zero_ok=False):
+    """(scalar or None, device float64 [G] or None) for a noise_prob argument: None = the batch's per-game sweep array if
+    it has one, else the config's value (0 asks for an explicit one); a number in (0, 1], or with zero_ok in [0, 1]; or an
+    array / tensor [G] (device data: the kernel refuses a game whose entry is out of range)."""
+    import torch
+    if noise_prob is None:
+        sw = getattr(batch, "sweep", None) or {}
+        if "noise_prob" in sw:
+            return None, sw["noise_prob"][:G].to(torch.float64).contiguous()
+        noise_prob = float(batch.cfg.noise_prob)
+        if noise_prob == 0.0:
+            raise ThrlError("%s: the batch was configured without env noise (noise_prob = 0): pass the "
+                            "noise_prob to analyse explicitly" % what)
+    if isinstance(noise_prob, torch.Tensor):
+        arr = noise_prob.to(device=batch.device, dtype=torch.float64).reshape(-1)[:G].contiguous()
+    elif np.ndim(noise_prob) > 0:
+        arr = torch.from_numpy(np.ascontiguousarray(np.asarray(noise_prob, np.float64).reshape(-1)[:G])).to(batch.device)
+    else:
+        p = float(noise_prob)
+        if not (0.0 <= p if zero_ok else 0.0 < p) or not p <= 1.0:
+            raise ThrlError("%s: noise_prob=%r out of %s0, 1]" % (what, noise_prob, "[" if zero_ok else "("))
+        return p, None
+    if arr.numel() != G:
+        raise ThrlError("%s: noise_prob must hold %d values" % (what, G))
+    return None, arr
+
+
+def bind_tables(a, tabs, fields, dev, what):
+    """The per-config tables `fields` = (field, shape, numpy dtype) of `tabs`, each made contiguous, checked against its
+    shape, copied to `dev` and bound to a.<field>.  Returns the device tensors: the caller keeps them until the call is
+    done."""
+    import torch
+    keep = []
+    for f, shape, dt in fields:
+        x = np.ascontiguousarray(tabs[f], dt)
+        if x.shape != shape:
+            raise ThrlError("%s: table %s has shape %s, expected %s" % (what, f, x.shape, shape))
+        keep.append(torch.from_numpy(x).to(dev))
+        setattr(a, f, keep[-1].data_ptr())
+    return keep
+
+
+def outputs(dev, *groups):
+    """The output dict of a run(): every group is (fields, shape, torch dtype name); {field: zeroed tensor on dev}."""
+    import torch
+    return {f: torch.zeros(shape, dtype=getattr(torch, dt), device=dev) for fields, shape, dt in groups for f in fields}
+
+
+def bind(a, out):
+    """a.<field> = the device address of every output tensor."""
+    for f, t in out.items():
+        setattr(a, f, t.data_ptr())
+
+
+def fetch(out):
+    """The outputs as numpy arrays (synchronises through the copies)."""
+    return {f: t.cpu().numpy() for f, t in out.items()}
+
+
 def state0_tensor(batch, state0, G, what):
     """The start prices of the first G games (matches) as a contiguous device float64 tensor [G]: the batch's state
     for None, else the first G of a tensor or array."""

@@ -149,12 +149,11 @@ def run(batch, state0=None, policies=False, q=None, policy=None, reset=True, n_g
             out["state_rep"] = torch.zeros((G, S), dtype=torch.int16, device=dev)
             out["state_mu"] = torch.zeros((G, S), dtype=torch.int16, device=dev)
         a.state0, a.policy = s0.data_ptr(), policy.data_ptr()
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        an.bind(a, out)
         _lib.check(batch.L.thrl_attractors(ctypes.byref(batch.cfg), None if given else q.data_ptr(), ctypes.byref(a),
                                            batch._stream()), "thrl_attractors")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
     for f in STATE_FIELDS:
         if f in res:
             res[f] = res[f].view(np.uint16)

@@ -222,8 +222,7 @@ def run(batch, seats, steps=0, horizon=None, state0=None, rows=False, group_stat
                    "cycle_reward": torch.zeros((N, M), dtype=torch.float64, device=dev),
                    "cycle_action": torch.zeros((N, M), dtype=torch.float64, device=dev)}
             a.seat, a.state0 = seat.data_ptr(), start.data_ptr()
-            for f, t in out.items():
-                setattr(a, f, t.data_ptr())
+            an.bind(a, out)
             rr_host, ra_host = [], []
             b0 = 0
             while True:

@@ -13,6 +13,9 @@
 //   change is a maximum, whose order is free: it goes through LDS in two levels, no shuffle.  The ordered output sums
 //   follow k_ts_chain: chunks of 64 tuples, one lane per tuple for the products, then one lane per output reading them
 //   back in ascending t; `agree` is one more lane over the D terms parked in the dead iterate.
+//   The body is calls: the staging, Z(d), the M / W pass, the sum over the distinct prices, the block maximum and agree's
+//   terms are thrl_sampled_dev.h's, shared with k_spn_chain; the unsolved outputs, the lazy update, the read-back and the
+//   final store are thrl_chain_dev.h's, shared with all four chain kernels.  Only the staging of the products is here.
 //   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
 #include "thrl_sampled_dev.h"
 
@@ -38,74 +41,23 @@ __device__ __forceinline__ void sp_block(const SpArgs& a, unsigned char* s_mem, 
     for (int t = tid; t < T; t += kSpBlock) perm[t] = (uint16_t)min(max(a.grp_perm[t], 0), T - 1);
 
     for (int64_t g = bid; g < G; g += nblk) {
-        bool ok = true;
-        for (int i = 0; i < N; i++)
-            if (a.kind[i] == 0) {
-                const double e = a.eps_g ? a.eps_g[(int64_t)i * G + g] : a.eps[i];
-                ok = ok && e >= 0.0 && e <= 1.0;
-            }
+        bool ok = sp_eps_ok(a, g);
         int t_start = -1;
         if (a.start_tuple) {
             t_start = a.start[g];
             ok = ok && t_start >= 0 && t_start < T;
         }
         if (!ok) {                                       // block-uniform: this game is not solved
-            if (tid == 0) {
-                a.iters[g] = -1;
-                a.change[g] = 0.0;
-                a.mass[g] = 0.0;
-                a.samp_price[g] = 0.0;
-                a.agree[g] = 0.0;
-            }
-            if (tid < N) {
-                a.samp_reward[(int64_t)tid * G + g] = 0.0;
-                a.samp_action[(int64_t)tid * G + g] = 0.0;
-            }
-            if (a.pi)
-                for (int t = tid; t < T; t += kSpBlock) a.pi[g * T + t] = 0.0;
+            chain_unsolved(a.iters, a.change, a.mass, a.samp_price, a.samp_reward, a.samp_action, a.pi, g, G, N, T, tid, kSpBlock);
+            if (tid == 0) a.agree[g] = 0.0;
             continue;
         }
         __syncthreads();                                 // the game before is read to its end; the grouping is staged
 
         // ---- the game's rows and constants
-        if (tid < N) {
-            double lo = 0.0, hi = 0.0;
-            if (a.kind[tid] == 0) {
-                const double e = a.eps_g ? a.eps_g[(int64_t)tid * G + g] : a.eps[tid];
-                lo = __ddiv_rn(e, (double)a.n_actions[tid]);
-                hi = __dadd_rn(__dsub_rn(1.0, e), lo);
-            }
-            cst->lo[tid] = lo;
-            cst->hi[tid] = hi;
-        }
-        for (int i = 0; i < N; i++) {
-            const int A = a.n_actions[i];
-            if (a.kind[i] == 0) {
-                uint16_t* rq = reinterpret_cast<uint16_t*>(s_mem + a.o_row[i]);
-                const uint16_t* __restrict__ src = a.dpolicy + (g * N + i) * D;
-                for (int d = tid; d < D; d += kSpBlock) rq[d] = (uint16_t)min((int)src[d], A - 1);
-            } else {
-                float* rf = reinterpret_cast<float*>(s_mem + a.o_row[i]);
-                const int n = D * A;
-                const float* __restrict__ src = a.prob[i] + g * n;
-                for (int j = tid; j < n; j += kSpBlock) rf[j] = src[j];
-            }
-        }
+        sp_stage_game<1>(a, s_mem, cst, g, tid);
         __syncthreads();
-        for (int d = tid; d < D; d += kSpBlock) {
-            double z = 1.0;
-            for (int i = 0; i < N; i++) {
-                double S = 1.0;
-                if (a.kind[i] != 0) {
-                    const int A = a.n_actions[i];
-                    const float* rf = reinterpret_cast<const float*>(s_mem + a.o_row[i]) + d * A;
-                    S = 0.0;
-                    for (int k = 0; k < A; k++) S = __dadd_rn(S, (double)rf[k]);
-                }
-                z = i == 0 ? S : __dmul_rn(z, S);
-            }
-            Z[d] = z;
-        }
+        sp_normaliser(a, s_mem, Z, tid);
         const double unif = __ddiv_rn(1.0, (double)T);
         for (int t = tid; t < T; t += kSpBlock) ma[t] = a.start_tuple ? (t == t_start ? 1.0 : 0.0) : unif;
         __syncthreads();
@@ -120,43 +72,12 @@ __device__ __forceinline__ void sp_block(const SpArgs& a, unsigned char* s_mem, 
             __syncthreads();
             double c = 0.0;
             for (int t = tid; t < T; t += kSpBlock) {
-                int off[MAXN];                           // where this tuple's action sits in a row of agent i
-#pragma unroll
-                for (int i = 0; i < MAXN; i++) off[i] = i < N ? (t / a.tstride[i]) % a.n_actions[i] : 0;
-                double s = 0.0;
-                for (int d = 0; d < D; d++) {
-                    const double w = W[d];
-                    if (w == 0.0) continue;              // no mass at this price: the terms are +0.0
-                    double term = w;
-#pragma unroll
-                    for (int i = 0; i < MAXN; i++) {
-                        if (i >= N) break;
-                        double p;
-                        if (a.kind[i] == 0) {
-                            const uint16_t* rq = reinterpret_cast<const uint16_t*>(s_mem + a.o_row[i]);
-                            p = (int)rq[d] == off[i] ? cst->hi[i] : cst->lo[i];
-                        } else {
-                            const float* rf = reinterpret_cast<const float*>(s_mem + a.o_row[i]);
-                            p = (double)rf[d * a.n_actions[i] + off[i]];
-                        }
-                        term = __dmul_rn(term, p);
-                    }
-                    s = __dadd_rn(s, term);
-                }
-                const double v = __dadd_rn(__dmul_rn(0.5, mo[t]), __dmul_rn(0.5, s));
-                mn[t] = v;
-                c = fmax(c, fabs(__dsub_rn(v, mo[t])));
+                int off[MAXN];
+                sp_offsets<MAXN>(a, t, off);
+                const double s = sp_price_sum<MAXN>(a, s_mem, cst, W, off);
+                mn[t] = chain_lazy(mo[t], s, c);
             }
-            prod[tid] = c;
-            __syncthreads();
-            if (tid < 16) {
-                double cc = prod[tid * 16];
-                for (int k = 1; k < 16; k++) cc = fmax(cc, prod[tid * 16 + k]);
-                cst->red[tid] = cc;
-            }
-            __syncthreads();
-            c = cst->red[0];
-            for (int k = 1; k < 16; k++) c = fmax(c, cst->red[k]);
+            c = sp_block_max(prod, cst, c, tid);
             double* tm = mo; mo = mn; mn = tm;
             it++;
             chg = c;
@@ -167,21 +88,7 @@ __device__ __forceinline__ void sp_block(const SpArgs& a, unsigned char* s_mem, 
         // ---- the outputs, from the last iterate
         sp_weights(a, mo, first, perm, Z, W, tid);
         __syncthreads();
-        for (int d = tid; d < D; d += kSpBlock) {        // agree's terms, parked in the dead iterate (D <= T)
-            double term = W[d];
-            for (int i = 0; i < N; i++) {
-                const int A = a.n_actions[i];
-                double p;
-                if (a.kind[i] == 0) {
-                    p = cst->hi[i];
-                } else {
-                    const int gi = min((int)a.dpolicy[(g * N + i) * D + d], A - 1);
-                    p = (double)(reinterpret_cast<const float*>(s_mem + a.o_row[i])[d * A + gi]);
-                }
-                term = __dmul_rn(term, p);
-            }
-            mn[d] = term;
-        }
+        sp_agree_terms(a, s_mem, cst, W, mn, g, tid);    // parked in the dead iterate (D <= T)
         if (a.pi)
             for (int t = tid; t < T; t += kSpBlock) a.pi[g * T + t] = mo[t];
         double acc = 0.0;
@@ -197,28 +104,13 @@ __device__ __forceinline__ void sp_block(const SpArgs& a, unsigned char* s_mem, 
                 prod[(1 + 2 * N) * 64 + tid] = __dmul_rn(m, a.price[t]);
             }
             __syncthreads();
-            const int n = min(64, T - t0);
-            if (tid < n_out) {
-                const double* pr = prod + tid * 64;
-                for (int kk = 0; kk < n; kk++) acc = __dadd_rn(acc, pr[kk]);
-            } else if (tid == 64 && t0 == 0) {
+            acc = chain_read_back(prod, n_out, min(64, T - t0), acc, tid);
+            if (tid == 64 && t0 == 0)
                 for (int d = 0; d < D; d++) acc = __dadd_rn(acc, mn[d]);
-            }
             __syncthreads();
         }
-        if (tid == 0) {
-            a.iters[g] = it;
-            a.change[g] = chg;
-            a.mass[g] = acc;
-        } else if (tid <= N) {
-            a.samp_reward[(int64_t)(tid - 1) * G + g] = acc;
-        } else if (tid <= 2 * N) {
-            a.samp_action[(int64_t)(tid - 1 - N) * G + g] = acc;
-        } else if (tid == 2 * N + 1) {
-            a.samp_price[g] = acc;
-        } else if (tid == 64) {
-            a.agree[g] = acc;
-        }
+        chain_store(a.iters, a.change, a.mass, a.samp_price, a.samp_reward, a.samp_action, g, G, N, tid, it, chg, acc);
+        if (tid == 64) a.agree[g] = acc;
     }
 }
 

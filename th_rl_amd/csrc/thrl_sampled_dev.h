@@ -1,10 +1,12 @@
 // thrl_sampled_dev.h -- the device functions k_sp_chain (thrl_sampled.hip) and k_spn_chain (thrl_sampled_noise.hip)
 // share: the per-game constants, the staging of the distinct-price rows with their normaliser Z(d), the M / W pass, the
-// ordered sum over the distinct prices for one output tuple and the block's maximum.  Everything sits in namespace thrl's
+// ordered sum over the distinct prices for one output tuple and the block's maximum.  What all four chain kernels share
+// (the unsolved outputs, the lazy update, the read-back and the final store) is thrl_chain_dev.h's.  Everything sits in namespace thrl's
 // anonymous namespace, once per including file; with THRL_SP_HOST_BUILD the host harness supplies __device__, __syncthreads() and
 // the rounded operations.
 #pragma once
 #include "thrl_sampled.h"
+#include "thrl_chain_dev.h"
 
 namespace thrl {
 
@@ -37,7 +39,10 @@ __device__ __forceinline__ bool sp_eps_ok(const SpArgs& a, int64_t g) {
     return ok;
 }
 
-// the game's constants and its rows at the distinct prices; the caller synchronises before it reads them
+// the game's constants and its rows at the distinct prices; the caller synchronises before it reads them.  UNROLL is the
+// QTable rows' copy's: it runs once per game, but its registers count.  k_sp_chain keeps it rolled (the compiler's own
+// choice costs it six registers and a wave per SIMD); k_spn_chain<8>, which has none to spare, takes scratch unless it is 2
+template <int UNROLL>
 __device__ __forceinline__ void sp_stage_game(const SpArgs& a, unsigned char* s_mem, SpCst* cst, int64_t g, int tid) {
     const int N = a.N, G = a.G, D = a.D;
     if (tid < N) {
@@ -55,6 +60,7 @@ __device__ __forceinline__ void sp_stage_game(const SpArgs& a, unsigned char* s_
         if (a.kind[i] == 0) {
             uint16_t* rq = reinterpret_cast<uint16_t*>(s_mem + a.o_row[i]);
             const uint16_t* __restrict__ src = a.dpolicy + (g * N + i) * D;
+#pragma unroll UNROLL
             for (int d = tid; d < D; d += kSpBlock) rq[d] = (uint16_t)min((int)src[d], A - 1);
         } else {
             float* rf = reinterpret_cast<float*>(s_mem + a.o_row[i]);

@@ -221,25 +221,14 @@ __device__ __forceinline__ void spn_block(const SpnArgs& a, unsigned char* s_mem
             ok = ok && t_start >= 0 && t_start < T;
         }
         if (!ok) {                                       // block-uniform: this game is not solved
-            if (tid == 0) {
-                sa.iters[g] = -1;
-                sa.change[g] = 0.0;
-                sa.mass[g] = 0.0;
-                sa.samp_price[g] = 0.0;
-                sa.agree[g] = 0.0;
-            }
-            if (tid < N) {
-                sa.samp_reward[(int64_t)tid * G + g] = 0.0;
-                sa.samp_action[(int64_t)tid * G + g] = 0.0;
-            }
-            if (sa.pi)
-                for (int t = tid; t < T; t += kSpBlock) sa.pi[g * T + t] = 0.0;
+            chain_unsolved(sa.iters, sa.change, sa.mass, sa.samp_price, sa.samp_reward, sa.samp_action, sa.pi, g, G, N, T, tid, kSpBlock);
+            if (tid == 0) sa.agree[g] = 0.0;
             continue;
         }
         __syncthreads();                                 // the game before is read to its end; the grouping is staged
 
         // ---- the game's rows and constants; the QTable agents' entries at the nodes
-        sp_stage_game(sa, s_mem, cst, g, tid);
+        sp_stage_game<2>(sa, s_mem, cst, g, tid);
         for (int i = 0; i < N; i++)
             if (sa.kind[i] == 0) {
                 uint16_t* nq = reinterpret_cast<uint16_t*>(s_mem + a.o_nrow[i]);
@@ -274,9 +263,7 @@ __device__ __forceinline__ void spn_block(const SpnArgs& a, unsigned char* s_mem
                 sp_offsets<MAXN>(sa, t, off);
                 const double sd = sp_price_sum<MAXN>(sa, s_mem, cst, W, off);
                 const double s = __dadd_rn(__dmul_rn(q, sd), __dmul_rn(p, mn[t]));
-                const double v = __dadd_rn(__dmul_rn(0.5, mo[t]), __dmul_rn(0.5, s));
-                mn[t] = v;
-                c = fmax(c, fabs(__dsub_rn(v, mo[t])));
+                mn[t] = chain_lazy(mo[t], s, c);
             }
             c = sp_block_max(prod, cst, c, tid);
             double* tm = mo; mo = mn; mn = tm;
@@ -308,11 +295,8 @@ __device__ __forceinline__ void spn_block(const SpnArgs& a, unsigned char* s_mem
                 prod[(1 + 2 * N) * 64 + tid] = __dmul_rn(m, __dadd_rn(__dmul_rn(q, sa.price[t]), __dmul_rn(p, a.noise_price[t])));
             }
             __syncthreads();
-            const int n = min(64, T - t0);
-            if (tid < n_out) {
-                const double* pr = prod + tid * 64;
-                for (int kk = 0; kk < n; kk++) acc = __dadd_rn(acc, pr[kk]);
-            } else if (tid == 64 && t0 == 0) {
+            acc = chain_read_back(prod, n_out, min(64, T - t0), acc, tid);
+            if (tid == 64 && t0 == 0) {
                 for (int d = 0; d < D; d++) acc = __dadd_rn(acc, mn[d]);
             } else if (tid == 128 && t0 == 0) {
                 for (int j = 0; j < Jn; j++) acc = __dadd_rn(acc, V[j]);
@@ -320,19 +304,8 @@ __device__ __forceinline__ void spn_block(const SpnArgs& a, unsigned char* s_mem
             }
             __syncthreads();
         }
-        if (tid == 0) {
-            sa.iters[g] = it;
-            sa.change[g] = chg;
-            sa.mass[g] = acc;
-        } else if (tid <= N) {
-            sa.samp_reward[(int64_t)(tid - 1) * G + g] = acc;
-        } else if (tid <= 2 * N) {
-            sa.samp_action[(int64_t)(tid - 1 - N) * G + g] = acc;
-        } else if (tid == 2 * N + 1) {
-            sa.samp_price[g] = acc;
-        } else if (tid == 64) {
-            sa.agree[g] = __dadd_rn(__dmul_rn(q, acc), __dmul_rn(p, cst->red[0]));
-        }
+        chain_store(sa.iters, sa.change, sa.mass, sa.samp_price, sa.samp_reward, sa.samp_action, g, G, N, tid, it, chg, acc);
+        if (tid == 64) sa.agree[g] = __dadd_rn(__dmul_rn(q, acc), __dmul_rn(p, cst->red[0]));
     }
 }
 

@@ -12,6 +12,7 @@
 // output sums follow k_attractors: chunks of 64 cells, one lane per cell for the products, then one lane per output
 // reading them back from LDS in ascending k.
 #include "thrl_stationary.h"
+#include "thrl_chain_dev.h"
 
 namespace thrl {
 
@@ -84,18 +85,7 @@ __global__ void __launch_bounds__(64) k_stationary(const StatArgs a) {
             ok = ok && best < J;
         }
         if (!ok) {                                       // wave-uniform: this game is not solved
-            if (lane == 0) {
-                a.iters[g] = -1;
-                a.change[g] = 0.0;
-                a.mass[g] = 0.0;
-                a.stat_price[g] = 0.0;
-            }
-            if (lane < N) {
-                a.stat_reward[(int64_t)lane * G + g] = 0.0;
-                a.stat_action[(int64_t)lane * G + g] = 0.0;
-            }
-            if (a.pi)
-                for (int k = lane; k < J; k += 64) a.pi[g * J + k] = 0.0;
+            chain_unsolved(a.iters, a.change, a.mass, a.stat_price, a.stat_reward, a.stat_action, a.pi, g, G, N, J, lane, 64);
             __syncthreads();
             continue;
         }
@@ -126,14 +116,8 @@ __global__ void __launch_bounds__(64) k_stationary(const StatArgs a) {
                     if (P0 != 0.0) s0 = __dadd_rn(s0, __dmul_rn(m, P0));
                     if (P1 != 0.0) s1 = __dadd_rn(s1, __dmul_rn(m, P1));
                 }
-                const double v0 = __dadd_rn(__dmul_rn(0.5, mo[k0]), __dmul_rn(0.5, s0));
-                mn[k0] = v0;
-                c = fmax(c, fabs(__dsub_rn(v0, mo[k0])));
-                if (k1 < J) {
-                    const double v1 = __dadd_rn(__dmul_rn(0.5, mo[k1]), __dmul_rn(0.5, s1));
-                    mn[k1] = v1;
-                    c = fmax(c, fabs(__dsub_rn(v1, mo[k1])));
-                }
+                mn[k0] = chain_lazy(mo[k0], s0, c);
+                if (k1 < J) mn[k1] = chain_lazy(mo[k1], s1, c);
             }
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) c = fmax(c, __shfl_xor(c, m));
@@ -170,23 +154,10 @@ __global__ void __launch_bounds__(64) k_stationary(const StatArgs a) {
             }
             __syncthreads();
             const int n = min(64, J - k0);
-            if (lane < n_out) {
-                const double* pr = prod + lane * 64;
-                for (int kk = 0; kk < n; kk++) acc = __dadd_rn(acc, pr[kk]);
-            }
+            acc = chain_read_back(prod, n_out, n, acc, lane);
             __syncthreads();
         }
-        if (lane == 0) {
-            a.iters[g] = it;
-            a.change[g] = chg;
-            a.mass[g] = acc;
-        } else if (lane <= N) {
-            a.stat_reward[(int64_t)(lane - 1) * G + g] = acc;
-        } else if (lane <= 2 * N) {
-            a.stat_action[(int64_t)(lane - 1 - N) * G + g] = acc;
-        } else if (lane == 2 * N + 1) {
-            a.stat_price[g] = acc;
-        }
+        chain_store(a.iters, a.change, a.mass, a.stat_price, a.stat_reward, a.stat_action, g, G, N, lane, it, chg, acc);
         __syncthreads();                                 // this game's LDS reads before the next game's writes
     }
 }

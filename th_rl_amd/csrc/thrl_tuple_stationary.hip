@@ -17,6 +17,7 @@
 // k_ts_switch: one wavefront per game: the pairs of adjacent cells on which a network's entry differs, counted by
 //   ballot, their widths added by lane 0 in ascending k.
 #include "thrl_tuple_stationary.h"
+#include "thrl_chain_dev.h"
 
 namespace thrl {
 
@@ -88,18 +89,7 @@ __global__ void __launch_bounds__(kTsBlock) k_ts_chain(const TsArgs a) {
             ok = ok && t_start >= 0 && t_start < T;
         }
         if (!ok) {                                       // block-uniform: this game is not solved
-            if (tid == 0) {
-                a.iters[g] = -1;
-                a.change[g] = 0.0;
-                a.mass[g] = 0.0;
-                a.stat_price[g] = 0.0;
-            }
-            if (tid < N) {
-                a.stat_reward[(int64_t)tid * G + g] = 0.0;
-                a.stat_action[(int64_t)tid * G + g] = 0.0;
-            }
-            if (a.pi)
-                for (int t = tid; t < T; t += kTsBlock) a.pi[g * T + t] = 0.0;
+            chain_unsolved(a.iters, a.change, a.mass, a.stat_price, a.stat_reward, a.stat_action, a.pi, g, G, N, T, tid, kTsBlock);
             continue;
         }
 
@@ -153,9 +143,7 @@ __global__ void __launch_bounds__(kTsBlock) k_ts_chain(const TsArgs a) {
                 e = firstk[t + 1];
                 for (int s = firstk[t]; s < e; s++) nn = __dadd_rn(nn, nu[permk[s]]);
                 const double sv = __dadd_rn(__dmul_rn(q, d), __dmul_rn(p, nn));
-                const double v = __dadd_rn(__dmul_rn(0.5, mo[t]), __dmul_rn(0.5, sv));
-                mn[t] = v;
-                c = fmax(c, fabs(__dsub_rn(v, mo[t])));
+                mn[t] = chain_lazy(mo[t], sv, c);
             }
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) c = fmax(c, __shfl_xor(c, m));
@@ -187,23 +175,10 @@ __global__ void __launch_bounds__(kTsBlock) k_ts_chain(const TsArgs a) {
             }
             __syncthreads();
             const int n = min(64, T - t0);
-            if (tid < n_out) {
-                const double* pr = prod + tid * 64;
-                for (int kk = 0; kk < n; kk++) acc = __dadd_rn(acc, pr[kk]);
-            }
+            acc = chain_read_back(prod, n_out, n, acc, tid);
             __syncthreads();
         }
-        if (tid == 0) {
-            a.iters[g] = it;
-            a.change[g] = chg;
-            a.mass[g] = acc;
-        } else if (tid <= N) {
-            a.stat_reward[(int64_t)(tid - 1) * G + g] = acc;
-        } else if (tid <= 2 * N) {
-            a.stat_action[(int64_t)(tid - 1 - N) * G + g] = acc;
-        } else if (tid == 2 * N + 1) {
-            a.stat_price[g] = acc;
-        }
+        chain_store(a.iters, a.change, a.mass, a.stat_price, a.stat_reward, a.stat_action, g, G, N, tid, it, chg, acc);
     }
 }
 

@@ -125,8 +125,7 @@ def run(batch, deviator=0, steps=32, dev_len=1, action="best_response", horizon=
         a.state0 = s0.data_ptr()
         gam = batch.sweep.get("gamma") if getattr(batch, "sweep", None) else None
         a.sweep_gamma = gam.data_ptr() if gam is not None else None
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        an.bind(a, out)
         want = bool(rows) or group_stats is not None
         chunk = max(1, min(K, int(budget) // (8 * N * G))) if want else K
         st = group_stats.zeros(K, dev) if group_stats is not None else None
@@ -152,7 +151,7 @@ def run(batch, deviator=0, steps=32, dev_len=1, action="best_response", horizon=
             if b0 >= K or not want:
                 break
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["horizon"] = H
         if rows:
             res["reward_rows"] = np.concatenate(host_r, axis=0)

@@ -158,22 +158,16 @@ def run(batch, agents=None, state0=None, policies=False, tol=0.0, q=None):
             sel = gam[ag]
             if not bool(((sel >= 0.0) & (sel < 1.0)).all()):
                 raise ThrlError("equilibrium: the per-game sweep gamma must lie in [0, 1)")
-        out = {"mu": torch.zeros((G,), dtype=torch.int32, device=dev),
-               "lam": torch.zeros((G,), dtype=torch.int32, device=dev)}
-        out.update({f: torch.zeros((N, G), dtype=torch.int32, device=dev) for f in INT_FIELDS})
-        out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in FLOAT_FIELDS})
-        if policies:
-            out["br_policy"] = torch.zeros((N, G, S), dtype=torch.int16, device=dev)
-            out["v_opt"] = torch.zeros((N, G, S), dtype=torch.float64, device=dev)
-            out["v_pi"] = torch.zeros((N, G, S), dtype=torch.float64, device=dev)
+        out = an.outputs(dev, (("mu", "lam"), (G,), "int32"), (INT_FIELDS, (N, G), "int32"), (FLOAT_FIELDS, (N, G), "float64"),
+                         (("br_policy",) if policies else (), (N, G, S), "int16"),
+                         (("v_opt", "v_pi") if policies else (), (N, G, S), "float64"))
         a.state0 = s0.data_ptr()
         a.sweep_gamma = gam.data_ptr() if gam is not None else None
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        an.bind(a, out)
         _lib.check(batch.L.thrl_equilibrium(ctypes.byref(batch.cfg), q.data_ptr(), ctypes.byref(a), batch._stream()),
                    "thrl_equilibrium")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
     if policies:
         res["br_policy"] = res["br_policy"].view(np.uint16)
     res["agents"] = ag
@@ -195,9 +189,7 @@ def run_noise(batch, agents=None, noise_prob=None, eval_tol=1e-12, max_sweeps=81
     from . import stationary as sn
     from .attractors import policy_entries
     N = batch.N
-    G = batch.G if n_games is None else int(n_games)
-    if not 1 <= G <= batch.G:
-        raise ThrlError("equilibrium_noise: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    G = an.games(batch, n_games, "equilibrium_noise")
     ag, mask = agents_mask(agents, N)
     dev = batch.device
     given = policy is not None
@@ -209,7 +201,6 @@ def run_noise(batch, agents=None, noise_prob=None, eval_tol=1e-12, max_sweeps=81
     if tabs is None:
         tabs = sn.tables(batch.config)
     J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
-    shapes = dict(cell_rows=(N, J), det_cell=(T,), band_lo=(T,), band=(T, W), noise_reward=(N, T))
     a = _lib.EquilibriumNoiseArgs()
     a.n_games, a.agents, a.n_cells, a.band_w = G, mask, J, W
     a.max_sweeps, a.eval_tol = int(max_sweeps), float(eval_tol)
@@ -238,13 +229,9 @@ def run_noise(batch, agents=None, noise_prob=None, eval_tol=1e-12, max_sweeps=81
                 raise ThrlError("equilibrium_noise: weights must be shaped %s, got %s" % ((G, J), tuple(pi.shape)))
         if not given:
             policy = torch.empty((G, P), dtype=torch.int16, device=dev)
-        keep = {}
-        for f, shape in shapes.items():
-            x = np.ascontiguousarray(tabs[f], np.float64 if f in ("band", "noise_reward") else np.int32)
-            if x.shape != shape:
-                raise ThrlError("equilibrium_noise: table %s has shape %s, expected %s" % (f, x.shape, shape))
-            keep[f] = torch.from_numpy(x).to(dev)
-            setattr(a, f, keep[f].data_ptr())
+        keep = an.bind_tables(a, tabs, [("cell_rows", (N, J), np.int32), ("det_cell", (T,), np.int32),
+                                        ("band_lo", (T,), np.int32), ("band", (T, W), np.float64),
+                                        ("noise_reward", (N, T), np.float64)], dev, "equilibrium_noise")
         if p_g is not None:
             a.noise_prob_g = p_g.data_ptr()
         else:
@@ -254,24 +241,20 @@ def run_noise(batch, agents=None, noise_prob=None, eval_tol=1e-12, max_sweeps=81
             gam = gam[:, :G].contiguous()
             a.sweep_gamma = gam.data_ptr()
         a.policy = policy.data_ptr()
-        out = {f: torch.zeros((N, G), dtype=torch.int32, device=dev) for f in NOISE_INT}
-        out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in NOISE_FLOAT})
         if pi is not None:
             a.weights = pi.data_ptr()
-            out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in NOISE_WEIGHTED})
-        if policies:
-            out["br_policy"] = torch.zeros((N, G, J), dtype=torch.int16, device=dev)
-            out["v_opt"] = torch.zeros((N, G, J), dtype=torch.float64, device=dev)
-            out["v_pi"] = torch.zeros((N, G, J), dtype=torch.float64, device=dev)
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        out = an.outputs(dev, (NOISE_INT, (N, G), "int32"), (NOISE_FLOAT, (N, G), "float64"),
+                         (NOISE_WEIGHTED if pi is not None else (), (N, G), "float64"),
+                         (("br_policy",) if policies else (), (N, G, J), "int16"),
+                         (("v_opt", "v_pi") if policies else (), (N, G, J), "float64"))
+        an.bind(a, out)
         rc = batch.L.thrl_equilibrium_noise(ctypes.byref(batch.cfg), None if given else q.data_ptr(), ctypes.byref(a),
                                             batch._stream())
         if nt.value >= 0 and nt.value != T:
             raise ThrlError("equilibrium_noise: the tables hold %d action tuples, the batch's config has %d" % (T, nt.value))
         _lib.check(rc, "thrl_equilibrium_noise")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["noise_prob"] = np.full(G, p, np.float64) if p_g is None else p_g.cpu().numpy()
     if policies:
         res["br_policy"] = res["br_policy"].view(np.uint16)

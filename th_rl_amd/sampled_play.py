@@ -81,28 +81,15 @@ def parse_options(opt, config):
         out["epsilon"] = [_check_eps(x, name + ".epsilon") for x in e]
     elif e != "current":
         out["epsilon"] = _check_eps(e, name + ".epsilon")
-    starts = STARTS if noise is None else NOISE_STARTS
-    if out["start"] not in starts:
-        raise ValueError("%s.start must be one of %s, got %r" % (name, starts, out["start"]))
-    if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float)) or not out["tol"] >= 0.0:
-        raise ValueError("%s.tol must be a number >= 0, got %r" % (name, out["tol"]))
-    out["tol"] = float(out["tol"])
-    if isinstance(out["max_iters"], bool) or not isinstance(out["max_iters"], int) \
-            or not 1 <= out["max_iters"] <= _lib.STAT_MAX_ITERS:
-        raise ValueError("%s.max_iters must be an integer in [1, %d], got %r" % (name, _lib.STAT_MAX_ITERS, out["max_iters"]))
-    if not isinstance(out["pi"], bool):
-        raise ValueError("%s.pi must be true or false, got %r" % (name, out["pi"]))
+    an.chain_options(out, name, STARTS if noise is None else NOISE_STARTS)
     ws = working_set(config)
     if not ws["fits"]:
         raise ValueError("%s: a game's working set is %d bytes (T=%d, D=%d), a CU's LDS holds %d"
                          % (name, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
     if noise is not None:
         from . import tuple_stationary as ts
-        if noise["noise_prob"] is None:     # the run's own noise: refuse a noise-free run before training
-            env = dict(_lib.ENV_DEFAULTS, **config["environment"])
-            sweep = config.get("training", {}).get("sweep") or {}
-            if float(env["noise_prob"]) == 0.0 and "noise_prob" not in sweep:
-                raise ValueError("%s.noise: the environment has noise_prob = 0: give the noise_prob to analyse" % name)
+        if noise["noise_prob"] is None:
+            an.check_own_noise(config, name + ".noise")
         else:
             noise["noise_prob"] = _check_eps(noise["noise_prob"], name + ".noise.noise_prob")
         noise["resolution"] = ts._check_resolution(noise["resolution"], name + ".noise.resolution")
@@ -191,9 +178,9 @@ def noise_tables(config, resolution=NOISE_DEFAULTS["resolution"], tabs=None):
     out = dict(tables(config) if tabs is None else tabs)
     Jn = n_nodes_of(config, resolution)
     c = ts.cuts(config, resolution)
-    geo = ts.noise_geometry(config, tp.tables(config), c)
+    geo = sn.noise_geometry(config, tp.tables(config), c)
     nn = np.concatenate([geo["z"][:, None], geo["length"]], axis=1) / geo["width"]
-    band_lo, band = ts.band_of(nn)
+    band_lo, band = sn.band_of(nn)
     nprice = np.ascontiguousarray(geo["noise_price"])
     out.update(xn=np.concatenate([[0.0], geo["cell_x"]]), node_w=np.concatenate([[0.0], geo["cell_w"]]), nn=nn,
                band_lo=band_lo, band=band, noise_price=nprice,
@@ -205,9 +192,7 @@ def noise_tables(config, resolution=NOISE_DEFAULTS["resolution"], tabs=None):
 
 # ---------------------------------------------------------------------------------------------- the device calls
 def _games(batch, n_games):
-    G = batch.G if n_games is None else int(n_games)
-    if not 1 <= G <= batch.G:
-        raise ThrlError("sampled_play: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    G = an.games(batch, n_games, "sampled_play")
     if not getattr(batch, "initialized", True):
         raise ThrlError("sampled_play: call init_tables() or set_tables() first")
     return G
@@ -275,30 +260,8 @@ def resolve_epsilon(batch, epsilon, G):
 
 
 def resolve_noise(batch, noise_prob, G):
-    """(scalar or None, device float64 [G] or None) for run()'s noise_prob: None = the batch's per-game sweep array if it
-    has one, else the config's value (0 asks for an explicit one, as stationary.resolve_noise does); a number in [0, 1];
-    or an array / tensor [G] (device data: an entry outside [0, 1] refuses that game)."""
-    import torch
-    if noise_prob is None:
-        sw = getattr(batch, "sweep", None) or {}
-        if "noise_prob" in sw:
-            return None, sw["noise_prob"][:G].to(torch.float64).contiguous()
-        noise_prob = float(batch.cfg.noise_prob)
-        if noise_prob == 0.0:
-            raise ThrlError("sampled_play: the batch was configured without env noise (noise_prob = 0): pass the "
-                            "noise_prob to analyse explicitly")
-    if isinstance(noise_prob, torch.Tensor):
-        arr = noise_prob.to(device=batch.device, dtype=torch.float64).reshape(-1)[:G].contiguous()
-    elif np.ndim(noise_prob) > 0:
-        arr = torch.from_numpy(np.ascontiguousarray(np.asarray(noise_prob, np.float64).reshape(-1)[:G])).to(batch.device)
-    else:
-        p = float(noise_prob)
-        if not 0.0 <= p <= 1.0:
-            raise ThrlError("sampled_play: noise_prob=%r out of [0, 1]" % (noise_prob,))
-        return p, None
-    if arr.numel() != G:
-        raise ThrlError("sampled_play: noise_prob must hold %d values" % G)
-    return None, arr
+    """analysis.resolve_noise for run()'s noise_prob: a number lies in [0, 1]."""
+    return an.resolve_noise(batch, noise_prob, G, "sampled_play", zero_ok=True)
 
 
 def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None, tuple_policy=None,
@@ -402,21 +365,10 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
                     raise ThrlError("sampled_play: nprobs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
                 a.nprob[i] = pn.data_ptr()
             a.npolicy = npolicy.data_ptr()
-        keep = {}
-        for f, shape, dt in tab_list:
-            x = np.ascontiguousarray(tabs[f], dt)
-            if x.shape != shape:
-                raise ThrlError("sampled_play: table %s has shape %s, expected %s" % (f, x.shape, shape))
-            keep[f] = torch.from_numpy(x).to(dev)
-            setattr(a, f, keep[f].data_ptr())
+        keep = an.bind_tables(a, tabs, tab_list, dev, "sampled_play")
         t0 = None
         if given_start:
-            if isinstance(start, torch.Tensor):
-                t0 = start.to(device=dev, dtype=torch.int32).reshape(-1)[:G].contiguous()
-            else:
-                t0 = torch.from_numpy(np.ascontiguousarray(np.asarray(start).reshape(-1)[:G].astype(np.int32))).to(dev)
-            if t0.numel() != G:
-                raise ThrlError("sampled_play: start must hold %d tuples" % G)
+            t0 = an.start_tensor(start, G, dev, "sampled_play")
         elif start == "state":
             t0 = tp.start_tuples(batch.state[:G], tabs).to(torch.int32).contiguous()
         elif start == "reset":
@@ -424,19 +376,12 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
         if t0 is not None:
             a.flags = _lib.SP_START_TUPLE                # THRL_SPN_START_TUPLE has the same value
             a.start = t0.data_ptr()
-        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
-        out = {"iters": torch.zeros((G,), dtype=torch.int32, device=dev)}
-        out.update({f: f64(G) for f in GAME_FLOAT})
-        out.update({f: f64(N, G) for f in AGENT_FLOAT})
-        if pi:
-            out["pi"] = f64(G, T)
-        if noise:
-            out["max_jump"] = f64(G)
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        out = an.outputs(dev, (("iters",), (G,), "int32"), (GAME_FLOAT, (G,), "float64"), (AGENT_FLOAT, (N, G), "float64"),
+                         (("pi",) if pi else (), (G, T), "float64"), (("max_jump",) if noise else (), (G,), "float64"))
+        an.bind(a, out)
         _lib.check(getattr(batch.L, call)(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()), call)
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["epsilon"] = np.repeat(np.asarray(eps, np.float64)[:, None], G, axis=1) if eps_g is None else eps_g.cpu().numpy()
         if t0 is not None:
             res["start"] = t0.cpu().numpy()

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _lib
 from . import analysis as an
+from . import tuple_play as tp
 from ._lib import ThrlError
 from .analysis import QUANTILES, save_json  # noqa: F401  (sn.save_json stays a public name)
 from .attractors import encode64, policy_entries, starts
@@ -60,63 +61,75 @@ def parse_options(opt, config):
     out = an.options("stationary", opt, DEFAULTS, tables=True)
     if out["noise_prob"] is not None:
         out["noise_prob"] = check_prob(out["noise_prob"], "training.stationary.noise_prob")
-    else:       # the run's own noise: refuse a noise-free run before training, as the batch would after it
-        env = dict(_lib.ENV_DEFAULTS, **config["environment"])
-        sweep = config.get("training", {}).get("sweep") or {}
-        if float(env["noise_prob"]) == 0.0 and "noise_prob" not in sweep:
-            raise ValueError("training.stationary: the environment has noise_prob = 0: give the noise_prob to analyse")
-    if out["start"] not in STARTS:
-        raise ValueError("training.stationary.start must be one of %s, got %r" % (STARTS, out["start"]))
-    if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float)) or not out["tol"] >= 0.0:
-        raise ValueError("training.stationary.tol must be a number >= 0, got %r" % (out["tol"],))
-    out["tol"] = float(out["tol"])
-    if isinstance(out["max_iters"], bool) or not isinstance(out["max_iters"], int) \
-            or not 1 <= out["max_iters"] <= _lib.STAT_MAX_ITERS:
-        raise ValueError("training.stationary.max_iters must be an integer in [1, %d], got %r"
-                         % (_lib.STAT_MAX_ITERS, out["max_iters"]))
-    if not isinstance(out["pi"], bool):
-        raise ValueError("training.stationary.pi must be true or false, got %r" % (out["pi"],))
+    else:
+        an.check_own_noise(config, "training.stationary")
+    an.chain_options(out, "training.stationary", STARTS)
     return out
 
 
 # ---------------------------------------------------------------------------------------------- the per-config tables
-def cuts(config):
-    """c float64 [J + 1]: the ends of the cells of attractors.starts(config), cell k = [c[k], c[k + 1])."""
+def breakpoints(config):
+    """The arrays the price axis is cut at: [0, a] and, per QTable agent, its encode breakpoints inside (0, a)."""
     env = dict(_lib.ENV_DEFAULTS, **config["environment"])
     a = float(env["a"])
     parts = [np.array([0.0, a])]
     for ag in config["agents"]:
+        if ag.get("name", "QTable") != "QTable":
+            continue
         p = dict(_lib.QTABLE_DEFAULTS, **ag)
         n, ms = int(p["states"]), float(p["max_state"])
         b = (np.arange(n, dtype=np.float64) + 0.5) * ms / float(n)
         parts.append(b[(b > 0.0) & (b < a)])
-    return np.unique(np.concatenate(parts))
+    return parts
 
 
-def tuple_steps(config):
+def cuts(config):
+    """c float64 [J + 1]: the ends of the cells of attractors.starts(config), cell k = [c[k], c[k + 1])."""
+    return np.unique(np.concatenate(breakpoints(config)))
+
+
+def tuple_steps(config, t=None):
     """The env step of every action tuple (agent 0 slowest), operation for operation the device's scale_action and
-    env_step: (quantity [N, T] = ratio * scaled action, u [T] = the amount subtracted from the intercept, price [T] =
-    the noise-free price, scaled [N, T])."""
+    env_step, from tuple_play.tables(config) (t): (quantity [N, T] = ratio * scaled action, u [T] = the amount subtracted
+    from the intercept, price [T] = the noise-free price, scaled [N, T])."""
+    t = tp.tables(config) if t is None else t
     env = dict(_lib.ENV_DEFAULTS, **config["environment"])
     a, b = float(env["a"]), float(env["b"])
-    ps = [dict(_lib.QTABLE_DEFAULTS, **ag) for ag in config["agents"]]
-    nact = [int(p["actions"]) for p in ps]
-    idx = np.unravel_index(np.arange(int(np.prod(nact))), nact)
-    ratio = a / b
-    scaled, quantity = [], []
-    total = np.zeros(idx[0].shape, np.float64)
-    for i, p in enumerate(ps):
-        lo, hi = float(p["action_range"][0]), float(p["action_range"][1])
-        x = idx[i].astype(np.float64) / (float(nact[i]) - 1.0)
-        x = x * (hi - lo)
-        x = x + lo
-        scaled.append(x)
-        quantity.append(ratio * x)
-        total = total + quantity[-1]
-    u = b * total
-    price = a - u
-    price = np.where(price > 0.0, price, 0.0)
-    return np.stack(quantity), u, price, np.stack(scaled)
+    quantity = (a / b) * t["scaled"]
+    total = np.zeros(t["T"], np.float64)
+    for qn in quantity:
+        total = total + qn
+    return quantity, b * total, t["price"], t["scaled"]
+
+
+def noise_geometry(config, t, c):
+    """What the redrawn price of every tuple covers of the cells with the ends c: dict(length [T, J], the length of
+    [0.7 a - u(t), a - u(t)) inside each cell; z [T], the length clipped to price 0; width = 0.3 a; noise_price [T];
+    quantity [N, T]; cell_w and cell_x [J]).  tables() and tuple_stationary.tables() lump z into cell 0;
+    sampled_play.noise_tables gives it a node of its own."""
+    quantity, u, _, _ = tuple_steps(config, t)
+    a = float(dict(_lib.ENV_DEFAULTS, **config["environment"])["a"])
+    w = (c[1:] - c[:-1]) / a
+    x = 0.5 * (c[:-1] + c[1:])
+    noise_lo = a * 0.7
+    lo, hi, width = noise_lo - u, a - u, a - noise_lo
+    length = np.maximum(0.0, np.minimum(c[None, 1:], hi[:, None]) - np.maximum(c[None, :-1], lo[:, None]))
+    z = np.maximum(0.0, -lo) - np.maximum(0.0, -hi)
+    nprice = np.where(lo >= 0.0, (lo + hi) / 2.0, np.where(hi <= 0.0, 0.0, hi * hi / (2.0 * width)))
+    return dict(length=length, z=z, width=width, noise_price=nprice, quantity=quantity, cell_w=w, cell_x=x, u=u, a=a)
+
+
+def band_of(n):
+    """(band_lo int32 [T], band [T, W]) of the weights n [T, J]: every row from its first to its last non-zero entry,
+    padded with zeros to the widest."""
+    T, J = n.shape
+    nz = n > 0.0
+    first = np.where(nz.any(axis=1), nz.argmax(axis=1), 0)
+    last = np.where(nz.any(axis=1), J - 1 - nz[:, ::-1].argmax(axis=1), 0)
+    W = int((last - first + 1).max())
+    pad = np.concatenate([n, np.zeros((T, W))], axis=1)
+    band = pad[np.arange(T)[:, None], first[:, None] + np.arange(W)[None, :]]
+    return first.astype(np.int32), np.ascontiguousarray(band, np.float64)
 
 
 def tables(config):
@@ -136,75 +149,41 @@ def tables(config):
     Ji = int(w.size)
     if c.size != Ji + 1:
         raise ValueError("stationary: %d cell ends for %d cells" % (c.size, Ji))
-    env = dict(_lib.ENV_DEFAULTS, **config["environment"])
-    a = float(env["a"])
     ps = [dict(_lib.QTABLE_DEFAULTS, **ag) for ag in config["agents"]]
-    quantity, u, price, _ = tuple_steps(config)
-    T = int(u.size)
+    t = tp.tables(config)
+    price, T = t["price"], int(t["T"])
     # det_cell: the cell with the row tuple of the noise-free price; a row tuple that no interval has becomes a point cell
     cell_of = {tuple(int(v) for v in rows[:, k]): k for k in range(Ji)}
     prow = np.stack([encode64(price, int(p["states"]), float(p["max_state"])) for p in ps])
     det = np.zeros(T, np.int32)
     points = []
-    for t in range(T):
-        key = tuple(int(v) for v in prow[:, t])
+    for k in range(T):
+        key = tuple(int(v) for v in prow[:, k])
         if key not in cell_of:
             cell_of[key] = Ji + len(points)
             points.append(key)
-        det[t] = cell_of[key]
+        det[k] = cell_of[key]
     J = Ji + len(points)
     if points:
         rows = np.concatenate([rows, np.array(points, np.int32).T], axis=1)
         w = np.concatenate([w, np.zeros(len(points))])
     if J > _lib.STAT_MAX_CELLS:
         raise ValueError("stationary: %d cells, at most %d" % (J, _lib.STAT_MAX_CELLS))
-    # band: where a redrawn intercept puts the price
-    noise_lo = a * 0.7
-    lo, hi, width = noise_lo - u, a - u, a - noise_lo
-    length = np.maximum(0.0, np.minimum(c[None, 1:], hi[:, None]) - np.maximum(c[None, :-1], lo[:, None]))
-    z = np.maximum(0.0, -lo) - np.maximum(0.0, -hi)
-    length[:, 0] = length[:, 0] + z
-    n = np.concatenate([length / width, np.zeros((T, J - Ji))], axis=1)       # no intercept lands on a point cell
-    nz = n > 0.0
-    first = np.where(nz.any(axis=1), nz.argmax(axis=1), 0)
-    last = np.where(nz.any(axis=1), J - 1 - nz[:, ::-1].argmax(axis=1), 0)
-    W = int((last - first + 1).max())
-    pad = np.concatenate([n, np.zeros((T, W))], axis=1)
-    band = pad[np.arange(T)[:, None], first[:, None] + np.arange(W)[None, :]]
-    # the expected price and rewards under a redrawn intercept
-    nprice = np.where(lo >= 0.0, (lo + hi) / 2.0, np.where(hi <= 0.0, 0.0, hi * hi / (2.0 * width)))
+    # band: where a redrawn intercept puts the price; no intercept lands on a point cell
+    geo = noise_geometry(config, t, c)
+    length, nprice = geo["length"], geo["noise_price"]
+    length[:, 0] = length[:, 0] + geo["z"]
+    first, band = band_of(np.concatenate([length / geo["width"], np.zeros((T, J - Ji))], axis=1))
     return dict(cell_rows=np.ascontiguousarray(rows, np.int32), cell_w=np.ascontiguousarray(w, np.float64),
-                det_cell=det, band_lo=first.astype(np.int32), band=np.ascontiguousarray(band, np.float64),
-                noise_reward=np.ascontiguousarray(nprice[None, :] * quantity), noise_price=np.ascontiguousarray(nprice),
-                n_cells=J, n_intervals=Ji, n_tuples=T, band_w=W)
+                det_cell=det, band_lo=first, band=band,
+                noise_reward=np.ascontiguousarray(nprice[None, :] * geo["quantity"]), noise_price=np.ascontiguousarray(nprice),
+                n_cells=J, n_intervals=Ji, n_tuples=T, band_w=int(band.shape[1]))
 
 
 # ---------------------------------------------------------------------------------------------- the device call
 def resolve_noise(batch, noise_prob, G):
-    """(scalar or None, device [G] tensor or None) for GameBatch.stationary's noise_prob argument: None = the batch's
-    per-game sweep array if it has one, else the config's value (0 asks for an explicit one); a number; or an array /
-    tensor [G]."""
-    import torch
-    if noise_prob is None:
-        if "noise_prob" in batch.sweep:
-            return None, batch.sweep["noise_prob"][:G].contiguous()
-        p = float(batch.cfg.noise_prob)
-        if p == 0.0:
-            raise ThrlError("stationary: the batch was configured without env noise (noise_prob = 0): pass the "
-                            "noise_prob to analyse explicitly")
-        noise_prob = p
-    if isinstance(noise_prob, torch.Tensor):
-        arr = noise_prob.to(device=batch.device, dtype=torch.float64).reshape(-1)[:G].contiguous()
-    elif np.ndim(noise_prob) > 0:
-        arr = torch.from_numpy(np.ascontiguousarray(np.asarray(noise_prob, np.float64).reshape(-1)[:G])).to(batch.device)
-    else:
-        p = float(noise_prob)
-        if not 0.0 < p <= 1.0:
-            raise ThrlError("stationary: noise_prob=%r out of (0, 1]" % (noise_prob,))
-        return p, None
-    if arr.numel() != G:
-        raise ThrlError("stationary: noise_prob must hold %d values" % G)
-    return None, arr
+    """analysis.resolve_noise for GameBatch.stationary's noise_prob argument: a number lies in (0, 1]."""
+    return an.resolve_noise(batch, noise_prob, G, "stationary")
 
 
 def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters=8192, pi=False, q=None, policy=None,
@@ -214,9 +193,7 @@ def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters
     Returns a dict of numpy arrays."""
     import torch
     N = batch.N
-    G = batch.G if n_games is None else int(n_games)
-    if not 1 <= G <= batch.G:
-        raise ThrlError("stationary: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    G = an.games(batch, n_games, "stationary")
     if start not in STARTS:
         raise ThrlError("stationary: start must be one of %s, got %r" % (STARTS, start))
     dev = batch.device
@@ -229,8 +206,6 @@ def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters
     if tabs is None:
         tabs = tables(batch.config)
     J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
-    shapes = dict(cell_rows=(N, J), cell_w=(J,), det_cell=(T,), band_lo=(T,), band=(T, W), noise_reward=(N, T),
-                  noise_price=(T,))
     a = _lib.StationaryArgs()
     a.n_games, a.n_cells, a.band_w, a.max_iters, a.tol = G, J, W, int(max_iters), float(tol)
     a.flags = (_lib.STAT_POLICY_GIVEN if given else 0) | (_lib.STAT_START_STATE if start == "state" else 0)
@@ -238,13 +213,10 @@ def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters
     a.n_tuples = ctypes.pointer(nt)
     with torch.cuda.device(dev):
         p, p_g = resolve_noise(batch, noise_prob, G)
-        keep = {}
-        for f, shape in shapes.items():
-            x = np.ascontiguousarray(tabs[f], np.int32 if f in ("cell_rows", "det_cell", "band_lo") else np.float64)
-            if x.shape != shape:
-                raise ThrlError("stationary: table %s has shape %s, expected %s" % (f, x.shape, shape))
-            keep[f] = torch.from_numpy(x).to(dev)
-            setattr(a, f, keep[f].data_ptr())
+        keep = an.bind_tables(a, tabs, [("cell_rows", (N, J), np.int32), ("cell_w", (J,), np.float64),
+                                        ("det_cell", (T,), np.int32), ("band_lo", (T,), np.int32),
+                                        ("band", (T, W), np.float64), ("noise_reward", (N, T), np.float64),
+                                        ("noise_price", (T,), np.float64)], dev, "stationary")
         if p_g is not None:
             a.noise_prob_g = p_g.data_ptr()
         else:
@@ -255,21 +227,16 @@ def run(batch, noise_prob=None, start="reset", state0=None, tol=1e-12, max_iters
         if not given:
             policy = torch.empty((G, P), dtype=torch.int16, device=dev)
         a.policy = policy.data_ptr()
-        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
-        out = {"iters": torch.zeros((G,), dtype=torch.int32, device=dev)}
-        out.update({f: f64(G) for f in GAME_FLOAT})
-        out.update({f: f64(N, G) for f in AGENT_FLOAT})
-        if pi:
-            out["pi"] = f64(G, J)
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        out = an.outputs(dev, (("iters",), (G,), "int32"), (GAME_FLOAT, (G,), "float64"), (AGENT_FLOAT, (N, G), "float64"),
+                         (("pi",) if pi else (), (G, J), "float64"))
+        an.bind(a, out)
         rc = batch.L.thrl_stationary(ctypes.byref(batch.cfg), None if given else q.data_ptr(), ctypes.byref(a),
                                      batch._stream())
         if nt.value >= 0 and nt.value != T:
             raise ThrlError("stationary: the tables hold %d action tuples, the batch's config has %d" % (T, nt.value))
         _lib.check(rc, "thrl_stationary")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["noise_prob"] = np.full(G, p, np.float64) if p_g is None else p_g.cpu().numpy()
     res["n_cells"], res["max_iters"] = J, int(max_iters)
     return res

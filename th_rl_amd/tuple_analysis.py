@@ -257,8 +257,7 @@ def deviation(batch, deviator=0, steps=32, dev_len=1, action="best_response", ho
         a.start, a.tuple_policy, a.reward, a.scaled = t0.data_ptr(), tuple_policy.data_ptr(), d_rew.data_ptr(), d_sca.data_ptr()
         gam = _gamma(batch)
         a.sweep_gamma = gam.data_ptr() if gam is not None else None
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        an.bind(a, out)
         want = bool(rows) or group_stats is not None
         chunk = max(1, min(K, int(budget) // (8 * N * G))) if want else K
         st = group_stats.zeros(K, dev) if group_stats is not None else None
@@ -284,7 +283,7 @@ def deviation(batch, deviator=0, steps=32, dev_len=1, action="best_response", ho
             if b0 >= K or not want:
                 break
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["start"] = t0.cpu().numpy()
         res["horizon"] = H
         if rows:
@@ -313,22 +312,16 @@ def equilibrium(batch, agents=None, start=None, policies=False, tol=0.0, tuple_p
             sel = gam[ag]
             if not bool(((sel >= 0.0) & (sel < 1.0)).all()):
                 raise ThrlError("equilibrium: every solved agent's gamma must lie in [0, 1)")
-        out = {"mu": torch.zeros((G,), dtype=torch.int32, device=dev),
-               "lam": torch.zeros((G,), dtype=torch.int32, device=dev)}
-        out.update({f: torch.zeros((N, G), dtype=torch.int32, device=dev) for f in eq.INT_FIELDS})
-        out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in eq.FLOAT_FIELDS})
-        if policies:
-            out["br_policy"] = torch.zeros((N, G, T), dtype=torch.int16, device=dev)
-            out["v_opt"] = torch.zeros((N, G, T), dtype=torch.float64, device=dev)
-            out["v_pi"] = torch.zeros((N, G, T), dtype=torch.float64, device=dev)
+        out = an.outputs(dev, (("mu", "lam"), (G,), "int32"), (eq.INT_FIELDS, (N, G), "int32"),
+                         (eq.FLOAT_FIELDS, (N, G), "float64"), (("br_policy",) if policies else (), (N, G, T), "int16"),
+                         (("v_opt", "v_pi") if policies else (), (N, G, T), "float64"))
         a.start, a.tuple_policy, a.reward = t0.data_ptr(), tuple_policy.data_ptr(), d_rew.data_ptr()
         a.sweep_gamma = gam.data_ptr() if gam is not None else None
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        an.bind(a, out)
         _lib.check(batch.L.thrl_tuple_equilibrium(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
                    "thrl_tuple_equilibrium")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["start"] = t0.cpu().numpy()
     if policies:
         res["br_policy"] = res["br_policy"].view(np.uint16)
@@ -367,12 +360,11 @@ def attractors(batch, start=None, weights="uniform", policies=False, tuple_polic
             out["tuple_rep"] = torch.zeros((G, T), dtype=torch.int16, device=dev)
             out["tuple_mu"] = torch.zeros((G, T), dtype=torch.int16, device=dev)
         a.start, a.tuple_policy, a.reward, a.scaled = t0.data_ptr(), tuple_policy.data_ptr(), d_rew.data_ptr(), d_sca.data_ptr()
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        an.bind(a, out)
         _lib.check(batch.L.thrl_tuple_attractors(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
                    "thrl_tuple_attractors")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["start"] = t0.cpu().numpy()
     for f in TUPLE_FIELDS:
         if f in res:
@@ -395,9 +387,7 @@ def equilibrium_noise(batch, agents=None, noise_prob=None, resolution=NOISE_DEFA
     from . import stationary as sn
     from . import tuple_stationary as ts
     N = batch.N
-    G = batch.G if n_games is None else int(n_games)
-    if not 1 <= G <= batch.G:
-        raise ThrlError("greedy_equilibrium_noise: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    G = an.games(batch, n_games, "greedy_equilibrium_noise")
     ag, mask = eq.agents_mask(agents, N)
     if tabs is None:
         tabs = ts.tables(batch.config, resolution)
@@ -405,7 +395,6 @@ def equilibrium_noise(batch, agents=None, noise_prob=None, resolution=NOISE_DEFA
     dev = batch.device
     J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
     S = T + J
-    shapes = dict(reward=(N, T), band_lo=(T,), band=(T, W), noise_reward=(N, T))
     if tuple_policy is None:
         tuple_policy = tp.extract(batch, tabs)
     if not an.is_policy(tuple_policy, (batch.G, N, T), batch.state.device):
@@ -437,13 +426,9 @@ def equilibrium_noise(batch, agents=None, noise_prob=None, resolution=NOISE_DEFA
                 pi = torch.from_numpy(np.ascontiguousarray(np.asarray(weights, np.float64))).to(dev)
             if tuple(pi.shape) != (G, T):
                 raise ThrlError("greedy_equilibrium_noise: weights must be shaped %s, got %s" % ((G, T), tuple(pi.shape)))
-        keep = {}
-        for f, shape in shapes.items():
-            x = np.ascontiguousarray(tabs[f], np.int32 if f == "band_lo" else np.float64)
-            if x.shape != shape:
-                raise ThrlError("greedy_equilibrium_noise: table %s has shape %s, expected %s" % (f, x.shape, shape))
-            keep[f] = torch.from_numpy(x).to(dev)
-            setattr(a, f, keep[f].data_ptr())
+        keep = an.bind_tables(a, tabs, [("reward", (N, T), np.float64), ("band_lo", (T,), np.int32),
+                                        ("band", (T, W), np.float64), ("noise_reward", (N, T), np.float64)],
+                              dev, "greedy_equilibrium_noise")
         if p_g is not None:
             a.noise_prob_g = p_g.data_ptr()
         else:
@@ -453,21 +438,17 @@ def equilibrium_noise(batch, agents=None, noise_prob=None, resolution=NOISE_DEFA
             gam = gam[:, :G].contiguous()
             a.sweep_gamma = gam.data_ptr()
         a.tuple_policy, a.cell_policy = tuple_policy.data_ptr(), cell_policy.data_ptr()
-        out = {f: torch.zeros((N, G), dtype=torch.int32, device=dev) for f in NOISE_INT}
-        out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in NOISE_FLOAT})
         if pi is not None:
             a.pi = pi.data_ptr()
-            out.update({f: torch.zeros((N, G), dtype=torch.float64, device=dev) for f in NOISE_WEIGHTED})
-        if policies:
-            out["br_policy"] = torch.zeros((N, G, S), dtype=torch.int16, device=dev)
-            out["v_opt"] = torch.zeros((N, G, S), dtype=torch.float64, device=dev)
-            out["v_pi"] = torch.zeros((N, G, S), dtype=torch.float64, device=dev)
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        out = an.outputs(dev, (NOISE_INT, (N, G), "int32"), (NOISE_FLOAT, (N, G), "float64"),
+                         (NOISE_WEIGHTED if pi is not None else (), (N, G), "float64"),
+                         (("br_policy",) if policies else (), (N, G, S), "int16"),
+                         (("v_opt", "v_pi") if policies else (), (N, G, S), "float64"))
+        an.bind(a, out)
         _lib.check(batch.L.thrl_tuple_equilibrium_noise(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
                    "thrl_tuple_equilibrium_noise")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["noise_prob"] = np.full(G, p, np.float64) if p_g is None else p_g.cpu().numpy()
         if pi is not None:
             res["pi"] = pi.cpu().numpy()

@@ -259,8 +259,7 @@ def run(batch, seats=None, start=None, steps=0, rows=False, horizon=None, tuple_
                    "cycle_reward": torch.zeros((N, M), dtype=torch.float64, device=dev),
                    "cycle_action": torch.zeros((N, M), dtype=torch.float64, device=dev)}
             a.seat, a.start = seat.data_ptr(), t0.data_ptr()
-            for f, t in out.items():
-                setattr(a, f, t.data_ptr())
+            an.bind(a, out)
             rr_host, ra_host = [], []
             b0 = 0
             while True:

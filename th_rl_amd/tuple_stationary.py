@@ -53,21 +53,9 @@ def parse_options(opt, config):
     out = an.options("greedy_stationary", opt, DEFAULTS)
     if out["noise_prob"] is not None:
         out["noise_prob"] = sn.check_prob(out["noise_prob"], name + ".noise_prob")
-    else:       # the run's own noise: refuse a noise-free run before training, as the batch would after it
-        env = dict(_lib.ENV_DEFAULTS, **config["environment"])
-        sweep = config.get("training", {}).get("sweep") or {}
-        if float(env["noise_prob"]) == 0.0 and "noise_prob" not in sweep:
-            raise ValueError("%s: the environment has noise_prob = 0: give the noise_prob to analyse" % name)
-    if out["start"] not in STARTS:
-        raise ValueError("%s.start must be one of %s, got %r" % (name, STARTS, out["start"]))
-    if isinstance(out["tol"], bool) or not isinstance(out["tol"], (int, float)) or not out["tol"] >= 0.0:
-        raise ValueError("%s.tol must be a number >= 0, got %r" % (name, out["tol"]))
-    out["tol"] = float(out["tol"])
-    if isinstance(out["max_iters"], bool) or not isinstance(out["max_iters"], int) \
-            or not 1 <= out["max_iters"] <= _lib.STAT_MAX_ITERS:
-        raise ValueError("%s.max_iters must be an integer in [1, %d], got %r" % (name, _lib.STAT_MAX_ITERS, out["max_iters"]))
-    if not isinstance(out["pi"], bool):
-        raise ValueError("%s.pi must be true or false, got %r" % (name, out["pi"]))
+    else:
+        an.check_own_noise(config, name)
+    an.chain_options(out, name, STARTS)
     out["resolution"] = _check_resolution(out["resolution"], name + ".resolution")
     try:
         cuts(config, out["resolution"])          # more than MAX_CELLS cells: refused before training
@@ -83,16 +71,8 @@ def cuts(config, resolution):
     cuts so close that the midpoint between them rounds onto one of them (the same number reached by two roundings) are
     one cut: every midpoint lies strictly inside its cell."""
     resolution = _check_resolution(resolution, "resolution")
-    env = dict(_lib.ENV_DEFAULTS, **config["environment"])
-    a = float(env["a"])
-    parts = [np.array([0.0, a])]
-    for ag in config["agents"]:
-        if ag.get("name", "QTable") != "QTable":
-            continue
-        p = dict(_lib.QTABLE_DEFAULTS, **ag)
-        n, ms = int(p["states"]), float(p["max_state"])
-        b = (np.arange(n, dtype=np.float64) + 0.5) * ms / float(n)
-        parts.append(b[(b > 0.0) & (b < a)])
+    parts = sn.breakpoints(config)
+    a = float(parts[0][1])
     if resolution > 1:
         u = a * np.arange(1, resolution, dtype=np.float64) / float(resolution)
         parts.append(u[(u > 0.0) & (u < a)])
@@ -109,41 +89,7 @@ def cuts(config, resolution):
     return c
 
 
-def noise_geometry(config, t, c):
-    """What the redrawn price of every tuple covers of the cells with the ends c: dict(length [T, J], the length of
-    [0.7 a - u(t), a - u(t)) inside each cell; z [T], the length clipped to price 0; width = 0.3 a; noise_price [T];
-    quantity [N, T]; cell_w and cell_x [J]).  tables() lumps z into cell 0; sampled_play.noise_tables gives it a node of
-    its own."""
-    env = dict(_lib.ENV_DEFAULTS, **config["environment"])
-    a, b = float(env["a"]), float(env["b"])
-    # u(t): the amount env_step subtracts from the intercept, from tuple_play's quantities
-    ratio = a / b
-    quantity = ratio * t["scaled"]
-    total = np.zeros(t["T"], np.float64)
-    for qn in quantity:
-        total = total + qn
-    u = b * total
-    w = (c[1:] - c[:-1]) / a
-    x = 0.5 * (c[:-1] + c[1:])
-    noise_lo = a * 0.7
-    lo, hi, width = noise_lo - u, a - u, a - noise_lo
-    length = np.maximum(0.0, np.minimum(c[None, 1:], hi[:, None]) - np.maximum(c[None, :-1], lo[:, None]))
-    z = np.maximum(0.0, -lo) - np.maximum(0.0, -hi)
-    nprice = np.where(lo >= 0.0, (lo + hi) / 2.0, np.where(hi <= 0.0, 0.0, hi * hi / (2.0 * width)))
-    return dict(length=length, z=z, width=width, noise_price=nprice, quantity=quantity, cell_w=w, cell_x=x, u=u, a=a)
-
-
-def band_of(n):
-    """(band_lo int32 [T], band [T, W]) of the weights n [T, J]: every row from its first to its last non-zero entry,
-    padded with zeros to the widest."""
-    T, J = n.shape
-    nz = n > 0.0
-    first = np.where(nz.any(axis=1), nz.argmax(axis=1), 0)
-    last = np.where(nz.any(axis=1), J - 1 - nz[:, ::-1].argmax(axis=1), 0)
-    W = int((last - first + 1).max())
-    pad = np.concatenate([n, np.zeros((T, W))], axis=1)
-    band = pad[np.arange(T)[:, None], first[:, None] + np.arange(W)[None, :]]
-    return first.astype(np.int32), np.ascontiguousarray(band, np.float64)
+noise_geometry, band_of = sn.noise_geometry, sn.band_of     # stationary.py holds the one copy; the names stay here
 
 
 def tables(config, resolution=DEFAULTS["resolution"]):
@@ -178,9 +124,7 @@ def price_policy(batch, price, per_game=False, n_games=None):
     kinds = tp._kinds(batch)
     if not getattr(batch, "initialized", True):
         raise ThrlError("tuple_stationary: call init_tables() or set_tables() first")
-    G = batch.G if n_games is None else int(n_games)
-    if not 1 <= G <= batch.G:
-        raise ThrlError("tuple_stationary: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    G = an.games(batch, n_games, "tuple_stationary")
     dev = batch.device
     with torch.cuda.device(dev):
         if isinstance(price, torch.Tensor):
@@ -237,9 +181,7 @@ def run(batch, noise_prob=None, start="reset", resolution=DEFAULTS["resolution"]
     extracted here).  tabs: tables(batch.config, resolution).  Returns a dict of numpy arrays."""
     import torch
     N = batch.N
-    G = batch.G if n_games is None else int(n_games)
-    if not 1 <= G <= batch.G:
-        raise ThrlError("tuple_stationary: n_games=%r out of [1, %d]" % (n_games, batch.G))
+    G = an.games(batch, n_games, "tuple_stationary")
     given_start = not isinstance(start, str)
     if not given_start and start not in STARTS:
         raise ThrlError("tuple_stationary: start must be one of %s or an array of tuples, got %r" % (STARTS, start))
@@ -248,8 +190,6 @@ def run(batch, noise_prob=None, start="reset", resolution=DEFAULTS["resolution"]
     tp._batch_tables(batch, tabs)
     dev = batch.device
     J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
-    shapes = dict(cell_w=(J,), reward=(N, T), scaled=(N, T), price=(T,), band_lo=(T,), band=(T, W), noise_reward=(N, T),
-                  noise_price=(T,))
     sdev = batch.state.device
     if tuple_policy is None:
         tuple_policy = tp.extract(batch, tabs)
@@ -264,44 +204,31 @@ def run(batch, noise_prob=None, start="reset", resolution=DEFAULTS["resolution"]
         a.kind[i] = tp.KINDS[k]
     with torch.cuda.device(dev):
         p, p_g = sn.resolve_noise(batch, noise_prob, G)
-        keep = {}
-        for f, shape in shapes.items():
-            x = np.ascontiguousarray(tabs[f], np.int32 if f == "band_lo" else np.float64)
-            if x.shape != shape:
-                raise ThrlError("tuple_stationary: table %s has shape %s, expected %s" % (f, x.shape, shape))
-            keep[f] = torch.from_numpy(x).to(dev)
-            setattr(a, f, keep[f].data_ptr())
+        keep = an.bind_tables(a, tabs, [("cell_w", (J,), np.float64), ("reward", (N, T), np.float64),
+                                        ("scaled", (N, T), np.float64), ("price", (T,), np.float64),
+                                        ("band_lo", (T,), np.int32), ("band", (T, W), np.float64),
+                                        ("noise_reward", (N, T), np.float64), ("noise_price", (T,), np.float64)],
+                              dev, "tuple_stationary")
         if p_g is not None:
             a.noise_prob_g = p_g.data_ptr()
         else:
             a.noise_prob = p
         t0 = None
         if given_start:
-            if isinstance(start, torch.Tensor):
-                t0 = start.to(device=dev, dtype=torch.int32).reshape(-1)[:G].contiguous()
-            else:
-                t0 = torch.from_numpy(np.ascontiguousarray(np.asarray(start).reshape(-1)[:G].astype(np.int32))).to(dev)
-            if t0.numel() != G:
-                raise ThrlError("tuple_stationary: start must hold %d tuples" % G)
+            t0 = an.start_tensor(start, G, dev, "tuple_stationary")
         elif start == "state":
             t0 = state_tuples(batch, tabs, n_games=G)
         if t0 is not None:
             a.flags = _lib.TS_START_TUPLE
             a.start = t0.data_ptr()
         a.tuple_policy, a.cell_policy = tuple_policy.data_ptr(), cell_policy.data_ptr()
-        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
-        out = {"iters": torch.zeros((G,), dtype=torch.int32, device=dev),
-               "n_switch": torch.zeros((G,), dtype=torch.int32, device=dev)}
-        out.update({f: f64(G) for f in GAME_FLOAT})
-        out.update({f: f64(N, G) for f in AGENT_FLOAT})
-        if pi:
-            out["pi"] = f64(G, T)
-        for f, t in out.items():
-            setattr(a, f, t.data_ptr())
+        out = an.outputs(dev, (("iters", "n_switch"), (G,), "int32"), (GAME_FLOAT, (G,), "float64"),
+                         (AGENT_FLOAT, (N, G), "float64"), (("pi",) if pi else (), (G, T), "float64"))
+        an.bind(a, out)
         _lib.check(batch.L.thrl_tuple_stationary(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
                    "thrl_tuple_stationary")
         torch.cuda.synchronize(dev)
-        res = {f: t.cpu().numpy() for f, t in out.items()}
+        res = an.fetch(out)
         res["noise_prob"] = np.full(G, p, np.float64) if p_g is None else p_g.cpu().numpy()
         if t0 is not None:
             res["start"] = t0.cpu().numpy()
