@@ -1050,6 +1050,104 @@ typedef struct {
 int thrl_equilibrium_noise(const thrl_cfg* cfg, const void* q, const thrl_equilibrium_noise_args* args, void* stream);
 
 /*
+ * Deviation test under demand noise: thrl_deviation's question -- does a deviation pay, do the others punish, does
+ * play return -- in the environment of thrl_stationary, where the demand intercept is redrawn with probability p at
+ * every step.  Under noise a game follows no single path into one cycle, so a punishment seen on one path says little
+ * about what a deviator can expect; the exact answer is the propagation of a distribution: noisy greedy play is a
+ * finite Markov chain on the price cells, a forced deviation replaces the deviator's action in every cell for L
+ * periods, and the response is the sequence of distributions that follow from the one the shock hits.  No sampling.
+ * No reference counterpart.  QTable agents only; q, and everything else of the batch, is read only.  Every [.][G]
+ * array has G = args.n_games: the first n_games games of q.  All arithmetic is float64, every operation rounded once,
+ * in the order written here; every sum over cells runs over ascending k (or j) from 0.0.
+ *
+ * Cells, tuples, per-config tables, noise probability, policies: thrl_stationary's, word for word (cell_rows, det_cell,
+ * band_lo, band, noise_reward with J = n_cells and W = band_w; r_i(t) from the cached per-config plan and sc_i(t); p_g
+ * and q_g = 1 - p_g; policy with or without THRL_STAT_POLICY_GIVEN, the only flag; t_g(k) = the tuple of the clamped
+ * policy entries at cell_rows[.][k]).  cell_w and noise_price are not read.  *n_tuples (HOST, optional) receives T as
+ * soon as cfg is accepted.
+ *
+ *   R_i(t)    = q_g * r_i(t) + p_g * noise_reward_i(t)   (thrl_stationary's expected reward)
+ *   t'_g(k)   = t_g(k) with the deviator d's action replaced: by dev_action, or with dev_action = -1 by d's one-period
+ *               best response in that cell, the argmax over d's actions a of R_d(t_g(k) with a in place d), the first
+ *               maximum under strict >
+ *   P_g(j, k) = q_g [det_cell(t(j)) = k] + p_g n(t(j), k), as in thrl_stationary (the product p_g * n is computed, and
+ *               q_g is added to it only where the bracket is 1); P'_g the same with t'
+ *   m_0       = weights[g] (device double [G][J], required): the distribution the shock hits, e.g. thrl_stationary's pi
+ *   m_{tau+1}(k) = sum_j m_tau(j) * P^(tau)(j, k), P^(tau) = P' for tau < L and P otherwise, t^(tau) likewise: the plain
+ *               step, not the lazy one, so the iterate after tau steps is the distribution at period tau.  Terms that
+ *               are zero may be skipped: adding +0.0 is exact
+ *   E_i(tau)  = sum_k m_tau(k) * R_i(t^(tau)(k)),  A_i(tau) = sum_k m_tau(k) * sc_i(t^(tau)(k))
+ *   D(tau)    = 0.5 * sum_k |m_tau(k) - m_0(k)|: the total-variation distance from the start (D(0) = 0)
+ *
+ * Rows reward_rows / action_rows [row_count][N][G] (optional) hold E_i(tau) / A_i(tau) for tau in [row_begin, row_begin +
+ * row_count): the layout of the episode rows, so thrl_group_stats reduces them as they are (E = row_count); dist_rows
+ * [row_count][G] (optional) holds D(tau).  The kernel walks all K periods whatever rows it stores.
+ *
+ * Outputs, per game:
+ *   base_reward[i][g] = sum_k m_0(k) * R_i(t(k)): the expression of thrl_stationary's stat_reward, bit-equal to it with
+ *                       its pi as weights;  base_action[i][g] = sum_k m_0(k) * sc_i(t(k))
+ *   dev_share[g]      = the sum of m_0(k) over the cells with t'(k) != t(k) (+0.0 elsewhere): the long-run share of
+ *                       periods in which the deviation changes anything
+ *   gain[g]           = sum_{tau<K} w_tau * (E_d(tau) - base_reward_d), w_0 = 1, w_{tau+1} = w_tau * gamma_d (subtract,
+ *                       multiply, add); gamma_d = sweep_gamma[d][g] when given, else cfg.gamma[d]
+ *   gain_dev[g]       = the same sum over tau < L: what the deviation itself earns; gain - gain_dev is the aftermath
+ *   low[g]            = min_{L <= tau < K} (E_d(tau) - base_reward_d), low_step[g] its first tau; K == L: 0.0 and -1
+ *   ret_step[g]       = the first tau in [L, K] with D(tau) <= ret_tol, else -1
+ *   dist[g] = D(K),  mass[g] = sum_k m_K(k)
+ * A game whose noise_prob_g entry lies outside (0, 1] (NaN included) gets zeros in every float64 output, its rows
+ * included, and -1 in low_step and ret_step; no other game is affected (thrl_stationary's rule).
+ *
+ * Limits: T <= THRL_EQ_MAX_TUPLES, J <= THRL_STAT_MAX_CELLS and a game's working set in one block's 64 KB of LDS: both
+ * iterates, t(k) and t'(k), and the staging of the ordered sums, 20 J + 512 (2 N + 2) + 16 bytes; otherwise
+ * THRL_ERR_UNSUPPORTED.  J = 3,001 with N = 2 fits.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games outside [1, cfg.n_games], an unknown flag, a deviator outside [0, N),
+ * dev_len < 1, n_steps < dev_len or > THRL_DEV_MAX_STEPS, dev_action outside {-1} + [0, n_actions[d]), a row range
+ * outside [0, n_steps), n_cells < 1, band_w < 1, ret_tol < 0 or NaN, or a host-visible noise_prob outside (0, 1];
+ * THRL_ERR_UNSUPPORTED for the limits; THRL_ERR_NULL for a missing table (cell_rows, det_cell, band_lo, band,
+ * noise_reward), weights, policy or per-game output, or a missing q without THRL_STAT_POLICY_GIVEN.  All of these are
+ * decided before any launch.
+ */
+typedef struct {
+    int32_t n_games;                 /* G in [1, cfg.n_games]                            */
+    int32_t flags;                   /* 0 or THRL_STAT_POLICY_GIVEN                      */
+    int32_t n_cells;                 /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t band_w;                  /* W >= 1                                           */
+    int32_t deviator;                /* d in [0, N)                                      */
+    int32_t dev_len;                 /* L >= 1                                           */
+    int32_t n_steps;                 /* K >= L                                           */
+    int32_t dev_action;              /* fixed action index of d, or -1 = best response   */
+    int32_t row_begin;               /* rows stored: tau in [row_begin, row_begin + row_count) */
+    int32_t row_count;
+    double  noise_prob;              /* p in (0, 1], read when noise_prob_g is NULL      */
+    double  ret_tol;                 /* >= 0                                             */
+    const double* noise_prob_g;      /* device [G] or NULL                               */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    uint16_t* policy;                /* device [G][P]: out without the flag, in with it  */
+    const int32_t* cell_rows;        /* device [N][J]                                    */
+    const int32_t* det_cell;         /* device [T]                                       */
+    const int32_t* band_lo;          /* device [T]                                       */
+    const double* band;              /* device [T][W]                                    */
+    const double* noise_reward;      /* device [N][T]                                    */
+    const double* weights;           /* device [G][J] (required): m_0                    */
+    int32_t* n_tuples;               /* HOST [1] <- T, or NULL                           */
+    double*  base_reward;            /* device [N][G]                                    */
+    double*  base_action;            /* device [N][G]                                    */
+    double*  dev_share;              /* device [G]                                       */
+    double*  gain;                   /* device [G]                                       */
+    double*  gain_dev;               /* device [G]                                       */
+    double*  low;                    /* device [G]                                       */
+    int32_t* low_step;               /* device [G]                                       */
+    int32_t* ret_step;               /* device [G]                                       */
+    double*  dist;                   /* device [G]                                       */
+    double*  mass;                   /* device [G]                                       */
+    double*  reward_rows;            /* device [row_count][N][G] or NULL                 */
+    double*  action_rows;            /* device [row_count][N][G] or NULL                 */
+    double*  dist_rows;              /* device [row_count][G] or NULL                    */
+} thrl_deviation_noise_args;
+int thrl_deviation_noise(const thrl_cfg* cfg, const void* q, const thrl_deviation_noise_args* args, void* stream);
+
+/*
  * Strategies as tables over the game's action tuples, for ANY discrete agent: QTable, Reinforce, ActorCritic.  No
  * reference counterpart.  The analyses above index a policy by the agent's table row, which a network does not have.
  * The game has a finite state set of its own: with discrete agents and no env noise the price after a step is a

@@ -235,6 +235,24 @@ class EquilibriumNoiseArgs(ctypes.Structure):
     ]
 
 
+class DeviationNoiseArgs(ctypes.Structure):
+    """thrl_deviation_noise_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("flags", ctypes.c_int32), ("n_cells", ctypes.c_int32), ("band_w", ctypes.c_int32),
+        ("deviator", ctypes.c_int32), ("dev_len", ctypes.c_int32), ("n_steps", ctypes.c_int32),
+        ("dev_action", ctypes.c_int32), ("row_begin", ctypes.c_int32), ("row_count", ctypes.c_int32),
+        ("noise_prob", ctypes.c_double), ("ret_tol", ctypes.c_double),
+        ("noise_prob_g", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p), ("policy", ctypes.c_void_p),
+        ("cell_rows", ctypes.c_void_p), ("det_cell", ctypes.c_void_p), ("band_lo", ctypes.c_void_p),
+        ("band", ctypes.c_void_p), ("noise_reward", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+        ("n_tuples", ctypes.POINTER(ctypes.c_int32)),
+        ("base_reward", ctypes.c_void_p), ("base_action", ctypes.c_void_p), ("dev_share", ctypes.c_void_p),
+        ("gain", ctypes.c_void_p), ("gain_dev", ctypes.c_void_p), ("low", ctypes.c_void_p),
+        ("low_step", ctypes.c_void_p), ("ret_step", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("mass", ctypes.c_void_p),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p), ("dist_rows", ctypes.c_void_p),
+    ]
+
+
 TP_MAX_TUPLES = 4096
 
 
@@ -420,7 +438,7 @@ SYMBOLS = [
     "thrl_mixed_episodes", "thrl_mixed_policy_table_bytes", "thrl_ac_param_count", "thrl_ac_init", "thrl_ac_act", "thrl_ac_train",
     "thrl_cac_init", "thrl_cac_act", "thrl_cac_train", "thrl_group_stats", "thrl_ewm_rows", "thrl_deviation",
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
-    "thrl_equilibrium_noise",
+    "thrl_equilibrium_noise", "thrl_deviation_noise",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
     "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary", "thrl_tuple_equilibrium_noise", "thrl_price_probs", "thrl_sampled_chain",
     "thrl_sampled_noise_chain",
@@ -541,6 +559,8 @@ def load():
     L.thrl_stationary.argtypes = [cfgp, vp, ctypes.POINTER(StationaryArgs), vp]
     L.thrl_equilibrium_noise.restype = ctypes.c_int
     L.thrl_equilibrium_noise.argtypes = [cfgp, vp, ctypes.POINTER(EquilibriumNoiseArgs), vp]
+    L.thrl_deviation_noise.restype = ctypes.c_int
+    L.thrl_deviation_noise.argtypes = [cfgp, vp, ctypes.POINTER(DeviationNoiseArgs), vp]
     L.thrl_tuple_policy.restype = ctypes.c_int
     L.thrl_tuple_policy.argtypes = [cfgp, vp, ctypes.POINTER(TuplePolicyArgs), vp]
     L.thrl_tuple_walk.restype = ctypes.c_int

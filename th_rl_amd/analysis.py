@@ -304,7 +304,7 @@ def n_states(batch, call, args):
 
 # ---------------------------------------------------------------------------------------------- the batch methods
 class AnalysisMethods:
-    """The analysis methods of GameBatch and MixedGameBatch.  The QTable analyses (deviation, equilibrium(_noise), crossplay,
+    """The analysis methods of GameBatch and MixedGameBatch.  The QTable analyses (deviation(_noise), equilibrium(_noise), crossplay,
     attractors, stationary, track_convergence) read the tables, which both classes lay out alike; a MixedGameBatch with a
     neural agent raises ThrlError there, and its greedy_* / sampled_play methods are the ones for any mix of QTable,
     Reinforce and ActorCritic agents.  Tables, counters, state, epsilon and the episode index are never touched."""
@@ -332,6 +332,31 @@ class AnalysisMethods:
         self._ready()
         return dv.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, horizon=horizon,
                       state0=state0, rows=rows, group_stats=group_stats, budget=budget or dv.ROW_BUDGET)
+
+    def deviation_noise(self, deviator=0, steps=32, dev_len=1, action="best_response", noise_prob=None, ret_tol=1e-6,
+                        weights="stationary", rows=False, group_stats=None, budget=None, q=None, policy=None, n_games=None,
+                        tabs=None, tol=1e-12, max_iters=8192):
+        """The deviation test UNDER DEMAND NOISE (thrl_deviation_noise; definitions in include/thrl.h): the expected
+        impulse response of noisy greedy play to a deviation.  In the environment of stationary() a game follows no
+        single path, so the test propagates a distribution over the price cells: from `weights` ("stationary" = each
+        game's long-run distribution, stationary(pi=True, start="reset", tol, max_iters) at the same noise and policy;
+        or [G, J] values) deviator `deviator` plays `action` ("best_response": its one-period best response in every
+        cell, or an action index) for dev_len of `steps` periods, every other period is greedy.  Returns a dict of numpy
+        arrays: base_reward, base_action [N, G] (what the start distribution earns; with stationary weights
+        stationary()'s stat_reward), dev_share (the share of periods in which the deviation changes anything), gain
+        (discounted by the per-game sweep gamma, else the deviator's), gain_dev (its first dev_len periods), low,
+        low_step (the deviator's worst period after the deviation), ret_step (the first period from dev_len on whose
+        distribution is within ret_tol of the start in total variation, -1: none), dist, mass [G], noise_prob [G],
+        stat_iters [G], n_cells.  rows=True adds reward_rows / action_rows [steps, N, G] (the expected rewards and
+        actions per period) and dist_rows [steps, G]; group_stats (a GroupSpec) reduces the rows on the device as
+        deviation() does.  noise_prob, q, policy, n_games and tabs as in stationary()."""
+        from . import deviation as dv
+        self._qtable_only("deviation_noise", dv.NEURAL_FOLLOW_UP)
+        self._ready()
+        return dv.run_noise(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, noise_prob=noise_prob,
+                            ret_tol=ret_tol, weights=weights, rows=rows, group_stats=group_stats,
+                            budget=budget or dv.ROW_BUDGET, q=q, policy=policy, n_games=n_games, tabs=tabs, tol=tol,
+                            max_iters=max_iters)
 
     def equilibrium(self, agents=None, state0=None, policies=False, tol=0.0):
         """Equilibrium check of every game's greedy strategies (thrl_equilibrium; definitions in include/thrl.h): for

@@ -14,6 +14,7 @@
 #include "thrl_converge.h"
 #include "thrl_crossplay.h"
 #include "thrl_deviation.h"
+#include "thrl_deviation_noise.h"
 #include "thrl_equilibrium.h"
 #include "thrl_equilibrium_noise.h"
 #include "thrl_host.h"
@@ -62,24 +63,37 @@ int check_steps_rows(int n_steps, int row_begin, int row_count) {       // the w
         return fail(THRL_ERR_BAD_CONFIG, "n_steps=%d out of [0,%d]", n_steps, THRL_DEV_MAX_STEPS);
     return check_rows(row_begin, row_count, n_steps);
 }
-int check_deviation(const thrl_cfg* c, int deviator, int dev_len, int n_steps, int horizon, int dev_action) {
+// the deviator, the deviation's length and the steps; then the action: the parts of check_deviation that a call without a
+// horizon makes too (thrl_deviation_noise)
+int check_deviator(const thrl_cfg* c, int deviator, int dev_len, int n_steps) {
     const int N = c->n_agents;
     if (deviator < 0 || deviator >= N) return fail(THRL_ERR_BAD_CONFIG, "deviator=%d out of [0,%d)", deviator, N);
     if (dev_len < 1) return fail(THRL_ERR_BAD_CONFIG, "dev_len=%d must be >= 1", dev_len);
     if (n_steps < dev_len || n_steps > THRL_DEV_MAX_STEPS)
         return fail(THRL_ERR_BAD_CONFIG, "n_steps=%d out of [dev_len=%d, %d]", n_steps, dev_len, THRL_DEV_MAX_STEPS);
-    if (const int rc = check_horizon(horizon)) return rc;
+    return THRL_OK;
+}
+int check_dev_action(const thrl_cfg* c, int deviator, int dev_action) {
     if (dev_action < -1 || dev_action >= c->n_actions[deviator])
         return fail(THRL_ERR_BAD_CONFIG, "dev_action=%d: -1 (best response) or an action of agent %d in [0,%d)", dev_action,
                     deviator, c->n_actions[deviator]);
     return THRL_OK;
 }
+int check_deviation(const thrl_cfg* c, int deviator, int dev_len, int n_steps, int horizon, int dev_action) {
+    if (const int rc = check_deviator(c, deviator, dev_len, n_steps)) return rc;
+    if (const int rc = check_horizon(horizon)) return rc;
+    return check_dev_action(c, deviator, dev_action);
+}
+int check_tol(double tol, const char* tol_name) {               // a tolerance: >= 0, which refuses NaN
+    return tol >= 0.0 ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "%s=%g must be >= 0", tol_name, tol);
+}
 int check_iters_tol(int max_iters, double tol, const char* iters_name = "max_iters", const char* tol_name = "tol") {
     if (max_iters < 1 || max_iters > THRL_STAT_MAX_ITERS)
         return fail(THRL_ERR_BAD_CONFIG, "%s=%d out of [1,%d]", iters_name, max_iters, THRL_STAT_MAX_ITERS);
-    return tol >= 0.0 ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "%s=%g must be >= 0", tol_name, tol);
+    return check_tol(tol, tol_name);
 }
-// ---- the checks of the two calls on the cells of noisy play (thrl_stationary, thrl_equilibrium_noise), `call` their name
+// ---- the checks of the calls on the cells of noisy play (thrl_stationary, thrl_equilibrium_noise,
+// thrl_deviation_noise), `call` their name
 int check_tuple_limit(const thrl_cfg* c, const char* call, int* T) {   // T = prod n_actions needs no plan
     int64_t T64 = 1;
     for (int i = 0; i < c->n_agents; i++) {
@@ -1221,6 +1235,70 @@ int thrl_equilibrium_noise(const thrl_cfg* c, const void* q, const thrl_equilibr
     const int grid = grid_for(cus, lds_cu, a.lds_bytes, kEqnMaxBlocksPerCu, a.G);
     const int e = thrl::launch_equilibrium_noise(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_equilibrium_noise launch") : THRL_OK;
+}
+
+int thrl_deviation_noise(const thrl_cfg* c, const void* q, const thrl_deviation_noise_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_stationary's checks in its order, with the deviation and its rows as thrl_deviation checks them
+    int T = 0;
+    if ((rc = check_tuple_limit(c, "thrl_deviation_noise", &T)) != THRL_OK) return rc;
+    if (x->n_tuples) *x->n_tuples = T;
+    if ((rc = check_games_of(x->n_games, c)) != THRL_OK) return rc;
+    if (x->flags & ~THRL_STAT_POLICY_GIVEN) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if ((rc = check_deviator(c, x->deviator, x->dev_len, x->n_steps)) != THRL_OK) return rc;
+    if ((rc = check_dev_action(c, x->deviator, x->dev_action)) != THRL_OK) return rc;
+    if ((rc = check_rows(x->row_begin, x->row_count, x->n_steps)) != THRL_OK) return rc;
+    if ((rc = check_cells_band(x->n_cells, x->band_w)) != THRL_OK) return rc;
+    if ((rc = check_tol(x->ret_tol, "ret_tol")) != THRL_OK) return rc;
+    if ((rc = check_noise_prob(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
+    if ((rc = check_cell_limit("thrl_deviation_noise", x->n_cells)) != THRL_OK) return rc;
+    DevnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.J = x->n_cells;
+    const int64_t need = thrl::devn_layout(a);
+    if (need > kDevnLdsBudget) return lds_refusal("thrl_deviation_noise", need, N, x->n_cells);
+    const bool given = (x->flags & THRL_STAT_POLICY_GIVEN) != 0;
+    if (!x->cell_rows || !x->det_cell || !x->band_lo || !x->band || !x->noise_reward)
+        return missing("cell_rows / det_cell / band_lo / band / noise_reward");
+    if (!x->weights) return missing("weights");
+    if (!x->policy || !x->base_reward || !x->base_action || !x->dev_share || !x->gain || !x->gain_dev || !x->low
+        || !x->low_step || !x->ret_step || !x->dist || !x->mass)
+        return missing("policy / base_reward / base_action / dev_share / gain / gain_dev / low / low_step / ret_step / dist / "
+                       "mass");
+    if (!given && !q) return missing_q("THRL_STAT_POLICY_GIVEN");
+
+    a.G = x->n_games; a.T = T; a.W = x->band_w;
+    a.d = x->deviator; a.L = x->dev_len; a.K = x->n_steps; a.dev_action = x->dev_action;
+    a.row_begin = x->row_begin; a.row_count = x->row_count;
+    a.noise_prob = x->noise_prob; a.ret_tol = x->ret_tol; a.gamma_d = c->gamma[x->deviator];
+    fill_agents(c, a.ag, nullptr);
+    tuple_strides(c, nullptr, a.tstride);
+    a.P = table_rows(a.ag, N, a.row_off, nullptr, nullptr);
+    int devs = 0;
+    if (hipGetDeviceCount(&devs) != hipSuccess || devs <= 0) {
+        (void)hipGetLastError();
+        return hip_fail((int)hipErrorNoDevice, "thrl_deviation_noise");
+    }
+    EqSlot sl;
+    if ((rc = eq_cached_plan(c, sl)) != THRL_OK) return rc;
+
+    if (!given && (rc = extract_policies(c, q, x->n_games, x->policy, stream)) != THRL_OK) return rc;
+
+    a.policy = x->policy; a.noise_prob_g = x->noise_prob_g; a.sweep_gamma = x->sweep_gamma; a.weights = x->weights;
+    a.rew = (const double*)sl.mem;
+    a.cell_rows = x->cell_rows; a.det_cell = x->det_cell; a.band_lo = x->band_lo; a.band = x->band;
+    a.noise_reward = x->noise_reward;
+    a.base_reward = x->base_reward; a.base_action = x->base_action; a.dev_share = x->dev_share; a.gain = x->gain;
+    a.gain_dev = x->gain_dev; a.low = x->low; a.low_step = x->low_step; a.ret_step = x->ret_step; a.dist = x->dist;
+    a.mass = x->mass; a.reward_rows = x->reward_rows; a.action_rows = x->action_rows; a.dist_rows = x->dist_rows;
+    int cus = 0, lds_cu = 0;
+    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
+    const int grid = grid_for(cus, lds_cu, a.lds_bytes, kDevnMaxBlocksPerCu, a.G);
+    const int e = thrl::launch_deviation_noise(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_deviation_noise launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -108,7 +108,10 @@ def merge_group_stats(config, out, world):
     dv = training.get("deviation")
     if dv is not None and dv is not False:
         from th_rl_amd.deviation import parse_options as deviation_options
-        prefixes += ["dev%d" % d for d in deviation_options(dv, config)["agents"]]
+        dvo = deviation_options(dv, config)
+        prefixes += ["dev%d" % d for d in dvo["agents"]]
+        if dvo.get("noise"):       # the response curves of the test under demand noise
+            prefixes += ["devn%d" % d for d in dvo["agents"]]
     xp = training.get("crossplay")
     if xp is not None and xp is not False:
         from th_rl_amd.crossplay import parse_options as crossplay_options

@@ -84,6 +84,12 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                      # (mu, lam), dev_cycle_reward / dev_cycle_action.npy [N, G], per deviator d
                                      # dev<d>_post.npy int32 [4, G] (mu_post, lam_post, ret_step, act_dev) and
                                      # dev<d>_gain.npy [G]; with group_stats the response rows' dev<d>_*.npy [steps, ...];
+                                     # "noise": true or {"noise_prob": null, "ret_tol": 1e-6, "tol": 1e-12, "max_iters":
+                                     # 8192} adds the test UNDER DEMAND NOISE (noise_prob null = the run's own): the
+                                     # expected response of noisy greedy play from its long-run distribution,
+                                     # deviation_noise.json, devn_prob / devn_stat_iters.npy [G], per deviator
+                                     # devn<d>_games.npy [6, G], devn<d>_steps.npy int32 [2, G], devn<d>_base.npy
+                                     # [2, N, G] and with group_stats devn<d>_*.npy [steps, ...];
                                      # "tables": "final" (default) | "converged" (needs convergence.snapshot): analyse
                                      # each game's tables and state at its convergence (never converged: final tables)
                  "convergence": null, # true or {"window": ceil(100000 / max_steps), "every": 20, "stop": null,

@@ -217,6 +217,41 @@ def deviation_games(exp_path, deviator=0):
     return pandas.concat(frames)
 
 
+def deviation_noise_summary(exp_path):
+    """A run's deviation test under demand noise (training.deviation with "noise"): deviation_noise.json's summary as a
+    DataFrame with one row per (group, deviator) -- games, solved, deviates, dev_share_mean, unprofitable, gain_mean and
+    gain_q*, gain_dev_mean, low_mean, returned, ret_step_mean, dist_mean.  The expected response curves of a run that
+    also has training.group_stats are the per-group statistics of prefix "devn<d>":
+    group_quantiles(exp_path, group, "total", prefix="devn0"), one row per period after the shock."""
+    if not os.path.isfile(os.path.join(exp_path, "deviation_noise.json")):
+        raise KeyError("no deviation test under noise (deviation_noise.json) under %s (training.deviation.noise)" % exp_path)
+    desc = _load_json(exp_path, "deviation_noise.json")
+    df = pandas.DataFrame(desc["summary"])
+    df["n_cells"] = int(desc["n_cells"])
+    return df
+
+
+def deviation_noise_games(exp_path, deviator=0):
+    """Per-game results of the deviation test under demand noise for `deviator`, one row per game indexed by its GLOBAL
+    id: noise_prob, stat_iters, dev_share, gain, gain_dev, low, dist, mass, low_step, ret_step, base_reward_<i> /
+    base_action_<i> and solved.  Reads exp_path's devn*.npy, or those of exp_path/shard*/ in game order."""
+    from th_rl_amd import deviation as dv
+    dirs = _run_dirs(exp_path, "devn_prob.npy", "deviation test under noise", "deviation.noise")
+    frames = []
+    for d in dirs:
+        off = _game_offset(d, exp_path)
+        g = dv.load_noise_games(d, int(deviator))
+        cols = {"noise_prob": g["noise_prob"], "stat_iters": g["stat_iters"]}
+        cols.update({f: g[f] for f in dv.NOISE_FLOAT + dv.NOISE_INT})
+        for i in range(g["base_reward"].shape[0]):
+            cols["base_reward_%d" % i] = g["base_reward"][i]
+            cols["base_action_%d" % i] = g["base_action"][i]
+        cols["solved"] = dv.solved_noise(g)
+        n = g["noise_prob"].shape[0]
+        frames.append(pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game")))
+    return pandas.concat(frames)
+
+
 def equilibrium_summary(exp_path):
     """A run's equilibrium check (training.equilibrium): equilibrium.json's summary as a DataFrame.  Rows with an
     agent: games, br_on, br_all (fractions of games in which the agent's greedy strategy is a best response on the
