@@ -4,7 +4,10 @@ unspecified): probabilities rtol 2e-5 (at the initial weight scale; the derived 
 tests/policy_reference.py otherwise, see tests/test_gpu_policy.py), clipped gradients rtol 2e-4 + atol 2e-6, Adam
 moments rtol 1e-3, parameters atol 5e-6 except Adam's sign-sensitive near-zero-gradient elements (<= 0.2 %).
 The tests here run ActorCritic and CAC in the clipped, critic-dominated regime only (fc_v at its initial bias), where the
-entropy term is below the tolerance; tests/test_gpu_update_terms.py pins each term of the three updates."""
+entropy term is below the tolerance; tests/test_gpu_update_terms.py pins each term of the three updates.  The CAC tests
+here see the heads at the initial weight scale (or three games of fixture G9) only; the forward side of CAC -- heads,
+softplus, sigmoid, Box-Muller, in k_cac_act and in the fused kernel -- is held to the float64 mirror
+tests/cac_reference.py by tests/test_gpu_cac_policy.py, at every scale and edge."""
 import os
 
 import numpy as np
