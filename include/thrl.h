@@ -36,8 +36,10 @@
 extern "C" {
 #endif
 
-#define THRL_ABI_VERSION 3          /* 2: per-game sweeps in thrl_qtable_init, thrl_mixed and the *_train entry points;
-                                       3: thrl_build_info, THRL_KERNEL_WAVE_PLAIN / _GREEDY, replay rings [G][buf_len] */
+#define THRL_ABI_VERSION 4          /* 2: per-game sweeps in thrl_qtable_init, thrl_mixed and the *_train entry points;
+                                       3: thrl_build_info, THRL_KERNEL_WAVE_PLAIN / _GREEDY, replay rings [G][buf_len];
+                                       4: the choice arrays of thrl_op_draws / thrl_op_sample_action are int32 (an int8
+                                       buffer of a version-3 caller would be overrun fourfold) */
 #define THRL_MAXA 8          /* max agents per game (reference configs use 2) */
 #define THRL_MAX_EPISODES_PER_LAUNCH 32
 
@@ -123,7 +125,9 @@ typedef struct {
      * generic kernel keeps the sequential per-step sums. */
     /* parity mode: the reference's recorded random draws, or NULL for Philox       */
     const double* inj_u;             /* device [n_episodes][T][N][G] random.uniform(0,1) (agents.py:81) */
-    const int8_t* inj_choice;        /* device [n_episodes][T][N][G] random.choice idx   (agents.py:82) */
+    const int8_t* inj_choice;        /* device [n_episodes][T][N][G] random.choice idx   (agents.py:82); one byte, so the
+                                        generic kernel's route is THRL_ERR_BAD_CONFIG under injection with an agent of
+                                        more than 128 actions (the LDS kernels stop at 64); read unsigned, clamped */
     const double* inj_noise_u;       /* device [n_episodes][T][G]    (environments.py:28); NULL if noise_prob<=0 */
     const double* inj_noise_a;       /* device [n_episodes][T][G]    (environments.py:29) */
     void*    workspace;              /* device scratch, thrl_workspace_bytes()           */
@@ -156,7 +160,7 @@ typedef struct {
 
 int         thrl_version(void);
 const char* thrl_last_error(void);
-/* What this binary is: "abi=3;ablate=<mask>;src=<hash of all kernel sources>;wave=<hash of the sources of the
+/* What this binary is: "abi=4;ablate=<mask>;src=<hash of all kernel sources>;wave=<hash of the sources of the
  * headline kernel>;nn=<hash of the neural-agent kernels' sources>".  ablate != 0 marks a
  * TIMING-ONLY diagnostic build (phases of the fused kernel compiled out, results wrong by construction;
  * profiles/ablate.py) -- callers that report results or throughput must refuse it (bench.py does). */
@@ -229,10 +233,13 @@ int thrl_play_greedy(const thrl_cfg* cfg, const void* q, const double* state0,
  * still runs on the device.
  */
 /* QTable.sample_action / get_action for agent `agent` (agents.py:80-92):
- * u/choice device [G] (u==NULL => greedy get_action); price device [G];
- * encode32 != 0 applies the trainer's float32 cast first (trainer.py:53). */
+ * u device [G] f64, choice device [G] int32 (u==NULL => greedy get_action); price device [G];
+ * encode32 != 0 applies the trainer's float32 cast first (trainer.py:53).  choice is int32 since ABI v4: an agent
+ * may have 32,000 actions, and a byte wrapped every choice of 128 and more.  A choice outside [0, n_actions) is
+ * device data the host cannot see: it is clamped to the last action (the rule of the injected choices below), so
+ * a bad caller array cannot make the following thrl_op_td_update index outside the table. */
 int thrl_op_sample_action(const thrl_cfg* cfg, int agent, const void* q, const double* price,
-                          double eps, const double* u, const int8_t* choice, int encode32,
+                          double eps, const double* u, const int32_t* choice, int encode32,
                           int32_t* action_out, void* stream);
 /* QTable.encode for agent `agent` (agents.py:47-49): price [G] f64 -> row index [G] int32;
  * as_float32 != 0 evaluates it on the float32-cast state as sample_action does (trainer.py:53). */
@@ -379,7 +386,8 @@ typedef struct {
      * the game, inj_action with a Reinforce / ActorCritic agent, inj_noise_u and inj_noise_a with
      * cfg.noise_prob > 0 -- otherwise THRL_ERR_BAD_CONFIG.  An injected choice or action outside [0, n_actions) is
      * device data the host cannot see: it is clamped to the last action (thrl_crossplay's rule for policy entries),
-     * nothing is read or written out of bounds.  A game with a CAC agent is THRL_ERR_UNSUPPORTED under injection:
+     * nothing is read or written out of bounds.  inj_choice is one byte per draw: a QTable agent of more than 128 actions
+     * is THRL_ERR_BAD_CONFIG under injection.  A game with a CAC agent is THRL_ERR_UNSUPPORTED under injection:
      * its action is a float, and the reference's play path for it cannot run (see thrl_cac_act).  Per-game sweeps
      * combine with injection as in thrl_qtable_episodes. */
     const double* inj_u;                 /* device [n_episodes][T][N][G] random.uniform(0,1) (agents.py:81)   */
@@ -402,11 +410,11 @@ int thrl_mixed_episodes(const thrl_cfg* cfg, thrl_mixed* mx, void* q, int32_t* c
                         thrl_run* run, double* game_reward_log, double* game_action_log, void* stream);
 
 /* Philox draws for one lockstep step of a caller-driven loop: u [N][G] f64 uniforms and
- * choice [N][G] int8 indices (agents.py:81-82), optionally u2 [N][G] (the word behind `choice` as a
+ * choice [N][G] int32 indices in [0, n_actions[i]) (agents.py:81-82; int8 before ABI v4), optionally u2 [N][G] (the word behind `choice` as a
  * uniform: CAC's second Box-Muller input) and the env's two noise draws [G]
  * (environments.py:28-29); same streams/counters as thrl_qtable_episodes uses internally. */
 int thrl_op_draws(const thrl_cfg* cfg, uint64_t seed, uint64_t game_offset, uint64_t episode, int32_t step,
-                  double* u_out, int8_t* choice_out, double* u2_out, double* noise_u_out, double* noise_a_out,
+                  double* u_out, int32_t* choice_out, double* u2_out, double* noise_u_out, double* noise_a_out,
                   void* stream);
 
 /*

@@ -8,7 +8,11 @@ individual analyses already have.
 
 The module also runs where a GPU is present, so no case may get as far as a launch even if its refusal were lost: every
 args struct leaves NULL a pointer that the entry point's last NULL check tests (LAST_NULL, asserted before every call),
-so the worst a mistake can do is THRL_ERR_NULL and a failing comparison.  No GPU is needed."""
+so the worst a mistake can do is THRL_ERR_NULL and a failing comparison.  No GPU is needed.
+
+The two episode entry points are here for one refusal each: parity mode with a QTable agent of more than 128 actions, whose
+choices the injected int8 format cannot hold.  Behind it thrl_qtable_episodes finds no replay memory and
+thrl_mixed_episodes no kernel for more than 64 actions, so these cases cannot launch either."""
 import ctypes
 import json
 import os
@@ -55,6 +59,8 @@ CONFIGS = {
     "gamma_one": _two(gamma=1.0),
     "gamma_nan": _two(gamma=float("nan")),
     "sp_big": _two(32, 32),           # thrl_sampled_chain's working set does not fit
+    "inj_wide": _two(129, 21),        # one action more than an injected int8 choice holds
+    "inj_wide_second": _two(21, 129),
 }
 
 
@@ -99,6 +105,9 @@ LAST_NULL = {
                                      else [getattr(a, f) for f in ("state0", "policy") + AT.OUTPUTS]),
     "thrl_stationary": lambda a, q: ([q] if not a.flags & 1 else [a.state0] if a.flags & 2
                                      else [getattr(a, f) for f in ("policy",) + ST.OUTPUTS]),
+    # (what is left unset behind the refusal under test: see the module docstring)
+    "thrl_qtable_episodes": lambda a, q: [a.replay_mem],
+    "thrl_mixed_episodes": lambda a, q: [a.policy_tab],
 }
 TAKES_Q = {"thrl_deviation", "thrl_policy_track", "thrl_crossplay", "thrl_tuple_policy", "thrl_price_policy", "thrl_equilibrium",
            "thrl_attractors", "thrl_stationary"}
@@ -118,6 +127,30 @@ def _gs_args(**kw):
 def _tuple_policy(**kw):
     kinds = kw.pop("kinds", (0, 1))
     return TP._policy_args(kinds=kinds, **kw)
+
+
+def _episode_buffers(**kw):
+    from th_rl_amd import _lib
+    b = _lib.Buffers()
+    for f in ("q", "state", "inj_u", "inj_choice"):
+        setattr(b, f, FAKE)
+    for k, v in kw.items():
+        setattr(b, k, v)
+    return b
+
+
+def _mixed_args(kind=(0, 0), **kw):
+    from th_rl_amd import _lib
+    mx = _lib.Mixed()
+    for i, k in enumerate(kind):
+        mx.kind[i] = k
+        if k:
+            mx.nn_params[i] = FAKE
+    for f in ("inj_u", "inj_choice", "inj_action"):
+        setattr(mx, f, FAKE)
+    for k, v in kw.items():
+        setattr(mx, k, v)
+    return mx
 
 
 def cases():
@@ -307,6 +340,13 @@ def cases():
     add("thrl_stationary", ST._args, dict(flags=1, mass=None), q=None)
     add("thrl_stationary", ST._args, {}, q=None, ident="q=None")
     nulls("thrl_stationary", ST._args, q=None)
+
+    # ---- thrl_qtable_episodes, thrl_mixed_episodes: injection past what an int8 choice holds
+    for cfg in ("inj_wide", "inj_wide_second"):
+        add("thrl_qtable_episodes", _episode_buffers, {}, cfg=cfg)
+        add("thrl_mixed_episodes", _mixed_args, {}, cfg=cfg)
+    add("thrl_mixed_episodes", _mixed_args, dict(kind=(0, 1)), cfg="inj_wide")
+    add("thrl_mixed_episodes", _mixed_args, dict(kind=(1, 0)), cfg="inj_wide_second")
     return out
 
 
@@ -321,6 +361,12 @@ def run(lib):
         pa = None if a is None else ctypes.byref(a)
         if entry == "thrl_group_stats":
             rc = lib.thrl_group_stats(pa, None)
+        elif entry in ("thrl_qtable_episodes", "thrl_mixed_episodes"):
+            r = _lib.Run()
+            r.n_episodes = 1
+            fake = ctypes.c_void_p(FAKE)
+            rc = (lib.thrl_qtable_episodes(ctypes.byref(cfgs[cfg]), pa, ctypes.byref(r), None) if entry == "thrl_qtable_episodes"
+                  else lib.thrl_mixed_episodes(ctypes.byref(cfgs[cfg]), pa, fake, fake, fake, ctypes.byref(r), fake, fake, None))
         else:
             pc = None if cfg is None else ctypes.byref(cfgs[cfg])
             fn = getattr(lib, entry)

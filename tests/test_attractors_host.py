@@ -203,7 +203,7 @@ def test_args_struct_and_limits_match_header():
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    want = [ctypes.sizeof(_lib.AttractorsArgs), _lib.ATTR_KEEP, _lib.ATTR_POLICY_GIVEN, _lib.ATTR_MAX_STARTS, 3]
+    want = [ctypes.sizeof(_lib.AttractorsArgs), _lib.ATTR_KEEP, _lib.ATTR_POLICY_GIVEN, _lib.ATTR_MAX_STARTS, 4]
     assert got == want + [getattr(_lib.AttractorsArgs, f).offset for f in fields]
     assert A.KEEP == at.KEEP == _lib.ATTR_KEEP and "thrl_attractors" in _lib.SYMBOLS
 

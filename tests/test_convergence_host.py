@@ -45,7 +45,7 @@ def test_library_exports_policy_track(lib):
     from th_rl_amd import _lib
     assert "thrl_policy_track" in _lib.SYMBOLS
     assert hasattr(lib, "thrl_policy_track")
-    assert lib.thrl_version() == 3
+    assert lib.thrl_version() == 4
 
 
 def test_args_struct_matches_header():

@@ -293,7 +293,7 @@ def test_args_struct_and_limits_match_header():
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
     A = _lib.CrossplayArgs
     assert got == [ctypes.sizeof(A), A.seat.offset, A.action_rows.offset, _lib.XPLAY_POLICY_GIVEN, _lib.DEV_MAX_STEPS,
-                   _lib.DEV_MAX_HORIZON, 3]
+                   _lib.DEV_MAX_HORIZON, 4]
     assert "thrl_crossplay" in _lib.SYMBOLS
 
 

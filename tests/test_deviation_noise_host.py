@@ -114,9 +114,9 @@ def test_args_struct_and_limits_match_header():
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    want = [ctypes.sizeof(_lib.DeviationNoiseArgs), _lib.STAT_POLICY_GIVEN, _lib.STAT_MAX_CELLS, _lib.DEV_MAX_STEPS, 3]
+    want = [ctypes.sizeof(_lib.DeviationNoiseArgs), _lib.STAT_POLICY_GIVEN, _lib.STAT_MAX_CELLS, _lib.DEV_MAX_STEPS, 4]
     assert got == want + [getattr(_lib.DeviationNoiseArgs, f).offset for f in fields]
-    assert "thrl_deviation_noise" in _lib.SYMBOLS and _lib.ABI_VERSION == 3
+    assert "thrl_deviation_noise" in _lib.SYMBOLS and _lib.ABI_VERSION == 4
 
 
 # ------------------------------------------------------------------------------------------------ options

@@ -224,7 +224,7 @@ def test_args_struct_and_limits_match_header():
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    assert got == [ctypes.sizeof(_lib.EquilibriumArgs), _lib.EQ_MAX_ITERS, _lib.EQ_MAX_TUPLES, _lib.EQ_MAX_STATES, 3]
+    assert got == [ctypes.sizeof(_lib.EquilibriumArgs), _lib.EQ_MAX_ITERS, _lib.EQ_MAX_TUPLES, _lib.EQ_MAX_STATES, 4]
     assert E.MAX_ITERS == _lib.EQ_MAX_ITERS
 
 

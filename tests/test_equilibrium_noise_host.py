@@ -256,9 +256,9 @@ def test_args_struct_and_limits_match_header():
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
     want = [ctypes.sizeof(_lib.EquilibriumNoiseArgs), _lib.EQN_POLICY_GIVEN, _lib.STAT_MAX_CELLS, _lib.STAT_MAX_ITERS,
-            _lib.EQ_MAX_ITERS, 3]
+            _lib.EQ_MAX_ITERS, 4]
     assert got == want + [getattr(_lib.EquilibriumNoiseArgs, f).offset for f in fields]
-    assert "thrl_equilibrium_noise" in _lib.SYMBOLS and EN.MAX_ITERS == _lib.EQ_MAX_ITERS and _lib.ABI_VERSION == 3
+    assert "thrl_equilibrium_noise" in _lib.SYMBOLS and EN.MAX_ITERS == _lib.EQ_MAX_ITERS and _lib.ABI_VERSION == 4
 
 
 # ------------------------------------------------------------------------------------------------ options

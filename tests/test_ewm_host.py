@@ -130,9 +130,9 @@ def test_args_struct_matches_header():
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    assert got == [ctypes.sizeof(_lib.EwmRowsArgs), 3] + [getattr(_lib.EwmRowsArgs, f).offset for f in FIELDS]
+    assert got == [ctypes.sizeof(_lib.EwmRowsArgs), 4] + [getattr(_lib.EwmRowsArgs, f).offset for f in FIELDS]
     assert [f for f, _ in _lib.EwmRowsArgs._fields_] == list(FIELDS)
-    assert "thrl_ewm_rows" in _lib.SYMBOLS and _lib.ABI_VERSION == 3
+    assert "thrl_ewm_rows" in _lib.SYMBOLS and _lib.ABI_VERSION == 4
 
 
 def _args(**kw):

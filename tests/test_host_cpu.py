@@ -37,7 +37,7 @@ def test_library_exports_every_declared_symbol(lib):
     assert declared and set(declared) == set(_lib.SYMBOLS)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.thrl_version() == 3
+    assert lib.thrl_version() == 4
 
 
 def test_struct_layout_matches_header(lib):
@@ -352,7 +352,7 @@ def test_build_info_names_the_binary(lib):
     binary was built from -- bench.py prints it and refuses an ablation build for any reported number."""
     from th_rl_amd import _lib, build
     info = _lib.build_info()
-    assert info["abi"] == 3 and info["ablate"] == 0 and lib.thrl_ablate_mask() == 0
+    assert info["abi"] == 4 and info["ablate"] == 0 and lib.thrl_ablate_mask() == 0
     assert info["src"] == build.source_hash() and re.fullmatch(r"[0-9a-f]{12}", info["src"])
     assert info["wave"] == build.source_hash(build.WAVE_FILES) and info["nn"] == build.source_hash(build.NN_FILES)
     assert info["path"].endswith("libthrl_hip.so")

@@ -69,7 +69,7 @@ def test_thrl_mixed_mirror_matches_the_header():
 def test_abi_version_is_unchanged():
     from th_rl_amd import build, _lib
     build.build()
-    assert _lib.load().thrl_version() == 3
+    assert _lib.load().thrl_version() == 4
 
 
 KINDS = ["QTable", "Reinforce"]

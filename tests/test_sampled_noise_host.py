@@ -302,8 +302,8 @@ def test_args_struct_matches_the_header():
     got, mine = _offsets(_lib.SampledNoiseChainArgs, "thrl_sampled_noise_chain_args",
                          ["THRL_SPN_START_TUPLE", "THRL_SPN_START_RESET", "THRL_SPN_TILE", "THRL_SP_MAX_LDS", "THRL_STAT_MAX_CELLS",
                           "THRL_ABI_VERSION"])
-    assert got == mine[:1] + [_lib.SPN_START_TUPLE, _lib.SPN_START_RESET, _lib.SPN_TILE, _lib.SP_MAX_LDS, sp.MAX_CELLS, 3] + mine[1:]
-    assert "thrl_sampled_noise_chain" in _lib.SYMBOLS and _lib.ABI_VERSION == 3 and sp.TILE == 64
+    assert got == mine[:1] + [_lib.SPN_START_TUPLE, _lib.SPN_START_RESET, _lib.SPN_TILE, _lib.SP_MAX_LDS, sp.MAX_CELLS, 4] + mine[1:]
+    assert "thrl_sampled_noise_chain" in _lib.SYMBOLS and _lib.ABI_VERSION == 4 and sp.TILE == 64
 
 
 SN_REQUIRED = ("dpolicy", "npolicy", "grp_first", "grp_perm", "reward", "scaled", "price", "band_lo", "band", "noise_price",

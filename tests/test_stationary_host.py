@@ -259,7 +259,7 @@ def test_args_struct_and_limits_match_header():
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
     want = [ctypes.sizeof(_lib.StationaryArgs), _lib.STAT_POLICY_GIVEN, _lib.STAT_START_STATE, _lib.STAT_MAX_CELLS,
-            _lib.STAT_MAX_ITERS, 3]
+            _lib.STAT_MAX_ITERS, 4]
     assert got == want + [getattr(_lib.StationaryArgs, f).offset for f in fields]
     assert "thrl_stationary" in _lib.SYMBOLS
 

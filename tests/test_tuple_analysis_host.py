@@ -223,11 +223,11 @@ def test_args_structs_match_header():
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    want = [ctypes.sizeof(D), ctypes.sizeof(E), 4096, 3] + [getattr(D, f).offset for f in dfields] \
+    want = [ctypes.sizeof(D), ctypes.sizeof(E), 4096, 4] + [getattr(D, f).offset for f in dfields] \
         + [getattr(E, f).offset for f in efields]
     assert got == want
     assert len(dfields) == 26 and len(efields) == 21
-    assert "thrl_tuple_deviation" in _lib.SYMBOLS and "thrl_tuple_equilibrium" in _lib.SYMBOLS and _lib.ABI_VERSION == 3
+    assert "thrl_tuple_deviation" in _lib.SYMBOLS and "thrl_tuple_equilibrium" in _lib.SYMBOLS and _lib.ABI_VERSION == 4
 
 
 FAKE = 4096                           # never dereferenced: validation fails before any launch

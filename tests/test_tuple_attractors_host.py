@@ -254,8 +254,8 @@ def test_args_struct_matches_header():
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    assert got == [ctypes.sizeof(A), 4096, KEEP, 3] + [getattr(A, f).offset for f in fields]
-    assert len(fields) == 25 and "thrl_tuple_attractors" in _lib.SYMBOLS and _lib.ABI_VERSION == 3 and ta.KEEP == KEEP
+    assert got == [ctypes.sizeof(A), 4096, KEEP, 4] + [getattr(A, f).offset for f in fields]
+    assert len(fields) == 25 and "thrl_tuple_attractors" in _lib.SYMBOLS and _lib.ABI_VERSION == 4 and ta.KEEP == KEEP
 
 
 FAKE = 4096                           # never dereferenced: validation fails before any launch

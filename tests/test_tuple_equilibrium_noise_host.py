@@ -311,8 +311,8 @@ def test_args_struct_and_limits_match_header():
     got, mine = _offsets(_lib.TupleEquilibriumNoiseArgs, "thrl_tuple_equilibrium_noise_args",
                          ["THRL_TEN_MAX_LDS", "THRL_STAT_MAX_CELLS", "THRL_STAT_MAX_ITERS", "THRL_EQ_MAX_ITERS",
                           "THRL_TP_MAX_TUPLES", "THRL_ABI_VERSION"])
-    assert got == mine[:1] + [_lib.TEN_MAX_LDS, _lib.STAT_MAX_CELLS, _lib.STAT_MAX_ITERS, _lib.EQ_MAX_ITERS, 4096, 3] + mine[1:]
-    assert "thrl_tuple_equilibrium_noise" in _lib.SYMBOLS and TM.MAX_ITERS == _lib.EQ_MAX_ITERS and _lib.ABI_VERSION == 3
+    assert got == mine[:1] + [_lib.TEN_MAX_LDS, _lib.STAT_MAX_CELLS, _lib.STAT_MAX_ITERS, _lib.EQ_MAX_ITERS, 4096, 4] + mine[1:]
+    assert "thrl_tuple_equilibrium_noise" in _lib.SYMBOLS and TM.MAX_ITERS == _lib.EQ_MAX_ITERS and _lib.ABI_VERSION == 4
 
 
 # ------------------------------------------------------------------------------------------------ summary, readers

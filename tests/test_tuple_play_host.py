@@ -222,8 +222,8 @@ def test_args_structs_and_limits_match_header():
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
     P, W = _lib.TuplePolicyArgs, _lib.TupleWalkArgs
     assert got == [ctypes.sizeof(P), P.kind.offset, P.nn_params.offset, P.price.offset, P.tuple_policy.offset,
-                   ctypes.sizeof(W), W.seat.offset, W.cycle_start.offset, W.action_rows.offset, 4096, 3]
-    assert _lib.TP_MAX_TUPLES == tp.MAX_TUPLES == 4096 and _lib.ABI_VERSION == 3
+                   ctypes.sizeof(W), W.seat.offset, W.cycle_start.offset, W.action_rows.offset, 4096, 4]
+    assert _lib.TP_MAX_TUPLES == tp.MAX_TUPLES == 4096 and _lib.ABI_VERSION == 4
     assert "thrl_tuple_policy" in _lib.SYMBOLS and "thrl_tuple_walk" in _lib.SYMBOLS
 
 

@@ -10,7 +10,7 @@ MAXA = 8
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_WAVE, KERNEL_WAVE_PLAIN, KERNEL_WAVE_GREEDY, KERNEL_TUPLE = 0, 1, 2, 3, 4, 5
 KERNEL_NAMES = {0: "auto", 1: "generic", 2: "wave", 5: "tuple"}
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class ThrlError(RuntimeError):
@@ -501,6 +501,7 @@ def load():
     L.thrl_play_greedy.restype = ctypes.c_int
     L.thrl_play_greedy.argtypes = [cfgp, vp, vp, i32, u64, u64, vp, vp, vp]
     L.thrl_op_sample_action.restype = ctypes.c_int
+    # (choice: device int32 [G] since ABI v4 -- an int8 buffer here is read four games to the word)
     L.thrl_op_sample_action.argtypes = [cfgp, ctypes.c_int, vp, vp, dbl, vp, vp, ctypes.c_int, vp, vp]
     L.thrl_op_env_step.restype = ctypes.c_int
     L.thrl_op_env_step.argtypes = [cfgp, vp, vp, vp, vp, vp, vp]
@@ -520,6 +521,7 @@ def load():
     L.thrl_nn_reinforce_train.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, i32, i32, i32, vp, vp, vp,
                                           dbl, dbl, dbl, vp, vp, vp, vp, vp]
     L.thrl_op_draws.restype = ctypes.c_int
+    # (choice_out: device int32 [N][G] since ABI v4)
     L.thrl_op_draws.argtypes = [cfgp, u64, u64, u64, i32, vp, vp, vp, vp, vp, vp]
     L.thrl_cac_init.restype = ctypes.c_int
     L.thrl_cac_init.argtypes = [ctypes.c_int, vp, u64, u64, ctypes.c_int, vp]

@@ -38,6 +38,15 @@ def _require_gpu(device):
     return torch.device(device)
 
 
+def as_int8(a, name):
+    """An injected integer array in the recorded format (int8), or ThrlError: astype alone would wrap a value of 128 and
+    more silently.  The one range test of both batch classes (GameBatch.run, mixed.check_injection)."""
+    a = np.asarray(a)
+    if a.dtype != np.int8 and a.size and (a.min() < -128 or a.max() > 127):
+        raise ThrlError("injected %r does not fit int8" % name)
+    return np.ascontiguousarray(a, dtype=np.int8)
+
+
 def check_smooth(smooth, n_agents, n_games, per_game_logs, group_stats):
     """run(smooth=...) of both batch classes: a Smoother of this batch's games, with something to show for it."""
     if smooth is None:
@@ -200,9 +209,9 @@ class GameBatch(AnalysisMethods):
             injected = inj is not None
             if injected:
                 u = np.asarray(inj["u"], np.float64)
-                ch = np.asarray(inj["choice"], np.int8)
-                if u.shape != (E, T, N, G) or ch.shape != (E, T, N, G):
+                if u.shape != (E, T, N, G) or np.shape(inj["choice"]) != (E, T, N, G):
                     raise ThrlError("injected draws must have shape [E,T,N,G]=%r" % ((E, T, N, G),))
+                ch = as_int8(inj["choice"], "choice")
                 b.inj_u, b.inj_choice = self._ptr(dev(u, torch.float64)), self._ptr(dev(ch, torch.int8))
                 if self.cfg.noise_prob > 0:
                     nu = np.asarray(inj["noise_u"], np.float64)

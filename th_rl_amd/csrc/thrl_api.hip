@@ -553,7 +553,22 @@ int thrl_qtable_init(const thrl_cfg* c, void* q, int32_t* counter, double* state
     return e ? hip_fail(e, "k_init launch") : THRL_OK;
 }
 
+// inj_choice is one byte per draw, read unsigned-then-clamped by every kernel, and the callers' arrays are int8: an agent
+// with more actions than that format holds cannot replay a reference run, whose choices reach n_actions - 1
+constexpr int kInjMaxActions = 128;
+static int inj_choice_fits(const thrl_cfg* c, const int32_t* kind, const char* who) {
+    for (int i = 0; i < c->n_agents; i++)
+        if ((!kind || kind[i] == 0) && c->n_actions[i] > kInjMaxActions)
+            return fail(THRL_ERR_BAD_CONFIG, "%s: injection: QTable agent %d has %d actions, inj_choice (int8) holds the choices of at most %d",
+                        who, i, c->n_actions[i], kInjMaxActions);
+    return THRL_OK;
+}
+
 static int run_generic(const thrl_cfg* c, const thrl_buffers* b, thrl_run* run, hipStream_t s) {
+    if (b->inj_u) {
+        const int rc = inj_choice_fits(c, nullptr, "thrl_qtable_episodes");
+        if (rc) return rc;
+    }
     if ((b->sweep_eps_end || b->sweep_eps_step) && !b->sweep_eps)
         return fail(THRL_ERR_NULL, "sweep_eps_end / sweep_eps_step need the per-game epsilon state sweep_eps");
     if (b->sweep_noise_prob && !(c->noise_prob > 0.0))
@@ -858,7 +873,7 @@ static int op_common(const thrl_cfg* c, OpArgs* a) {
 }
 
 int thrl_op_sample_action(const thrl_cfg* c, int agent, const void* q, const double* price, double eps,
-                          const double* u, const int8_t* choice, int encode32, int32_t* action_out,
+                          const double* u, const int32_t* choice, int encode32, int32_t* action_out,
                           void* stream) {
     OpArgs a;
     int rc = op_common(c, &a);
@@ -1193,6 +1208,10 @@ int thrl_mixed_episodes(const thrl_cfg* c, thrl_mixed* mx, void* q, int32_t* cou
         }
         if (has_q && (!mx->inj_u || !mx->inj_choice))
             return fail(THRL_ERR_BAD_CONFIG, "injection: a QTable agent needs inj_u and inj_choice");
+        if (has_q) {
+            const int rc = inj_choice_fits(c, mx->kind, "thrl_mixed_episodes");
+            if (rc) return rc;
+        }
         if (has_policy && !mx->inj_action)
             return fail(THRL_ERR_BAD_CONFIG, "injection: a Reinforce / ActorCritic agent needs inj_action");
         if (c->noise_prob > 0.0 && (!mx->inj_noise_u || !mx->inj_noise_a))
@@ -1323,7 +1342,7 @@ int thrl_cac_train(int n_games, float* params, float* adam_m, float* adam_v, int
 }
 
 int thrl_op_draws(const thrl_cfg* c, uint64_t seed, uint64_t game_offset, uint64_t episode, int32_t step,
-                  double* u_out, int8_t* choice_out, double* u2_out, double* noise_u_out, double* noise_a_out,
+                  double* u_out, int32_t* choice_out, double* u2_out, double* noise_u_out, double* noise_a_out,
                   void* stream) {
     int rc = validate(c);
     if (rc) return rc;

@@ -57,7 +57,8 @@ __global__ void __launch_bounds__(256) k_generic_episodes(const GenericArgs a) {
                 double u; int ch;
                 if (a.inj_u) {
                     const size_t k = (((size_t)e * T_steps + t) * N + i) * G + gc;
-                    u = a.inj_u[k]; ch = a.inj_choice[k];
+                    // the byte as the other kernels read it: unsigned, and one that is no action of the agent is the last one
+                    u = a.inj_u[k]; ch = (int)min((uint32_t)(uint8_t)a.inj_choice[k], (uint32_t)(p.n_actions - 1));
                 } else {
                     if ((i & 1) == 0) x = draw(a.seed, gid, eg, (uint32_t)t, (uint32_t)(i >> 1));
                     const uint32_t xu = (i & 1) ? x.z : x.x, xc = (i & 1) ? x.w : x.y;

@@ -236,7 +236,7 @@ struct OpArgs {
     EnvParams env;
     AgentParams ag[THRL_MAXA];
     void* q; int32_t* counter;
-    const double* price; const double* next_price; const double* u; const int8_t* choice;
+    const double* price; const double* next_price; const double* u; const int32_t* choice;
     const int32_t* action; const double* reward; const double* noise_u; const double* noise_a;
     const double* scaled;
     double eps;
@@ -304,7 +304,7 @@ int launch_cac_train(int G, float* params, float* m, float* v, int step, int N, 
                      const double* reward, const double* nprice, float gamma, float ent, float lr,
                      const double* gamma_g, const double* ent_g, float* grad, hipStream_t s);
 int launch_op_draws(int G, int N, uint64_t seed, uint64_t off, uint32_t episode, uint32_t step, double env_a,
-                    double noise_lo, const int32_t* nA, double* u, int8_t* ch, double* u2, double* nu, double* na,
+                    double noise_lo, const int32_t* nA, double* u, int32_t* ch, double* u2, double* nu, double* na,
                     hipStream_t s);
 
 }  // namespace thrl

@@ -987,7 +987,7 @@ __global__ void __launch_bounds__(64) k_nn_returns(int G, int N, int ld, const d
 // Philox draws of one lockstep step (same counters as the episode kernels)
 __global__ void __launch_bounds__(256) k_op_draws(int G, int N, uint64_t seed, uint64_t game_offset,
         uint32_t episode, uint32_t step, double env_a, double noise_lo, int32_t nA0, int32_t nA1, int32_t nA2,
-        int32_t nA3, int32_t nA4, int32_t nA5, int32_t nA6, int32_t nA7, double* u_out, int8_t* choice_out,
+        int32_t nA3, int32_t nA4, int32_t nA5, int32_t nA6, int32_t nA7, double* u_out, int32_t* choice_out,
         double* u2_out, double* noise_u_out, double* noise_a_out) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
@@ -998,7 +998,7 @@ __global__ void __launch_bounds__(256) k_op_draws(int G, int N, uint64_t seed, u
         if ((i & 1) == 0) x = draw(seed, gid, episode, step, (uint32_t)(i >> 1));
         const uint32_t xu = (i & 1) ? x.z : x.x, xc = (i & 1) ? x.w : x.y;
         u_out[(size_t)i * G + g] = u01_32(xu);
-        choice_out[(size_t)i * G + g] = (int8_t)__umulhi(xc, (uint32_t)nA[i]);
+        choice_out[(size_t)i * G + g] = (int32_t)__umulhi(xc, (uint32_t)nA[i]);      // < nA[i] <= 32,000: no narrower type holds it
         if (u2_out) u2_out[(size_t)i * G + g] = u01_32(xc);      // the second word as a uniform (CAC's Box-Muller)
     }
     if (noise_u_out) {
@@ -1058,7 +1058,7 @@ int launch_nn_train(int G, int A, float* params, float* m, float* v, int step, i
     return (int)hipGetLastError();
 }
 int launch_op_draws(int G, int N, uint64_t seed, uint64_t off, uint32_t episode, uint32_t step, double env_a,
-                    double noise_lo, const int32_t* nA, double* u, int8_t* ch, double* u2, double* nu, double* na,
+                    double noise_lo, const int32_t* nA, double* u, int32_t* ch, double* u2, double* nu, double* na,
                     hipStream_t s) {
     hipLaunchKernelGGL(k_op_draws, dim3((G + 255) / 256), dim3(256), 0, s, G, N, seed, off, episode, step, env_a,
                        noise_lo, nA[0], nA[1], nA[2], nA[3], nA[4], nA[5], nA[6], nA[7], u, ch, u2, nu, na);

@@ -114,7 +114,9 @@ __global__ void __launch_bounds__(256) k_op_sample(const OpArgs a) {
     const AgentParams& p = a.ag[a.agent];
     int aa;
     if (a.u && a.u[g] < a.eps) {
-        aa = a.choice[g];
+        // a choice that is no action of the agent counts as the last one (the fused kernels' rule for injected values):
+        // a bad caller array cannot index outside the table
+        aa = (int)min((uint32_t)a.choice[g], (uint32_t)(p.n_actions - 1));
     } else {
         const int row = a.encode32 ? encode32(a.price[g], p) : encode64(a.price[g], p);
         const T* qg = reinterpret_cast<const T*>(a.q) + (int64_t)g * a.stride + p.table_off;

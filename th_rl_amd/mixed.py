@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import ThrlError
 from .analysis import AnalysisMethods
-from .batched import _require_gpu, _torch, check_smooth
+from .batched import _require_gpu, _torch, as_int8, check_smooth
 from .nn import ActorCriticBatch, CACBatch, ReinforceBatch
 
 NN_DEFAULTS = dict(states=4, actions=2, action_range=[0, 1], gamma=0.98, capacity=50000, min_memory=1000,
@@ -33,12 +33,16 @@ NN_DEFAULTS = dict(states=4, actions=2, action_range=[0, 1], gamma=0.98, capacit
 INJ_KEYS = ("u", "choice", "action", "noise_u", "noise_a")
 
 
-def check_injection(inj, E, T, N, G, kinds, noise):
+INJ_MAX_ACTIONS = 128       # what one int8 choice holds: the library refuses injection for a wider QTable agent
+
+
+def check_injection(inj, E, T, N, G, kinds, noise, actions=None):
     """Validate the parity-mode arrays of MixedGameBatch.run (host only, no device needed).  inj: dict of arrays,
     `u` (float64), `choice`, `action` (int8) of shape [E, T, N, G] and `noise_u`, `noise_a` (float64) of shape [E, T, G].
     All or nothing: `u` and `choice` are required with a QTable agent in the game, `action` with a Reinforce /
     ActorCritic agent, the two noise arrays with noise_prob > 0.  Returns the arrays the game consumes, C-contiguous
-    in the library's dtypes."""
+    in the library's dtypes.  actions (per agent, optional): a QTable agent of more than INJ_MAX_ACTIONS actions is refused,
+    as thrl_mixed_episodes refuses it: the recorded format cannot hold its choices."""
     if not isinstance(inj, dict):
         raise ThrlError("inj must be a dict of arrays (keys: %s)" % ", ".join(INJ_KEYS))
     unknown = sorted(set(inj) - set(INJ_KEYS))
@@ -47,6 +51,13 @@ def check_injection(inj, E, T, N, G, kinds, noise):
     if "CAC" in kinds:
         raise ThrlError("a game with a CAC agent cannot run from injected draws: its action is a float and the "
                         "reference's play path for it cannot run")
+    if actions is not None:
+        for i, k in enumerate(kinds):
+            if k == "QTable" and int(actions[i]) > INJ_MAX_ACTIONS:
+                e = ThrlError("injection: QTable agent %d has %d actions, inj_choice (int8) holds the choices of at most %d"
+                              % (i, int(actions[i]), INJ_MAX_ACTIONS))
+                e.code = _lib.ERR_BAD_CONFIG
+                raise e
     need = []
     if "QTable" in kinds:
         need += ["u", "choice"]
@@ -66,9 +77,7 @@ def check_injection(inj, E, T, N, G, kinds, noise):
         if a.shape != shape:
             raise ThrlError("injected %r must have shape %s=%r, got %r"
                             % (k, "[E,T,G]" if k.startswith("noise") else "[E,T,N,G]", shape, a.shape))
-        if dt is np.int8 and a.dtype != np.int8 and a.size and (a.min() < -128 or a.max() > 127):
-            raise ThrlError("injected %r does not fit int8" % k)
-        out[k] = np.ascontiguousarray(a, dtype=dt)
+        out[k] = as_int8(a, k) if dt is np.int8 else np.ascontiguousarray(a, dtype=dt)
     return out
 
 
@@ -254,7 +263,7 @@ class MixedGameBatch(AnalysisMethods):
             mr = torch.zeros((iters, N, G), dtype=torch.float64, device=self.device)
             ma = torch.zeros((iters, N, G), dtype=torch.float64, device=self.device)
             u = torch.zeros((N, G), dtype=torch.float64, device=self.device)
-            ch = torch.zeros((N, G), dtype=torch.int8, device=self.device)
+            ch = torch.zeros((N, G), dtype=torch.int32, device=self.device)
             nu = torch.zeros((G,), dtype=torch.float64, device=self.device) if noise else None
             na = torch.zeros((G,), dtype=torch.float64, device=self.device) if noise else None
             acts = torch.zeros((N, G), dtype=torch.int32, device=self.device)
@@ -385,7 +394,8 @@ class MixedGameBatch(AnalysisMethods):
         game_action_smooth (keep_games applies).  Both paths take it."""
         check_smooth(smooth, self.N, self.G, per_game_logs or fused is False, group_stats)
         if inj is not None:
-            inj = check_injection(inj, int(n_episodes), self.T, self.N, self.G, self.kinds, self.cfg.noise_prob > 0)
+            inj = check_injection(inj, int(n_episodes), self.T, self.N, self.G, self.kinds, self.cfg.noise_prob > 0,
+                                  actions=[self.cfg.n_actions[i] for i in range(self.N)])
         if fused is None:
             first = self.episode
             try:
@@ -533,7 +543,7 @@ class MixedGameBatch(AnalysisMethods):
             rlog = torch.zeros((E, N, G), dtype=torch.float64, device=self.device)
             alog = torch.zeros((E, N, G), dtype=torch.float64, device=self.device)
             u = torch.zeros((N, G), dtype=torch.float64, device=self.device)
-            ch = torch.zeros((N, G), dtype=torch.int8, device=self.device)
+            ch = torch.zeros((N, G), dtype=torch.int32, device=self.device)
             has_cac = "CAC" in self.kinds
             u2 = torch.zeros((N, G), dtype=torch.float64, device=self.device) if has_cac else None
             acts_f = torch.zeros((N, G), dtype=torch.float32, device=self.device) if has_cac else None
@@ -548,6 +558,8 @@ class MixedGameBatch(AnalysisMethods):
             # reference's IEEE division
             T_t = torch.tensor(float(T), dtype=torch.float64, device=self.device)
             dinj = self._inj_to_device(inj) if inj is not None else None
+            if dinj is not None and "choice" in dinj:      # the operators carry a choice as int32: the recorded bytes, once
+                dinj["choice"] = (dinj["choice"].to(torch.int32) & 0xFF).contiguous()
             for e in range(E):
                 for t in range(T):
                     if dinj is None:
