@@ -113,6 +113,17 @@ def test_3000_state_config_direct_extraction_and_gathered_walk():
     _check(gb, BIG, _rotate(G, 9), state0=np.linspace(0.5, 9.5, G), steps=4)
 
 
+def test_three_agents_gathered_walk():
+    """Three agents of 1,000 states each: the policy windows are past the walk's LDS budget (k_xplay_walk<gathered, 8>)."""
+    config = {"agents": [dict(a, states=1000) for a in THREE["agents"]], "environment": THREE["environment"]}
+    G = 300                                                             # a full block of 256 lanes and a partial one
+    gb = _batch(config, G, seed=8)
+    _check(gb, config, _rotate(G, 1, 3), strangers=False)
+    rs = np.random.RandomState(8)
+    out = _check(gb, config, rs.randint(0, G, size=(3, G)), state0=rs.uniform(0, 10, G), steps=3, horizon=3, strangers=False)
+    assert (out["lam"] == 0).any() and (out["mu"][out["lam"] == 0] == 3).all()
+
+
 def test_unaligned_tables_take_the_direct_extraction_path():
     import torch
     from th_rl_amd import crossplay as xp

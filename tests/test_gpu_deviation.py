@@ -86,6 +86,28 @@ def test_direct_path_matches_mirror():
     _check(gb, BIG, deviator=0, steps=8, dev_len=2, action=5, state0=np.linspace(0.5, 9.5, 128))
 
 
+# Three agents on every path of the plan (k_deviation<.., 8>): the staged policy in one byte, in two bytes (257 actions
+# on 12 states: the windows still fit the LDS budget), and the direct path (1,000 states each: they do not)
+_A3 = [dict(AG, actions=7, states=30, action_range=[0.1, 0.5]), dict(AG, actions=11, states=30, action_range=[0.2, 0.4], gamma=0.9),
+       dict(AG, actions=5, states=40, action_range=[0.0, 0.3])]
+THREE_PATHS = {
+    "one-byte": {"agents": _A3, "environment": dict(ENV, nplayers=3, max_steps=40)},
+    "two-byte": {"agents": [dict(_A3[0], actions=257, states=12)] + _A3[1:], "environment": dict(ENV, nplayers=3, max_steps=40)},
+    "direct": {"agents": [dict(a, states=1000) for a in _A3], "environment": dict(ENV, nplayers=3, max_steps=40)},
+}
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("name", list(THREE_PATHS))
+def test_three_agents_on_every_path(name, dtype):
+    config, G = THREE_PATHS[name], 300                      # a full block of 256 lanes and a partial one
+    gb = _batch(config, G, dtype, seed=9)
+    _check(gb, config, deviator=0, steps=6, dev_len=2)
+    # a horizon of 3: games whose cycle closes later report mu = 3, lam = 0, before and after the deviation
+    out = _check(gb, config, deviator=2, steps=5, dev_len=1, action=1, horizon=3, state0=np.linspace(0.0, 10.0, G))
+    assert (out["lam"] == 0).any() and (out["mu"][out["lam"] == 0] == 3).all()
+
+
 def test_gamma_sweep_discounts_with_the_games_gamma():
     G = 256
     gam = np.array([[0.35, 0.9, 0.95, 0.5][g % 4] for g in range(G)])

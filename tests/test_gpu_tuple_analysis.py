@@ -247,6 +247,28 @@ def test_4096_tuples_exactly():
         _bits_equal(dev[f], ref[f], f)
 
 
+def test_three_agents_with_tables_in_global_memory():
+    """16 x 11 x 8 = 1,408 tuples of three agents: 2 N T doubles are past the deviation's LDS budget, so
+    k_ta_deviation<global, 8> reads the reward and scaled tables from global memory."""
+    from th_rl_amd import tuple_play as tp
+    config = {"agents": [dict(THREE["agents"][0], actions=16), THREE["agents"][1], dict(THREE["agents"][2], actions=8)],
+              "environment": THREE["environment"]}
+    n = 300                                                             # a full block of 256 lanes and a partial one
+    mb, gam = _mixed(config, n_games=n, seed=29, weights_seed=11)
+    tabs = tp.tables(config)
+    assert tabs["T"] == 1408 and 2 * 3 * tabs["T"] * 8 > 64 * 1024
+    given = tp.extract(mb)
+    pol = given.cpu().numpy().view(np.uint16)
+    start = _starts(tabs["T"], n, 31)
+    for d, horizon in ((0, None), (2, 2)):                              # horizon 2: lam = 0 where the cycle closes later
+        kw = {} if horizon is None else {"horizon": horizon}
+        dev = mb.greedy_deviation(deviator=d, steps=5, dev_len=2, start=start, rows=True, tuple_policy=given, **kw)
+        ref = DM.analyse(tabs, pol, start, deviator=d, steps=5, dev_len=2, gamma=gam[d], **kw)
+        for f in DEV_OUT + ROWS:
+            _bits_equal(dev[f], ref[f], "d=%d %s" % (d, f))
+    assert ((dev["lam"] == 0) & (dev["mu"] == 2)).any()
+
+
 def test_one_game_halves_and_nothing_written():
     import torch
     from th_rl_amd import tuple_play as tp

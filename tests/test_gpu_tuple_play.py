@@ -244,6 +244,28 @@ def test_other_configs_match_mirror(name):
     _check(mb, tabs, pol, rs.randint(0, 96, size=(N, 150)), rs.randint(0, T, size=150), steps=4)
 
 
+# reward and scaled tables past the LDS budget (2 N T doubles > 64 KiB): k_tp_walk reads them from global memory
+GLOBAL_TABLES = {"TWO": ({"agents": [dict(AG, actions=128), dict(RF, actions=32)], "environment": dict(ENV)}, 4096),
+                 "THREE": ({"agents": [dict(THREE["agents"][0], actions=16), THREE["agents"][1], dict(THREE["agents"][2], actions=8)],
+                            "environment": THREE["environment"]}, 1408)}
+
+
+@pytest.mark.parametrize("name", list(GLOBAL_TABLES))
+def test_tables_in_global_memory_match_mirror(name):
+    from th_rl_amd import tuple_play as tp
+    config, T = GLOBAL_TABLES[name]
+    N = len(config["agents"])
+    assert 2 * N * T * 8 > 64 * 1024
+    mb = _mixed(config, n_games=40, seed=17, weights_seed=8)
+    tabs, pol = tp.tables(config), _policy(mb)
+    assert tabs["T"] == T
+    rs = np.random.RandomState(5)
+    seats, start = rs.randint(0, 40, size=(N, 300)), rs.randint(0, T, size=300)     # a full block of 256 lanes and a partial one
+    _check(mb, tabs, pol, seats, start, steps=4, strangers=False)
+    out = _check(mb, tabs, pol, seats, start, horizon=2, steps=0, strangers=False)
+    assert (out["lam"] == 0).any() and (out["mu"][out["lam"] == 0] == 2).all()
+
+
 # ------------------------------------------------------------------------------------------------ existing analyses
 def test_all_qtable_batch_against_crossplay():
     from th_rl_amd import crossplay as xp, tuple_play as tp

@@ -12,8 +12,11 @@
 //   LDS (consecutive lanes take consecutive entries of one game's window, so the gather is a run of 2-byte loads per
 //   seat) together with a LUT of every agent's scaled actions; the walk then touches no global memory.  Configs whose
 //   windows do not fit kXpLdsBudget gather each visited entry from the policy array.  Both paths walk the same map with
-//   the same operations, so both give the same bits.
+//   the same operations, so both give the same bits.  The cycle search, the refused match's zeros, the store of the
+//   means and of the row slice, the window lookup and the LUT fill are thrl_walk_dev.h's.
 #include "thrl_crossplay.h"
+
+#include "thrl_walk_dev.h"
 
 namespace thrl {
 
@@ -97,29 +100,11 @@ template <bool kStaged, int MAXN>
 __device__ __forceinline__ int policy(const XpWalkArgs& a, const Seats<kStaged, MAXN>& v, int i, int r) {
     int act;
     if constexpr (kStaged) {
-        int k = r - a.win_lo[i];
-        if ((unsigned)k >= (unsigned)a.win_n[i]) k = a.win_n[i];      // outside the window only x_0's row is visited
-        act = (int)v.pol[(a.pol_off[i] + k) * kXpTile];
+        act = (int)v.pol[window_entry(a, i, r) * kXpTile];
     } else {
         act = (int)v.gp[i][r];
     }
     return min(act, a.ag[i].n_actions - 1);
-}
-
-template <int MAXN>
-__device__ __forceinline__ void copy_rows(int* dst, const int* src, int N) {
-#pragma unroll
-    for (int i = 0; i < MAXN; i++)
-        if (i < N) dst[i] = src[i];
-}
-
-template <int MAXN>
-__device__ __forceinline__ bool same_rows(const int* x, const int* y, int N) {
-    bool e = true;
-#pragma unroll
-    for (int i = 0; i < MAXN; i++)
-        if (i < N) e = e && x[i] == y[i];
-    return e;
 }
 
 // One transition from x under the greedy policies: scaled actions, rewards, and the next rows into x.
@@ -138,58 +123,6 @@ __device__ __forceinline__ void step(const XpWalkArgs& a, const Seats<kStaged, M
         if (i < N) x[i] = encode64_fast(p, a.ag[i]);
 }
 
-// x <- F(x): the greedy map on row tuples
-template <bool kStaged, int MAXN>
-__device__ __forceinline__ void greedy_map(const XpWalkArgs& a, const Seats<kStaged, MAXN>& v, int* x) {
-    double sc[MAXN], rew[MAXN];
-    step<kStaged, MAXN>(a, v, sc, rew, x);
-}
-
-// Cycle of F from x0 within the horizon H (Brent, O(1) state), the search of k_deviation: found iff mu + lam <= H,
-// then s = x_mu; otherwise mu = H, lam = 0.  Phase 1 stops at hare position 3H: if mu + lam <= H it detects the
-// period by then (the tortoise sits at 2^k - 1 and detection comes at the first 2^k >= max(lam, mu + 1), so the hare
-// is at 2^k - 1 + lam <= 3H - 2); phase 2 stops as soon as mu + lam would pass H.
-template <bool kStaged, int MAXN>
-__device__ __forceinline__ void find_cycle(const XpWalkArgs& a, const Seats<kStaged, MAXN>& v, const int* x0, int& mu,
-                                           int& lam, int* s) {
-    const int N = a.N, H = a.H;
-    int tort[MAXN], hare[MAXN];
-    copy_rows<MAXN>(tort, x0, N);
-    copy_rows<MAXN>(hare, x0, N);
-    greedy_map<kStaged, MAXN>(a, v, hare);
-    int power = 1, l = 1, pos = 1;
-    bool det = false;
-    for (;;) {
-        if (same_rows<MAXN>(tort, hare, N)) { det = true; break; }
-        if (pos >= 3 * H) break;
-        if (power == l) { copy_rows<MAXN>(tort, hare, N); power <<= 1; l = 0; }
-        greedy_map<kStaged, MAXN>(a, v, hare);
-        l++;
-        pos++;
-    }
-    bool found = det && l <= H;
-    int m = 0;
-    if (found) {
-        copy_rows<MAXN>(tort, x0, N);
-        copy_rows<MAXN>(hare, x0, N);
-        for (int j = 0; j < l; j++) greedy_map<kStaged, MAXN>(a, v, hare);
-        while (!same_rows<MAXN>(tort, hare, N)) {
-            if (m + l >= H) { found = false; break; }
-            greedy_map<kStaged, MAXN>(a, v, tort);
-            greedy_map<kStaged, MAXN>(a, v, hare);
-            m++;
-        }
-    }
-    if (found) {
-        mu = m;
-        lam = l;
-        copy_rows<MAXN>(s, tort, N);
-    } else {
-        mu = H;
-        lam = 0;
-    }
-}
-
 template <bool kStaged, int MAXN>
 __global__ void __launch_bounds__(kXpTile) k_xplay_walk(const XpWalkArgs a) {
     extern __shared__ __align__(16) unsigned char s_mem[];
@@ -199,29 +132,18 @@ __global__ void __launch_bounds__(kXpTile) k_xplay_walk(const XpWalkArgs a) {
     const int64_t m = m0 + tid;
     double* lut = reinterpret_cast<double*>(s_mem);
     uint16_t* pol = reinterpret_cast<uint16_t*>(s_mem + (a.use_lut ? ((a.lut_n * 8 + 15) & ~15) : 0));
-    if (a.use_lut) {
-        for (int j = tid; j < a.lut_n; j += kXpTile) {
-            int i = 0;
-            while (i + 1 < N && j >= a.lut_off[i + 1]) i++;
-            lut[j] = scale_action(j - a.lut_off[i], a.ag[i]);
-        }
-    }
+    if (a.use_lut) fill_scale_lut(a, lut, tid, kXpTile);
     if constexpr (kStaged) {
         // entry e of local match ml at item ml * E + e: consecutive lanes take consecutive rows of one seat's window
         const int E = a.pol_entries;
         const int n_loc = (int)(M - m0 < kXpTile ? M - m0 : kXpTile);
         for (int it = tid; it < n_loc * E; it += kXpTile) {
             const int ml = it / E, e = it - ml * E;
-            int i = 0;
-            while (i + 1 < N && e >= a.pol_off[i + 1]) i++;
+            const int i = window_agent(a, e);
             const int64_t g = a.seat[(int64_t)i * M + m0 + ml];
             uint16_t act = 0;
-            if (g >= 0 && g < a.G) {                     // a seat out of range reads nothing
-                const AgentParams& p = a.ag[i];
-                const int k = e - a.pol_off[i];
-                const int row = k < a.win_n[i] ? a.win_lo[i] + k : encode64_fast(a.state0[m0 + ml], p);
-                act = a.policy[g * a.P + a.row_off[i] + row];
-            }
+            if (g >= 0 && g < a.G)                       // a seat out of range reads nothing
+                act = a.policy[g * a.P + a.row_off[i] + window_row(a, i, e, a.state0[m0 + ml])];
             pol[e * kXpTile + ml] = act;
         }
     }
@@ -240,21 +162,10 @@ __global__ void __launch_bounds__(kXpTile) k_xplay_walk(const XpWalkArgs a) {
         ok = ok && in;
         if constexpr (!kStaged) v.gp[i] = a.policy + (in ? g : 0) * a.P + a.row_off[i];
     }
-    const int64_t plane = (int64_t)N * M;
-    const int n_rows = a.row_count;
-
     if (!ok) {                                          // the stated sentinel: mu = -1, lam = 0 and zeros
         a.mu[m] = -1;
         a.lam[m] = 0;
-        for (int i = 0; i < N; i++) {
-            a.cycle_reward[(int64_t)i * M + m] = 0.0;
-            a.cycle_action[(int64_t)i * M + m] = 0.0;
-            for (int rr = 0; rr < n_rows; rr++) {
-                const int64_t o = (int64_t)rr * plane + (int64_t)i * M + m;
-                if (a.reward_rows) a.reward_rows[o] = 0.0;
-                if (a.action_rows) a.action_rows[o] = 0.0;
-            }
-        }
+        store_refused(a, m, M);
         return;
     }
 
@@ -264,7 +175,12 @@ __global__ void __launch_bounds__(kXpTile) k_xplay_walk(const XpWalkArgs a) {
     for (int i = 0; i < MAXN; i++)
         if (i < N) x0[i] = encode64_fast(st, a.ag[i]);
     int mu, lam;
-    find_cycle<kStaged, MAXN>(a, v, x0, mu, lam, s);
+    find_cycle(x0, N, a.H, [&](int* x) THRL_WALK_INLINE {               // x <- F(x): the greedy map on row tuples
+        double sc[MAXN], rew[MAXN];
+        step<kStaged, MAXN>(a, v, sc, rew, x);
+    }, mu, lam, s, false);
+    // cycle_means of thrl_walk_dev.h, kept inline: through the shared function <direct, 8> takes 196 VGPRs for 156 and
+    // loses a wave per SIMD (profiles/walk_shared_resource_usage.txt)
     double cr[MAXN], ca[MAXN];
 #pragma unroll
     for (int i = 0; i < MAXN; i++) { cr[i] = 0.0; ca[i] = 0.0; }
@@ -284,31 +200,17 @@ __global__ void __launch_bounds__(kXpTile) k_xplay_walk(const XpWalkArgs a) {
     }
     a.mu[m] = mu;
     a.lam[m] = lam;
-#pragma unroll
-    for (int i = 0; i < MAXN; i++) {
-        if (i >= N) break;
-        a.cycle_reward[(int64_t)i * M + m] = cr[i];
-        a.cycle_action[(int64_t)i * M + m] = ca[i];
-    }
+    store_means<MAXN>(a, m, M, cr, ca);
 
     // the path from x_0: the rows of tau in [row_begin, row_begin + row_count)
-    if (n_rows > 0 && (a.reward_rows || a.action_rows)) {
+    if (a.row_count > 0 && (a.reward_rows || a.action_rows)) {
         int x[MAXN];
         double sc[MAXN], rew[MAXN];
         copy_rows<MAXN>(x, x0, N);
-        const int end = a.row_begin + n_rows;
+        const int end = a.row_begin + a.row_count;
         for (int t = 0; t < end; t++) {
             step<kStaged, MAXN>(a, v, sc, rew, x);
-            const int rr = t - a.row_begin;
-            if (rr >= 0) {
-#pragma unroll
-                for (int i = 0; i < MAXN; i++) {
-                    if (i >= N) break;
-                    const int64_t o = (int64_t)rr * plane + (int64_t)i * M + m;
-                    if (a.reward_rows) a.reward_rows[o] = rew[i];
-                    if (a.action_rows) a.action_rows[o] = sc[i];
-                }
-            }
+            store_step<MAXN>(a, t, m, M, StepOut{rew, sc, 1});
         }
     }
 }

@@ -3,9 +3,11 @@
 // QTable, Reinforce and ActorCritic agents, on the uint16 tables thrl_tuple_policy writes.  No encode, no network and
 // no env arithmetic: rewards and scaled actions are looked up in the caller's per-config tables.  Two kernels.
 //
-// k_ta_deviation: one lane per game, k_tp_walk's shape.  The walk (Brent, the deviation and baseline paths in
-//   lockstep, the return) runs on a single integer; the 2-byte policy entries it visits are gathered from global
-//   memory and the reward / scaled tables sit in LDS when they fit kTaDevLdsBudget.
+// k_ta_deviation: one lane per game, k_tp_walk's shape.  The walk (the cycle search, the deviation and baseline paths
+//   in lockstep, the return) runs on a single integer; the 2-byte policy entries it visits are gathered from global
+//   memory and the reward / scaled tables sit in LDS when they fit kTaDevLdsBudget.  The map on tuple indices, the
+//   search, the means over the cycle, the refused game's zeros, the store of the row slice and the staging of the
+//   tables are thrl_walk_dev.h's; the lockstep loop is this file's.
 // k_ta_equilibrium: one 256-thread block per game, looping over games; lanes own the states s = tid, tid + 256, ..
 //   (at most 16 each).  The state set is the T tuples, up to four times thrl_equilibrium's 1024 states, and every
 //   doubling pass of an evaluation depends on the whole previous pass, so four waves share a game.  LDS holds, per
@@ -17,76 +19,13 @@
 //   along the cycle.  Nothing depends on the grid size or on which block takes which game.
 #include "thrl_tuple_analysis.h"
 
+#include "thrl_walk_dev.h"
+
 namespace thrl {
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ deviation
-template <int MAXN>
-struct TaView {
-    const uint16_t* gp[MAXN];       // agent i's T entries of this lane's game
-};
-
-template <int MAXN>
-__device__ __forceinline__ int ta_act(const TaDevArgs& a, const TaView<MAXN>& v, int i, int t) {
-    return min((int)v.gp[i][t], a.n_actions[i] - 1);
-}
-
-// F(t): the index of the tuple the game's agents play at t
-template <int MAXN>
-__device__ __forceinline__ int ta_next(const TaDevArgs& a, const TaView<MAXN>& v, int t) {
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < MAXN; i++)
-        if (i < a.N) n += ta_act<MAXN>(a, v, i, t) * a.tstride[i];
-    return n;
-}
-
-// Cycle of F from t0 within the horizon H, find_cycle of thrl_deviation.hip on one integer.  Found iff mu + lam <= H:
-// then s = t_mu.  Otherwise mu = H, lam = 0 and s = t_H (when want_s).
-template <int MAXN>
-__device__ __forceinline__ bool ta_cycle(const TaDevArgs& a, const TaView<MAXN>& v, int t0, int& mu, int& lam, int& s,
-                                         bool want_s) {
-    const int H = a.H;
-    int tort = t0, hare = ta_next<MAXN>(a, v, t0);
-    int power = 1, l = 1, pos = 1;
-    bool det = false;
-    for (;;) {
-        if (tort == hare) { det = true; break; }
-        if (pos >= 3 * H) break;
-        if (power == l) { tort = hare; power <<= 1; l = 0; }
-        hare = ta_next<MAXN>(a, v, hare);
-        l++;
-        pos++;
-    }
-    bool found = det && l <= H;
-    int m = 0;
-    if (found) {
-        tort = t0;
-        hare = t0;
-        for (int j = 0; j < l; j++) hare = ta_next<MAXN>(a, v, hare);
-        while (tort != hare) {
-            if (m + l >= H) { found = false; break; }
-            tort = ta_next<MAXN>(a, v, tort);
-            hare = ta_next<MAXN>(a, v, hare);
-            m++;
-        }
-    }
-    if (found) {
-        mu = m;
-        lam = l;
-        s = tort;
-    } else {
-        mu = H;
-        lam = 0;
-        if (want_s) {
-            s = t0;
-            for (int j = 0; j < H; j++) s = ta_next<MAXN>(a, v, s);
-        }
-    }
-    return found;
-}
-
 template <bool kLds, int MAXN>
 __global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) {
     extern __shared__ __align__(16) unsigned char s_mem[];
@@ -94,19 +33,9 @@ __global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) 
     const int G = a.G, N = a.N, T = a.T;
     const double* rew = a.reward;
     const double* sca = a.scaled;
-    if constexpr (kLds) {
-        double* tab = reinterpret_cast<double*>(s_mem);
-        for (int j = tid; j < N * T; j += kTaDevTile) {
-            tab[j] = a.reward[j];
-            tab[N * T + j] = a.scaled[j];
-        }
-        __syncthreads();
-        rew = tab;
-        sca = tab + N * T;
-    }
+    if constexpr (kLds) stage_tables(s_mem, N * T, tid, kTaDevTile, rew, sca);
     const int64_t g = (int64_t)blockIdx.x * kTaDevTile + tid;
     if (g >= G) return;
-    const int64_t plane = (int64_t)N * G;
     const int t0 = a.start[g];
 
     if (t0 < 0 || t0 >= T) {                            // the stated refusal: nothing of the game is read
@@ -117,41 +46,26 @@ __global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) 
         a.ret_step[g] = -1;
         a.act_dev[g] = -1;
         a.gain[g] = 0.0;
-        for (int i = 0; i < N; i++) {
-            a.cycle_reward[(int64_t)i * G + g] = 0.0;
-            a.cycle_action[(int64_t)i * G + g] = 0.0;
-            for (int rr = 0; rr < a.row_count; rr++) {
-                const int64_t o = (int64_t)rr * plane + (int64_t)i * G + g;
-                if (a.reward_rows) a.reward_rows[o] = 0.0;
-                if (a.action_rows) a.action_rows[o] = 0.0;
-            }
-        }
+        store_refused(a, g, G);
         return;
     }
 
-    TaView<MAXN> v;
+    TupleView<MAXN> v;              // this lane's game
 #pragma unroll
     for (int i = 0; i < MAXN; i++)
         v.gp[i] = a.policy + (g * N + (i < N ? i : 0)) * T;
+    // t <- the index of the tuple the game's agents play at t, and where the values of that tuple lie
+    const auto next = [&](int& t) THRL_WALK_INLINE {
+        t = tuple_next<MAXN>(a, v, t);
+        return StepOut{rew + t, sca + t, T};
+    };
 
     // pre-shock cycle
     int mu, lam, s;
-    ta_cycle<MAXN>(a, v, t0, mu, lam, s, true);
+    find_cycle(t0, N, a.H, next, mu, lam, s, true);
     double cr[MAXN], ca[MAXN];
-#pragma unroll
-    for (int i = 0; i < MAXN; i++) { cr[i] = 0.0; ca[i] = 0.0; }
-    if (lam > 0) {
-        int x = s;
-        for (int j = 0; j < lam; j++) {
-            x = ta_next<MAXN>(a, v, x);
-#pragma unroll
-            for (int i = 0; i < MAXN; i++)
-                if (i < N) { cr[i] = __dadd_rn(cr[i], rew[i * T + x]); ca[i] = __dadd_rn(ca[i], sca[i * T + x]); }
-        }
-#pragma unroll
-        for (int i = 0; i < MAXN; i++)
-            if (i < N) { cr[i] = __ddiv_rn(cr[i], (double)lam); ca[i] = __ddiv_rn(ca[i], (double)lam); }
-    }
+    int x = s;
+    cycle_means<MAXN>(N, lam, cr, ca, [&]() THRL_WALK_INLINE { return next(x); });
 
     // deviation path y and baseline path z, in lockstep
     const int d = a.d, L = a.L, K = a.K;
@@ -166,7 +80,7 @@ __global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) 
             int ub = 0;                                 // the others greedy at y
 #pragma unroll
             for (int i = 0; i < MAXN; i++)
-                if (i < N && i != d) ub += ta_act<MAXN>(a, v, i, y) * a.tstride[i];
+                if (i < N && i != d) ub += tuple_act<MAXN>(a, v, i, y) * a.tstride[i];
             int ad = a.dev_action;
             if (ad < 0) {                               // one-period best response: first maximum of d's reward
                 double bv = 0.0;
@@ -179,19 +93,10 @@ __global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) 
             if (t == 0) adev = ad;
             y = ub + ad * tsd;
         } else {
-            y = ta_next<MAXN>(a, v, y);
+            next(y);
         }
-        const int rr = t - a.row_begin;
-        if (rr >= 0 && rr < a.row_count) {
-#pragma unroll
-            for (int i = 0; i < MAXN; i++) {
-                if (i >= N) break;
-                const int64_t o = (int64_t)rr * plane + (int64_t)i * G + g;
-                if (a.reward_rows) a.reward_rows[o] = rew[i * T + y];
-                if (a.action_rows) a.action_rows[o] = sca[i * T + y];
-            }
-        }
-        z = ta_next<MAXN>(a, v, z);
+        store_step<MAXN>(a, t, g, G, StepOut{rew + y, sca + y, T});
+        next(z);
         gain = __dadd_rn(gain, __dmul_rn(w, __dsub_rn(rd[y], rd[z])));
         w = __dmul_rn(w, gam);
         if (t + 1 == L) yL = y;
@@ -199,12 +104,12 @@ __global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) 
 
     // return to the pre-shock cycle
     int mp, lp, sp = 0;
-    const bool fp = ta_cycle<MAXN>(a, v, yL, mp, lp, sp, false);
+    const bool fp = find_cycle(yL, N, a.H, next, mp, lp, sp, false);
     int ret = -1;
     if (lam > 0 && fp) {
         for (int j = 0; j < lp; j++) {
             if (sp == s) { ret = L + mp; break; }
-            sp = ta_next<MAXN>(a, v, sp);
+            next(sp);
         }
     }
 
@@ -215,12 +120,7 @@ __global__ void __launch_bounds__(kTaDevTile) k_ta_deviation(const TaDevArgs a) 
     a.ret_step[g] = ret;
     a.act_dev[g] = adev;
     a.gain[g] = gain;
-#pragma unroll
-    for (int i = 0; i < MAXN; i++) {
-        if (i >= N) break;
-        a.cycle_reward[(int64_t)i * G + g] = cr[i];
-        a.cycle_action[(int64_t)i * G + g] = ca[i];
-    }
+    store_means<MAXN>(a, g, G, cr, ca);
 }
 
 template <bool kLds>

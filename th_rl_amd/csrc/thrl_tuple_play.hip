@@ -16,10 +16,12 @@
 //   Consecutive tuples have neighbouring prices, so a wave reads a few neighbouring rows and its stores are contiguous.
 // k_tp_walk: one lane per match, the walk of k_xplay_walk on a single integer.  The 2-byte policy entries it visits
 //   are gathered from global memory (mu + lam is a handful of steps); the per-config reward and scaled-action tables
-//   sit in LDS when they fit kTpLdsBudget.
+//   sit in LDS when they fit kTpLdsBudget.  The map on tuple indices, the cycle search, the means over the cycle, the
+//   refused match's zeros, the store of the row slice and the staging of the tables are thrl_walk_dev.h's.
 #include "thrl_tuple_play.h"
 
 #include "thrl_policy.h"
+#include "thrl_walk_dev.h"
 
 namespace thrl {
 
@@ -91,42 +93,18 @@ __global__ void __launch_bounds__(256) k_tp_qtable(const TpPolicyArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ walk
-template <int MAXN>
-struct TpSeats {
-    const uint16_t* gp[MAXN];       // agent i's T entries of the seated game
-};
-
-// t <- the index of the tuple the seated agents play at t
-template <int MAXN>
-__device__ __forceinline__ int tp_next(const TpWalkArgs& a, const TpSeats<MAXN>& v, int t) {
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < MAXN; i++)
-        if (i < a.N) n += min((int)v.gp[i][t], a.n_actions[i] - 1) * a.tstride[i];
-    return n;
-}
-
 template <bool kLds, int MAXN>
 __global__ void __launch_bounds__(kTpTile) k_tp_walk(const TpWalkArgs a) {
     extern __shared__ __align__(16) unsigned char s_mem[];
     const int tid = threadIdx.x;
-    const int M = a.M, N = a.N, T = a.T, H = a.H;
+    const int M = a.M, N = a.N, T = a.T;
     const double* rew = a.reward;
     const double* sca = a.scaled;
-    if constexpr (kLds) {
-        double* tab = reinterpret_cast<double*>(s_mem);
-        for (int j = tid; j < N * T; j += kTpTile) {
-            tab[j] = a.reward[j];
-            tab[N * T + j] = a.scaled[j];
-        }
-        __syncthreads();
-        rew = tab;
-        sca = tab + N * T;
-    }
+    if constexpr (kLds) stage_tables(s_mem, N * T, tid, kTpTile, rew, sca);
     const int64_t m = (int64_t)blockIdx.x * kTpTile + tid;
     if (m >= M) return;
 
-    TpSeats<MAXN> v;
+    TupleView<MAXN> v;              // the seated games' entries
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < MAXN; i++) {
@@ -138,95 +116,34 @@ __global__ void __launch_bounds__(kTpTile) k_tp_walk(const TpWalkArgs a) {
     }
     const int t0 = a.start[m];
     ok = ok && t0 >= 0 && t0 < T;
-    const int64_t plane = (int64_t)N * M;
-    const int n_rows = a.row_count;
-
     if (!ok) {                                          // the stated sentinel: mu = -1, lam = 0 and zeros
         a.mu[m] = -1;
         a.lam[m] = 0;
         if (a.cycle_start) a.cycle_start[m] = -1;
-        for (int i = 0; i < N; i++) {
-            a.cycle_reward[(int64_t)i * M + m] = 0.0;
-            a.cycle_action[(int64_t)i * M + m] = 0.0;
-            for (int rr = 0; rr < n_rows; rr++) {
-                const int64_t o = (int64_t)rr * plane + (int64_t)i * M + m;
-                if (a.reward_rows) a.reward_rows[o] = 0.0;
-                if (a.action_rows) a.action_rows[o] = 0.0;
-            }
-        }
+        store_refused(a, m, M);
         return;
     }
 
-    // Brent, the search of k_xplay_walk: found iff mu + lam <= H; phase 1 stops at hare position 3H
-    int tort = t0, hare = tp_next<MAXN>(a, v, t0);
-    int power = 1, l = 1, pos = 1;
-    bool det = false;
-    for (;;) {
-        if (tort == hare) { det = true; break; }
-        if (pos >= 3 * H) break;
-        if (power == l) { tort = hare; power <<= 1; l = 0; }
-        hare = tp_next<MAXN>(a, v, hare);
-        l++;
-        pos++;
-    }
-    bool found = det && l <= H;
-    int mu = 0;
-    if (found) {
-        tort = t0;
-        hare = t0;
-        for (int j = 0; j < l; j++) hare = tp_next<MAXN>(a, v, hare);
-        while (tort != hare) {
-            if (mu + l >= H) { found = false; break; }
-            tort = tp_next<MAXN>(a, v, tort);
-            hare = tp_next<MAXN>(a, v, hare);
-            mu++;
-        }
-    }
-    const int lam = found ? l : 0;
-    if (!found) mu = H;
-
+    // t <- the index of the tuple the seated agents play at t, and where the values of that tuple lie
+    const auto next = [&](int& t) THRL_WALK_INLINE {
+        t = tuple_next<MAXN>(a, v, t);
+        return StepOut{rew + t, sca + t, T};
+    };
+    int mu, lam, s = 0;
+    find_cycle(t0, N, a.H, next, mu, lam, s, false);
     double cr[MAXN], ca[MAXN];
-#pragma unroll
-    for (int i = 0; i < MAXN; i++) { cr[i] = 0.0; ca[i] = 0.0; }
-    if (lam > 0) {
-        int x = tort;
-        for (int j = 0; j < lam; j++) {
-            x = tp_next<MAXN>(a, v, x);
-#pragma unroll
-            for (int i = 0; i < MAXN; i++)
-                if (i < N) { cr[i] = __dadd_rn(cr[i], rew[i * T + x]); ca[i] = __dadd_rn(ca[i], sca[i * T + x]); }
-        }
-#pragma unroll
-        for (int i = 0; i < MAXN; i++)
-            if (i < N) { cr[i] = __ddiv_rn(cr[i], (double)lam); ca[i] = __ddiv_rn(ca[i], (double)lam); }
-    }
+    int x = s;
+    cycle_means<MAXN>(N, lam, cr, ca, [&]() THRL_WALK_INLINE { return next(x); });
     a.mu[m] = mu;
     a.lam[m] = lam;
-    if (a.cycle_start) a.cycle_start[m] = lam > 0 ? tort : -1;
-#pragma unroll
-    for (int i = 0; i < MAXN; i++) {
-        if (i >= N) break;
-        a.cycle_reward[(int64_t)i * M + m] = cr[i];
-        a.cycle_action[(int64_t)i * M + m] = ca[i];
-    }
+    if (a.cycle_start) a.cycle_start[m] = lam > 0 ? s : -1;
+    store_means<MAXN>(a, m, M, cr, ca);
 
     // the path from t_0: the rows of tau in [row_begin, row_begin + row_count)
-    if (n_rows > 0 && (a.reward_rows || a.action_rows)) {
-        int x = t0;
-        const int end = a.row_begin + n_rows;
-        for (int tau = 0; tau < end; tau++) {
-            x = tp_next<MAXN>(a, v, x);
-            const int rr = tau - a.row_begin;
-            if (rr >= 0) {
-#pragma unroll
-                for (int i = 0; i < MAXN; i++) {
-                    if (i >= N) break;
-                    const int64_t o = (int64_t)rr * plane + (int64_t)i * M + m;
-                    if (a.reward_rows) a.reward_rows[o] = rew[i * T + x];
-                    if (a.action_rows) a.action_rows[o] = sca[i * T + x];
-                }
-            }
-        }
+    if (a.row_count > 0 && (a.reward_rows || a.action_rows)) {
+        x = t0;
+        const int end = a.row_begin + a.row_count;
+        for (int tau = 0; tau < end; tau++) store_step<MAXN>(a, tau, m, M, next(x));
     }
 }
 
