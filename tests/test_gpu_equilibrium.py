@@ -1,6 +1,6 @@
 """Equilibrium check on the device (thrl_equilibrium, GameBatch.equilibrium, training.equilibrium): every output
 bit-equal to the numpy mirror (tests/equilibrium_mirror.py) on fresh and trained tables, f32 and f64, individual grids
-(S = 87: several states per lane), the 3,000-state config, a gamma sweep, an agents mask, given and default start
+(S = 87: several states per lane, on f32 tables and on f64 ones), 64 x 64 action tuples (the reward LUT in global memory), the 3,000-state config, a gamma sweep, an agents mask, given and default start
 prices, a game count that is no multiple of anything; the known answers through set_tables; mu / lam against the
 deviation analysis; and the invariances (learning state untouched, halves, MixedGameBatch, the trainer's artefacts at
 convergence, a sharded launch, error codes)."""
@@ -24,6 +24,7 @@ THREE = {"agents": [dict(AG, actions=7, states=30, action_range=[0.1, 0.5], min_
                     dict(AG, actions=11, states=60, action_range=[0.2, 0.4], min_memory=10, gamma=0.9),
                     dict(AG, actions=5, states=40, action_range=[0.0, 0.3], min_memory=10, max_state=8)],
          "environment": dict(ENV, nplayers=3, max_steps=40)}
+WIDE2 = {"agents": [dict(AG, actions=64, states=200), dict(AG, actions=64, states=200, gamma=0.9)], "environment": dict(ENV)}
 BIG = {"agents": [dict(AG, states=3000), dict(AG, states=3000)], "environment": dict(ENV)}
 MIXED = {"agents": [dict(AG), dict(name="Reinforce", gamma=0.995, actions=21, states=1, action_range=[0.2, 0.4])],
          "environment": dict(ENV)}
@@ -77,6 +78,30 @@ def test_three_agents_individual_grids_several_states_per_lane():
     out = _check(gb, THREE)
     assert out["n_states"] == 87 and out["n_states"] > 64               # the LDS evaluation path
     _check(gb, THREE, state0=np.linspace(0.0, 10.0, 96), agents=[1])
+
+
+def _random_batch(config, G, dtype, seed):
+    """Random tables through set_tables, no training: the mirror reads the same numbers on any machine."""
+    from oracle import oracle as O
+    from th_rl_amd.batched import GameBatch
+    cfg, _ = O.cfg_from_config(config, G, 1 if dtype == "float64" else 0)
+    rs = np.random.RandomState(seed)
+    q = rs.normal(0.0, 1.0, (G, O.table_stride(cfg))).astype(dtype)
+    return GameBatch(config, n_games=G, dtype=dtype, seed=seed).set_tables(q, rs.uniform(0, 10, G))
+
+
+def test_lds_evaluation_path_on_float64_tables():
+    gb = _random_batch(THREE, 96, "float64", seed=21)                   # k_equilibrium<double, S > 64, reward LUT in LDS>
+    out = _check(gb, THREE)
+    assert out["n_states"] == 87 and out["iters"].min() >= 0 and out["iters"].max() >= 2
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_reward_lut_in_global_memory_with_the_lds_evaluation_path(dtype):
+    # 64 x 64 = 4,096 tuples: the reward LUT alone is the 64 KiB budget, so it stays in global memory; S = 81 > 64
+    gb = _random_batch(WIDE2, 12, dtype, seed=22)
+    out = _check(gb, WIDE2)
+    assert out["n_states"] == 81 and out["iters"].min() >= 0 and out["iters"].max() >= 2
 
 
 def test_3000_state_config_matches_mirror():

@@ -16,6 +16,8 @@
 // reading the 64 starts of a chunk back from LDS).
 #include "thrl_attractors.h"
 
+#include "thrl_solve_dev.h"
+
 namespace thrl {
 
 namespace {
@@ -84,30 +86,12 @@ __global__ void __launch_bounds__(64) k_attractors(const AttrArgs a) {
         const uint16_t* __restrict__ pg = a.policy + g * a.P;
         const double st = a.state0[g];
 
-        // ---- the greedy action of every (agent, state) row, and of x_0's rows
-        for (int e = lane; e < N * S + N; e += 64) {
-            int i, row;
-            if (e < N * S) {
-                i = e / S;
-                row = a.srow[e];
-            } else {
-                i = e - N * S;
-                row = encode64_fast(st, a.ag[i]);
-                x0row[i] = row;
-            }
-            pol[e] = (uint16_t)min((int)pg[a.row_off[i] + row], a.ag[i].n_actions - 1);
-        }
-        __syncthreads();
-
-        // ---- the greedy map on states, and x_0's place in it
-        int found = -1;
-        for (int s = lane; s < S; s += 64) {
-            int t = 0;
-            bool eq = true;
-            for (int i = 0; i < N; i++) {
-                t += (int)pol[i * S + s] * a.tstride[i];
-                eq = eq && a.srow[i * S + s] == x0row[i];
-            }
+        // ---- the greedy action of every (agent, state) row and of x_0's rows (the policy word), the greedy map on
+        // states, and x_0's place in it
+        int t0;
+        const int s0 = stage_game(a, st, pol, x0row, lane, [&](int i, int row) THRL_SOLVE_INLINE {
+            return row_action(a, pg, i, row);
+        }, [&](int s, int t) THRL_SOLVE_INLINE {
             tup[s] = (uint16_t)t;
             lev[s] = sid[t];
             ma[s] = (uint16_t)s;
@@ -115,12 +99,7 @@ __global__ void __launch_bounds__(64) k_attractors(const AttrArgs a) {
             basin[s] = 0;
             lamc[s] = 0;
             slotof[s] = -1;
-            if (eq) found = s;
-        }
-        int t0 = 0;
-        for (int i = 0; i < N; i++) t0 += (int)pol[N * S + i] * a.tstride[i];
-        const unsigned long long hit = __ballot(found >= 0);
-        const int s0 = hit ? __shfl(found, __ffsll((long long)hit) - 1) : -1;
+        }, t0);
         const int s1 = sid[t0];                          // x_1, a member whatever x_0 is
         __syncthreads();
 
@@ -128,14 +107,7 @@ __global__ void __launch_bounds__(64) k_attractors(const AttrArgs a) {
         uint16_t* mo = ma;
         uint16_t* mn = mb;
         for (int k = 0; k < L; k++) {
-            const uint16_t* lo = lev + k * S;
-            uint16_t* ln = lev + (k + 1) * S;
-            for (int s = lane; s < S; s += 64) {
-                const int m = lo[s];
-                ln[s] = lo[m];
-                mn[s] = min(mo[s], mo[m]);
-            }
-            __syncthreads();
+            double_min_round<64>(lev + k * S, lev + (k + 1) * S, mo, mn, S, lane);
             uint16_t* tm = mo; mo = mn; mn = tm;
         }
         const uint16_t* land = lev + L * S;             // f^(2^L), 2^L >= S: on a cycle from every state
@@ -177,18 +149,8 @@ __global__ void __launch_bounds__(64) k_attractors(const AttrArgs a) {
         // ---- the kept attractors: the largest (basin, -rep) below the one taken before, KEEP times
         uint32_t prev = 0xffffffffu;
         for (int k = 0; k < kKeep; k++) {
-            uint32_t best = 0;
-            for (int s = lane; s < S; s += 64) {
-                const uint32_t key = ((uint32_t)basin[s] << 16) | (uint32_t)(0xffff - s);
-                if (rep[s] == s && key < prev && key > best) best = key;
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, m));
-            if (lane == 0) {
-                const int r = best ? 0xffff - (int)(best & 0xffffu) : -1;
-                sel[k] = r;
-                if (r >= 0) slotof[r] = (int16_t)k;
-            }
+            const uint32_t best = keep_scan<64>(basin, rep, S, prev, lane);
+            if (lane == 0) keep_take(best, k, sel, slotof);
             prev = best;                                 // 0 after the last attractor: nothing lies below it
         }
         __syncthreads();
@@ -224,12 +186,7 @@ __global__ void __launch_bounds__(64) k_attractors(const AttrArgs a) {
             for (int j0 = 0; j0 < J; j0 += 64) {
                 const int j = j0 + lane;
                 if (j < J) {
-                    int t = 0;
-                    for (int i = 0; i < N; i++) {
-                        const int row = clamp_row(a.start_rows[(int64_t)i * J + j], a.ag[i]);
-                        t += min((int)pg[a.row_off[i] + row], a.ag[i].n_actions - 1) * a.tstride[i];
-                    }
-                    const int r = rep[sid[t]];
+                    const int r = rep[sid[cell_tuple(a, pg, a.start_rows, J, j)]];
                     const double w = a.start_w[j];
                     const int lm = lamc[r];
                     cslot[lane] = slotof[r];
@@ -241,20 +198,10 @@ __global__ void __launch_bounds__(64) k_attractors(const AttrArgs a) {
                     }
                 }
                 __syncthreads();
-                const int n = min(64, J - j0);
-                if (lane <= kKeep) {                     // lanes 0 .. KEEP-1: the slots; lane KEEP: the attractors not kept
-                    const int want = lane < kKeep ? lane : -1;
-                    for (int jj = 0; jj < n; jj++)
-                        if (cslot[jj] == want) acc = __dadd_rn(acc, cw[jj]);
-                } else if (lane < kKeep + 1 + N) {       // one lane per agent
-                    const double* pr = cprod + (lane - kKeep - 1) * 64;
-                    for (int jj = 0; jj < n; jj++) acc = __dadd_rn(acc, pr[jj]);
-                }
+                acc = start_read_back<64>(cslot, cw, cprod, kKeep, N, min(64, J - j0), acc, lane);
                 __syncthreads();
             }
-            if (lane < kKeep) a.reset_mass[(int64_t)lane * G + g] = acc;
-            else if (lane == kKeep) a.reset_mass_other[g] = acc;
-            else if (lane < kKeep + 1 + N) a.reset_reward[(int64_t)(lane - kKeep - 1) * G + g] = acc;
+            start_store(a.reset_mass, a.reset_mass_other, a.reset_reward, g, G, kKeep, N, lane, acc);
         }
         __syncthreads();                                 // this game's LDS reads before the next game's writes
     }

@@ -39,10 +39,12 @@ __device__ __forceinline__ double chain_lazy(double m, double s, double& c) {
     return v;
 }
 
-// lane tid < n_out adds the n staged terms of its output in ascending order; the caller's barriers stand around it
+// lane tid < n_out adds the n staged terms of its output (a row of kRow) in ascending order; the caller's barriers stand
+// around it
+template <int kRow = 64>
 __device__ __forceinline__ double chain_read_back(const double* prod, int n_out, int n, double acc, int tid) {
     if (tid < n_out) {
-        const double* pr = prod + tid * 64;
+        const double* pr = prod + tid * kRow;
         for (int kk = 0; kk < n; kk++) acc = __dadd_rn(acc, pr[kk]);
     }
     return acc;

@@ -14,7 +14,7 @@
 // products, then one lane per sum reading them back from LDS in ascending k.  The lane of a sum keeps what is derived
 // from it in registers over the periods: lane d the gain, lane 2N the distance and ret_step.
 #include "thrl_deviation_noise.h"
-#include "thrl_chain_dev.h"
+#include "thrl_solve_dev.h"
 
 namespace thrl {
 
@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(64) k_deviation_noise(const DevnArgs a) {
             int t = 0, cur = 0;
             for (int i = 0; i < N; i++) {
                 const int row = clamp_row(a.cell_rows[(int64_t)i * J + k], a.ag[i]);
-                const int ai = min((int)pg[a.row_off[i] + row], a.ag[i].n_actions - 1);
+                const int ai = row_action(a, pg, i, row);
                 t += ai * a.tstride[i];
                 if (i == d) cur = ai;
             }
@@ -71,13 +71,10 @@ __global__ void __launch_bounds__(64) k_deviation_noise(const DevnArgs a) {
                 const int t0 = t - cur * ts;
                 const double* __restrict__ rd = a.rew + (int64_t)d * TT;
                 const double* __restrict__ nd = a.noise_reward + (int64_t)d * TT;
-                double best = __dadd_rn(__dmul_rn(q, rd[t0]), __dmul_rn(p, nd[t0]));
-                ad = 0;
-                for (int b = 1; b < a.ag[d].n_actions; b++) {
-                    const int tt = t0 + b * ts;
-                    const double R = __dadd_rn(__dmul_rn(q, rd[tt]), __dmul_rn(p, nd[tt]));
-                    if (R > best) { best = R; ad = b; }
-                }
+                double best;
+                ad = first_max(a.ag[d].n_actions, [&](int b) THRL_SOLVE_INLINE {
+                    return noise_blend(q, rd[t0 + b * ts], p, nd[t0 + b * ts]);
+                }, best);
             }
             tup[k] = (uint16_t)t;
             tupd[k] = (uint16_t)(t + (ad - cur) * a.tstride[d]);
@@ -99,7 +96,7 @@ __global__ void __launch_bounds__(64) k_deviation_noise(const DevnArgs a) {
                         const int ai = rest / a.tstride[i];
                         rest -= ai * a.tstride[i];
                         const double r = a.rew[(int64_t)i * TT + t], nr = a.noise_reward[(int64_t)i * TT + t];
-                        prod[i * 64 + lane] = __dmul_rn(mk, __dadd_rn(__dmul_rn(q, r), __dmul_rn(p, nr)));
+                        prod[i * 64 + lane] = __dmul_rn(mk, noise_blend(q, r, p, nr));
                         prod[(N + i) * 64 + lane] = __dmul_rn(mk, scale_action(ai, a.ag[i]));
                     }
                     prod[2 * N * 64 + lane] = base ? ((int)tupd[k] != t ? mk : 0.0) : fabs(__dsub_rn(mk, w0[k]));

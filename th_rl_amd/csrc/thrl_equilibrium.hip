@@ -12,11 +12,11 @@
 // done by all lanes on the same LDS words, so no result has to be broadcast.
 #include "thrl_equilibrium.h"
 
+#include "thrl_solve_dev.h"
+
 namespace thrl {
 
 namespace {
-
-constexpr int kEqMaxD = 64;
 
 // argmax_row (first maximum under strict >) with eight loads in flight; reads row[0 .. n) only
 template <typename T>
@@ -63,45 +63,22 @@ __global__ void __launch_bounds__(64) k_equilibrium(const EqArgs a) {
         const T* __restrict__ qg = qbase + g * a.stride;
         const double st = a.state0[g];
 
-        // ---- the greedy action of every (agent, state) row, and of x_0's rows
-        for (int e = lane; e < N * S + N; e += 64) {
-            int i, row;
-            if (e < N * S) {
-                i = e / S;
-                row = a.srow[e];
-            } else {
-                i = e - N * S;
-                row = encode64_fast(st, a.ag[i]);
-                x0row[i] = row;
-            }
+        // ---- the greedy action of every (agent, state) row and of x_0's rows (the argmax of the table row), the joint
+        // greedy map on states, x_0's place in it, and the cycle
+        int t0;
+        const int s0 = stage_game(a, st, pol, x0row, lane, [&](int i, int row) THRL_SOLVE_INLINE {
             const AgentParams& p = a.ag[i];
-            pol[e] = (uint16_t)argmax_row8(qg + p.table_off + (int64_t)row * p.n_actions, p.n_actions);
-        }
-        __syncthreads();
-
-        // ---- the joint greedy map on states, x_0's place in it, and the cycle
-        int found = -1;
-        for (int s = lane; s < S; s += 64) {
-            int t = 0;
-            bool eq = true;
-            for (int i = 0; i < N; i++) {
-                t += (int)pol[i * S + s] * a.tstride[i];
-                eq = eq && a.srow[i * S + s] == x0row[i];
-            }
+            return argmax_row8(qg + p.table_off + (int64_t)row * p.n_actions, p.n_actions);
+        }, [&](int s, int t) THRL_SOLVE_INLINE {
             jn[s] = sid[t];
             first[s] = -1;
-            if (eq) found = s;
-        }
-        int t0 = 0;
-        for (int i = 0; i < N; i++) t0 += (int)pol[N * S + i] * a.tstride[i];
-        const unsigned long long hit = __ballot(found >= 0);
-        const int s0 = hit ? __shfl(found, __ffsll((long long)hit) - 1) : -1;
+        }, t0);
         __syncthreads();
         int cur = s0 >= 0 ? s0 : (int)sid[t0];
         int tm = s0 >= 0 ? 0 : 1;
         int mu = 0, lam = 1;
-        for (int guard = 0; guard <= S; guard++) {       // every lane walks the same words
-            const int f = first[cur];
+        for (int guard = 0; guard <= S; guard++) {       // every lane walks the same words (first_visit_walk's lines, inline:
+            const int f = first[cur];                    // through the function the launch is 1 % slower)
             if (f >= 0) { mu = f; lam = tm - f; break; }
             first[cur] = (int16_t)tm;
             cur = jn[cur];
@@ -115,16 +92,10 @@ __global__ void __launch_bounds__(64) k_equilibrium(const EqArgs a) {
             const int64_t o = (int64_t)i * G + g;
             const double gam = a.sweep_gamma ? a.sweep_gamma[o] : a.ag[i].gamma;
             if (!(gam >= 0.0 && gam < 1.0)) {
-                if (lane == 0) {
-                    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-                    a.iters[o] = -1; a.n_diff_all[o] = 0; a.n_diff_on[o] = 0;
-                    a.loss_all[o] = nan; a.loss_on[o] = nan; a.loss_all_mean[o] = nan; a.loss_on_mean[o] = nan;
-                    a.v_on[o] = nan;
-                }
+                if (lane == 0) store_agent_unsolved(a, o);
                 continue;
             }
-            int D = 0;
-            for (double w = gam; w >= 0x1p-64 && D < kEqMaxD; D++) w = __dmul_rn(w, w);
+            const int D = doubling_rounds(gam);
             const int nact = a.ag[i].n_actions, ts = a.tstride[i];
             const double* __restrict__ R = (kLutLds ? rlds : a.rew) + (int64_t)i * TT;
 
@@ -136,6 +107,7 @@ __global__ void __launch_bounds__(64) k_equilibrium(const EqArgs a) {
                 sigma[s] = pol[i * S + s];
             }
 
+            const auto succ = [&](int t) THRL_SOLVE_INLINE { return (int)sid[t]; };    // the state a tuple leads to
             double* V = Va;                              // where the evaluation leaves V
             int iters = -1;
             for (int k = 0;; k++) {
@@ -159,35 +131,14 @@ __global__ void __launch_bounds__(64) k_equilibrium(const EqArgs a) {
                     if (lane < S) Va[lane] = v;
                     __syncthreads();
                 } else {
-                    double* Vo = Va;
-                    double* Vn = Vb;
-                    uint16_t* no = na;
-                    uint16_t* nn = nb;
-                    for (int s = lane; s < S; s += 64) {
-                        const int t = base[s] + (int)sigma[s] * ts;
-                        Vo[s] = R[t];
-                        no[s] = sid[t];
-                    }
-                    __syncthreads();
-                    double w = gam;
-                    for (int d = 0; d < D; d++) {
-                        for (int s = lane; s < S; s += 64) {
-                            const int m = no[s];
-                            Vn[s] = __dadd_rn(Vo[s], __dmul_rn(w, Vo[m]));
-                            nn[s] = no[m];
-                        }
-                        __syncthreads();
-                        double* tv = Vo; Vo = Vn; Vn = tv;
-                        uint16_t* tn = no; no = nn; nn = tn;
-                        w = __dmul_rn(w, w);
-                    }
-                    V = Vo;
+                    V = eval_doubling<64>(Va, Vb, na, nb, base, sigma, ts, R, S, D, gam, lane, succ);
                 }
                 if (k == 0)
                     for (int s = lane; s < S; s += 64) Vpi[s] = V[s];
                 if (k == THRL_EQ_MAX_ITERS) break;
 
                 // ---- improvement: keep the incumbent unless some action is strictly better
+                // (improve_strict's lines, inline: through the function this kernel's launch is 4 % slower)
                 bool changed = false;
                 for (int s = lane; s < S; s += 64) {
                     const int b = base[s];
@@ -214,43 +165,28 @@ __global__ void __launch_bounds__(64) k_equilibrium(const EqArgs a) {
             double lmax = -__builtin_huge_val();
             for (int s = lane; s < S; s += 64) {
                 const double vs = V[s], vp = Vpi[s];
-                const double l = (vs == vp || vs == 0.0) ? 0.0 : __ddiv_rn(__dsub_rn(vs, vp), vs);
+                const double l = rel_loss(vs, vp);
                 loss[s] = l;
                 if (l > lmax) lmax = l;
                 nd += sigma[s] != pol[i * S + s] ? 1 : 0;
-                const int64_t os = o * S + s;
-                if (a.br_policy) a.br_policy[os] = sigma[s];
-                if (a.v_opt) a.v_opt[os] = vs;
-                if (a.v_pi) a.v_pi[os] = vp;
+                store_state(a, o * S + s, sigma[s], vs, vp);
             }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const double ol = __shfl_xor(lmax, m);
-                if (ol > lmax) lmax = ol;
-                nd += __shfl_xor(nd, m);
-            }
+            wave_max_sum(lmax, nd);
             __syncthreads();
             double sum_all = 0.0;
             for (int s = 0; s < S; s++) sum_all = __dadd_rn(sum_all, loss[s]);
-            double sum_on = 0.0, von = 0.0, lon = -__builtin_huge_val();
-            int nd_on = 0, c = c0;
-            for (int j = 0; j < lam; j++) {
-                const double l = loss[c];
-                sum_on = __dadd_rn(sum_on, l);
-                von = __dadd_rn(von, Vpi[c]);
-                if (l > lon) lon = l;
-                nd_on += sigma[c] != pol[i * S + c] ? 1 : 0;
-                c = jn[c];
-            }
+            const OnCycle on = on_cycle_sums(loss, Vpi, jn, c0, lam, [&](int c) THRL_SOLVE_INLINE {
+                return sigma[c] != pol[i * S + c] ? 1 : 0;
+            });
             if (lane == 0) {
                 a.iters[o] = iters;
                 a.n_diff_all[o] = nd;
-                a.n_diff_on[o] = nd_on;
+                a.n_diff_on[o] = on.nd;
                 a.loss_all[o] = lmax;
-                a.loss_on[o] = lon;
+                a.loss_on[o] = on.lon;
                 a.loss_all_mean[o] = __ddiv_rn(sum_all, (double)S);
-                a.loss_on_mean[o] = __ddiv_rn(sum_on, (double)lam);
-                a.v_on[o] = __ddiv_rn(von, (double)lam);
+                a.loss_on_mean[o] = __ddiv_rn(on.sum, (double)lam);
+                a.v_on[o] = __ddiv_rn(on.von, (double)lam);
             }
             __syncthreads();                             // loss / V / sigma reads before the next agent's writes
         }

@@ -10,8 +10,10 @@
 // step needs z_V of every (cell, action): where the game has no more tuples than that and LDS has the room, z is staged
 // once per tuple and round; otherwise it is computed per (cell, action).  z depends on the tuple alone, so both give the
 // same bits.  The ordered output sums follow k_stationary: chunks of 64 cells, one lane per cell for the terms, then one
-// lane per sum reading them back from LDS in ascending k.
+// lane per sum reading them back from LDS in ascending k (chain_read_back).
 #include "thrl_equilibrium_noise.h"
+
+#include "thrl_solve_dev.h"
 
 namespace thrl {
 
@@ -49,19 +51,11 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
                     a.loss_all[o] = 0.0; a.loss_all_mean[o] = 0.0;
                     if (a.weights) { a.loss_w[o] = 0.0; a.diff_w[o] = 0.0; a.v_w[o] = 0.0; }
                 }
-                for (int k = lane; k < J; k += 64) {
-                    if (a.br_policy) a.br_policy[o * J + k] = 0;
-                    if (a.v_opt) a.v_opt[o * J + k] = 0.0;
-                    if (a.v_pi) a.v_pi[o * J + k] = 0.0;
-                }
+                store_states_unsolved(a, o * J, J, lane, 0.0, [](int) THRL_SOLVE_INLINE { return 0; });
             }
             continue;
         }
 
-        // the w of a band row that starts at cell b0 whose cells b0 + w lie in [0, J): [band_first, band_end), at most J
-        // of them whatever W and b0 are
-        auto band_first = [&](int b0) -> int { return b0 < 0 ? (int)min((int64_t)W, -(int64_t)b0) : 0; };
-        auto band_end = [&](int b0) -> int { return (int)max((int64_t)0, min((int64_t)W, (int64_t)J - b0)); };
         // z_V(t) of the definition, V in LDS
         auto z_of = [&](const double* V, int t) -> double {
             const int d = a.det_cell[t];
@@ -69,19 +63,12 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
             const double* __restrict__ br = a.band + (int64_t)t * W;
             const double s0 = (d >= 0 && d < J) ? __dmul_rn(q, V[d]) : 0.0;
             double b = 0.0;
-            for (int w = band_first(b0), we = band_end(b0); w < we; w++) b = __dadd_rn(b, __dmul_rn(br[w], V[b0 + w]));
+            for (int w = band_first(b0, W), we = band_end(b0, W, J); w < we; w++) b = __dadd_rn(b, __dmul_rn(br[w], V[b0 + w]));
             return __dadd_rn(s0, __dmul_rn(p, b));
         };
 
         // ---- the tuple of every cell
-        for (int k = lane; k < J; k += 64) {
-            int t = 0;
-            for (int i = 0; i < N; i++) {
-                const int row = clamp_row(a.cell_rows[(int64_t)i * J + k], a.ag[i]);
-                t += min((int)pg[a.row_off[i] + row], a.ag[i].n_actions - 1) * a.tstride[i];
-            }
-            tup[k] = (uint16_t)t;
-        }
+        for (int k = lane; k < J; k += 64) tup[k] = (uint16_t)cell_tuple(a, pg, a.cell_rows, J, k);
         __syncthreads();
 
         for (int i = 0; i < N; i++) {
@@ -91,7 +78,7 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
             const double gam = a.sweep_gamma ? a.sweep_gamma[o] : a.ag[i].gamma;
             const double* __restrict__ R = a.rew + (int64_t)i * TT;
             const double* __restrict__ NR = a.noise_reward + (int64_t)i * TT;
-            auto reward = [&](int t) -> double { return __dadd_rn(__dmul_rn(q, R[t]), __dmul_rn(p, NR[t])); };
+            auto reward = [&](int t) -> double { return noise_blend(q, R[t], p, NR[t]); };
 
             bool solved = gam >= 0.0 && gam < 1.0;       // wave-uniform throughout
             int iters = -1, sweeps = 0;
@@ -106,8 +93,7 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
                     base[k] = (uint16_t)(t - ai * ts);
                     Va[k] = 0.0;
                 }
-                const double margin = __ddiv_rn(__dmul_rn(__dmul_rn(__dmul_rn(2.0, gam), gam), a.eval_tol),
-                                                __dsub_rn(1.0, gam));
+                const double margin = improve_margin(gam, a.eval_tol);
                 const bool staged = a.zt_lds && TT <= J * nact;
                 __syncthreads();
 
@@ -134,7 +120,7 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
                             const double s0 = d != 0xffff ? __dmul_rn(q, V[d]) : 0.0;
                             double b = 0.0;
 #pragma unroll 4
-                            for (int w = band_first(b0), we = band_end(b0); w < we; w++)
+                            for (int w = band_first(b0, W), we = band_end(b0, W, J); w < we; w++)
                                 b = __dadd_rn(b, __dmul_rn(br[w], V[b0 + w]));
                             const double v = __dadd_rn(Rs[k], __dmul_rn(gam, __dadd_rn(s0, __dmul_rn(p, b))));
                             Vn[k] = v;
@@ -162,15 +148,14 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
                     bool changed = false;
                     for (int k = lane; k < J; k += 64) {
                         const int b = base[k], cur = sigma[k];
-                        double bv = 0.0, qc = 0.0;
-                        int ba = 0;
-                        for (int act = 0; act < nact; act++) {
+                        double bv, qc = 0.0;
+                        const int ba = first_max(nact, [&](int act) THRL_SOLVE_INLINE {
                             const int t = b + act * ts;
                             const double z = staged ? zt[t] : z_of(V, t);
                             const double qv = __dadd_rn(reward(t), __dmul_rn(gam, z));
-                            if (act == 0 || qv > bv) { bv = qv; ba = act; }
                             if (act == cur) qc = qv;
-                        }
+                            return qv;
+                        }, bv);
                         if (bv > __dadd_rn(qc, margin)) { sigma[k] = (uint16_t)ba; changed = true; }
                     }
                     const bool any = __ballot(changed) != 0;
@@ -186,11 +171,7 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
                     a.loss_all[o] = nan; a.loss_all_mean[o] = nan;
                     if (a.weights) { a.loss_w[o] = nan; a.diff_w[o] = nan; a.v_w[o] = nan; }
                 }
-                for (int k = lane; k < J; k += 64) {
-                    if (a.br_policy) a.br_policy[o * J + k] = (uint16_t)(((int)tup[k] / ts) % nact);
-                    if (a.v_opt) a.v_opt[o * J + k] = nan;
-                    if (a.v_pi) a.v_pi[o * J + k] = nan;
-                }
+                store_states_unsolved(a, o * J, J, lane, nan, [&](int k) THRL_SOLVE_INLINE { return ((int)tup[k] / ts) % nact; });
                 __syncthreads();
                 continue;
             }
@@ -201,20 +182,13 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
             double lmax = -__builtin_huge_val();
             for (int k = lane; k < J; k += 64) {
                 const double vs = V[k], vp = Vpi[k];
-                const double l = (vs == vp || vs == 0.0) ? 0.0 : __ddiv_rn(__dsub_rn(vs, vp), vs);
+                const double l = rel_loss(vs, vp);
                 loss[k] = l;
                 if (l > lmax) lmax = l;
                 nd += sigma[k] != pol[k] ? 1 : 0;
-                if (a.br_policy) a.br_policy[o * J + k] = sigma[k];
-                if (a.v_opt) a.v_opt[o * J + k] = vs;
-                if (a.v_pi) a.v_pi[o * J + k] = vp;
+                store_state(a, o * J + k, sigma[k], vs, vp);
             }
-#pragma unroll
-            for (int x = 32; x >= 1; x >>= 1) {
-                const double ol = __shfl_xor(lmax, x);
-                if (ol > lmax) lmax = ol;
-                nd += __shfl_xor(nd, x);
-            }
+            wave_max_sum(lmax, nd);
             __syncthreads();
             const int n_sums = a.weights ? kEqnSums : 1;
             double acc = 0.0;
@@ -231,11 +205,7 @@ __global__ void __launch_bounds__(64) k_equilibrium_noise(const EqnArgs a) {
                     }
                 }
                 __syncthreads();
-                const int cnt = min(64, J - k0);
-                if (lane < n_sums) {
-                    const double* pr = prod + lane * 64;
-                    for (int kk = 0; kk < cnt; kk++) acc = __dadd_rn(acc, pr[kk]);
-                }
+                acc = chain_read_back(prod, n_sums, min(64, J - k0), acc, lane);
                 __syncthreads();
             }
             if (lane == 0) {

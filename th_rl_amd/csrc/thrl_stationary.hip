@@ -12,7 +12,7 @@
 // output sums follow k_attractors: chunks of 64 cells, one lane per cell for the products, then one lane per output
 // reading them back from LDS in ascending k.
 #include "thrl_stationary.h"
-#include "thrl_chain_dev.h"
+#include "thrl_solve_dev.h"
 
 namespace thrl {
 
@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(64) k_stationary(const StatArgs a) {
             bool eq = true;
             for (int i = 0; i < N; i++) {
                 const int row = clamp_row(a.cell_rows[(int64_t)i * J + k], a.ag[i]);
-                t += min((int)pg[a.row_off[i] + row], a.ag[i].n_actions - 1) * a.tstride[i];
+                t += row_action(a, pg, i, row) * a.tstride[i];
                 if (a.start_state) eq = eq && row == encode64(st, a.ag[i]);
             }
             tup[k] = (uint16_t)t;
@@ -146,10 +146,10 @@ __global__ void __launch_bounds__(64) k_stationary(const StatArgs a) {
                 prod[lane] = m;
                 for (int i = 0; i < N; i++) {
                     const double r = a.rew[(int64_t)i * TT + t], nr = a.noise_reward[(int64_t)i * TT + t];
-                    prod[(1 + i) * 64 + lane] = __dmul_rn(m, __dadd_rn(__dmul_rn(q, r), __dmul_rn(p, nr)));
+                    prod[(1 + i) * 64 + lane] = __dmul_rn(m, noise_blend(q, r, p, nr));
                     prod[(1 + N + i) * 64 + lane] = __dmul_rn(m, sc[i]);
                 }
-                prod[(1 + 2 * N) * 64 + lane] = __dmul_rn(m, __dadd_rn(__dmul_rn(q, price), __dmul_rn(p, a.noise_price[t])));
+                prod[(1 + 2 * N) * 64 + lane] = __dmul_rn(m, noise_blend(q, price, p, a.noise_price[t]));
                 if (a.pi) a.pi[g * J + k] = m;
             }
             __syncthreads();

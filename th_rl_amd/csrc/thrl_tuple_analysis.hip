@@ -19,6 +19,7 @@
 //   along the cycle.  Nothing depends on the grid size or on which block takes which game.
 #include "thrl_tuple_analysis.h"
 
+#include "thrl_solve_dev.h"
 #include "thrl_walk_dev.h"
 
 namespace thrl {
@@ -132,8 +133,6 @@ void launch_dev_n(const TaDevArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ equilibrium
-constexpr int kTaEqMaxD = 64;
-
 __global__ void __launch_bounds__(kTaEqBlock) k_ta_equilibrium(const TaEqArgs a) {
     extern __shared__ __align__(16) unsigned char s_mem[];
     constexpr int B = kTaEqBlock;
@@ -157,26 +156,14 @@ __global__ void __launch_bounds__(kTaEqBlock) k_ta_equilibrium(const TaEqArgs a)
 
         // ---- the joint greedy map, and the path from the start tuple (wave 0 alone: its lanes walk the same words)
         for (int s = tid; s < T; s += B) {
-            int t = 0;
-            for (int i = 0; i < N; i++) t += min((int)pg[i * T + s], a.n_actions[i] - 1) * a.tstride[i];
-            jn[s] = (uint16_t)t;
+            jn[s] = (uint16_t)tuple_map(a, pg, T, s, -1);
             mark[s] = -1;
         }
         __syncthreads();
         if (wave == 0) {
             const int t0 = a.start[g];
             int mu = -1, lam = 0, cur = 0;
-            if (t0 >= 0 && t0 < T) {
-                cur = t0;
-                int tm = 0;
-                for (int guard = 0; guard <= T; guard++) {
-                    const int f = mark[cur];
-                    if (f >= 0) { mu = f; lam = tm - f; break; }
-                    mark[cur] = (int16_t)tm;
-                    cur = jn[cur];
-                    tm++;
-                }
-            }
+            if (t0 >= 0 && t0 < T) cur = first_visit_walk(mark, jn, T, t0, 0, mu, lam);
             if (lane == 0) {
                 red_i[4] = mu; red_i[5] = lam; red_i[6] = cur;
                 a.mu[g] = mu;
@@ -191,57 +178,28 @@ __global__ void __launch_bounds__(kTaEqBlock) k_ta_equilibrium(const TaEqArgs a)
             const int64_t o = (int64_t)i * G + g;
             const double gam = a.sweep_gamma ? a.sweep_gamma[o] : a.gamma[i];
             if (!(gam >= 0.0 && gam < 1.0)) {
-                if (tid == 0) {
-                    a.iters[o] = -1; a.n_diff_all[o] = 0; a.n_diff_on[o] = 0;
-                    a.loss_all[o] = nan; a.loss_on[o] = nan; a.loss_all_mean[o] = nan; a.loss_on_mean[o] = nan;
-                    a.v_on[o] = nan;
-                }
+                if (tid == 0) store_agent_unsolved(a, o);
                 continue;
             }
-            int D = 0;
-            for (double w = gam; w >= 0x1p-64 && D < kTaEqMaxD; D++) w = __dmul_rn(w, w);
+            const int D = doubling_rounds(gam);
             const int nact = a.n_actions[i], ts = a.tstride[i];
             const uint16_t* __restrict__ pi = pg + i * T;
             const double* __restrict__ Rg = a.reward + (int64_t)i * T;
 
             for (int s = tid; s < T; s += B) {
-                int t = 0;
-                for (int j = 0; j < N; j++)
-                    if (j != i) t += min((int)pg[j * T + s], a.n_actions[j] - 1) * a.tstride[j];
-                base[s] = (uint16_t)t;
+                base[s] = (uint16_t)tuple_map(a, pg, T, s, i);
                 sigma[s] = (uint16_t)min((int)pi[s], nact - 1);
                 R[s] = Rg[s];
             }
             __syncthreads();
 
+            const auto succ = [](int t) THRL_SOLVE_INLINE { return t; };    // a tuple is the state it leads to
             double vpi[kTaEqMaxPerLane];                 // V_pi of this lane's states
             double* V = Va;
             int iters = -1;
             for (int k = 0;; k++) {
                 // ---- V = evaluation of sigma
-                double* Vo = Va;
-                double* Vn = Vb;
-                uint16_t* no = na;
-                uint16_t* nn = nb;
-                for (int s = tid; s < T; s += B) {
-                    const int t = (int)base[s] + (int)sigma[s] * ts;
-                    Vo[s] = R[t];
-                    no[s] = (uint16_t)t;
-                }
-                __syncthreads();
-                double w = gam;
-                for (int d = 0; d < D; d++) {
-                    for (int s = tid; s < T; s += B) {
-                        const int m = no[s];
-                        Vn[s] = __dadd_rn(Vo[s], __dmul_rn(w, Vo[m]));
-                        nn[s] = no[m];
-                    }
-                    __syncthreads();
-                    double* tv = Vo; Vo = Vn; Vn = tv;
-                    uint16_t* tn = no; no = nn; nn = tn;
-                    w = __dmul_rn(w, w);
-                }
-                V = Vo;
+                V = eval_doubling<B>(Va, Vb, na, nb, base, sigma, ts, R, T, D, gam, tid, succ);
                 if (k == 0) {
 #pragma unroll
                     for (int kk = 0; kk < kTaEqMaxPerLane; kk++) {
@@ -252,20 +210,7 @@ __global__ void __launch_bounds__(kTaEqBlock) k_ta_equilibrium(const TaEqArgs a)
                 if (k == THRL_EQ_MAX_ITERS) break;
 
                 // ---- improvement: keep the incumbent unless some action is strictly better
-                int changed = 0;
-                for (int s = tid; s < T; s += B) {
-                    const int b = base[s];
-                    const int tc = b + (int)sigma[s] * ts;
-                    const double qc = __dadd_rn(R[tc], __dmul_rn(gam, V[tc]));
-                    double bv = __dadd_rn(R[b], __dmul_rn(gam, V[b]));
-                    int ba = 0;
-                    for (int act = 1; act < nact; act++) {
-                        const int t = b + act * ts;
-                        const double qv = __dadd_rn(R[t], __dmul_rn(gam, V[t]));
-                        if (qv > bv) { bv = qv; ba = act; }
-                    }
-                    if (bv > qc) { sigma[s] = (uint16_t)ba; changed = 1; }
-                }
+                const int changed = improve_strict<B>(base, sigma, ts, nact, R, V, T, gam, tid, succ) ? 1 : 0;
                 // the barrier also ends every read of V before the next evaluation overwrites it
                 if (!__syncthreads_or(changed)) { iters = k; break; }
             }
@@ -279,24 +224,16 @@ __global__ void __launch_bounds__(kTaEqBlock) k_ta_equilibrium(const TaEqArgs a)
                 const int s = tid + kk * B;
                 if (s < T) {
                     const double vs = V[s], vp = vpi[kk];
-                    const double l = (vs == vp || vs == 0.0) ? 0.0 : __ddiv_rn(__dsub_rn(vs, vp), vs);
+                    const double l = rel_loss(vs, vp);
                     loss[s] = l;
                     if (l > lmax) lmax = l;
                     const int diff = (int)sigma[s] != min((int)pi[s], nact - 1) ? 1 : 0;
                     mark[s] = (int16_t)diff;
                     nd += diff;
-                    const int64_t os = o * T + s;
-                    if (a.br_policy) a.br_policy[os] = sigma[s];
-                    if (a.v_opt) a.v_opt[os] = vs;
-                    if (a.v_pi) a.v_pi[os] = vp;
+                    store_state(a, o * T + s, sigma[s], vs, vp);
                 }
             }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const double ol = __shfl_xor(lmax, m);
-                if (ol > lmax) lmax = ol;
-                nd += __shfl_xor(nd, m);
-            }
+            wave_max_sum(lmax, nd);
             if (lane == 0) { red_d[wave] = lmax; red_i[wave] = nd; }
             __syncthreads();                             // every read of V* is done
 #pragma unroll
@@ -321,21 +258,12 @@ __global__ void __launch_bounds__(kTaEqBlock) k_ta_equilibrium(const TaEqArgs a)
                     a.loss_all_mean[o] = __ddiv_rn(sum_all, (double)T);
                 }
             } else if (wave == 1) {                      // the cycle, in cycle order
-                double sum_on = 0.0, von = 0.0, lon = -__builtin_huge_val();
-                int nd_on = 0, c = c0;
-                for (int j = 0; j < lam; j++) {
-                    const double l = loss[c];
-                    sum_on = __dadd_rn(sum_on, l);
-                    von = __dadd_rn(von, V[c]);
-                    if (l > lon) lon = l;
-                    nd_on += mark[c];
-                    c = jn[c];
-                }
+                const OnCycle on = on_cycle_sums(loss, V, jn, c0, lam, [&](int c) THRL_SOLVE_INLINE { return (int)mark[c]; });
                 if (lane == 0) {
-                    a.n_diff_on[o] = nd_on;
-                    a.loss_on[o] = lam > 0 ? lon : nan;
-                    a.loss_on_mean[o] = lam > 0 ? __ddiv_rn(sum_on, (double)lam) : nan;
-                    a.v_on[o] = lam > 0 ? __ddiv_rn(von, (double)lam) : nan;
+                    a.n_diff_on[o] = on.nd;
+                    a.loss_on[o] = lam > 0 ? on.lon : nan;
+                    a.loss_on_mean[o] = lam > 0 ? __ddiv_rn(on.sum, (double)lam) : nan;
+                    a.v_on[o] = lam > 0 ? __ddiv_rn(on.von, (double)lam) : nan;
                 }
             }
             __syncthreads();                             // loss / V / mark reads before the next agent's writes

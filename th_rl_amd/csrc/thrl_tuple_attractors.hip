@@ -19,6 +19,8 @@
 // Nothing depends on the grid size or on which block takes which game.
 #include "thrl_tuple_attractors.h"
 
+#include "thrl_solve_dev.h"
+
 namespace thrl {
 
 namespace {
@@ -64,8 +66,7 @@ __global__ void __launch_bounds__(kTatBlock) k_ta_attractors(const TatArgs a) {
 
         // ---- the greedy map
         for (int s = tid; s < T; s += B) {
-            int t = 0;
-            for (int i = 0; i < N; i++) t += min((int)pg[i * T + s], a.n_actions[i] - 1) * a.tstride[i];
+            const int t = tuple_map(a, pg, T, s, -1);
             F[s] = (uint16_t)t;
             pa[s] = (uint16_t)t;
             ma[s] = (uint16_t)s;
@@ -82,12 +83,7 @@ __global__ void __launch_bounds__(kTatBlock) k_ta_attractors(const TatArgs a) {
         uint16_t* mo = ma;
         uint16_t* mn = mb;
         for (int k = 0; k < L; k++) {
-            for (int s = tid; s < T; s += B) {
-                const int m = po[s];
-                pn[s] = po[m];
-                mn[s] = min(mo[s], mo[m]);
-            }
-            __syncthreads();
+            double_min_round<B>(po, pn, mo, mn, T, tid);
             uint16_t* tp = po; po = pn; pn = tp;
             uint16_t* tm = mo; mo = mn; mn = tm;
         }
@@ -148,22 +144,12 @@ __global__ void __launch_bounds__(kTatBlock) k_ta_attractors(const TatArgs a) {
         // ---- the kept attractors: the largest (basin, -rep) below the one taken before, KEEP times
         uint32_t prev = 0xffffffffu;
         for (int k = 0; k < kKeep; k++) {
-            uint32_t best = 0;
-            for (int s = tid; s < T; s += B) {
-                const uint32_t key = ((uint32_t)basin[s] << 16) | (uint32_t)(0xffff - s);
-                if (rep[s] == s && key < prev && key > best) best = key;
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, m));
+            uint32_t best = keep_scan<B>(basin, rep, T, prev, tid);
             int32_t* rk = red + (k & 1) * 4;            // two rounds apart: the barrier between ends every read
             if (lane == 0) rk[wave] = (int32_t)best;
             __syncthreads();
             best = max(max((uint32_t)rk[0], (uint32_t)rk[1]), max((uint32_t)rk[2], (uint32_t)rk[3]));
-            if (tid == 0) {
-                const int r = best ? 0xffff - (int)(best & 0xffffu) : -1;
-                sel[k] = r;
-                if (r >= 0) slotof[r] = (int16_t)k;
-            }
+            if (tid == 0) keep_take(best, k, sel, slotof);
             prev = best;                                 // 0 after the last attractor: nothing lies below it
         }
         __syncthreads();
@@ -220,20 +206,10 @@ __global__ void __launch_bounds__(kTatBlock) k_ta_attractors(const TatArgs a) {
                     }
                 }
                 __syncthreads();
-                const int n = min(B, T - j0);
-                if (tid <= kKeep) {                      // threads 0 .. KEEP-1: the slots; thread KEEP: the attractors not kept
-                    const int want = tid < kKeep ? tid : -1;
-                    for (int jj = 0; jj < n; jj++)
-                        if (cslot[jj] == want) acc = __dadd_rn(acc, cw[jj]);
-                } else if (tid < kKeep + 1 + N) {        // one thread per agent
-                    const double* pr = cprod + (tid - kKeep - 1) * B;
-                    for (int jj = 0; jj < n; jj++) acc = __dadd_rn(acc, pr[jj]);
-                }
+                acc = start_read_back<B>(cslot, cw, cprod, kKeep, N, min(B, T - j0), acc, tid);
                 __syncthreads();
             }
-            if (tid < kKeep) a.start_mass[(int64_t)tid * G + g] = acc;
-            else if (tid == kKeep) a.start_mass_other[g] = acc;
-            else if (tid < kKeep + 1 + N) a.start_reward[(int64_t)(tid - kKeep - 1) * G + g] = acc;
+            start_store(a.start_mass, a.start_mass_other, a.start_reward, g, G, kKeep, N, tid, acc);
         }
         __syncthreads();                                 // this game's LDS reads before the next game's writes
     }

@@ -15,6 +15,8 @@
 // terms, then one lane per sum reading them back from LDS in ascending order.
 #include "thrl_tuple_equilibrium_noise.h"
 
+#include "thrl_solve_dev.h"
+
 namespace thrl {
 
 namespace {
@@ -47,11 +49,7 @@ __global__ void __launch_bounds__(64) k_tuple_equilibrium_noise(const TenArgs a)
                     a.loss_all[o] = 0.0; a.loss_tuples_mean[o] = 0.0; a.loss_cells_mean[o] = 0.0;
                     if (a.pi) { a.loss_w[o] = 0.0; a.diff_w[o] = 0.0; a.v_w[o] = 0.0; }
                 }
-                for (int s = lane; s < S; s += 64) {
-                    if (a.br_policy) a.br_policy[o * S + s] = 0;
-                    if (a.v_opt) a.v_opt[o * S + s] = 0.0;
-                    if (a.v_pi) a.v_pi[o * S + s] = 0.0;
-                }
+                store_states_unsolved(a, o * S, S, lane, 0.0, [](int) THRL_SOLVE_INLINE { return 0; });
             }
             continue;
         }
@@ -82,8 +80,7 @@ __global__ void __launch_bounds__(64) k_tuple_equilibrium_noise(const TenArgs a)
                 for (int t = lane; t < T; t += 64) {
                     const int b0 = a.band_lo[t];
                     const double* __restrict__ br = a.band + (int64_t)t * W;
-                    const int w0 = b0 < 0 ? (int)min((int64_t)W, -(int64_t)b0) : 0;
-                    const int w1 = (int)max((int64_t)0, min((int64_t)W, (int64_t)J - b0));
+                    const int w0 = band_first(b0, W), w1 = band_end(b0, W, J);
                     // every lane walks a row of its own, so a load touches 64 cache lines whatever its width: four
                     // entries per load (8-byte aligned: W may be odd), the adds in the order of the definition
                     double b = 0.0;
@@ -113,10 +110,8 @@ __global__ void __launch_bounds__(64) k_tuple_equilibrium_noise(const TenArgs a)
                     Va[s] = 0.0;
                 }
                 for (int t = lane; t < T; t += 64)
-                    Rt[t] = __dadd_rn(__dmul_rn(q, a.reward[(int64_t)i * T + t]),
-                                      __dmul_rn(p, a.noise_reward[(int64_t)i * T + t]));
-                const double margin = __ddiv_rn(__dmul_rn(__dmul_rn(__dmul_rn(2.0, gam), gam), a.eval_tol),
-                                                __dsub_rn(1.0, gam));
+                    Rt[t] = noise_blend(q, a.reward[(int64_t)i * T + t], p, a.noise_reward[(int64_t)i * T + t]);
+                const double margin = improve_margin(gam, a.eval_tol);
                 __syncthreads();
 
                 for (int n = 0;; n++) {
@@ -153,14 +148,9 @@ __global__ void __launch_bounds__(64) k_tuple_equilibrium_noise(const TenArgs a)
                         const int t0 = tup[s], tc = tcur[s];
                         const int b = t0 - ((t0 / ts) % nact) * ts;
                         const double qc = xt[tc];
-                        double bv = 0.0;
-                        int bt = 0;
-                        for (int act = 0; act < nact; act++) {
-                            const int t = b + act * ts;
-                            const double qv = xt[t];
-                            if (act == 0 || qv > bv) { bv = qv; bt = t; }
-                        }
-                        if (bv > __dadd_rn(qc, margin)) { tcur[s] = (uint16_t)bt; changed = true; }
+                        double bv;
+                        const int ba = first_max(nact, [&](int act) THRL_SOLVE_INLINE { return xt[b + act * ts]; }, bv);
+                        if (bv > __dadd_rn(qc, margin)) { tcur[s] = (uint16_t)(b + ba * ts); changed = true; }
                     }
                     const bool any = __ballot(changed) != 0;
                     __syncthreads();                     // tcur of every lane; every read of xt before it changes
@@ -175,11 +165,7 @@ __global__ void __launch_bounds__(64) k_tuple_equilibrium_noise(const TenArgs a)
                     a.loss_all[o] = nan; a.loss_tuples_mean[o] = nan; a.loss_cells_mean[o] = nan;
                     if (a.pi) { a.loss_w[o] = nan; a.diff_w[o] = nan; a.v_w[o] = nan; }
                 }
-                for (int s = lane; s < S; s += 64) {
-                    if (a.br_policy) a.br_policy[o * S + s] = (uint16_t)(((int)tup[s] / ts) % nact);
-                    if (a.v_opt) a.v_opt[o * S + s] = nan;
-                    if (a.v_pi) a.v_pi[o * S + s] = nan;
-                }
+                store_states_unsolved(a, o * S, S, lane, nan, [&](int s) THRL_SOLVE_INLINE { return ((int)tup[s] / ts) % nact; });
                 __syncthreads();
                 continue;
             }
@@ -190,15 +176,14 @@ __global__ void __launch_bounds__(64) k_tuple_equilibrium_noise(const TenArgs a)
             double lmax = -__builtin_huge_val();
             for (int s = lane; s < S; s += 64) {
                 const double vs = V[s], vp = Vpi[s];
-                const double l = (vs == vp || vs == 0.0) ? 0.0 : __ddiv_rn(__dsub_rn(vs, vp), vs);
+                const double l = rel_loss(vs, vp);
                 loss[s] = l;
                 if (l > lmax) lmax = l;
                 const int d = tcur[s] != tup[s] ? 1 : 0;
                 if (s < T) ndt += d; else ndc += d;
-                if (a.br_policy) a.br_policy[o * S + s] = (uint16_t)(((int)tcur[s] / ts) % nact);
-                if (a.v_opt) a.v_opt[o * S + s] = vs;
-                if (a.v_pi) a.v_pi[o * S + s] = vp;
+                store_state(a, o * S + s, ((int)tcur[s] / ts) % nact, vs, vp);
             }
+            // two counts in one loop, not wave_max_sum and a second loop: that order of the shuffles costs 68 bytes of scratch
 #pragma unroll
             for (int x = 32; x >= 1; x >>= 1) {
                 const double ol = __shfl_xor(lmax, x);
