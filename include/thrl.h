@@ -1707,6 +1707,112 @@ typedef struct {
 int thrl_tuple_equilibrium_noise(const thrl_cfg* cfg, const thrl_tuple_equilibrium_noise_args* args, void* stream);
 
 /*
+ * thrl_tuple_deviation_noise: the deviation test under demand noise (thrl_deviation_noise) for ANY mix of QTable,
+ * Reinforce and ActorCritic agents: does a deviation pay, do the others punish, does play return, in expectation, in
+ * the environment of thrl_tuple_stationary.  No reference counterpart.  Under noise greedy play follows no single path
+ * of tuples, so the answer is the propagation of a distribution: the tuple greedy play intends at a period is a Markov
+ * chain on the T action tuples, a forced deviation replaces the deviator's action in the tuple actually played for L
+ * periods, and the response is the sequence of distributions that follow from the one the shock hits.  No sampling.
+ * The world is thrl_tuple_stationary's, unchanged: the action tuples t < T = args.n_tuples, the J = args.n_cells cells,
+ * tuple_policy [G][N][T] and cell_policy [G][N][J] with F_g, tau_g, the clamping rule and tstride, the per-config tables
+ * reward, scaled, band_lo, band (W = band_w) and noise_reward, n(t, k), p_g and q_g = 1 - p_g with the host-visible and
+ * the per-game rules.  cell_w, price and noise_price are not read.  Of a valid cfg only n_agents, n_actions and gamma
+ * are used; nothing of a batch is read or written, every input is read only.  All arithmetic is float64, every
+ * operation rounded once, in the order written here; every sum runs over ascending index from 0.0.
+ *
+ *   R_i(u)    = q_g * reward_i(u) + p_g * noise_reward_i(u)   (thrl_tuple_stationary's expected reward)
+ *   Dv_g(t)   = t with the deviator d's action replaced, a map on tuples: by dev_action, or with dev_action = -1 by
+ *               d's one-period best response to the rivals' actions in t, the argmax over a < A_d of R_d(t with a in
+ *               place d), the first maximum under strict >.  With per-game noise Dv is per game
+ *   e_tau(t)  = Dv_g(t) for tau < L, t afterwards: the tuple actually played when greedy play intends t
+ *   m_tau(t)  = the probability that the tuple greedy play intends at period tau is t
+ *   m_0       = weights[g] (device double [G][T], required): the distribution the shock hits, e.g.
+ *               thrl_tuple_stationary's pi
+ *   the plain step, not the lazy one, so the iterate after tau steps is the distribution at period tau:
+ *     nu(k)   = sum_t m_tau(t) * n(e_tau(t), k)                       terms that are zero may be skipped
+ *     D(t')   = sum over the t with F_g(e_tau(t)) = t' of m_tau(t)
+ *     Nn(t')  = sum over the k with tau_g(k) = t' of nu(k)
+ *     m_{tau+1}(t') = q_g * D(t') + p_g * Nn(t')                      two products, one add
+ *   E_i(tau)  = sum_t m_tau(t) * R_i(e_tau(t)),  A_i(tau) = sum_t m_tau(t) * scaled_i(e_tau(t))
+ *   Dist(tau) = 0.5 * sum_t |m_tau(t) - m_0(t)|: the total-variation distance from the start (Dist(0) = 0)
+ *
+ * Rows reward_rows / action_rows [row_count][N][G] (optional) hold E_i(tau) / A_i(tau) for tau in [row_begin, row_begin +
+ * row_count): the layout of the episode rows, so thrl_group_stats reduces them as they are (E = row_count); dist_rows
+ * [row_count][G] (optional) holds Dist(tau).  The kernel walks all K periods whatever rows it stores.
+ *
+ * Outputs, per game:
+ *   base_reward[i][g] = sum_t m_0(t) * R_i(t): the expression of thrl_tuple_stationary's stat_reward, bit-equal to it
+ *                       with its pi as weights;  base_action[i][g] = sum_t m_0(t) * scaled_i(t)
+ *   dev_share[g]      = the sum of m_0(t) over the tuples with Dv_g(t) != t (+0.0 elsewhere): the long-run share of
+ *                       periods in which the deviation changes anything
+ *   gain[g]           = sum_{tau<K} w_tau * (E_d(tau) - base_reward_d), w_0 = 1, w_{tau+1} = w_tau * gamma_d (subtract,
+ *                       multiply, add); gamma_d = sweep_gamma[d][g] when given, else cfg.gamma[d]
+ *   gain_dev[g]       = the same sum over tau < L: what the deviation itself earns; gain - gain_dev is the aftermath
+ *   low[g]            = min_{L <= tau < K} (E_d(tau) - base_reward_d), low_step[g] its first tau; K == L: 0.0 and -1
+ *   ret_step[g]       = the first tau in [L, K] with Dist(tau) <= ret_tol, else -1
+ *   dist[g] = Dist(K),  mass[g] = sum_t m_K(t)
+ * A game whose noise_prob_g entry lies outside (0, 1] (NaN included) gets zeros in every float64 output, its rows
+ * included, and -1 in low_step and ret_step; no other game is affected.
+ *
+ * Working set.  A game is solved by one block in LDS: the two iterates and nu (16 T + 8 J bytes), the stable groupings
+ * of the cells by tau_g, of the tuples by F_g o Dv_g and of the tuples by F_g (2 J + 10 T + 6 bytes), Dv_g (2 T) and
+ * 512 (2 N + 2) bytes of staging, the sum rounded up to 16 bytes: 28 T + 10 J + 512 (2 N + 2) + 6.  Above
+ * THRL_TDN_MAX_LDS = 160 KB (a CU's LDS on CDNA4), or the device's own limit, the call returns THRL_ERR_UNSUPPORTED
+ * without launching; with two agents it does not within the limits on T and J (158,736 bytes at T = J = 4096), so every
+ * two-agent game thrl_tuple_stationary solves is solved here.
+ *
+ * Returns THRL_ERR_BAD_CONFIG for n_games < 1, flags or reserved != 0, a kind outside [0, 3], n_tuples < 1 or n_tuples
+ * != prod_i n_actions_i, a deviator outside [0, N), dev_len < 1, n_steps < dev_len or > THRL_DEV_MAX_STEPS, dev_action
+ * outside {-1} + [0, n_actions[d]), a row range outside [0, n_steps), n_cells < 1, band_w < 1, ret_tol < 0 or NaN, or a
+ * host-visible noise_prob outside (0, 1]; THRL_ERR_UNSUPPORTED for a CAC agent (kind 3), n_tuples > THRL_TP_MAX_TUPLES,
+ * n_cells > THRL_STAT_MAX_CELLS or the working set; THRL_ERR_NULL for a missing cfg, args, tuple_policy, cell_policy,
+ * table (reward, scaled, band_lo, band, noise_reward), weights or per-game output.  All of these are decided before
+ * any launch.
+ */
+#define THRL_TDN_MAX_LDS (160 * 1024)
+typedef struct {
+    int32_t n_games;                 /* G >= 1: games of tuple_policy and cell_policy    */
+    int32_t n_tuples;                /* T = prod_i n_actions_i <= THRL_TP_MAX_TUPLES     */
+    int32_t n_cells;                 /* J in [1, THRL_STAT_MAX_CELLS]                    */
+    int32_t band_w;                  /* W >= 1                                           */
+    int32_t deviator;                /* d in [0, N)                                      */
+    int32_t dev_len;                 /* L >= 1                                           */
+    int32_t n_steps;                 /* K >= L                                           */
+    int32_t dev_action;              /* fixed action index of d, or -1 = best response   */
+    int32_t row_begin;               /* rows stored: tau in [row_begin, row_begin + row_count) */
+    int32_t row_count;
+    int32_t flags;                   /* 0                                                */
+    int32_t reserved;                /* 0                                                */
+    int32_t kind[THRL_MAXA];         /* 0 = QTable, 1 = Reinforce, 2 = ActorCritic       */
+    double  noise_prob;              /* p in (0, 1], read when noise_prob_g is NULL      */
+    double  ret_tol;                 /* >= 0                                             */
+    const double* noise_prob_g;      /* device [G] or NULL                               */
+    const double* sweep_gamma;       /* device [N][G] or NULL                            */
+    const uint16_t* tuple_policy;    /* device [G][N][T]                                 */
+    const uint16_t* cell_policy;     /* device [G][N][J]                                 */
+    const double* reward;            /* device [N][T]                                    */
+    const double* scaled;            /* device [N][T]                                    */
+    const int32_t* band_lo;          /* device [T]                                       */
+    const double* band;              /* device [T][W]                                    */
+    const double* noise_reward;      /* device [N][T]                                    */
+    const double* weights;           /* device [G][T] (required): m_0                    */
+    double*  base_reward;            /* device [N][G]                                    */
+    double*  base_action;            /* device [N][G]                                    */
+    double*  dev_share;              /* device [G]                                       */
+    double*  gain;                   /* device [G]                                       */
+    double*  gain_dev;               /* device [G]                                       */
+    double*  low;                    /* device [G]                                       */
+    int32_t* low_step;               /* device [G]                                       */
+    int32_t* ret_step;               /* device [G]                                       */
+    double*  dist;                   /* device [G]                                       */
+    double*  mass;                   /* device [G]                                       */
+    double*  reward_rows;            /* device [row_count][N][G] or NULL                 */
+    double*  action_rows;            /* device [row_count][N][G] or NULL                 */
+    double*  dist_rows;              /* device [row_count][G] or NULL                    */
+} thrl_tuple_deviation_noise_args;
+int thrl_tuple_deviation_noise(const thrl_cfg* cfg, const thrl_tuple_deviation_noise_args* args, void* stream);
+
+/*
  * thrl_price_probs: the action PROBABILITIES of the neural agents at a free list of prices, where thrl_price_policy
  * gives their greedy action.  No reference counterpart.  For every agent i with kind[i] = 1 / 2 (Reinforce /
  * ActorCritic) the call writes prob[i] (device float32 [G][J][A_i], G = args.n_games in [1, cfg.n_games], J =

@@ -376,6 +376,28 @@ class TupleEquilibriumNoiseArgs(ctypes.Structure):
     ]
 
 
+TDN_MAX_LDS = 160 * 1024
+
+
+class TupleDeviationNoiseArgs(ctypes.Structure):
+    """thrl_tuple_deviation_noise_args"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("n_cells", ctypes.c_int32), ("band_w", ctypes.c_int32),
+        ("deviator", ctypes.c_int32), ("dev_len", ctypes.c_int32), ("n_steps", ctypes.c_int32),
+        ("dev_action", ctypes.c_int32), ("row_begin", ctypes.c_int32), ("row_count", ctypes.c_int32),
+        ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("kind", ctypes.c_int32 * MAXA),
+        ("noise_prob", ctypes.c_double), ("ret_tol", ctypes.c_double),
+        ("noise_prob_g", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p), ("tuple_policy", ctypes.c_void_p),
+        ("cell_policy", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("scaled", ctypes.c_void_p),
+        ("band_lo", ctypes.c_void_p), ("band", ctypes.c_void_p), ("noise_reward", ctypes.c_void_p),
+        ("weights", ctypes.c_void_p),
+        ("base_reward", ctypes.c_void_p), ("base_action", ctypes.c_void_p), ("dev_share", ctypes.c_void_p),
+        ("gain", ctypes.c_void_p), ("gain_dev", ctypes.c_void_p), ("low", ctypes.c_void_p),
+        ("low_step", ctypes.c_void_p), ("ret_step", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("mass", ctypes.c_void_p),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p), ("dist_rows", ctypes.c_void_p),
+    ]
+
+
 SP_START_TUPLE = 1
 SP_MAX_LDS = 160 * 1024
 
@@ -440,7 +462,7 @@ SYMBOLS = [
     "thrl_policy_track", "thrl_equilibrium", "thrl_crossplay", "thrl_attractors", "thrl_stationary",
     "thrl_equilibrium_noise", "thrl_deviation_noise",
     "thrl_tuple_policy", "thrl_tuple_walk", "thrl_tuple_deviation", "thrl_tuple_equilibrium",
-    "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary", "thrl_tuple_equilibrium_noise", "thrl_price_probs", "thrl_sampled_chain",
+    "thrl_tuple_attractors", "thrl_price_policy", "thrl_tuple_stationary", "thrl_tuple_equilibrium_noise", "thrl_tuple_deviation_noise", "thrl_price_probs", "thrl_sampled_chain",
     "thrl_sampled_noise_chain",
 ]
 CAC_PARAMS = 1283
@@ -579,6 +601,8 @@ def load():
     L.thrl_tuple_stationary.argtypes = [cfgp, ctypes.POINTER(TupleStationaryArgs), vp]
     L.thrl_tuple_equilibrium_noise.restype = ctypes.c_int
     L.thrl_tuple_equilibrium_noise.argtypes = [cfgp, ctypes.POINTER(TupleEquilibriumNoiseArgs), vp]
+    L.thrl_tuple_deviation_noise.restype = ctypes.c_int
+    L.thrl_tuple_deviation_noise.argtypes = [cfgp, ctypes.POINTER(TupleDeviationNoiseArgs), vp]
     L.thrl_price_probs.restype = ctypes.c_int
     L.thrl_price_probs.argtypes = [cfgp, ctypes.POINTER(PriceProbsArgs), vp]
     L.thrl_sampled_chain.restype = ctypes.c_int

@@ -467,6 +467,36 @@ class AnalysisMethods:
                             start=start, rows=rows, group_stats=group_stats, tuple_policy=tuple_policy,
                             budget=budget or ta.dv.ROW_BUDGET)
 
+    def greedy_deviation_noise(self, deviator=0, steps=32, dev_len=1, action="best_response", noise_prob=None,
+                               resolution=1024, ret_tol=1e-6, weights="stationary", rows=False, group_stats=None,
+                               budget=None, tuple_policy=None, cell_policy=None, n_games=None, tabs=None, tol=1e-12,
+                               max_iters=8192):
+        """The deviation test UNDER DEMAND NOISE for ANY mix of QTable, Reinforce and ActorCritic agents
+        (tuple_analysis.deviation_noise, thrl_tuple_deviation_noise; definitions in include/thrl.h): the expected
+        impulse response of noisy greedy play to a deviation.  In the environment of greedy_stationary() a game follows
+        no single path of tuples, so the test propagates a distribution over the tuple greedy play intends: from
+        `weights` ("stationary" = each game's long-run distribution over the tuple played, greedy_stationary(pi=True,
+        start="reset", tol, max_iters) on the same tables and strategies -- its last iterate also where that iteration
+        stopped at its step limit; or [G, T] values) deviator `deviator` plays `action` ("best_response": its one-period
+        best response to the rivals' actions in every tuple, or an action index) in place of its own for dev_len of
+        `steps` periods, every other period is greedy.  Returns a dict of numpy arrays: base_reward, base_action [N, G]
+        (what the start distribution earns; with stationary weights greedy_stationary()'s stat_reward, bit for bit),
+        dev_share (the share of periods in which the deviation changes anything), gain (discounted by the per-game sweep
+        gamma, else the deviator's own gamma), gain_dev (its first dev_len periods), low, low_step (the deviator's worst
+        period after the deviation), ret_step (the first period from dev_len on whose distribution is within ret_tol of
+        the start in total variation, -1: none), dist, mass [G], noise_prob [G], stat_iters, n_switch, unresolved [G]
+        (the sampling diagnostics of greedy_stationary()), T, n_cells.  rows=True adds reward_rows / action_rows
+        [steps, N, G] (the expected rewards and actions per period) and dist_rows [steps, G]; group_stats (a GroupSpec)
+        reduces the rows on the device as greedy_deviation() does.  noise_prob, resolution, tuple_policy, cell_policy,
+        n_games and tabs as in greedy_stationary().  A batch with a CAC agent or more than 4096 action tuples or cells
+        raises ValueError; a working set above a CU's LDS is THRL_ERR_UNSUPPORTED."""
+        from . import tuple_analysis as ta
+        self._ready()
+        return ta.deviation_noise(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action,
+                                  noise_prob=noise_prob, resolution=resolution, ret_tol=ret_tol, weights=weights, rows=rows,
+                                  group_stats=group_stats, budget=budget or ta.dv.ROW_BUDGET, tuple_policy=tuple_policy,
+                                  cell_policy=cell_policy, n_games=n_games, tabs=tabs, tol=tol, max_iters=max_iters)
+
     def greedy_equilibrium(self, agents=None, start=None, policies=False, tol=0.0, tuple_policy=None):
         """The equilibrium check for ANY mix of QTable, Reinforce and ActorCritic agents (tuple_analysis.equilibrium,
         thrl_tuple_equilibrium): equilibrium's outputs with the game's T action tuples as the state set

@@ -20,6 +20,7 @@
 #include "thrl_host.h"
 #include "thrl_tuple_analysis.h"
 #include "thrl_tuple_attractors.h"
+#include "thrl_tuple_deviation_noise.h"
 #include "thrl_tuple_equilibrium_noise.h"
 #include "thrl_tuple_play.h"
 #include "thrl_sampled.h"
@@ -711,6 +712,55 @@ int thrl_tuple_equilibrium_noise(const thrl_cfg* c, const thrl_tuple_equilibrium
     const int grid = grid_for(cus, lds_cu, a.lds_bytes, kTenMaxBlocksPerCu, a.G);
     const int e = thrl::launch_tuple_equilibrium_noise(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_tuple_equilibrium_noise launch") : THRL_OK;
+}
+
+int thrl_tuple_deviation_noise(const thrl_cfg* c, const thrl_tuple_deviation_noise_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_tuple_stationary's checks in its order, with the deviation and its rows as thrl_deviation_noise checks them;
+    // every host-visible argument is checked before the device is touched
+    if ((rc = check_games(x->n_games)) != THRL_OK) return rc;
+    if (x->flags != 0) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_deviator(c, x->deviator, x->dev_len, x->n_steps)) != THRL_OK) return rc;
+    if ((rc = check_dev_action(c, x->deviator, x->dev_action)) != THRL_OK) return rc;
+    if ((rc = check_rows(x->row_begin, x->row_count, x->n_steps)) != THRL_OK) return rc;
+    if ((rc = check_cells_band(x->n_cells, x->band_w)) != THRL_OK) return rc;
+    if ((rc = check_tol(x->ret_tol, "ret_tol")) != THRL_OK) return rc;
+    if ((rc = check_noise_prob(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
+    if ((rc = check_cell_limit("thrl_tuple_deviation_noise", x->n_cells)) != THRL_OK) return rc;
+    TdnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.G = x->n_games; a.N = N; a.T = x->n_tuples; a.J = x->n_cells; a.W = x->band_w;
+    const int64_t need = thrl::tdn_layout(a);            // the working set of include/thrl.h
+    if (need > THRL_TDN_MAX_LDS) return lds_refusal("thrl_tuple_deviation_noise", need, N, x->n_cells);
+    if (!x->tuple_policy || !x->cell_policy || !x->reward || !x->scaled || !x->band_lo || !x->band || !x->noise_reward)
+        return missing("tuple_policy / cell_policy / reward / scaled / band_lo / band / noise_reward");
+    if (!x->weights) return missing("weights");
+    if (!x->base_reward || !x->base_action || !x->dev_share || !x->gain || !x->gain_dev || !x->low || !x->low_step
+        || !x->ret_step || !x->dist || !x->mass)
+        return missing("base_reward / base_action / dev_share / gain / gain_dev / low / low_step / ret_step / dist / mass");
+
+    a.d = x->deviator; a.L = x->dev_len; a.K = x->n_steps; a.dev_action = x->dev_action;
+    a.row_begin = x->row_begin; a.row_count = x->row_count;
+    a.noise_prob = x->noise_prob; a.ret_tol = x->ret_tol; a.gamma_d = c->gamma[x->deviator];
+    tuple_strides(c, a.n_actions, a.tstride);
+    a.noise_prob_g = x->noise_prob_g; a.sweep_gamma = x->sweep_gamma;
+    a.tuple_policy = x->tuple_policy; a.cell_policy = x->cell_policy; a.reward = x->reward; a.scaled = x->scaled;
+    a.band_lo = x->band_lo; a.band = x->band; a.noise_reward = x->noise_reward; a.weights = x->weights;
+    a.base_reward = x->base_reward; a.base_action = x->base_action; a.dev_share = x->dev_share; a.gain = x->gain;
+    a.gain_dev = x->gain_dev; a.low = x->low; a.low_step = x->low_step; a.ret_step = x->ret_step; a.dist = x->dist;
+    a.mass = x->mass; a.reward_rows = x->reward_rows; a.action_rows = x->action_rows; a.dist_rows = x->dist_rows;
+    int cus = 0, lds_cu = 0;
+    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
+    if (lds_cu > 0 && a.lds_bytes > lds_cu) return lds_refusal("thrl_tuple_deviation_noise", need, N, x->n_cells);
+    const int grid = grid_for(cus, lds_cu, a.lds_bytes, kTdnMaxBlocksPerCu, a.G);
+    const int e = thrl::launch_tuple_deviation_noise(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_tdn_chain launch") : THRL_OK;
 }
 
 int thrl_price_probs(const thrl_cfg* c, const thrl_price_probs_args* x, void* stream) {

@@ -18,51 +18,11 @@
 //   ballot, their widths added by lane 0 in ascending k.
 #include "thrl_tuple_stationary.h"
 #include "thrl_chain_dev.h"
+#include "thrl_group_dev.h"
 
 namespace thrl {
 
 namespace {
-
-// the stable grouping of n items by key(idx) in [0, T): perm[s] = the idx at sorted place s, first[key] = the first place
-// with a key >= key (first[T] = n), so the items of key are perm[first[key] .. first[key + 1])
-__device__ __forceinline__ void ts_group(const TsArgs& a, const uint16_t* __restrict__ pol, int n, uint32_t* srt,
-                                         uint16_t* perm, uint16_t* first, int tid) {
-    int p2 = 1;
-    while (p2 < n) p2 <<= 1;
-    __syncthreads();                                     // whatever read the aliased arrays is done
-    for (int idx = tid; idx < p2; idx += kTsBlock) {
-        uint32_t w = 0xffffffffu;
-        if (idx < n) {
-            int key = 0;
-            for (int i = 0; i < a.N; i++) key += min((int)pol[(int64_t)i * n + idx], a.n_actions[i] - 1) * a.tstride[i];
-            w = ((uint32_t)key << 16) | (uint32_t)idx;
-        }
-        srt[idx] = w;
-    }
-    __syncthreads();
-    for (int k = 2; k <= p2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int idx = tid; idx < p2; idx += kTsBlock) {
-                const int ixj = idx ^ j;
-                if (ixj > idx) {
-                    const uint32_t x = srt[idx], y = srt[ixj];
-                    if ((x > y) == ((idx & k) == 0)) { srt[idx] = y; srt[ixj] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int s = tid; s < n; s += kTsBlock) {
-        const uint32_t w = srt[s];
-        const int key = (int)(w >> 16);
-        perm[s] = (uint16_t)(w & 0xffffu);
-        const int prev = s > 0 ? (int)(srt[s - 1] >> 16) : -1;
-        for (int kk = prev + 1; kk <= key; kk++) first[kk] = (uint16_t)s;
-        if (s == n - 1)
-            for (int kk = key + 1; kk <= a.T; kk++) first[kk] = (uint16_t)n;
-    }
-    __syncthreads();
-}
 
 __global__ void __launch_bounds__(kTsBlock) k_ts_chain(const TsArgs a) {
     extern __shared__ __align__(16) unsigned char s_mem[];
@@ -94,8 +54,8 @@ __global__ void __launch_bounds__(kTsBlock) k_ts_chain(const TsArgs a) {
         }
 
         // ---- the cells by the tuple they play, the tuples by their successor
-        ts_group(a, a.cell_policy + g * N * J, J, srt, permk, firstk, tid);
-        ts_group(a, a.tuple_policy + g * N * T, T, srt, permt, firstt, tid);
+        ts_group<kTsBlock>(a, a.cell_policy + g * N * J, nullptr, J, srt, permk, firstk, tid);
+        ts_group<kTsBlock>(a, a.tuple_policy + g * N * T, nullptr, T, srt, permt, firstt, tid);
 
         for (int t = tid; t < T; t += kTsBlock) {
             double m0 = 0.0;

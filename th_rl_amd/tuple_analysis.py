@@ -27,6 +27,12 @@ loss_tuples_mean, loss_cells_mean [N, G] and, weighted by where decisions are ma
 tuple_stationary.run's pi, or a pi of the caller's), loss_w, diff_w, v_w [N, G], with equilibrium.flags_noise's br_all,
 br_w and perfect.  The noise-free artefacts are what they were; the noisy ones are geqn_*.npy and
 greedy_equilibrium_noise.json.
+
+The deviation test under demand noise (thrl_tuple_deviation_noise; the option "noise" of training.greedy_deviation) is
+deviation.run_noise on the tuples: deviation_noise() starts from the long-run distribution over the tuple played
+(tuple_stationary.run's pi from the reset start, or weights of the caller's), replaces the deviator's action in the tuple
+played for dev_len periods and returns deviation.run_noise's fields plus n_switch, unresolved, T.  The noise-free
+artefacts are what they were; the noisy ones are gdevn_*.npy, gdevn<d>_*.npy and greedy_deviation_noise.json.
 """
 import ctypes
 import os
@@ -44,6 +50,7 @@ from ._lib import ThrlError
 DEV_DEFAULTS = dict(dv.DEFAULTS)
 EQ_DEFAULTS = dict(eq.DEFAULTS)
 NOISE_DEFAULTS = dict(eq.NOISE_DEFAULTS, resolution=1024)
+DEV_NOISE_DEFAULTS = dict(dv.NOISE_DEFAULTS, resolution=1024)
 NOISE_INT = ("iters", "sweeps", "n_diff_tuples", "n_diff_cells")
 NOISE_FLOAT = ("loss_all", "loss_tuples_mean", "loss_cells_mean")
 NOISE_WEIGHTED = eq.NOISE_WEIGHTED
@@ -83,6 +90,11 @@ def parse_deviation_options(opt, config):
     name = "training.greedy_deviation"
     ps, _ = tp.check_config(config)
     n = len(ps)
+    noise = None
+    if isinstance(opt, dict) and "noise" in opt:
+        opt = dict(opt)
+        noise = opt.pop("noise")
+        noise = None if noise is None or noise is False else parse_deviation_noise(noise, config)
     out = an.options("greedy_deviation", opt, dict(DEV_DEFAULTS, agents=list(range(n))))
     out["agents"] = _agents(name, out["agents"], n)
     out["steps"], out["dev_len"] = _int(name + ".steps", out["steps"]), _int(name + ".dev_len", out["dev_len"])
@@ -98,6 +110,28 @@ def parse_deviation_options(opt, config):
         out["horizon"] = _int(name + ".horizon", out["horizon"])
         if not 1 <= out["horizon"] <= _lib.DEV_MAX_HORIZON:
             raise ValueError("%s.horizon=%d out of [1, %d]" % (name, out["horizon"], _lib.DEV_MAX_HORIZON))
+    if noise is not None:
+        out["noise"] = noise
+    return out
+
+
+def parse_deviation_noise(noise, config):
+    """training.greedy_deviation.noise (true or a dict) -> the dict with every key filled in: deviation.parse_noise's
+    noise_prob (None = the run's own noise, refused for a noise-free run), ret_tol, tol and max_iters, and resolution
+    (tuple_stationary's uniform cuts of the price axis; more than its MAX_CELLS cells is refused before training)."""
+    from . import tuple_stationary as ts
+    name = "training.greedy_deviation.noise"
+    out = an.options("greedy_deviation.noise", noise, DEV_NOISE_DEFAULTS)
+    resolution = out.pop("resolution")
+    try:
+        out = dv.parse_noise(out, config)
+    except ValueError as e:
+        raise ValueError(str(e).replace("training.deviation.noise", name))
+    out["resolution"] = ts._check_resolution(resolution, name + ".resolution")
+    try:
+        ts.cuts(config, out["resolution"])
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e))
     return out
 
 
@@ -461,6 +495,143 @@ def equilibrium_noise(batch, agents=None, noise_prob=None, resolution=NOISE_DEFA
     return res
 
 
+def deviation_noise(batch, deviator=0, steps=32, dev_len=1, action="best_response", noise_prob=None,
+                    resolution=DEV_NOISE_DEFAULTS["resolution"], ret_tol=1e-6, weights="stationary", rows=False,
+                    group_stats=None, budget=dv.ROW_BUDGET, tuple_policy=None, cell_policy=None, n_games=None, tabs=None,
+                    tol=1e-12, max_iters=8192):
+    """thrl_tuple_deviation_noise for the first n_games (default all) games of `batch` (see
+    AnalysisMethods.greedy_deviation_noise).  tabs: tuple_stationary.tables(batch.config, resolution).  tuple_policy /
+    cell_policy: the strategies of tuple_play.extract() / tuple_stationary.extract_cells() (default: extracted here, once,
+    for this call and for the stationary one).  weights="stationary": tuple_stationary.run(pi=True, start="reset", tol,
+    max_iters) on the same tables and strategies gives m_0 [G, T]; a game whose iteration stopped at its step limit starts
+    from its last iterate all the same, and a game that iteration did not solve is not solved here.  The rows are
+    produced in tau-chunks of at most `budget` bytes per device buffer.  Returns a dict of numpy arrays."""
+    import torch
+    from . import stationary as sn
+    from . import tuple_stationary as ts
+    N = batch.N
+    G = an.games(batch, n_games, "greedy_deviation_noise")
+    K, L = int(steps), int(dev_len)
+    if not 0 <= int(deviator) < N:
+        raise ThrlError("deviator %d out of [0, %d)" % (int(deviator), N))
+    if group_stats is not None and group_stats.G != G:
+        raise ThrlError("group_stats spec is for %d games, this call has %d" % (group_stats.G, G))
+    if tabs is None:
+        tabs = ts.tables(batch.config, resolution)
+    tp._batch_tables(batch, tabs)
+    dev = batch.device
+    J, T, W = int(tabs["n_cells"]), int(tabs["n_tuples"]), int(tabs["band_w"])
+    if tuple_policy is None:
+        tuple_policy = tp.extract(batch, tabs)
+    if not an.is_policy(tuple_policy, (batch.G, N, T), batch.state.device):
+        an.check_policy(batch, tuple_policy, (G, N, T), "greedy_deviation_noise", "tuple_policy")
+    if cell_policy is None:
+        cell_policy = ts.extract_cells(batch, tabs, n_games=G)
+    an.check_policy(batch, cell_policy, (G, N, J), "greedy_deviation_noise", "cell_policy")
+    a = _lib.TupleDeviationNoiseArgs()
+    a.n_games, a.n_tuples, a.n_cells, a.band_w = G, T, J, W
+    a.deviator, a.dev_len, a.n_steps, a.dev_action = int(deviator), L, K, dv.action_index(action)
+    a.ret_tol = float(ret_tol)
+    for i, k in enumerate(tp._kinds(batch)):
+        a.kind[i] = tp.KINDS[k]
+    with torch.cuda.device(dev):
+        p, p_g = sn.resolve_noise(batch, noise_prob, G)
+        stat_iters = np.zeros(G, np.int32)
+        if isinstance(weights, str):
+            if weights != "stationary":
+                raise ThrlError("greedy_deviation_noise: weights must be 'stationary' or a [G, T] array, got %r" % (weights,))
+            st = ts.run(batch, noise_prob=noise_prob, start="reset", tol=tol, max_iters=max_iters, pi=True,
+                        tuple_policy=tuple_policy, cell_policy=cell_policy, n_games=G, tabs=tabs)
+            m0 = torch.from_numpy(np.ascontiguousarray(st["pi"])).to(dev)
+            stat_iters = np.asarray(st["iters"], np.int32)
+            n_switch, unresolved = st["n_switch"], st["unresolved"]
+        else:
+            if weights is None:
+                raise ThrlError("greedy_deviation_noise: weights must be 'stationary' or a [G, T] array, got None")
+            if isinstance(weights, torch.Tensor):
+                m0 = weights.to(device=dev, dtype=torch.float64).contiguous()
+            else:
+                m0 = torch.from_numpy(np.ascontiguousarray(np.asarray(weights, np.float64))).to(dev)
+            if tuple(m0.shape) != (G, T):
+                raise ThrlError("greedy_deviation_noise: weights must be shaped %s, got %s" % ((G, T), tuple(m0.shape)))
+            n_switch, unresolved = _switches(batch, tabs, cell_policy, G)
+        keep = an.bind_tables(a, tabs, [("reward", (N, T), np.float64), ("scaled", (N, T), np.float64),
+                                        ("band_lo", (T,), np.int32), ("band", (T, W), np.float64),
+                                        ("noise_reward", (N, T), np.float64)], dev, "greedy_deviation_noise")
+        if p_g is not None:
+            a.noise_prob_g = p_g.data_ptr()
+        else:
+            a.noise_prob = p
+        gam = _gamma(batch)
+        if gam is not None:
+            gam = gam[:, :G].contiguous()
+            a.sweep_gamma = gam.data_ptr()
+        a.tuple_policy, a.cell_policy, a.weights = tuple_policy.data_ptr(), cell_policy.data_ptr(), m0.data_ptr()
+        out = an.outputs(dev, (dv.NOISE_AGENT, (N, G), "float64"), (dv.NOISE_FLOAT, (G,), "float64"),
+                         (dv.NOISE_INT, (G,), "int32"))
+        an.bind(a, out)
+        want = bool(rows) or group_stats is not None
+        chunk = max(1, min(K, int(budget) // (8 * N * G))) if want else K
+        st = group_stats.zeros(K, dev) if group_stats is not None else None
+        host_r, host_a, host_d = [], [], []
+        b0 = 0
+        while True:
+            k = min(chunk, K - b0) if want else 0
+            rr = ra = rd = None
+            if k:
+                rr = torch.empty((k, N, G), dtype=torch.float64, device=dev)
+                ra = torch.empty((k, N, G), dtype=torch.float64, device=dev)
+                rd = torch.empty((k, G), dtype=torch.float64, device=dev) if rows else None
+            a.row_begin, a.row_count = b0, k
+            a.reward_rows = rr.data_ptr() if rr is not None else None
+            a.action_rows = ra.data_ptr() if ra is not None else None
+            a.dist_rows = rd.data_ptr() if rd is not None else None
+            _lib.check(batch.L.thrl_tuple_deviation_noise(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                       "thrl_tuple_deviation_noise")
+            if st is not None and k:
+                group_stats.reduce(batch.L, rr, ra, k, st, batch._stream(), at=b0)
+            if rows and k:
+                host_r.append(rr.cpu().numpy())
+                host_a.append(ra.cpu().numpy())
+                host_d.append(rd.cpu().numpy())
+            b0 += k
+            if b0 >= K or not want:
+                break
+        torch.cuda.synchronize(dev)
+        res = an.fetch(out)
+        res["noise_prob"] = np.full(G, p, np.float64) if p_g is None else p_g.cpu().numpy()
+        if rows:
+            res["reward_rows"] = np.concatenate(host_r, axis=0)
+            res["action_rows"] = np.concatenate(host_a, axis=0)
+            res["dist_rows"] = np.concatenate(host_d, axis=0)
+        if st is not None:
+            from .group_stats import to_numpy
+            res["group_stats"] = to_numpy(st)
+        del keep
+    res["stat_iters"], res["n_switch"], res["unresolved"] = stat_iters, np.asarray(n_switch, np.int32), np.asarray(unresolved)
+    res["n_cells"], res["T"], res["ret_tol"] = J, T, float(ret_tol)
+    res["resolution"] = int(tabs.get("resolution", resolution))
+    return res
+
+
+def _switches(batch, tabs, cell_policy, G):
+    """(n_switch int32 [G], unresolved [G]) of thrl_tuple_stationary's sampling diagnostics, on the host: the pairs of
+    adjacent cells on which the clamped entry of some neural agent differs, and their share of the price axis, the
+    widths added in ascending k from 0.0."""
+    cp = cell_policy[:G].cpu().numpy().view(np.uint16).astype(np.int64)
+    J = cp.shape[2]
+    w = np.asarray(tabs["cell_w"], np.float64)
+    flag = np.zeros((G, max(J - 1, 0)), bool)
+    for i, k in enumerate(tp._kinds(batch)):
+        if k != "QTable":
+            e = np.minimum(cp[:, i], int(tabs["n_actions"][i]) - 1)
+            flag |= e[:, :-1] != e[:, 1:]
+    un = np.zeros(G)
+    for k in range(J - 1):
+        un = np.where(flag[:, k], un + 0.5 * (w[k] + w[k + 1]), un)
+    return flag.sum(axis=1).astype(np.int32), un
+
+
 # ---------------------------------------------------------------------------------------------- host side
 def summarize_equilibrium_noise(games, ids, n_groups, agents, tol=0.0):
     """equilibrium.summarize_noise's rows (per (group, agent): games, capped, br_all, br_w, the quantiles of loss_all and
@@ -507,6 +678,79 @@ def load_equilibrium_noise_games(d):
         g.update(br_policy=np.load(os.path.join(d, "geqn_policy.npy")), v_opt=np.load(os.path.join(d, "geqn_v_opt.npy")),
                  v_pi=np.load(os.path.join(d, "geqn_v_pi.npy")))
     return g
+
+
+def summarize_deviation_noise(games, ids, n_groups, deviators):
+    """deviation.summarize_noise's rows (one per (group, deviator)) with n_switch_max and unresolved_mean over the
+    group's games (solved or not: they describe the sampling of the strategies, not the chain) added."""
+    rows = dv.summarize_noise(games, ids, n_groups, deviators)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    for r in rows:
+        g = games[r["deviator"]]
+        m = ids == r["group"]
+        r["n_switch_max"] = int(np.asarray(g["n_switch"])[m].max()) if m.any() else None
+        r["unresolved_mean"] = an.mean(np.asarray(g["unresolved"], np.float64)[m])
+    return rows
+
+
+def save_deviation_noise_games(d, deviator, r):
+    """gdevn<d>_games float64 [6, G] (dev_share, gain, gain_dev, low, dist, mass), gdevn<d>_steps int32 [2, G] (low_step,
+    ret_step), gdevn<d>_base float64 [2, N, G] (base_reward, base_action); gdevn_prob [G] (the noise probabilities
+    analysed), gdevn_stat int32 [2, G] (the stationary iteration behind the weights: iters, n_switch) and
+    gdevn_unresolved [G] are the same for every deviator."""
+    np.save(os.path.join(d, "gdevn%d_games.npy" % deviator), np.stack([r[f] for f in dv.NOISE_FLOAT]).astype(np.float64))
+    np.save(os.path.join(d, "gdevn%d_steps.npy" % deviator), np.stack([r[f] for f in dv.NOISE_INT]).astype(np.int32))
+    np.save(os.path.join(d, "gdevn%d_base.npy" % deviator), np.stack([r[f] for f in dv.NOISE_AGENT]).astype(np.float64))
+    np.save(os.path.join(d, "gdevn_prob.npy"), np.asarray(r["noise_prob"], np.float64))
+    np.save(os.path.join(d, "gdevn_stat.npy"), np.stack([r["stat_iters"], r["n_switch"]]).astype(np.int32))
+    np.save(os.path.join(d, "gdevn_unresolved.npy"), np.asarray(r["unresolved"], np.float64))
+
+
+def load_deviation_noise_games(d, deviator):
+    """The per-game arrays of the test under noise a run directory holds for `deviator` (training.greedy_deviation.noise)."""
+    gm = np.load(os.path.join(d, "gdevn%d_games.npy" % deviator))
+    st = np.load(os.path.join(d, "gdevn%d_steps.npy" % deviator))
+    base = np.load(os.path.join(d, "gdevn%d_base.npy" % deviator))
+    g = {f: gm[k] for k, f in enumerate(dv.NOISE_FLOAT)}
+    g.update({f: st[k] for k, f in enumerate(dv.NOISE_INT)})
+    g.update({f: base[k] for k, f in enumerate(dv.NOISE_AGENT)})
+    g["noise_prob"] = np.load(os.path.join(d, "gdevn_prob.npy"))
+    stat = np.load(os.path.join(d, "gdevn_stat.npy"))
+    g["stat_iters"], g["n_switch"] = stat[0], stat[1]
+    g["unresolved"] = np.load(os.path.join(d, "gdevn_unresolved.npy"))
+    return g
+
+
+def write_deviation_noise(exp_path, batch, config, opt, ids, n_groups, spec=None, histograms=False, budget=dv.ROW_BUDGET,
+                          tuple_policy=None):
+    """The outputs of the option "noise" of training.greedy_deviation: per deviator gdevn<d>_games / _steps / _base.npy,
+    gdevn_prob / gdevn_stat / gdevn_unresolved.npy (save_deviation_noise_games), gdevn<d>_*.npy group statistics of the
+    response curves with a spec, and greedy_deviation_noise.json.  The cells' strategies and the long-run distribution
+    are computed once for all deviators."""
+    from . import trainer
+    from . import tuple_stationary as ts
+    nz = opt["noise"]
+    tabs = ts.tables(config, nz["resolution"])
+    if tuple_policy is None:
+        tuple_policy = tp.extract(batch, tabs)
+    cell_policy = ts.extract_cells(batch, tabs)
+    st = ts.run(batch, noise_prob=nz["noise_prob"], start="reset", tol=nz["tol"], max_iters=nz["max_iters"], pi=True,
+                tuple_policy=tuple_policy, cell_policy=cell_policy, tabs=tabs)
+    games = {}
+    for d in opt["agents"]:
+        r = deviation_noise(batch, deviator=d, steps=opt["steps"], dev_len=opt["dev_len"], action=opt["action"],
+                            noise_prob=nz["noise_prob"], ret_tol=nz["ret_tol"], weights=st["pi"], group_stats=spec,
+                            budget=budget, tuple_policy=tuple_policy, cell_policy=cell_policy, tabs=tabs)
+        r.update(stat_iters=np.asarray(st["iters"], np.int32), n_switch=st["n_switch"], unresolved=st["unresolved"])
+        games[d] = r
+        save_deviation_noise_games(exp_path, d, r)
+        if spec is not None:
+            trainer.save_group_stats(exp_path, "gdevn%d" % d, r["group_stats"], spec, histograms)
+    first = games[opt["agents"][0]]
+    an.save_json(os.path.join(exp_path, "greedy_deviation_noise.json"),
+                 {"options": opt, "n_cells": int(first["n_cells"]), "T": int(first["T"]), "quantiles": list(dv.QUANTILES),
+                  "summary": summarize_deviation_noise(games, ids, n_groups, opt["agents"])})
+    return games
 
 
 def _no_start(rows, start, ids):
@@ -632,7 +876,8 @@ def write_deviation(exp_path, batch, config, opt, ids, n_groups, spec=None, hist
     """train_one's training.greedy_deviation outputs, with the shapes of deviation.write_artefacts': gdev_cycle.npy int32
     [3, G] (mu, lam, start), gdev_cycle_reward / gdev_cycle_action [N, G], per deviator gdev<d>_post.npy int32 [4, G]
     (mu_post, lam_post, ret_step, act_dev) and gdev<d>_gain.npy [G], gdev<d>_*.npy group statistics with a spec, and
-    greedy_deviation.json.  Returns the last deviator's per-game arrays."""
+    greedy_deviation.json; with the option "noise" the test under demand noise after them (write_deviation_noise).
+    Returns the last deviator's per-game arrays."""
     from . import trainer
     nash, cartel = dv.optimal(config)
     tabs = tp.tables(config)
@@ -654,6 +899,9 @@ def write_deviation(exp_path, batch, config, opt, ids, n_groups, spec=None, hist
         summary += summarize_deviation(r, ids, n_groups, nash, cartel, d)
     an.save_json(os.path.join(exp_path, "greedy_deviation.json"),
                  dict(dv.describe(dict(opt, horizon_used=int(r["horizon"])), nash, cartel, summary), T=int(tabs["T"])))
+    if opt.get("noise"):        # the test under demand noise after it; what is above is what it is without the option
+        write_deviation_noise(exp_path, batch, config, opt, ids, n_groups, spec=spec, histograms=histograms, budget=budget,
+                              tuple_policy=tuple_policy)
     return dict(r, full_cycle=opt["horizon"] is None)
 
 

@@ -570,6 +570,42 @@ def greedy_deviation_games(exp_path, deviator=0):
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
 
 
+def greedy_deviation_noise_summary(exp_path):
+    """A run's deviation test under demand noise in tuple form (training.greedy_deviation with "noise"):
+    greedy_deviation_noise.json's summary as a DataFrame with deviation_noise_summary's columns, one row per (group,
+    deviator), plus n_switch_max and unresolved_mean (the sampling of the networks' strategies on the price cells), T and
+    n_cells.  The expected response curves of a run that also has training.group_stats are the per-group statistics of
+    prefix "gdevn<d>": group_quantiles(exp_path, group, "total", prefix="gdevn0"), one row per period after the shock."""
+    if not os.path.isfile(os.path.join(exp_path, "greedy_deviation_noise.json")):
+        raise KeyError("no deviation test under noise in tuple form (greedy_deviation_noise.json) under %s "
+                       "(training.greedy_deviation.noise)" % exp_path)
+    desc = _load_json(exp_path, "greedy_deviation_noise.json")
+    df = pandas.DataFrame(desc["summary"])
+    df["T"], df["n_cells"] = int(desc["T"]), int(desc["n_cells"])
+    return df
+
+
+def greedy_deviation_noise_games(exp_path, deviator=0):
+    """Per-game results of the deviation test under demand noise in tuple form for `deviator`, one row per game indexed
+    by its GLOBAL id: noise_prob, stat_iters, n_switch, unresolved, dev_share, gain, gain_dev, low, dist, mass, low_step,
+    ret_step, base_reward_<i> / base_action_<i> and solved."""
+    from th_rl_amd import deviation as dv, tuple_analysis as ta
+    _run_dirs(exp_path, "gdevn_prob.npy", "deviation test under noise in tuple form", "greedy_deviation.noise", shards=False)
+    desc = _load_json(exp_path, "greedy_deviation_noise.json")
+    if int(deviator) not in desc["options"]["agents"]:
+        raise KeyError("deviator %d was not analysed (agents %s)" % (int(deviator), desc["options"]["agents"]))
+    off = _game_offset(exp_path, exp_path)
+    g = ta.load_deviation_noise_games(exp_path, int(deviator))
+    cols = {f: g[f] for f in ("noise_prob", "stat_iters", "n_switch", "unresolved")}
+    cols.update({f: g[f] for f in dv.NOISE_FLOAT + dv.NOISE_INT})
+    for i in range(g["base_reward"].shape[0]):
+        cols["base_reward_%d" % i] = g["base_reward"][i]
+        cols["base_action_%d" % i] = g["base_action"][i]
+    cols["solved"] = dv.solved_noise(g)
+    n = g["noise_prob"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
 def greedy_equilibrium_summary(exp_path):
     """A run's equilibrium check in tuple form (training.greedy_equilibrium): greedy_equilibrium.json's summary as a
     DataFrame with equilibrium_summary's columns (n_states = T, the game's action tuples) plus no_start."""
