@@ -579,6 +579,22 @@ class AnalysisMethods:
                       tuple_policy=tuple_policy, probs=probs, dpolicy=dpolicy, tabs=tabs, noise_prob=noise_prob,
                       resolution=resolution, nprobs=nprobs, npolicy=npolicy)
 
+    def sampled_response(self, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_sweeps=8192, policies=False,
+                         pi=None, n_games=None, probs=None, dpolicy=None, tabs=None):
+        """Exact best responses to the rivals' STOCHASTIC policies (sampled_response.run, thrl_sampled_response;
+        definitions in include/thrl_response.h): for each agent in `agents` (default all) the value V_pi of its own
+        mixed policy against rivals that sample -- a network its softmax, a QTable agent epsilon-greedily -- and its best
+        deterministic reply V*, sigma*, on the D distinct prices (Jacobi sweeps to eval_tol, at most max_sweeps per
+        evaluation; policy iteration from the modal action).  Returns a dict of numpy arrays: iters (-1: not solved or
+        capped), sweeps, n_diff, loss_all, loss_mean [N, G]; weighted by pi (None = the long-run distribution of
+        sampled_play(pi=True), an array [G, T], or False = none) loss_w, gain_w, v_w, br_prob_w [N, G]; gamma, epsilon
+        [N, G]; policies=True adds br_policy (uint16), v_opt, v_pi [N, G, D].  gamma: None = each agent's own (the
+        per-game sweep where there is one), a number, N numbers or [N, G].  Noise-free play only."""
+        from . import sampled_response as sr
+        self._ready()
+        return sr.run(self, agents=agents, epsilon=epsilon, gamma=gamma, eval_tol=eval_tol, max_sweeps=max_sweeps,
+                      policies=policies, pi=pi, n_games=n_games, probs=probs, dpolicy=dpolicy, tabs=tabs)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
         its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.

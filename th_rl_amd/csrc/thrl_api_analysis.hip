@@ -25,7 +25,10 @@
 #include "thrl_tuple_play.h"
 #include "thrl_sampled.h"
 #include "thrl_sampled_noise.h"
+#include "thrl_sampled_response.h"
 #include "thrl_tuple_stationary.h"
+
+#include "../../include/thrl_response.h"
 
 using namespace thrl;
 using namespace thrl::host;
@@ -897,6 +900,54 @@ int thrl_sampled_noise_chain(const thrl_cfg* c, const thrl_sampled_noise_chain_a
     const int grid = grid_for(cus, lds_cu, sa.lds_bytes, kSpMaxBlocksPerCu, sa.G);
     const int e = thrl::launch_sampled_noise_chain(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_spn_jump / k_spn_chain launch") : THRL_OK;
+}
+
+int thrl_sampled_response(const thrl_cfg* c, const thrl_sampled_response_args* x, void* stream) {
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_sampled_chain's checks in its order, with the agents and their gammas as thrl_tuple_equilibrium_noise checks
+    // them; every host-visible argument is checked, and the working set planned, before any pointer is looked at
+    if ((rc = check_games(x->n_games)) != THRL_OK) return rc;
+    if (x->flags != 0) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    for (int k = 0; k < 2; k++)
+        if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
+    if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if (x->n_prices < 1 || x->n_prices > x->n_tuples)
+        return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", x->n_prices, x->n_tuples);
+    if (!x->sweep_gamma && (rc = check_gamma(x->gamma, N, x->agents)) != THRL_OK) return rc;
+    if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
+    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    thrl::SrArgs a;
+    memset(&a, 0, sizeof(a));
+    SpArgs& sa = a.sp;
+    sa.G = x->n_games; sa.N = N; sa.T = x->n_tuples; sa.D = x->n_prices;
+    tuple_strides(c, sa.n_actions, sa.tstride);
+    for (int i = 0; i < N; i++) { sa.kind[i] = x->kind[i]; sa.eps[i] = x->eps[i]; sa.prob[i] = x->prob[i]; a.gamma[i] = x->gamma[i]; }
+    const int64_t lds = thrl::sr_layout(a);          // the working set of include/thrl_response.h
+    // (the cells of this analysis are the distinct prices)
+    if (lds > THRL_SR_MAX_LDS) return lds_refusal("thrl_sampled_response", lds, N, x->n_prices);
+    for (int i = 0; i < N; i++)
+        if (x->kind[i] != 0 && !x->prob[i]) return fail(THRL_ERR_NULL, "prob[%d] is NULL", i);
+    if (!x->dpolicy || !x->grp_first || !x->grp_perm || !x->reward) return missing("dpolicy / grp_first / grp_perm / reward");
+    if (!x->iters || !x->sweeps || !x->n_diff || !x->loss_all || !x->loss_mean)
+        return missing("iters / sweeps / n_diff / loss_all / loss_mean");
+    if (x->pi && (!x->loss_w || !x->gain_w || !x->v_w || !x->br_prob_w)) return missing("with pi, loss_w / gain_w / v_w / br_prob_w");
+    a.agents = x->agents; a.max_sweeps = x->max_sweeps; a.eval_tol = x->eval_tol;
+    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm; sa.reward = x->reward;
+    a.sweep_gamma = x->sweep_gamma; a.pi = x->pi;
+    a.iters = x->iters; a.sweeps = x->sweeps; a.n_diff = x->n_diff; a.loss_all = x->loss_all; a.loss_mean = x->loss_mean;
+    a.loss_w = x->loss_w; a.gain_w = x->gain_w; a.v_w = x->v_w; a.br_prob_w = x->br_prob_w;
+    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+    int cus = 0, lds_cu = 0;
+    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
+    if (lds_cu > 0 && sa.lds_bytes > lds_cu) return lds_refusal("thrl_sampled_response", lds, N, x->n_prices);
+    const int grid = grid_for(cus, lds_cu, sa.lds_bytes, kSrMaxBlocksPerCu, sa.G);
+    const int e = thrl::launch_sampled_response(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_sr_response launch") : THRL_OK;
 }
 
 }  // extern "C"

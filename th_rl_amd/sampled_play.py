@@ -58,14 +58,21 @@ def _check_eps(e, what):
 def parse_options(opt, config):
     """training.sampled_play (true or a dict) -> the dict with every key filled in: epsilon ("current": the QTable
     agents' epsilon where training stopped; a number, or one per agent), start ("uniform" or "state"), tol, max_iters,
-    pi (store the distributions).  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
+    pi (store the distributions).  The optional key "response" (true or a dict, sampled_response.parse_options) asks for
+    the best responses to the stochastic policies; it stays in the result, filled in, only when given, and is refused
+    together with "noise".  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
     run's own noise, refused for a noise-free run as training.greedy_stationary does; "resolution": the uniform cuts of
     the price axis behind the nodes}) asks for play under demand noise; it stays in the result, filled in, only when
     given, and with it start may be "reset".  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples, more than
     MAX_CELLS - 1 cells and a working set above a CU's LDS."""
     name = "training.sampled_play"
     tp.check_config(config)
-    noise = None
+    noise = response = None
+    if isinstance(opt, dict) and "response" in opt:
+        opt = dict(opt)
+        response = opt.pop("response")
+        if response is None or response is False:
+            response = None
     if isinstance(opt, dict) and "noise" in opt:
         opt = dict(opt)
         noise = opt.pop("noise")
@@ -101,6 +108,11 @@ def parse_options(opt, config):
             raise ValueError("%s.noise: under noise a game's working set is %d bytes (T=%d, D=%d, Jn=%d), a CU's LDS holds %d"
                              % (name, ws["bytes"], ws["T"], ws["D"], ws["Jn"], MAX_LDS))
         out["noise"] = noise
+    if response is not None:
+        from . import sampled_response as sr
+        if noise is not None:
+            raise ValueError("%s: \"response\" with \"noise\": %s" % (name, sr.NOISE_FOLLOW_UP))
+        out["response"] = sr.parse_options(response, config)
     return out
 
 
@@ -536,6 +548,12 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=No
     cyc = greedy_cycles_of(exp_path, np.asarray(r["iters"]).size) if with_cycles else None
     gn = greedy_noise_of(exp_path, r["noise_prob"]) if noise else None
     summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"], cycle_reward=cyc, greedy_noise=gn)
+    shown = {k: v for k, v in opt.items() if k != "response"}        # sampled_response.json holds its own options
     an.save_json(os.path.join(exp_path, "sampled_play.json"),
-                 describe(opt, r["T"], r["n_prices"], nash, cartel, summary, n_nodes=r.get("n_nodes")))
+                 describe(shown, r["T"], r["n_prices"], nash, cartel, summary, n_nodes=r.get("n_nodes")))
+    if opt.get("response"):
+        from . import sampled_response as sr
+        same = opt["pi"] and opt["start"] == "uniform"               # the stored distributions are the ones it would compute
+        sr.write_artefacts(exp_path, batch, config, opt["response"], ids, n_groups, epsilon=opt["epsilon"], tabs=tabs,
+                           pi=r["pi"] if same else None)
     return r

@@ -1,0 +1,306 @@
+"""Sampled play: exact best responses to the rivals' STOCHASTIC policies (thrl_sampled_response,
+include/thrl_response.h) -- the exploitability of the policies the agents were trained with.
+
+sampled_play says what the stochastic policies earn in the long run; this module says whether each of them is a good
+reply to the others.  An agent conditions on the price alone, so agent i's problem against a sampling softmax and an
+epsilon-greedy table lives on the D distinct prices of the config: V_pi, the value of its own mixed policy, and V*,
+sigma*, its best deterministic reply, by Jacobi sweeps and policy iteration (definitions in the header).  run() returns
+per selected agent and game iters (-1: not solved or capped), sweeps, n_diff, loss_all, loss_mean and, weighted by the
+long-run distribution pi of sampled play, loss_w, gain_w (what the best reply adds to the discounted value), v_w and
+br_prob_w (the long-run share of steps on which the agent already plays its best response).  (1 - gamma_i) gain_w is the
+agent's exploitability in reward units per period; its sum over the agents is the profile's NashConv.  It separates
+"prices above Nash because the profile is an epsilon-equilibrium" from "prices above Nash because nobody has learned to
+undercut a randomising rival".  Noise-free play only; the mode under demand noise is the follow-up.
+
+In train_one the analysis is the sub-key "response" of training.sampled_play, as "noise" is: true, or {"agents",
+"eval_tol", "max_sweeps", "policies"}.  It writes sampled_response.json and sresp_*.npy; utils.sampled_response_summary
+and utils.sampled_response_games read them.  Sharded runs (th_rl_amd.launch) are out of scope, as sampled_play is.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from . import _lib
+from . import analysis as an
+from . import equilibrium as eq
+from . import sampled_play as sp
+from . import tuple_play as tp
+from ._lib import ThrlError
+from .deviation import optimal
+
+DEFAULTS = dict(agents=None, eval_tol=1e-12, max_sweeps=8192, policies=False)
+NOISE_FOLLOW_UP = "best responses to sampled play under demand noise are the follow-up: drop \"noise\" or \"response\""
+MAX_LDS = _lib.SR_MAX_LDS
+MAX_TEAM_BYTES = 32 * 1024
+INT = ("iters", "sweeps", "n_diff")
+FLOAT = ("loss_all", "loss_mean")
+WEIGHTED = ("loss_w", "gain_w", "v_w", "br_prob_w")
+PER_GAME = INT + FLOAT + WEIGHTED + ("gamma", "epsilon", "br_policy", "v_opt", "v_pi")
+
+
+def parse_options(opt, config):
+    """training.sampled_play.response (true or a dict) -> the dict with every key filled in: agents (None = all, or a
+    list), eval_tol (>= 0), max_sweeps (an integer in [1, STAT_MAX_ITERS]), policies (store sigma*, V* and V_pi).  Refuses
+    a working set above a CU's LDS."""
+    name = "training.sampled_play.response"
+    out = an.options("sampled_play.response", opt, DEFAULTS)
+    n = len(config["agents"])
+    if out["agents"] is not None:
+        ag = out["agents"]
+        if not isinstance(ag, (list, tuple)) or not ag or any(isinstance(d, bool) or not isinstance(d, int) or not 0 <= d < n
+                                                              for d in ag):
+            raise ValueError("%s.agents must be a non-empty list of agents in [0, %d), got %r" % (name, n, ag))
+        out["agents"] = sorted(set(ag))
+    if isinstance(out["eval_tol"], bool) or not isinstance(out["eval_tol"], (int, float)) or not out["eval_tol"] >= 0.0:
+        raise ValueError("%s.eval_tol must be a number >= 0, got %r" % (name, out["eval_tol"]))
+    out["eval_tol"] = float(out["eval_tol"])
+    if isinstance(out["max_sweeps"], bool) or not isinstance(out["max_sweeps"], int) \
+            or not 1 <= out["max_sweeps"] <= _lib.STAT_MAX_ITERS:
+        raise ValueError("%s.max_sweeps must be an integer in [1, %d], got %r" % (name, _lib.STAT_MAX_ITERS, out["max_sweeps"]))
+    if not isinstance(out["policies"], bool):
+        raise ValueError("%s.policies must be true or false, got %r" % (name, out["policies"]))
+    ws = working_set(config)
+    if not ws["fits"]:
+        raise ValueError("%s: a game's working set is %d bytes (T=%d, D=%d), a CU's LDS holds %d"
+                         % (name, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
+    return out
+
+
+def team_of(D, max_actions):
+    """The threads that share one price's actions (sr_layout): the largest power of two with team * D <= 256 and team <=
+    the largest action count, 1 where the staging of 8 D max_i A_i bytes would pass 32 KB."""
+    team = 1
+    while team * 2 * D <= 256 and team * 2 <= max_actions:
+        team *= 2
+    return 1 if 8 * D * max_actions > MAX_TEAM_BYTES else team
+
+
+def working_set(config, tabs=None):
+    """The LDS bytes one game takes in thrl_sampled_response, by include/thrl_response.h's formula (sr_layout): the sum of
+    r16(x) over five arrays of 8 D, two of 8 T, 4 D A_i per network, 2 D per QTable agent, 2 (D + 1), 2 T, 2 T, 2 D, 2 D,
+    2,048, the team's staging 8 D max_i A_i (where a team shares a price) and 256.  Returns dict(bytes, T, D, team, fits)."""
+    tabs = sp.tables(config) if tabs is None else tabs
+    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
+    r16 = sp._r16
+    acts = [int(a) for a in tabs["n_actions"]]
+    team = team_of(D, max(acts))
+    b = 5 * r16(8 * D) + 2 * r16(8 * T)
+    for kind, A in zip(tabs["kinds"], acts):
+        b += r16(2 * D) if kind == "QTable" else r16(4 * D * A)
+    b += r16(2 * (D + 1)) + 2 * r16(2 * T) + 2 * r16(2 * D) + 2048 + (r16(8 * D * max(acts)) if team > 1 else 0) + 256
+    return dict(bytes=int(b), T=T, D=D, team=team, fits=b <= MAX_LDS)
+
+
+def resolve_gamma(batch, gamma, G):
+    """(gamma [N] floats, device float64 [N, G] or None) for `gamma`: None = each agent's own (a network's, else the
+    config's) and the per-game sweep array where a sweep has one; a number = every agent's; N numbers; or an array [N, G]
+    (device data: an entry outside [0, 1) leaves that (agent, game) unsolved)."""
+    import torch
+    N = batch.N
+    if gamma is None:
+        nn = getattr(batch, "nn", None) or {}
+        own = [float(nn[i].gamma) if i in nn else float(batch.cfg.gamma[i]) for i in range(N)]
+        sw = getattr(batch, "sweep", None) or {}
+        if "gamma" in sw:
+            return own, sw["gamma"][:, :G].to(torch.float64).contiguous()
+        return own, None
+    if isinstance(gamma, torch.Tensor) or np.ndim(gamma) == 2:
+        x = gamma if isinstance(gamma, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gamma, np.float64))
+        x = x.to(device=batch.device, dtype=torch.float64)
+        if x.dim() != 2 or x.shape[0] != N or x.shape[1] < G:
+            raise ThrlError("sampled_response: a per-game gamma must be [N=%d, G>=%d], got %s" % (N, G, tuple(x.shape)))
+        return [0.0] * N, x[:, :G].contiguous()
+    x = [float(gamma)] * N if np.ndim(gamma) == 0 else [float(v) for v in gamma]
+    if len(x) != N:
+        raise ThrlError("sampled_response: gamma holds %d numbers, the game has %d agents" % (len(x), N))
+    return x, None
+
+
+def run(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_sweeps=8192, policies=False, pi=None,
+        n_games=None, probs=None, dpolicy=None, tabs=None):
+    """thrl_sampled_response for the first n_games (default all) games of `batch` (a MixedGameBatch of QTable / Reinforce
+    / ActorCritic agents, or a GameBatch).  agents: the agents solved (default all).  epsilon: sampled_play's rules.
+    gamma: resolve_gamma's.  pi: the long-run distribution that weights loss_w, gain_w, v_w and br_prob_w: None = computed
+    here with sampled_play.run(pi=True) on the same strategies, an array [G, T], or False = no weighted outputs.  probs,
+    dpolicy, tabs as in sampled_play.run.  policies=True adds br_policy (uint16), v_opt, v_pi [N, G, D].  Returns a dict
+    of numpy arrays, [N, G] with zeros for the agents that are not selected."""
+    import torch
+    from . import tuple_stationary as ts
+    N = batch.N
+    G = sp._games(batch, n_games)
+    ag, mask = eq.agents_mask(agents, N)
+    if isinstance(max_sweeps, bool) or not 1 <= int(max_sweeps) <= _lib.STAT_MAX_ITERS:
+        raise ThrlError("sampled_response: max_sweeps=%r out of [1, %d]" % (max_sweeps, _lib.STAT_MAX_ITERS))
+    if tabs is None:
+        tabs = sp.tables(batch.config)
+    tp._batch_tables(batch, tabs)
+    ws = working_set(batch.config, tabs)
+    if not ws["fits"]:                                   # what the call answers from the shape alone
+        err = ThrlError("thrl_sampled_response refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d), at most %d"
+                        % (_lib.ERR_UNSUPPORTED, ws["bytes"], ws["T"], ws["D"], MAX_LDS))   # (the library: lds_refusal's words)
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    kinds = tp._kinds(batch)
+    dev = batch.device
+    sdev = batch.state.device
+    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
+    a = _lib.SampledResponseArgs()
+    a.n_games, a.n_tuples, a.n_prices, a.agents = G, T, D, mask
+    a.max_sweeps, a.eval_tol = int(max_sweeps), float(eval_tol)
+    for i, k in enumerate(kinds):
+        a.kind[i] = tp.KINDS[k]
+    with torch.cuda.device(dev):
+        eps, eps_g = sp.resolve_epsilon(batch, epsilon, G)
+        gam, gam_g = resolve_gamma(batch, gamma, G)
+        for i in range(N):
+            a.eps[i], a.gamma[i] = eps[i], gam[i]
+        if eps_g is not None:
+            a.eps_g = eps_g.data_ptr()
+        if gam_g is not None:
+            a.sweep_gamma = gam_g.data_ptr()
+        if probs is None:
+            probs = sp.price_probs(batch, tabs["dprice"], n_games=G)
+        if dpolicy is None:
+            dpolicy = ts.price_policy(batch, tabs["dprice"], n_games=G)
+        an.check_policy(batch, dpolicy, (G, N, D), "sampled_response", "dpolicy")
+        for i, k in enumerate(kinds):
+            if k == "QTable":
+                continue
+            p = probs.get(i)
+            shape = (G, D, int(batch.cfg.n_actions[i]))
+            if p is None or tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != sdev or not p.is_contiguous():
+                raise ThrlError("sampled_response: probs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
+            a.prob[i] = p.data_ptr()
+        a.dpolicy = dpolicy.data_ptr()
+        pi_t = None
+        if pi is None:
+            e = epsilon if eps_g is None else eps_g
+            st = sp.run(batch, epsilon=e, pi=True, n_games=G, probs=probs, dpolicy=dpolicy, tabs=tabs)
+            pi_t = torch.from_numpy(np.ascontiguousarray(st["pi"])).to(dev)
+        elif pi is not False:
+            if isinstance(pi, torch.Tensor):
+                pi_t = pi.to(device=dev, dtype=torch.float64).contiguous()
+            else:
+                pi_t = torch.from_numpy(np.ascontiguousarray(np.asarray(pi, np.float64))).to(dev)
+            if tuple(pi_t.shape) != (G, T):
+                raise ThrlError("sampled_response: pi must be shaped %s, got %s" % ((G, T), tuple(pi_t.shape)))
+        if pi_t is not None:
+            a.pi = pi_t.data_ptr()
+        keep = an.bind_tables(a, tabs, [("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32),
+                                        ("reward", (N, T), np.float64)], dev, "sampled_response")
+        out = an.outputs(dev, (INT, (N, G), "int32"), (FLOAT, (N, G), "float64"),
+                         (WEIGHTED if pi_t is not None else (), (N, G), "float64"),
+                         (("br_policy",) if policies else (), (N, G, D), "int16"),
+                         (("v_opt", "v_pi") if policies else (), (N, G, D), "float64"))
+        an.bind(a, out)
+        _lib.check(batch.L.thrl_sampled_response(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                   "thrl_sampled_response")
+        torch.cuda.synchronize(dev)
+        res = an.fetch(out)
+        del keep
+        res["epsilon"] = np.repeat(np.asarray(eps, np.float64)[:, None], G, axis=1) if eps_g is None else eps_g.cpu().numpy()
+        res["gamma"] = np.repeat(np.asarray(gam, np.float64)[:, None], G, axis=1) if gam_g is None else gam_g.cpu().numpy()
+        if pi_t is not None:
+            res["pi"] = pi_t.cpu().numpy()
+    if policies:
+        res["br_policy"] = res["br_policy"].view(np.uint16)
+    res["agents"], res["T"], res["n_prices"], res["lds_bytes"] = ag, T, D, ws["bytes"]
+    res["eval_tol"], res["max_sweeps"] = float(eval_tol), int(max_sweeps)
+    return res
+
+
+# ---------------------------------------------------------------------------------------------- host side
+def exploitability(games):
+    """(1 - gamma_i) * gain_w [N, G]: what agent i's best reply adds, in reward units per period."""
+    return (1.0 - np.asarray(games["gamma"], np.float64)) * np.asarray(games["gain_w"], np.float64)
+
+
+def summarize(games, agents, ids, n_groups, nash, cartel):
+    """The summary rows.  One per (group, agent) with "agent": games, capped (the share of games not solved), br_all (the
+    share of the solved games whose own policy loses nothing anywhere: loss_all <= 0), loss_all_q25 / q50 / q75,
+    loss_w_mean, br_prob_w_mean and exploit_mean, the mean of (1 - gamma_i) * gain_w, over the solved games.  One per
+    group with "agent": None: games, solved (the games solved for every selected agent), nashconv_mean (nashconv = the sum
+    of the agents' exploitabilities) and nashconv_small, the share of those games with nashconv < 1 % of Cartel - Nash."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    iters = np.asarray(games["iters"], np.int64)
+    loss_all = np.asarray(games["loss_all"], np.float64)
+    has_w = "gain_w" in games
+    ex = exploitability(games) if has_w else None
+    out = []
+    for k in range(int(n_groups)):
+        m = ids == k
+        every = m.copy()
+        for i in agents:
+            ms = m & (iters[i] >= 0)
+            every &= iters[i] >= 0
+            row = {"group": k, "agent": int(i), "games": int(m.sum()), "capped": an.frac(iters[i][m] < 0) if m.any() else None,
+                   "br_all": an.frac(loss_all[i][ms] <= 0.0) if ms.any() else None}
+            an.quantiles(row, "loss_all", loss_all[i][ms])
+            if has_w:
+                row["loss_w_mean"] = an.mean(np.asarray(games["loss_w"], np.float64)[i][ms])
+                row["br_prob_w_mean"] = an.mean(np.asarray(games["br_prob_w"], np.float64)[i][ms])
+                row["exploit_mean"] = an.mean(ex[i][ms])
+            out.append(row)
+        row = {"group": k, "agent": None, "games": int(m.sum()), "solved": int(every.sum())}
+        if has_w:
+            nc = np.zeros(ids.size)
+            for i in agents:
+                nc = nc + np.where(every, ex[i], 0.0)
+            row["nashconv_mean"] = an.mean(nc[every])
+            row["nashconv_small"] = an.frac(nc[every] < 0.01 * (float(cartel) - float(nash))) if every.any() else None
+        out.append(row)
+    return out
+
+
+def describe(options, r, nash, cartel, summary):
+    """sampled_response.json's content."""
+    return {"options": options, "agents": [int(i) for i in r["agents"]], "T": int(r["T"]), "n_prices": int(r["n_prices"]),
+            "nash": nash, "cartel": cartel, "quantiles": list(an.QUANTILES),
+            "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)", "summary": summary}
+
+
+FILES = (("sresp_counts.npy", INT, np.int32), ("sresp_loss.npy", FLOAT, np.float64), ("sresp_weighted.npy", WEIGHTED, np.float64))
+OPTIONAL = (("br_policy", "sresp_br_policy.npy", np.uint16), ("v_opt", "sresp_v_opt.npy", np.float64),
+            ("v_pi", "sresp_v_pi.npy", np.float64))
+
+
+def save_games(d, r):
+    """sresp_counts int32 [3, N, G] (iters, sweeps, n_diff), sresp_loss float64 [2, N, G] (loss_all, loss_mean),
+    sresp_weighted float64 [4, N, G] (loss_w, gain_w, v_w, br_prob_w), sresp_gamma and sresp_epsilon float64 [N, G]; with
+    the policies sresp_br_policy uint16, sresp_v_opt and sresp_v_pi float64 [N, G, D]."""
+    for name, fields, dt in FILES:
+        np.save(os.path.join(d, name), np.stack([np.asarray(r[f], dt) for f in fields]))
+    np.save(os.path.join(d, "sresp_gamma.npy"), np.asarray(r["gamma"], np.float64))
+    np.save(os.path.join(d, "sresp_epsilon.npy"), np.asarray(r["epsilon"], np.float64))
+    for f, name, dt in OPTIONAL:
+        path = os.path.join(d, name)
+        if f in r:
+            np.save(path, np.asarray(r[f], dt))
+        elif os.path.isfile(path):               # a file left by an earlier run with other options
+            os.remove(path)
+
+
+def load_games(d):
+    """The per-game arrays one run directory holds (training.sampled_play.response)."""
+    g = {}
+    for name, fields, _ in FILES:
+        x = np.load(os.path.join(d, name))
+        g.update({f: x[k] for k, f in enumerate(fields)})
+    g["gamma"], g["epsilon"] = np.load(os.path.join(d, "sresp_gamma.npy")), np.load(os.path.join(d, "sresp_epsilon.npy"))
+    for f, name, _ in OPTIONAL:
+        if os.path.isfile(os.path.join(d, name)):
+            g[f] = np.load(os.path.join(d, name))
+    return g
+
+
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, epsilon="current", tabs=None, pi=None):
+    """train_one's training.sampled_play.response outputs: the per-game sresp_*.npy files and sampled_response.json.
+    epsilon: sampled_play's option; pi: its distributions where it stored them (else computed here)."""
+    r = run(batch, agents=opt["agents"], epsilon=epsilon, eval_tol=opt["eval_tol"], max_sweeps=opt["max_sweeps"],
+            policies=opt["policies"], pi=pi, tabs=tabs)
+    save_games(exp_path, r)
+    nash, cartel = optimal(config)
+    summary = summarize(r, r["agents"], ids, n_groups, nash, cartel)
+    an.save_json(os.path.join(exp_path, "sampled_response.json"), describe(opt, r, nash, cartel, summary))
+    return r

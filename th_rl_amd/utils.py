@@ -783,3 +783,41 @@ def sampled_play_games(exp_path):
             cols[f] = g[f]
     n = g["iters"].shape[0]
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
+def sampled_response_summary(exp_path):
+    """A run's best responses to sampled play (training.sampled_play.response: how good a reply each agent's stochastic
+    policy is to the others'): sampled_response.json's summary as a DataFrame.  One row per (group, agent): games, capped,
+    br_all (the share of solved games whose policy loses nothing at any price), loss_all_q25 / q50 / q75, loss_w_mean,
+    br_prob_w_mean (the long-run share of steps on which the agent already plays its best response) and exploit_mean, the
+    mean of (1 - gamma_i) * gain_w in reward units per period; and one row per group with agent = NaN: solved,
+    nashconv_mean (the sum of the agents' exploitabilities) and nashconv_small, the share of games whose NashConv is
+    below 1 % of Cartel - Nash; plus T, n_prices, Nash and Cartel."""
+    desc = _load_json(exp_path, "sampled_response.json")
+    df = pandas.DataFrame(desc["summary"])
+    df["T"], df["n_prices"] = int(desc["T"]), int(desc["n_prices"])
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def sampled_response_games(exp_path):
+    """Per-game results of training.sampled_play.response, one row per game indexed by its GLOBAL id, per solved agent i:
+    iters_<i>, sweeps_<i>, n_diff_<i>, loss_all_<i>, loss_mean_<i>, loss_w_<i>, gain_w_<i>, v_w_<i>, br_prob_w_<i>,
+    gamma_<i>, epsilon_<i>, exploit_<i> = (1 - gamma_i) * gain_w; and nashconv, their sum over the solved agents (NaN
+    where one of them is not solved)."""
+    from th_rl_amd import sampled_response as sr
+    _run_dirs(exp_path, "sresp_counts.npy", "sampled-response analysis", "sampled_play", shards=False)
+    desc = _load_json(exp_path, "sampled_response.json")
+    off = _game_offset(exp_path, exp_path)
+    g = sr.load_games(exp_path)
+    ex = sr.exploitability(g)
+    cols = {}
+    n = g["iters"].shape[1]
+    nc = numpy.zeros(n)
+    for i in desc["agents"]:
+        for f in sr.INT + sr.FLOAT + sr.WEIGHTED + ("gamma", "epsilon"):
+            cols["%s_%d" % (f, i)] = g[f][i]
+        cols["exploit_%d" % i] = ex[i]
+        nc = nc + ex[i]
+    cols["nashconv"] = nc
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
