@@ -1,0 +1,129 @@
+// sampled_response_noise_check.cpp -- k_srn_response's source (th_rl_amd/csrc/thrl_sampled_response_noise.hip) compiled for
+// the host and run as 256 threads with barriers, for address / undefined-behaviour (or thread) sanitizers.  Reads the
+// inputs and the mirror's outputs that tests/sampled_response_noise_mirror.write_case writes, runs every game through
+// srn_block and compares every output bit for bit.  Built as host code (hipcc -x hip --cuda-host-only
+// -DTHRL_SP_HOST_BUILD), so that thrl_solve_dev.h's __host__ __device__ pieces are the ones the device build uses; it makes
+// no HIP call and needs no GPU.
+#include <algorithm>
+#include <barrier>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+// the shared solver pieces first, as HIP declares them: improve_margin, rel_loss and the band's limits are __host__ __device__
+#include "../th_rl_amd/csrc/thrl_solve_dev.h"
+
+// from here on a __device__ function is a host function, a barrier is the host threads', an _rn operation a plain one
+// (the build's -ffp-contract=off rounds each separately)
+static std::barrier<>* g_bar;
+#undef __device__
+#define __device__
+#define __syncthreads() g_bar->arrive_and_wait()
+#define __dadd_rn(a, b) ((a) + (b))
+#define __dsub_rn(a, b) ((a) - (b))
+#define __dmul_rn(a, b) ((a) * (b))
+#define __ddiv_rn(a, b) ((a) / (b))
+
+#include "../th_rl_amd/csrc/thrl_sampled_response_noise.hip"
+
+template <typename T>
+static std::vector<T> rd(FILE* f, size_t n) {
+    std::vector<T> v(n);
+    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "short read\n"); exit(2); }
+    return v;
+}
+
+template <typename T>
+static int cmp(const char* what, const std::vector<T>& a, const std::vector<T>& b) {
+    int bad = 0;
+    for (size_t i = 0; i < a.size(); i++) bad += memcmp(&a[i], &b[i], sizeof(T)) != 0;
+    if (bad) printf("  %s: %d of %zu differ\n", what, bad, a.size());
+    return bad;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    // G N T D Jn W agents max_sweeps has_eps_g has_gamma_g has_noise_g has_pi n_blocks
+    auto h = rd<int32_t>(f, 13);
+    thrl::SrnArgs a;
+    memset(&a, 0, sizeof(a));
+    thrl::SpArgs& sp = a.sp;
+    sp.G = h[0]; sp.N = h[1]; sp.T = h[2]; sp.D = h[3]; a.Jn = h[4]; a.W = h[5]; a.agents = h[6]; a.max_sweeps = h[7];
+    const int nblk = h[12];
+    auto kind = rd<int32_t>(f, 8), nact = rd<int32_t>(f, 8);
+    auto eps = rd<double>(f, 8), gam = rd<double>(f, 8), two = rd<double>(f, 2);
+    int ts = 1;
+    for (int i = sp.N - 1; i >= 0; i--) {
+        sp.kind[i] = kind[i]; sp.n_actions[i] = nact[i]; sp.tstride[i] = ts; ts *= nact[i]; sp.eps[i] = eps[i]; a.gamma[i] = gam[i];
+    }
+    a.eval_tol = two[0]; a.noise_prob = two[1];
+    const size_t G = sp.G, N = sp.N, T = sp.T, D = sp.D, Jn = a.Jn, W = a.W, S = D + Jn;
+    auto eps_g = rd<double>(f, h[8] ? N * G : 0);
+    auto gam_g = rd<double>(f, h[9] ? N * G : 0);
+    auto noise_g = rd<double>(f, h[10] ? G : 0);
+    std::vector<std::vector<float>> prob(N), nprob(N);
+    for (size_t i = 0; i < N; i++) {
+        prob[i] = rd<float>(f, kind[i] ? G * D * nact[i] : 0);
+        nprob[i] = rd<float>(f, kind[i] ? G * Jn * nact[i] : 0);
+    }
+    auto dpol = rd<uint16_t>(f, G * N * D), npol = rd<uint16_t>(f, G * N * Jn);
+    auto first = rd<int32_t>(f, D + 1), perm = rd<int32_t>(f, T);
+    auto reward = rd<double>(f, N * T);
+    auto band_lo = rd<int32_t>(f, T);
+    auto band = rd<double>(f, T * W), nreward = rd<double>(f, N * T);
+    auto pi = rd<double>(f, h[11] ? G * T : 0);
+    auto w_iters = rd<int32_t>(f, N * G), w_sweeps = rd<int32_t>(f, N * G), w_ndp = rd<int32_t>(f, N * G), w_ndn = rd<int32_t>(f, N * G);
+    auto w_lall = rd<double>(f, N * G), w_lp = rd<double>(f, N * G), w_ln = rd<double>(f, N * G), w_lw = rd<double>(f, N * G),
+         w_gw = rd<double>(f, N * G), w_vw = rd<double>(f, N * G), w_bw = rd<double>(f, N * G);
+    auto w_br = rd<uint16_t>(f, N * G * S);
+    auto w_vopt = rd<double>(f, N * G * S), w_vpi = rd<double>(f, N * G * S);
+    fclose(f);
+    // zeroed as the caller's are: the entries of agents that are not selected are not written
+    std::vector<int32_t> iters(N * G, 0), sweeps(N * G, 0), ndp(N * G, 0), ndn(N * G, 0);
+    std::vector<double> lall(N * G, 0.0), lp(N * G, 0.0), ln(N * G, 0.0), lw(N * G, 0.0), gw(N * G, 0.0), vw(N * G, 0.0), bw(N * G, 0.0);
+    std::vector<uint16_t> br(N * G * S, 0);
+    std::vector<double> vopt(N * G * S, 0.0), vpi(N * G * S, 0.0);
+    sp.eps_g = h[8] ? eps_g.data() : nullptr; a.sweep_gamma = h[9] ? gam_g.data() : nullptr;
+    a.noise_prob_g = h[10] ? noise_g.data() : nullptr;
+    sp.dpolicy = dpol.data(); a.npolicy = npol.data();
+    for (size_t i = 0; i < N; i++) {
+        sp.prob[i] = kind[i] ? prob[i].data() : nullptr;
+        a.nprob[i] = kind[i] ? nprob[i].data() : nullptr;
+    }
+    sp.grp_first = first.data(); sp.grp_perm = perm.data(); sp.reward = reward.data();
+    a.band_lo = band_lo.data(); a.band = band.data(); a.noise_reward = nreward.data();
+    a.pi = h[11] ? pi.data() : nullptr;
+    a.iters = iters.data(); a.sweeps = sweeps.data(); a.n_diff_prices = ndp.data(); a.n_diff_nodes = ndn.data();
+    a.loss_all = lall.data(); a.loss_prices_mean = lp.data(); a.loss_nodes_mean = ln.data();
+    a.loss_w = lw.data(); a.gain_w = gw.data(); a.v_w = vw.data(); a.br_prob_w = bw.data();
+    a.br_policy = br.data(); a.v_opt = vopt.data(); a.v_pi = vpi.data();
+    const long long lds = thrl::srn_layout(a);
+    printf("G=%d N=%d T=%d D=%d Jn=%d W=%d S=%zu agents=0x%x max_sweeps=%d blocks=%d: %lld bytes of LDS\n", sp.G, sp.N, sp.T, sp.D,
+           a.Jn, a.W, S, a.agents, a.max_sweeps, nblk, lds);
+    for (int b = 0; b < nblk; b++) {
+        // exactly lds bytes, on the heap: an access past the working set is an access past the allocation
+        unsigned char* mem = static_cast<unsigned char*>(aligned_alloc(16, (size_t)lds));
+        std::barrier<> bar(thrl::kSpBlock);
+        g_bar = &bar;
+        std::vector<std::thread> th;
+        for (int t = 0; t < thrl::kSpBlock; t++)
+            th.emplace_back([&, t] {
+                if (sp.N <= 2) thrl::srn_block<2>(a, mem, t, b, nblk);
+                else thrl::srn_block<thrl::kSpMaxA>(a, mem, t, b, nblk);
+            });
+        for (auto& x : th) x.join();
+        free(mem);
+    }
+    int bad = cmp("iters", iters, w_iters) + cmp("sweeps", sweeps, w_sweeps) + cmp("n_diff_prices", ndp, w_ndp)
+        + cmp("n_diff_nodes", ndn, w_ndn) + cmp("loss_all", lall, w_lall) + cmp("loss_prices_mean", lp, w_lp)
+        + cmp("loss_nodes_mean", ln, w_ln) + cmp("loss_w", lw, w_lw) + cmp("gain_w", gw, w_gw) + cmp("v_w", vw, w_vw)
+        + cmp("br_prob_w", bw, w_bw) + cmp("br_policy", br, w_br) + cmp("v_opt", vopt, w_vopt) + cmp("v_pi", vpi, w_vpi);
+    printf(bad ? "DIFFERENT from the mirror\n" : "equal to the mirror bit for bit\n");
+    return bad ? 1 : 0;
+}

@@ -470,6 +470,29 @@ class SampledResponseArgs(ctypes.Structure):
     ]
 
 
+SRN_MAX_LDS = 160 * 1024
+
+
+class SampledResponseNoiseArgs(ctypes.Structure):
+    """thrl_sampled_response_noise_args (include/thrl_response_noise.h)"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("n_prices", ctypes.c_int32), ("n_nodes", ctypes.c_int32),
+        ("band_w", ctypes.c_int32), ("agents", ctypes.c_int32), ("max_sweeps", ctypes.c_int32), ("flags", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 2),
+        ("kind", ctypes.c_int32 * MAXA), ("eps", ctypes.c_double * MAXA), ("gamma", ctypes.c_double * MAXA),
+        ("eval_tol", ctypes.c_double), ("noise_prob", ctypes.c_double),
+        ("eps_g", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p), ("noise_prob_g", ctypes.c_void_p),
+        ("prob", ctypes.c_void_p * MAXA), ("nprob", ctypes.c_void_p * MAXA),
+        ("dpolicy", ctypes.c_void_p), ("npolicy", ctypes.c_void_p), ("grp_first", ctypes.c_void_p), ("grp_perm", ctypes.c_void_p),
+        ("reward", ctypes.c_void_p), ("band_lo", ctypes.c_void_p), ("band", ctypes.c_void_p), ("noise_reward", ctypes.c_void_p),
+        ("pi", ctypes.c_void_p),
+        ("iters", ctypes.c_void_p), ("sweeps", ctypes.c_void_p), ("n_diff_prices", ctypes.c_void_p),
+        ("n_diff_nodes", ctypes.c_void_p), ("loss_all", ctypes.c_void_p), ("loss_prices_mean", ctypes.c_void_p),
+        ("loss_nodes_mean", ctypes.c_void_p), ("loss_w", ctypes.c_void_p), ("gain_w", ctypes.c_void_p), ("v_w", ctypes.c_void_p),
+        ("br_prob_w", ctypes.c_void_p), ("br_policy", ctypes.c_void_p), ("v_opt", ctypes.c_void_p), ("v_pi", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -487,6 +510,8 @@ SYMBOLS = [
 ]
 # every symbol include/thrl_response.h declares
 RESPONSE_SYMBOLS = ["thrl_sampled_response"]
+# every symbol include/thrl_response_noise.h declares
+RESPONSE_NOISE_SYMBOLS = ["thrl_sampled_response_noise"]
 CAC_PARAMS = 1283
 
 _lib = None
@@ -633,6 +658,8 @@ def load():
     L.thrl_sampled_noise_chain.argtypes = [cfgp, ctypes.POINTER(SampledNoiseChainArgs), vp]
     L.thrl_sampled_response.restype = ctypes.c_int
     L.thrl_sampled_response.argtypes = [cfgp, ctypes.POINTER(SampledResponseArgs), vp]
+    L.thrl_sampled_response_noise.restype = ctypes.c_int
+    L.thrl_sampled_response_noise.argtypes = [cfgp, ctypes.POINTER(SampledResponseNoiseArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

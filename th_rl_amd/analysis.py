@@ -595,6 +595,22 @@ class AnalysisMethods:
         return sr.run(self, agents=agents, epsilon=epsilon, gamma=gamma, eval_tol=eval_tol, max_sweeps=max_sweeps,
                       policies=policies, pi=pi, n_games=n_games, probs=probs, dpolicy=dpolicy, tabs=tabs)
 
+    def sampled_response_noise(self, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_sweeps=8192,
+                               policies=False, pi=None, n_games=None, probs=None, dpolicy=None, tabs=None, noise_prob=None,
+                               resolution=1024, nprobs=None, npolicy=None, ntabs=None):
+        """sampled_response under DEMAND NOISE (sampled_response.run_noise, thrl_sampled_response_noise; definitions in
+        include/thrl_response_noise.h): the same values and best replies on the D distinct prices and then the Jn nodes of
+        the redrawn price (sampled_play.noise_tables(config, resolution)).  noise_prob: a number in (0, 1], an array [G]
+        or None = the batch's own.  Returns sampled_response's arrays with n_diff_prices / n_diff_nodes and
+        loss_prices_mean / loss_nodes_mean in place of n_diff / loss_mean, the weights being the long-run distribution of
+        the state in which a decision is made (pi: None = sampled_play(noise_prob=..., pi=True)), and noise_prob [G];
+        policies=True adds br_policy, v_opt, v_pi [N, G, D + Jn], the prices first."""
+        from . import sampled_response as sr
+        self._ready()
+        return sr.run_noise(self, agents=agents, epsilon=epsilon, gamma=gamma, eval_tol=eval_tol, max_sweeps=max_sweeps,
+                            policies=policies, pi=pi, n_games=n_games, probs=probs, dpolicy=dpolicy, tabs=tabs,
+                            noise_prob=noise_prob, resolution=resolution, nprobs=nprobs, npolicy=npolicy, ntabs=ntabs)
+
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),
         its baseline taken now at self.episode; tracker.check() after a launch that ends at a check episode.

@@ -26,9 +26,11 @@
 #include "thrl_sampled.h"
 #include "thrl_sampled_noise.h"
 #include "thrl_sampled_response.h"
+#include "thrl_sampled_response_noise.h"
 #include "thrl_tuple_stationary.h"
 
 #include "../../include/thrl_response.h"
+#include "../../include/thrl_response_noise.h"
 
 using namespace thrl;
 using namespace thrl::host;
@@ -120,10 +122,25 @@ int check_cell_limit(const char* call, int n_cells) {
     const bool ok = n_cells <= THRL_STAT_MAX_CELLS;
     return ok ? THRL_OK : fail(THRL_ERR_UNSUPPORTED, "%s: n_cells=%d, at most %d", call, n_cells, THRL_STAT_MAX_CELLS);
 }
+// ---- the checks of the calls on sampled play (thrl_sampled_chain, thrl_sampled_noise_chain, thrl_sampled_response,
+// thrl_sampled_response_noise)
+int check_prices(int n_prices, int n_tuples) {
+    const bool ok = n_prices >= 1 && n_prices <= n_tuples;
+    return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", n_prices, n_tuples);
+}
+int check_nodes_band(int n_nodes, int band_w) {
+    const bool ok = n_nodes >= 2 && band_w >= 1;
+    return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "n_nodes=%d must be >= 2 and band_w=%d >= 1", n_nodes, band_w);
+}
+int check_node_limit(const char* call, int n_nodes) {
+    const bool ok = n_nodes <= THRL_STAT_MAX_CELLS;
+    return ok ? THRL_OK : fail(THRL_ERR_UNSUPPORTED, "%s: n_nodes=%d, at most %d", call, n_nodes, THRL_STAT_MAX_CELLS);
+}
 int lds_refusal(const char* call, int64_t need, int N, int n_cells) {
     return fail(THRL_ERR_UNSUPPORTED, "%s: %lld bytes of LDS per game (N=%d, n_cells=%d)", call, (long long)need, N, n_cells);
 }
 int missing(const char* names) { return fail(THRL_ERR_NULL, "%s is NULL", names); }
+int missing_rows(int i) { return fail(THRL_ERR_NULL, "prob[%d] / nprob[%d] is NULL", i, i); }    // a network's, prices and nodes
 int missing_q(const char* flag) { return fail(THRL_ERR_NULL, "q is NULL without %s", flag); }
 int check_eps(int N, const int32_t* kind, const double* eps) {  // the scalar epsilons of the QTable agents (no eps_g)
     for (int i = 0; i < N; i++)
@@ -803,8 +820,7 @@ int thrl_sampled_chain(const thrl_cfg* c, const thrl_sampled_chain_args* x, void
     if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
     if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
     if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
-    if (x->n_prices < 1 || x->n_prices > x->n_tuples)
-        return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", x->n_prices, x->n_tuples);
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
     if ((rc = check_iters_tol(x->max_iters, x->tol)) != THRL_OK) return rc;
     if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
     SpArgs a;
@@ -853,16 +869,13 @@ int thrl_sampled_noise_chain(const thrl_cfg* c, const thrl_sampled_noise_chain_a
     if (x->reserved != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved);
     if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
     if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
-    if (x->n_prices < 1 || x->n_prices > x->n_tuples)
-        return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", x->n_prices, x->n_tuples);
-    if (x->n_nodes < 2 || x->band_w < 1)
-        return fail(THRL_ERR_BAD_CONFIG, "n_nodes=%d must be >= 2 and band_w=%d >= 1", x->n_nodes, x->band_w);
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_nodes_band(x->n_nodes, x->band_w)) != THRL_OK) return rc;
     if ((rc = check_iters_tol(x->max_iters, x->tol)) != THRL_OK) return rc;
     if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
     if (!x->noise_prob_g && !(x->noise_prob >= 0.0 && x->noise_prob <= 1.0))
         return fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of [0, 1]", x->noise_prob);
-    if (x->n_nodes > THRL_STAT_MAX_CELLS)
-        return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_noise_chain: n_nodes=%d, at most %d", x->n_nodes, THRL_STAT_MAX_CELLS);
+    if ((rc = check_node_limit("thrl_sampled_noise_chain", x->n_nodes)) != THRL_OK) return rc;
     thrl::SpnArgs a;
     memset(&a, 0, sizeof(a));
     SpArgs& sa = a.sp;
@@ -878,7 +891,7 @@ int thrl_sampled_noise_chain(const thrl_cfg* c, const thrl_sampled_noise_chain_a
         return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_noise_chain: %lld bytes of LDS per game (T=%d, n_prices=%d, n_nodes=%d), at most %d",
                     (long long)lds, sa.T, sa.D, a.Jn, THRL_SP_MAX_LDS);
     for (int i = 0; i < N; i++)
-        if (x->kind[i] != 0 && (!x->prob[i] || !x->nprob[i])) return fail(THRL_ERR_NULL, "prob[%d] / nprob[%d] is NULL", i, i);
+        if (x->kind[i] != 0 && (!x->prob[i] || !x->nprob[i])) return missing_rows(i);
     if (!x->dpolicy || !x->npolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->scaled || !x->price)
         return fail(THRL_ERR_NULL, "dpolicy / npolicy / grp_first / grp_perm / reward / scaled / price is NULL");
     if (!x->band_lo || !x->band || !x->noise_price || !x->noise_reward || !x->node_w)
@@ -916,8 +929,7 @@ int thrl_sampled_response(const thrl_cfg* c, const thrl_sampled_response_args* x
     if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
     if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
     if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
-    if (x->n_prices < 1 || x->n_prices > x->n_tuples)
-        return fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", x->n_prices, x->n_tuples);
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
     if (!x->sweep_gamma && (rc = check_gamma(x->gamma, N, x->agents)) != THRL_OK) return rc;
     if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
     if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
@@ -948,6 +960,64 @@ int thrl_sampled_response(const thrl_cfg* c, const thrl_sampled_response_args* x
     const int grid = grid_for(cus, lds_cu, sa.lds_bytes, kSrMaxBlocksPerCu, sa.G);
     const int e = thrl::launch_sampled_response(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_sr_response launch") : THRL_OK;
+}
+
+int thrl_sampled_response_noise(const thrl_cfg* c, const thrl_sampled_response_noise_args* x, void* stream) {
+    static_assert(THRL_SRN_MAX_LDS == THRL_SR_MAX_LDS, "both response calls plan for a CU's LDS");
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_sampled_response's checks in its order with thrl_sampled_noise_chain's of the nodes and the noise between them;
+    // every host-visible argument is checked, and the working set planned, before any pointer is looked at
+    if ((rc = check_games(x->n_games)) != THRL_OK) return rc;
+    if (x->flags != 0) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    for (int k = 0; k < 2; k++)
+        if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
+    if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_nodes_band(x->n_nodes, x->band_w)) != THRL_OK) return rc;
+    if (!x->sweep_gamma && (rc = check_gamma(x->gamma, N, x->agents)) != THRL_OK) return rc;
+    if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
+    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    if ((rc = check_noise_prob(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
+    if ((rc = check_node_limit("thrl_sampled_response_noise", x->n_nodes)) != THRL_OK) return rc;
+    thrl::SrnArgs a;
+    memset(&a, 0, sizeof(a));
+    SpArgs& sa = a.sp;
+    sa.G = x->n_games; sa.N = N; sa.T = x->n_tuples; sa.D = x->n_prices;
+    a.Jn = x->n_nodes; a.W = x->band_w;
+    tuple_strides(c, sa.n_actions, sa.tstride);
+    for (int i = 0; i < N; i++) {
+        sa.kind[i] = x->kind[i]; sa.eps[i] = x->eps[i]; sa.prob[i] = x->prob[i]; a.nprob[i] = x->nprob[i]; a.gamma[i] = x->gamma[i];
+    }
+    const int64_t lds = thrl::srn_layout(a);         // the working set of include/thrl_response_noise.h
+    // (the cells of this analysis are its states: the distinct prices and the nodes)
+    if (lds > THRL_SRN_MAX_LDS) return lds_refusal("thrl_sampled_response_noise", lds, N, x->n_prices + x->n_nodes);
+    for (int i = 0; i < N; i++)
+        if (x->kind[i] != 0 && (!x->prob[i] || !x->nprob[i])) return missing_rows(i);
+    if (!x->dpolicy || !x->npolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->band_lo || !x->band || !x->noise_reward)
+        return missing("dpolicy / npolicy / grp_first / grp_perm / reward / band_lo / band / noise_reward");
+    if (!x->iters || !x->sweeps || !x->n_diff_prices || !x->n_diff_nodes || !x->loss_all || !x->loss_prices_mean
+        || !x->loss_nodes_mean)
+        return missing("iters / sweeps / n_diff_prices / n_diff_nodes / loss_all / loss_prices_mean / loss_nodes_mean");
+    if (x->pi && (!x->loss_w || !x->gain_w || !x->v_w || !x->br_prob_w)) return missing("with pi, loss_w / gain_w / v_w / br_prob_w");
+    a.agents = x->agents; a.max_sweeps = x->max_sweeps; a.eval_tol = x->eval_tol; a.noise_prob = x->noise_prob;
+    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm; sa.reward = x->reward;
+    a.sweep_gamma = x->sweep_gamma; a.noise_prob_g = x->noise_prob_g; a.pi = x->pi;
+    a.npolicy = x->npolicy; a.band_lo = x->band_lo; a.band = x->band; a.noise_reward = x->noise_reward;
+    a.iters = x->iters; a.sweeps = x->sweeps; a.n_diff_prices = x->n_diff_prices; a.n_diff_nodes = x->n_diff_nodes;
+    a.loss_all = x->loss_all; a.loss_prices_mean = x->loss_prices_mean; a.loss_nodes_mean = x->loss_nodes_mean;
+    a.loss_w = x->loss_w; a.gain_w = x->gain_w; a.v_w = x->v_w; a.br_prob_w = x->br_prob_w;
+    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+    int cus = 0, lds_cu = 0;
+    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
+    if (lds_cu > 0 && sa.lds_bytes > lds_cu) return lds_refusal("thrl_sampled_response_noise", lds, N, x->n_prices + x->n_nodes);
+    const int grid = grid_for(cus, lds_cu, sa.lds_bytes, kSrnMaxBlocksPerCu, sa.G);
+    const int e = thrl::launch_sampled_response_noise(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_srn_response launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -12,53 +12,16 @@
 //   one Q_V(d, sigma(d)) per price: a thread per price, 1 / A_i of the work.  The largest change is a maximum, whose
 //   order is free: sp_block_max.  The ordered output sums are one lane each over the D terms.
 //   The staging, Z's factors and the block maximum are thrl_sampled_dev.h's; the margin, the first maximum and the
-//   relative loss are thrl_solve_dev.h's.  Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source
-//   runs as 256 host threads with barriers.
+//   relative loss are thrl_solve_dev.h's; sr_prob and sr_q are thrl_response_dev.h's, shared with k_srn_response.
+//   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
 #include "thrl_sampled_dev.h"
 #include "thrl_sampled_response.h"
 #include "thrl_solve_dev.h"
+#include "thrl_response_dev.h"
 
 namespace thrl {
 
 namespace {
-
-// P_j(x|d) from the staged rows
-__device__ __forceinline__ double sr_prob(const SpArgs& a, const unsigned char* s_mem, const SpCst* cst, int j, int d, int x) {
-    if (a.kind[j] == 0) {
-        const uint16_t* rq = reinterpret_cast<const uint16_t*>(s_mem + a.o_row[j]);
-        return (int)rq[d] == x ? cst->hi[j] : cst->lo[j];
-    }
-    const float* rf = reinterpret_cast<const float*>(s_mem + a.o_row[j]);
-    return (double)rf[d * a.n_actions[j] + x];
-}
-
-// Q_V(d, k) of agent i: sum over the tuples t with a_i(t) = k, ascending t from 0.0, of w(t|d) * U(t), divided by zm
-template <int MAXN>
-__device__ __forceinline__ double sr_q(const SpArgs& a, const unsigned char* s_mem, const SpCst* cst, const double* U, double zm,
-                                       int i, int d, int k) {
-    const int N = a.N, T = a.T, A = a.n_actions[i], ts = a.tstride[i];
-    double acc = 0.0;
-    if (MAXN == 2 && N == 2) {                           // one rival: its action is the other digit of t
-        const int r = 1 - i, Ar = a.n_actions[r];
-        const int t0 = i == 0 ? k * Ar : k, dt = i == 0 ? 1 : A;
-        for (int x = 0; x < Ar; x++) acc = __dadd_rn(acc, __dmul_rn(sr_prob(a, s_mem, cst, r, d, x), U[t0 + x * dt]));
-        return __ddiv_rn(acc, zm);
-    }
-    for (int base = k * ts; base < T; base += A * ts)
-        for (int lo = 0; lo < ts; lo++) {
-            const int t = base + lo;
-            double w = 1.0;
-            bool first = true;
-            for (int j = 0; j < N; j++) {
-                if (j == i) continue;
-                const double p = sr_prob(a, s_mem, cst, j, d, (t / a.tstride[j]) % a.n_actions[j]);
-                w = first ? p : __dmul_rn(w, p);
-                first = false;
-            }
-            acc = __dadd_rn(acc, __dmul_rn(w, U[t]));
-        }
-    return __ddiv_rn(acc, zm);
-}
 
 template <int MAXN>
 __device__ __forceinline__ void sr_block(const SrArgs& a, unsigned char* s_mem, int tid, int bid, int nblk) {

@@ -59,8 +59,9 @@ def parse_options(opt, config):
     """training.sampled_play (true or a dict) -> the dict with every key filled in: epsilon ("current": the QTable
     agents' epsilon where training stopped; a number, or one per agent), start ("uniform" or "state"), tol, max_iters,
     pi (store the distributions).  The optional key "response" (true or a dict, sampled_response.parse_options) asks for
-    the best responses to the stochastic policies; it stays in the result, filled in, only when given, and is refused
-    together with "noise".  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
+    the best responses to the stochastic policies; it stays in the result, filled in, only when given, and together with
+    "noise" it is refused unless it opts in with its own "noise": true (then the best responses are those under the same
+    demand noise, at sampled_play's noise_prob and resolution).  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
     run's own noise, refused for a noise-free run as training.greedy_stationary does; "resolution": the uniform cuts of
     the price axis behind the nodes}) asks for play under demand noise; it stays in the result, filled in, only when
     given, and with it start may be "reset".  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples, more than
@@ -110,9 +111,10 @@ def parse_options(opt, config):
         out["noise"] = noise
     if response is not None:
         from . import sampled_response as sr
-        if noise is not None:
+        opted = isinstance(response, dict) and response.get("noise") not in (None, False)     # (checked by its parser)
+        if noise is not None and not opted:
             raise ValueError("%s: \"response\" with \"noise\": %s" % (name, sr.NOISE_FOLLOW_UP))
-        out["response"] = sr.parse_options(response, config)
+        out["response"] = sr.parse_options(response, config, noise=noise)
     return out
 
 
@@ -554,6 +556,10 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=No
     if opt.get("response"):
         from . import sampled_response as sr
         same = opt["pi"] and opt["start"] == "uniform"               # the stored distributions are the ones it would compute
-        sr.write_artefacts(exp_path, batch, config, opt["response"], ids, n_groups, epsilon=opt["epsilon"], tabs=tabs,
-                           pi=r["pi"] if same else None)
+        if opt["response"].get("noise"):
+            sr.write_artefacts_noise(exp_path, batch, config, opt["response"], ids, n_groups, r["noise_prob"],
+                                     epsilon=opt["epsilon"], tabs=tabs, pi=r["pi"] if same else None, max_jump=r["max_jump"])
+        else:
+            sr.write_artefacts(exp_path, batch, config, opt["response"], ids, n_groups, epsilon=opt["epsilon"], tabs=tabs,
+                               pi=r["pi"] if same else None)
     return r

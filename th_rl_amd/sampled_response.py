@@ -10,11 +10,19 @@ long-run distribution pi of sampled play, loss_w, gain_w (what the best reply ad
 br_prob_w (the long-run share of steps on which the agent already plays its best response).  (1 - gamma_i) gain_w is the
 agent's exploitability in reward units per period; its sum over the agents is the profile's NashConv.  It separates
 "prices above Nash because the profile is an epsilon-equilibrium" from "prices above Nash because nobody has learned to
-undercut a randomising rival".  Noise-free play only; the mode under demand noise is the follow-up.
+undercut a randomising rival".
+
+run() is noise-free play.  run_noise() is the same question in the environment the reference ships (NoisyPriceState,
+thrl_sampled_response_noise, include/thrl_response_noise.h): the agent's states are the D distinct prices and then the Jn
+quadrature nodes of the redrawn price (sampled_play.noise_tables), n_diff and loss_mean come per kind of state, and the
+weights are the long-run distribution of the state in which a decision is made.
 
 In train_one the analysis is the sub-key "response" of training.sampled_play, as "noise" is: true, or {"agents",
 "eval_tol", "max_sweeps", "policies"}.  It writes sampled_response.json and sresp_*.npy; utils.sampled_response_summary
-and utils.sampled_response_games read them.  Sharded runs (th_rl_amd.launch) are out of scope, as sampled_play is.
+and utils.sampled_response_games read them.  With "noise": true in that dict (and sampled_play's own "noise", whose
+noise_prob and resolution it takes) the analysis is run_noise's and writes sampled_response_noise.json and srespn_*.npy
+(utils.sampled_response_noise_summary / sampled_response_noise_games).  Sharded runs (th_rl_amd.launch) are out of scope,
+as sampled_play is.
 """
 import ctypes
 import os
@@ -30,20 +38,31 @@ from ._lib import ThrlError
 from .deviation import optimal
 
 DEFAULTS = dict(agents=None, eval_tol=1e-12, max_sweeps=8192, policies=False)
-NOISE_FOLLOW_UP = "best responses to sampled play under demand noise are the follow-up: drop \"noise\" or \"response\""
+NOISE_FOLLOW_UP = ("best responses to sampled play under demand noise are the follow-up of the noise-free ones and opted into: "
+                   "set \"noise\": true inside \"response\", or drop \"noise\" or \"response\"")
 MAX_LDS = _lib.SR_MAX_LDS
 MAX_TEAM_BYTES = 32 * 1024
 INT = ("iters", "sweeps", "n_diff")
 FLOAT = ("loss_all", "loss_mean")
 WEIGHTED = ("loss_w", "gain_w", "v_w", "br_prob_w")
 PER_GAME = INT + FLOAT + WEIGHTED + ("gamma", "epsilon", "br_policy", "v_opt", "v_pi")
+NOISE_INT = ("iters", "sweeps", "n_diff_prices", "n_diff_nodes")
+NOISE_FLOAT = ("loss_all", "loss_prices_mean", "loss_nodes_mean")
 
 
-def parse_options(opt, config):
+def parse_options(opt, config, noise=None):
     """training.sampled_play.response (true or a dict) -> the dict with every key filled in: agents (None = all, or a
     list), eval_tol (>= 0), max_sweeps (an integer in [1, STAT_MAX_ITERS]), policies (store sigma*, V* and V_pi).  Refuses
-    a working set above a CU's LDS."""
+    a working set above a CU's LDS.  The optional key "noise" (true or false) opts into the analysis under demand noise
+    and stays in the result only when given; true needs `noise`, the parsed "noise" of training.sampled_play (its
+    noise_prob and resolution are the analysis'), and the working set checked is then working_set_noise's."""
     name = "training.sampled_play.response"
+    under_noise = None
+    if isinstance(opt, dict) and "noise" in opt:
+        opt = dict(opt)
+        under_noise = opt.pop("noise")
+        if not isinstance(under_noise, bool):
+            raise ValueError("%s.noise must be true or false, got %r" % (name, under_noise))
     out = an.options("sampled_play.response", opt, DEFAULTS)
     n = len(config["agents"])
     if out["agents"] is not None:
@@ -60,10 +79,20 @@ def parse_options(opt, config):
         raise ValueError("%s.max_sweeps must be an integer in [1, %d], got %r" % (name, _lib.STAT_MAX_ITERS, out["max_sweeps"]))
     if not isinstance(out["policies"], bool):
         raise ValueError("%s.policies must be true or false, got %r" % (name, out["policies"]))
-    ws = working_set(config)
-    if not ws["fits"]:
-        raise ValueError("%s: a game's working set is %d bytes (T=%d, D=%d), a CU's LDS holds %d"
-                         % (name, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
+    if under_noise and noise is None:
+        raise ValueError("%s.noise: training.sampled_play has no \"noise\", whose noise_prob and resolution this mode takes" % name)
+    if under_noise:
+        ws = working_set_noise(config, noise["resolution"])
+        if not ws["fits"]:
+            raise ValueError("%s.noise: under noise a game's working set is %d bytes (T=%d, D=%d, Jn=%d), a CU's LDS holds %d"
+                             % (name, ws["bytes"], ws["T"], ws["D"], ws["Jn"], MAX_LDS))
+    else:
+        ws = working_set(config)
+        if not ws["fits"]:
+            raise ValueError("%s: a game's working set is %d bytes (T=%d, D=%d), a CU's LDS holds %d"
+                             % (name, ws["bytes"], ws["T"], ws["D"], MAX_LDS))
+    if under_noise is not None:
+        out["noise"] = under_noise
     return out
 
 
@@ -90,6 +119,24 @@ def working_set(config, tabs=None):
         b += r16(2 * D) if kind == "QTable" else r16(4 * D * A)
     b += r16(2 * (D + 1)) + 2 * r16(2 * T) + 2 * r16(2 * D) + 2048 + (r16(8 * D * max(acts)) if team > 1 else 0) + 256
     return dict(bytes=int(b), T=T, D=D, team=team, fits=b <= MAX_LDS)
+
+
+def working_set_noise(config, resolution=sp.NOISE_DEFAULTS["resolution"], tabs=None, n_nodes=None):
+    """The LDS bytes one game takes in thrl_sampled_response_noise, by include/thrl_response_noise.h's formula
+    (srn_layout), S = D + Jn: the sum of r16(x) over five arrays of 8 S, two of 8 T, 4 D A_i per network, 2 D per QTable
+    agent, 2 (D + 1), 2 T, 2 T, 2 S, 2 S, 2 Jn per QTable agent, 2,048 and 256.  The networks' node rows are not part of
+    it.  Jn from resolution (sampled_play.n_nodes_of) unless n_nodes is given.  Returns dict(bytes, T, D, Jn, fits)."""
+    tabs = sp.tables(config) if tabs is None else tabs
+    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
+    Jn = int(n_nodes) if n_nodes is not None else sp.n_nodes_of(config, resolution)
+    S = D + Jn
+    r16 = sp._r16
+    b = 5 * r16(8 * S) + 2 * r16(8 * T)
+    for kind, A in zip(tabs["kinds"], tabs["n_actions"]):
+        b += r16(2 * D) if kind == "QTable" else r16(4 * D * int(A))
+    b += r16(2 * (D + 1)) + 2 * r16(2 * T) + 2 * r16(2 * S)
+    b += sum(r16(2 * Jn) for kind in tabs["kinds"] if kind == "QTable") + 2048 + 256
+    return dict(bytes=int(b), T=T, D=D, Jn=Jn, fits=b <= MAX_LDS)
 
 
 def resolve_gamma(batch, gamma, G):
@@ -210,6 +257,122 @@ def run(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_s
     return res
 
 
+def run_noise(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_sweeps=8192, policies=False, pi=None,
+              n_games=None, probs=None, dpolicy=None, tabs=None, noise_prob=None, resolution=sp.NOISE_DEFAULTS["resolution"],
+              nprobs=None, npolicy=None, ntabs=None):
+    """thrl_sampled_response_noise for the first n_games (default all) games of `batch`: run()'s question under demand
+    noise, on the D distinct prices and then the Jn nodes of the redrawn price.  agents, epsilon, gamma, eval_tol,
+    max_sweeps, policies, probs, dpolicy as in run().  noise_prob: a number in (0, 1], an array [G] (device data: an entry
+    outside (0, 1] refuses that game) or None = the batch's own (sampled_play.resolve_noise).  resolution: the uniform
+    cuts behind the nodes; ntabs (or tabs): sampled_play.noise_tables(batch.config, resolution); nprobs / npolicy: the
+    strategies at ntabs["xn"] as in sampled_play.run.  pi: None = computed here with sampled_play.run(noise_prob=...,
+    pi=True) on the same strategies, an array [G, T], or False = no weighted outputs.  policies=True adds br_policy
+    (uint16), v_opt, v_pi [N, G, D + Jn], the prices first.  Returns a dict of numpy arrays, [N, G] with zeros for the
+    agents that are not selected: iters, sweeps, n_diff_prices, n_diff_nodes, loss_all, loss_prices_mean,
+    loss_nodes_mean, loss_w, gain_w, v_w, br_prob_w, gamma, epsilon, and noise_prob [G]."""
+    import torch
+    from . import tuple_stationary as ts
+    N = batch.N
+    G = sp._games(batch, n_games)
+    ag, mask = eq.agents_mask(agents, N)
+    if isinstance(max_sweeps, bool) or not 1 <= int(max_sweeps) <= _lib.STAT_MAX_ITERS:
+        raise ThrlError("sampled_response: max_sweeps=%r out of [1, %d]" % (max_sweeps, _lib.STAT_MAX_ITERS))
+    tabs = ntabs if ntabs is not None else tabs
+    if tabs is None or "xn" not in tabs:
+        tabs = sp.noise_tables(batch.config, resolution, tabs=tabs)
+    tp._batch_tables(batch, tabs)
+    T, D, Jn, W = int(tabs["n_tuples"]), int(tabs["n_prices"]), int(tabs["n_nodes"]), int(tabs["band_w"])
+    ws = working_set_noise(batch.config, tabs=tabs, n_nodes=Jn)
+    if not ws["fits"]:                                   # what the call answers from the shape alone (the library's own
+        # message is the shared "(N=.., n_cells=..)" with n_cells = D + Jn, the states; this one names the parts)
+        err = ThrlError("thrl_sampled_response_noise refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d, "
+                        "n_nodes=%d), at most %d" % (_lib.ERR_UNSUPPORTED, ws["bytes"], T, D, Jn, MAX_LDS))
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    kinds = tp._kinds(batch)
+    dev = batch.device
+    sdev = batch.state.device
+    a = _lib.SampledResponseNoiseArgs()
+    a.n_games, a.n_tuples, a.n_prices, a.n_nodes, a.band_w, a.agents = G, T, D, Jn, W, mask
+    a.max_sweeps, a.eval_tol = int(max_sweeps), float(eval_tol)
+    for i, k in enumerate(kinds):
+        a.kind[i] = tp.KINDS[k]
+    with torch.cuda.device(dev):
+        eps, eps_g = sp.resolve_epsilon(batch, epsilon, G)
+        gam, gam_g = resolve_gamma(batch, gamma, G)
+        p_noise, p_g = an.resolve_noise(batch, noise_prob, G, "sampled_response")
+        for i in range(N):
+            a.eps[i], a.gamma[i] = eps[i], gam[i]
+        if eps_g is not None:
+            a.eps_g = eps_g.data_ptr()
+        if gam_g is not None:
+            a.sweep_gamma = gam_g.data_ptr()
+        if p_g is not None:
+            a.noise_prob_g = p_g.data_ptr()
+        else:
+            a.noise_prob = p_noise
+        if probs is None:
+            probs = sp.price_probs(batch, tabs["dprice"], n_games=G)
+        if dpolicy is None:
+            dpolicy = ts.price_policy(batch, tabs["dprice"], n_games=G)
+        if nprobs is None:
+            nprobs = sp.price_probs(batch, tabs["xn"], n_games=G)
+        if npolicy is None:
+            npolicy = ts.price_policy(batch, tabs["xn"], n_games=G)
+        an.check_policy(batch, dpolicy, (G, N, D), "sampled_response", "dpolicy")
+        an.check_policy(batch, npolicy, (G, N, Jn), "sampled_response", "npolicy")
+        for i, k in enumerate(kinds):
+            if k == "QTable":
+                continue
+            for what, rows, J, field in (("probs", probs, D, a.prob), ("nprobs", nprobs, Jn, a.nprob)):
+                x = rows.get(i)
+                shape = (G, J, int(batch.cfg.n_actions[i]))
+                if x is None or tuple(x.shape) != shape or x.dtype != torch.float32 or x.device != sdev or not x.is_contiguous():
+                    raise ThrlError("sampled_response: %s[%d] must be a contiguous float32 tensor %s on %s" % (what, i, shape, dev))
+                field[i] = x.data_ptr()
+        a.dpolicy, a.npolicy = dpolicy.data_ptr(), npolicy.data_ptr()
+        pi_t = None
+        if pi is None:
+            e = epsilon if eps_g is None else eps_g
+            st = sp.run(batch, epsilon=e, pi=True, n_games=G, probs=probs, dpolicy=dpolicy, tabs=tabs,
+                        noise_prob=p_noise if p_g is None else p_g, nprobs=nprobs, npolicy=npolicy)
+            pi_t = torch.from_numpy(np.ascontiguousarray(st["pi"])).to(dev)
+        elif pi is not False:
+            if isinstance(pi, torch.Tensor):
+                pi_t = pi.to(device=dev, dtype=torch.float64).contiguous()
+            else:
+                pi_t = torch.from_numpy(np.ascontiguousarray(np.asarray(pi, np.float64))).to(dev)
+            if tuple(pi_t.shape) != (G, T):
+                raise ThrlError("sampled_response: pi must be shaped %s, got %s" % ((G, T), tuple(pi_t.shape)))
+        if pi_t is not None:
+            a.pi = pi_t.data_ptr()
+        keep = an.bind_tables(a, tabs, [("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32),
+                                        ("reward", (N, T), np.float64), ("band_lo", (T,), np.int32), ("band", (T, W), np.float64),
+                                        ("noise_reward", (N, T), np.float64)], dev, "sampled_response")
+        S = D + Jn
+        out = an.outputs(dev, (NOISE_INT, (N, G), "int32"), (NOISE_FLOAT, (N, G), "float64"),
+                         (WEIGHTED if pi_t is not None else (), (N, G), "float64"),
+                         (("br_policy",) if policies else (), (N, G, S), "int16"),
+                         (("v_opt", "v_pi") if policies else (), (N, G, S), "float64"))
+        an.bind(a, out)
+        _lib.check(batch.L.thrl_sampled_response_noise(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
+                   "thrl_sampled_response_noise")
+        torch.cuda.synchronize(dev)
+        res = an.fetch(out)
+        del keep
+        res["epsilon"] = np.repeat(np.asarray(eps, np.float64)[:, None], G, axis=1) if eps_g is None else eps_g.cpu().numpy()
+        res["gamma"] = np.repeat(np.asarray(gam, np.float64)[:, None], G, axis=1) if gam_g is None else gam_g.cpu().numpy()
+        res["noise_prob"] = np.full(G, p_noise, np.float64) if p_g is None else p_g.cpu().numpy()
+        if pi_t is not None:
+            res["pi"] = pi_t.cpu().numpy()
+    if policies:
+        res["br_policy"] = res["br_policy"].view(np.uint16)
+    res["agents"], res["T"], res["n_prices"], res["n_nodes"], res["lds_bytes"] = ag, T, D, Jn, ws["bytes"]
+    res["resolution"] = int(tabs.get("resolution", resolution))
+    res["eval_tol"], res["max_sweeps"] = float(eval_tol), int(max_sweeps)
+    return res
+
+
 # ---------------------------------------------------------------------------------------------- host side
 def exploitability(games):
     """(1 - gamma_i) * gain_w [N, G]: what agent i's best reply adds, in reward units per period."""
@@ -303,4 +466,83 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, epsilon="curren
     nash, cartel = optimal(config)
     summary = summarize(r, r["agents"], ids, n_groups, nash, cartel)
     an.save_json(os.path.join(exp_path, "sampled_response.json"), describe(opt, r, nash, cartel, summary))
+    return r
+
+
+# ---------------------------------------------------------------------------------------------- under demand noise
+def summarize_noise(games, agents, ids, n_groups, nash, cartel, max_jump=None):
+    """summarize()'s rows for run_noise()'s arrays.  A (group, agent) row also has diff_nodes_mean, the mean number of
+    node-states where the best reply is not the modal action, over the solved games; a group's own row also has
+    max_jump_max, the chain's honesty figure of the midpoint rule (sampled_play.summarize), over the group's games, where
+    max_jump [G] is given."""
+    rows = summarize(games, agents, ids, n_groups, nash, cartel)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    iters = np.asarray(games["iters"], np.int64)
+    nodes = np.asarray(games["n_diff_nodes"], np.float64)
+    for row in rows:
+        m = ids == row["group"]
+        if row["agent"] is not None:
+            i = row["agent"]
+            row["diff_nodes_mean"] = an.mean(nodes[i][m & (iters[i] >= 0)])
+        elif max_jump is not None:
+            row["max_jump_max"] = an.num(np.asarray(max_jump, np.float64)[m].max()) if m.any() else None
+    return rows
+
+
+def describe_noise(options, r, nash, cartel, summary):
+    """sampled_response_noise.json's content."""
+    d = describe(options, r, nash, cartel, summary)
+    d.update(n_nodes=int(r["n_nodes"]), resolution=int(r["resolution"]))
+    return d
+
+
+NOISE_FILES = (("srespn_counts.npy", NOISE_INT, np.int32), ("srespn_loss.npy", NOISE_FLOAT, np.float64),
+               ("srespn_weighted.npy", WEIGHTED, np.float64))
+NOISE_PLAIN = (("gamma", "srespn_gamma.npy"), ("epsilon", "srespn_epsilon.npy"), ("noise_prob", "srespn_noise_prob.npy"))
+NOISE_OPTIONAL = (("br_policy", "srespn_br_policy.npy", np.uint16), ("v_opt", "srespn_v_opt.npy", np.float64),
+                  ("v_pi", "srespn_v_pi.npy", np.float64))
+
+
+def save_games_noise(d, r):
+    """srespn_counts int32 [4, N, G] (iters, sweeps, n_diff_prices, n_diff_nodes), srespn_loss float64 [3, N, G] (loss_all,
+    loss_prices_mean, loss_nodes_mean), srespn_weighted float64 [4, N, G] (loss_w, gain_w, v_w, br_prob_w), srespn_gamma
+    and srespn_epsilon float64 [N, G], srespn_noise_prob float64 [G]; with the policies srespn_br_policy uint16,
+    srespn_v_opt and srespn_v_pi float64 [N, G, D + Jn]."""
+    for name, fields, dt in NOISE_FILES:
+        np.save(os.path.join(d, name), np.stack([np.asarray(r[f], dt) for f in fields]))
+    for f, name in NOISE_PLAIN:
+        np.save(os.path.join(d, name), np.asarray(r[f], np.float64))
+    for f, name, dt in NOISE_OPTIONAL:
+        path = os.path.join(d, name)
+        if f in r:
+            np.save(path, np.asarray(r[f], dt))
+        elif os.path.isfile(path):               # a file left by an earlier run with other options
+            os.remove(path)
+
+
+def load_games_noise(d):
+    """The per-game arrays one run directory holds (training.sampled_play.response with "noise")."""
+    g = {}
+    for name, fields, _ in NOISE_FILES:
+        x = np.load(os.path.join(d, name))
+        g.update({f: x[k] for k, f in enumerate(fields)})
+    for f, name in NOISE_PLAIN:
+        g[f] = np.load(os.path.join(d, name))
+    for f, name, _ in NOISE_OPTIONAL:
+        if os.path.isfile(os.path.join(d, name)):
+            g[f] = np.load(os.path.join(d, name))
+    return g
+
+
+def write_artefacts_noise(exp_path, batch, config, opt, ids, n_groups, noise_prob, epsilon="current", tabs=None, pi=None,
+                          max_jump=None):
+    """train_one's training.sampled_play.response outputs under demand noise: the per-game srespn_*.npy files and
+    sampled_response_noise.json.  noise_prob and tabs (sampled_play.noise_tables) are sampled_play's own; pi: its
+    distributions where it stored them (else computed here); max_jump: its honesty figure, carried into the summary."""
+    r = run_noise(batch, agents=opt["agents"], epsilon=epsilon, eval_tol=opt["eval_tol"], max_sweeps=opt["max_sweeps"],
+                  policies=opt["policies"], pi=pi, ntabs=tabs, noise_prob=noise_prob)
+    save_games_noise(exp_path, r)
+    nash, cartel = optimal(config)
+    summary = summarize_noise(r, r["agents"], ids, n_groups, nash, cartel, max_jump=max_jump)
+    an.save_json(os.path.join(exp_path, "sampled_response_noise.json"), describe_noise(opt, r, nash, cartel, summary))
     return r

@@ -821,3 +821,40 @@ def sampled_response_games(exp_path):
         nc = nc + ex[i]
     cols["nashconv"] = nc
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
+def sampled_response_noise_summary(exp_path):
+    """A run's best responses to sampled play UNDER DEMAND NOISE (training.sampled_play.response with "noise": true):
+    sampled_response_noise.json's summary as a DataFrame.  sampled_response_summary's rows, a (group, agent) row with
+    diff_nodes_mean (the mean number of node-states where the best reply is not the modal action) beside them and a
+    group's own row with max_jump_max (sampled_play's honesty figure of the quadrature); plus T, n_prices, n_nodes, Nash
+    and Cartel."""
+    desc = _load_json(exp_path, "sampled_response_noise.json")
+    df = pandas.DataFrame(desc["summary"])
+    df["T"], df["n_prices"], df["n_nodes"] = int(desc["T"]), int(desc["n_prices"]), int(desc["n_nodes"])
+    df["Nash"], df["Cartel"] = float(desc["nash"]), float(desc["cartel"])
+    return df
+
+
+def sampled_response_noise_games(exp_path):
+    """Per-game results of training.sampled_play.response under demand noise, one row per game indexed by its GLOBAL id:
+    noise_prob, per solved agent i iters_<i>, sweeps_<i>, n_diff_prices_<i>, n_diff_nodes_<i>, loss_all_<i>,
+    loss_prices_mean_<i>, loss_nodes_mean_<i>, loss_w_<i>, gain_w_<i>, v_w_<i>, br_prob_w_<i>, gamma_<i>, epsilon_<i>,
+    exploit_<i> = (1 - gamma_i) * gain_w; and nashconv, their sum over the solved agents (NaN where one of them is not
+    solved)."""
+    from th_rl_amd import sampled_response as sr
+    _run_dirs(exp_path, "srespn_counts.npy", "sampled-response analysis under noise", "sampled_play", shards=False)
+    desc = _load_json(exp_path, "sampled_response_noise.json")
+    off = _game_offset(exp_path, exp_path)
+    g = sr.load_games_noise(exp_path)
+    ex = sr.exploitability(g)
+    cols = {"noise_prob": g["noise_prob"]}
+    n = g["iters"].shape[1]
+    nc = numpy.zeros(n)
+    for i in desc["agents"]:
+        for f in sr.NOISE_INT + sr.NOISE_FLOAT + sr.WEIGHTED + ("gamma", "epsilon"):
+            cols["%s_%d" % (f, i)] = g[f][i]
+        cols["exploit_%d" % i] = ex[i]
+        nc = nc + ex[i]
+    cols["nashconv"] = nc
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
