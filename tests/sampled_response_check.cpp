@@ -3,46 +3,8 @@
 // the mirror's outputs that tests/sampled_response_mirror.write_case writes, runs every game through sr_block and
 // compares every output bit for bit.  Built as host code (hipcc -x hip --cuda-host-only -DTHRL_SP_HOST_BUILD), so that
 // thrl_solve_dev.h's __host__ __device__ pieces are the ones the device build uses; it makes no HIP call and needs no GPU.
-#include <algorithm>
-#include <barrier>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-// the shared solver pieces first, as HIP declares them: improve_margin, first_max and rel_loss are __host__ __device__
-#include "../th_rl_amd/csrc/thrl_solve_dev.h"
-
-// from here on a __device__ function is a host function, a barrier is the host threads', an _rn operation a plain one
-// (the build's -ffp-contract=off rounds each separately)
-static std::barrier<>* g_bar;
-#undef __device__
-#define __device__
-#define __syncthreads() g_bar->arrive_and_wait()
-#define __dadd_rn(a, b) ((a) + (b))
-#define __dsub_rn(a, b) ((a) - (b))
-#define __dmul_rn(a, b) ((a) * (b))
-#define __ddiv_rn(a, b) ((a) / (b))
-
+#include "response_check.h"
 #include "../th_rl_amd/csrc/thrl_sampled_response.hip"
-
-template <typename T>
-static std::vector<T> rd(FILE* f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "short read\n"); exit(2); }
-    return v;
-}
-
-template <typename T>
-static int cmp(const char* what, const std::vector<T>& a, const std::vector<T>& b) {
-    int bad = 0;
-    for (size_t i = 0; i < a.size(); i++) bad += memcmp(&a[i], &b[i], sizeof(T)) != 0;
-    if (bad) printf("  %s: %d of %zu differ\n", what, bad, a.size());
-    return bad;
-}
 
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
@@ -91,20 +53,10 @@ int main(int argc, char** argv) {
     const long long lds = thrl::sr_layout(a);
     printf("G=%d N=%d T=%d D=%d agents=0x%x max_sweeps=%d blocks=%d team=%d: %lld bytes of LDS\n", sp.G, sp.N, sp.T, sp.D, a.agents,
            a.max_sweeps, nblk, a.team, lds);
-    for (int b = 0; b < nblk; b++) {
-        // exactly lds bytes, on the heap: an access past the working set is an access past the allocation
-        unsigned char* mem = static_cast<unsigned char*>(aligned_alloc(16, (size_t)lds));
-        std::barrier<> bar(thrl::kSpBlock);
-        g_bar = &bar;
-        std::vector<std::thread> th;
-        for (int t = 0; t < thrl::kSpBlock; t++)
-            th.emplace_back([&, t] {
-                if (sp.N <= 2) thrl::sr_block<2>(a, mem, t, b, nblk);
-                else thrl::sr_block<thrl::kSpMaxA>(a, mem, t, b, nblk);
-            });
-        for (auto& x : th) x.join();
-        free(mem);
-    }
+    run_blocks(lds, nblk, thrl::kSpBlock, [&](unsigned char* mem, int t, int b) {
+        if (sp.N <= 2) thrl::sr_block<2>(a, mem, t, b, nblk);
+        else thrl::sr_block<thrl::kSpMaxA>(a, mem, t, b, nblk);
+    });
     int bad = cmp("iters", iters, w_iters) + cmp("sweeps", sweeps, w_sweeps) + cmp("n_diff", ndiff, w_ndiff)
         + cmp("loss_all", lall, w_lall) + cmp("loss_mean", lmean, w_lmean) + cmp("loss_w", lw, w_lw) + cmp("gain_w", gw, w_gw)
         + cmp("v_w", vw, w_vw) + cmp("br_prob_w", bw, w_bw) + cmp("br_policy", br, w_br) + cmp("v_opt", vopt, w_vopt)

@@ -809,6 +809,66 @@ int thrl_price_probs(const thrl_cfg* c, const thrl_price_probs_args* x, void* st
     return THRL_OK;
 }
 
+}  // extern "C"
+
+// ---- what the four calls on sampled play share; X is the call's public argument struct
+namespace {
+
+// the head of SpArgs: the counts, the tuple strides and the agents' kinds, epsilons and rows at the distinct prices
+template <typename X>
+void sp_fill_head(SpArgs& sa, const thrl_cfg* c, const X* x) {
+    sa.G = x->n_games; sa.N = c->n_agents; sa.T = x->n_tuples; sa.D = x->n_prices;
+    tuple_strides(c, sa.n_actions, sa.tstride);
+    for (int i = 0; i < sa.N; i++) { sa.kind[i] = x->kind[i]; sa.eps[i] = x->eps[i]; sa.prob[i] = x->prob[i]; }
+}
+
+// the plan's tail: the device's figures, then *grid; where a block's LDS is more than the device's lds_cu, what
+// refuse(lds_cu) returns: the refusal in the call's own words
+template <typename R>
+int sp_plan_grid(const SpArgs& sa, int max_per_cu, int* grid, R refuse) {
+    int cus = 0, lds_cu = 0;
+    if (const int rc = cu_figures(&cus, &lds_cu)) return rc;
+    if (lds_cu > 0 && sa.lds_bytes > lds_cu) return refuse(lds_cu);
+    *grid = grid_for(cus, lds_cu, sa.lds_bytes, max_per_cu, sa.G);
+    return THRL_OK;
+}
+
+// the host-visible checks of both response calls behind their games, flags and reserved words (whose refusals an entry
+// point words itself): thrl_sampled_chain's in its order, with the agents and their gammas as
+// thrl_tuple_equilibrium_noise checks them; after_prices() is the place of the noise call's check of its nodes and band
+template <typename X, typename M>
+int sr_check_args(const thrl_cfg* c, const X* x, M after_prices) {
+    const int N = c->n_agents;
+    int rc;
+    if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = after_prices()) != THRL_OK) return rc;
+    if (!x->sweep_gamma && (rc = check_gamma(x->gamma, N, x->agents)) != THRL_OK) return rc;
+    if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
+    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    return THRL_OK;
+}
+
+// what both response calls hand to their kernels under one name: the agents, their gammas and the sweeps' limits, the
+// noise-free inputs, pi and the eleven outputs; A is SrArgs or SrnArgs
+template <typename A, typename X>
+void sr_copy_common(A& a, const X* x) {
+    for (int i = 0; i < a.sp.N; i++) a.gamma[i] = x->gamma[i];
+    a.agents = x->agents; a.max_sweeps = x->max_sweeps; a.eval_tol = x->eval_tol;
+    a.sp.eps_g = x->eps_g; a.sp.dpolicy = x->dpolicy; a.sp.grp_first = x->grp_first; a.sp.grp_perm = x->grp_perm;
+    a.sp.reward = x->reward;
+    a.sweep_gamma = x->sweep_gamma; a.pi = x->pi;
+    a.iters = x->iters; a.sweeps = x->sweeps; a.loss_all = x->loss_all;
+    a.loss_w = x->loss_w; a.gain_w = x->gain_w; a.v_w = x->v_w; a.br_prob_w = x->br_prob_w;
+    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+}
+
+}  // namespace
+
+extern "C" {
+
 int thrl_sampled_chain(const thrl_cfg* c, const thrl_sampled_chain_args* x, void* stream) {
     int rc = validate(c);
     if (rc) return rc;
@@ -825,11 +885,9 @@ int thrl_sampled_chain(const thrl_cfg* c, const thrl_sampled_chain_args* x, void
     if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
     SpArgs a;
     memset(&a, 0, sizeof(a));
-    a.G = x->n_games; a.N = N; a.T = x->n_tuples; a.D = x->n_prices;
+    sp_fill_head(a, c, x);
     a.max_iters = x->max_iters; a.start_tuple = (x->flags & THRL_SP_START_TUPLE) != 0;
     a.tol = x->tol;
-    tuple_strides(c, a.n_actions, a.tstride);
-    for (int i = 0; i < N; i++) { a.kind[i] = x->kind[i]; a.eps[i] = x->eps[i]; a.prob[i] = x->prob[i]; }
     thrl::sp_layout(a);                              // the working set of include/thrl.h
     if (a.lds_bytes > THRL_SP_MAX_LDS)
         return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_chain: %d bytes of LDS per game (T=%d, n_prices=%d), at most %d",
@@ -845,12 +903,12 @@ int thrl_sampled_chain(const thrl_cfg* c, const thrl_sampled_chain_args* x, void
     a.reward = x->reward; a.scaled = x->scaled; a.price = x->price;
     a.iters = x->iters; a.change = x->change; a.mass = x->mass; a.samp_reward = x->samp_reward;
     a.samp_action = x->samp_action; a.samp_price = x->samp_price; a.agree = x->agree; a.pi = x->pi;
-    int cus = 0, lds_cu = 0;
-    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
-    if (lds_cu > 0 && a.lds_bytes > lds_cu)
+    int grid = 0;
+    rc = sp_plan_grid(a, kSpMaxBlocksPerCu, &grid, [&](int lds_cu) {
         return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_chain: %d bytes of LDS per game (T=%d, n_prices=%d), the device has %d",
                     a.lds_bytes, a.T, a.D, lds_cu);
-    const int grid = grid_for(cus, lds_cu, a.lds_bytes, kSpMaxBlocksPerCu, a.G);
+    });
+    if (rc) return rc;
     const int e = thrl::launch_sampled_chain(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_sp_chain launch") : THRL_OK;
 }
@@ -879,13 +937,12 @@ int thrl_sampled_noise_chain(const thrl_cfg* c, const thrl_sampled_noise_chain_a
     thrl::SpnArgs a;
     memset(&a, 0, sizeof(a));
     SpArgs& sa = a.sp;
-    sa.G = x->n_games; sa.N = N; sa.T = x->n_tuples; sa.D = x->n_prices;
+    sp_fill_head(sa, c, x);
     sa.max_iters = x->max_iters; sa.start_tuple = (x->flags & THRL_SPN_START_TUPLE) != 0;
     sa.tol = x->tol;
     a.Jn = x->n_nodes; a.W = x->band_w; a.start_reset = (x->flags & THRL_SPN_START_RESET) != 0;
     a.noise_prob = x->noise_prob;
-    tuple_strides(c, sa.n_actions, sa.tstride);
-    for (int i = 0; i < N; i++) { sa.kind[i] = x->kind[i]; sa.eps[i] = x->eps[i]; sa.prob[i] = x->prob[i]; a.nprob[i] = x->nprob[i]; }
+    for (int i = 0; i < N; i++) a.nprob[i] = x->nprob[i];
     const int64_t lds = thrl::spn_layout(a);         // the working set of include/thrl.h
     if (lds > THRL_SP_MAX_LDS)
         return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_noise_chain: %lld bytes of LDS per game (T=%d, n_prices=%d, n_nodes=%d), at most %d",
@@ -905,12 +962,12 @@ int thrl_sampled_noise_chain(const thrl_cfg* c, const thrl_sampled_noise_chain_a
     sa.samp_action = x->samp_action; sa.samp_price = x->samp_price; sa.agree = x->agree; sa.pi = x->pi;
     a.noise_prob_g = x->noise_prob_g; a.npolicy = x->npolicy; a.band_lo = x->band_lo; a.band = x->band;
     a.noise_price = x->noise_price; a.noise_reward = x->noise_reward; a.node_w = x->node_w; a.max_jump = x->max_jump;
-    int cus = 0, lds_cu = 0;
-    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
-    if (lds_cu > 0 && sa.lds_bytes > lds_cu)
+    int grid = 0;
+    rc = sp_plan_grid(sa, kSpMaxBlocksPerCu, &grid, [&](int lds_cu) {
         return fail(THRL_ERR_UNSUPPORTED, "thrl_sampled_noise_chain: %d bytes of LDS per game (T=%d, n_prices=%d, n_nodes=%d), the device has %d",
                     sa.lds_bytes, sa.T, sa.D, a.Jn, lds_cu);
-    const int grid = grid_for(cus, lds_cu, sa.lds_bytes, kSpMaxBlocksPerCu, sa.G);
+    });
+    if (rc) return rc;
     const int e = thrl::launch_sampled_noise_chain(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_spn_jump / k_spn_chain launch") : THRL_OK;
 }
@@ -920,25 +977,16 @@ int thrl_sampled_response(const thrl_cfg* c, const thrl_sampled_response_args* x
     if (rc) return rc;
     if (!x) return fail(THRL_ERR_NULL, "args is NULL");
     const int N = c->n_agents;
-    // thrl_sampled_chain's checks in its order, with the agents and their gammas as thrl_tuple_equilibrium_noise checks
-    // them; every host-visible argument is checked, and the working set planned, before any pointer is looked at
+    // every host-visible argument is checked, and the working set planned, before any pointer is looked at
     if ((rc = check_games(x->n_games)) != THRL_OK) return rc;
     if (x->flags != 0) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
     for (int k = 0; k < 2; k++)
         if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
-    if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
-    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
-    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
-    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
-    if (!x->sweep_gamma && (rc = check_gamma(x->gamma, N, x->agents)) != THRL_OK) return rc;
-    if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
-    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    if ((rc = sr_check_args(c, x, [] { return (int)THRL_OK; })) != THRL_OK) return rc;
     thrl::SrArgs a;
     memset(&a, 0, sizeof(a));
     SpArgs& sa = a.sp;
-    sa.G = x->n_games; sa.N = N; sa.T = x->n_tuples; sa.D = x->n_prices;
-    tuple_strides(c, sa.n_actions, sa.tstride);
-    for (int i = 0; i < N; i++) { sa.kind[i] = x->kind[i]; sa.eps[i] = x->eps[i]; sa.prob[i] = x->prob[i]; a.gamma[i] = x->gamma[i]; }
+    sp_fill_head(sa, c, x);
     const int64_t lds = thrl::sr_layout(a);          // the working set of include/thrl_response.h
     // (the cells of this analysis are the distinct prices)
     if (lds > THRL_SR_MAX_LDS) return lds_refusal("thrl_sampled_response", lds, N, x->n_prices);
@@ -948,16 +996,11 @@ int thrl_sampled_response(const thrl_cfg* c, const thrl_sampled_response_args* x
     if (!x->iters || !x->sweeps || !x->n_diff || !x->loss_all || !x->loss_mean)
         return missing("iters / sweeps / n_diff / loss_all / loss_mean");
     if (x->pi && (!x->loss_w || !x->gain_w || !x->v_w || !x->br_prob_w)) return missing("with pi, loss_w / gain_w / v_w / br_prob_w");
-    a.agents = x->agents; a.max_sweeps = x->max_sweeps; a.eval_tol = x->eval_tol;
-    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm; sa.reward = x->reward;
-    a.sweep_gamma = x->sweep_gamma; a.pi = x->pi;
-    a.iters = x->iters; a.sweeps = x->sweeps; a.n_diff = x->n_diff; a.loss_all = x->loss_all; a.loss_mean = x->loss_mean;
-    a.loss_w = x->loss_w; a.gain_w = x->gain_w; a.v_w = x->v_w; a.br_prob_w = x->br_prob_w;
-    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
-    int cus = 0, lds_cu = 0;
-    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
-    if (lds_cu > 0 && sa.lds_bytes > lds_cu) return lds_refusal("thrl_sampled_response", lds, N, x->n_prices);
-    const int grid = grid_for(cus, lds_cu, sa.lds_bytes, kSrMaxBlocksPerCu, sa.G);
+    sr_copy_common(a, x);
+    a.n_diff = x->n_diff; a.loss_mean = x->loss_mean;
+    int grid = 0;
+    rc = sp_plan_grid(sa, kSrMaxBlocksPerCu, &grid, [&](int) { return lds_refusal("thrl_sampled_response", lds, N, x->n_prices); });
+    if (rc) return rc;
     const int e = thrl::launch_sampled_response(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_sr_response launch") : THRL_OK;
 }
@@ -974,25 +1017,15 @@ int thrl_sampled_response_noise(const thrl_cfg* c, const thrl_sampled_response_n
     if (x->flags != 0) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
     for (int k = 0; k < 2; k++)
         if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
-    if ((rc = check_agents_mask(x->agents, N)) != THRL_OK) return rc;
-    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
-    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
-    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
-    if ((rc = check_nodes_band(x->n_nodes, x->band_w)) != THRL_OK) return rc;
-    if (!x->sweep_gamma && (rc = check_gamma(x->gamma, N, x->agents)) != THRL_OK) return rc;
-    if ((rc = check_iters_tol(x->max_sweeps, x->eval_tol, "max_sweeps", "eval_tol")) != THRL_OK) return rc;
-    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    if ((rc = sr_check_args(c, x, [&] { return check_nodes_band(x->n_nodes, x->band_w); })) != THRL_OK) return rc;
     if ((rc = check_noise_prob(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
     if ((rc = check_node_limit("thrl_sampled_response_noise", x->n_nodes)) != THRL_OK) return rc;
     thrl::SrnArgs a;
     memset(&a, 0, sizeof(a));
     SpArgs& sa = a.sp;
-    sa.G = x->n_games; sa.N = N; sa.T = x->n_tuples; sa.D = x->n_prices;
+    sp_fill_head(sa, c, x);
     a.Jn = x->n_nodes; a.W = x->band_w;
-    tuple_strides(c, sa.n_actions, sa.tstride);
-    for (int i = 0; i < N; i++) {
-        sa.kind[i] = x->kind[i]; sa.eps[i] = x->eps[i]; sa.prob[i] = x->prob[i]; a.nprob[i] = x->nprob[i]; a.gamma[i] = x->gamma[i];
-    }
+    for (int i = 0; i < N; i++) a.nprob[i] = x->nprob[i];
     const int64_t lds = thrl::srn_layout(a);         // the working set of include/thrl_response_noise.h
     // (the cells of this analysis are its states: the distinct prices and the nodes)
     if (lds > THRL_SRN_MAX_LDS) return lds_refusal("thrl_sampled_response_noise", lds, N, x->n_prices + x->n_nodes);
@@ -1004,18 +1037,15 @@ int thrl_sampled_response_noise(const thrl_cfg* c, const thrl_sampled_response_n
         || !x->loss_nodes_mean)
         return missing("iters / sweeps / n_diff_prices / n_diff_nodes / loss_all / loss_prices_mean / loss_nodes_mean");
     if (x->pi && (!x->loss_w || !x->gain_w || !x->v_w || !x->br_prob_w)) return missing("with pi, loss_w / gain_w / v_w / br_prob_w");
-    a.agents = x->agents; a.max_sweeps = x->max_sweeps; a.eval_tol = x->eval_tol; a.noise_prob = x->noise_prob;
-    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm; sa.reward = x->reward;
-    a.sweep_gamma = x->sweep_gamma; a.noise_prob_g = x->noise_prob_g; a.pi = x->pi;
+    sr_copy_common(a, x);
+    a.noise_prob = x->noise_prob; a.noise_prob_g = x->noise_prob_g;
     a.npolicy = x->npolicy; a.band_lo = x->band_lo; a.band = x->band; a.noise_reward = x->noise_reward;
-    a.iters = x->iters; a.sweeps = x->sweeps; a.n_diff_prices = x->n_diff_prices; a.n_diff_nodes = x->n_diff_nodes;
-    a.loss_all = x->loss_all; a.loss_prices_mean = x->loss_prices_mean; a.loss_nodes_mean = x->loss_nodes_mean;
-    a.loss_w = x->loss_w; a.gain_w = x->gain_w; a.v_w = x->v_w; a.br_prob_w = x->br_prob_w;
-    a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
-    int cus = 0, lds_cu = 0;
-    if ((rc = cu_figures(&cus, &lds_cu)) != THRL_OK) return rc;
-    if (lds_cu > 0 && sa.lds_bytes > lds_cu) return lds_refusal("thrl_sampled_response_noise", lds, N, x->n_prices + x->n_nodes);
-    const int grid = grid_for(cus, lds_cu, sa.lds_bytes, kSrnMaxBlocksPerCu, sa.G);
+    a.n_diff_prices = x->n_diff_prices; a.n_diff_nodes = x->n_diff_nodes;
+    a.loss_prices_mean = x->loss_prices_mean; a.loss_nodes_mean = x->loss_nodes_mean;
+    int grid = 0;
+    rc = sp_plan_grid(sa, kSrnMaxBlocksPerCu, &grid,
+                      [&](int) { return lds_refusal("thrl_sampled_response_noise", lds, N, x->n_prices + x->n_nodes); });
+    if (rc) return rc;
     const int e = thrl::launch_sampled_response_noise(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_srn_response launch") : THRL_OK;
 }

@@ -1,5 +1,7 @@
 // thrl_sampled.h -- launch arguments of sampled play (thrl_sampled_chain, include/thrl.h).  thrl_api_analysis.hip validates;
-// sp_layout() is the one place the LDS layout is written down; thrl_sampled.hip holds the kernel.
+// sp_layout() is the one place the LDS layout is written down; thrl_sampled.hip holds the kernel.  Also what the four
+// calls on sampled play share on the host: the head of the two response layouts (sr_layout_head) and the launch of a
+// block kernel in its <2> or <kSpMaxA> form (sp_launch).
 #pragma once
 #ifndef THRL_SP_HOST_BUILD
 #include <hip/hip_runtime.h>
@@ -42,9 +44,10 @@ struct SpArgs {
     double *change, *mass, *samp_reward, *samp_action, *samp_price, *agree, *pi;
 };
 
+inline int64_t r16(int64_t x) { return (x + 15) & ~(int64_t)15; }   // every LDS array starts on a multiple of 16
+
 // the LDS layout of include/thrl.h's working set; returns the bytes of a block
 inline int32_t sp_layout(SpArgs& a) {
-    auto r16 = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
     int64_t off = 0;
     a.o_ma = (int32_t)off; off += r16(8 * (int64_t)a.T);
     a.o_mb = (int32_t)off; off += r16(8 * (int64_t)a.T);
@@ -62,8 +65,48 @@ inline int32_t sp_layout(SpArgs& a) {
     return a.lds_bytes;
 }
 
+// The head of sr_layout and srn_layout (Args = SrArgs, SrnArgs) over S states: five arrays of 8 S (o_va, o_vb, o_vpi, o_zm,
+// o_si), two of 8 T (o_u, o_rt), the agents' rows at the D prices, first, perm, trow, and sigma and modal of 2 S.  Returns
+// the offset behind them, where each layout's own tail begins.
+template <typename Args>
+inline int64_t sr_layout_head(Args& a, int64_t S) {
+    const int64_t T = a.sp.T, D = a.sp.D;
+    int64_t off = 0;
+    a.o_va = (int32_t)off; off += r16(8 * S);
+    a.o_vb = (int32_t)off; off += r16(8 * S);
+    a.o_vpi = (int32_t)off; off += r16(8 * S);
+    a.o_zm = (int32_t)off; off += r16(8 * S);
+    a.o_si = (int32_t)off; off += r16(8 * S);
+    a.o_u = (int32_t)off; off += r16(8 * T);
+    a.o_rt = (int32_t)off; off += r16(8 * T);
+    for (int i = 0; i < a.sp.N; i++) {
+        a.sp.o_row[i] = (int32_t)off;
+        off += r16(a.sp.kind[i] == 0 ? 2 * D : 4 * D * a.sp.n_actions[i]);
+    }
+    a.sp.o_first = (int32_t)off; off += r16(2 * (D + 1));
+    a.sp.o_perm = (int32_t)off; off += r16(2 * T);
+    a.o_trow = (int32_t)off; off += r16(2 * T);
+    a.o_sigma = (int32_t)off; off += r16(2 * S);
+    a.o_modal = (int32_t)off; off += r16(2 * S);
+    return off;
+}
+
 #ifndef THRL_SP_HOST_BUILD
 int launch_sampled_chain(const SpArgs& a, int grid, hipStream_t s);
+
+// Launches a block kernel of sampled play on `grid` blocks of kSpBlock threads with sp.lds_bytes of dynamic LDS: k2 with
+// two agents, k8 with more.  Above 64 KB the kernel is first allowed that much.  Returns the HIP error, 0 for none.
+template <typename Args>
+inline int sp_launch(void (*k2)(const Args), void (*k8)(const Args), const Args& a, const SpArgs& sp, int grid, hipStream_t s) {
+    void (*const k)(const Args) = sp.N <= 2 ? k2 : k8;
+    if (sp.lds_bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 sp.lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kSpBlock), (size_t)sp.lds_bytes, s, a);
+    return (int)hipGetLastError();
+}
 #endif
 
 }  // namespace thrl

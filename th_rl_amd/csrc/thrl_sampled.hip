@@ -126,14 +126,7 @@ __global__ void __launch_bounds__(kSpBlock) k_sp_chain(const SpArgs a) {
 
 #ifndef THRL_SP_HOST_BUILD
 int launch_sampled_chain(const SpArgs& a, int grid, hipStream_t s) {
-    const void* fn = a.N <= 2 ? reinterpret_cast<const void*>(k_sp_chain<2>) : reinterpret_cast<const void*>(k_sp_chain<kSpMaxA>);
-    if (a.lds_bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (a.N <= 2) hipLaunchKernelGGL(k_sp_chain<2>, dim3(grid), dim3(kSpBlock), (size_t)a.lds_bytes, s, a);
-    else hipLaunchKernelGGL(k_sp_chain<kSpMaxA>, dim3(grid), dim3(kSpBlock), (size_t)a.lds_bytes, s, a);
-    return (int)hipGetLastError();
+    return sp_launch(k_sp_chain<2>, k_sp_chain<kSpMaxA>, a, a, grid, s);
 }
 #endif
 

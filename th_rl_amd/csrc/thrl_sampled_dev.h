@@ -1,6 +1,9 @@
 // thrl_sampled_dev.h -- the device functions k_sp_chain (thrl_sampled.hip) and k_spn_chain (thrl_sampled_noise.hip)
 // share: the per-game constants, the staging of the distinct-price rows with their normaliser Z(d), the M / W pass, the
-// ordered sum over the distinct prices for one output tuple and the block's maximum.  What all four chain kernels share
+// ordered sum over the distinct prices for one output tuple and the block's maximum.  The two response kernels
+// (k_sr_response, k_srn_response) take the constants, the epsilon check, the game's staging and the maximum from here;
+// what those two share beyond that is thrl_response_dev.h's, and the launch of all four is thrl_sampled.h's sp_launch.
+// What all four chain kernels share
 // (the unsolved outputs, the lazy update, the read-back and the final store) is thrl_chain_dev.h's.  Everything sits in namespace thrl's
 // anonymous namespace, once per including file; with THRL_SP_HOST_BUILD the host harness supplies __device__, __syncthreads() and
 // the rounded operations.

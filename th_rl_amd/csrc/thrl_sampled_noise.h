@@ -33,7 +33,6 @@ struct SpnArgs {
 // the LDS layout of include/thrl.h's working set: sp_layout's arrays, then V, the QTable agents' node entries and the
 // networks' double-buffered tiles; returns the bytes of a block (also left in a.sp.lds_bytes)
 inline int64_t spn_layout(SpnArgs& a) {
-    auto r16 = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
     int64_t off = sp_layout(a.sp);
     a.o_v = (int32_t)off; off += r16(8 * (int64_t)a.Jn);
     for (int i = 0; i < a.sp.N; i++) {

@@ -355,15 +355,7 @@ int launch_sampled_noise_chain(const SpnArgs& a, int grid, hipStream_t s) {
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
-    const void* fn = a.sp.N <= 2 ? reinterpret_cast<const void*>(k_spn_chain<2>)
-                                 : reinterpret_cast<const void*>(k_spn_chain<kSpMaxA>);
-    if (a.sp.lds_bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.sp.lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (a.sp.N <= 2) hipLaunchKernelGGL(k_spn_chain<2>, dim3(grid), dim3(kSpBlock), (size_t)a.sp.lds_bytes, s, a);
-    else hipLaunchKernelGGL(k_spn_chain<kSpMaxA>, dim3(grid), dim3(kSpBlock), (size_t)a.sp.lds_bytes, s, a);
-    return (int)hipGetLastError();
+    return sp_launch(k_spn_chain<2>, k_spn_chain<kSpMaxA>, a, a.sp, grid, s);
 }
 #endif
 

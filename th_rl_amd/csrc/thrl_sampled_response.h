@@ -33,31 +33,14 @@ struct SrArgs {
 // clamped to INT32_MAX).  team: the largest power of two with team * D <= 256 whose staging of 8 D max_i A_i bytes stays
 // within kSrMaxTeamBytes, else 1 (no staging).
 inline int64_t sr_layout(SrArgs& a) {
-    auto r16 = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
-    const int64_t T = a.sp.T, D = a.sp.D;
+    const int64_t D = a.sp.D;
     int64_t maxA = 1;
     for (int i = 0; i < a.sp.N; i++) maxA = a.sp.n_actions[i] > maxA ? a.sp.n_actions[i] : maxA;
     int team = 1;
     while ((int64_t)team * 2 * D <= kSpBlock && team * 2 <= maxA) team *= 2;
     if (8 * D * maxA > kSrMaxTeamBytes) team = 1;
     a.team = team;
-    int64_t off = 0;
-    a.o_va = (int32_t)off; off += r16(8 * D);
-    a.o_vb = (int32_t)off; off += r16(8 * D);
-    a.o_vpi = (int32_t)off; off += r16(8 * D);
-    a.o_zm = (int32_t)off; off += r16(8 * D);
-    a.o_si = (int32_t)off; off += r16(8 * D);
-    a.o_u = (int32_t)off; off += r16(8 * T);
-    a.o_rt = (int32_t)off; off += r16(8 * T);
-    for (int i = 0; i < a.sp.N; i++) {
-        a.sp.o_row[i] = (int32_t)off;
-        off += r16(a.sp.kind[i] == 0 ? 2 * D : 4 * D * a.sp.n_actions[i]);
-    }
-    a.sp.o_first = (int32_t)off; off += r16(2 * (D + 1));
-    a.sp.o_perm = (int32_t)off; off += r16(2 * T);
-    a.o_trow = (int32_t)off; off += r16(2 * T);
-    a.o_sigma = (int32_t)off; off += r16(2 * D);
-    a.o_modal = (int32_t)off; off += r16(2 * D);
+    int64_t off = sr_layout_head(a, D);
     a.sp.o_prod = (int32_t)off; off += 8 * kSpBlock;
     a.o_q = (int32_t)off; off += team > 1 ? r16(8 * D * maxA) : 0;
     a.sp.o_cst = (int32_t)off; off += 256;

@@ -11,12 +11,12 @@
 //   through a staging array and the team's first thread adds them up in order.  A sweep of a deterministic strategy needs
 //   one Q_V(d, sigma(d)) per price: a thread per price, 1 / A_i of the work.  The largest change is a maximum, whose
 //   order is free: sp_block_max.  The ordered output sums are one lane each over the D terms.
-//   The staging, Z's factors and the block maximum are thrl_sampled_dev.h's; the margin, the first maximum and the
-//   relative loss are thrl_solve_dev.h's; sr_prob and sr_q are thrl_response_dev.h's, shared with k_srn_response.
+//   Here are the sweeps and the improvement step with their team split, the agent's rewards and the weights M(d).  The
+//   game's staging and the block maximum are thrl_sampled_dev.h's; the margin, the first maximum and the relative loss
+//   are thrl_solve_dev.h's; sr_prob and sr_q, the staging of the grouping, the outputs of a refused game and of an
+//   unsolved agent, the per-price setup, a solved price's stores, the loss sums and the four weighted sums are
+//   thrl_response_dev.h's, shared with k_srn_response; the launch is thrl_sampled.h's sp_launch.
 //   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
-#include "thrl_sampled_dev.h"
-#include "thrl_sampled_response.h"
-#include "thrl_solve_dev.h"
 #include "thrl_response_dev.h"
 
 namespace thrl {
@@ -42,36 +42,13 @@ __device__ __forceinline__ void sr_block(const SrArgs& a, unsigned char* s_mem, 
     uint16_t* modal = reinterpret_cast<uint16_t*>(s_mem + a.o_modal);
     double* prod = reinterpret_cast<double*>(s_mem + sp.o_prod);      // [256] the threads' maxima
     SpCst* cst = reinterpret_cast<SpCst*>(s_mem + sp.o_cst);
-    const double nan = __builtin_nan("");
 
-    // ---- the grouping of the tuples by price: per config, staged once; no entry leads out of bounds
-    for (int d = tid; d <= D; d += kSpBlock) first[d] = (uint16_t)min(max(sp.grp_first[d], 0), T);
-    for (int t = tid; t < T; t += kSpBlock) {
-        perm[t] = (uint16_t)min(max(sp.grp_perm[t], 0), T - 1);
-        trow[t] = 0;
-    }
-    __syncthreads();
-    for (int d = tid; d < D; d += kSpBlock) {
-        const int e = first[d + 1];
-        for (int s = first[d]; s < e; s++) trow[perm[s]] = (uint16_t)d;
-    }
+    sr_stage_grouping(sp, first, perm, trow, tid);       // per config, staged once
 
     for (int64_t g = bid; g < G; g += nblk) {
         if (!sp_eps_ok(sp, g)) {                         // block-uniform: no agent of this game is solved, zeros
-            for (int i = 0; i < N; i++) {
-                if (!((a.agents >> i) & 1)) continue;
-                const int64_t o = (int64_t)i * G + g;
-                if (tid == 0) {
-                    a.iters[o] = -1; a.sweeps[o] = 0; a.n_diff[o] = 0;
-                    a.loss_all[o] = 0.0; a.loss_mean[o] = 0.0;
-                    if (a.pi) { a.loss_w[o] = 0.0; a.gain_w[o] = 0.0; a.v_w[o] = 0.0; a.br_prob_w[o] = 0.0; }
-                }
-                for (int d = tid; d < D; d += kSpBlock) {
-                    if (a.br_policy) a.br_policy[o * D + d] = 0;
-                    if (a.v_opt) a.v_opt[o * D + d] = 0.0;
-                    if (a.v_pi) a.v_pi[o * D + d] = 0.0;
-                }
-            }
+            for (int i = 0; i < N; i++)
+                if ((a.agents >> i) & 1) sr_flat_outputs(a, (int64_t)i * G + g, D, 0.0, 0, nullptr, tid);
             continue;
         }
         __syncthreads();                                 // the game before is read to its end; the grouping is staged
@@ -87,34 +64,9 @@ __device__ __forceinline__ void sr_block(const SrArgs& a, unsigned char* s_mem, 
             const double gam = a.sweep_gamma ? a.sweep_gamma[o] : a.gamma[i];
 
             // ---- per price: Z_-i, S_i and the modal action; per tuple: the agent's reward
-            for (int d = tid; d < D; d += kSpBlock) {
-                double z = 1.0, Sown = 1.0;
-                bool have = false;
-                for (int j = 0; j < N; j++) {
-                    double S = 1.0;
-                    if (sp.kind[j] != 0) {
-                        const int Aj = sp.n_actions[j];
-                        const float* rf = reinterpret_cast<const float*>(s_mem + sp.o_row[j]) + d * Aj;
-                        S = 0.0;
-                        for (int k = 0; k < Aj; k++) S = __dadd_rn(S, (double)rf[k]);
-                    }
-                    if (j == i) { Sown = S; continue; }
-                    z = have ? __dmul_rn(z, S) : S;
-                    have = true;
-                }
-                Zm[d] = z;
-                Si[d] = Sown;
-                int mo;
-                if (sp.kind[i] == 0) {
-                    mo = reinterpret_cast<const uint16_t*>(s_mem + sp.o_row[i])[d];
-                } else {
-                    double bv;
-                    mo = first_max(A, [&](int k) THRL_SOLVE_INLINE { return sr_prob(sp, s_mem, cst, i, d, k); }, bv);
-                }
-                modal[d] = (uint16_t)mo;
-                sigma[d] = (uint16_t)mo;
-                Va[d] = 0.0;
-            }
+            sr_setup_states(sp, i, D, Zm, Si, modal, sigma, Va, tid,
+                            [&](int j, int d, int k) THRL_SOLVE_INLINE { return sr_prob(sp, s_mem, cst, j, d, k); },
+                            [&](int d) THRL_SOLVE_INLINE { return (int)reinterpret_cast<const uint16_t*>(s_mem + sp.o_row[i])[d]; });
             for (int t = tid; t < T; t += kSpBlock) Rt[t] = sp.reward[(int64_t)i * T + t];
 
             double* V = Va;                              // the last iterate
@@ -211,16 +163,7 @@ __device__ __forceinline__ void sr_block(const SrArgs& a, unsigned char* s_mem, 
             __syncthreads();                             // Vpi, V and sigma of every thread
 
             if (!solved) {                               // a gamma outside [0, 1), or capped: NaN, br_policy = the modal action
-                if (tid == 0) {
-                    a.iters[o] = -1; a.sweeps[o] = sweeps; a.n_diff[o] = 0;
-                    a.loss_all[o] = nan; a.loss_mean[o] = nan;
-                    if (a.pi) { a.loss_w[o] = nan; a.gain_w[o] = nan; a.v_w[o] = nan; a.br_prob_w[o] = nan; }
-                }
-                for (int d = tid; d < D; d += kSpBlock) {
-                    if (a.br_policy) a.br_policy[o * D + d] = modal[d];
-                    if (a.v_opt) a.v_opt[o * D + d] = nan;
-                    if (a.v_pi) a.v_pi[o * D + d] = nan;
-                }
+                sr_flat_outputs(a, o, D, __builtin_nan(""), sweeps, modal, tid);
                 __syncthreads();
                 continue;
             }
@@ -229,11 +172,7 @@ __device__ __forceinline__ void sr_block(const SrArgs& a, unsigned char* s_mem, 
             double* loss = Vn;
             const double* __restrict__ pig = a.pi ? a.pi + g * T : nullptr;
             for (int d = tid; d < D; d += kSpBlock) {
-                const double vs = V[d], vp = Vpi[d];
-                loss[d] = rel_loss(vs, vp);
-                if (a.br_policy) a.br_policy[o * D + d] = sigma[d];
-                if (a.v_opt) a.v_opt[o * D + d] = vs;
-                if (a.v_pi) a.v_pi[o * D + d] = vp;
+                sr_store_state(a, o, D, d, V, Vpi, sigma, loss);
                 if (pig) {
                     double M = 0.0;
                     const int e = first[d + 1];
@@ -245,27 +184,12 @@ __device__ __forceinline__ void sr_block(const SrArgs& a, unsigned char* s_mem, 
             if (tid == 0) {
                 double lmax = -__builtin_huge_val(), acc = 0.0;
                 int nd = 0;
-                for (int d = 0; d < D; d++) {
-                    const double l = loss[d];
-                    if (l > lmax) lmax = l;
-                    acc = __dadd_rn(acc, l);
-                    nd += sigma[d] != modal[d] ? 1 : 0;
-                }
-                a.iters[o] = iters; a.sweeps[o] = sweeps; a.n_diff[o] = nd;
-                a.loss_all[o] = lmax;
-                a.loss_mean[o] = __ddiv_rn(acc, (double)D);
-            } else if (pig && tid >= 64 && tid < 68) {   // a lane of another wave for each weighted sum
-                double acc = 0.0;
-                for (int d = 0; d < D; d++) {
-                    const double M = U[d];
-                    double term;
-                    if (tid == 64) term = __dmul_rn(M, loss[d]);
-                    else if (tid == 65) term = __dmul_rn(M, __dsub_rn(V[d], Vpi[d]));
-                    else if (tid == 66) term = __dmul_rn(M, Vpi[d]);
-                    else term = __ddiv_rn(__dmul_rn(M, sr_prob(sp, s_mem, cst, i, d, sigma[d])), Si[d]);
-                    acc = __dadd_rn(acc, term);
-                }
-                (tid == 64 ? a.loss_w : tid == 65 ? a.gain_w : tid == 66 ? a.v_w : a.br_prob_w)[o] = acc;
+                sr_loss_range(loss, sigma, modal, 0, D, lmax, acc, nd);
+                a.iters[o] = iters; a.sweeps[o] = sweeps;
+                sr_summary(a, o, lmax, nd, acc, 0, 0.0);
+            } else if (pig) {                            // the weights M(d) are in U
+                sr_weighted_sums(a, o, D, U, loss, V, Vpi, Si, sigma, tid,
+                                 [&](int d, int k) THRL_SOLVE_INLINE { return sr_prob(sp, s_mem, cst, i, d, k); });
             }
             __syncthreads();                             // loss / V / sigma reads before the next agent's writes
         }
@@ -284,15 +208,7 @@ __global__ void __launch_bounds__(kSpBlock) k_sr_response(const SrArgs a) {
 
 #ifndef THRL_SP_HOST_BUILD
 int launch_sampled_response(const SrArgs& a, int grid, hipStream_t s) {
-    const int lds = a.sp.lds_bytes;
-    const void* fn = a.sp.N <= 2 ? reinterpret_cast<const void*>(k_sr_response<2>) : reinterpret_cast<const void*>(k_sr_response<kSpMaxA>);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (a.sp.N <= 2) hipLaunchKernelGGL(k_sr_response<2>, dim3(grid), dim3(kSpBlock), (size_t)lds, s, a);
-    else hipLaunchKernelGGL(k_sr_response<kSpMaxA>, dim3(grid), dim3(kSpBlock), (size_t)lds, s, a);
-    return (int)hipGetLastError();
+    return sp_launch(k_sr_response<2>, k_sr_response<kSpMaxA>, a, a.sp, grid, s);
 }
 #endif
 

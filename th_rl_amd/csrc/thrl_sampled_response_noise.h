@@ -42,25 +42,8 @@ struct SrnArgs {
 // returns the bytes of a block (also left in a.sp.lds_bytes, clamped to INT32_MAX).  The networks' node rows are not part
 // of it: they stay in global memory.
 inline int64_t srn_layout(SrnArgs& a) {
-    auto r16 = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
-    const int64_t T = a.sp.T, D = a.sp.D, Jn = a.Jn, S = D + Jn;
-    int64_t off = 0;
-    a.o_va = (int32_t)off; off += r16(8 * S);
-    a.o_vb = (int32_t)off; off += r16(8 * S);
-    a.o_vpi = (int32_t)off; off += r16(8 * S);
-    a.o_zm = (int32_t)off; off += r16(8 * S);
-    a.o_si = (int32_t)off; off += r16(8 * S);
-    a.o_u = (int32_t)off; off += r16(8 * T);
-    a.o_rt = (int32_t)off; off += r16(8 * T);
-    for (int i = 0; i < a.sp.N; i++) {
-        a.sp.o_row[i] = (int32_t)off;
-        off += r16(a.sp.kind[i] == 0 ? 2 * D : 4 * D * a.sp.n_actions[i]);
-    }
-    a.sp.o_first = (int32_t)off; off += r16(2 * (D + 1));
-    a.sp.o_perm = (int32_t)off; off += r16(2 * T);
-    a.o_trow = (int32_t)off; off += r16(2 * T);
-    a.o_sigma = (int32_t)off; off += r16(2 * S);
-    a.o_modal = (int32_t)off; off += r16(2 * S);
+    const int64_t Jn = a.Jn;
+    int64_t off = sr_layout_head(a, a.sp.D + Jn);
     for (int i = 0; i < a.sp.N; i++) {
         a.o_nrow[i] = 0;
         if (a.sp.kind[i] == 0) { a.o_nrow[i] = (int32_t)off; off += r16(2 * Jn); }

@@ -13,12 +13,13 @@
 //   node rows (4 Jn A_j bytes, more than the rest of the working set) stay in global memory and are read every sweep:
 //   the threads of a wave own adjacent nodes, whose rows are adjacent.  The largest change is a maximum over all S
 //   states (sp_block_max).  The ordered output sums are one lane each over the S terms, prices first.
-//   The staging and the block maximum are thrl_sampled_dev.h's, sr_prob / sr_q / sr_q_of thrl_response_dev.h's, the
-//   margin, the first maximum, the relative loss and the band's limits thrl_solve_dev.h's.  Nothing in the body is
-//   wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
-#include "thrl_sampled_dev.h"
-#include "thrl_sampled_response_noise.h"
-#include "thrl_solve_dev.h"
+//   Here are a state's probabilities (a price's or a node's), the one loop of the sweeps with its band walk, the agent's
+//   rewards under noise and the weights w(s).  The game's staging and the block maximum are thrl_sampled_dev.h's; the
+//   margin, the relative loss and the band's limits thrl_solve_dev.h's; sr_prob / sr_q / sr_q_of, the staging of the
+//   grouping, the outputs of a refused game and of an unsolved agent, the per-state setup, a solved state's stores, the
+//   loss sums and the four weighted sums are thrl_response_dev.h's, shared with k_sr_response; the launch is
+//   thrl_sampled.h's sp_launch.  Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as
+//   256 host threads with barriers.
 #include "thrl_response_dev.h"
 
 namespace thrl {
@@ -76,37 +77,14 @@ __device__ __forceinline__ void srn_block(const SrnArgs& a, unsigned char* s_mem
     uint16_t* modal = reinterpret_cast<uint16_t*>(s_mem + a.o_modal); // [S]
     double* prod = reinterpret_cast<double*>(s_mem + sp.o_prod);      // [256] the threads' maxima
     SpCst* cst = reinterpret_cast<SpCst*>(s_mem + sp.o_cst);
-    const double nan = __builtin_nan("");
 
-    // ---- the grouping of the tuples by price: per config, staged once; no entry leads out of bounds
-    for (int d = tid; d <= D; d += kSpBlock) first[d] = (uint16_t)min(max(sp.grp_first[d], 0), T);
-    for (int t = tid; t < T; t += kSpBlock) {
-        perm[t] = (uint16_t)min(max(sp.grp_perm[t], 0), T - 1);
-        trow[t] = 0;
-    }
-    __syncthreads();
-    for (int d = tid; d < D; d += kSpBlock) {
-        const int e = first[d + 1];
-        for (int s = first[d]; s < e; s++) trow[perm[s]] = (uint16_t)d;
-    }
+    sr_stage_grouping(sp, first, perm, trow, tid);       // per config, staged once
 
     for (int64_t g = bid; g < G; g += nblk) {
         const double p = a.noise_prob_g ? a.noise_prob_g[g] : a.noise_prob;
         if (!(sp_eps_ok(sp, g) && p > 0.0 && p <= 1.0)) { // block-uniform: no agent of this game is solved, zeros
-            for (int i = 0; i < N; i++) {
-                if (!((a.agents >> i) & 1)) continue;
-                const int64_t o = (int64_t)i * G + g;
-                if (tid == 0) {
-                    a.iters[o] = -1; a.sweeps[o] = 0; a.n_diff_prices[o] = 0; a.n_diff_nodes[o] = 0;
-                    a.loss_all[o] = 0.0; a.loss_prices_mean[o] = 0.0; a.loss_nodes_mean[o] = 0.0;
-                    if (a.pi) { a.loss_w[o] = 0.0; a.gain_w[o] = 0.0; a.v_w[o] = 0.0; a.br_prob_w[o] = 0.0; }
-                }
-                for (int s = tid; s < S; s += kSpBlock) {
-                    if (a.br_policy) a.br_policy[o * S + s] = 0;
-                    if (a.v_opt) a.v_opt[o * S + s] = 0.0;
-                    if (a.v_pi) a.v_pi[o * S + s] = 0.0;
-                }
-            }
+            for (int i = 0; i < N; i++)
+                if ((a.agents >> i) & 1) sr_flat_outputs(a, (int64_t)i * G + g, S, 0.0, 0, nullptr, tid);
             continue;
         }
         const double q = __dsub_rn(1.0, p);
@@ -130,34 +108,12 @@ __device__ __forceinline__ void srn_block(const SrnArgs& a, unsigned char* s_mem
             const double gam = a.sweep_gamma ? a.sweep_gamma[o] : a.gamma[i];
 
             // ---- per state: Z_-i, S_i and the modal action; per tuple: the agent's reward under noise
-            for (int s = tid; s < S; s += kSpBlock) {
-                double z = 1.0, Sown = 1.0;
-                bool have = false;
-                for (int j = 0; j < N; j++) {
-                    double Sj = 1.0;
-                    if (sp.kind[j] != 0) {
-                        const int Aj = sp.n_actions[j];
-                        Sj = 0.0;
-                        for (int k = 0; k < Aj; k++) Sj = __dadd_rn(Sj, srn_prob(a, s_mem, cst, g, j, s, k));
-                    }
-                    if (j == i) { Sown = Sj; continue; }
-                    z = have ? __dmul_rn(z, Sj) : Sj;
-                    have = true;
-                }
-                Zm[s] = z;
-                Si[s] = Sown;
-                int mo;
-                if (sp.kind[i] == 0) {
-                    mo = s < D ? reinterpret_cast<const uint16_t*>(s_mem + sp.o_row[i])[s]
-                               : reinterpret_cast<const uint16_t*>(s_mem + a.o_nrow[i])[s - D];
-                } else {
-                    double bv;
-                    mo = first_max(A, [&](int k) THRL_SOLVE_INLINE { return srn_prob(a, s_mem, cst, g, i, s, k); }, bv);
-                }
-                modal[s] = (uint16_t)mo;
-                sigma[s] = (uint16_t)mo;
-                Va[s] = 0.0;
-            }
+            sr_setup_states(sp, i, S, Zm, Si, modal, sigma, Va, tid,
+                            [&](int j, int s, int k) THRL_SOLVE_INLINE { return srn_prob(a, s_mem, cst, g, j, s, k); },
+                            [&](int s) THRL_SOLVE_INLINE {
+                                return (int)(s < D ? reinterpret_cast<const uint16_t*>(s_mem + sp.o_row[i])[s]
+                                                   : reinterpret_cast<const uint16_t*>(s_mem + a.o_nrow[i])[s - D]);
+                            });
             for (int t = tid; t < T; t += kSpBlock)
                 Rt[t] = __dadd_rn(__dmul_rn(q, sp.reward[(int64_t)i * T + t]), __dmul_rn(p, a.noise_reward[(int64_t)i * T + t]));
 
@@ -246,16 +202,7 @@ __device__ __forceinline__ void srn_block(const SrnArgs& a, unsigned char* s_mem
             __syncthreads();                             // Vpi, V and sigma of every thread
 
             if (!solved) {                               // a gamma outside [0, 1), or capped: NaN, br_policy = the modal action
-                if (tid == 0) {
-                    a.iters[o] = -1; a.sweeps[o] = sweeps; a.n_diff_prices[o] = 0; a.n_diff_nodes[o] = 0;
-                    a.loss_all[o] = nan; a.loss_prices_mean[o] = nan; a.loss_nodes_mean[o] = nan;
-                    if (a.pi) { a.loss_w[o] = nan; a.gain_w[o] = nan; a.v_w[o] = nan; a.br_prob_w[o] = nan; }
-                }
-                for (int s = tid; s < S; s += kSpBlock) {
-                    if (a.br_policy) a.br_policy[o * S + s] = modal[s];
-                    if (a.v_opt) a.v_opt[o * S + s] = nan;
-                    if (a.v_pi) a.v_pi[o * S + s] = nan;
-                }
+                sr_flat_outputs(a, o, S, __builtin_nan(""), sweeps, modal, tid);
                 __syncthreads();
                 continue;
             }
@@ -268,11 +215,7 @@ __device__ __forceinline__ void srn_block(const SrnArgs& a, unsigned char* s_mem
             double* wgt = Zm;
             const double* __restrict__ pig = a.pi ? a.pi + g * T : nullptr;
             for (int s = tid; s < S; s += kSpBlock) {
-                const double vs = V[s], vp = Vpi[s];
-                loss[s] = rel_loss(vs, vp);
-                if (a.br_policy) a.br_policy[o * S + s] = sigma[s];
-                if (a.v_opt) a.v_opt[o * S + s] = vs;
-                if (a.v_pi) a.v_pi[o * S + s] = vp;
+                sr_store_state(a, o, S, s, V, Vpi, sigma, loss);
                 if (!pig) continue;
                 if (s < D) {                             // w(d) = q M(d)
                     double M = 0.0;
@@ -293,34 +236,13 @@ __device__ __forceinline__ void srn_block(const SrnArgs& a, unsigned char* s_mem
             if (tid == 0) {
                 double lmax = -__builtin_huge_val(), accd = 0.0, accn = 0.0;
                 int ndd = 0, ndn = 0;
-                for (int s = 0; s < D; s++) {
-                    const double l = loss[s];
-                    if (l > lmax) lmax = l;
-                    accd = __dadd_rn(accd, l);
-                    ndd += sigma[s] != modal[s] ? 1 : 0;
-                }
-                for (int s = D; s < S; s++) {
-                    const double l = loss[s];
-                    if (l > lmax) lmax = l;
-                    accn = __dadd_rn(accn, l);
-                    ndn += sigma[s] != modal[s] ? 1 : 0;
-                }
-                a.iters[o] = iters; a.sweeps[o] = sweeps; a.n_diff_prices[o] = ndd; a.n_diff_nodes[o] = ndn;
-                a.loss_all[o] = lmax;
-                a.loss_prices_mean[o] = __ddiv_rn(accd, (double)D);
-                a.loss_nodes_mean[o] = __ddiv_rn(accn, (double)Jn);
-            } else if (pig && tid >= 64 && tid < 68) {   // a lane of another wave for each weighted sum
-                double acc = 0.0;
-                for (int s = 0; s < S; s++) {
-                    const double w = wgt[s];
-                    double term;
-                    if (tid == 64) term = __dmul_rn(w, loss[s]);
-                    else if (tid == 65) term = __dmul_rn(w, __dsub_rn(V[s], Vpi[s]));
-                    else if (tid == 66) term = __dmul_rn(w, Vpi[s]);
-                    else term = __ddiv_rn(__dmul_rn(w, srn_prob(a, s_mem, cst, g, i, s, sigma[s])), Si[s]);
-                    acc = __dadd_rn(acc, term);
-                }
-                (tid == 64 ? a.loss_w : tid == 65 ? a.gain_w : tid == 66 ? a.v_w : a.br_prob_w)[o] = acc;
+                sr_loss_range(loss, sigma, modal, 0, D, lmax, accd, ndd);
+                sr_loss_range(loss, sigma, modal, D, S, lmax, accn, ndn);
+                a.iters[o] = iters; a.sweeps[o] = sweeps;
+                sr_summary(a, o, lmax, ndd, accd, ndn, accn);
+            } else if (pig) {
+                sr_weighted_sums(a, o, S, wgt, loss, V, Vpi, Si, sigma, tid,
+                                 [&](int s, int k) THRL_SOLVE_INLINE { return srn_prob(a, s_mem, cst, g, i, s, k); });
             }
             __syncthreads();                             // loss / V / sigma reads before the next agent's writes
         }
@@ -339,15 +261,7 @@ __global__ void __launch_bounds__(kSpBlock) k_srn_response(const SrnArgs a) {
 
 #ifndef THRL_SP_HOST_BUILD
 int launch_sampled_response_noise(const SrnArgs& a, int grid, hipStream_t s) {
-    const int lds = a.sp.lds_bytes;
-    const void* fn = a.sp.N <= 2 ? reinterpret_cast<const void*>(k_srn_response<2>) : reinterpret_cast<const void*>(k_srn_response<kSpMaxA>);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (a.sp.N <= 2) hipLaunchKernelGGL(k_srn_response<2>, dim3(grid), dim3(kSpBlock), (size_t)lds, s, a);
-    else hipLaunchKernelGGL(k_srn_response<kSpMaxA>, dim3(grid), dim3(kSpBlock), (size_t)lds, s, a);
-    return (int)hipGetLastError();
+    return sp_launch(k_srn_response<2>, k_srn_response<kSpMaxA>, a, a.sp, grid, s);
 }
 #endif
 

@@ -278,6 +278,23 @@ def resolve_noise(batch, noise_prob, G):
     return an.resolve_noise(batch, noise_prob, G, "sampled_play", zero_ok=True)
 
 
+def bind_rows(batch, kinds, G, who, *sets):
+    """The networks' probability rows of a call: for each network i and each (what, rows, J, field) of `sets`, rows[i]
+    must be a contiguous float32 tensor [G, J, A_i] on the batch's device, and field[i] takes its address.  who: the
+    caller's name in the refusal."""
+    import torch
+    for i, k in enumerate(kinds):
+        if k == "QTable":
+            continue
+        for what, rows, J, field in sets:
+            x = rows.get(i)
+            shape = (G, J, int(batch.cfg.n_actions[i]))
+            if x is None or tuple(x.shape) != shape or x.dtype != torch.float32 or x.device != batch.state.device \
+                    or not x.is_contiguous():
+                raise ThrlError("%s: %s[%d] must be a contiguous float32 tensor %s on %s" % (who, what, i, shape, batch.device))
+            field[i] = x.data_ptr()
+
+
 def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi=False, n_games=None, tuple_policy=None,
         probs=None, dpolicy=None, tabs=None, noise_prob=0.0, resolution=NOISE_DEFAULTS["resolution"], nprobs=None, npolicy=None):
     """thrl_sampled_chain for the first n_games (default all) games of `batch` (a MixedGameBatch of QTable / Reinforce /
@@ -348,14 +365,7 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
             else:
                 dpolicy = ts.price_policy(batch, tabs["dprice"], n_games=G)
         an.check_policy(batch, dpolicy, (G, N, D), "sampled_play", "dpolicy")
-        for i, k in enumerate(kinds):
-            if k == "QTable":
-                continue
-            p = probs.get(i)
-            shape = (G, D, int(batch.cfg.n_actions[i]))
-            if p is None or tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != sdev or not p.is_contiguous():
-                raise ThrlError("sampled_play: probs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
-            a.prob[i] = p.data_ptr()
+        bind_rows(batch, kinds, G, "sampled_play", ("probs", probs, D, a.prob))
         a.dpolicy = dpolicy.data_ptr()
         p_noise = p_g = None
         if noise:
@@ -369,15 +379,7 @@ def run(batch, epsilon="current", start="uniform", tol=1e-12, max_iters=8192, pi
             if npolicy is None:
                 npolicy = ts.price_policy(batch, tabs["xn"], n_games=G)
             an.check_policy(batch, npolicy, (G, N, Jn), "sampled_play", "npolicy")
-            for i, k in enumerate(kinds):
-                if k == "QTable":
-                    continue
-                pn = nprobs.get(i)
-                shape = (G, Jn, int(batch.cfg.n_actions[i]))
-                if pn is None or tuple(pn.shape) != shape or pn.dtype != torch.float32 or pn.device != sdev \
-                        or not pn.is_contiguous():
-                    raise ThrlError("sampled_play: nprobs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
-                a.nprob[i] = pn.data_ptr()
+            bind_rows(batch, kinds, G, "sampled_play", ("nprobs", nprobs, Jn, a.nprob))
             a.npolicy = npolicy.data_ptr()
         keep = an.bind_tables(a, tabs, tab_list, dev, "sampled_play")
         t0 = None

@@ -105,19 +105,28 @@ def team_of(D, max_actions):
     return 1 if 8 * D * max_actions > MAX_TEAM_BYTES else team
 
 
+def _working_head(tabs, n_nodes=0):
+    """(bytes, T, D) of what sr_layout and srn_layout share (sr_layout_head) over S = D + n_nodes states: the sum of
+    r16(x) over five arrays of 8 S, two of 8 T, the staged rows (4 D A_i per network, 2 D per QTable agent), 2 (D + 1),
+    2 T, 2 T, 2 S and 2 S."""
+    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
+    S = D + n_nodes
+    r16 = sp._r16
+    b = 5 * r16(8 * S) + 2 * r16(8 * T)
+    for kind, A in zip(tabs["kinds"], tabs["n_actions"]):
+        b += r16(2 * D) if kind == "QTable" else r16(4 * D * int(A))
+    return b + r16(2 * (D + 1)) + 2 * r16(2 * T) + 2 * r16(2 * S), T, D
+
+
 def working_set(config, tabs=None):
     """The LDS bytes one game takes in thrl_sampled_response, by include/thrl_response.h's formula (sr_layout): the sum of
     r16(x) over five arrays of 8 D, two of 8 T, 4 D A_i per network, 2 D per QTable agent, 2 (D + 1), 2 T, 2 T, 2 D, 2 D,
     2,048, the team's staging 8 D max_i A_i (where a team shares a price) and 256.  Returns dict(bytes, T, D, team, fits)."""
     tabs = sp.tables(config) if tabs is None else tabs
-    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
-    r16 = sp._r16
-    acts = [int(a) for a in tabs["n_actions"]]
-    team = team_of(D, max(acts))
-    b = 5 * r16(8 * D) + 2 * r16(8 * T)
-    for kind, A in zip(tabs["kinds"], acts):
-        b += r16(2 * D) if kind == "QTable" else r16(4 * D * A)
-    b += r16(2 * (D + 1)) + 2 * r16(2 * T) + 2 * r16(2 * D) + 2048 + (r16(8 * D * max(acts)) if team > 1 else 0) + 256
+    b, T, D = _working_head(tabs)
+    max_actions = max(int(a) for a in tabs["n_actions"])
+    team = team_of(D, max_actions)
+    b += 2048 + (sp._r16(8 * D * max_actions) if team > 1 else 0) + 256
     return dict(bytes=int(b), T=T, D=D, team=team, fits=b <= MAX_LDS)
 
 
@@ -127,15 +136,9 @@ def working_set_noise(config, resolution=sp.NOISE_DEFAULTS["resolution"], tabs=N
     agent, 2 (D + 1), 2 T, 2 T, 2 S, 2 S, 2 Jn per QTable agent, 2,048 and 256.  The networks' node rows are not part of
     it.  Jn from resolution (sampled_play.n_nodes_of) unless n_nodes is given.  Returns dict(bytes, T, D, Jn, fits)."""
     tabs = sp.tables(config) if tabs is None else tabs
-    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
     Jn = int(n_nodes) if n_nodes is not None else sp.n_nodes_of(config, resolution)
-    S = D + Jn
-    r16 = sp._r16
-    b = 5 * r16(8 * S) + 2 * r16(8 * T)
-    for kind, A in zip(tabs["kinds"], tabs["n_actions"]):
-        b += r16(2 * D) if kind == "QTable" else r16(4 * D * int(A))
-    b += r16(2 * (D + 1)) + 2 * r16(2 * T) + 2 * r16(2 * S)
-    b += sum(r16(2 * Jn) for kind in tabs["kinds"] if kind == "QTable") + 2048 + 256
+    b, T, D = _working_head(tabs, Jn)
+    b += sum(sp._r16(2 * Jn) for kind in tabs["kinds"] if kind == "QTable") + 2048 + 256
     return dict(bytes=int(b), T=T, D=D, Jn=Jn, fits=b <= MAX_LDS)
 
 
@@ -164,14 +167,11 @@ def resolve_gamma(batch, gamma, G):
     return x, None
 
 
-def run(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_sweeps=8192, policies=False, pi=None,
-        n_games=None, probs=None, dpolicy=None, tabs=None):
-    """thrl_sampled_response for the first n_games (default all) games of `batch` (a MixedGameBatch of QTable / Reinforce
-    / ActorCritic agents, or a GameBatch).  agents: the agents solved (default all).  epsilon: sampled_play's rules.
-    gamma: resolve_gamma's.  pi: the long-run distribution that weights loss_w, gain_w, v_w and br_prob_w: None = computed
-    here with sampled_play.run(pi=True) on the same strategies, an array [G, T], or False = no weighted outputs.  probs,
-    dpolicy, tabs as in sampled_play.run.  policies=True adds br_policy (uint16), v_opt, v_pi [N, G, D].  Returns a dict
-    of numpy arrays, [N, G] with zeros for the agents that are not selected."""
+def _run(batch, noise, agents, epsilon, gamma, eval_tol, max_sweeps, policies, pi, n_games, probs, dpolicy, tabs,
+         noise_prob=None, resolution=None, nprobs=None, npolicy=None):
+    """run()'s body (noise false) and run_noise()'s (true): under noise the call also takes the nodes and the band, the
+    noise probability, the strategies at the nodes and three more tables, the arrays over the states are [D + Jn], and the
+    counts and mean losses come per kind of state."""
     import torch
     from . import tuple_stationary as ts
     N = batch.N
@@ -179,22 +179,31 @@ def run(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_s
     ag, mask = eq.agents_mask(agents, N)
     if isinstance(max_sweeps, bool) or not 1 <= int(max_sweeps) <= _lib.STAT_MAX_ITERS:
         raise ThrlError("sampled_response: max_sweeps=%r out of [1, %d]" % (max_sweeps, _lib.STAT_MAX_ITERS))
+    if noise and (tabs is None or "xn" not in tabs):
+        tabs = sp.noise_tables(batch.config, resolution, tabs=tabs)
     if tabs is None:
         tabs = sp.tables(batch.config)
     tp._batch_tables(batch, tabs)
-    ws = working_set(batch.config, tabs)
-    if not ws["fits"]:                                   # what the call answers from the shape alone
-        err = ThrlError("thrl_sampled_response refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d), at most %d"
-                        % (_lib.ERR_UNSUPPORTED, ws["bytes"], ws["T"], ws["D"], MAX_LDS))   # (the library: lds_refusal's words)
+    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
+    Jn, W = (int(tabs["n_nodes"]), int(tabs["band_w"])) if noise else (0, 0)
+    S = D + Jn
+    call = "thrl_sampled_response_noise" if noise else "thrl_sampled_response"
+    ws = working_set_noise(batch.config, tabs=tabs, n_nodes=Jn) if noise else working_set(batch.config, tabs)
+    if not ws["fits"]:                                   # what the call answers from the shape alone (the library's own
+        # message is the shared "(N=.., n_cells=..)" with n_cells = the states; this one names the parts)
+        err = ThrlError("%s refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d%s), at most %d"
+                        % (call, _lib.ERR_UNSUPPORTED, ws["bytes"], T, D, ", n_nodes=%d" % Jn if noise else "", MAX_LDS))
         err.code = _lib.ERR_UNSUPPORTED
         raise err
     kinds = tp._kinds(batch)
     dev = batch.device
-    sdev = batch.state.device
-    T, D = int(tabs["n_tuples"]), int(tabs["n_prices"])
-    a = _lib.SampledResponseArgs()
+    a = _lib.SampledResponseNoiseArgs() if noise else _lib.SampledResponseArgs()
     a.n_games, a.n_tuples, a.n_prices, a.agents = G, T, D, mask
     a.max_sweeps, a.eval_tol = int(max_sweeps), float(eval_tol)
+    tab_list = [("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32), ("reward", (N, T), np.float64)]
+    if noise:
+        a.n_nodes, a.band_w = Jn, W
+        tab_list += [("band_lo", (T,), np.int32), ("band", (T, W), np.float64), ("noise_reward", (N, T), np.float64)]
     for i, k in enumerate(kinds):
         a.kind[i] = tp.KINDS[k]
     with torch.cuda.device(dev):
@@ -206,24 +215,34 @@ def run(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_s
             a.eps_g = eps_g.data_ptr()
         if gam_g is not None:
             a.sweep_gamma = gam_g.data_ptr()
+        if noise:
+            p_noise, p_g = an.resolve_noise(batch, noise_prob, G, "sampled_response")
+            if p_g is not None:
+                a.noise_prob_g = p_g.data_ptr()
+            else:
+                a.noise_prob = p_noise
         if probs is None:
             probs = sp.price_probs(batch, tabs["dprice"], n_games=G)
         if dpolicy is None:
             dpolicy = ts.price_policy(batch, tabs["dprice"], n_games=G)
+        if noise and nprobs is None:
+            nprobs = sp.price_probs(batch, tabs["xn"], n_games=G)
+        if noise and npolicy is None:
+            npolicy = ts.price_policy(batch, tabs["xn"], n_games=G)
         an.check_policy(batch, dpolicy, (G, N, D), "sampled_response", "dpolicy")
-        for i, k in enumerate(kinds):
-            if k == "QTable":
-                continue
-            p = probs.get(i)
-            shape = (G, D, int(batch.cfg.n_actions[i]))
-            if p is None or tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != sdev or not p.is_contiguous():
-                raise ThrlError("sampled_response: probs[%d] must be a contiguous float32 tensor %s on %s" % (i, shape, dev))
-            a.prob[i] = p.data_ptr()
+        rows = [("probs", probs, D, a.prob)]
+        chain = {}                                       # what sampled_play.run takes on top, for pi
+        if noise:
+            an.check_policy(batch, npolicy, (G, N, Jn), "sampled_response", "npolicy")
+            rows.append(("nprobs", nprobs, Jn, a.nprob))
+            a.npolicy = npolicy.data_ptr()
+            chain = dict(noise_prob=p_noise if p_g is None else p_g, nprobs=nprobs, npolicy=npolicy)
+        sp.bind_rows(batch, kinds, G, "sampled_response", *rows)
         a.dpolicy = dpolicy.data_ptr()
         pi_t = None
         if pi is None:
             e = epsilon if eps_g is None else eps_g
-            st = sp.run(batch, epsilon=e, pi=True, n_games=G, probs=probs, dpolicy=dpolicy, tabs=tabs)
+            st = sp.run(batch, epsilon=e, pi=True, n_games=G, probs=probs, dpolicy=dpolicy, tabs=tabs, **chain)
             pi_t = torch.from_numpy(np.ascontiguousarray(st["pi"])).to(dev)
         elif pi is not False:
             if isinstance(pi, torch.Tensor):
@@ -234,27 +253,40 @@ def run(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_s
                 raise ThrlError("sampled_response: pi must be shaped %s, got %s" % ((G, T), tuple(pi_t.shape)))
         if pi_t is not None:
             a.pi = pi_t.data_ptr()
-        keep = an.bind_tables(a, tabs, [("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32),
-                                        ("reward", (N, T), np.float64)], dev, "sampled_response")
-        out = an.outputs(dev, (INT, (N, G), "int32"), (FLOAT, (N, G), "float64"),
+        keep = an.bind_tables(a, tabs, tab_list, dev, "sampled_response")
+        out = an.outputs(dev, (NOISE_INT if noise else INT, (N, G), "int32"), (NOISE_FLOAT if noise else FLOAT, (N, G), "float64"),
                          (WEIGHTED if pi_t is not None else (), (N, G), "float64"),
-                         (("br_policy",) if policies else (), (N, G, D), "int16"),
-                         (("v_opt", "v_pi") if policies else (), (N, G, D), "float64"))
+                         (("br_policy",) if policies else (), (N, G, S), "int16"),
+                         (("v_opt", "v_pi") if policies else (), (N, G, S), "float64"))
         an.bind(a, out)
-        _lib.check(batch.L.thrl_sampled_response(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
-                   "thrl_sampled_response")
+        _lib.check(getattr(batch.L, call)(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()), call)
         torch.cuda.synchronize(dev)
         res = an.fetch(out)
         del keep
         res["epsilon"] = np.repeat(np.asarray(eps, np.float64)[:, None], G, axis=1) if eps_g is None else eps_g.cpu().numpy()
         res["gamma"] = np.repeat(np.asarray(gam, np.float64)[:, None], G, axis=1) if gam_g is None else gam_g.cpu().numpy()
+        if noise:
+            res["noise_prob"] = np.full(G, p_noise, np.float64) if p_g is None else p_g.cpu().numpy()
         if pi_t is not None:
             res["pi"] = pi_t.cpu().numpy()
     if policies:
         res["br_policy"] = res["br_policy"].view(np.uint16)
     res["agents"], res["T"], res["n_prices"], res["lds_bytes"] = ag, T, D, ws["bytes"]
+    if noise:
+        res["n_nodes"], res["resolution"] = Jn, int(tabs.get("resolution", resolution))
     res["eval_tol"], res["max_sweeps"] = float(eval_tol), int(max_sweeps)
     return res
+
+
+def run(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_sweeps=8192, policies=False, pi=None,
+        n_games=None, probs=None, dpolicy=None, tabs=None):
+    """thrl_sampled_response for the first n_games (default all) games of `batch` (a MixedGameBatch of QTable / Reinforce
+    / ActorCritic agents, or a GameBatch).  agents: the agents solved (default all).  epsilon: sampled_play's rules.
+    gamma: resolve_gamma's.  pi: the long-run distribution that weights loss_w, gain_w, v_w and br_prob_w: None = computed
+    here with sampled_play.run(pi=True) on the same strategies, an array [G, T], or False = no weighted outputs.  probs,
+    dpolicy, tabs as in sampled_play.run.  policies=True adds br_policy (uint16), v_opt, v_pi [N, G, D].  Returns a dict
+    of numpy arrays, [N, G] with zeros for the agents that are not selected."""
+    return _run(batch, False, agents, epsilon, gamma, eval_tol, max_sweeps, policies, pi, n_games, probs, dpolicy, tabs)
 
 
 def run_noise(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12, max_sweeps=8192, policies=False, pi=None,
@@ -270,107 +302,8 @@ def run_noise(batch, agents=None, epsilon="current", gamma=None, eval_tol=1e-12,
     (uint16), v_opt, v_pi [N, G, D + Jn], the prices first.  Returns a dict of numpy arrays, [N, G] with zeros for the
     agents that are not selected: iters, sweeps, n_diff_prices, n_diff_nodes, loss_all, loss_prices_mean,
     loss_nodes_mean, loss_w, gain_w, v_w, br_prob_w, gamma, epsilon, and noise_prob [G]."""
-    import torch
-    from . import tuple_stationary as ts
-    N = batch.N
-    G = sp._games(batch, n_games)
-    ag, mask = eq.agents_mask(agents, N)
-    if isinstance(max_sweeps, bool) or not 1 <= int(max_sweeps) <= _lib.STAT_MAX_ITERS:
-        raise ThrlError("sampled_response: max_sweeps=%r out of [1, %d]" % (max_sweeps, _lib.STAT_MAX_ITERS))
-    tabs = ntabs if ntabs is not None else tabs
-    if tabs is None or "xn" not in tabs:
-        tabs = sp.noise_tables(batch.config, resolution, tabs=tabs)
-    tp._batch_tables(batch, tabs)
-    T, D, Jn, W = int(tabs["n_tuples"]), int(tabs["n_prices"]), int(tabs["n_nodes"]), int(tabs["band_w"])
-    ws = working_set_noise(batch.config, tabs=tabs, n_nodes=Jn)
-    if not ws["fits"]:                                   # what the call answers from the shape alone (the library's own
-        # message is the shared "(N=.., n_cells=..)" with n_cells = D + Jn, the states; this one names the parts)
-        err = ThrlError("thrl_sampled_response_noise refused (thrl_err %d): %d bytes of LDS per game (T=%d, n_prices=%d, "
-                        "n_nodes=%d), at most %d" % (_lib.ERR_UNSUPPORTED, ws["bytes"], T, D, Jn, MAX_LDS))
-        err.code = _lib.ERR_UNSUPPORTED
-        raise err
-    kinds = tp._kinds(batch)
-    dev = batch.device
-    sdev = batch.state.device
-    a = _lib.SampledResponseNoiseArgs()
-    a.n_games, a.n_tuples, a.n_prices, a.n_nodes, a.band_w, a.agents = G, T, D, Jn, W, mask
-    a.max_sweeps, a.eval_tol = int(max_sweeps), float(eval_tol)
-    for i, k in enumerate(kinds):
-        a.kind[i] = tp.KINDS[k]
-    with torch.cuda.device(dev):
-        eps, eps_g = sp.resolve_epsilon(batch, epsilon, G)
-        gam, gam_g = resolve_gamma(batch, gamma, G)
-        p_noise, p_g = an.resolve_noise(batch, noise_prob, G, "sampled_response")
-        for i in range(N):
-            a.eps[i], a.gamma[i] = eps[i], gam[i]
-        if eps_g is not None:
-            a.eps_g = eps_g.data_ptr()
-        if gam_g is not None:
-            a.sweep_gamma = gam_g.data_ptr()
-        if p_g is not None:
-            a.noise_prob_g = p_g.data_ptr()
-        else:
-            a.noise_prob = p_noise
-        if probs is None:
-            probs = sp.price_probs(batch, tabs["dprice"], n_games=G)
-        if dpolicy is None:
-            dpolicy = ts.price_policy(batch, tabs["dprice"], n_games=G)
-        if nprobs is None:
-            nprobs = sp.price_probs(batch, tabs["xn"], n_games=G)
-        if npolicy is None:
-            npolicy = ts.price_policy(batch, tabs["xn"], n_games=G)
-        an.check_policy(batch, dpolicy, (G, N, D), "sampled_response", "dpolicy")
-        an.check_policy(batch, npolicy, (G, N, Jn), "sampled_response", "npolicy")
-        for i, k in enumerate(kinds):
-            if k == "QTable":
-                continue
-            for what, rows, J, field in (("probs", probs, D, a.prob), ("nprobs", nprobs, Jn, a.nprob)):
-                x = rows.get(i)
-                shape = (G, J, int(batch.cfg.n_actions[i]))
-                if x is None or tuple(x.shape) != shape or x.dtype != torch.float32 or x.device != sdev or not x.is_contiguous():
-                    raise ThrlError("sampled_response: %s[%d] must be a contiguous float32 tensor %s on %s" % (what, i, shape, dev))
-                field[i] = x.data_ptr()
-        a.dpolicy, a.npolicy = dpolicy.data_ptr(), npolicy.data_ptr()
-        pi_t = None
-        if pi is None:
-            e = epsilon if eps_g is None else eps_g
-            st = sp.run(batch, epsilon=e, pi=True, n_games=G, probs=probs, dpolicy=dpolicy, tabs=tabs,
-                        noise_prob=p_noise if p_g is None else p_g, nprobs=nprobs, npolicy=npolicy)
-            pi_t = torch.from_numpy(np.ascontiguousarray(st["pi"])).to(dev)
-        elif pi is not False:
-            if isinstance(pi, torch.Tensor):
-                pi_t = pi.to(device=dev, dtype=torch.float64).contiguous()
-            else:
-                pi_t = torch.from_numpy(np.ascontiguousarray(np.asarray(pi, np.float64))).to(dev)
-            if tuple(pi_t.shape) != (G, T):
-                raise ThrlError("sampled_response: pi must be shaped %s, got %s" % ((G, T), tuple(pi_t.shape)))
-        if pi_t is not None:
-            a.pi = pi_t.data_ptr()
-        keep = an.bind_tables(a, tabs, [("grp_first", (D + 1,), np.int32), ("grp_perm", (T,), np.int32),
-                                        ("reward", (N, T), np.float64), ("band_lo", (T,), np.int32), ("band", (T, W), np.float64),
-                                        ("noise_reward", (N, T), np.float64)], dev, "sampled_response")
-        S = D + Jn
-        out = an.outputs(dev, (NOISE_INT, (N, G), "int32"), (NOISE_FLOAT, (N, G), "float64"),
-                         (WEIGHTED if pi_t is not None else (), (N, G), "float64"),
-                         (("br_policy",) if policies else (), (N, G, S), "int16"),
-                         (("v_opt", "v_pi") if policies else (), (N, G, S), "float64"))
-        an.bind(a, out)
-        _lib.check(batch.L.thrl_sampled_response_noise(ctypes.byref(batch.cfg), ctypes.byref(a), batch._stream()),
-                   "thrl_sampled_response_noise")
-        torch.cuda.synchronize(dev)
-        res = an.fetch(out)
-        del keep
-        res["epsilon"] = np.repeat(np.asarray(eps, np.float64)[:, None], G, axis=1) if eps_g is None else eps_g.cpu().numpy()
-        res["gamma"] = np.repeat(np.asarray(gam, np.float64)[:, None], G, axis=1) if gam_g is None else gam_g.cpu().numpy()
-        res["noise_prob"] = np.full(G, p_noise, np.float64) if p_g is None else p_g.cpu().numpy()
-        if pi_t is not None:
-            res["pi"] = pi_t.cpu().numpy()
-    if policies:
-        res["br_policy"] = res["br_policy"].view(np.uint16)
-    res["agents"], res["T"], res["n_prices"], res["n_nodes"], res["lds_bytes"] = ag, T, D, Jn, ws["bytes"]
-    res["resolution"] = int(tabs.get("resolution", resolution))
-    res["eval_tol"], res["max_sweeps"] = float(eval_tol), int(max_sweeps)
-    return res
+    return _run(batch, True, agents, epsilon, gamma, eval_tol, max_sweeps, policies, pi, n_games, probs, dpolicy,
+                ntabs if ntabs is not None else tabs, noise_prob, resolution, nprobs, npolicy)
 
 
 # ---------------------------------------------------------------------------------------------- host side
@@ -416,60 +349,6 @@ def summarize(games, agents, ids, n_groups, nash, cartel):
     return out
 
 
-def describe(options, r, nash, cartel, summary):
-    """sampled_response.json's content."""
-    return {"options": options, "agents": [int(i) for i in r["agents"]], "T": int(r["T"]), "n_prices": int(r["n_prices"]),
-            "nash": nash, "cartel": cartel, "quantiles": list(an.QUANTILES),
-            "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)", "summary": summary}
-
-
-FILES = (("sresp_counts.npy", INT, np.int32), ("sresp_loss.npy", FLOAT, np.float64), ("sresp_weighted.npy", WEIGHTED, np.float64))
-OPTIONAL = (("br_policy", "sresp_br_policy.npy", np.uint16), ("v_opt", "sresp_v_opt.npy", np.float64),
-            ("v_pi", "sresp_v_pi.npy", np.float64))
-
-
-def save_games(d, r):
-    """sresp_counts int32 [3, N, G] (iters, sweeps, n_diff), sresp_loss float64 [2, N, G] (loss_all, loss_mean),
-    sresp_weighted float64 [4, N, G] (loss_w, gain_w, v_w, br_prob_w), sresp_gamma and sresp_epsilon float64 [N, G]; with
-    the policies sresp_br_policy uint16, sresp_v_opt and sresp_v_pi float64 [N, G, D]."""
-    for name, fields, dt in FILES:
-        np.save(os.path.join(d, name), np.stack([np.asarray(r[f], dt) for f in fields]))
-    np.save(os.path.join(d, "sresp_gamma.npy"), np.asarray(r["gamma"], np.float64))
-    np.save(os.path.join(d, "sresp_epsilon.npy"), np.asarray(r["epsilon"], np.float64))
-    for f, name, dt in OPTIONAL:
-        path = os.path.join(d, name)
-        if f in r:
-            np.save(path, np.asarray(r[f], dt))
-        elif os.path.isfile(path):               # a file left by an earlier run with other options
-            os.remove(path)
-
-
-def load_games(d):
-    """The per-game arrays one run directory holds (training.sampled_play.response)."""
-    g = {}
-    for name, fields, _ in FILES:
-        x = np.load(os.path.join(d, name))
-        g.update({f: x[k] for k, f in enumerate(fields)})
-    g["gamma"], g["epsilon"] = np.load(os.path.join(d, "sresp_gamma.npy")), np.load(os.path.join(d, "sresp_epsilon.npy"))
-    for f, name, _ in OPTIONAL:
-        if os.path.isfile(os.path.join(d, name)):
-            g[f] = np.load(os.path.join(d, name))
-    return g
-
-
-def write_artefacts(exp_path, batch, config, opt, ids, n_groups, epsilon="current", tabs=None, pi=None):
-    """train_one's training.sampled_play.response outputs: the per-game sresp_*.npy files and sampled_response.json.
-    epsilon: sampled_play's option; pi: its distributions where it stored them (else computed here)."""
-    r = run(batch, agents=opt["agents"], epsilon=epsilon, eval_tol=opt["eval_tol"], max_sweeps=opt["max_sweeps"],
-            policies=opt["policies"], pi=pi, tabs=tabs)
-    save_games(exp_path, r)
-    nash, cartel = optimal(config)
-    summary = summarize(r, r["agents"], ids, n_groups, nash, cartel)
-    an.save_json(os.path.join(exp_path, "sampled_response.json"), describe(opt, r, nash, cartel, summary))
-    return r
-
-
-# ---------------------------------------------------------------------------------------------- under demand noise
 def summarize_noise(games, agents, ids, n_groups, nash, cartel, max_jump=None):
     """summarize()'s rows for run_noise()'s arrays.  A (group, agent) row also has diff_nodes_mean, the mean number of
     node-states where the best reply is not the modal action, over the solved games; a group's own row also has
@@ -489,30 +368,33 @@ def summarize_noise(games, agents, ids, n_groups, nash, cartel, max_jump=None):
     return rows
 
 
-def describe_noise(options, r, nash, cartel, summary):
-    """sampled_response_noise.json's content."""
-    d = describe(options, r, nash, cartel, summary)
-    d.update(n_nodes=int(r["n_nodes"]), resolution=int(r["resolution"]))
-    return d
+# ---------------------------------------------------------------------------------------------- artefacts
+class FileSet:
+    """The files one analysis writes into a run directory.  json: the summary's name.  files: (name, fields, dtype), the
+    fields stacked: <prefix>_counts int32 [len(ints), N, G], <prefix>_loss float64 [len(floats), N, G], <prefix>_weighted
+    float64 [4, N, G] (loss_w, gain_w, v_w, br_prob_w).  plain: (field, name), float64 as run() returns it:
+    <prefix>_gamma and <prefix>_epsilon [N, G], under noise <prefix>_noise_prob [G].  optional: (field, name, dtype),
+    written with the policies: <prefix>_br_policy uint16, <prefix>_v_opt and <prefix>_v_pi float64 [N, G, states]."""
+
+    def __init__(self, prefix, json, ints, floats, plain):
+        self.json = json
+        self.files = (("%s_counts.npy" % prefix, ints, np.int32), ("%s_loss.npy" % prefix, floats, np.float64),
+                      ("%s_weighted.npy" % prefix, WEIGHTED, np.float64))
+        self.plain = tuple((f, "%s_%s.npy" % (prefix, f)) for f in plain)
+        self.optional = tuple((f, "%s_%s.npy" % (prefix, f), dt)
+                              for f, dt in (("br_policy", np.uint16), ("v_opt", np.float64), ("v_pi", np.float64)))
 
 
-NOISE_FILES = (("srespn_counts.npy", NOISE_INT, np.int32), ("srespn_loss.npy", NOISE_FLOAT, np.float64),
-               ("srespn_weighted.npy", WEIGHTED, np.float64))
-NOISE_PLAIN = (("gamma", "srespn_gamma.npy"), ("epsilon", "srespn_epsilon.npy"), ("noise_prob", "srespn_noise_prob.npy"))
-NOISE_OPTIONAL = (("br_policy", "srespn_br_policy.npy", np.uint16), ("v_opt", "srespn_v_opt.npy", np.float64),
-                  ("v_pi", "srespn_v_pi.npy", np.float64))
+PLAY_FILES = FileSet("sresp", "sampled_response.json", INT, FLOAT, ("gamma", "epsilon"))
+NOISE_FILES = FileSet("srespn", "sampled_response_noise.json", NOISE_INT, NOISE_FLOAT, ("gamma", "epsilon", "noise_prob"))
 
 
-def save_games_noise(d, r):
-    """srespn_counts int32 [4, N, G] (iters, sweeps, n_diff_prices, n_diff_nodes), srespn_loss float64 [3, N, G] (loss_all,
-    loss_prices_mean, loss_nodes_mean), srespn_weighted float64 [4, N, G] (loss_w, gain_w, v_w, br_prob_w), srespn_gamma
-    and srespn_epsilon float64 [N, G], srespn_noise_prob float64 [G]; with the policies srespn_br_policy uint16,
-    srespn_v_opt and srespn_v_pi float64 [N, G, D + Jn]."""
-    for name, fields, dt in NOISE_FILES:
+def _save(fs, d, r):
+    for name, fields, dt in fs.files:
         np.save(os.path.join(d, name), np.stack([np.asarray(r[f], dt) for f in fields]))
-    for f, name in NOISE_PLAIN:
+    for f, name in fs.plain:
         np.save(os.path.join(d, name), np.asarray(r[f], np.float64))
-    for f, name, dt in NOISE_OPTIONAL:
+    for f, name, dt in fs.optional:
         path = os.path.join(d, name)
         if f in r:
             np.save(path, np.asarray(r[f], dt))
@@ -520,18 +402,74 @@ def save_games_noise(d, r):
             os.remove(path)
 
 
-def load_games_noise(d):
-    """The per-game arrays one run directory holds (training.sampled_play.response with "noise")."""
+def _load(fs, d):
     g = {}
-    for name, fields, _ in NOISE_FILES:
+    for name, fields, _ in fs.files:
         x = np.load(os.path.join(d, name))
         g.update({f: x[k] for k, f in enumerate(fields)})
-    for f, name in NOISE_PLAIN:
+    for f, name in fs.plain:
         g[f] = np.load(os.path.join(d, name))
-    for f, name, _ in NOISE_OPTIONAL:
+    for f, name, _ in fs.optional:
         if os.path.isfile(os.path.join(d, name)):
             g[f] = np.load(os.path.join(d, name))
     return g
+
+
+def save_games(d, r):
+    """sresp_counts int32 [3, N, G] (iters, sweeps, n_diff), sresp_loss float64 [2, N, G] (loss_all, loss_mean),
+    sresp_weighted float64 [4, N, G] (loss_w, gain_w, v_w, br_prob_w), sresp_gamma and sresp_epsilon float64 [N, G]; with
+    the policies sresp_br_policy uint16, sresp_v_opt and sresp_v_pi float64 [N, G, D]."""
+    _save(PLAY_FILES, d, r)
+
+
+def save_games_noise(d, r):
+    """srespn_counts int32 [4, N, G] (iters, sweeps, n_diff_prices, n_diff_nodes), srespn_loss float64 [3, N, G] (loss_all,
+    loss_prices_mean, loss_nodes_mean), srespn_weighted float64 [4, N, G] (loss_w, gain_w, v_w, br_prob_w), srespn_gamma
+    and srespn_epsilon float64 [N, G], srespn_noise_prob float64 [G]; with the policies srespn_br_policy uint16,
+    srespn_v_opt and srespn_v_pi float64 [N, G, D + Jn]."""
+    _save(NOISE_FILES, d, r)
+
+
+def load_games(d):
+    """The per-game arrays one run directory holds (training.sampled_play.response)."""
+    return _load(PLAY_FILES, d)
+
+
+def load_games_noise(d):
+    """The per-game arrays one run directory holds (training.sampled_play.response with "noise")."""
+    return _load(NOISE_FILES, d)
+
+
+def describe(options, r, nash, cartel, summary):
+    """sampled_response.json's content."""
+    return {"options": options, "agents": [int(i) for i in r["agents"]], "T": int(r["T"]), "n_prices": int(r["n_prices"]),
+            "nash": nash, "cartel": cartel, "quantiles": list(an.QUANTILES),
+            "benchmark": "noise-free Nash and Cartel rewards (environment.get_optimal)", "summary": summary}
+
+
+def describe_noise(options, r, nash, cartel, summary):
+    """sampled_response_noise.json's content."""
+    d = describe(options, r, nash, cartel, summary)
+    d.update(n_nodes=int(r["n_nodes"]), resolution=int(r["resolution"]))
+    return d
+
+
+def _write(fs, exp_path, config, opt, r, rows, content):
+    """The artefacts of the result r: the file set's per-game arrays and its json, content(opt, r, nash, cartel, summary)
+    with the summary rows(r, r["agents"], nash, cartel)."""
+    _save(fs, exp_path, r)
+    nash, cartel = optimal(config)
+    an.save_json(os.path.join(exp_path, fs.json), content(opt, r, nash, cartel, rows(r, r["agents"], nash, cartel)))
+    return r
+
+
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, epsilon="current", tabs=None, pi=None):
+    """train_one's training.sampled_play.response outputs: the per-game sresp_*.npy files and sampled_response.json.
+    epsilon: sampled_play's option; pi: its distributions where it stored them (else computed here)."""
+    r = run(batch, agents=opt["agents"], epsilon=epsilon, eval_tol=opt["eval_tol"], max_sweeps=opt["max_sweeps"],
+            policies=opt["policies"], pi=pi, tabs=tabs)
+    return _write(PLAY_FILES, exp_path, config, opt, r, lambda g, ag, nash, cartel: summarize(g, ag, ids, n_groups, nash, cartel),
+                  describe)
 
 
 def write_artefacts_noise(exp_path, batch, config, opt, ids, n_groups, noise_prob, epsilon="current", tabs=None, pi=None,
@@ -541,8 +479,5 @@ def write_artefacts_noise(exp_path, batch, config, opt, ids, n_groups, noise_pro
     distributions where it stored them (else computed here); max_jump: its honesty figure, carried into the summary."""
     r = run_noise(batch, agents=opt["agents"], epsilon=epsilon, eval_tol=opt["eval_tol"], max_sweeps=opt["max_sweeps"],
                   policies=opt["policies"], pi=pi, ntabs=tabs, noise_prob=noise_prob)
-    save_games_noise(exp_path, r)
-    nash, cartel = optimal(config)
-    summary = summarize_noise(r, r["agents"], ids, n_groups, nash, cartel, max_jump=max_jump)
-    an.save_json(os.path.join(exp_path, "sampled_response_noise.json"), describe_noise(opt, r, nash, cartel, summary))
-    return r
+    return _write(NOISE_FILES, exp_path, config, opt, r,
+                  lambda g, ag, nash, cartel: summarize_noise(g, ag, ids, n_groups, nash, cartel, max_jump=max_jump), describe_noise)
