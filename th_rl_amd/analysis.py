@@ -59,7 +59,8 @@ REGISTRY = (
     _a("greedy_attractors", "tuple_analysis", "greedy_attractor", "parse_attractor_options", "write_attractors",
        tuple_policy="extract"),
     _a("greedy_stationary", "tuple_stationary", "greedy_stationary", tuple_policy="extract"),
-    _a("sampled_play", "sampled_play", "sampled_play", tuple_policy="use", after=(("with_cycles", "greedy_cycles"),)),
+    _a("sampled_play", "sampled_play", "sampled_play", tuple_policy="use", rows=True,       # the sub-key "deviation"'s curves
+       after=(("with_cycles", "greedy_cycles"),)),
 )
 
 
@@ -610,6 +611,28 @@ class AnalysisMethods:
         return sr.run_noise(self, agents=agents, epsilon=epsilon, gamma=gamma, eval_tol=eval_tol, max_sweeps=max_sweeps,
                             policies=policies, pi=pi, n_games=n_games, probs=probs, dpolicy=dpolicy, tabs=tabs,
                             noise_prob=noise_prob, resolution=resolution, nprobs=nprobs, npolicy=npolicy, ntabs=ntabs)
+
+    def sampled_deviation(self, deviator=0, steps=32, dev_len=1, action="best_response", epsilon="current", gamma=None,
+                          ret_tol=1e-6, weights="stationary", rows=False, group_stats=None, budget=None, n_games=None,
+                          probs=None, dpolicy=None, tabs=None, tol=1e-12, max_iters=8192):
+        """The deviation test of SAMPLED play (sampled_deviation.run, thrl_sampled_deviation; definitions in
+        include/thrl_sampled_deviation.h): the expected impulse response of the agents' stochastic policies -- a network
+        its softmax, a QTable agent epsilon-greedily -- when `deviator` plays a deterministic strategy of the price for
+        dev_len periods and its own policy again for the remaining steps - dev_len.  action: "best_response" (one period,
+        to the rivals' mixed policies), an action index, "best_reply" (sampled_response's br_policy, the patient best
+        reply) or a [G, D] array.  No episodes are sampled: a distribution over the tuple played is propagated from
+        weights ("stationary" = the long-run distribution of sampled_play(pi=True, tol, max_iters), or an array [G, T]).
+        Returns a dict of numpy arrays: base_reward, base_action [N, G]; base_price, dev_share (the share of periods the
+        deviation changes), gain and gain_dev (the discounted gain of all steps and of the deviation itself; gamma: None
+        = the deviator's own), low and low_step (the deepest punishment), ret_step (the first period at which the
+        distribution is back within ret_tol in total variation, else -1), dist, mass, gamma, stat_iters [G]; epsilon
+        [N, G]; solved [G].  rows=True adds reward_rows / action_rows [steps, N, G] and price_rows / dist_rows [steps, G];
+        group_stats (a GroupSpec): the rows are reduced on the device.  Noise-free play only."""
+        from . import sampled_deviation as sd
+        self._ready()
+        return sd.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, epsilon=epsilon, gamma=gamma,
+                      ret_tol=ret_tol, weights=weights, rows=rows, group_stats=group_stats, budget=budget, n_games=n_games,
+                      probs=probs, dpolicy=dpolicy, tabs=tabs, tol=tol, max_iters=max_iters)
 
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),

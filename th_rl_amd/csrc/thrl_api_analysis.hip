@@ -24,6 +24,7 @@
 #include "thrl_tuple_equilibrium_noise.h"
 #include "thrl_tuple_play.h"
 #include "thrl_sampled.h"
+#include "thrl_sampled_deviation.h"
 #include "thrl_sampled_noise.h"
 #include "thrl_sampled_response.h"
 #include "thrl_sampled_response_noise.h"
@@ -31,6 +32,7 @@
 
 #include "../../include/thrl_response.h"
 #include "../../include/thrl_response_noise.h"
+#include "../../include/thrl_sampled_deviation.h"
 
 using namespace thrl;
 using namespace thrl::host;
@@ -123,7 +125,7 @@ int check_cell_limit(const char* call, int n_cells) {
     return ok ? THRL_OK : fail(THRL_ERR_UNSUPPORTED, "%s: n_cells=%d, at most %d", call, n_cells, THRL_STAT_MAX_CELLS);
 }
 // ---- the checks of the calls on sampled play (thrl_sampled_chain, thrl_sampled_noise_chain, thrl_sampled_response,
-// thrl_sampled_response_noise)
+// thrl_sampled_response_noise, thrl_sampled_deviation)
 int check_prices(int n_prices, int n_tuples) {
     const bool ok = n_prices >= 1 && n_prices <= n_tuples;
     return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", n_prices, n_tuples);
@@ -1048,6 +1050,71 @@ int thrl_sampled_response_noise(const thrl_cfg* c, const thrl_sampled_response_n
     if (rc) return rc;
     const int e = thrl::launch_sampled_response_noise(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_srn_response launch") : THRL_OK;
+}
+
+int thrl_sampled_deviation(const thrl_cfg* c, const thrl_sampled_deviation_args* x, void* stream) {
+    static_assert(THRL_SD_MAX_LDS == THRL_SP_MAX_LDS, "the deviation test plans for a CU's LDS as sampled play does");
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_sampled_chain's checks in its order with the deviation and its rows as thrl_tuple_deviation_noise checks them;
+    // every host-visible argument is checked, and the working set planned, before any pointer is looked at
+    if ((rc = check_games(x->n_games)) != THRL_OK) return rc;
+    if (x->flags & ~THRL_SD_POLICY) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    for (int k = 0; k < 2; k++)
+        if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_deviator(c, x->deviator, x->dev_len, x->n_steps)) != THRL_OK) return rc;
+    const bool use_policy = (x->flags & THRL_SD_POLICY) != 0;
+    if (use_policy) {                                    // the strategy is dev_policy: no action of the deviator is one
+        thrl_cfg none = *c;
+        none.n_actions[x->deviator] = 0;
+        if ((rc = check_dev_action(&none, x->deviator, x->dev_action)) != THRL_OK) return rc;
+    } else if ((rc = check_dev_action(c, x->deviator, x->dev_action)) != THRL_OK) {
+        return rc;
+    }
+    if ((rc = check_rows(x->row_begin, x->row_count, x->n_steps)) != THRL_OK) return rc;
+    if ((rc = check_tol(x->ret_tol, "ret_tol")) != THRL_OK) return rc;
+    if (!x->sweep_gamma) {                               // gamma in [0, 1]: both ends through the check of a tolerance
+        if ((rc = check_tol(x->gamma, "gamma")) != THRL_OK) return rc;
+        if ((rc = check_tol(1.0 - x->gamma, "1 - gamma")) != THRL_OK) return rc;
+    }
+    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    thrl::SdArgs a;
+    memset(&a, 0, sizeof(a));
+    SpArgs& sa = a.sp;
+    sp_fill_head(sa, c, x);
+    const int64_t lds = thrl::sd_layout(a);          // the working set of include/thrl_sampled_deviation.h
+    // (the cells of this analysis are the distinct prices)
+    if (lds > THRL_SD_MAX_LDS) return lds_refusal("thrl_sampled_deviation", lds, N, x->n_prices);
+    for (int i = 0; i < N; i++)
+        if (x->kind[i] != 0 && !x->prob[i]) return fail(THRL_ERR_NULL, "prob[%d] is NULL", i);
+    if (!x->dpolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->scaled || !x->price)
+        return missing("dpolicy / grp_first / grp_perm / reward / scaled / price");
+    if (!x->weights) return missing("weights");
+    if (use_policy && !x->dev_policy) return missing("with THRL_SD_POLICY, dev_policy");
+    if (!x->base_reward || !x->base_action || !x->base_price || !x->dev_share || !x->gain || !x->gain_dev || !x->low
+        || !x->low_step || !x->ret_step || !x->dist || !x->mass)
+        return missing("base_reward / base_action / base_price / dev_share / gain / gain_dev / low / low_step / ret_step / "
+                       "dist / mass");
+    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm;
+    sa.reward = x->reward; sa.scaled = x->scaled; sa.price = x->price;
+    a.d = x->deviator; a.L = x->dev_len; a.K = x->n_steps; a.dev_action = x->dev_action; a.use_policy = use_policy;
+    a.row_begin = x->row_begin; a.row_count = x->row_count;
+    a.gamma = x->gamma; a.ret_tol = x->ret_tol;
+    a.sweep_gamma = x->sweep_gamma; a.dev_policy = x->dev_policy; a.weights = x->weights;
+    a.base_reward = x->base_reward; a.base_action = x->base_action; a.base_price = x->base_price;
+    a.dev_share = x->dev_share; a.gain = x->gain; a.gain_dev = x->gain_dev; a.low = x->low; a.low_step = x->low_step;
+    a.ret_step = x->ret_step; a.dist = x->dist; a.mass = x->mass;
+    a.reward_rows = x->reward_rows; a.action_rows = x->action_rows; a.price_rows = x->price_rows; a.dist_rows = x->dist_rows;
+    int grid = 0;
+    rc = sp_plan_grid(sa, kSdMaxBlocksPerCu, &grid, [&](int) { return lds_refusal("thrl_sampled_deviation", lds, N, x->n_prices); });
+    if (rc) return rc;
+    const int e = thrl::launch_sampled_deviation(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_sd_chain launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,260 @@
+// thrl_sampled_deviation.hip -- the deviation test of SAMPLED play (thrl_sampled_deviation,
+// include/thrl_sampled_deviation.h): the expected impulse response of the agents' stochastic policies to a forced
+// deviation of one of them, by propagating a distribution over the tuple played through thrl_sampled_chain's chain -- L
+// steps with the deviator's row replaced by a deterministic strategy ad_g of the price, then K - L plain steps -- and what
+// every period's distribution earns.  One kernel.
+//
+// k_sd_chain has k_sp_chain's shape: a 256-thread block per game, looping over games, everything in LDS.  Per game the
+//   block stages the rows at the distinct prices exactly as k_sp_chain does (sp_stage_game, sp_normaliser), then once:
+//   ad_g(d) (uint16 [D]; for a best response the first maximum over k of q(d, k), thrl_response_dev.h's sr_q with U =
+//   reward_d staged in the second iterate, which is dead until the first step: a thread per price, k ascending) and the
+//   deviation step's Z(d), the product with S_d = 1.0; the terms of dev_share parked over U once it is read.  A step is
+//   k_sp_chain's without the lazy half: sp_weights with the step's Z, then a thread per output tuple walking the prices
+//   in ascending order (sp_price_sum).  For the deviation step the deviator's staged row is written over: a QTable
+//   deviator's greedy row by ad_g with hi = 1.0 and lo = 0.0 in its constants, a network's probabilities by the float32
+//   rows that are 1.0 at ad_g(d) and 0.0 elsewhere (exact when widened), so sp_price_sum evaluates the step as it stands;
+//   after L periods the game's rows and constants are staged again.  The ordered sums of a period follow k_sp_chain's
+//   outputs: chunks of 64 tuples, one lane per tuple for the products, then one lane per sum reading them back in
+//   ascending t (chain_read_back), keyed as chain_store keys them -- 0 the mass, 1 .. N the rewards, N + 1 .. 2 N the
+//   actions, 2 N + 1 the price -- and lane 2 N + 2 the distance from its own staging row.  The lane of a sum keeps what is
+//   derived from it in registers over the periods, as k_tdn_chain does: lane 1 + d the gain and the low, lane 2 N + 2 the
+//   distance and ret_step.  x_0 is re-read from global memory (coalesced) for the distance.  No atomic is involved.
+//   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
+#include "thrl_response_dev.h"
+#include "thrl_sampled_deviation.h"
+
+namespace thrl {
+
+namespace {
+
+// S_j(d) from the staged rows
+__device__ __forceinline__ double sd_row_sum(const SpArgs& sp, const unsigned char* s_mem, int j, int d) {
+    if (sp.kind[j] == 0) return 1.0;
+    const int A = sp.n_actions[j];
+    const float* rf = reinterpret_cast<const float*>(s_mem + sp.o_row[j]) + d * A;
+    double S = 0.0;
+    for (int k = 0; k < A; k++) S = __dadd_rn(S, (double)rf[k]);
+    return S;
+}
+
+// game g is not solved: zeros in every float64 output, its rows included, and -1 in low_step and ret_step
+__device__ __forceinline__ void sd_unsolved(const SdArgs& a, int64_t g, int tid) {
+    const int N = a.sp.N, G = a.sp.G, rc = a.row_count;
+    if (tid < N) {
+        a.base_reward[(int64_t)tid * G + g] = 0.0;
+        a.base_action[(int64_t)tid * G + g] = 0.0;
+    }
+    if (tid == 0) {
+        a.base_price[g] = 0.0; a.dev_share[g] = 0.0; a.gain[g] = 0.0; a.gain_dev[g] = 0.0; a.low[g] = 0.0; a.dist[g] = 0.0;
+        a.mass[g] = 0.0; a.low_step[g] = -1; a.ret_step[g] = -1;
+    }
+    for (int r = tid; r < rc * N; r += kSpBlock) {
+        if (a.reward_rows) a.reward_rows[(int64_t)r * G + g] = 0.0;
+        if (a.action_rows) a.action_rows[(int64_t)r * G + g] = 0.0;
+    }
+    for (int r = tid; r < rc; r += kSpBlock) {
+        if (a.price_rows) a.price_rows[(int64_t)r * G + g] = 0.0;
+        if (a.dist_rows) a.dist_rows[(int64_t)r * G + g] = 0.0;
+    }
+}
+
+// the ordered sums of one distribution m against x_0 = w0; lane o <= 2N + 2 its own: 0 the mass, 1 .. N the rewards,
+// N + 1 .. 2N the actions, 2N + 1 the price, 2N + 2 the sum of |m - x_0| (staged in drow)
+__device__ __forceinline__ double sd_sums(const SpArgs& sp, const double* m, const double* __restrict__ w0, double* prod,
+                                          double* drow, int tid) {
+    const int N = sp.N, T = sp.T, n_out = 2 * N + 2;
+    double acc = 0.0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + tid;
+        if (tid < 64 && t < T) {
+            const double mt = m[t];
+            prod[tid] = mt;
+            for (int i = 0; i < N; i++) {
+                prod[(1 + i) * 64 + tid] = __dmul_rn(mt, sp.reward[(int64_t)i * T + t]);
+                prod[(1 + N + i) * 64 + tid] = __dmul_rn(mt, sp.scaled[(int64_t)i * T + t]);
+            }
+            prod[(1 + 2 * N) * 64 + tid] = __dmul_rn(mt, sp.price[t]);
+            drow[tid] = fabs(__dsub_rn(mt, w0[t]));
+        }
+        __syncthreads();
+        const int n = min(64, T - t0);
+        acc = tid == n_out ? chain_read_back(drow, 1, n, acc, 0) : chain_read_back(prod, n_out, n, acc, tid);
+        __syncthreads();
+    }
+    return acc;
+}
+
+template <int MAXN>
+__device__ __forceinline__ void sd_block(const SdArgs& a, unsigned char* s_mem, int tid, int bid, int nblk) {
+    const SpArgs& sp = a.sp;
+    const int N = sp.N, G = sp.G, T = sp.T, D = sp.D, K = a.K, L = a.L, dv = a.d;
+    double* ma = reinterpret_cast<double*>(s_mem + sp.o_ma);
+    double* mb = reinterpret_cast<double*>(s_mem + sp.o_mb);          // before the first step: reward_d, then dev_share's terms
+    double* W = reinterpret_cast<double*>(s_mem + sp.o_w);
+    double* Z = reinterpret_cast<double*>(s_mem + sp.o_z);
+    double* Zd = reinterpret_cast<double*>(s_mem + a.o_zd);           // [D] the deviation step's Z
+    uint16_t* first = reinterpret_cast<uint16_t*>(s_mem + sp.o_first);
+    uint16_t* perm = reinterpret_cast<uint16_t*>(s_mem + sp.o_perm);
+    uint16_t* ad = reinterpret_cast<uint16_t*>(s_mem + a.o_ad);       // [D] ad_g
+    double* prod = reinterpret_cast<double*>(s_mem + sp.o_prod);      // [2N + 2][64] the chunk's terms per sum
+    double* drow = reinterpret_cast<double*>(s_mem + a.o_dist);       // [64] the chunk's |x - x_0|
+    SpCst* cst = reinterpret_cast<SpCst*>(s_mem + sp.o_cst);
+    const int n_out = 2 * N + 2;                                      // mass, N rewards, N actions, price; lane n_out: distance
+    const int rb = a.row_begin, rc = a.row_count;
+    const int A = sp.n_actions[dv];
+
+    // ---- the grouping of the tuples by price: per config, staged once; no entry leads out of bounds
+    for (int d = tid; d <= D; d += kSpBlock) first[d] = (uint16_t)min(max(sp.grp_first[d], 0), T);
+    for (int t = tid; t < T; t += kSpBlock) perm[t] = (uint16_t)min(max(sp.grp_perm[t], 0), T - 1);
+
+    for (int64_t g = bid; g < G; g += nblk) {
+        if (!sp_eps_ok(sp, g)) {                         // block-uniform: this game is not solved
+            sd_unsolved(a, g, tid);
+            continue;
+        }
+        __syncthreads();                                 // the game before is read to its end; the grouping is staged
+        const double* __restrict__ w0 = a.weights + g * T;
+
+        // ---- the game's rows and constants, x_0 and the deviator's rewards
+        sp_stage_game<1>(sp, s_mem, cst, g, tid);
+        for (int t = tid; t < T; t += kSpBlock) {
+            ma[t] = w0[t];
+            mb[t] = sp.reward[(int64_t)dv * T + t];
+        }
+        __syncthreads();
+        sp_normaliser(sp, s_mem, Z, tid);
+
+        // ---- per price: ad_g and the deviation step's Z
+        for (int d = tid; d < D; d += kSpBlock) {
+            double zm = 1.0, zd = 1.0;                   // Z_-d and Z with S_d = 1.0
+            bool have = false;
+            for (int j = 0; j < N; j++) {
+                const double Sj = j == dv ? 1.0 : sd_row_sum(sp, s_mem, j, d);
+                zd = j == 0 ? Sj : __dmul_rn(zd, Sj);
+                if (j == dv) continue;
+                zm = have ? __dmul_rn(zm, Sj) : Sj;
+                have = true;
+            }
+            int act;
+            if (a.use_policy) {
+                act = min((int)a.dev_policy[g * D + d], A - 1);
+            } else if (a.dev_action >= 0) {
+                act = a.dev_action;
+            } else {                                     // the one-period best response to the rivals' mixed policies
+                double bv;
+                act = first_max(A, [&](int k) THRL_SOLVE_INLINE { return sr_q<MAXN>(sp, s_mem, cst, mb, zm, dv, d, k); }, bv);
+            }
+            ad[d] = (uint16_t)act;
+            Zd[d] = zd;
+        }
+        __syncthreads();                                 // reward_d is read; ad_g of every price
+
+        // ---- dev_share's terms over the dead second iterate (D <= T): M_0(d) * (1 - P_d(ad_g(d)|d) / S_d(d))
+        for (int d = tid; d < D; d += kSpBlock) {
+            double M = 0.0;
+            const int e = first[d + 1];
+            for (int s = first[d]; s < e; s++) M = __dadd_rn(M, ma[perm[s]]);
+            const double own = __ddiv_rn(sr_prob(sp, s_mem, cst, dv, d, (int)ad[d]), sd_row_sum(sp, s_mem, dv, d));
+            mb[d] = __dmul_rn(M, __dsub_rn(1.0, own));
+        }
+
+        // ---- the baseline: what x_0 earns, and the share of periods the deviation changes
+        double acc = sd_sums(sp, ma, w0, prod, drow, tid);       // its first barrier also ends the pass above
+        const double base = acc;                         // lane 1 + i: base_reward_i
+        if (tid >= 1 && tid <= N) a.base_reward[(int64_t)(tid - 1) * G + g] = acc;
+        else if (tid > N && tid <= 2 * N) a.base_action[(int64_t)(tid - 1 - N) * G + g] = acc;
+        else if (tid == 2 * N + 1) a.base_price[g] = acc;
+        if (tid == 64) {
+            double s = 0.0;
+            for (int d = 0; d < D; d++) s = __dadd_rn(s, mb[d]);
+            a.dev_share[g] = s;
+        }
+
+        // ---- the deviator's row while the deviation lasts: P_d(k|d) = 1.0 for k = ad_g(d), else 0.0 (every thread is
+        // past the barriers of the sums, so past its reads of the own row)
+        if (sp.kind[dv] == 0) {
+            uint16_t* rq = reinterpret_cast<uint16_t*>(s_mem + sp.o_row[dv]);
+            for (int d = tid; d < D; d += kSpBlock) rq[d] = ad[d];
+            if (tid == 0) { cst->hi[dv] = 1.0; cst->lo[dv] = 0.0; }
+        } else {
+            float* rf = reinterpret_cast<float*>(s_mem + sp.o_row[dv]);
+            for (int d = tid; d < D; d += kSpBlock) {
+                const int act = ad[d];
+                for (int k = 0; k < A; k++) rf[d * A + k] = k == act ? 1.0f : 0.0f;
+            }
+        }
+        __syncthreads();                                 // the terms are read before the second iterate is written
+
+        // ---- K periods: the step x_{tau+1} = step_tau(x_tau), then the sums of x_{tau+1}
+        const double gam = a.sweep_gamma ? a.sweep_gamma[(int64_t)dv * G + g] : a.gamma;
+        double w = 1.0, gain = 0.0, gain_dev = 0.0, low = 0.0, Dist = 0.0;
+        int low_step = -1, ret = -1;
+        double* mo = ma;
+        double* mn = mb;
+        for (int tau = 0; tau < K; tau++) {
+            const bool dev = tau < L;
+            if (tau == L) sp_stage_game<1>(sp, s_mem, cst, g, tid);     // the agents' own rows from here on
+            sp_weights(sp, mo, first, perm, dev ? Zd : Z, W, tid);
+            __syncthreads();
+            for (int t = tid; t < T; t += kSpBlock) {
+                int off[MAXN];
+                sp_offsets<MAXN>(sp, t, off);
+                mn[t] = sp_price_sum<MAXN>(sp, s_mem, cst, W, off);
+            }
+            __syncthreads();
+            double* tm = mo; mo = mn; mn = tm;
+            acc = sd_sums(sp, mo, w0, prod, drow, tid);
+            Dist = __dmul_rn(0.5, acc);                  // the distance, on lane n_out
+            if (tid == 1 + dv) {
+                const double diff = __dsub_rn(acc, base);
+                const double term = __dmul_rn(w, diff);
+                gain = __dadd_rn(gain, term);
+                if (dev) {
+                    gain_dev = __dadd_rn(gain_dev, term);
+                } else if (tau == L || diff < low) {
+                    low = diff;
+                    low_step = tau;
+                }
+                w = __dmul_rn(w, gam);
+            }
+            if (tid == n_out && !dev && ret < 0 && Dist <= a.ret_tol) ret = tau;
+            const int r = tau - rb;
+            if (r >= 0 && r < rc) {
+                if (tid >= 1 && tid <= N) {
+                    if (a.reward_rows) a.reward_rows[((int64_t)r * N + (tid - 1)) * G + g] = acc;
+                } else if (tid > N && tid <= 2 * N) {
+                    if (a.action_rows) a.action_rows[((int64_t)r * N + (tid - 1 - N)) * G + g] = acc;
+                } else if (tid == 2 * N + 1) {
+                    if (a.price_rows) a.price_rows[(int64_t)r * G + g] = acc;
+                } else if (tid == n_out) {
+                    if (a.dist_rows) a.dist_rows[(int64_t)r * G + g] = Dist;
+                }
+            }
+        }
+        if (tid == 1 + dv) {
+            a.gain[g] = gain; a.gain_dev[g] = gain_dev; a.low[g] = low; a.low_step[g] = low_step;
+        } else if (tid == n_out) {
+            a.ret_step[g] = ret; a.dist[g] = Dist;
+        } else if (tid == 0) {
+            a.mass[g] = acc;
+        }
+    }
+}
+
+#ifndef THRL_SP_HOST_BUILD
+template <int MAXN>
+__global__ void __launch_bounds__(kSpBlock) k_sd_chain(const SdArgs a) {
+    extern __shared__ __align__(16) unsigned char s_mem[];
+    sd_block<MAXN>(a, s_mem, (int)threadIdx.x, (int)blockIdx.x, (int)gridDim.x);
+}
+#endif
+
+}  // namespace
+
+#ifndef THRL_SP_HOST_BUILD
+int launch_sampled_deviation(const SdArgs& a, int grid, hipStream_t s) {
+    return sp_launch(k_sd_chain<2>, k_sd_chain<kSpMaxA>, a, a.sp, grid, s);
+}
+#endif
+
+}  // namespace thrl

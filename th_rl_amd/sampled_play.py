@@ -61,14 +61,21 @@ def parse_options(opt, config):
     pi (store the distributions).  The optional key "response" (true or a dict, sampled_response.parse_options) asks for
     the best responses to the stochastic policies; it stays in the result, filled in, only when given, and together with
     "noise" it is refused unless it opts in with its own "noise": true (then the best responses are those under the same
-    demand noise, at sampled_play's noise_prob and resolution).  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
+    demand noise, at sampled_play's noise_prob and resolution).  The optional key "deviation" (true or a dict,
+    sampled_deviation.parse_options) asks for the deviation test of sampled play; it stays in the result, filled in, only
+    when given, and together with "noise" it is refused: the test under demand noise is the follow-up.  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
     run's own noise, refused for a noise-free run as training.greedy_stationary does; "resolution": the uniform cuts of
     the price axis behind the nodes}) asks for play under demand noise; it stays in the result, filled in, only when
     given, and with it start may be "reset".  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples, more than
     MAX_CELLS - 1 cells and a working set above a CU's LDS."""
     name = "training.sampled_play"
     tp.check_config(config)
-    noise = response = None
+    noise = response = deviation = None
+    if isinstance(opt, dict) and "deviation" in opt:
+        opt = dict(opt)
+        deviation = opt.pop("deviation")
+        if deviation is None or deviation is False:
+            deviation = None
     if isinstance(opt, dict) and "response" in opt:
         opt = dict(opt)
         response = opt.pop("response")
@@ -115,6 +122,11 @@ def parse_options(opt, config):
         if noise is not None and not opted:
             raise ValueError("%s: \"response\" with \"noise\": %s" % (name, sr.NOISE_FOLLOW_UP))
         out["response"] = sr.parse_options(response, config, noise=noise)
+    if deviation is not None:
+        from . import sampled_deviation as sd
+        if noise is not None:
+            raise ValueError("%s: \"deviation\" with \"noise\": %s" % (name, sd.NOISE_FOLLOW_UP))
+        out["deviation"] = sd.parse_options(deviation, config)
     return out
 
 
@@ -535,10 +547,12 @@ def greedy_noise_of(d, noise_prob):
     return g["stat_reward"], g["iters"]
 
 
-def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None, with_cycles=False):
+def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=None, with_cycles=False, spec=None,
+                    histograms=False, budget=None):
     """train_one's training.sampled_play outputs: the per-game splay_*.npy files and sampled_play.json.  with_cycles:
     this run wrote the gcyc_* files (training.greedy_cycles) just before; only then does the summary carry
-    delta_greedy_mean and randomness_cost_mean."""
+    delta_greedy_mean and randomness_cost_mean.  spec, histograms, budget: the run's group statistics, for the response
+    curves of the sub-key "deviation"."""
     noise = opt.get("noise")
     tabs = noise_tables(config, noise["resolution"]) if noise else tables(config)
     noise_prob = 0.0
@@ -552,7 +566,7 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=No
     cyc = greedy_cycles_of(exp_path, np.asarray(r["iters"]).size) if with_cycles else None
     gn = greedy_noise_of(exp_path, r["noise_prob"]) if noise else None
     summary = summarize(r, ids, n_groups, nash, cartel, opt["max_iters"], cycle_reward=cyc, greedy_noise=gn)
-    shown = {k: v for k, v in opt.items() if k != "response"}        # sampled_response.json holds its own options
+    shown = {k: v for k, v in opt.items() if k not in ("response", "deviation")}    # their own files hold their options
     an.save_json(os.path.join(exp_path, "sampled_play.json"),
                  describe(shown, r["T"], r["n_prices"], nash, cartel, summary, n_nodes=r.get("n_nodes")))
     if opt.get("response"):
@@ -564,4 +578,10 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=No
         else:
             sr.write_artefacts(exp_path, batch, config, opt["response"], ids, n_groups, epsilon=opt["epsilon"], tabs=tabs,
                                pi=r["pi"] if same else None)
+    if opt.get("deviation"):
+        from . import sampled_deviation as sd
+        same = opt["pi"] and opt["start"] == "uniform"
+        sd.write_artefacts(exp_path, batch, config, opt["deviation"], ids, n_groups, epsilon=opt["epsilon"], tabs=tabs,
+                           pi=r["pi"] if same else None, stat_iters=r["iters"] if same else None, spec=spec,
+                           histograms=histograms, budget=budget)
     return r

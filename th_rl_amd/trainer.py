@@ -77,6 +77,7 @@ kernels).  The JSON schema is the reference's; the optional extra keys in the
                                       # QTable, Reinforce and ActorCritic agents: sampled_play.json, splay_iters.npy int32
                                       # [G], splay_games.npy [4, G] (change, mass, price, agree), splay_reward.npy /
                                       # splay_action.npy / splay_epsilon.npy [N, G]; with pi splay_pi.npy [G, T]
+                                      # (its sub-keys "response" and "deviation": sampled_response.py, sampled_deviation.py)
                  "deviation": null,  # true or {"agents": [all], "steps": 32, "dev_len": 1, "action": "best_response",
                                      # "horizon": null}: after training (and the greedy statistics) the deviation
                                      # analysis of the greedy policies (deviation.py, QTable agents only): deviation.json

@@ -858,3 +858,41 @@ def sampled_response_noise_games(exp_path):
         nc = nc + ex[i]
     cols["nashconv"] = nc
     return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
+
+
+def sampled_deviation_summary(exp_path):
+    """A run's deviation test of sampled play (training.sampled_play.deviation: do the others' stochastic policies punish
+    a departure, and was it profitable): sampled_deviation.json's summary as a DataFrame with deviation_noise_summary's
+    columns, one row per (group, deviator) -- games, solved, deviates, dev_share_mean, unprofitable, gain_mean and gain_q*,
+    gain_dev_mean, low_mean, returned, ret_step_mean, dist_mean -- plus T and n_prices.  The expected response curves of a
+    run that also has training.group_stats are the per-group statistics of prefix "sdev<d>":
+    group_quantiles(exp_path, group, "total", prefix="sdev0"), one row per period after the shock."""
+    if not os.path.isfile(os.path.join(exp_path, "sampled_deviation.json")):
+        raise KeyError("no deviation test of sampled play (sampled_deviation.json) under %s (training.sampled_play.deviation)"
+                       % exp_path)
+    desc = _load_json(exp_path, "sampled_deviation.json")
+    df = pandas.DataFrame(desc["summary"])
+    df["T"], df["n_prices"] = int(desc["T"]), int(desc["n_prices"])
+    return df
+
+
+def sampled_deviation_games(exp_path, deviator=0):
+    """Per-game results of the deviation test of sampled play for `deviator`, one row per game indexed by its GLOBAL id:
+    stat_iters, gamma, base_price, dev_share, gain, gain_dev, low, dist, mass, low_step, ret_step, base_reward_<i> /
+    base_action_<i> / epsilon_<i> and solved."""
+    from th_rl_amd import sampled_deviation as sd
+    _run_dirs(exp_path, "sdev_stat_iters.npy", "deviation test of sampled play", "sampled_play.deviation", shards=False)
+    desc = _load_json(exp_path, "sampled_deviation.json")
+    if int(deviator) not in desc["options"]["agents"]:
+        raise KeyError("deviator %d was not analysed (agents %s)" % (int(deviator), desc["options"]["agents"]))
+    off = _game_offset(exp_path, exp_path)
+    g = sd.load_games(exp_path, int(deviator))
+    cols = {f: g[f] for f in ("stat_iters", "gamma")}
+    cols.update({f: g[f] for f in sd.FLOAT + sd.INT})
+    for i in range(g["base_reward"].shape[0]):
+        cols["base_reward_%d" % i] = g["base_reward"][i]
+        cols["base_action_%d" % i] = g["base_action"][i]
+        cols["epsilon_%d" % i] = g["epsilon"][i]
+    cols["solved"] = g["solved"]
+    n = g["stat_iters"].shape[0]
+    return pandas.DataFrame(cols, index=pandas.RangeIndex(off, off + n, name="game"))
