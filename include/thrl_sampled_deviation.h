@@ -18,7 +18,8 @@ extern "C" {
  * run, thrl_sampled_response what each agent gives up against rivals that sample; this call asks the question that
  * separates collusion from failure to learn: if one agent departs from its policy for a few periods, do the others'
  * sampled policies punish it, how deep is the punishment, how long until play is back, and was the departure
- * profitable?  No reference counterpart.  Noise-free play only.  No episodes are sampled: the tuple played is a Markov
+ * profitable?  No reference counterpart.  Noise-free play; under demand noise the call is thrl_sampled_deviation_noise
+ * (include/thrl_sampled_deviation_noise.h).  No episodes are sampled: the tuple played is a Markov
  * chain on the T action tuples whose row depends on the tuple only through its price, and the call propagates a
  * distribution through that chain, L periods with the deviator's policy replaced, then K - L plain periods, and records
  * what every period's distribution earns.  Of a valid cfg only n_agents and n_actions are used (cfg.gamma is not read);

@@ -518,6 +518,33 @@ class SampledDeviationArgs(ctypes.Structure):
     ]
 
 
+SDN_POLICY = 1
+SDN_MAX_LDS = 160 * 1024
+
+
+class SampledDeviationNoiseArgs(ctypes.Structure):
+    """thrl_sampled_deviation_noise_args (include/thrl_sampled_deviation_noise.h)"""
+    _fields_ = [
+        ("n_games", ctypes.c_int32), ("n_tuples", ctypes.c_int32), ("n_prices", ctypes.c_int32), ("n_nodes", ctypes.c_int32),
+        ("band_w", ctypes.c_int32), ("deviator", ctypes.c_int32), ("dev_len", ctypes.c_int32), ("n_steps", ctypes.c_int32),
+        ("dev_action", ctypes.c_int32), ("row_begin", ctypes.c_int32), ("row_count", ctypes.c_int32), ("flags", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 2),
+        ("kind", ctypes.c_int32 * MAXA), ("eps", ctypes.c_double * MAXA), ("gamma", ctypes.c_double),
+        ("ret_tol", ctypes.c_double), ("noise_prob", ctypes.c_double),
+        ("eps_g", ctypes.c_void_p), ("sweep_gamma", ctypes.c_void_p), ("noise_prob_g", ctypes.c_void_p),
+        ("prob", ctypes.c_void_p * MAXA), ("nprob", ctypes.c_void_p * MAXA),
+        ("dpolicy", ctypes.c_void_p), ("npolicy", ctypes.c_void_p), ("dev_policy", ctypes.c_void_p),
+        ("grp_first", ctypes.c_void_p), ("grp_perm", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("scaled", ctypes.c_void_p),
+        ("price", ctypes.c_void_p), ("band_lo", ctypes.c_void_p), ("band", ctypes.c_void_p), ("noise_price", ctypes.c_void_p),
+        ("noise_reward", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+        ("base_reward", ctypes.c_void_p), ("base_action", ctypes.c_void_p), ("base_price", ctypes.c_void_p),
+        ("dev_share", ctypes.c_void_p), ("gain", ctypes.c_void_p), ("gain_dev", ctypes.c_void_p), ("low", ctypes.c_void_p),
+        ("low_step", ctypes.c_void_p), ("ret_step", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("mass", ctypes.c_void_p),
+        ("reward_rows", ctypes.c_void_p), ("action_rows", ctypes.c_void_p), ("price_rows", ctypes.c_void_p),
+        ("dist_rows", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/thrl.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "thrl_version", "thrl_last_error", "thrl_build_info", "thrl_ablate_mask", "thrl_table_stride", "thrl_table_offset",
@@ -539,6 +566,8 @@ RESPONSE_SYMBOLS = ["thrl_sampled_response"]
 RESPONSE_NOISE_SYMBOLS = ["thrl_sampled_response_noise"]
 # every symbol include/thrl_sampled_deviation.h declares
 SAMPLED_DEVIATION_SYMBOLS = ["thrl_sampled_deviation"]
+# every symbol include/thrl_sampled_deviation_noise.h declares
+SAMPLED_DEVIATION_NOISE_SYMBOLS = ["thrl_sampled_deviation_noise"]
 CAC_PARAMS = 1283
 
 _lib = None
@@ -689,6 +718,8 @@ def load():
     L.thrl_sampled_response_noise.argtypes = [cfgp, ctypes.POINTER(SampledResponseNoiseArgs), vp]
     L.thrl_sampled_deviation.restype = ctypes.c_int
     L.thrl_sampled_deviation.argtypes = [cfgp, ctypes.POINTER(SampledDeviationArgs), vp]
+    L.thrl_sampled_deviation_noise.restype = ctypes.c_int
+    L.thrl_sampled_deviation_noise.argtypes = [cfgp, ctypes.POINTER(SampledDeviationNoiseArgs), vp]
     if L.thrl_version() != ABI_VERSION:
         raise ThrlError("th_rl_amd: ABI version mismatch (%d)" % L.thrl_version())
     _lib = L

@@ -627,12 +627,32 @@ class AnalysisMethods:
         = the deviator's own), low and low_step (the deepest punishment), ret_step (the first period at which the
         distribution is back within ret_tol in total variation, else -1), dist, mass, gamma, stat_iters [G]; epsilon
         [N, G]; solved [G].  rows=True adds reward_rows / action_rows [steps, N, G] and price_rows / dist_rows [steps, G];
-        group_stats (a GroupSpec): the rows are reduced on the device.  Noise-free play only."""
+        group_stats (a GroupSpec): the rows are reduced on the device.  Noise-free play; under demand noise:
+        sampled_deviation_noise."""
         from . import sampled_deviation as sd
         self._ready()
         return sd.run(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, epsilon=epsilon, gamma=gamma,
                       ret_tol=ret_tol, weights=weights, rows=rows, group_stats=group_stats, budget=budget, n_games=n_games,
                       probs=probs, dpolicy=dpolicy, tabs=tabs, tol=tol, max_iters=max_iters)
+
+    def sampled_deviation_noise(self, deviator=0, steps=32, dev_len=1, action="best_response", epsilon="current", gamma=None,
+                                ret_tol=1e-6, weights="stationary", rows=False, group_stats=None, budget=None, n_games=None,
+                                probs=None, dpolicy=None, tabs=None, tol=1e-12, max_iters=8192, noise_prob=None, resolution=1024,
+                                nprobs=None, npolicy=None):
+        """sampled_deviation under DEMAND NOISE (sampled_deviation.run_noise, thrl_sampled_deviation_noise; definitions in
+        include/thrl_sampled_deviation_noise.h): the same impulse response in the chain of sampled_play(noise_prob=...),
+        every period's reward and price in expectation over the redrawn demand.  The deviator's strategy lives on the D
+        distinct prices and then the Jn nodes of the redrawn price (sampled_play.noise_tables(config, resolution)): action
+        "best_response" is the one-period best response at each of them, "best_reply" sampled_response_noise's
+        br_policy, an array is [G, D + Jn].  noise_prob: a number in [0, 1], an array [G] or None = the batch's own;
+        weights "stationary" = the long-run distribution under the same noise.  Returns sampled_deviation's dict plus
+        noise_prob, max_jump [G], n_nodes, lds_bytes, and dev_policy [G, D + Jn] when a strategy was given or computed."""
+        from . import sampled_deviation as sd
+        self._ready()
+        return sd.run_noise(self, deviator=deviator, steps=steps, dev_len=dev_len, action=action, epsilon=epsilon, gamma=gamma,
+                            ret_tol=ret_tol, weights=weights, rows=rows, group_stats=group_stats, budget=budget,
+                            n_games=n_games, probs=probs, dpolicy=dpolicy, tabs=tabs, tol=tol, max_iters=max_iters,
+                            noise_prob=noise_prob, resolution=resolution, nprobs=nprobs, npolicy=npolicy)
 
     def track_convergence(self, window, every=1, snapshot=False):
         """A convergence.Tracker of every game's greedy policies (thrl_policy_track; definitions in include/thrl.h),

@@ -25,11 +25,12 @@ SOURCES = ["thrl_api.hip", "thrl_api_analysis.hip", "thrl_generic.hip", "thrl_op
            "thrl_wave_f64n.hip", "thrl_wave_f64nc.hip", "thrl_wave_f64s.hip", "thrl_nn.hip", "thrl_mixed.hip", "thrl_cac.hip",
            "thrl_tuple.hip", "thrl_tuple_f32.hip", "thrl_tuple_f64.hip", "thrl_tuple_f32_noise.hip", "thrl_tuple_f64_noise.hip", "thrl_tuple_f32_sweep.hip", "thrl_tuple_f64_sweep.hip",
            "thrl_ptuple.hip", "thrl_stats.hip", "thrl_ewm.hip", "thrl_deviation.hip", "thrl_converge.hip", "thrl_equilibrium.hip", "thrl_crossplay.hip", "thrl_attractors.hip", "thrl_stationary.hip", "thrl_equilibrium_noise.hip", "thrl_deviation_noise.hip", "thrl_tuple_play.hip", "thrl_tuple_analysis.hip",
-           "thrl_tuple_attractors.hip", "thrl_tuple_stationary.hip", "thrl_tuple_equilibrium_noise.hip", "thrl_tuple_deviation_noise.hip", "thrl_sampled.hip", "thrl_sampled_noise.hip", "thrl_sampled_response.hip", "thrl_sampled_response_noise.hip", "thrl_sampled_deviation.hip"]
-HEADERS = ["thrl_device.h", "thrl_kernels.h", "thrl_host.h", "thrl_wave_lut.h", "thrl_wave_kernel.h", "thrl_tuple_kernel.h", "thrl_policy.h", "thrl_cac.h", "thrl_deviation.h", "thrl_converge.h", "thrl_equilibrium.h", "thrl_crossplay.h", "thrl_attractors.h", "thrl_stationary.h", "thrl_equilibrium_noise.h", "thrl_deviation_noise.h", "thrl_tuple_play.h", "thrl_tuple_analysis.h", "thrl_tuple_attractors.h", "thrl_tuple_stationary.h", "thrl_tuple_equilibrium_noise.h", "thrl_tuple_deviation_noise.h", "thrl_sampled.h", "thrl_chain_dev.h", "thrl_group_dev.h", "thrl_walk_dev.h", "thrl_solve_dev.h", "thrl_sampled_dev.h", "thrl_sampled_noise.h", "thrl_sampled_response.h", "thrl_response_dev.h", "thrl_sampled_response_noise.h", "thrl_sampled_deviation.h",
+           "thrl_tuple_attractors.hip", "thrl_tuple_stationary.hip", "thrl_tuple_equilibrium_noise.hip", "thrl_tuple_deviation_noise.hip", "thrl_sampled.hip", "thrl_sampled_noise.hip", "thrl_sampled_response.hip", "thrl_sampled_response_noise.hip", "thrl_sampled_deviation.hip", "thrl_sampled_deviation_noise.hip"]
+HEADERS = ["thrl_device.h", "thrl_kernels.h", "thrl_host.h", "thrl_wave_lut.h", "thrl_wave_kernel.h", "thrl_tuple_kernel.h", "thrl_policy.h", "thrl_cac.h", "thrl_deviation.h", "thrl_converge.h", "thrl_equilibrium.h", "thrl_crossplay.h", "thrl_attractors.h", "thrl_stationary.h", "thrl_equilibrium_noise.h", "thrl_deviation_noise.h", "thrl_tuple_play.h", "thrl_tuple_analysis.h", "thrl_tuple_attractors.h", "thrl_tuple_stationary.h", "thrl_tuple_equilibrium_noise.h", "thrl_tuple_deviation_noise.h", "thrl_sampled.h", "thrl_chain_dev.h", "thrl_group_dev.h", "thrl_walk_dev.h", "thrl_solve_dev.h", "thrl_sampled_dev.h", "thrl_sampled_noise.h", "thrl_sampled_response.h", "thrl_response_dev.h", "thrl_sampled_response_noise.h", "thrl_sampled_deviation.h", "thrl_sampled_noise_dev.h", "thrl_sampled_deviation_dev.h", "thrl_sampled_deviation_noise.h",
            os.path.join("..", "..", "include", "thrl.h"), os.path.join("..", "..", "include", "thrl_response.h"),
            os.path.join("..", "..", "include", "thrl_response_noise.h"),
-           os.path.join("..", "..", "include", "thrl_sampled_deviation.h")]
+           os.path.join("..", "..", "include", "thrl_sampled_deviation.h"),
+           os.path.join("..", "..", "include", "thrl_sampled_deviation_noise.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wno-pass-failed"]
 
 

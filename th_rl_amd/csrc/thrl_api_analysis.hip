@@ -25,6 +25,7 @@
 #include "thrl_tuple_play.h"
 #include "thrl_sampled.h"
 #include "thrl_sampled_deviation.h"
+#include "thrl_sampled_deviation_noise.h"
 #include "thrl_sampled_noise.h"
 #include "thrl_sampled_response.h"
 #include "thrl_sampled_response_noise.h"
@@ -33,6 +34,7 @@
 #include "../../include/thrl_response.h"
 #include "../../include/thrl_response_noise.h"
 #include "../../include/thrl_sampled_deviation.h"
+#include "../../include/thrl_sampled_deviation_noise.h"
 
 using namespace thrl;
 using namespace thrl::host;
@@ -125,7 +127,7 @@ int check_cell_limit(const char* call, int n_cells) {
     return ok ? THRL_OK : fail(THRL_ERR_UNSUPPORTED, "%s: n_cells=%d, at most %d", call, n_cells, THRL_STAT_MAX_CELLS);
 }
 // ---- the checks of the calls on sampled play (thrl_sampled_chain, thrl_sampled_noise_chain, thrl_sampled_response,
-// thrl_sampled_response_noise, thrl_sampled_deviation)
+// thrl_sampled_response_noise, thrl_sampled_deviation, thrl_sampled_deviation_noise)
 int check_prices(int n_prices, int n_tuples) {
     const bool ok = n_prices >= 1 && n_prices <= n_tuples;
     return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "n_prices=%d out of [1, n_tuples=%d]", n_prices, n_tuples);
@@ -133,6 +135,10 @@ int check_prices(int n_prices, int n_tuples) {
 int check_nodes_band(int n_nodes, int band_w) {
     const bool ok = n_nodes >= 2 && band_w >= 1;
     return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "n_nodes=%d must be >= 2 and band_w=%d >= 1", n_nodes, band_w);
+}
+int check_noise_prob_closed(const double* noise_prob_g, double noise_prob) {    // p = 0 allowed: the chains under noise
+    const bool ok = noise_prob_g || (noise_prob >= 0.0 && noise_prob <= 1.0);
+    return ok ? THRL_OK : fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of [0, 1]", noise_prob);
 }
 int check_node_limit(const char* call, int n_nodes) {
     const bool ok = n_nodes <= THRL_STAT_MAX_CELLS;
@@ -933,8 +939,7 @@ int thrl_sampled_noise_chain(const thrl_cfg* c, const thrl_sampled_noise_chain_a
     if ((rc = check_nodes_band(x->n_nodes, x->band_w)) != THRL_OK) return rc;
     if ((rc = check_iters_tol(x->max_iters, x->tol)) != THRL_OK) return rc;
     if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
-    if (!x->noise_prob_g && !(x->noise_prob >= 0.0 && x->noise_prob <= 1.0))
-        return fail(THRL_ERR_BAD_CONFIG, "noise_prob=%g out of [0, 1]", x->noise_prob);
+    if ((rc = check_noise_prob_closed(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
     if ((rc = check_node_limit("thrl_sampled_noise_chain", x->n_nodes)) != THRL_OK) return rc;
     thrl::SpnArgs a;
     memset(&a, 0, sizeof(a));
@@ -1115,6 +1120,82 @@ int thrl_sampled_deviation(const thrl_cfg* c, const thrl_sampled_deviation_args*
     if (rc) return rc;
     const int e = thrl::launch_sampled_deviation(a, grid, (hipStream_t)stream);
     return e ? hip_fail(e, "k_sd_chain launch") : THRL_OK;
+}
+
+int thrl_sampled_deviation_noise(const thrl_cfg* c, const thrl_sampled_deviation_noise_args* x, void* stream) {
+    static_assert(THRL_SDN_MAX_LDS == THRL_SD_MAX_LDS && THRL_SDN_POLICY == THRL_SD_POLICY, "the two deviation tests of sampled play agree");
+    int rc = validate(c);
+    if (rc) return rc;
+    if (!x) return fail(THRL_ERR_NULL, "args is NULL");
+    const int N = c->n_agents;
+    // thrl_sampled_deviation's checks in its order with thrl_sampled_noise_chain's of the nodes and the noise between them;
+    // every host-visible argument is checked, and the working set planned, before any pointer is looked at
+    if ((rc = check_games(x->n_games)) != THRL_OK) return rc;
+    if (x->flags & ~THRL_SDN_POLICY) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
+    for (int k = 0; k < 2; k++)
+        if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_nodes_band(x->n_nodes, x->band_w)) != THRL_OK) return rc;
+    if ((rc = check_deviator(c, x->deviator, x->dev_len, x->n_steps)) != THRL_OK) return rc;
+    const bool use_policy = (x->flags & THRL_SDN_POLICY) != 0;
+    if (use_policy) {                                    // the strategy is dev_policy: no action of the deviator is one
+        thrl_cfg none = *c;
+        none.n_actions[x->deviator] = 0;
+        if ((rc = check_dev_action(&none, x->deviator, x->dev_action)) != THRL_OK) return rc;
+    } else if ((rc = check_dev_action(c, x->deviator, x->dev_action)) != THRL_OK) {
+        return rc;
+    }
+    if ((rc = check_rows(x->row_begin, x->row_count, x->n_steps)) != THRL_OK) return rc;
+    if ((rc = check_tol(x->ret_tol, "ret_tol")) != THRL_OK) return rc;
+    if (!x->sweep_gamma) {                               // gamma in [0, 1]: both ends through the check of a tolerance
+        if ((rc = check_tol(x->gamma, "gamma")) != THRL_OK) return rc;
+        if ((rc = check_tol(1.0 - x->gamma, "1 - gamma")) != THRL_OK) return rc;
+    }
+    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    if ((rc = check_noise_prob_closed(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
+    if ((rc = check_node_limit("thrl_sampled_deviation_noise", x->n_nodes)) != THRL_OK) return rc;
+    thrl::SdnArgs a;
+    memset(&a, 0, sizeof(a));
+    thrl::SpnArgs& na = a.n;
+    SpArgs& sa = na.sp;
+    thrl::SdArgs& sd = a.sd;
+    sp_fill_head(sa, c, x);
+    na.Jn = x->n_nodes; na.W = x->band_w; na.noise_prob = x->noise_prob;
+    for (int i = 0; i < N; i++) na.nprob[i] = x->nprob[i];
+    const int64_t lds = thrl::sdn_layout(a);         // the working set of include/thrl_sampled_deviation_noise.h
+    // (the cells of this analysis are the deviator's states: the distinct prices and the nodes)
+    if (lds > THRL_SDN_MAX_LDS) return lds_refusal("thrl_sampled_deviation_noise", lds, N, x->n_prices + x->n_nodes);
+    for (int i = 0; i < N; i++)
+        if (x->kind[i] != 0 && (!x->prob[i] || !x->nprob[i])) return missing_rows(i);
+    if (!x->dpolicy || !x->npolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->scaled || !x->price)
+        return missing("dpolicy / npolicy / grp_first / grp_perm / reward / scaled / price");
+    if (!x->band_lo || !x->band || !x->noise_price || !x->noise_reward) return missing("band_lo / band / noise_price / noise_reward");
+    if (!x->weights) return missing("weights");
+    if (use_policy && !x->dev_policy) return missing("with THRL_SDN_POLICY, dev_policy");
+    if (!x->base_reward || !x->base_action || !x->base_price || !x->dev_share || !x->gain || !x->gain_dev || !x->low
+        || !x->low_step || !x->ret_step || !x->dist || !x->mass)
+        return missing("base_reward / base_action / base_price / dev_share / gain / gain_dev / low / low_step / ret_step / "
+                       "dist / mass");
+    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm;
+    sa.reward = x->reward; sa.scaled = x->scaled; sa.price = x->price;
+    na.noise_prob_g = x->noise_prob_g; na.npolicy = x->npolicy; na.band_lo = x->band_lo; na.band = x->band;
+    na.noise_price = x->noise_price; na.noise_reward = x->noise_reward;
+    sd.d = x->deviator; sd.L = x->dev_len; sd.K = x->n_steps; sd.dev_action = x->dev_action; sd.use_policy = use_policy;
+    sd.row_begin = x->row_begin; sd.row_count = x->row_count;
+    sd.gamma = x->gamma; sd.ret_tol = x->ret_tol;
+    sd.sweep_gamma = x->sweep_gamma; sd.dev_policy = x->dev_policy; sd.weights = x->weights;
+    sd.base_reward = x->base_reward; sd.base_action = x->base_action; sd.base_price = x->base_price;
+    sd.dev_share = x->dev_share; sd.gain = x->gain; sd.gain_dev = x->gain_dev; sd.low = x->low; sd.low_step = x->low_step;
+    sd.ret_step = x->ret_step; sd.dist = x->dist; sd.mass = x->mass;
+    sd.reward_rows = x->reward_rows; sd.action_rows = x->action_rows; sd.price_rows = x->price_rows; sd.dist_rows = x->dist_rows;
+    int grid = 0;
+    rc = sp_plan_grid(sa, kSdnMaxBlocksPerCu, &grid,
+                      [&](int) { return lds_refusal("thrl_sampled_deviation_noise", lds, N, x->n_prices + x->n_nodes); });
+    if (rc) return rc;
+    const int e = thrl::launch_sampled_deviation_noise(a, grid, (hipStream_t)stream);
+    return e ? hip_fail(e, "k_sdn_chain launch") : THRL_OK;
 }
 
 }  // extern "C"

@@ -19,70 +19,15 @@
 //   actions, 2 N + 1 the price -- and lane 2 N + 2 the distance from its own staging row.  The lane of a sum keeps what is
 //   derived from it in registers over the periods, as k_tdn_chain does: lane 1 + d the gain and the low, lane 2 N + 2 the
 //   distance and ret_step.  x_0 is re-read from global memory (coalesced) for the distance.  No atomic is involved.
+//   The row sum, the unsolved outputs and the period's sums sit in thrl_sampled_deviation_dev.h, shared with k_sdn_chain.
 //   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
 #include "thrl_response_dev.h"
 #include "thrl_sampled_deviation.h"
+#include "thrl_sampled_deviation_dev.h"
 
 namespace thrl {
 
 namespace {
-
-// S_j(d) from the staged rows
-__device__ __forceinline__ double sd_row_sum(const SpArgs& sp, const unsigned char* s_mem, int j, int d) {
-    if (sp.kind[j] == 0) return 1.0;
-    const int A = sp.n_actions[j];
-    const float* rf = reinterpret_cast<const float*>(s_mem + sp.o_row[j]) + d * A;
-    double S = 0.0;
-    for (int k = 0; k < A; k++) S = __dadd_rn(S, (double)rf[k]);
-    return S;
-}
-
-// game g is not solved: zeros in every float64 output, its rows included, and -1 in low_step and ret_step
-__device__ __forceinline__ void sd_unsolved(const SdArgs& a, int64_t g, int tid) {
-    const int N = a.sp.N, G = a.sp.G, rc = a.row_count;
-    if (tid < N) {
-        a.base_reward[(int64_t)tid * G + g] = 0.0;
-        a.base_action[(int64_t)tid * G + g] = 0.0;
-    }
-    if (tid == 0) {
-        a.base_price[g] = 0.0; a.dev_share[g] = 0.0; a.gain[g] = 0.0; a.gain_dev[g] = 0.0; a.low[g] = 0.0; a.dist[g] = 0.0;
-        a.mass[g] = 0.0; a.low_step[g] = -1; a.ret_step[g] = -1;
-    }
-    for (int r = tid; r < rc * N; r += kSpBlock) {
-        if (a.reward_rows) a.reward_rows[(int64_t)r * G + g] = 0.0;
-        if (a.action_rows) a.action_rows[(int64_t)r * G + g] = 0.0;
-    }
-    for (int r = tid; r < rc; r += kSpBlock) {
-        if (a.price_rows) a.price_rows[(int64_t)r * G + g] = 0.0;
-        if (a.dist_rows) a.dist_rows[(int64_t)r * G + g] = 0.0;
-    }
-}
-
-// the ordered sums of one distribution m against x_0 = w0; lane o <= 2N + 2 its own: 0 the mass, 1 .. N the rewards,
-// N + 1 .. 2N the actions, 2N + 1 the price, 2N + 2 the sum of |m - x_0| (staged in drow)
-__device__ __forceinline__ double sd_sums(const SpArgs& sp, const double* m, const double* __restrict__ w0, double* prod,
-                                          double* drow, int tid) {
-    const int N = sp.N, T = sp.T, n_out = 2 * N + 2;
-    double acc = 0.0;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-        const int t = t0 + tid;
-        if (tid < 64 && t < T) {
-            const double mt = m[t];
-            prod[tid] = mt;
-            for (int i = 0; i < N; i++) {
-                prod[(1 + i) * 64 + tid] = __dmul_rn(mt, sp.reward[(int64_t)i * T + t]);
-                prod[(1 + N + i) * 64 + tid] = __dmul_rn(mt, sp.scaled[(int64_t)i * T + t]);
-            }
-            prod[(1 + 2 * N) * 64 + tid] = __dmul_rn(mt, sp.price[t]);
-            drow[tid] = fabs(__dsub_rn(mt, w0[t]));
-        }
-        __syncthreads();
-        const int n = min(64, T - t0);
-        acc = tid == n_out ? chain_read_back(drow, 1, n, acc, 0) : chain_read_back(prod, n_out, n, acc, tid);
-        __syncthreads();
-    }
-    return acc;
-}
 
 template <int MAXN>
 __device__ __forceinline__ void sd_block(const SdArgs& a, unsigned char* s_mem, int tid, int bid, int nblk) {
@@ -109,7 +54,7 @@ __device__ __forceinline__ void sd_block(const SdArgs& a, unsigned char* s_mem, 
 
     for (int64_t g = bid; g < G; g += nblk) {
         if (!sp_eps_ok(sp, g)) {                         // block-uniform: this game is not solved
-            sd_unsolved(a, g, tid);
+            sd_unsolved(sp, a, g, tid);
             continue;
         }
         __syncthreads();                                 // the game before is read to its end; the grouping is staged

@@ -63,7 +63,8 @@ def parse_options(opt, config):
     "noise" it is refused unless it opts in with its own "noise": true (then the best responses are those under the same
     demand noise, at sampled_play's noise_prob and resolution).  The optional key "deviation" (true or a dict,
     sampled_deviation.parse_options) asks for the deviation test of sampled play; it stays in the result, filled in, only
-    when given, and together with "noise" it is refused: the test under demand noise is the follow-up.  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
+    when given, and together with "noise" it is refused unless it opts in with its own "noise": true (then the test is the
+    one under the same demand noise, at sampled_play's noise_prob and resolution).  The optional key "noise" (true or {"noise_prob": a number in [0, 1] or None = the
     run's own noise, refused for a noise-free run as training.greedy_stationary does; "resolution": the uniform cuts of
     the price axis behind the nodes}) asks for play under demand noise; it stays in the result, filled in, only when
     given, and with it start may be "reset".  Refuses a CAC agent, more than tuple_play.MAX_TUPLES tuples, more than
@@ -124,9 +125,10 @@ def parse_options(opt, config):
         out["response"] = sr.parse_options(response, config, noise=noise)
     if deviation is not None:
         from . import sampled_deviation as sd
-        if noise is not None:
+        opted = isinstance(deviation, dict) and deviation.get("noise") not in (None, False)    # (checked by its parser)
+        if noise is not None and not opted:
             raise ValueError("%s: \"deviation\" with \"noise\": %s" % (name, sd.NOISE_FOLLOW_UP))
-        out["deviation"] = sd.parse_options(deviation, config)
+        out["deviation"] = sd.parse_options(deviation, config, noise=noise)
     return out
 
 
@@ -581,7 +583,10 @@ def write_artefacts(exp_path, batch, config, opt, ids, n_groups, tuple_policy=No
     if opt.get("deviation"):
         from . import sampled_deviation as sd
         same = opt["pi"] and opt["start"] == "uniform"
-        sd.write_artefacts(exp_path, batch, config, opt["deviation"], ids, n_groups, epsilon=opt["epsilon"], tabs=tabs,
-                           pi=r["pi"] if same else None, stat_iters=r["iters"] if same else None, spec=spec,
-                           histograms=histograms, budget=budget)
+        more = dict(epsilon=opt["epsilon"], tabs=tabs, pi=r["pi"] if same else None, stat_iters=r["iters"] if same else None,
+                    spec=spec, histograms=histograms, budget=budget)
+        if opt["deviation"].get("noise"):
+            sd.write_artefacts_noise(exp_path, batch, config, opt["deviation"], ids, n_groups, r["noise_prob"], **more)
+        else:
+            sd.write_artefacts(exp_path, batch, config, opt["deviation"], ids, n_groups, **more)
     return r

@@ -880,14 +880,41 @@ def sampled_deviation_games(exp_path, deviator=0):
     """Per-game results of the deviation test of sampled play for `deviator`, one row per game indexed by its GLOBAL id:
     stat_iters, gamma, base_price, dev_share, gain, gain_dev, low, dist, mass, low_step, ret_step, base_reward_<i> /
     base_action_<i> / epsilon_<i> and solved."""
+    return _sampled_deviation_games(exp_path, deviator, "sdev", "sampled_deviation.json", "deviation test of sampled play",
+                                    "sampled_play.deviation", ())
+
+
+def sampled_deviation_noise_summary(exp_path):
+    """A run's deviation test of sampled play UNDER DEMAND NOISE (training.sampled_play.deviation with "noise": true beside
+    sampled_play's "noise"): sampled_deviation_noise.json's summary as a DataFrame with sampled_deviation_summary's
+    columns plus max_jump_max, and T, n_prices, n_nodes and resolution.  The expected response curves of a run that also
+    has training.group_stats are the per-group statistics of prefix "sdevn<d>"."""
+    if not os.path.isfile(os.path.join(exp_path, "sampled_deviation_noise.json")):
+        raise KeyError("no deviation test of sampled play under demand noise (sampled_deviation_noise.json) under %s "
+                       "(training.sampled_play.deviation with \"noise\")" % exp_path)
+    desc = _load_json(exp_path, "sampled_deviation_noise.json")
+    df = pandas.DataFrame(desc["summary"])
+    for f in ("T", "n_prices", "n_nodes", "resolution"):
+        df[f] = int(desc[f])
+    return df
+
+
+def sampled_deviation_noise_games(exp_path, deviator=0):
+    """sampled_deviation_games' columns for the test under demand noise, plus noise_prob and max_jump."""
+    return _sampled_deviation_games(exp_path, deviator, "sdevn", "sampled_deviation_noise.json",
+                                    "deviation test of sampled play under demand noise", "sampled_play.deviation with \"noise\"",
+                                    ("noise_prob", "max_jump"))
+
+
+def _sampled_deviation_games(exp_path, deviator, prefix, json_name, what, key, more):
     from th_rl_amd import sampled_deviation as sd
-    _run_dirs(exp_path, "sdev_stat_iters.npy", "deviation test of sampled play", "sampled_play.deviation", shards=False)
-    desc = _load_json(exp_path, "sampled_deviation.json")
+    _run_dirs(exp_path, prefix + "_stat_iters.npy", what, key, shards=False)
+    desc = _load_json(exp_path, json_name)
     if int(deviator) not in desc["options"]["agents"]:
         raise KeyError("deviator %d was not analysed (agents %s)" % (int(deviator), desc["options"]["agents"]))
     off = _game_offset(exp_path, exp_path)
-    g = sd.load_games(exp_path, int(deviator))
-    cols = {f: g[f] for f in ("stat_iters", "gamma")}
+    g = sd.load_games(exp_path, int(deviator), prefix)
+    cols = {f: g[f] for f in ("stat_iters", "gamma") + tuple(more)}
     cols.update({f: g[f] for f in sd.FLOAT + sd.INT})
     for i in range(g["base_reward"].shape[0]):
         cols["base_reward_%d" % i] = g["base_reward"][i]
