@@ -3,76 +3,29 @@
 // the mirror's outputs that tests/sampled_deviation_mirror.write_case writes, runs every game through sd_block and
 // compares every output bit for bit.  Built as host code (hipcc -x hip --cuda-host-only -DTHRL_SP_HOST_BUILD), so that
 // thrl_solve_dev.h's __host__ __device__ pieces are the ones the device build uses; it makes no HIP call and needs no GPU.
-#include <cmath>
-#include <hip/hip_runtime.h>
-// thrl_chain_dev.h's read-back as host code: response_check.h's first include would bring it as HIP declares it, as device
-// functions, before its shims stand
-#pragma push_macro("__device__")
-#undef __device__
-#define __device__
-#define __dadd_rn(a, b) ((a) + (b))
-#define __dsub_rn(a, b) ((a) - (b))
-#define __dmul_rn(a, b) ((a) * (b))
-#include "../th_rl_amd/csrc/thrl_chain_dev.h"
-#undef __dadd_rn
-#undef __dsub_rn
-#undef __dmul_rn
-#pragma pop_macro("__device__")
-#include "response_check.h"
+// What it shares with sampled_deviation_noise_check.cpp is in deviation_check.h.
+#include "deviation_check.h"
 #include "../th_rl_amd/csrc/thrl_sampled_deviation.hip"
 
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
-    FILE* f = fopen(argv[1], "rb");
-    if (!f) return 2;
+    SdCase c{fopen(argv[1], "rb")};
+    if (!c.f) return 2;
     // G N T D deviator dev_len n_steps dev_action has_dev_policy has_eps_g has_gamma_g row_begin row_count n_blocks
-    auto h = rd<int32_t>(f, 14);
+    auto h = rd<int32_t>(c.f, 14);
     thrl::SdArgs a;
     memset(&a, 0, sizeof(a));
     thrl::SpArgs& sp = a.sp;
     sp.G = h[0]; sp.N = h[1]; sp.T = h[2]; sp.D = h[3];
     a.d = h[4]; a.L = h[5]; a.K = h[6]; a.dev_action = h[7]; a.use_policy = h[8]; a.row_begin = h[11]; a.row_count = h[12];
     const int nblk = h[13];
-    auto kind = rd<int32_t>(f, 8), nact = rd<int32_t>(f, 8);
-    auto eps = rd<double>(f, 8), gr = rd<double>(f, 2);
-    int ts = 1;
-    for (int i = sp.N - 1; i >= 0; i--) {
-        sp.kind[i] = kind[i]; sp.n_actions[i] = nact[i]; sp.tstride[i] = ts; ts *= nact[i]; sp.eps[i] = eps[i];
-    }
-    a.gamma = gr[0]; a.ret_tol = gr[1];
-    const size_t G = sp.G, N = sp.N, T = sp.T, D = sp.D, R = a.row_count;
-    auto eps_g = rd<double>(f, h[9] ? N * G : 0);
-    auto gam_g = rd<double>(f, h[10] ? N * G : 0);
-    std::vector<std::vector<float>> prob(N);
-    for (size_t i = 0; i < N; i++) prob[i] = rd<float>(f, kind[i] ? G * D * nact[i] : 0);
-    auto dpol = rd<uint16_t>(f, G * N * D);
-    auto devpol = rd<uint16_t>(f, h[8] ? G * D : 0);
-    auto first = rd<int32_t>(f, D + 1), perm = rd<int32_t>(f, T);
-    auto reward = rd<double>(f, N * T), scaled = rd<double>(f, N * T), price = rd<double>(f, T);
-    auto weights = rd<double>(f, G * T);
-    auto w_brew = rd<double>(f, N * G), w_bact = rd<double>(f, N * G);
-    auto w_bprice = rd<double>(f, G), w_share = rd<double>(f, G), w_gain = rd<double>(f, G), w_gdev = rd<double>(f, G),
-         w_low = rd<double>(f, G), w_dist = rd<double>(f, G), w_mass = rd<double>(f, G);
-    auto w_lstep = rd<int32_t>(f, G), w_ret = rd<int32_t>(f, G);
-    auto w_rrows = rd<double>(f, R * N * G), w_arows = rd<double>(f, R * N * G), w_prows = rd<double>(f, R * G),
-         w_drows = rd<double>(f, R * G);
-    fclose(f);
-    // poisoned, not zeroed: the call writes every entry of every output
-    const double poison = -7.25;
-    std::vector<double> brew(N * G, poison), bact(N * G, poison), bprice(G, poison), share(G, poison), gain(G, poison),
-        gdev(G, poison), low(G, poison), dist(G, poison), mass(G, poison), rrows(R * N * G, poison), arows(R * N * G, poison),
-        prows(R * G, poison), drows(R * G, poison);
-    std::vector<int32_t> lstep(G, -7), ret(G, -7);
-    sp.eps_g = h[9] ? eps_g.data() : nullptr; a.sweep_gamma = h[10] ? gam_g.data() : nullptr; sp.dpolicy = dpol.data();
-    a.dev_policy = h[8] ? devpol.data() : nullptr;
-    for (size_t i = 0; i < N; i++) sp.prob[i] = kind[i] ? prob[i].data() : nullptr;
-    sp.grp_first = first.data(); sp.grp_perm = perm.data(); sp.reward = reward.data(); sp.scaled = scaled.data();
-    sp.price = price.data();
-    a.weights = weights.data();
-    a.base_reward = brew.data(); a.base_action = bact.data(); a.base_price = bprice.data(); a.dev_share = share.data();
-    a.gain = gain.data(); a.gain_dev = gdev.data(); a.low = low.data(); a.dist = dist.data(); a.mass = mass.data();
-    a.low_step = lstep.data(); a.ret_step = ret.data();
-    a.reward_rows = rrows.data(); a.action_rows = arows.data(); a.price_rows = prows.data(); a.dist_rows = drows.data();
+    c.agents(sp, a, 2, h[9], h[10]);
+    c.rows();
+    c.dpol = rd<uint16_t>(c.f, c.G * c.N * c.D);
+    c.devpol = rd<uint16_t>(c.f, h[8] ? c.G * c.D : 0);
+    c.tables();
+    c.expected();
+    c.bind(sp, a);
     const long long lds = thrl::sd_layout(a);
     printf("G=%d N=%d T=%d D=%d deviator=%d L=%d K=%d dev_action=%d policy=%d rows [%d, +%d) blocks=%d: %lld bytes of LDS\n", sp.G, sp.N,
            sp.T, sp.D, a.d, a.L, a.K, a.dev_action, a.use_policy, a.row_begin, a.row_count, nblk, lds);
@@ -80,11 +33,5 @@ int main(int argc, char** argv) {
         if (sp.N <= 2) thrl::sd_block<2>(a, mem, t, b, nblk);
         else thrl::sd_block<thrl::kSpMaxA>(a, mem, t, b, nblk);
     });
-    int bad = cmp("base_reward", brew, w_brew) + cmp("base_action", bact, w_bact) + cmp("base_price", bprice, w_bprice)
-        + cmp("dev_share", share, w_share) + cmp("gain", gain, w_gain) + cmp("gain_dev", gdev, w_gdev) + cmp("low", low, w_low)
-        + cmp("dist", dist, w_dist) + cmp("mass", mass, w_mass) + cmp("low_step", lstep, w_lstep) + cmp("ret_step", ret, w_ret)
-        + cmp("reward_rows", rrows, w_rrows) + cmp("action_rows", arows, w_arows) + cmp("price_rows", prows, w_prows)
-        + cmp("dist_rows", drows, w_drows);
-    printf(bad ? "DIFFERENT from the mirror\n" : "equal to the mirror bit for bit\n");
-    return bad ? 1 : 0;
+    return c.compare();
 }

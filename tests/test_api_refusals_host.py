@@ -4,7 +4,9 @@ tests/golden/api_refusals.json holds (entry point, case, return code, thrl_last_
 from the library before the analysis wrappers were split off into thrl_api_analysis.hip and their repeated checks
 became shared helpers.  The test replays the cases and compares; it never writes the file (that is
 `python tests/test_api_refusals_host.py --record`).  The bad-argument tables are the ones the *_host.py tests of the
-individual analyses already have.
+individual analyses already have.  The entries of thrl_sampled_response, thrl_sampled_response_noise, thrl_sampled_deviation
+and thrl_sampled_deviation_noise were added later, from the library before the deviation pair's checks became sd_check_args
+and sd_copy_common; the entries that were there came out of that recording byte for byte.
 
 The module also runs where a GPU is present, so no case may get as far as a launch even if its refusal were lost: every
 args struct leaves NULL a pointer that the entry point's last NULL check tests (LAST_NULL, asserted before every call),
@@ -30,8 +32,12 @@ import test_convergence_host as CV
 import test_crossplay_host as XP
 import test_deviation_host as DV
 import test_equilibrium_host as EQ
+import test_sampled_deviation_host as SD
+import test_sampled_deviation_noise_host as SDN
 import test_sampled_host as SC
 import test_sampled_noise_host as SN
+import test_sampled_response_host as SR
+import test_sampled_response_noise_host as SRN
 import test_stationary_host as ST
 import test_tuple_analysis_host as TA
 import test_tuple_attractors_host as TT
@@ -59,6 +65,10 @@ CONFIGS = {
     "gamma_one": _two(gamma=1.0),
     "gamma_nan": _two(gamma=float("nan")),
     "sp_big": _two(32, 32),           # thrl_sampled_chain's working set does not fit
+    "sr_big": _two(26, 32),           # the lightest shapes whose working sets the four newer calls on sampled play refuse
+    "srn_big": _two(35, 21),
+    "sd_big": _two(35, 32),
+    "sdn_big": _two(35, 28),
     "inj_wide": _two(129, 21),        # one action more than an injected int8 choice holds
     "inj_wide_second": _two(21, 129),
 }
@@ -99,6 +109,10 @@ LAST_NULL = {
     "thrl_price_probs": lambda a, q: _neural(a, ("nn_params", "prob")),
     "thrl_sampled_chain": lambda a, q: [a.start] if a.flags & 1 else [getattr(a, f) for f in SC.SC_REQUIRED[-7:]],
     "thrl_sampled_noise_chain": lambda a, q: [a.start] if a.flags & 1 else [getattr(a, f) for f in SN.SN_REQUIRED[-7:]],
+    "thrl_sampled_response": lambda a, q: [getattr(a, f) for f in (SR.SR_WEIGHTED if a.pi else SR.SR_REQUIRED[-5:])],
+    "thrl_sampled_response_noise": lambda a, q: [getattr(a, f) for f in (SRN.SRN_WEIGHTED if a.pi else SRN.SRN_OUTPUTS)],
+    "thrl_sampled_deviation": lambda a, q: [getattr(a, f) for f in SD.SD_OUTPUTS],
+    "thrl_sampled_deviation_noise": lambda a, q: [getattr(a, f) for f in SDN.SDN_OUTPUTS],
     "thrl_equilibrium": lambda a, q: [q] + [getattr(a, f) for f in ("state0", "mu", "lam", "iters", "n_diff_all", "n_diff_on",
                                                                      "loss_all", "loss_on", "loss_all_mean", "loss_on_mean", "v_on")],
     "thrl_attractors": lambda a, q: ([q] if not a.flags & 1 else [getattr(a, f) for f in AT.RESET] if a.n_starts > 0
@@ -307,6 +321,43 @@ def cases():
     add("thrl_sampled_noise_chain", SN.sn_args, dict(g, nprob=[None, None]))
     add("thrl_sampled_noise_chain", SN.sn_args, dict(flags=1))
     nulls("thrl_sampled_noise_chain", SN.sn_args, g)
+
+    # ---- thrl_sampled_response, thrl_sampled_response_noise, thrl_sampled_deviation, thrl_sampled_deviation_noise: the
+    # tables of their own host tests, the cases those tests accept up to a missing pointer, and the working set's edge
+    def sampled(entry, build, g, bad, fine, required, rows, big, ws):
+        for kw in bad + fine:
+            add(entry, build, dict(g, **kw), cfg="forty" if kw.get("n_tuples") == 21 * 40 else "base")
+        tuple_counts(entry, build, g, dict(n_prices=1))
+        tuple_kinds(entry, build, g, dict(n_tuples=21 * 40, n_prices=21))
+        shape = dict(n_tuples=ws["T"], n_prices=ws["D"], **({"n_nodes": ws["Jn"]} if "Jn" in ws else {}))
+        add(entry, build, dict(g, **shape), cfg=big)
+        for f in required:
+            add(entry, build, dict(g, **{f: None}))
+        for r in rows:
+            add(entry, build, dict(g, **{r: [None, None]}))
+        nulls(entry, build, g)
+
+    g = dict(loss_all=None)
+    fine = [dict(agents=1, gamma=[0.5, 7.0]), dict(eps=[0.0, 7.0]), dict(gamma=[7.0], sweep_gamma=FAKE), dict(eps=[7.0], eps_g=FAKE)]
+    sampled("thrl_sampled_response", SR.sr_args, g, SR.SR_BAD, fine, SR.SR_REQUIRED, ("prob",), "sr_big",
+            SR.sr.working_set(SDN._shape(26, 32)))
+    sampled("thrl_sampled_response_noise", SRN.srn_args, g, SRN.SRN_BAD,
+            fine + [dict(noise_prob=7.0, noise_prob_g=FAKE), dict(n_nodes=4097)], SRN.SRN_INPUTS + SRN.SRN_OUTPUTS, ("prob", "nprob"),
+            "srn_big", SRN.sr.working_set_noise(SDN._shape(35, 21)))
+    for entry, build, weighted in (("thrl_sampled_response", SR.sr_args, SR.SR_WEIGHTED),
+                                   ("thrl_sampled_response_noise", SRN.srn_args, SRN.SRN_WEIGHTED)):
+        for f in weighted:
+            add(entry, build, dict({w: FAKE for w in weighted}, pi=FAKE, **{f: None}))
+    g = dict(mass=None)
+    fine = [dict(flags=1, dev_action=3), dict(gamma=0.0), dict(gamma=1.0), dict(eps=[0.0, 7.0]), dict(gamma=7.0, sweep_gamma=FAKE),
+            dict(eps=[7.0], eps_g=FAKE), dict(dev_action=20, deviator=0), dict(row_begin=29, row_count=3), dict(flags=1, dev_policy=FAKE),
+            dict(dev_len=32), dict(flags=1)]
+    sampled("thrl_sampled_deviation", SD.sd_args, g, SD.SD_BAD, fine, SD.SD_TABLES + SD.SD_OUTPUTS, ("prob",), "sd_big",
+            SD.sd.working_set(SDN._shape(35, 32)))
+    sampled("thrl_sampled_deviation_noise", SDN.sdn_args, g, SDN.SDN_BAD,
+            fine + [dict(noise_prob=0.0), dict(noise_prob=1.0), dict(noise_prob=7.0, noise_prob_g=FAKE), dict(n_nodes=2, band_w=1),
+                    dict(n_nodes=4097)], SDN.SDN_TABLES + SDN.SDN_OUTPUTS, ("prob", "nprob"), "sdn_big",
+            SDN.sd.working_set_noise(SDN._shape(35, 28)))
 
     # ---- thrl_equilibrium, thrl_attractors, thrl_stationary: their plan and their limits come before the other checks
     g = dict(v_on=None)

@@ -6,11 +6,11 @@ import ctypes
 import json
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import sampled_host_checks as HC
 import sampled_mirror as SPM
 import sampled_response_mirror as SRM
 from sampled_mirror import AG, ENV, QQ, QR, QRA, RF, RR, SHIP
@@ -113,10 +113,7 @@ def test_the_best_response_fed_back_loses_nothing():
 
 # ------------------------------------------------------------------------------------------------ the kernel on the host
 def build_check(path, sanitizer):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++20", "-O1", "-g", "-ffp-contract=off",
-                           "-DTHRL_SP_HOST_BUILD", "-fno-omit-frame-pointer"] + sanitizer
-                          + [os.path.join(ROOT, "tests", "sampled_response_check.cpp"), "-o", path, "-lpthread"])
+    HC.build_check("sampled_response_check.cpp", path, sanitizer)
 
 
 def run_cases(exe, d):
@@ -153,19 +150,10 @@ def test_the_kernels_source_on_the_host_equals_the_mirror_under_sanitizers(tmp_p
 # ------------------------------------------------------------------------------------------------ the entry point
 def test_args_struct_matches_the_header():
     from th_rl_amd import _lib
-    struct, cname = _lib.SampledResponseArgs, "thrl_sampled_response_args"
-    fields = [n for n, _ in struct._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "thrl_response.h"\nint main(){printf("%%zu %%d %%d %%d %%d %%d",'
-           'sizeof(%s),THRL_SR_MAX_LDS,THRL_STAT_MAX_ITERS,THRL_TP_MAX_TUPLES,THRL_EQ_MAX_ITERS,THRL_ABI_VERSION);\n' % cname)
-    for f in fields:
-        src += 'printf(" %%zu",offsetof(%s,%s));\n' % (cname, f)
-    src += 'return 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
-        got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    mine = [ctypes.sizeof(struct), _lib.SR_MAX_LDS, _lib.STAT_MAX_ITERS, 4096, SRM.EQ_MAX_ITERS, 4]
-    assert got == mine + [getattr(struct, f).offset for f in fields]
+    HC.assert_struct_matches_header(
+        _lib.SampledResponseArgs, "thrl_sampled_response_args", "thrl_response.h",
+        [("THRL_SR_MAX_LDS", _lib.SR_MAX_LDS), ("THRL_STAT_MAX_ITERS", _lib.STAT_MAX_ITERS), ("THRL_TP_MAX_TUPLES", 4096),
+         ("THRL_EQ_MAX_ITERS", SRM.EQ_MAX_ITERS), ("THRL_ABI_VERSION", 4)])
     assert sr.MAX_LDS == _lib.SR_MAX_LDS == 160 * 1024 and _lib.ABI_VERSION == 4
 
 

@@ -819,7 +819,8 @@ int thrl_price_probs(const thrl_cfg* c, const thrl_price_probs_args* x, void* st
 
 }  // extern "C"
 
-// ---- what the four calls on sampled play share; X is the call's public argument struct
+// ---- what the six calls on sampled play share (the two chains, the two response calls, the two deviation tests); X is the
+// call's public argument struct
 namespace {
 
 // the head of SpArgs: the counts, the tuple strides and the agents' kinds, epsilons and rows at the distinct prices
@@ -871,6 +872,58 @@ void sr_copy_common(A& a, const X* x) {
     a.iters = x->iters; a.sweeps = x->sweeps; a.loss_all = x->loss_all;
     a.loss_w = x->loss_w; a.gain_w = x->gain_w; a.v_w = x->v_w; a.br_prob_w = x->br_prob_w;
     a.br_policy = x->br_policy; a.v_opt = x->v_opt; a.v_pi = x->v_pi;
+}
+
+// the host-visible checks of both deviation tests behind their games, flags and reserved words (whose refusals an entry
+// point words itself): thrl_sampled_chain's in its order with the deviation and its rows as thrl_tuple_deviation_noise
+// checks them; after_prices() is the place of the noise call's check of its nodes and band
+template <typename X, typename M>
+int sd_check_args(const thrl_cfg* c, const X* x, bool use_policy, M after_prices) {
+    int rc;
+    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
+    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
+    if ((rc = after_prices()) != THRL_OK) return rc;
+    if ((rc = check_deviator(c, x->deviator, x->dev_len, x->n_steps)) != THRL_OK) return rc;
+    if (use_policy) {                                    // the strategy is dev_policy: no action of the deviator is one
+        thrl_cfg none = *c;
+        none.n_actions[x->deviator] = 0;
+        if ((rc = check_dev_action(&none, x->deviator, x->dev_action)) != THRL_OK) return rc;
+    } else if ((rc = check_dev_action(c, x->deviator, x->dev_action)) != THRL_OK) {
+        return rc;
+    }
+    if ((rc = check_rows(x->row_begin, x->row_count, x->n_steps)) != THRL_OK) return rc;
+    if ((rc = check_tol(x->ret_tol, "ret_tol")) != THRL_OK) return rc;
+    if (!x->sweep_gamma) {                               // gamma in [0, 1]: both ends through the check of a tolerance
+        if ((rc = check_tol(x->gamma, "gamma")) != THRL_OK) return rc;
+        if ((rc = check_tol(1.0 - x->gamma, "1 - gamma")) != THRL_OK) return rc;
+    }
+    if (!x->eps_g && (rc = check_eps(c->n_agents, x->kind, x->eps)) != THRL_OK) return rc;
+    return THRL_OK;
+}
+
+// the last NULL checks of both deviation tests (x_0, dev_policy under the call's flag, refused as missing(policy_names), and
+// the eleven outputs), then what both hand to their kernels under one name: the noise-free tables into sa, the deviation, its
+// rows and the outputs into a
+template <typename X>
+int sd_copy_common(thrl::SdArgs& a, SpArgs& sa, const X* x, bool use_policy, const char* policy_names) {
+    if (!x->weights) return missing("weights");
+    if (use_policy && !x->dev_policy) return missing(policy_names);
+    if (!x->base_reward || !x->base_action || !x->base_price || !x->dev_share || !x->gain || !x->gain_dev || !x->low
+        || !x->low_step || !x->ret_step || !x->dist || !x->mass)
+        return missing("base_reward / base_action / base_price / dev_share / gain / gain_dev / low / low_step / ret_step / "
+                       "dist / mass");
+    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm;
+    sa.reward = x->reward; sa.scaled = x->scaled; sa.price = x->price;
+    a.d = x->deviator; a.L = x->dev_len; a.K = x->n_steps; a.dev_action = x->dev_action; a.use_policy = use_policy;
+    a.row_begin = x->row_begin; a.row_count = x->row_count;
+    a.gamma = x->gamma; a.ret_tol = x->ret_tol;
+    a.sweep_gamma = x->sweep_gamma; a.dev_policy = x->dev_policy; a.weights = x->weights;
+    a.base_reward = x->base_reward; a.base_action = x->base_action; a.base_price = x->base_price;
+    a.dev_share = x->dev_share; a.gain = x->gain; a.gain_dev = x->gain_dev; a.low = x->low; a.low_step = x->low_step;
+    a.ret_step = x->ret_step; a.dist = x->dist; a.mass = x->mass;
+    a.reward_rows = x->reward_rows; a.action_rows = x->action_rows; a.price_rows = x->price_rows; a.dist_rows = x->dist_rows;
+    return THRL_OK;
 }
 
 }  // namespace
@@ -1069,25 +1122,8 @@ int thrl_sampled_deviation(const thrl_cfg* c, const thrl_sampled_deviation_args*
     if (x->flags & ~THRL_SD_POLICY) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
     for (int k = 0; k < 2; k++)
         if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
-    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
-    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
-    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
-    if ((rc = check_deviator(c, x->deviator, x->dev_len, x->n_steps)) != THRL_OK) return rc;
     const bool use_policy = (x->flags & THRL_SD_POLICY) != 0;
-    if (use_policy) {                                    // the strategy is dev_policy: no action of the deviator is one
-        thrl_cfg none = *c;
-        none.n_actions[x->deviator] = 0;
-        if ((rc = check_dev_action(&none, x->deviator, x->dev_action)) != THRL_OK) return rc;
-    } else if ((rc = check_dev_action(c, x->deviator, x->dev_action)) != THRL_OK) {
-        return rc;
-    }
-    if ((rc = check_rows(x->row_begin, x->row_count, x->n_steps)) != THRL_OK) return rc;
-    if ((rc = check_tol(x->ret_tol, "ret_tol")) != THRL_OK) return rc;
-    if (!x->sweep_gamma) {                               // gamma in [0, 1]: both ends through the check of a tolerance
-        if ((rc = check_tol(x->gamma, "gamma")) != THRL_OK) return rc;
-        if ((rc = check_tol(1.0 - x->gamma, "1 - gamma")) != THRL_OK) return rc;
-    }
-    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    if ((rc = sd_check_args(c, x, use_policy, [] { return (int)THRL_OK; })) != THRL_OK) return rc;
     thrl::SdArgs a;
     memset(&a, 0, sizeof(a));
     SpArgs& sa = a.sp;
@@ -1099,22 +1135,7 @@ int thrl_sampled_deviation(const thrl_cfg* c, const thrl_sampled_deviation_args*
         if (x->kind[i] != 0 && !x->prob[i]) return fail(THRL_ERR_NULL, "prob[%d] is NULL", i);
     if (!x->dpolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->scaled || !x->price)
         return missing("dpolicy / grp_first / grp_perm / reward / scaled / price");
-    if (!x->weights) return missing("weights");
-    if (use_policy && !x->dev_policy) return missing("with THRL_SD_POLICY, dev_policy");
-    if (!x->base_reward || !x->base_action || !x->base_price || !x->dev_share || !x->gain || !x->gain_dev || !x->low
-        || !x->low_step || !x->ret_step || !x->dist || !x->mass)
-        return missing("base_reward / base_action / base_price / dev_share / gain / gain_dev / low / low_step / ret_step / "
-                       "dist / mass");
-    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm;
-    sa.reward = x->reward; sa.scaled = x->scaled; sa.price = x->price;
-    a.d = x->deviator; a.L = x->dev_len; a.K = x->n_steps; a.dev_action = x->dev_action; a.use_policy = use_policy;
-    a.row_begin = x->row_begin; a.row_count = x->row_count;
-    a.gamma = x->gamma; a.ret_tol = x->ret_tol;
-    a.sweep_gamma = x->sweep_gamma; a.dev_policy = x->dev_policy; a.weights = x->weights;
-    a.base_reward = x->base_reward; a.base_action = x->base_action; a.base_price = x->base_price;
-    a.dev_share = x->dev_share; a.gain = x->gain; a.gain_dev = x->gain_dev; a.low = x->low; a.low_step = x->low_step;
-    a.ret_step = x->ret_step; a.dist = x->dist; a.mass = x->mass;
-    a.reward_rows = x->reward_rows; a.action_rows = x->action_rows; a.price_rows = x->price_rows; a.dist_rows = x->dist_rows;
+    if ((rc = sd_copy_common(a, sa, x, use_policy, "with THRL_SD_POLICY, dev_policy")) != THRL_OK) return rc;
     int grid = 0;
     rc = sp_plan_grid(sa, kSdMaxBlocksPerCu, &grid, [&](int) { return lds_refusal("thrl_sampled_deviation", lds, N, x->n_prices); });
     if (rc) return rc;
@@ -1134,26 +1155,8 @@ int thrl_sampled_deviation_noise(const thrl_cfg* c, const thrl_sampled_deviation
     if (x->flags & ~THRL_SDN_POLICY) return fail(THRL_ERR_BAD_CONFIG, "unknown flags 0x%x", x->flags);
     for (int k = 0; k < 2; k++)
         if (x->reserved[k] != 0) return fail(THRL_ERR_BAD_CONFIG, "reserved=%d must be 0", x->reserved[k]);
-    if ((rc = tuple_kinds_check(c, x->kind)) != THRL_OK) return rc;
-    if ((rc = tuple_count_check(c, x->n_tuples)) != THRL_OK) return rc;
-    if ((rc = check_prices(x->n_prices, x->n_tuples)) != THRL_OK) return rc;
-    if ((rc = check_nodes_band(x->n_nodes, x->band_w)) != THRL_OK) return rc;
-    if ((rc = check_deviator(c, x->deviator, x->dev_len, x->n_steps)) != THRL_OK) return rc;
     const bool use_policy = (x->flags & THRL_SDN_POLICY) != 0;
-    if (use_policy) {                                    // the strategy is dev_policy: no action of the deviator is one
-        thrl_cfg none = *c;
-        none.n_actions[x->deviator] = 0;
-        if ((rc = check_dev_action(&none, x->deviator, x->dev_action)) != THRL_OK) return rc;
-    } else if ((rc = check_dev_action(c, x->deviator, x->dev_action)) != THRL_OK) {
-        return rc;
-    }
-    if ((rc = check_rows(x->row_begin, x->row_count, x->n_steps)) != THRL_OK) return rc;
-    if ((rc = check_tol(x->ret_tol, "ret_tol")) != THRL_OK) return rc;
-    if (!x->sweep_gamma) {                               // gamma in [0, 1]: both ends through the check of a tolerance
-        if ((rc = check_tol(x->gamma, "gamma")) != THRL_OK) return rc;
-        if ((rc = check_tol(1.0 - x->gamma, "1 - gamma")) != THRL_OK) return rc;
-    }
-    if (!x->eps_g && (rc = check_eps(N, x->kind, x->eps)) != THRL_OK) return rc;
+    if ((rc = sd_check_args(c, x, use_policy, [&] { return check_nodes_band(x->n_nodes, x->band_w); })) != THRL_OK) return rc;
     if ((rc = check_noise_prob_closed(x->noise_prob_g, x->noise_prob)) != THRL_OK) return rc;
     if ((rc = check_node_limit("thrl_sampled_deviation_noise", x->n_nodes)) != THRL_OK) return rc;
     thrl::SdnArgs a;
@@ -1172,24 +1175,9 @@ int thrl_sampled_deviation_noise(const thrl_cfg* c, const thrl_sampled_deviation
     if (!x->dpolicy || !x->npolicy || !x->grp_first || !x->grp_perm || !x->reward || !x->scaled || !x->price)
         return missing("dpolicy / npolicy / grp_first / grp_perm / reward / scaled / price");
     if (!x->band_lo || !x->band || !x->noise_price || !x->noise_reward) return missing("band_lo / band / noise_price / noise_reward");
-    if (!x->weights) return missing("weights");
-    if (use_policy && !x->dev_policy) return missing("with THRL_SDN_POLICY, dev_policy");
-    if (!x->base_reward || !x->base_action || !x->base_price || !x->dev_share || !x->gain || !x->gain_dev || !x->low
-        || !x->low_step || !x->ret_step || !x->dist || !x->mass)
-        return missing("base_reward / base_action / base_price / dev_share / gain / gain_dev / low / low_step / ret_step / "
-                       "dist / mass");
-    sa.eps_g = x->eps_g; sa.dpolicy = x->dpolicy; sa.grp_first = x->grp_first; sa.grp_perm = x->grp_perm;
-    sa.reward = x->reward; sa.scaled = x->scaled; sa.price = x->price;
+    if ((rc = sd_copy_common(sd, sa, x, use_policy, "with THRL_SDN_POLICY, dev_policy")) != THRL_OK) return rc;
     na.noise_prob_g = x->noise_prob_g; na.npolicy = x->npolicy; na.band_lo = x->band_lo; na.band = x->band;
     na.noise_price = x->noise_price; na.noise_reward = x->noise_reward;
-    sd.d = x->deviator; sd.L = x->dev_len; sd.K = x->n_steps; sd.dev_action = x->dev_action; sd.use_policy = use_policy;
-    sd.row_begin = x->row_begin; sd.row_count = x->row_count;
-    sd.gamma = x->gamma; sd.ret_tol = x->ret_tol;
-    sd.sweep_gamma = x->sweep_gamma; sd.dev_policy = x->dev_policy; sd.weights = x->weights;
-    sd.base_reward = x->base_reward; sd.base_action = x->base_action; sd.base_price = x->base_price;
-    sd.dev_share = x->dev_share; sd.gain = x->gain; sd.gain_dev = x->gain_dev; sd.low = x->low; sd.low_step = x->low_step;
-    sd.ret_step = x->ret_step; sd.dist = x->dist; sd.mass = x->mass;
-    sd.reward_rows = x->reward_rows; sd.action_rows = x->action_rows; sd.price_rows = x->price_rows; sd.dist_rows = x->dist_rows;
     int grid = 0;
     rc = sp_plan_grid(sa, kSdnMaxBlocksPerCu, &grid,
                       [&](int) { return lds_refusal("thrl_sampled_deviation_noise", lds, N, x->n_prices + x->n_nodes); });

@@ -19,7 +19,10 @@
 //   actions, 2 N + 1 the price -- and lane 2 N + 2 the distance from its own staging row.  The lane of a sum keeps what is
 //   derived from it in registers over the periods, as k_tdn_chain does: lane 1 + d the gain and the low, lane 2 N + 2 the
 //   distance and ret_step.  x_0 is re-read from global memory (coalesced) for the distance.  No atomic is involved.
-//   The row sum, the unsolved outputs and the period's sums sit in thrl_sampled_deviation_dev.h, shared with k_sdn_chain.
+//   What this file keeps is the order of a game's passes and the step.  Everything else -- the staging of the grouping,
+//   the row sum, the unsolved outputs, ad_g and Z at the prices, dev_share's terms, a period's sums, the baseline's stores,
+//   the replaced rows and the lanes' bookkeeping over the periods -- sits in thrl_sampled_deviation_dev.h, one copy that
+//   k_sdn_chain calls too.
 //   Nothing in the body is wave-specific: with THRL_SP_HOST_BUILD the same source runs as 256 host threads with barriers.
 #include "thrl_response_dev.h"
 #include "thrl_sampled_deviation.h"
@@ -32,7 +35,7 @@ namespace {
 template <int MAXN>
 __device__ __forceinline__ void sd_block(const SdArgs& a, unsigned char* s_mem, int tid, int bid, int nblk) {
     const SpArgs& sp = a.sp;
-    const int N = sp.N, G = sp.G, T = sp.T, D = sp.D, K = a.K, L = a.L, dv = a.d;
+    const int G = sp.G, T = sp.T, D = sp.D, K = a.K, L = a.L, dv = a.d, dev_action = a.dev_action;
     double* ma = reinterpret_cast<double*>(s_mem + sp.o_ma);
     double* mb = reinterpret_cast<double*>(s_mem + sp.o_mb);          // before the first step: reward_d, then dev_share's terms
     double* W = reinterpret_cast<double*>(s_mem + sp.o_w);
@@ -44,13 +47,9 @@ __device__ __forceinline__ void sd_block(const SdArgs& a, unsigned char* s_mem, 
     double* prod = reinterpret_cast<double*>(s_mem + sp.o_prod);      // [2N + 2][64] the chunk's terms per sum
     double* drow = reinterpret_cast<double*>(s_mem + a.o_dist);       // [64] the chunk's |x - x_0|
     SpCst* cst = reinterpret_cast<SpCst*>(s_mem + sp.o_cst);
-    const int n_out = 2 * N + 2;                                      // mass, N rewards, N actions, price; lane n_out: distance
     const int rb = a.row_begin, rc = a.row_count;
-    const int A = sp.n_actions[dv];
 
-    // ---- the grouping of the tuples by price: per config, staged once; no entry leads out of bounds
-    for (int d = tid; d <= D; d += kSpBlock) first[d] = (uint16_t)min(max(sp.grp_first[d], 0), T);
-    for (int t = tid; t < T; t += kSpBlock) perm[t] = (uint16_t)min(max(sp.grp_perm[t], 0), T - 1);
+    sd_stage_grouping(sp, first, perm, tid);             // per config, staged once
 
     for (int64_t g = bid; g < G; g += nblk) {
         if (!sp_eps_ok(sp, g)) {                         // block-uniform: this game is not solved
@@ -70,70 +69,31 @@ __device__ __forceinline__ void sd_block(const SdArgs& a, unsigned char* s_mem, 
         sp_normaliser(sp, s_mem, Z, tid);
 
         // ---- per price: ad_g and the deviation step's Z
-        for (int d = tid; d < D; d += kSpBlock) {
-            double zm = 1.0, zd = 1.0;                   // Z_-d and Z with S_d = 1.0
-            bool have = false;
-            for (int j = 0; j < N; j++) {
-                const double Sj = j == dv ? 1.0 : sd_row_sum(sp, s_mem, j, d);
-                zd = j == 0 ? Sj : __dmul_rn(zd, Sj);
-                if (j == dv) continue;
-                zm = have ? __dmul_rn(zm, Sj) : Sj;
-                have = true;
-            }
-            int act;
-            if (a.use_policy) {
-                act = min((int)a.dev_policy[g * D + d], A - 1);
-            } else if (a.dev_action >= 0) {
-                act = a.dev_action;
-            } else {                                     // the one-period best response to the rivals' mixed policies
-                double bv;
-                act = first_max(A, [&](int k) THRL_SOLVE_INLINE { return sr_q<MAXN>(sp, s_mem, cst, mb, zm, dv, d, k); }, bv);
-            }
-            ad[d] = (uint16_t)act;
-            Zd[d] = zd;
-        }
+        const uint16_t* devpol = a.use_policy ? a.dev_policy + g * D : nullptr;       // the game's row
+        sd_price_strategy<MAXN>(sp, s_mem, cst, mb, ad, Zd, dv, dev_action, devpol, tid);
         __syncthreads();                                 // reward_d is read; ad_g of every price
 
-        // ---- dev_share's terms over the dead second iterate (D <= T): M_0(d) * (1 - P_d(ad_g(d)|d) / S_d(d))
-        for (int d = tid; d < D; d += kSpBlock) {
-            double M = 0.0;
-            const int e = first[d + 1];
-            for (int s = first[d]; s < e; s++) M = __dadd_rn(M, ma[perm[s]]);
-            const double own = __ddiv_rn(sr_prob(sp, s_mem, cst, dv, d, (int)ad[d]), sd_row_sum(sp, s_mem, dv, d));
-            mb[d] = __dmul_rn(M, __dsub_rn(1.0, own));
-        }
+        // ---- dev_share's terms over the dead second iterate (D <= T)
+        sd_share_terms(sp, s_mem, cst, ma, first, perm, ad, mb, dv, tid);
 
         // ---- the baseline: what x_0 earns, and the share of periods the deviation changes
         double acc = sd_sums(sp, ma, w0, prod, drow, tid);       // its first barrier also ends the pass above
         const double base = acc;                         // lane 1 + i: base_reward_i
-        if (tid >= 1 && tid <= N) a.base_reward[(int64_t)(tid - 1) * G + g] = acc;
-        else if (tid > N && tid <= 2 * N) a.base_action[(int64_t)(tid - 1 - N) * G + g] = acc;
-        else if (tid == 2 * N + 1) a.base_price[g] = acc;
+        sd_store_base(sp, a, acc, g, tid);
         if (tid == 64) {
             double s = 0.0;
             for (int d = 0; d < D; d++) s = __dadd_rn(s, mb[d]);
             a.dev_share[g] = s;
         }
 
-        // ---- the deviator's row while the deviation lasts: P_d(k|d) = 1.0 for k = ad_g(d), else 0.0 (every thread is
-        // past the barriers of the sums, so past its reads of the own row)
-        if (sp.kind[dv] == 0) {
-            uint16_t* rq = reinterpret_cast<uint16_t*>(s_mem + sp.o_row[dv]);
-            for (int d = tid; d < D; d += kSpBlock) rq[d] = ad[d];
-            if (tid == 0) { cst->hi[dv] = 1.0; cst->lo[dv] = 0.0; }
-        } else {
-            float* rf = reinterpret_cast<float*>(s_mem + sp.o_row[dv]);
-            for (int d = tid; d < D; d += kSpBlock) {
-                const int act = ad[d];
-                for (int k = 0; k < A; k++) rf[d * A + k] = k == act ? 1.0f : 0.0f;
-            }
-        }
+        // ---- the deviator's row while the deviation lasts (every thread is past the barriers of the sums, so past its
+        // reads of the own row)
+        sd_replace_rows(sp, s_mem, cst, ad, dv, tid);
         __syncthreads();                                 // the terms are read before the second iterate is written
 
         // ---- K periods: the step x_{tau+1} = step_tau(x_tau), then the sums of x_{tau+1}
         const double gam = a.sweep_gamma ? a.sweep_gamma[(int64_t)dv * G + g] : a.gamma;
-        double w = 1.0, gain = 0.0, gain_dev = 0.0, low = 0.0, Dist = 0.0;
-        int low_step = -1, ret = -1;
+        SdTrack trk;
         double* mo = ma;
         double* mn = mb;
         for (int tau = 0; tau < K; tau++) {
@@ -149,40 +109,9 @@ __device__ __forceinline__ void sd_block(const SdArgs& a, unsigned char* s_mem, 
             __syncthreads();
             double* tm = mo; mo = mn; mn = tm;
             acc = sd_sums(sp, mo, w0, prod, drow, tid);
-            Dist = __dmul_rn(0.5, acc);                  // the distance, on lane n_out
-            if (tid == 1 + dv) {
-                const double diff = __dsub_rn(acc, base);
-                const double term = __dmul_rn(w, diff);
-                gain = __dadd_rn(gain, term);
-                if (dev) {
-                    gain_dev = __dadd_rn(gain_dev, term);
-                } else if (tau == L || diff < low) {
-                    low = diff;
-                    low_step = tau;
-                }
-                w = __dmul_rn(w, gam);
-            }
-            if (tid == n_out && !dev && ret < 0 && Dist <= a.ret_tol) ret = tau;
-            const int r = tau - rb;
-            if (r >= 0 && r < rc) {
-                if (tid >= 1 && tid <= N) {
-                    if (a.reward_rows) a.reward_rows[((int64_t)r * N + (tid - 1)) * G + g] = acc;
-                } else if (tid > N && tid <= 2 * N) {
-                    if (a.action_rows) a.action_rows[((int64_t)r * N + (tid - 1 - N)) * G + g] = acc;
-                } else if (tid == 2 * N + 1) {
-                    if (a.price_rows) a.price_rows[(int64_t)r * G + g] = acc;
-                } else if (tid == n_out) {
-                    if (a.dist_rows) a.dist_rows[(int64_t)r * G + g] = Dist;
-                }
-            }
+            sd_period(sp, a, trk, tau, acc, base, gam, dv, L, rb, rc, g, tid);
         }
-        if (tid == 1 + dv) {
-            a.gain[g] = gain; a.gain_dev[g] = gain_dev; a.low[g] = low; a.low_step[g] = low_step;
-        } else if (tid == n_out) {
-            a.ret_step[g] = ret; a.dist[g] = Dist;
-        } else if (tid == 0) {
-            a.mass[g] = acc;
-        }
+        sd_finish(sp, a, trk, acc, dv, g, tid);
     }
 }
 

@@ -1,20 +1,36 @@
-// thrl_sampled_deviation_dev.h -- the deviation bookkeeping of the two deviation tests of sampled play, k_sd_chain
-// (thrl_sampled_deviation.hip) and k_sdn_chain (thrl_sampled_deviation_noise.hip).  Both take from here a row sum from
-// the staged rows, the outputs of an unsolved game and the ordered sums of a period's distribution (with the noisy
-// expectations for k_sdn_chain).  The rest -- the baseline's stores, the replacement of the deviator's staged rows and
-// what the lanes of the sums derive over the periods (SdTrack, sd_period, sd_finish) -- is k_sd_chain's text as
-// functions, and only k_sdn_chain calls them: k_sd_chain keeps those lines inline, because taking them from here moved
-// its register allocation (103 / 123 VGPRs for 105 / 124, and 68 bytes of scratch reserved in <8>), and its figures are
-// pinned.  The functions take the SpArgs they read beside the SdArgs, so that k_sdn_chain, whose SpArgs sits in its
-// SpnArgs, passes that one.  Everything sits in namespace thrl's anonymous namespace, once per including file; with
+// thrl_sampled_deviation_dev.h -- what the two deviation tests of sampled play, k_sd_chain (thrl_sampled_deviation.hip)
+// and k_sdn_chain (thrl_sampled_deviation_noise.hip), have in common, once: the staging of the grouping
+// (sd_stage_grouping), a row sum from the staged rows (sd_row_sum), the outputs of an unsolved game (sd_unsolved), the
+// deviator's strategy at the distinct prices with the deviation step's Z (sd_price_strategy; it takes the game's row of
+// dev_policy, D long there and D + Jn here), dev_share's terms at the prices (sd_share_terms), the ordered sums of a
+// distribution (sd_sums, with the noisy expectations for k_sdn_chain), the baseline's stores (sd_store_base), the
+// replacement of the deviator's staged rows (sd_replace_rows) and what the lanes of the sums derive over the periods
+// (SdTrack, sd_period, sd_finish).  Both kernels call every one of them; what stays with a kernel is its step and, in
+// k_sdn_chain, the nodes.  The functions take the SpArgs they read beside the SdArgs, so that k_sdn_chain, whose SpArgs
+// sits in its SpnArgs, passes that one.  What a function needs of SdArgs' first run of fields -- the deviator, dev_len,
+// dev_action -- and the row range come by value, read once at the top of the caller's block function, and the strategy
+// functions take the game's row of dev_policy (or NULL), not the struct: a function that reads a.d or a.dev_action itself
+// has the run loaded again where it is inlined, and the compiler keeps a stack slot for the tuple it spills whole (20
+// bytes of scratch reserved, never accessed: in k_sd_chain<2> and <8> with sd_price_strategy reading a.d, in
+// k_sdn_chain<8> with it reading a.dev_action).  As it stands no kernel has scratch, k_sd_chain has 103 / 121 VGPRs and
+// the parent's 4 waves per SIMD (profiles/deviation_shared_resource_usage.txt), and its rate is the parent's
+// (profiles/deviation_shared.md).  Everything sits in namespace thrl's anonymous namespace, once per including file; with
 // THRL_SP_HOST_BUILD the host harness supplies __device__, __syncthreads() and the rounded operations.
 #pragma once
+#include "thrl_response_dev.h"
 #include "thrl_sampled_deviation.h"
 #include "thrl_sampled_dev.h"
 
 namespace thrl {
 
 namespace {
+
+// the grouping of the tuples by price: per config, staged once; no entry leads out of bounds
+__device__ __forceinline__ void sd_stage_grouping(const SpArgs& sp, uint16_t* first, uint16_t* perm, int tid) {
+    const int T = sp.T, D = sp.D;
+    for (int d = tid; d <= D; d += kSpBlock) first[d] = (uint16_t)min(max(sp.grp_first[d], 0), T);
+    for (int t = tid; t < T; t += kSpBlock) perm[t] = (uint16_t)min(max(sp.grp_perm[t], 0), T - 1);
+}
 
 // S_j(d) from the staged rows
 __device__ __forceinline__ double sd_row_sum(const SpArgs& sp, const unsigned char* s_mem, int j, int d) {
@@ -44,6 +60,52 @@ __device__ __forceinline__ void sd_unsolved(const SpArgs& sp, const SdArgs& a, i
     for (int r = tid; r < rc; r += kSpBlock) {
         if (a.price_rows) a.price_rows[(int64_t)r * G + g] = 0.0;
         if (a.dist_rows) a.dist_rows[(int64_t)r * G + g] = 0.0;
+    }
+}
+
+// per price, a thread each: ad_g(d) into ad -- the entry of policy_row, the game's row of dev_policy (clamped) or NULL; else
+// dev_action where it is one; else the one-period best response to the rivals' mixed policies, the first maximum over k of
+// sr_q with U the deviator's rewards -- and the deviation step's Z(d), the product with S_d = 1.0, into Zd
+template <int MAXN>
+__device__ __forceinline__ void sd_price_strategy(const SpArgs& sp, const unsigned char* s_mem, const SpCst* cst, const double* U,
+                                                  uint16_t* ad, double* Zd, int dv, int dev_action, const uint16_t* policy_row,
+                                                  int tid) {
+    const int N = sp.N, D = sp.D, A = sp.n_actions[dv];
+    for (int d = tid; d < D; d += kSpBlock) {
+        double zm = 1.0, zd = 1.0;                       // Z_-d and Z with S_d = 1.0
+        bool have = false;
+        for (int j = 0; j < N; j++) {
+            const double Sj = j == dv ? 1.0 : sd_row_sum(sp, s_mem, j, d);
+            zd = j == 0 ? Sj : __dmul_rn(zd, Sj);
+            if (j == dv) continue;
+            zm = have ? __dmul_rn(zm, Sj) : Sj;
+            have = true;
+        }
+        int act;
+        if (policy_row) {
+            act = min((int)policy_row[d], A - 1);
+        } else if (dev_action >= 0) {
+            act = dev_action;
+        } else {
+            double bv;
+            act = first_max(A, [&](int k) THRL_SOLVE_INLINE { return sr_q<MAXN>(sp, s_mem, cst, U, zm, dv, d, k); }, bv);
+        }
+        ad[d] = (uint16_t)act;
+        Zd[d] = zd;
+    }
+}
+
+// dev_share's terms at the prices, M_0(d) * (1 - P_d(ad_g(d)|d) / S_d(d)) with M_0 the mass of m at price d, into out[d]
+__device__ __forceinline__ void sd_share_terms(const SpArgs& sp, const unsigned char* s_mem, const SpCst* cst, const double* m,
+                                               const uint16_t* first, const uint16_t* perm, const uint16_t* ad, double* out, int dv,
+                                               int tid) {
+    const int D = sp.D;
+    for (int d = tid; d < D; d += kSpBlock) {
+        double M = 0.0;
+        const int e = first[d + 1];
+        for (int s = first[d]; s < e; s++) M = __dadd_rn(M, m[perm[s]]);
+        const double own = __ddiv_rn(sr_prob(sp, s_mem, cst, dv, d, (int)ad[d]), sd_row_sum(sp, s_mem, dv, d));
+        out[d] = __dmul_rn(M, __dsub_rn(1.0, own));
     }
 }
 

@@ -14,8 +14,10 @@
 //   (sdn_node_setup): with every network's tile resident, one lane per node takes ad_g(D + j) -- for a best response the
 //   first maximum over k of sr_q_of with U = Rn_delta, staged in the second iterate, which is dead until the first step, as
 //   k_sd_chain stages reward_delta -- and parks dev_share's node term nu_0(j) * (1 - Pn_delta(ad|j) / Sn_delta(j)) over
-//   nu_0(j) in V.  The periods' sums, the bookkeeping on the lanes of the sums and the stores are k_sd_chain's
-//   (thrl_sampled_deviation_dev.h), the sums with the noisy expectations.  No atomic is involved.  Nothing in the body is
+//   nu_0(j) in V.  What this file keeps is the node setup, the order of a game's passes and the step; the staging of the
+//   grouping, ad_g and Z at the prices (dev_policy's rows S long), dev_share's terms at the prices, the periods' sums (with
+//   the noisy expectations), the bookkeeping on the lanes of the sums and the stores are the functions k_sd_chain calls
+//   (thrl_sampled_deviation_dev.h).  No atomic is involved.  Nothing in the body is
 //   wave-specific beyond spn_nu's THRL_SPN_WAVE_FIRST: with THRL_SP_HOST_BUILD the same source runs as 256 host threads
 //   with barriers.
 #include "thrl_response_dev.h"
@@ -28,13 +30,13 @@ namespace thrl {
 namespace {
 
 // Once per game, tile by tile in ascending j with every network's rows resident: ad_g(D + j) into adn[j], and dev_share's
-// node term over nu_0(j) in V[j].  U holds Rn_delta.  Ends on a barrier.
+// node term over nu_0(j) in V[j].  U holds Rn_delta; dv, dev_action and policy_row (the game's row of dev_policy from its
+// entry of node 0 on, or NULL) as sd_price_strategy takes them.  Ends on a barrier.
 template <int MAXN>
-__device__ __forceinline__ void sdn_node_setup(const SdnArgs& a, unsigned char* s_mem, const SpCst* cst, const double* U, double* V,
-                                               uint16_t* adn, int64_t g, int tid) {
-    const SpnArgs& na = a.n;
+__device__ __forceinline__ void sdn_node_setup(const SpnArgs& na, unsigned char* s_mem, const SpCst* cst, const double* U, double* V,
+                                               uint16_t* adn, int dv, int dev_action, const uint16_t* policy_row, int64_t g, int tid) {
     const SpArgs& sp = na.sp;
-    const int N = sp.N, D = sp.D, Jn = na.Jn, dv = a.sd.d, A = sp.n_actions[dv];
+    const int N = sp.N, Jn = na.Jn, A = sp.n_actions[dv];
     const int n_tiles = (Jn + kSpnTile - 1) / kSpnTile;
     SpnWord st[MAXN][kSpnChunks];
     spn_tile_load<MAXN>(na, g, 0, tid, st);
@@ -66,10 +68,10 @@ __device__ __forceinline__ void sdn_node_setup(const SdnArgs& a, unsigned char* 
                 have = true;
             }
             int act;
-            if (a.sd.use_policy) {
-                act = min((int)a.sd.dev_policy[g * (D + Jn) + D + j], A - 1);
-            } else if (a.sd.dev_action >= 0) {
-                act = a.sd.dev_action;
+            if (policy_row) {
+                act = min((int)policy_row[j], A - 1);
+            } else if (dev_action >= 0) {
+                act = dev_action;
             } else {                                             // the one-period best response at the node
                 double bv;
                 act = first_max(A, [&](int x) THRL_SOLVE_INLINE { return sr_q_of<MAXN>(sp, U, zm, dv, x, prob); }, bv);
@@ -87,7 +89,7 @@ __device__ __forceinline__ void sdn_block(const SdnArgs& a, unsigned char* s_mem
     const SpnArgs& na = a.n;
     const SpArgs& sp = na.sp;
     const SdArgs& sd = a.sd;
-    const int N = sp.N, G = sp.G, T = sp.T, D = sp.D, Jn = na.Jn, K = sd.K, L = sd.L, dv = sd.d;
+    const int N = sp.N, G = sp.G, T = sp.T, D = sp.D, Jn = na.Jn, K = sd.K, L = sd.L, dv = sd.d, dev_action = sd.dev_action;
     double* ma = reinterpret_cast<double*>(s_mem + sp.o_ma);
     double* mb = reinterpret_cast<double*>(s_mem + sp.o_mb);          // before the first step: Rn_delta, then dev_share's terms
     double* W = reinterpret_cast<double*>(s_mem + sp.o_w);
@@ -101,11 +103,8 @@ __device__ __forceinline__ void sdn_block(const SdnArgs& a, unsigned char* s_mem
     double* drow = reinterpret_cast<double*>(s_mem + sd.o_dist);      // [64] the chunk's |x - x_0|
     SpCst* cst = reinterpret_cast<SpCst*>(s_mem + sp.o_cst);
     const int rb = sd.row_begin, rc = sd.row_count;
-    const int A = sp.n_actions[dv];
 
-    // ---- the grouping of the tuples by price: per config, staged once; no entry leads out of bounds
-    for (int d = tid; d <= D; d += kSpBlock) first[d] = (uint16_t)min(max(sp.grp_first[d], 0), T);
-    for (int t = tid; t < T; t += kSpBlock) perm[t] = (uint16_t)min(max(sp.grp_perm[t], 0), T - 1);
+    sd_stage_grouping(sp, first, perm, tid);             // per config, staged once
 
     for (int64_t g = bid; g < G; g += nblk) {
         const double p = na.noise_prob_g ? na.noise_prob_g[g] : na.noise_prob;
@@ -134,39 +133,14 @@ __device__ __forceinline__ void sdn_block(const SdnArgs& a, unsigned char* s_mem
         spn_nu(na, ma, V, tid);                          // nu_0
 
         // ---- per price: ad_g and the deviation step's Z
-        for (int d = tid; d < D; d += kSpBlock) {
-            double zm = 1.0, zd = 1.0;                   // Z_-d and Z with S_d = 1.0
-            bool have = false;
-            for (int j = 0; j < N; j++) {
-                const double Sj = j == dv ? 1.0 : sd_row_sum(sp, s_mem, j, d);
-                zd = j == 0 ? Sj : __dmul_rn(zd, Sj);
-                if (j == dv) continue;
-                zm = have ? __dmul_rn(zm, Sj) : Sj;
-                have = true;
-            }
-            int act;
-            if (sd.use_policy) {
-                act = min((int)sd.dev_policy[g * (D + Jn) + d], A - 1);
-            } else if (sd.dev_action >= 0) {
-                act = sd.dev_action;
-            } else {                                     // the one-period best response to the rivals' mixed policies
-                double bv;
-                act = first_max(A, [&](int k) THRL_SOLVE_INLINE { return sr_q<MAXN>(sp, s_mem, cst, mb, zm, dv, d, k); }, bv);
-            }
-            ad[d] = (uint16_t)act;
-            Zd[d] = zd;
-        }
+        const uint16_t* devpol = sd.use_policy ? sd.dev_policy + g * (D + Jn) : nullptr;     // the game's row: prices, nodes
+        sd_price_strategy<MAXN>(sp, s_mem, cst, mb, ad, Zd, dv, dev_action, devpol, tid);
         __syncthreads();                                 // nu_0 is whole
-        sdn_node_setup<MAXN>(a, s_mem, cst, mb, V, ad + D, g, tid);     // ends on a barrier: Rn is read, ad_g is whole
+        // (ends on a barrier: Rn is read, ad_g is whole)
+        sdn_node_setup<MAXN>(na, s_mem, cst, mb, V, ad + D, dv, dev_action, devpol ? devpol + D : nullptr, g, tid);
 
-        // ---- dev_share's terms at the prices over the dead second iterate (D <= T): M_0(d) * (1 - P_d(ad_g(d)|d) / S_d(d))
-        for (int d = tid; d < D; d += kSpBlock) {
-            double M = 0.0;
-            const int e = first[d + 1];
-            for (int s = first[d]; s < e; s++) M = __dadd_rn(M, ma[perm[s]]);
-            const double own = __ddiv_rn(sr_prob(sp, s_mem, cst, dv, d, (int)ad[d]), sd_row_sum(sp, s_mem, dv, d));
-            mb[d] = __dmul_rn(M, __dsub_rn(1.0, own));
-        }
+        // ---- dev_share's terms at the prices over the dead second iterate (D <= T)
+        sd_share_terms(sp, s_mem, cst, ma, first, perm, ad, mb, dv, tid);
 
         // ---- the baseline: what x_0 earns, and the share of periods the deviation changes
         double acc = sd_sums<true>(sp, ma, w0, prod, drow, tid, q, p, na.noise_reward, na.noise_price);   // its first barrier also ends the pass above
