@@ -441,7 +441,11 @@ constexpr size_t kLutRegion = 16384;            // workspace bytes reserved for 
 
 // Workspace of the wave kernel, sized from the config and the current device:
 //   [0, kLutRegion)   payoff-LUT image (+ the launch's work counter in its last 64 bytes)
-//   partial           [total_waves][kWaveMaxEpisodes][4] fixed-point log sums
+//   partial           [total_waves][kWaveMaxEpisodes][4] fixed-point log sums of the launch, one i64 per (wave, episode,
+//                     quantity), written by the kernel's last two stores and read by k_wave_reduce.  Until then the
+//                     instantiations without per-game logs and training cycles use a wave's 128 words as the parking
+//                     area of its current game: slot [e][k] holds the undivided float64 total k of episode e, which the
+//                     game's epilogue finishes (thrl_wave_kernel.h) -- same size, same layout, nothing else reads it
 //   tlog              [total_waves][kWaveMaxEpisodes][NSEG][64] cell words of the transitions (visit counters)
 // total_waves = the persistent grid: resident blocks per CU x CUs, or fewer when G is small.
 struct WaveWs { int grid, total_waves; size_t partial_off, tlog_off, bytes; };

@@ -80,7 +80,8 @@ struct WaveArgs {
     int32_t* counter;
     double* state;
     const unsigned char* lut_ns;    // device: payoff LUT image (thrl_wave_lut.h), lut_bytes long
-    long long* partial;             // device [total_waves][kWaveMaxEpisodes][4] per-wave log sums, fixed point
+    long long* partial;             // device [total_waves][kWaveMaxEpisodes][4] per-wave log sums, fixed point (during the launch
+                                    // also the parking area of a game's pending float64 totals: thrl_wave_kernel.h)
     double log_scale[2];            // fixed-point scales of the (reward, action) log sums: powers of two, sized by the host
                                     // so that G games cannot overflow 2^62; integer sums are order independent
     double* game_reward_log;        // device [n_episodes][2][G] per-game rows of this launch, or null

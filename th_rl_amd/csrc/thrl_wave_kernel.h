@@ -34,6 +34,13 @@
 //     straight-line code: the play loop is unrolled over a segment's 16 groups of four steps and the replay
 //     loop over a block's 8 groups (step / lane numbers are immediates), with copies for full segments and
 //     full blocks that carry no bounds tests;
+//   * log sums: an episode ends with one transposing reduction (wave_sum4) of its four totals.  The variants that keep
+//     per-game rows (LOG) or play several episodes per training cycle (CYCLE) finish them there, per episode: divide by
+//     T, scale to fixed point, round, add into the lane of that episode.  All others (the headline among them) only park
+//     the four totals -- one 8-byte store by four lanes into the wave's `partial` region, which holds the launch's sums only
+//     after the kernel's last two stores -- and the game's epilogue reads the region back with the transition log and
+//     finishes all of the game's episodes lane-parallel in two passes (lane L: slot L into acc, slot 64 + L into acc_hi):
+//     the same operations on the same doubles, once per lane and game instead of once per episode on a whole wave;
 //   * GREEDY variants (launched once epsilon is small): groups of four steps in which nobody explores read
 //     their next rows from per-episode composed tables, and a segment that cycles through 1-4 transitions
 //     (a converged game) is replayed as a recurrence in registers (cyclic_segment).
@@ -142,6 +149,14 @@ __device__ __forceinline__ void store_where(unsigned long long mask, unsigned ad
     asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tds_write_b64 %2, %3\n\ts_mov_b64 exec, %0"
                  : "=&s"(save) : "s"(mask), "v"(addr), "v"(v) : "memory");
 }
+// 8-byte global store by the lanes of `mask` only, to base + off (base and mask wave-uniform, off the lane's 32-bit byte
+// offset), for code that is only reached with all 64 lanes active: EXEC is set by scalar moves, no compare, no save and
+// no restore.  hipcc does not count the store (its s_waitcnt bookkeeping only gets more conservative by one), and
+// nothing waits for it: the wave reads the word back through the same path, in order.
+__device__ __forceinline__ void store_lanes(unsigned long long mask, long long* base, unsigned off, double v) {
+    asm volatile("s_mov_b64 exec, %0\n\tglobal_store_dwordx2 %1, %2, %3\n\ts_mov_b64 exec, -1"
+                 :: "s"(mask), "v"(off), "v"(v), "s"(base) : "memory");
+}
 // LDS store by the lanes whose replay key (phase (d2): 4 * group + pass number of the lane's transition) equals
 // `want`, for code that is only reached with all 64 lanes active: the compare writes EXEC itself (v_cmpx; on gfx9 it
 // writes VCC too) and EXEC is set back to all ones, no save and no restore.  No lane may match: the store then does
@@ -203,6 +218,16 @@ __device__ __forceinline__ double half32_allmax(double v) {
 }
 __device__ __forceinline__ double max_of(double a, double b) { return fmax(a, b); }
 
+// DPP move of a double without an old value (bound_ctrl, full masks): each half is one v_mov_b32_dpp that reads the source
+// register itself, with no v_mov_b32 copy in front of it.  Only for controls under which every lane has a source lane
+// (row_ror here).
+template <int CTRL>
+__device__ __forceinline__ double dpp_src64(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true),
+                            __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true));
+}
+
 // Sum FOUR per-lane doubles over the 64 lanes in one pass ("transpose" reduction):
 // returns, in every lane L, the wave total of quantity (L & 3) where the quantities are
 // ordered (q0, q1, q2, q3).  7 double adds instead of 24, no LDS traffic.
@@ -218,8 +243,8 @@ __device__ __forceinline__ double wave_sum4(double q0, double q1, double q2, dou
     const double kk = b1 ? a1 : a0, ss = b1 ? a0 : a1;
     double v = kk + dpp_mov64<0x4E>(ss);                      // quad_perm [2,3,0,1]
     // now lane L holds quantity (L&3) summed over its quad; rotate-add within the 16-lane row
-    v = v + dpp_mov64<0x124>(v);                              // row_ror:4
-    v = v + dpp_mov64<0x128>(v);                              // row_ror:8
+    v = v + dpp_src64<0x124>(v);                              // row_ror:4
+    v = v + dpp_src64<0x128>(v);                              // row_ror:8
     // across the four rows: swap-add with v_permlane16_swap / v_permlane32_swap
     {
         unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
@@ -818,6 +843,10 @@ k_wave_episodes(const WaveArgs a) {
     // variants without the NOISE / GREEDY additions to the fixed-point flag: replay schedule from three hazard ballots and
     // scalar mask arithmetic (phase (d2))
     constexpr bool kMaskSched = !NOISE && !GREEDY;
+    // variants that need an episode's log sums only in the launch's means (no per-game rows, one part per episode): phase
+    // (f) parks the four undivided totals in the wave's `partial` region and the game's epilogue finishes all of the game's
+    // episodes lane-parallel (divide, scale, round, add) -- once per lane and game instead of once per episode
+    constexpr bool kParkLogs = !LOG && !CYCLE;
 
     const AgentParams& p0 = a.ag[0];
     const AgentParams& p1 = a.ag[1];
@@ -828,6 +857,23 @@ k_wave_episodes(const WaveArgs a) {
     long long acc = 0, acc_hi = 0;
     const double log_scale = (lane & 2) ? a.log_scale[1] : a.log_scale[0];
     const int wave_gid = blockIdx.x * a.waves_per_block + wib;
+    // kParkLogs: the wave's region partial[wave_gid][e][k] holds the current game's pending totals (slot 4 e + k, written by
+    // lane 4 (e & 3) + k) until the kernel's last two stores put the sums there.  Lane L finishes slot L into acc and slot 64 + L into
+    // acc_hi: the lane and the accumulator that log_into gives episode e = 16 pass + (L >> 2), quantity k = L & 3.
+    auto load_parked = [&](int pass) {          // (L2-served like the transition log's read-back: the wave reads what it stored itself)
+        return __hip_atomic_load(&a.partial[(size_t)wave_gid * 128 + 64 * pass + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto finish_parked = [&](long long p0w, long long p1w) {
+#pragma unroll
+        for (int pass = 0; pass < 2; pass++) {
+            if (pass == 1 && a.n_episodes <= 16) break;
+            double v = __longlong_as_double(pass ? p1w : p0w);
+            if ((lane & 3) < 2) v = __ddiv_rn(v, inv_T_den);
+            const long long vq = __double2ll_rn(__dmul_rn(v, log_scale));
+            // a slot this game did not write holds anything (an earlier launch's sums): the ADD is masked, so it contributes nothing
+            if (16 * pass + (lane >> 2) < a.n_episodes) { if (pass) acc_hi += vq; else acc += vq; }
+        }
+    };
 
     // Games are handed out dynamically (one atomic per game): waves on less crowded CUs simply take
     // more games, which measured 7-13 % faster than the static grid-stride assignment.
@@ -1450,7 +1496,13 @@ k_wave_episodes(const WaveArgs a) {
 
             // ---- (f) per-episode log sums of this game into the wave accumulator:
             //      lane L gets the wave total of quantity L&3 = (reward0, reward1, action0, action1)
-            if (epk == 1) log_into(e, lr0, lr1, la0, la1, true);
+            //      kParkLogs: four lanes park the undivided totals for the game's epilogue instead.  wave_sum4's total is the
+            //      same in all four rows but not in all lanes of a row (the rotate-adds associate differently by position), so
+            //      the values parked are those of lanes 4 (e & 3) + k: bit for bit what lane 4 (e & 15) + k holds in log_into.
+            if constexpr (kParkLogs) {
+                const double v = (kAblate & 64) ? lr0 + lr1 + la0 + la1 : wave_sum4(lr0, lr1, la0, la1, lane);
+                store_lanes(0xFull << (4 * (e & 3)), a.partial + ((size_t)wave_gid * kWaveMaxEpisodes + e) * 4, ((unsigned)lane & 3u) << 3, v);
+            } else if (epk == 1) log_into(e, lr0, lr1, la0, la1, true);
             // epsilon decays after every train_net call (agents.py:78)
             if (SWEEP) {
                 epsg0 = __dadd_rn(eend0, __dmul_rn(__dsub_rn(epsg0, eend0), estep0));
@@ -1484,7 +1536,15 @@ k_wave_episodes(const WaveArgs a) {
         //      (relaxed, agent scope): consecutive cells, so coalesced, and no load whose return the wave would
         //      have to wait for.  At most one add per cell, game and launch -- not one per transition
         //      (2e9 scattered atomics per launch were a 70 ms floor).
-        if (a.counter && !(kAblate & 32)) {
+        const bool counting = a.counter && !(kAblate & 32);
+        if constexpr (kParkLogs) {
+            // ---- log sums of this game's episodes (no visit counters: a read-back of its own)
+            if (!counting && a.n_episodes > 0) {
+                const long long p0w = load_parked(0), p1w = load_parked(1);
+                finish_parked(p0w, p1w);
+            }
+        }
+        if (counting) {
             const int cells = (W + 2) * A;                       // per agent
             // may_alias: the histogram overlays the tables (no type-based reordering)
             typedef unsigned __attribute__((may_alias)) hist_u32;
@@ -1496,6 +1556,9 @@ k_wave_episodes(const WaveArgs a) {
             // log read-back: 4 episodes' loads in flight at a time (sc1 = L2-served: the wave
             // reads what it stored itself)
             const int n_cycles = a.n_episodes / epk;
+            // kParkLogs: the game's parked log totals come back with the first batch (no round trip of their own)
+            long long p0w = 0, p1w = 0;
+            if constexpr (kParkLogs) { p0w = load_parked(0); p1w = load_parked(1); }
             for (int c0 = 0; c0 < n_cycles; c0 += 4) {
                 unsigned w[4][NSEG];
 #pragma unroll
@@ -1516,6 +1579,7 @@ k_wave_episodes(const WaveArgs a) {
                         }
                     }
             }
+            if constexpr (kParkLogs) finish_parked(p0w, p1w);
             __builtin_amdgcn_wave_barrier();
             // apply: window rows are contiguous in HBM, so cell k of the window is element
             // lo*A + k of the agent's table (no row/column split); spill rows separately
